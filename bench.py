@@ -1,7 +1,7 @@
 """
 Headline benchmark: cube node-expansions/s (12-child fan-out + goal test) on a 1 M-state batch.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A "step" is one pass of the hot path over one batch: ONE launch of the fan-out kernel (rk_expand12) on 1 000 000
@@ -21,9 +21,22 @@ Prints ONE JSON line (rank 0) with the driver's contract fields plus
   roofline      algorithmic bytes (272 B per parent) / measured kernel time vs the 8 TB/s HBM peak; `frac` is
                 the total-bytes fraction, `frac_read` the read-bytes fraction (20 B per parent: the north star says
                 "HBM-read roofline"); kernel time = HIP events around the K back-to-back launches of the timed region,
-                plus min / median / mean of a second pass with one event pair per launch
-  cpu_baseline  the CPU port of the reference's fan-out idiom (oracle/, NumPy, 1 core) timed on a bounded sample,
+                plus (--full) min / median / mean of a second pass with one event pair per launch
+  cpu_baseline  (--full) the CPU port of the reference's fan-out idiom (oracle/, NumPy, 1 core) timed on a bounded sample,
                 and the C/OpenMP restatement on all host cores
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs (--dump-outputs DIR) and prints the line.
+Everything else runs only with --full, behind the timed region: the 4-input-set and unpaced-ring passes, the per-launch event
+pairs, the on-device check of every child of the last launches (`verified_children`), the search legs (N = 1: configs[2] /
+configs[3]; N > 1: the collectives' proof, configs[4] and the partitioned MCTS) and the CPU baseline.
+
+--dump-outputs DIR writes what the last timed step computed, for rank 0, as .npy files (about 33 MB in all):
+  children.npy      (12 S, 20)  float32: the 12 children of S = 32 768 parents, a fixed sample (seed DUMP_SEED) of the 1 M, in the
+                                order of the sampled parents' indices, parent-major / action-minor as rk_expand12 writes them
+  solved.npy        (12 S,)     float32: their solved flags (0 / 1)
+  children_sums.npy (20,)       float64: every sticker position summed over ALL 12 M children of the step
+  solved_count.npy  (1,)        float64: the number of solved flags set over all 12 M children of the step
+The inputs are seeded: the same arguments give the same parents, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -41,8 +54,11 @@ def parse_args(argv=None):
 	ap.add_argument("--gpus", type=int, default=1)
 	ap.add_argument("--steps", type=int, default=300)
 	ap.add_argument("--warmup", type=int, default=30)
-	ap.add_argument("--no-cpu-baseline", action="store_true")
-	ap.add_argument("--no-search-legs", action="store_true", help="skip the search legs behind the timed region (N = 1: configs[2] / configs[3]; "
+	ap.add_argument("--full", action="store_true", help="also run everything behind the headline: the kernel passes of their own (4 input "
+	                "sets, unpaced ring, per-launch event pairs), the on-device check of the last launches, the search legs and the CPU baseline")
+	ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed (rank 0) as .npy files into DIR")
+	ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+	ap.add_argument("--no-search-legs", action="store_true", help="--full: skip the search legs behind the timed region (N = 1: configs[2] / configs[3]; "
 	                "N > 1: configs[4] sharded A* strong + weak and the partitioned MCTS)")
 	ap.add_argument("--search-games", type=int, default=3, help="N > 1: games per scaling mode of the sharded A* leg")
 	ap.add_argument("--search-budget", type=int, default=0, help="N > 1: state budget of the sharded A* leg at world 1 (default: configs[4]'s 2 M)")
@@ -309,6 +325,25 @@ def pmc_traffic(kernel):
 	                                                    "from the Infinity Cache -- so fetch = 2 x 20 B per parent where HBM serves 1 x 20 B; writes are exact"}
 
 
+DUMP_SAMPLE = 32_768                      # parents whose 12 children --dump-outputs writes: 31.5 MB of float32 children
+DUMP_SEED = 20
+
+
+def dump_outputs(out_dir: str, children: torch.Tensor, solved: torch.Tensor):
+	"""The last timed step's outputs as .npy files (the module docstring lists them): a fixed, seeded sample of the parents with
+	all 12 children and flags of each, plus sums over the whole step so that a difference outside the sample still shows."""
+	os.makedirs(out_dir, exist_ok=True)
+	pick = np.sort(np.random.RandomState(DUMP_SEED).choice(N_PARENTS, DUMP_SAMPLE, replace=False))
+	idx = torch.from_numpy(pick).to(children.device)
+	kids = children.view(N_PARENTS, 12, 20)[idx].reshape(-1, 20)
+	flags = solved.view(N_PARENTS, 12)[idx].reshape(-1)
+	sums = sum(c.to(torch.int64).sum(0) for c in children.split(1 << 20))
+	np.save(os.path.join(out_dir, "children.npy"), kids.cpu().numpy().astype(np.float32))
+	np.save(os.path.join(out_dir, "solved.npy"), flags.cpu().numpy().astype(np.float32))
+	np.save(os.path.join(out_dir, "children_sums.npy"), sums.cpu().numpy().astype(np.float64))
+	np.save(os.path.join(out_dir, "solved_count.npy"), np.array([int(solved.sum(dtype=torch.int64))], dtype=np.float64))
+
+
 def max_over_ranks(elapsed: float, dist, device) -> float:
 	"""The slowest rank's time: what divides the whole job's units (weak scaling, no data-path collective)."""
 	t = torch.tensor([elapsed], dtype=torch.float64, device=device)
@@ -406,59 +441,61 @@ def main():
 
 	elapsed_max = max_over_ranks(elapsed, dist, reduce_device)
 	kernel_ms = ev0.elapsed_time(ev1) / args.steps          # HIP events on the launch stream: back-to-back launches
+	if args.dump_outputs and rank == 0:
+		dump_outputs(args.dump_outputs, *outs[(counter[0] - 1) % N_OUT_SETS])      # before a --full pass writes the output sets again
 
-	def back_to_back(n_launches):
-		e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-		torch.cuda.synchronize()
-		e0.record()
-		for _ in range(n_launches):
-			step()
-		e1.record()
-		torch.cuda.synchronize()
-		return e0.elapsed_time(e1) / n_launches
+	kernel_ms_4in = kernel_ms_ring = per = verified_children = None
+	if args.full:
+		def back_to_back(n_launches):
+			e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+			torch.cuda.synchronize()
+			e0.record()
+			for _ in range(n_launches):
+				step()
+			e1.record()
+			torch.cuda.synchronize()
+			return e0.elapsed_time(e1) / n_launches
 
-	# for the record (outside the timed region): round 2's rotation -- 4 parent sets = 80 MB, which the Infinity Cache could hold
-	in_sets[0] = 4
-	back_to_back(8)
-	kernel_ms_4in = back_to_back(max(40, min(args.steps, 300)))
-	in_sets[0] = N_IN_SETS
-
-	# for the record (outside the timed region): the UNPACED ring form on this very box, same rotation -- a box on which the
-	# paced form's 2.10 ns/tile schedule does not hold shows up as a ratio near 1 instead of as an unexplained lower fraction
-	kernel_ms_ring = None
-	if PACED:
-		_ffi.check(_ffi.lib().rk_set_pacing(0))
+		# for the record (outside the timed region): round 2's rotation -- 4 parent sets = 80 MB, which the Infinity Cache could hold
+		in_sets[0] = 4
 		back_to_back(8)
-		kernel_ms_ring = back_to_back(max(40, min(args.steps, 300)))
-		_ffi.check(_ffi.lib().rk_set_pacing(-1))
+		kernel_ms_4in = back_to_back(max(40, min(args.steps, 300)))
+		in_sets[0] = N_IN_SETS
 
-	# per-launch distribution (outside the timed region): one event pair per launch, same rotation
-	per = []
-	evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(min(args.steps, 200))]
-	for e0, e1 in evs:
-		e0.record()
-		step()
-		e1.record()
-	torch.cuda.synchronize()
-	per = sorted(e0.elapsed_time(e1) for e0, e1 in evs)
+		# for the record (outside the timed region): the UNPACED ring form on this very box, same rotation -- a box on which the
+		# paced form's 2.10 ns/tile schedule does not hold shows up as a ratio near 1 instead of as an unexplained lower fraction
+		if PACED:
+			_ffi.check(_ffi.lib().rk_set_pacing(0))
+			back_to_back(8)
+			kernel_ms_ring = back_to_back(max(40, min(args.steps, 300)))
+			_ffi.check(_ffi.lib().rk_set_pacing(-1))
 
-	# The timed work, verified IN FULL (outside the timed region): for every output set, ALL 12 M children of the last launch
-	# into it are moved back by the inverse action and compared with the 1 M parents that launch read -- on the device, in
-	# slices of 1 M children (one rk_multi_rotate + one comparison each); the flags are checked against a goal test of the children.
-	undo_slice = torch.arange(12, dtype=torch.uint8, device="cuda").bitwise_xor(1).repeat(1 << 16)
-	verified_children = 0
-	for o, k in sorted(last_in.items()):
-		parents, (children, solved) = ins[k], outs[o]
-		for lo in range(0, N_PARENTS, 1 << 16):
-			hi = min(lo + (1 << 16), N_PARENTS)
-			back = cube.device.multi_rotate(children[12 * lo:12 * hi], undo_slice[:12 * (hi - lo)])
-			if not torch.equal(back.view(hi - lo, 12, 20), parents[lo:hi].view(hi - lo, 1, 20).expand(hi - lo, 12, 20)):
-				raise AssertionError(f"output set {o}: children of parents {lo}..{hi} are not the fan-out of parent set {k}")
-			del back
-		if not torch.equal(cube.device.multi_is_solved(children), solved):
-			raise AssertionError(f"output set {o}: solved flags differ from a goal test of the children")
-		verified_children += 12 * N_PARENTS
-	assert int(stats[0]) == 0 or int(stats[1]) < 12 * N_PARENTS
+		# per-launch distribution (outside the timed region): one event pair per launch, same rotation
+		evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(min(args.steps, 200))]
+		for e0, e1 in evs:
+			e0.record()
+			step()
+			e1.record()
+		torch.cuda.synchronize()
+		per = sorted(e0.elapsed_time(e1) for e0, e1 in evs)
+
+		# The timed work, verified IN FULL (outside the timed region): for every output set, ALL 12 M children of the last launch
+		# into it are moved back by the inverse action and compared with the 1 M parents that launch read -- on the device, in
+		# slices of 1 M children (one rk_multi_rotate + one comparison each); the flags are checked against a goal test of the children.
+		undo_slice = torch.arange(12, dtype=torch.uint8, device="cuda").bitwise_xor(1).repeat(1 << 16)
+		verified_children = 0
+		for o, k in sorted(last_in.items()):
+			parents, (children, solved) = ins[k], outs[o]
+			for lo in range(0, N_PARENTS, 1 << 16):
+				hi = min(lo + (1 << 16), N_PARENTS)
+				back = cube.device.multi_rotate(children[12 * lo:12 * hi], undo_slice[:12 * (hi - lo)])
+				if not torch.equal(back.view(hi - lo, 12, 20), parents[lo:hi].view(hi - lo, 1, 20).expand(hi - lo, 12, 20)):
+					raise AssertionError(f"output set {o}: children of parents {lo}..{hi} are not the fan-out of parent set {k}")
+				del back
+			if not torch.equal(cube.device.multi_is_solved(children), solved):
+				raise AssertionError(f"output set {o}: solved flags differ from a goal test of the children")
+			verified_children += 12 * N_PARENTS
+		assert int(stats[0]) == 0 or int(stats[1]) < 12 * N_PARENTS
 	import ctypes
 	tau_c, src_c, us_c = ctypes.c_uint(0), ctypes.c_int(0), (ctypes.c_float * 5)()
 	_ffi.check(_ffi.lib().rk_get_pacing(tau_c, src_c, us_c))                    # the store schedule rk_init settled on for this device
@@ -489,7 +526,6 @@ def main():
 			           "input_sets": N_IN_SETS, "output_sets": N_OUT_SETS,
 			           "parallelism": f"independent batches x{world}"},
 			"transitions_per_s": 12 * value,
-			"verified_children": verified_children,          # every child of the last launch into each output set, undone and compared on the device
 			"pace_tau_ps": int(tau_c.value), "pace_source": {0: "compiled default", 1: "calibrated on this device", 2: "environment"}.get(int(src_c.value), "?"),
 			"pace_calibration_us": {"ring": us_c[0], "2000": us_c[1], "2100": us_c[2], "2200": us_c[3], "2400": us_c[4]},
 			"roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -498,26 +534,30 @@ def main():
 			             "kernel": kernel, "kernel_form": f"paced: a read phase (parents -> Infinity Cache), then one 64-parent tile per wave stored on a {tau_c.value / 1000:.2f} ns/tile "
 			                                    "schedule (DESIGN 3 step 3; RK_PACE=0 runs the unpaced ring form)" if paced else "ring form (RK_PACE=0, or the calibration chose it)",
 			             "kernel_ms_back_to_back": kernel_ms,
-			             "per_launch_event_pairs_ms": {"min": per[0], "median": per[len(per) // 2], "mean": sum(per) / len(per)},
-			             "kernel_ms_4_input_sets": kernel_ms_4in, "frac_4_input_sets": BYTES_PER_PARENT * N_PARENTS / (kernel_ms_4in * 1e-3) / 1e9 / HBM_PEAK_GBS,
-			             "kernel_ms_ring_same_box": kernel_ms_ring,
-			             "frac_ring_same_box": (BYTES_PER_PARENT * N_PARENTS / (kernel_ms_ring * 1e-3) / 1e9 / HBM_PEAK_GBS) if kernel_ms_ring else None,
 			             "algorithmic_bytes_per_launch": BYTES_PER_PARENT * N_PARENTS,
 			             "algorithmic_read_bytes_per_launch": READ_BYTES_PER_PARENT * N_PARENTS,
 			             "cache_neutral": True},
 		}
+		if args.full:
+			line["verified_children"] = verified_children          # every child of the last launch into each output set, undone and compared on the device
+			line["roofline"].update({
+				"per_launch_event_pairs_ms": {"min": per[0], "median": per[len(per) // 2], "mean": sum(per) / len(per)},
+				"kernel_ms_4_input_sets": kernel_ms_4in, "frac_4_input_sets": BYTES_PER_PARENT * N_PARENTS / (kernel_ms_4in * 1e-3) / 1e9 / HBM_PEAK_GBS,
+				"kernel_ms_ring_same_box": kernel_ms_ring,
+				"frac_ring_same_box": (BYTES_PER_PARENT * N_PARENTS / (kernel_ms_ring * 1e-3) / 1e9 / HBM_PEAK_GBS) if kernel_ms_ring else None,
+			})
 		if kernel_ms_ring:
 			# flat copies: the driver's parser keeps flat extra keys
 			line["frac_ring_same_box"] = line["roofline"]["frac_ring_same_box"]
 			line["paced_over_ring_same_box"] = kernel_ms_ring / kernel_ms
-		if world == 1 and not force_multi and not args.no_search_legs:
+		if args.full and world == 1 and not force_multi and not args.no_search_legs:
 			del ins, outs                                     # 1.6 GB back to the allocator before the pools of the search legs
 			torch.cuda.empty_cache()
 			try:
 				line.update(search_legs())
 			except Exception as e:                            # the headline line must not be lost to a leg: say what failed and go on
 				line["search_legs_error"] = f"{type(e).__name__}: {e}"[:400]
-		if world == 1 and not args.no_cpu_baseline:
+		if args.full and world == 1 and not args.no_cpu_baseline:
 			try:
 				line["cpu_baseline"] = cpu_baseline()
 			except Exception as e:
@@ -529,7 +569,7 @@ def main():
 	# headline's line, under a watchdog: should a leg hang (a collective that never completes on hardware the build never saw), every
 	# rank leaves after RK_BENCH_LEGS_TIMEOUT seconds and rank 0 still prints the line with what was finished -- the fan-out number of
 	# the scaling run is never lost to a leg.
-	if world > 1 or force_multi:
+	if args.full and (world > 1 or force_multi):
 		import threading
 		from benchmarks import multi_gpu
 		multi, finished = {}, threading.Event()

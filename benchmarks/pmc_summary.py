@@ -74,7 +74,7 @@ def main():
 	ap.add_argument("--write")
 	ap.add_argument("--kernel", default="k_expand12")
 	ap.add_argument("--commit", default="")
-	ap.add_argument("--command", default="python3 bench.py --steps 300 --warmup 30 --no-cpu-baseline")
+	ap.add_argument("--command", default="python3 bench.py --full --steps 300 --warmup 30 --no-cpu-baseline")
 	ap.add_argument("--algorithmic", type=float, default=272e6)
 	ap.add_argument("--out-pmc")
 	ap.add_argument("--out-stats")

@@ -11,12 +11,12 @@ timeout -k 10 900 python -m pytest tests -m gpu -x -q --durations=6 > $O/pytest_
 grep -q "exit 0" $O/pytest_gpu.log || exit 1
 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; tail -1 $O/smoke.log
 # headline: bench, the same command under rocprofv3 (stats), and the two PMC passes (never combined)
-python bench.py > $O/bench.log 2>&1; tail -1 $O/bench.log | cut -c1-300
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_stats -- python3 bench.py --steps 300 --warmup 30 --no-cpu-baseline > $O/bench_prof.log 2>&1
-rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_f -- python3 bench.py --steps 40 --warmup 8 --no-cpu-baseline > $O/pmc_f.log 2>&1
-rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pmc_w -- python3 bench.py --steps 40 --warmup 8 --no-cpu-baseline > $O/pmc_w.log 2>&1
+python bench.py --full > $O/bench.log 2>&1; tail -1 $O/bench.log | cut -c1-300
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_stats -- python3 bench.py --full --steps 300 --warmup 30 --no-cpu-baseline > $O/bench_prof.log 2>&1
+rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_f -- python3 bench.py --full --steps 40 --warmup 8 --no-cpu-baseline > $O/pmc_f.log 2>&1
+rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pmc_w -- python3 bench.py --full --steps 40 --warmup 8 --no-cpu-baseline > $O/pmc_w.log 2>&1
 # the N > 1 contract of bench.py, rehearsed with two ranks sharing the GPU (host-staged gloo collectives)
-RK_BENCH_BACKEND=gloo timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29541 bench.py --gpus 2 --steps 50 --warmup 5 > $O/bench_2ranks_gloo.log 2>&1; tail -1 $O/bench_2ranks_gloo.log | cut -c1-300
+RK_BENCH_BACKEND=gloo timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29541 bench.py --full --gpus 2 --steps 50 --warmup 5 > $O/bench_2ranks_gloo.log 2>&1; tail -1 $O/bench_2ranks_gloo.log | cut -c1-300
 # kernels
 python benchmarks/kernels.py 2>/dev/null | grep '^{' > $O/kernels.json
 python benchmarks/kernels686.py 2>/dev/null | grep '^{' > $O/kernels686.json

@@ -16,12 +16,12 @@ tests)
 	step 200 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; tail -1 $O/smoke.log
 	;;
 bench)
-	step 400 python bench.py > $O/bench.log 2>&1; tail -1 $O/bench.log | cut -c1-600
-	step 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_stats -- python3 bench.py --steps 300 --warmup 30 --no-cpu-baseline > $O/bench_prof.log 2>&1
-	step 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_f -- python3 bench.py --steps 64 --warmup 8 --no-cpu-baseline --no-search-legs > $O/pmc_f.log 2>&1
-	step 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pmc_w -- python3 bench.py --steps 64 --warmup 8 --no-cpu-baseline --no-search-legs > $O/pmc_w.log 2>&1
+	step 400 python bench.py --full > $O/bench.log 2>&1; tail -1 $O/bench.log | cut -c1-600
+	step 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_stats -- python3 bench.py --full --steps 300 --warmup 30 --no-cpu-baseline > $O/bench_prof.log 2>&1
+	step 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_f -- python3 bench.py --full --steps 64 --warmup 8 --no-cpu-baseline --no-search-legs > $O/pmc_f.log 2>&1
+	step 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pmc_w -- python3 bench.py --full --steps 64 --warmup 8 --no-cpu-baseline --no-search-legs > $O/pmc_w.log 2>&1
 	python benchmarks/pmc_summary.py --stats $O/prof_stats --fetch $O/pmc_f --write $O/pmc_w --kernel k_expand12p --commit "${RK_COMMIT:-unknown}" \
-		--command "python3 bench.py --steps 64 --warmup 8 --no-cpu-baseline --no-search-legs" --out-pmc $O/expand12_pmc.json --out-stats $O/expand12_kernel_stats.csv > $O/pmc_summary.log 2>&1; cut -c1-400 $O/pmc_summary.log
+		--command "python3 bench.py --full --steps 64 --warmup 8 --no-cpu-baseline --no-search-legs" --out-pmc $O/expand12_pmc.json --out-stats $O/expand12_kernel_stats.csv > $O/pmc_summary.log 2>&1; cut -c1-400 $O/pmc_summary.log
 	python benchmarks/search_legs_summary.py --stats $O/prof_stats --bench-log $O/bench_prof.log --out $O/search_legs.json --out-stats $O/search_legs_kernel_stats.csv > $O/search_legs.log 2>&1; cut -c1-600 $O/search_legs.log
 	find $O -name "*kernel_trace.csv" -size +40M -delete
 	step 200 python benchmarks/adi_cube.py > $O/adi_cube.json 2> $O/adi_cube.err; cat $O/adi_cube.json
@@ -35,7 +35,7 @@ sharded)
 	RK_SHARD_GRAPH=1 step 300 python benchmarks/sharded.py --net fc_small_bf16 --games 3 --max-states 2000000 2> $O/w1_graph.err | grep '^{' > $O/w1_graph.json; cut -c1-900 $O/w1_graph.json
 	RK_SHARD_GRAPH=1 step 300 python benchmarks/sharded.py --net stub --games 3 --max-states 2000000 2> $O/w1_graph_stub.err | grep '^{' > $O/w1_graph_stub.json; cut -c1-600 $O/w1_graph_stub.json
 	RK_SHARD_GRAPH=0 step 300 python benchmarks/sharded.py --net stub --games 3 --max-states 2000000 2> $O/w1_eager_stub.err | grep '^{' > $O/w1_eager_stub.json; cut -c1-600 $O/w1_eager_stub.json
-	RK_BENCH_BACKEND=gloo step 500 python bench.py --gpus 2 --steps 50 --warmup 5 > $O/bench_2ranks_gloo.log 2>&1; tail -1 $O/bench_2ranks_gloo.log | cut -c1-3000
+	RK_BENCH_BACKEND=gloo step 500 python bench.py --full --gpus 2 --steps 50 --warmup 5 > $O/bench_2ranks_gloo.log 2>&1; tail -1 $O/bench_2ranks_gloo.log | cut -c1-3000
 	step 400 python -m pytest tests/test_sharded_gpu.py -q -m gpu -s -k "captured_iteration_with_device_collectives" > $O/captured_collectives.log 2>&1; grep -a "nccl\|rk_comm\|passed\|failed" $O/captured_collectives.log | cut -c1-1200
 	;;
 mcts)

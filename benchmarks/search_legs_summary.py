@@ -69,7 +69,7 @@ def main():
 			if rest:
 				half_calls, half_us = len(rest), sum(rest) / len(rest) / 1e3
 	rec = {
-		"command": "rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 300 --warmup 30 --no-cpu-baseline",
+		"command": "rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --steps 300 --warmup 30 --no-cpu-baseline",
 		"astar_iterations_in_process": iters, "astar_engine_us_per_iteration_rocprof": engine_us, "astar_kernels": astar,
 		"mcts_backup_select_launches": sel_calls, "mcts_select_us_rocprof": sel_us,
 		"mcts_backup_select_half_batch_launches": half_calls, "mcts_select_us_rocprof_half_batch": half_us,

@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_prints_one_contract_line():
-	out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "3", "--no-cpu-baseline"],
+	out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "3", "--full", "--no-cpu-baseline"],
 	                     capture_output=True, text=True, timeout=300, cwd=ROOT)
 	assert out.returncode == 0, out.stderr[-2000:]
 	lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -36,6 +36,43 @@ def test_bench_prints_one_contract_line():
 	assert r["pace_tau_ps"] in (0, 2000, 2100, 2200, 2400) and r["pace_source"] in ("calibrated on this device", "environment")
 
 
+def test_plain_run_is_lean_and_dumps_the_last_step(tmp_path):
+	"""A plain run (no --full) prints the contract line and nothing of what --full adds; --dump-outputs writes the last timed step's
+	outputs, which are the fan-out of their parents with the flags of a goal test, and two runs with the same arguments write the
+	same arrays."""
+	import numpy as np
+	from oracle import c_oracle, cube_oracle as orc
+	dumps = []
+	for run in range(2):
+		d = tmp_path / f"run{run}"
+		out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs", str(d)],
+		                     capture_output=True, text=True, timeout=300, cwd=ROOT)
+		assert out.returncode == 0, out.stderr[-2000:]
+		lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+		assert len(lines) == 1
+		r = json.loads(lines[0])
+		assert r["steps"] == 7 and r["warmup"] == 2 and r["n_gpus"] == 1 and r["unit"] == "expansions/s" and r["dtype"] == "u8"
+		assert r["higher_is_better"] is True and abs(r["value"] - 1e6 / (r["ms_per_step"] * 1e-3)) / r["value"] < 1e-6
+		assert 0.2 < r["roofline"]["frac"] < 1.0
+		for key in ("verified_children", "cpu_baseline", "astar_states_per_s", "mcts_tree_sims_per_s", "frac_ring_same_box"):
+			assert key not in r, key
+		assert "kernel_ms_4_input_sets" not in r["roofline"] and "per_launch_event_pairs_ms" not in r["roofline"]
+		files = sorted(os.listdir(d))
+		assert files == ["children.npy", "children_sums.npy", "solved.npy", "solved_count.npy"]
+		assert sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+		dumps.append({f[:-4]: np.load(d / f) for f in files})
+	a, b = dumps
+	for k in a:
+		assert a[k].dtype in (np.float32, np.float64) and np.array_equal(a[k], b[k]), k
+	kids = a["children"].astype(np.int8)
+	assert kids.shape == (12 * 32_768, 20) and a["solved"].shape == (12 * 32_768,)
+	undo = np.tile(np.arange(12, dtype=np.uint8) ^ 1, 32_768)
+	back = c_oracle.multi_rotate(kids, undo, threads=8).reshape(-1, 12, 20)
+	assert (back == back[:, :1]).all()                               # the 12 children of a parent undo to one state
+	assert (a["solved"].astype(bool) == orc.multi_is_solved(kids)).all()
+	assert a["children_sums"].shape == (20,) and a["solved_count"].shape == (1,) and a["solved_count"][0] >= a["solved"].sum()
+
+
 def test_smoke_entry_point():
 	sys.path.insert(0, ROOT)
 	import __graft_entry__
@@ -56,7 +93,7 @@ def test_bench_two_ranks_without_a_launcher():
 	env["RK_BENCH_BACKEND"] = "gloo"
 	env["RK_BENCH_SEARCH_NET"] = "stub"
 	games, budget, N, depth = 2, 60_000, 100, 12
-	out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "2", "--search-games", str(games),
+	out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "2", "--full", "--search-games", str(games),
 	                      "--search-budget", str(budget), "--search-expansions", str(N), "--search-depth", str(depth), "--mcts-sims", "64"],
 	                     capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
 	assert out.returncode == 0, out.stderr[-3000:]
@@ -94,7 +131,7 @@ def test_a_hanging_leg_does_not_lose_the_headline():
 	rank 0 still prints the ONE line -- the fan-out value, the contract fields -- with `multi_gpu_legs_error` saying what happened."""
 	env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
 	env.update(RK_BENCH_BACKEND="gloo", RK_BENCH_SEARCH_NET="stub", RK_BENCH_LEGS_TIMEOUT="0.5")
-	out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "1"],
+	out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "1", "--full"],
 	                     capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
 	assert out.returncode == 0, out.stderr[-3000:]
 	lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -116,7 +153,7 @@ def test_the_multi_gpu_code_path_over_rccl_with_one_rank():
 	env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "RK_BENCH_BACKEND")}
 	env.update(RK_BENCH_FORCE_MULTI="1", RK_BENCH_SEARCH_NET="stub")
 	games, budget, N, depth = 2, 60_000, 100, 12
-	out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "2", "--no-cpu-baseline", "--search-games", str(games),
+	out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "2", "--full", "--no-cpu-baseline", "--search-games", str(games),
 	                      "--search-budget", str(budget), "--search-expansions", str(N), "--search-depth", str(depth), "--mcts-sims", "64"],
 	                     capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
 	assert out.returncode == 0, out.stderr[-3000:]

@@ -31,6 +31,20 @@ def test_bench_starts_its_own_ranks():
 	assert abs(r["max_over_ranks_s"] - 0.002) < 1e-9                        # the slowest rank's time, through the all-reduce
 
 
+def test_bench_options_reach_every_rank():
+	"""--full and --dump-outputs are off by default, parse, and travel with the rest of the arguments to the ranks bench.py starts."""
+	sys.path.insert(0, ROOT)
+	import bench
+	a = bench.parse_args(["--gpus", "1", "--steps", "5", "--warmup", "1"])
+	assert a.full is False and a.dump_outputs is None and a.steps == 5 and a.warmup == 1
+	a = bench.parse_args(["--full", "--dump-outputs", "out"])
+	assert a.full is True and a.dump_outputs == "out"
+	out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full",
+	                      "--dump-outputs", "unused", "--dry-run"], capture_output=True, text=True, timeout=300, cwd=ROOT, env=_clean_env())
+	assert out.returncode == 0, out.stderr[-2000:]
+	assert json.loads(out.stdout.strip().splitlines()[-1])["steps"] == 3
+
+
 def test_bench_under_a_launcher_does_not_spawn_again():
 	"""With WORLD_SIZE set (torch.distributed.run did the launching) the script is a rank, and a mismatch with --gpus is an error."""
 	env = dict(_clean_env(), RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29999")
