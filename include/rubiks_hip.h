@@ -48,6 +48,7 @@ extern "C" {
 #define RK_OH_F16  1
 #define RK_OH_BF16 2
 #define RK_OH_STATES 3   /* engines only: hand the net the 20-byte states themselves (first layer fused, rk_ohl_*) */
+#define RK_OH_I8   4     /* rk_oh686_from2024 only: int8 0 / 1 elements, i.e. the (6,8,6) state itself */
 
 #define RK_OHL_GATHER 0  /* exact float32 gather-sum through an LDS-resident weight slice */
 #define RK_OHL_MFMA   1  /* bf16 MFMA with the one-hot operand synthesised in registers; the form follows the batch size */
@@ -219,6 +220,18 @@ int rk_tail_linear(const void *d_x, size_t n, int K, size_t ldx, const void *d_w
 
 /* as_correct (cube.py:371-380): 686 one-hot int8 (n,288) -> float32 (n,48) of +1/-1. */
 int rk_as_correct686(const int8_t *d_states, float *d_out, size_t n, void *stream);
+
+/* 20-byte -> 6x8x6 (cube.py:58-71; the layout is as_oh of the 686 state, cube.py:363-369): n 20-byte states into n rows of
+ * 288 elements, element 48 f + 6 p + c = 1 where ring position p of face f shows colour c (48 ones per row).  out_dtype
+ * RK_OH_F32 / _F16 / _BF16 (a 6x8x6 net's input batch) or RK_OH_I8 (the int8 (6,8,6) states themselves).  The states must
+ * be legal (codes < 24, each position held once); an out-of-range code is read as 0 and the row is then meaningless.
+ * d_states20 4-byte, d_out 16-byte aligned; n = 0 is a no-op. */
+int rk_oh686_from2024(const int8_t *d_states20, void *d_out, int out_dtype, size_t n, void *stream);
+/* 6x8x6 -> 20-byte, the inverse (cube.py:58-71): n int8 (6,8,6) states (16-byte aligned) into n 20-byte states (4-byte
+ * aligned).  A row that is not a well-formed one-hot (six 0 / 1 bytes with exactly one 1 per slot) showing each of the 20
+ * cubies exactly once is written as twenty -1 bytes and counted: d_stats (int64[2], nullable, initialise to [0, INT64_MAX])
+ * gets [0] += such rows, [1] = min(first such row, previous value), as rk_multi_is_solved's counters. */
+int rk_686_to2024(const int8_t *d_states686, int8_t *d_out20, long long *d_stats, size_t n, void *stream);
 
 /* ---- batch weighted A* (agents.py:171-413): device-resident open set / closed set ---------------------------
  * Replaces the expand-children loop of AStar.search / expand_batch / relax_seen_states.  The engine owns:
@@ -506,6 +519,11 @@ int rk_apply_sequences_host(int repr, const uint8_t *h_actions, int depth, int g
 /* cube.as_oh as reference code calls it (cube.py:130-133, :265-277): states from HOST memory, the one-hot written to DEVICE
  * memory (`d_out`, 16-byte aligned, n x 480 or n x 288 elements of `out_dtype`), where the net reads it.  Synchronises. */
 int rk_as_oh_host(int repr, const int8_t *h_states, void *d_out, int out_dtype, size_t n, void *stream);
+/* rk_oh686_from2024 from HOST states (cube.py:58-71, 363-369), the rows written to DEVICE memory; synchronises. */
+int rk_oh686_from2024_host(const int8_t *h_states20, void *d_out, int out_dtype, size_t n, void *stream);
+/* rk_686_to2024 from HOST states into HOST memory (cube.py:58-71); h_stats (nullable) receives [count, first index] of the
+ * illegal rows ([0, INT64_MAX] when there are none); synchronises. */
+int rk_686_to2024_host(const int8_t *h_states686, int8_t *h_out20, long long *h_stats, size_t n, void *stream);
 
 #ifdef __cplusplus
 }

@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "librubiks_hip.so")
 
 REPR_2024, REPR_686 = 0, 1
-OH_F32, OH_F16, OH_BF16, OH_STATES = 0, 1, 2, 3
+OH_F32, OH_F16, OH_BF16, OH_STATES, OH_I8 = 0, 1, 2, 3, 4
 OHL_GATHER, OHL_MFMA, OHL_MFMA_DIRECT, OHL_MFMA_TILED = 0, 1, 2, 3
 OHL_ACT_NONE, OHL_ACT_ELU, OHL_ACT_RELU = 0, 1, 2
 INT64_MAX = (1 << 63) - 1
@@ -61,6 +61,8 @@ SIGNATURES = {
 	"rk_ohl_set_epilogue": (_i, [_vp, _i, C.c_float, _vp, _vp, _vp]),
 	"rk_tail_linear": (_i, [_vp, _sz, _i, _sz, _vp, _vp, _i, _i, C.c_float, _vp, _vp]),
 	"rk_as_correct686": (_i, [_vp, _vp, _sz, _vp]),
+	"rk_oh686_from2024": (_i, [_vp, _vp, _i, _sz, _vp]),
+	"rk_686_to2024": (_i, [_vp, _vp, _vp, _sz, _vp]),
 	"rk_astar_create": (_i, [C.POINTER(_vp), _sz, _i]),
 	"rk_astar_destroy": (_i, [_vp]),
 	"rk_astar_reset": (_i, [_vp, _vp, C.c_double, _vp]),
@@ -138,6 +140,8 @@ SIGNATURES = {
 	"rk_multi_is_solved_host": (_i, [_i, _vp, _vp, _vp, _sz, _vp]),
 	"rk_apply_sequences_host": (_i, [_i, _vp, _i, _i, _i, _i, _vp, _vp]),
 	"rk_as_oh_host": (_i, [_i, _vp, _vp, _i, _sz, _vp]),
+	"rk_oh686_from2024_host": (_i, [_vp, _vp, _i, _sz, _vp]),
+	"rk_686_to2024_host": (_i, [_vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -23,6 +23,9 @@ def adi_traindata(net, rollout_games: int, rollout_depth: int, alpha: float, rew
                   ff_batches: int = 1, fused_first_layer=False):
 	assert reward_method in ("paper", "lapanfix", "schultzfix", "reward0")
 	_ffi.require_gpu()
+	is2024 = cube.get_is2024()             # 6x8x6: the same walks in 20-byte form, the net's rows from the fused converter + encoder
+	if fused_first_layer and not is2024:
+		raise ValueError("fused_first_layer reads 20-byte states into a Linear(480, H); a 6x8x6 net has 288 inputs")
 	net.eval()
 	with_solved = reward_method == "lapanfix"
 	# scrambling: draws as cube.sequence_scrambler (cube.py:226-227), walks on the device           train.py:277
@@ -32,7 +35,7 @@ def adi_traindata(net, rollout_games: int, rollout_depth: int, alpha: float, rew
 	# walks, goal test of the scrambled states, fan-out and its goal test: ONE launch              train.py:277, :281, :285, :292
 	states, solved_scrambled, substates, solved_sub = cube.device.rollout_fanout(acts, with_solved)  # (games*depth, 20), ..., (12*games*depth, 20), ...
 	n = len(states)
-	oh_states = cube.device.as_oh(states)
+	oh_states = cube.device.as_oh(states) if is2024 else cube.device.to686(states, torch.float32)
 	solved_scrambled, solved_sub = solved_scrambled.bool(), solved_sub.bool()
 	rewards = torch.where(solved_sub, torch.tensor(0.0 if reward_method == "reward0" else 1.0, device=gpu),
 	                      torch.tensor(-1.0, device=gpu))                                         # train.py:294-296
@@ -49,10 +52,13 @@ def adi_traindata(net, rollout_games: int, rollout_depth: int, alpha: float, rew
 	else:
 		from librubiks_amd.solving.agents import _oh_dtype
 		oh_dtype = _oh_dtype(net)                  # a bf16 net gets bf16 rows straight from the kernel (0 / 1 are exact)
-		buf = torch.empty((min(step, 12 * n), 480), dtype=oh_dtype, device=gpu)
+		buf = torch.empty((min(step, 12 * n), 480 if is2024 else 288), dtype=oh_dtype, device=gpu)
 		for lo in range(0, 12 * n, step):
 			hi = min(lo + step, 12 * n)
-			cube.device.as_oh(substates[lo:hi], buf[:hi - lo], oh_dtype)
+			if is2024:
+				cube.device.as_oh(substates[lo:hi], buf[:hi - lo], oh_dtype)
+			else:
+				cube.device.to686(substates[lo:hi], oh_dtype, buf[:hi - lo])
 			values[lo:hi] = net(buf[:hi - lo], policy=False, value=True).reshape(-1).float()
 	values = (values + rewards).reshape(-1, 12)                                                   # train.py:313-314
 	policy_targets = torch.argmax(values, dim=1)

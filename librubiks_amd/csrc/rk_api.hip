@@ -436,6 +436,31 @@ int rk_as_correct686(const int8_t *d_states, float *d_out, size_t n, void *strea
 	return RK_OK;
 }
 
+int rk_oh686_from2024(const int8_t *d_states20, void *d_out, int out_dtype, size_t n, void *stream)
+{
+	if (out_dtype != RK_OH_F32 && out_dtype != RK_OH_F16 && out_dtype != RK_OH_BF16 && out_dtype != RK_OH_I8)
+		return fail(RK_EINVAL, "rk_oh686_from2024: unknown output dtype %d", out_dtype);
+	if (n == 0) return RK_OK;
+	if (!d_states20 || !d_out) return fail(RK_EINVAL, "rk_oh686_from2024: null pointer");
+	if (misaligned(d_states20, 4)) return fail(RK_EINVAL, "rk_oh686_from2024: states must be 4-byte aligned");
+	if (misaligned(d_out, 16)) return fail(RK_EINVAL, "rk_oh686_from2024: output must be 16-byte aligned");
+	launch_oh686_from2024(d_states20, d_out, out_dtype, n, (hipStream_t)stream);
+	RK_HIP(hipGetLastError());
+	return RK_OK;
+}
+
+int rk_686_to2024(const int8_t *d_states686, int8_t *d_out20, long long *d_stats, size_t n, void *stream)
+{
+	if (n == 0) return RK_OK;
+	if (!d_states686 || !d_out20) return fail(RK_EINVAL, "rk_686_to2024: null pointer");
+	if (misaligned(d_states686, 16)) return fail(RK_EINVAL, "rk_686_to2024: 6x8x6 states must be 16-byte aligned");
+	if (misaligned(d_out20, 4)) return fail(RK_EINVAL, "rk_686_to2024: output must be 4-byte aligned");
+	if (d_stats && misaligned(d_stats, 8)) return fail(RK_EINVAL, "rk_686_to2024: stats must be 8-byte aligned");
+	launch_686_to2024(d_states686, d_out20, d_stats, n, (hipStream_t)stream);
+	RK_HIP(hipGetLastError());
+	return RK_OK;
+}
+
 // ---- host-pointer conveniences ------------------------------------------------------------------------------
 
 static const long long STATS_INIT[2] = {0, LLONG_MAX};
@@ -606,6 +631,52 @@ int rk_as_oh_host(int repr, const int8_t *h_states, void *d_out, int out_dtype, 
 	RK_HIP(hipMemcpyAsync(in.p, h_states, n * sb, hipMemcpyHostToDevice, st));
 	if (int e = rk_as_oh(repr, (const int8_t *)in.p, d_out, out_dtype, n, stream)) return e;
 	RK_HIP(hipStreamSynchronize(st));
+	return RK_OK;
+}
+
+int rk_oh686_from2024_host(const int8_t *h_states20, void *d_out, int out_dtype, size_t n, void *stream)
+{
+	if (out_dtype != RK_OH_F32 && out_dtype != RK_OH_F16 && out_dtype != RK_OH_BF16 && out_dtype != RK_OH_I8)
+		return fail(RK_EINVAL, "rk_oh686_from2024_host: unknown output dtype %d", out_dtype);
+	if (n == 0) return RK_OK;
+	if (!h_states20 || !d_out) return fail(RK_EINVAL, "rk_oh686_from2024_host: null pointer");
+	if (misaligned(d_out, 16)) return fail(RK_EINVAL, "rk_oh686_from2024_host: output must be 16-byte aligned");
+	hipStream_t st = (hipStream_t)stream;
+	if (up256(n * STATE_BYTES) <= ZERO_COPY_MAX) {
+		if (PinnedBuf *b = pinned_buffer()) {                 // zero-copy: see ZERO_COPY_MAX
+			memcpy(b->host, h_states20, n * STATE_BYTES);
+			if (int e = rk_oh686_from2024((const int8_t *)b->dev, d_out, out_dtype, n, stream)) return e;
+			RK_HIP(hipStreamSynchronize(st));                 // the buffer belongs to the next call from here on
+			return RK_OK;
+		}
+	}
+	ScratchScope scope;
+	DevBuf in;
+	if (int e = in.alloc(n * STATE_BYTES)) return e;
+	RK_HIP(hipMemcpyAsync(in.p, h_states20, n * STATE_BYTES, hipMemcpyHostToDevice, st));
+	if (int e = rk_oh686_from2024((const int8_t *)in.p, d_out, out_dtype, n, stream)) return e;
+	RK_HIP(hipStreamSynchronize(st));
+	return RK_OK;
+}
+
+int rk_686_to2024_host(const int8_t *h_states686, int8_t *h_out20, long long *h_stats, size_t n, void *stream)
+{
+	if (n == 0) return RK_OK;
+	if (!h_states686 || !h_out20) return fail(RK_EINVAL, "rk_686_to2024_host: null pointer");
+	hipStream_t st = (hipStream_t)stream;
+	ScratchScope scope;
+	DevBuf in, out, stats;
+	if (int e = in.alloc(n * S686_BYTES)) return e;
+	if (int e = out.alloc(n * STATE_BYTES)) return e;
+	if (int e = stats.alloc(sizeof STATS_INIT)) return e;
+	RK_HIP(hipMemcpyAsync(in.p, h_states686, n * S686_BYTES, hipMemcpyHostToDevice, st));
+	RK_HIP(hipMemcpyAsync(stats.p, STATS_INIT, sizeof STATS_INIT, hipMemcpyHostToDevice, st));
+	if (int e = rk_686_to2024((const int8_t *)in.p, (int8_t *)out.p, (long long *)stats.p, n, stream)) return e;
+	RK_HIP(hipMemcpyAsync(h_out20, out.p, n * STATE_BYTES, hipMemcpyDeviceToHost, st));
+	long long got[2] = {0, LLONG_MAX};
+	RK_HIP(hipMemcpyAsync(got, stats.p, sizeof got, hipMemcpyDeviceToHost, st));
+	RK_HIP(hipStreamSynchronize(st));
+	if (h_stats) { h_stats[0] = got[0]; h_stats[1] = got[1]; }
 	return RK_OK;
 }
 

@@ -43,4 +43,9 @@ void launch_is_solved686(const int8_t *states, uint8_t *flags, long long *stats,
 void launch_as_oh686(const int8_t *states, void *out, int out_dtype, size_t n, hipStream_t st);
 void launch_as_correct686(const int8_t *states, float *out, size_t n, hipStream_t st);
 
+// 20-byte <-> 6x8x6 (rk_repr686.hip); output kinds are the RK_OH_* codes of the header (RK_OH_I8: the int8 (6,8,6) state)
+enum { RK686_F32 = 0, RK686_F16 = 1, RK686_BF16 = 2, RK686_I8 = 4 };
+void launch_oh686_from2024(const int8_t *states, void *out, int kind, size_t n, hipStream_t st);
+void launch_686_to2024(const int8_t *states, int8_t *out, long long *stats, size_t n, hipStream_t st);
+
 }  // namespace rk

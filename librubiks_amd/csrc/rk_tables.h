@@ -97,4 +97,95 @@ constexpr Tables make_tables()
 	return t;
 }
 
+// ---- 20-byte <-> 6x8x6 (the two representations of one cube, cube.py:58-71) ----------------------------------------
+// Both forms follow the same actions, so each cubie's stickers can be tracked through the 6x8x6 sticker permutation while
+// its 20-byte code is tracked through the move table: starting from the solved cube, a breadth-first walk over the 12
+// actions reaches every (cubie, code) pair and records which slot shows which of the cubie's colours there.  Nothing is
+// typed in: the slots of a cubie position are the slots that exactly the faces holding that position move, a sticker's
+// colour is the face of the slot it shows at home, and `consistent` checks that every path to a code agrees.
+struct alignas(16) Repr686Tables {
+	// fw[c][v]: cubie c (0..7 corners, 8..19 edges) with code v; sticker k (3 corners, 2 edges) in bits 9k..9k+8 as
+	// slot (6 bits, slot = 8*face + ring position) | colour << 6
+	uint32_t fw[20][24];
+	// home[pos]: the slots of cubie position pos (0..7 corners, 8..19 edges), its stickers' slots at home, ascending;
+	// inv[pos][c0][c1]: the cubie * 32 + code that shows colours c0, c1 at home[pos][0], home[pos][1]; 0xFFFF: none
+	uint8_t  home[20][3];
+	uint16_t inv[20][6][6];
+	bool     consistent;
+};
+
+constexpr int face_mask_of_slot(const Tables &t, int s)
+{
+	int m = 0;
+	for (int f = 0; f < 6; f++) if (t.perm686[2 * f][s] != s) m |= 1 << f;
+	return m;
+}
+
+constexpr Repr686Tables make_repr686_tables()
+{
+	const Tables t = make_tables();
+	Repr686Tables r{};
+	r.consistent = true;
+	uint8_t slot[20][24][3] = {};
+	bool known[20][24] = {};
+	for (int c = 0; c < 20; c++) {
+		const bool corner = c < 8;
+		const int pos = corner ? c : c - 8, n = corner ? 3 : 2;
+		int want = 0;
+		for (int f = 0; f < 6; f++)
+			for (int j = 0; j < 4; j++)
+				if ((corner ? FACES[f].corner[j] : FACES[f].edge[j]) == pos) want |= 1 << f;
+		int k = 0;
+		for (int s = 0; s < S686_SLOTS; s++)
+			if (face_mask_of_slot(t, s) == want) {
+				if (k < 3) r.home[c][k] = (uint8_t)s;
+				k++;
+			}
+		if (k != n) r.consistent = false;
+		const int v0 = corner ? 3 * pos : 2 * pos;
+		for (int j = 0; j < n; j++) slot[c][v0][j] = r.home[c][j];
+		known[c][v0] = true;
+		for (bool grew = true; grew;) {
+			grew = false;
+			for (int v = 0; v < 24; v++) {
+				if (!known[c][v]) continue;
+				for (int a = 0; a < N_ACTIONS; a++) {
+					const int w = t.lut[a][corner ? 0 : 1][v];
+					uint8_t moved[3] = {};
+					for (int j = 0; j < n; j++) moved[j] = t.perm686[a ^ 1][slot[c][v][j]];     // perm686[a ^ 1] inverts perm686[a]
+					if (known[c][w]) {
+						for (int j = 0; j < n; j++) if (slot[c][w][j] != moved[j]) r.consistent = false;
+					} else {
+						for (int j = 0; j < n; j++) slot[c][w][j] = moved[j];
+						known[c][w] = grew = true;
+					}
+				}
+			}
+		}
+		for (int v = 0; v < 24; v++) {
+			if (!known[c][v]) r.consistent = false;
+			uint32_t e = 0;
+			for (int j = 0; j < n; j++) e |= (uint32_t)(slot[c][v][j] | (r.home[c][j] >> 3) << 6) << (9 * j);
+			r.fw[c][v] = e;
+		}
+	}
+	for (int p = 0; p < 20; p++)
+		for (int a = 0; a < 6; a++)
+			for (int b = 0; b < 6; b++) r.inv[p][a][b] = 0xFFFF;
+	for (int c = 0; c < 20; c++) {
+		const bool corner = c < 8;
+		const int n = corner ? 3 : 2;
+		for (int v = 0; v < 24; v++) {
+			const int p = corner ? v / 3 : 8 + v / 2;
+			int col[2] = {-1, -1};
+			for (int j = 0; j < n; j++)
+				for (int h = 0; h < 2; h++)
+					if (slot[c][v][j] == r.home[p][h]) col[h] = r.home[c][j] >> 3;
+			if (col[0] < 0 || col[1] < 0 || r.inv[p][col[0]][col[1]] != 0xFFFF) { r.consistent = false; continue; }
+			r.inv[p][col[0]][col[1]] = (uint16_t)(c * 32 + v);
+		}
+	}
+	return r;
+}
+
 }  // namespace rk

@@ -427,6 +427,96 @@ class device:
 		_ffi.check(_ffi.lib().rk_as_oh(_repr_id(), states.data_ptr(), out.data_ptr(), code, n, _ffi.stream_ptr()))
 		return out
 
+	@staticmethod
+	def to686(states20: torch.Tensor, dtype: torch.dtype = torch.int8, out: torch.Tensor = None) -> torch.Tensor:
+		"""20-byte states (n, 20) -> their 6x8x6 form in ONE launch (cube.py:58-71): int8 (n, 6, 8, 6) states, or, for float32 /
+		float16 / bfloat16, the (n, 288) one-hot a 6x8x6 net reads (= as_oh of the int8 form, cube.py:363-369).  Any repr."""
+		_ffi.require_gpu()
+		_check_dev(states20, torch.int8, "states20")
+		n = len(states20)
+		if states20.numel() != 20 * n:
+			raise ValueError(f"states20 must have shape (n, 20), got {tuple(states20.shape)}")
+		code = {torch.int8: _ffi.OH_I8, torch.float32: _ffi.OH_F32, torch.float16: _ffi.OH_F16, torch.bfloat16: _ffi.OH_BF16}.get(dtype)
+		if code is None:
+			raise ValueError(f"to686 writes int8, float32, float16 or bfloat16, not {dtype}")
+		if out is None:
+			out = torch.empty((n, 6, 8, 6) if dtype == torch.int8 else (n, 288), dtype=dtype, device=states20.device)
+		else:
+			_check_dev(out, dtype, "out")
+			if out.numel() < 288 * n:
+				raise ValueError("to686 output too small")
+		_ffi.check(_ffi.lib().rk_oh686_from2024(states20.data_ptr(), out.data_ptr(), code, n, _ffi.stream_ptr()))
+		return out
+
+	@staticmethod
+	def from686(states686: torch.Tensor, out: torch.Tensor = None, stats: torch.Tensor = None, check: bool = True) -> torch.Tensor:
+		"""int8 (n, 6, 8, 6) [or (n, 288)] states -> (n, 20) states (cube.py:58-71).  A row that is not a well-formed one-hot showing
+		each cubie once is written as -1 bytes and counted in `stats` (int64[2] = [count, first index], initialise to [0, INT64_MAX]);
+		with `check` (and no `stats` of the caller's) such a row raises ValueError, which costs one synchronisation."""
+		_ffi.require_gpu()
+		_check_dev(states686, torch.int8, "states686")
+		n = len(states686)
+		if states686.numel() != 288 * n:
+			raise ValueError(f"states686 must have shape (n, 6, 8, 6), got {tuple(states686.shape)}")
+		if out is None:
+			out = torch.empty((n, 20), dtype=torch.int8, device=states686.device)
+		else:
+			_check_dev(out, torch.int8, "out")
+			if out.numel() < 20 * n:
+				raise ValueError("from686 output too small")
+		own = stats is None and check
+		if own:
+			stats = _new_stats()
+		elif stats is not None:
+			_check_dev(stats, torch.int64, "stats")
+		_ffi.check(_ffi.lib().rk_686_to2024(states686.data_ptr(), out.data_ptr(), stats.data_ptr() if stats is not None else None, n,
+		                                    _ffi.stream_ptr()))
+		if own:
+			bad, first = stats.tolist()
+			if bad:
+				raise ValueError(f"{bad} of {n} rows are not legal 6x8x6 cube states (the first is row {first})")
+		return out
+
+
+def as686(states20: np.ndarray) -> np.ndarray:
+	"""20-byte states (n, 20) [or one state (20,)] -> the same cubes as int8 (n, 6, 8, 6) [or (6, 8, 6)], whatever the current repr.
+	Device tensors in -> device tensors out."""
+	if _is_dev(states20):
+		one = states20.dim() == 1
+		out = device.to686(states20.reshape(-1, 20).contiguous())
+		return out[0] if one else out
+	src = np.ascontiguousarray(states20, dtype=np.int8)
+	one = src.ndim == 1
+	src = src.reshape(-1, 20)
+	if len(src) == 0:
+		return np.zeros((0, 6, 8, 6), np.int8)
+	_ffi.require_gpu()
+	out = torch.empty((len(src), 6, 8, 6), dtype=torch.int8, device=gpu)
+	_ffi.check(_ffi.lib().rk_oh686_from2024_host(src.ctypes.data, out.data_ptr(), _ffi.OH_I8, len(src), _ffi.stream_ptr()))
+	host = _to_host(out)
+	return host[0] if one else host
+
+
+def as2024(states686: np.ndarray) -> np.ndarray:
+	"""int8 (n, 6, 8, 6) states [or one (6, 8, 6)] -> the same cubes as 20-byte states, whatever the current repr.  ValueError
+	if a row is not a legal 6x8x6 state.  Device tensors in -> device tensors out."""
+	if _is_dev(states686):
+		one = states686.dim() == 3
+		out = device.from686(states686.reshape(-1, 6, 8, 6).contiguous())
+		return out[0] if one else out
+	src = np.ascontiguousarray(states686, dtype=np.int8)
+	one = src.ndim == 3
+	src = src.reshape(-1, 288)
+	if len(src) == 0:
+		return np.zeros((0, 20), np.int8)
+	_ffi.require_gpu()
+	out = np.empty((len(src), 20), np.int8)
+	stats = np.zeros(2, np.int64)
+	_ffi.check(_ffi.lib().rk_686_to2024_host(src.ctypes.data, out.ctypes.data, stats.ctypes.data, len(src), _ffi.stream_ptr()))
+	if stats[0]:
+		raise ValueError(f"{int(stats[0])} of {len(src)} rows are not legal 6x8x6 cube states (the first is row {int(stats[1])})")
+	return out[0] if one else out
+
 
 ################
 # Rotate logic #   (cube.py:41-52)

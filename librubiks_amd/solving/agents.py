@@ -115,6 +115,9 @@ class DeepAgent(Agent):
 		self._fused_mode = fused_first_layer or False
 		self._fused, self._fused_sig = None, None
 		self._fs = None                    # `_from_states` as checked at the start of the running search (hot loops use this)
+		self._is2024 = True                # the representation of the last search (cube.get_is2024() when it began); its exports follow it
+		self._r686 = None                  # the kept 6x8x6 adapter of this agent's net (_Net686), the same object from search to search
+		self._n686 = None                  # ... while the running search is in 6x8x6 mode, else None
 		self.net = net
 
 	@property
@@ -137,10 +140,69 @@ class DeepAgent(Agent):
 			self._fused, self._fused_sig = fused_net(self._net, self._fused_mode), sig
 		return self._fused
 
+	def _begin_repr(self):
+		"""Fixes the representation of the search that starts (the reference's agents follow cube.get_is2024()).  In 6x8x6 mode the
+		engines still run on 20-byte states and hand the net their rows as RK_OH_STATES; `_n686` turns them into the 6x8x6 one-hot
+		the net was trained on (rk_oh686_from2024)."""
+		self._is2024 = cube.get_is2024()
+		if self._is2024:
+			self._n686 = None
+			return
+		if self._fused_mode:
+			raise ValueError("fused_first_layer reads 20-byte states into a Linear(480, H); a net of the 6x8x6 representation has 288 "
+			                 "inputs and no fused form")
+		if self._r686 is None or self._r686.net is not self._net:
+			self._r686 = _Net686(self._net)
+		self._n686 = self._r686
+
+	def _roots20(self, states, n: int) -> np.ndarray:
+		"""The search's start states as (n, 20) int8 rows; in 6x8x6 mode converted (ValueError for a state that is not a legal cube)."""
+		if self._is2024:
+			return np.ascontiguousarray(states, dtype=np.int8).reshape(n, 20)
+		return np.ascontiguousarray(cube.as2024(np.asarray(states, dtype=np.int8).reshape(n, 6, 8, 6)))
+
+	def _states_out(self, states20: np.ndarray, n: int) -> np.ndarray:
+		"""An exported (rows, 20) array whose rows 1..n hold nodes, in the representation of the last search (other rows stay zero)."""
+		if self._is2024:
+			return states20
+		out = np.zeros((len(states20), 6, 8, 6), np.int8)
+		if n:
+			out[1:n + 1] = cube.as686(states20[1:n + 1])
+		return out
+
 	@classmethod
 	def from_saved(cls, loc: str, use_best: bool, loader=None):
 		"""agents.py:72-76."""
 		return cls(_load_net(loc, use_best, loader))
+
+
+from librubiks_amd.cube.cube import _solved2024 as _SOLVED20  # noqa: E402  (the 20-byte solved state, whatever the repr)
+
+
+class _Net686:
+	"""
+	`net(as_oh(6x8x6 form of rows))` for (n, 20) int8 rows: what a net trained on the 6x8x6 representation sees of the engines'
+	20-byte states.  One launch (rk_oh686_from2024) writes the one-hot in the net's dtype into a buffer this object keeps, then the
+	net runs on it.  The object and its buffers outlive a search, so a captured step that holds their addresses stays valid and a
+	second search replays it; a larger batch gets a new buffer and the old ones are kept (a kept graph may still read them).
+	"""
+	def __init__(self, net):
+		self.net = net
+		self._bufs = []
+
+	def _buffer(self, n: int, dtype: torch.dtype) -> torch.Tensor:
+		for b in reversed(self._bufs):
+			if b.dtype == dtype and len(b) >= n:
+				return b[:n]
+		b = torch.empty((max(n, 64), 288), dtype=dtype, device=gpu)
+		self._bufs.append(b)
+		return b[:n]
+
+	def __call__(self, rows: torch.Tensor, policy: bool = True, value: bool = True):
+		dtype = _oh_dtype(self.net)
+		x = self._buffer(len(rows), dtype)
+		cube.device.to686(rows, dtype, x)
+		return self.net(x, policy=policy, value=value)
 
 
 def _host_softmax(logits_cpu: torch.Tensor) -> torch.Tensor:
@@ -274,9 +336,16 @@ class EGVM(DeepAgent):
 			self.action_queue += deque(int(a) for a in paths[worker, :d + 1])
 		return False
 
+	def _oh(self, rows: torch.Tensor) -> torch.Tensor:
+		"""The float32 one-hot of 20-byte rows in the representation of the search (agents.py:697, :709: cube.as_oh)."""
+		return cube.device.as_oh(rows) if self._is2024 else cube.device.to686(rows, torch.float32)
+
 	def expand(self, state: np.ndarray):
-		"""Walks all workers `depth` moves on the device; row w*depth + d = worker w after d+1 moves."""
-		cur = torch.from_numpy(cube.repeat_state(np.asarray(state), self.workers)).to(gpu)
+		"""Walks all workers `depth` moves on the device; row w*depth + d = worker w after d+1 moves.  In 6x8x6 mode the walks run in
+		20-byte form (the same draws), the net sees 288-wide rows and the states come back as (6, 8, 6)."""
+		self._is2024 = cube.get_is2024()
+		root = self._roots20(state, 1)[0]
+		cur = torch.from_numpy(cube.repeat_state(root, self.workers)).to(gpu)
 		paths = np.empty((self.workers, self.depth), dtype=int)
 		visited = torch.empty((self.workers, self.depth, 20), dtype=torch.int8, device=gpu)
 		flags = torch.empty(self.workers, dtype=torch.uint8, device=gpu)
@@ -287,12 +356,16 @@ class EGVM(DeepAgent):
 			actions = np.empty(self.workers, dtype=int)
 			actions[use_random] = np.random.randint(0, cube.action_dim, use_random.sum())
 			if (~use_random).any():
-				p = self.net(cube.device.as_oh(cur[torch.from_numpy(~use_random).to(gpu)].contiguous()), value=False).float().cpu().numpy()
+				p = self.net(self._oh(cur[torch.from_numpy(~use_random).to(gpu)].contiguous()), value=False).float().cpu().numpy()
 				actions[~use_random] = p.argmax(axis=1)
 			paths[:, d] = actions
 			# move + goal test in one launch (agents.py:696-703); the host reads the two statistics words, not the flags
 			stats.copy_(stats0)
-			cur, _ = cube.device.multi_rotate_solved(cur, torch.from_numpy(actions.astype(np.uint8)).to(gpu), flags=flags, stats=stats)
+			acts = torch.from_numpy(actions.astype(np.uint8)).to(gpu)
+			nxt = torch.empty_like(cur)              # the walk is in 20-byte form whatever the repr: REPR_2024 explicitly
+			_ffi.check(_ffi.lib().rk_multi_rotate_solved(_ffi.REPR_2024, cur.data_ptr(), acts.data_ptr(), nxt.data_ptr(), flags.data_ptr(),
+			                                             stats.data_ptr(), self.workers, _ffi.stream_ptr()))
+			cur = nxt
 			hit = stats.cpu()
 			if int(hit[0]):
 				self._explored_states += (d + 1) * self.workers
@@ -300,7 +373,7 @@ class EGVM(DeepAgent):
 			visited[:, d] = cur
 		self._explored_states += self.workers * self.depth
 		flat = visited.reshape(self.workers * self.depth, 20)
-		return paths, flat.cpu().numpy(), cube.device.as_oh(flat), (-1, -1)
+		return paths, (flat.cpu().numpy() if self._is2024 else cube.as686(flat).cpu().numpy()), self._oh(flat), (-1, -1)
 
 	@classmethod
 	def from_saved(cls, loc: str, use_best: bool, epsilon: float, workers: int, depth: int, loader=None):
@@ -495,7 +568,7 @@ class AStar(DeepAgent):
 		_ffi.check(lib.rk_astar_step_expand(h, oh.data_ptr(), code, _ffi.stream_ptr()))
 		if ev is not None:
 			marks[1].record()
-		values = _values_for_engine(h, _sliced_value_forward(self._fs or self.net, oh))
+		values = _values_for_engine(h, _sliced_value_forward(self._fs or self._n686 or self.net, oh))
 		self._keep = values                # the commit kernels read it after this call returns
 		if ev is not None:
 			marks[2].record()
@@ -515,19 +588,22 @@ class AStar(DeepAgent):
 		K = 12 * self.expansions
 		cap = max(int(min(max_states, self.capacity or self.default_capacity)), K + 2)
 		lib = _ffi.lib()
+		self._begin_repr()                     # 6x8x6: the engine runs on the root's 20-byte form, the net gets 6x8x6 rows
+		root = self._roots20(state, 1)[0]
 		self._fs = self._from_states           # re-copied here if the net changed since the last search
-		code = _ffi.OH_STATES if self._fs is not None else _OH_CODES[_oh_dtype(self.net)]
+		rows_net = self._fs or self._n686      # the net as a function of 20-byte rows, or None
+		code = _ffi.OH_STATES if rows_net is not None else _OH_CODES[_oh_dtype(self.net)]
 		cached = self._graph_cache
 		if cached is not None and self.use_hipgraph and cached[2][1] == code and len(cached[2][0]) == K:
 			oh = cached[2][0]                  # the buffer the kept graph was captured on (rows are rewritten before they are read)
-		elif self._fs is not None:
-			oh = torch.from_numpy(cube.repeat_state(cube.get_solved(), K)).to(gpu)      # (K, 20) int8: valid codes everywhere
+		elif rows_net is not None:
+			oh = torch.from_numpy(cube.repeat_state(_SOLVED20, K)).to(gpu)      # (K, 20) int8: valid codes everywhere
 		else:
 			oh = torch.zeros((K, 480), dtype=_oh_dtype(self.net), device=gpu)
 		status = (C.c_longlong * 8)()
 		h = self._engine(cap)
 		cap = self._h_cap
-		_ffi.check(lib.rk_astar_reset(h, state.ctypes.data, float(self.lambda_), _ffi.stream_ptr()))
+		_ffi.check(lib.rk_astar_reset(h, root.ctypes.data, float(self.lambda_), _ffi.stream_ptr()))
 		_ffi.check(lib.rk_astar_set_budget(h, int(min(max_states, cap)), _ffi.stream_ptr()))
 		self._root, self._n, self._cache = state.copy(), 1, None
 		self.iterations, self.pops, self.grown = 0, [], 0
@@ -542,7 +618,7 @@ class AStar(DeepAgent):
 				# rewrites.  So the graph is KEPT from search to search and captured again only when one of those changes (a grown
 				# or new engine, another net or fused copy, another lambda): capturing cost every search about 7 ms
 				# (profiles/NOTES.md section 7), as much as a hundred iterations.
-				key = (h.value, cap, float(self.lambda_), code, oh.data_ptr(), _capture_key(self.net, self._fs))
+				key = (h.value, cap, float(self.lambda_), code, oh.data_ptr(), _capture_key(self.net, rows_net))
 				if self._graph_cache is not None and self._graph_cache[0] == key:
 					graph = self._graph_cache[1]
 				else:
@@ -555,7 +631,7 @@ class AStar(DeepAgent):
 					graph = torch.cuda.CUDAGraph()                 # (captured again after a growth: it holds the pool's addresses)
 					with torch.cuda.graph(graph, **CAPTURE):
 						self._iteration(h, oh, code)
-					self._graph_cache = (key, graph, (oh, code), (self.net, self._fs))     # the net stays alive with the graph that holds its addresses
+					self._graph_cache = (key, graph, (oh, code), (self.net, rows_net))     # the net stays alive with the graph that holds its addresses
 					self.captures += 1
 			budget = int(min(max_states, cap))
 			done = won = err = solved_idx = 0
@@ -572,7 +648,7 @@ class AStar(DeepAgent):
 				values = None
 				if n_new:
 					_ffi.check(lib.rk_astar_new_states_oh(h, oh.data_ptr(), code, _ffi.stream_ptr()))
-					values = _values_for_engine(h, _sliced_value_forward(self._fs or self.net, oh[:n_new]))
+					values = _values_for_engine(h, _sliced_value_forward(self._fs or self._n686 or self.net, oh[:n_new]))
 				_ffi.check(lib.rk_astar_commit(h, values.data_ptr() if values is not None else None, _ffi.stream_ptr()))
 				if time.perf_counter() - t0 >= time_limit:
 					break
@@ -633,7 +709,7 @@ class AStar(DeepAgent):
 				_ffi.check(_ffi.lib().rk_astar_export(
 					self._h, 1, n, states[1:].ctypes.data, G[1:].ctypes.data, parents[1:].ctypes.data, pact[1:].ctypes.data,
 					_ffi.stream_ptr()))
-			self._cache = (states, G, parents, pact)
+			self._cache = (self._states_out(states, n), G, parents, pact)
 		return self._cache
 
 	@property
@@ -669,7 +745,7 @@ class AStar(DeepAgent):
 		return list(zip(costs[:got].tolist(), idx[:got].tolist()))
 
 	def index_of(self, state: np.ndarray) -> int:
-		state = np.ascontiguousarray(state, dtype=np.int8)
+		state = self._roots20(state, 1)[0]
 		return int(_ffi.lib().rk_astar_lookup(self._h, state.ctypes.data, _ffi.stream_ptr()))
 
 	@no_grad
@@ -813,6 +889,10 @@ class MCTSBatch(DeepAgent):
 			# the first layer reads the children where the engine keeps them; no one-hot, no copy
 			x = self._fs.first.from_pointer(lib.rk_mcts_children(h), 12 * self.n_trees)
 			p, v = self._fs.tail(x)
+		elif self._n686 is not None:
+			# 6x8x6 net: the children's 20-byte rows, then their 6x8x6 one-hot in the net's dtype (one launch) and the net
+			_ffi.check(lib.rk_mcts_children_oh(h, oh.data_ptr(), _ffi.OH_STATES, _ffi.stream_ptr()))
+			p, v = self._n686(oh)
 		else:
 			_ffi.check(lib.rk_mcts_children_oh(h, oh.data_ptr(), _OH_CODES[oh.dtype], _ffi.stream_ptr()))
 			p, v = self.net(oh)
@@ -875,7 +955,8 @@ class MCTSBatch(DeepAgent):
 	def _begin(self, states: np.ndarray, max_states, max_sims, use_graph: bool):
 		_ffi.require_gpu()
 		self.net.eval()
-		states = np.ascontiguousarray(states, dtype=np.int8).reshape(self.n_trees, 20)
+		self._begin_repr()                     # 6x8x6: the trees grow in 20-byte form, the net gets 6x8x6 rows (_Net686)
+		states = self._roots20(states, self.n_trees)
 		if max_states is None:
 			max_states = self.capacity
 		self._budget = np.broadcast_to(np.asarray(max_states, dtype=np.int64), (self.n_trees,)).copy()      # what the caller asked for
@@ -883,13 +964,14 @@ class MCTSBatch(DeepAgent):
 		h, lib = self._engine(), _ffi.lib()
 		_ffi.check(lib.rk_mcts_reset(h, states.ctypes.data, ms.ctypes.data, self.c, self.nu, _ffi.stream_ptr()))
 		self._fs = self._from_states           # re-copied here if the net changed since the last search
-		if self._fs is not None:
+		rows_net = self._fs or self._n686
+		if rows_net is not None:
 			root_oh = torch.empty((self.n_trees, 20), dtype=torch.int8, device=gpu)
 			_ffi.check(lib.rk_mcts_roots_oh(h, root_oh.data_ptr(), _ffi.OH_STATES, _ffi.stream_ptr()))
-			p, v = _policy_value_f32(self._fs(root_oh))
+			p, v = _policy_value_f32(rows_net(root_oh))
 			oh = self._kept_buffer(_ffi.OH_STATES)
 			if oh is None:
-				oh = torch.from_numpy(cube.repeat_state(cube.get_solved(), 12 * self.n_trees)).to(gpu)
+				oh = torch.from_numpy(cube.repeat_state(_SOLVED20, 12 * self.n_trees)).to(gpu)
 		else:
 			oh_dtype = _oh_dtype(self.net)
 			root_oh = torch.empty((self.n_trees, 480), dtype=oh_dtype, device=gpu)
@@ -918,7 +1000,7 @@ class MCTSBatch(DeepAgent):
 		# simulation limit of the expand-ahead) --
 		# nothing of the trees, which live in device memory that rk_mcts_reset rewrites.  So the graph is KEPT from search to
 		# search and captured again only when one of those changes (grown or new engine, another net or fused copy).
-		key = (h.value, self._shape, self.c, self.nu, self.priors, self._max_sims, oh.data_ptr(), oh.dtype, _capture_key(self.net, self._fs))
+		key = (h.value, self._shape, self.c, self.nu, self.priors, self._max_sims, oh.data_ptr(), oh.dtype, _capture_key(self.net, self._fs or self._n686))
 		hit = self._graph_cache is not None and self._graph_cache[0] == key
 		if hit:
 			for _ in range(warm):                                      # real simulations: after them every tree is expanded ahead
@@ -937,7 +1019,7 @@ class MCTSBatch(DeepAgent):
 		self._graph = torch.cuda.CUDAGraph()
 		with torch.cuda.graph(self._graph, **CAPTURE):
 			self._step(oh, h, expand=False)
-		self._graph_cache = (key, self._graph, oh, (self.net, self._fs))      # the net stays alive with the graph that holds its addresses
+		self._graph_cache = (key, self._graph, oh, (self.net, self._fs or self._n686))      # the net stays alive with the graph that holds its addresses
 		self.captures += 1
 
 	def _net_half(self, first: int, count: int):
@@ -1091,6 +1173,7 @@ class MCTSBatch(DeepAgent):
 			out["P"][1:].ctypes.data, out["V"][1:].ctypes.data, out["N"][1:].ctypes.data, out["W"][1:].ctypes.data,
 			out["L"][1:].ctypes.data, _ffi.stream_ptr()))
 		out["leaves"] = out["leaves"].astype(bool)
+		out["states"] = self._states_out(out["states"], n)
 		out["n"] = n
 		return out
 
@@ -1154,6 +1237,7 @@ class MCTS(DeepAgent):
 			b = self._batch = MCTSBatch(self.net, self.c, 1, capacity=cap, nu=self.nu, priors=self.priors, search_graph=self.search_graph,
 			                            max_capacity=self.max_capacity)
 		b.net = self.net
+		self._is2024 = cube.get_is2024()
 		# the pool grows in place inside the batch engine while the budget is larger (agents.py:496-503)
 		solved = bool(b.search(np.asarray(state)[None], time_limit=time_limit, max_states=int(min(max_states, 2 ** 62)), poll=8,
 		                       use_graph=self.use_hipgraph)[0])
@@ -1169,7 +1253,7 @@ class MCTS(DeepAgent):
 	def _export(self) -> dict:
 		if self._arrays is None:
 			self._arrays = self._batch.tree_arrays(0) if self._batch is not None and self._n else dict(
-				states=np.zeros((1, 20), np.int8), neighbors=np.zeros((1, 12), np.int64), leaves=np.ones(1, bool),
+				states=np.zeros((1, 20) if self._is2024 else (1, 6, 8, 6), np.int8), neighbors=np.zeros((1, 12), np.int64), leaves=np.ones(1, bool),
 				P=np.zeros((1, 12)), V=np.zeros(1), N=np.zeros((1, 12), np.int64), W=np.zeros((1, 12)), L=np.zeros((1, 12)), n=0)
 		return self._arrays
 
@@ -1259,7 +1343,7 @@ class AStarBatch(DeepAgent):
 		if rows == 0:
 			values = self._no_values
 		else:
-			v = _sliced_value_forward(self._fs or self.net, oh[:min(len(oh), -(-rows // 64) * 64)], self.net_slice_rows or 12_288)
+			v = _sliced_value_forward(self._fs or self._n686 or self.net, oh[:min(len(oh), -(-rows // 64) * 64)], self.net_slice_rows or 12_288)
 			if isinstance(v, torch.Tensor) and v.is_cuda and v.dtype == torch.bfloat16 and v.is_contiguous():
 				values, vcode = v.detach().reshape(-1), _ffi.OH_BF16
 			else:
@@ -1280,7 +1364,7 @@ class AStarBatch(DeepAgent):
 		# torch's BatchNorm pick kernels for 16 384-row forwards that cost three times as much per row as for 12 000 rows)
 		K = 12 * self.expansions
 		rows = self.net_slice_rows or (K if K >= NET_SLICE_ROWS // 4 else (NET_SLICE_ROWS // K) * K)
-		v = _sliced_value_forward(self._fs or self.net, oh, rows)
+		v = _sliced_value_forward(self._fs or self._n686 or self.net, oh, rows)
 		if isinstance(v, torch.Tensor) and v.is_cuda and v.dtype == torch.bfloat16 and v.is_contiguous():
 			values, vcode = v.detach().reshape(-1), _ffi.OH_BF16        # a bf16 net's values go in as they are
 		else:
@@ -1304,7 +1388,8 @@ class AStarBatch(DeepAgent):
 		self.net.eval()
 		time_limit = time_limit or 1e10
 		S, K = self.n_searches, 12 * self.expansions
-		states = np.ascontiguousarray(states, dtype=np.int8).reshape(S, 20)
+		self._begin_repr()                     # 6x8x6: the searches run in 20-byte form, the net gets 6x8x6 rows (_Net686)
+		states = self._roots20(states, S)
 		budget = np.minimum(np.broadcast_to(np.asarray(self.capacity if max_states is None else max_states, dtype=np.int64), (S,)),
 		                    self.capacity).copy()
 		h, lib = self._engine(), _ffi.lib()
@@ -1312,8 +1397,8 @@ class AStarBatch(DeepAgent):
 		self._vcode = _ffi.OH_F32
 		_ffi.check(lib.rk_astarb_set_values_dtype(h, self._vcode, _ffi.stream_ptr()))
 		self._fs = self._from_states           # re-copied here if the net changed since the last search
-		if self._fs is not None:
-			oh, code = torch.from_numpy(cube.repeat_state(cube.get_solved(), S * K)).to(gpu), _ffi.OH_STATES
+		if self._fs is not None or self._n686 is not None:
+			oh, code = torch.from_numpy(cube.repeat_state(_SOLVED20, S * K)).to(gpu), _ffi.OH_STATES
 		else:
 			oh_dtype = _oh_dtype(self.net)
 			oh = torch.zeros((S * K, 480), dtype=oh_dtype, device=gpu)
@@ -1377,7 +1462,7 @@ class AStarBatch(DeepAgent):
 		parents, pact = np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int64)
 		_ffi.check(_ffi.lib().rk_astarb_export(self._h, search, 1, n, states[1:].ctypes.data, G[1:].ctypes.data, parents[1:].ctypes.data,
 		                                       pact[1:].ctypes.data, _ffi.stream_ptr()))
-		return states, G, parents, pact
+		return self._states_out(states, n), G, parents, pact
 
 	def __len__(self):
 		return int(self.status[:, 2].sum()) if self.status is not None else 0

@@ -289,6 +289,8 @@ class ShardedAStar(DeepAgent):
 	@no_grad
 	def search(self, state: np.ndarray, time_limit: float = None, max_states: int = None) -> bool:
 		_ffi.require_gpu()
+		if not cube.get_is2024():
+			raise NotImplementedError("ShardedAStar runs in the 20-byte representation only; search a 6x8x6 net with AStar or AStarBatch")
 		limits = (time_limit, max_states)
 		time_limit, max_states = self.reset(time_limit, max_states)
 		self.iterations, self.stop_reason = 0, "running"
@@ -450,6 +452,8 @@ class PartitionedMCTS:
 		self._queues = None
 
 	def search(self, states: np.ndarray, time_limit: float = None, max_states=None, max_sims: int = None, **kw) -> np.ndarray:
+		if not cube.get_is2024():
+			raise NotImplementedError("PartitionedMCTS runs in the 20-byte representation only; search a 6x8x6 net with MCTSBatch")
 		states = np.ascontiguousarray(states, np.int8).reshape(self.n_trees, 20)
 		per = -(-self.n_trees // self.tr.world)                              # trees per rank, rounded up: fixed-size rows
 		row = 4 + self.max_path                                             # solved, states, sims, path length, actions
