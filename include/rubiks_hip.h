@@ -304,6 +304,47 @@ long long rk_astar_export_open(rk_astar_t *h, double *h_costs, long long *h_indi
 /* The node indices the NEXT iteration pops, in heappop order (agents.py:238-239). */
 long long rk_astar_next_pops(rk_astar_t *h, long long *h_indices, size_t max_len, void *stream);
 
+/* ---- device-resident breadth-first search (agents.py:92-129) ---------------------------------------------------
+ * The node pool (int8 (C+1, 20), index 0 unused, root = 1), the parent index and action of every node, and an
+ * open-addressing table state -> index (the `self.states` dict, :103) live in HBM.  The FIFO queue (:104, :106, :121)
+ * is the pool itself in index order.  One iteration pops up to `pops` nodes and is four launches with no host
+ * synchronisation: 12-child fan-out in pop order with goal flag, membership test and in-batch first-occurrence
+ * election (:108-112); the prefix of first occurrences; the cut and the append (:119-121); bookkeeping.  The cut
+ * reproduces the check `len(self) < max_states` before every pop (:105) and the return of a solved child before it is
+ * stored (:113-118): results equal the reference's dict in insertion order.  The time limit is the caller's (checked
+ * between calls, not before every pop).  An engine handle is not thread-safe. */
+typedef struct rk_bfs rk_bfs_t;
+/* capacity: node pool size C (>= 2); pops: the most nodes one iteration pops (the grids are sized for it). */
+int rk_bfs_create(rk_bfs_t **out, size_t capacity, int pops);
+int rk_bfs_destroy(rk_bfs_t *h);
+/* self.states = {start: (None, None)}; queue = deque([start]) (:103-104), with max_states of :105.  The start state is
+ * a host 20-byte state that is not solved (:100 is the caller's).  Clears the table; synchronises. */
+int rk_bfs_reset(rk_bfs_t *h, const int8_t *h_start_state, long long max_states, void *stream);
+/* max_states of :105 for the iterations that follow.  A search that stopped at its budget goes on with a larger one, as
+ * if it had been started with it: the table is first rebuilt from the pool, dropping the tentative claims a cut inside
+ * a batch leaves behind.  Synchronises. */
+int rk_bfs_set_budget(rk_bfs_t *h, long long max_states, void *stream);
+/* `iterations` iterations of the while loop of :105-121, stream-ordered, no synchronisation; iterations after the
+ * search is done (won, out of budget, queue empty) are no-ops.  The caller keeps size + 12 * pops * iterations <= C
+ * (rk_bfs_grow); an iteration whose children might not fit is skipped and reported as error 1. */
+int rk_bfs_run(rk_bfs_t *h, int iterations, void *stream);
+/* Synchronises; h_status[8] = done, won, n_states (len(agent), :128-129), iterations, queue head index, stop reason
+ * (0 running, 1 won, 2 budget, 3 queue empty, 4 error), error, nodes the next iteration pops. */
+int rk_bfs_status(rk_bfs_t *h, long long *h_status, void *stream);
+/* Grows the node pool to new_capacity states in place between iterations: new arrays, device-to-device copies, one
+ * kernel that rebuilds the larger table.  The search continues where it stood.  Synchronises `stream`; RK_ECAPACITY
+ * when the device has no room (the engine is untouched then). */
+int rk_bfs_grow(rk_bfs_t *h, size_t new_capacity, void *stream);
+/* Number of stored states, len(self.states) (:128-129).  Synchronises. */
+long long rk_bfs_size(const rk_bfs_t *h);
+/* Rows [first, first+count) of the pool to HOST buffers (any may be NULL): states int8 (count, 20), parent index
+ * int64 and action int64 of every node -- the values of self.states (:120) as indices (0 for the root). */
+int rk_bfs_export(rk_bfs_t *h, size_t first, size_t count, int8_t *h_states, long long *h_parents, long long *h_actions,
+                  void *stream);
+/* The action queue of a won search (:114-117): the parents are walked on the device.  Returns its length or a negative
+ * error (RK_ESTATE: not won); writes at most max_len actions. */
+long long rk_bfs_path(rk_bfs_t *h, long long *h_actions, size_t max_len, void *stream);
+
 /* ---- batched A*: S independent searches in lock-step, no host synchronisation inside an iteration -------------
  * Every search is a complete rk_astar_* engine (agents.py:171-413: its own pool, hash table, open queue, counter block);
  * the batch launches the same kernels with a second grid dimension (search), so one iteration of ALL searches is the

@@ -82,6 +82,16 @@ SIGNATURES = {
 	"rk_astar_lookup": (C.c_longlong, [_vp, _vp, _vp]),
 	"rk_astar_export_open": (C.c_longlong, [_vp, _vp, _vp, _sz, _vp]),
 	"rk_astar_next_pops": (C.c_longlong, [_vp, _vp, _sz, _vp]),
+	"rk_bfs_create": (_i, [C.POINTER(_vp), _sz, _i]),
+	"rk_bfs_destroy": (_i, [_vp]),
+	"rk_bfs_reset": (_i, [_vp, _vp, C.c_longlong, _vp]),
+	"rk_bfs_set_budget": (_i, [_vp, C.c_longlong, _vp]),
+	"rk_bfs_run": (_i, [_vp, _i, _vp]),
+	"rk_bfs_status": (_i, [_vp, _vp, _vp]),
+	"rk_bfs_grow": (_i, [_vp, _sz, _vp]),
+	"rk_bfs_size": (C.c_longlong, [_vp]),
+	"rk_bfs_export": (_i, [_vp, _sz, _sz, _vp, _vp, _vp, _vp]),
+	"rk_bfs_path": (C.c_longlong, [_vp, _vp, _sz, _vp]),
 	"rk_astarb_create": (_i, [C.POINTER(_vp), _i, _sz, _i]),
 	"rk_astarb_destroy": (_i, [_vp]),
 	"rk_astarb_reset": (_i, [_vp, _vp, _vp, C.c_double, _vp]),

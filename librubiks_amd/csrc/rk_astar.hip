@@ -304,38 +304,19 @@ __device__ __forceinline__ void pop_select(const AstarDev &d, const int32_t *met
 __device__ __forceinline__ void child_of(const AstarDev &d, const u32x4 *s_act, int c, uint32_t s[5])
 {
 	const int i = c / 12;
-	load5(d.states + (size_t)d.exp_idx[i] * 5, s);
-	uint32_t tab[12];
-	load_action_table(s_act, (uint32_t)(c - 12 * i), tab);
-	move5(s, tab);
+	child_state(d.states, d.exp_idx[i], s_act, (uint32_t)(c - 12 * i), s);
 }
 
-// membership test + in-batch first-occurrence election through the hash table                    agents.py:286-295
+// membership test + in-batch first-occurrence election through the hash table (probe_elect)      agents.py:286-295
 // other(c', buf): state of batch position c' (recomputed or loaded).  Returns through seen / child_slot.
 template <typename Other>
 __device__ __forceinline__ void lookup_elect(const AstarDev &d, const uint32_t s[5], int c, Other other)
 {
-	uint32_t slot = hash_state(s) & d.mask;
-	for (;;) {
-		// (the claim IS the probe: an empty slot -- two children in three at N = 1000 are new states -- costs one round trip to the
-		//  table instead of a load and then the compare-and-swap; an occupied slot answers with its occupant either way)
-		const uint32_t e = atomicCAS(&d.table[slot], 0u, TENT | (uint32_t)c);
-		if (e == 0u) { d.seen[c] = 0; d.child_slot[c] = slot; return; }
-		if (e & TENT) {
-			uint32_t o[5];
-			other((int)(e & ~TENT), o);
-			if (((s[0] ^ o[0]) | (s[1] ^ o[1]) | (s[2] ^ o[2]) | (s[3] ^ o[3]) | (s[4] ^ o[4])) == 0u) {
-				atomicMin(&d.table[slot], TENT | (uint32_t)c);        // all claimants hold the same state: smallest position wins
-				d.seen[c] = 0; d.child_slot[c] = slot;
-				return;
-			}
-		} else if (equal5(s, d.states + (size_t)e * 5)) {
-			d.seen[c] = (int32_t)e;
-			atomicMin(&d.mark[e], (uint32_t)c);
-			return;
-		}
-		slot = (slot + 1) & d.mask;
-	}
+	uint32_t slot = 0;
+	const uint32_t e = probe_elect(d.table, d.mask, d.states, s, c, other, &slot);
+	if (e == 0u) { d.seen[c] = 0; d.child_slot[c] = slot; return; }
+	d.seen[c] = (int32_t)e;
+	atomicMin(&d.mark[e], (uint32_t)c);
 }
 
 // pop + gather + 12-child fan-out + goal flag + membership / election: one thread per child

@@ -1,4 +1,4 @@
-// Device-side pieces shared by the search engines (single A*, sharded A*, batched A*): queue records and their order,
+// Device-side pieces shared by the search engines (single A*, sharded A*, batched A*, breadth-first search): queue records and their order,
 // the state hash, order-preserving compaction inside a workgroup, binary search in a sorted run.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -63,6 +63,45 @@ __device__ __forceinline__ void load5(const uint32_t *p, uint32_t s[5])
 __device__ __forceinline__ bool equal5(const uint32_t a[5], const uint32_t *p)
 {
 	return ((a[0] ^ p[0]) | (a[1] ^ p[1]) | (a[2] ^ p[2]) | (a[3] ^ p[3]) | (a[4] ^ p[4])) == 0;
+}
+
+// child `a` of the stored state `parent` (s_act: the action tables staged in LDS by stage_action_tables)
+__device__ __forceinline__ void child_state(const uint32_t *states, int32_t parent, const u32x4 *s_act, uint32_t a, uint32_t s[5])
+{
+	load5(states + (size_t)parent * 5, s);
+	uint32_t tab[12];
+	load_action_table(s_act, a, tab);
+	move5(s, tab);
+}
+
+// Membership test + in-batch first-occurrence election through an open-addressing table of indices (T = mask + 1 slots,
+// linear probing).  Child c of the batch claims an empty slot as TENT | c; children that hold the same state settle on the
+// smallest position with atomicMin, so once every child has probed, a slot holds TENT | (first occurrence).  Returns the
+// stored index (> 0) of a state that is already in the table, or 0 when c took part in a claim; *slot_out is that slot.
+// other(c', buf): the state of batch position c' (recomputed or loaded).
+template <typename Other>
+__device__ __forceinline__ uint32_t probe_elect(uint32_t *table, uint32_t mask, const uint32_t *states, const uint32_t s[5], int c,
+                                                Other other, uint32_t *slot_out)
+{
+	uint32_t slot = hash_state(s) & mask;
+	for (;;) {
+		// (the claim IS the probe: an empty slot -- two children in three at N = 1000 are new states -- costs one round trip to the
+		//  table instead of a load and then the compare-and-swap; an occupied slot answers with its occupant either way)
+		const uint32_t e = atomicCAS(&table[slot], 0u, TENT | (uint32_t)c);
+		if (e == 0u) { *slot_out = slot; return 0u; }
+		if (e & TENT) {
+			uint32_t o[5];
+			other((int)(e & ~TENT), o);
+			if (((s[0] ^ o[0]) | (s[1] ^ o[1]) | (s[2] ^ o[2]) | (s[3] ^ o[3]) | (s[4] ^ o[4])) == 0u) {
+				atomicMin(&table[slot], TENT | (uint32_t)c);          // all claimants hold the same state: smallest position wins
+				*slot_out = slot;
+				return 0u;
+			}
+		} else if (equal5(s, states + (size_t)e * 5)) {
+			return e;
+		}
+		slot = (slot + 1) & mask;
+	}
 }
 
 // ---- order-preserving compaction across workgroups in ONE launch: tickets + look-back --------------------------------

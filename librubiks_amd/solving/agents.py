@@ -99,6 +99,23 @@ def _capture_key(net, fs) -> tuple:
 	return (id(net), bool(getattr(net, "training", False)), tuple(ptrs), id(fs))
 
 
+def _roots20(is2024: bool, states, n: int) -> np.ndarray:
+	"""A search's start states as (n, 20) int8 rows; in 6x8x6 mode converted (ValueError for a state that is not a legal cube)."""
+	if is2024:
+		return np.ascontiguousarray(states, dtype=np.int8).reshape(n, 20)
+	return np.ascontiguousarray(cube.as2024(np.asarray(states, dtype=np.int8).reshape(n, 6, 8, 6)))
+
+
+def _states_out(is2024: bool, states20: np.ndarray, n: int) -> np.ndarray:
+	"""An exported (rows, 20) array whose rows 1..n hold nodes, in the search's representation (other rows stay zero)."""
+	if is2024:
+		return states20
+	out = np.zeros((len(states20), 6, 8, 6), np.int8)
+	if n:
+		out[1:n + 1] = cube.as686(states20[1:n + 1])
+	return out
+
+
 class DeepAgent(Agent):
 	"""
 	An agent with a value/policy net.  `fused_first_layer` (False, True, "epilogue", "folded"; librubiks_amd.oh_linear)
@@ -156,19 +173,10 @@ class DeepAgent(Agent):
 		self._n686 = self._r686
 
 	def _roots20(self, states, n: int) -> np.ndarray:
-		"""The search's start states as (n, 20) int8 rows; in 6x8x6 mode converted (ValueError for a state that is not a legal cube)."""
-		if self._is2024:
-			return np.ascontiguousarray(states, dtype=np.int8).reshape(n, 20)
-		return np.ascontiguousarray(cube.as2024(np.asarray(states, dtype=np.int8).reshape(n, 6, 8, 6)))
+		return _roots20(self._is2024, states, n)
 
 	def _states_out(self, states20: np.ndarray, n: int) -> np.ndarray:
-		"""An exported (rows, 20) array whose rows 1..n hold nodes, in the representation of the last search (other rows stay zero)."""
-		if self._is2024:
-			return states20
-		out = np.zeros((len(states20), 6, 8, 6), np.int8)
-		if n:
-			out[1:n + 1] = cube.as686(states20[1:n + 1])
-		return out
+		return _states_out(self._is2024, states20, n)
 
 	@classmethod
 	def from_saved(cls, loc: str, use_best: bool, loader=None):
@@ -275,6 +283,157 @@ class BFS(Agent):
 
 	def __len__(self):
 		return len(self.states)
+
+
+class DeviceBFS(Agent):
+	"""
+	Breadth-first search (agents.py:92-129) with the whole search in HBM (engine rk_bfs_*, csrc/rk_bfs.hip): the node pool, the
+	parent and action of every node, and a hash table of the states seen.  The FIFO queue is the pool in index order.  One
+	iteration pops up to `pops` queued nodes, fans out their 12 children, tests them against the table, stores the first
+	occurrences of new states in order and applies the reference's stopping rules exactly: the state budget before every pop
+	(:105) and the return of the first solved child before it is stored (:111-118).  So the pool, len(agent) and the action
+	queue are the reference's, without a host round trip per child.  The host polls every `poll` iterations; the time limit is
+	checked there, not before every pop, so a time-limited search does not stop where the reference would.
+
+	`capacity` is the pool size a search starts with (default: what the budget needs, at most `default_capacity`).  Before an
+	iteration whose children might not fit, the pool doubles in place (rk_bfs_grow) up to `max_capacity`; at `max_capacity` the
+	search warns with `CapacityExhausted`, sets `capacity_exhausted` and returns False.  `grown` counts the growths.
+
+	The representation follows cube.get_is2024() when a search starts; the engine always runs on 20-byte states (the two forms
+	map one to one under the same moves), so `states` and `arrays()` convert on the way out.
+	"""
+	default_capacity = 8_000_000
+	max_capacity = 400_000_000
+	MAX_POPS = 1 << 22                      # rk_bfs_create's limit
+	MAX_CAPACITY = 0x3FFFFFF0
+
+	def __init__(self, pops: int = 16_384, capacity: int = None, max_capacity: int = None, poll: int = 8):
+		super().__init__()
+		if isinstance(pops, bool) or int(pops) != pops or not 1 <= int(pops) <= self.MAX_POPS:
+			raise ValueError(f"pops must be an integer in 1..{self.MAX_POPS}, got {pops!r}")
+		for name, v in (("capacity", capacity), ("max_capacity", max_capacity)):
+			if v is not None and (isinstance(v, bool) or int(v) != v or not 2 <= int(v) <= self.MAX_CAPACITY):
+				raise ValueError(f"{name} must be an integer in 2..{self.MAX_CAPACITY}, got {v!r}")
+		if isinstance(poll, bool) or int(poll) != poll or int(poll) < 1:
+			raise ValueError(f"poll must be a positive integer, got {poll!r}")
+		self.pops, self.poll = int(pops), int(poll)
+		self.capacity = int(capacity) if capacity is not None else None
+		if max_capacity is not None:
+			self.max_capacity = int(max_capacity)
+		self._h, self._h_cap = None, 0
+		self._n = 0
+		self._is2024 = True
+		self._cache = None
+		self.iterations = 0
+		self.popped = 0                     # queued nodes the last search popped (each has 12 children)
+		self.grown = 0
+		self.capacity_exhausted = False
+
+	def _engine(self, capacity: int):
+		if self._h is not None and self._h_cap >= capacity:
+			return self._h                  # (a pool that grew in an earlier search is kept: rk_bfs_reset clears its table)
+		self._free()
+		h = C.c_void_p()
+		_ffi.check(_ffi.lib().rk_bfs_create(C.byref(h), capacity, self.pops))
+		self._h, self._h_cap = h, capacity
+		return h
+
+	def _free(self):
+		if getattr(self, "_h", None) is not None:
+			_ffi.lib().rk_bfs_destroy(self._h)
+			self._h = None
+
+	def __del__(self):
+		try:
+			self._free()
+		except Exception:
+			pass
+
+	def _grow(self, h) -> bool:
+		if self._h_cap >= self.max_capacity:
+			self.capacity_exhausted = True
+			import warnings
+			warnings.warn(f"{self}: node pool of {self._h_cap} states cannot take the next iteration; raise max_capacity", CapacityExhausted)
+			return False
+		cap = min(2 * self._h_cap, self.max_capacity)
+		_ffi.check(_ffi.lib().rk_bfs_grow(h, cap, _ffi.stream_ptr()))
+		self._h_cap = cap
+		self.grown += 1
+		return True
+
+	@no_grad
+	def search(self, state: np.ndarray, time_limit: float = None, max_states: int = None) -> bool:
+		_ffi.require_gpu()
+		t0 = time.perf_counter()
+		time_limit, max_states = self.reset(time_limit, max_states)
+		self._n, self._cache, self.iterations, self.grown, self.capacity_exhausted = 0, None, 0, 0, False
+		self.popped = 0
+		self._is2024 = cube.get_is2024()
+		root = _roots20(self._is2024, state, 1)[0]          # ValueError for an illegal 6x8x6 state
+		if (root == _SOLVED20).all():
+			return True
+		lib, stream = _ffi.lib(), _ffi.stream_ptr()
+		K = 12 * self.pops
+		budget = int(min(max_states, 2 ** 31 - 1))
+		cap = self.capacity or min(budget + K, self.default_capacity)
+		cap = max(2, min(cap, self.max_capacity, self.MAX_CAPACITY))
+		h = self._engine(cap)
+		_ffi.check(lib.rk_bfs_reset(h, root.ctypes.data, budget, stream))
+		self._n = 1
+		status = (C.c_longlong * 8)()
+		_ffi.check(lib.rk_bfs_status(h, status, stream))
+		while not status[0]:
+			room = (self._h_cap - self._n) // K              # iterations the pool takes whatever they find
+			if room == 0:
+				if not self._grow(h):
+					return False
+				continue
+			# never launch past the budget: a search grows by at most K states per iteration, so it cannot reach its budget in
+			# fewer than (budget - len) // K iterations -- launch that many (at least one, at most `poll`), as AStar does
+			_ffi.check(lib.rk_bfs_run(h, max(1, min(self.poll, room, (budget - self._n) // K)), stream))
+			_ffi.check(lib.rk_bfs_status(h, status, stream))
+			self._n, self.iterations, self.popped = int(status[2]), int(status[3]), int(status[4]) - 1
+			if status[6]:
+				raise _ffi.RubiksHipError(f"BFS engine error code {int(status[6])}")
+			if not status[0] and time.perf_counter() - t0 >= time_limit:
+				return False
+		if status[1]:
+			path = (C.c_longlong * 4096)()
+			n = lib.rk_bfs_path(h, path, 4096, stream)
+			if n < 0:
+				_ffi.check(int(n))
+			self.action_queue = deque(int(a) for a in path[:n])
+			return True
+		return False
+
+	def arrays(self):
+		"""(states, parents, actions) of nodes 1 .. len(agent) in index order = the reference's dict in insertion order: states
+		(n, 20) int8, or (n, 6, 8, 6) in 6x8x6 mode; parents int64 node indices (0 for the start); actions int64 (-1 for the start)."""
+		if self._cache is None:
+			n = self._n
+			states = np.zeros((n + 1, 20), np.int8)
+			parents, actions = np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int64)
+			if n and self._h is not None:
+				_ffi.check(_ffi.lib().rk_bfs_export(self._h, 1, n, states[1:].ctypes.data, parents[1:].ctypes.data,
+				                                     actions[1:].ctypes.data, _ffi.stream_ptr()))
+			if n:
+				actions[1] = -1
+			self._cache = (_states_out(self._is2024, states, n)[1:], parents[1:], actions[1:])
+		return self._cache
+
+	@property
+	def states(self) -> dict:
+		"""The reference's `self.states` (agents.py:103, :120): state bytes -> (predecessor bytes, action), (None, None) for the
+		start, in insertion order.  Built on the host from arrays(): meant for small searches."""
+		states, parents, actions = self.arrays()
+		keys = [s.tobytes() for s in states]
+		return {k: (None, None) if p == 0 else (keys[p - 1], int(a)) for k, p, a in zip(keys, parents.tolist(), actions.tolist())}
+
+	def __len__(self):
+		return self._n
+
+	def __str__(self):
+		return f"Breadth-first search (device, pops={self.pops})"
 
 
 class PolicySearch(DeepAgent):
