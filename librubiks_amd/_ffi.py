@@ -182,6 +182,33 @@ def check(rc: int):
 		raise RubiksHipError(f"librubiks_hip error {rc}: {lib().rk_last_error().decode()}")
 
 
+class Owner:
+	"""
+	Owns one object of the library: made by an `rk_*_create` entry point, destroyed by its `rk_*_destroy` exactly once.  `_h` is
+	the handle the other entry points take, None while there is no object (before the first `_create`, after `_free`).
+	"""
+	_h = None
+	_destroy = None
+
+	def _create(self, create: str, destroy: str, *args):
+		self._free()
+		h = C.c_void_p()
+		check(getattr(lib(), create)(C.byref(h), *args))
+		self._h, self._destroy = h, destroy
+		return h
+
+	def _free(self):
+		h, self._h = self._h, None
+		if h is not None:
+			getattr(lib(), self._destroy)(h)
+
+	def __del__(self):
+		try:
+			self._free()
+		except Exception:
+			pass
+
+
 _gpu_seen = False
 
 

@@ -21,8 +21,6 @@ the Linear layers behind them: the same function in exact arithmetic, different 
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from librubiks_amd import _ffi
@@ -34,7 +32,7 @@ _ROUTES = {"gather": _ffi.OHL_GATHER, "mfma": _ffi.OHL_MFMA, "mfma_direct": _ffi
 _CODES = {torch.float32: _ffi.OH_F32, torch.bfloat16: _ffi.OH_BF16}
 
 
-class OhLinear:
+class OhLinear(_ffi.Owner):
 	def __init__(self, linear: torch.nn.Linear, route: str = None):
 		if linear.in_features != 480:
 			raise ValueError("the fused layer replaces nn.Linear(480, H) behind the 20-byte representation's one-hot")
@@ -45,18 +43,8 @@ class OhLinear:
 		# the exact route for float32 nets, the matrix cores for bf16 nets, unless told otherwise
 		self.route = route or ("gather" if w.dtype == torch.float32 else "mfma")
 		b = linear.bias.detach().to(w.dtype).contiguous() if linear.bias is not None else None
-		h = C.c_void_p()
-		_ffi.check(_ffi.lib().rk_ohl_create(C.byref(h), w.contiguous().data_ptr(), _CODES[w.dtype], b.data_ptr() if b is not None else None,
-		                                    self.out_features, _ffi.stream_ptr()))
-		self._h = h
-
-	def __del__(self):
-		try:
-			if getattr(self, "_h", None) is not None:
-				_ffi.lib().rk_ohl_destroy(self._h)
-				self._h = None
-		except Exception:
-			pass
+		self._create("rk_ohl_create", "rk_ohl_destroy", w.contiguous().data_ptr(), _CODES[w.dtype], b.data_ptr() if b is not None else None,
+		             self.out_features, _ffi.stream_ptr())
 
 	def set_epilogue(self, activation: torch.nn.Module = None, batchnorm: torch.nn.BatchNorm1d = None):
 		"""

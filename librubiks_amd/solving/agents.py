@@ -21,6 +21,10 @@ import torch
 
 from librubiks_amd import gpu, no_grad, _ffi
 from librubiks_amd import cube
+from librubiks_amd.solving import _engine as eng
+from librubiks_amd.solving._engine import (  # noqa: F401  (callers import these names from here)
+	CAPTURE, NET_SLICE_ROWS, CapacityExhausted, OH_CODES as _OH_CODES, SOLVED20 as _SOLVED20, oh_dtype as _oh_dtype,
+	sliced_value_forward as _sliced_value_forward)
 
 
 class Agent:
@@ -81,24 +85,6 @@ def _net_signature(net):
 	return tuple(sig)
 
 
-#: How every search step is captured: errors of the capture are judged per THREAD.  In a process with a torch.distributed process group
-#: the NCCL (RCCL) watchdog thread polls events while the main thread captures; under the default "global" mode such a call from another
-#: thread invalidates the capture -- a sporadic failure of the first search of a rank (seen once in the round-5 test runs).
-CAPTURE = {"capture_error_mode": "thread_local"}
-
-
-def _capture_key(net, fs) -> tuple:
-	"""What a captured search step holds of the net: the module, its mode, and the storage of every parameter and buffer (their
-	VALUES are read at replay time, so in-place training between searches keeps a captured step valid; the fused copy `fs` is
-	rebuilt -- a new object -- whenever the values change)."""
-	ptrs = []
-	for get in ("parameters", "buffers"):
-		it = getattr(net, get, None)
-		if callable(it):
-			ptrs += [(t.data_ptr(), t.dtype) for t in it()]
-	return (id(net), bool(getattr(net, "training", False)), tuple(ptrs), id(fs))
-
-
 def _roots20(is2024: bool, states, n: int) -> np.ndarray:
 	"""A search's start states as (n, 20) int8 rows; in 6x8x6 mode converted (ValueError for a state that is not a legal cube)."""
 	if is2024:
@@ -135,6 +121,7 @@ class DeepAgent(Agent):
 		self._is2024 = True                # the representation of the last search (cube.get_is2024() when it began); its exports follow it
 		self._r686 = None                  # the kept 6x8x6 adapter of this agent's net (_Net686), the same object from search to search
 		self._n686 = None                  # ... while the running search is in 6x8x6 mode, else None
+		self._forward = None               # what the running search evaluates: `_fs`, `_n686` or the net itself (_begin_net)
 		self.net = net
 
 	@property
@@ -172,6 +159,19 @@ class DeepAgent(Agent):
 			self._r686 = _Net686(self._net)
 		self._n686 = self._r686
 
+	def _begin_net(self):
+		"""A search's view of the net, taken when it starts: fixes the representation, re-copies the fused form if the net changed
+		since the last search, and returns (forward, reads_states, code): the callable the search evaluates (`self._forward`, which
+		the hot loops use), whether it reads the engine's 20-byte rows (the fused copy, the 6x8x6 adapter) rather than a 480-wide
+		one-hot, and the RK_OH_* code of the batch the engine is to write for it."""
+		self._begin_repr()
+		self._fs = self._from_states
+		rows_net = self._fs or self._n686      # the net as a function of 20-byte rows, or None
+		self._forward = rows_net or self._net
+		if rows_net is not None:
+			return self._forward, True, _ffi.OH_STATES
+		return self._forward, False, _OH_CODES[_oh_dtype(self._net)]
+
 	def _roots20(self, states, n: int) -> np.ndarray:
 		return _roots20(self._is2024, states, n)
 
@@ -182,9 +182,6 @@ class DeepAgent(Agent):
 	def from_saved(cls, loc: str, use_best: bool, loader=None):
 		"""agents.py:72-76."""
 		return cls(_load_net(loc, use_best, loader))
-
-
-from librubiks_amd.cube.cube import _solved2024 as _SOLVED20  # noqa: E402  (the 20-byte solved state, whatever the repr)
 
 
 class _Net686:
@@ -285,7 +282,7 @@ class BFS(Agent):
 		return len(self.states)
 
 
-class DeviceBFS(Agent):
+class DeviceBFS(Agent, _ffi.Owner):
 	"""
 	Breadth-first search (agents.py:92-129) with the whole search in HBM (engine rk_bfs_*, csrc/rk_bfs.hip): the node pool, the
 	parent and action of every node, and a hash table of the states seen.  The FIFO queue is the pool in index order.  One
@@ -332,28 +329,12 @@ class DeviceBFS(Agent):
 	def _engine(self, capacity: int):
 		if self._h is not None and self._h_cap >= capacity:
 			return self._h                  # (a pool that grew in an earlier search is kept: rk_bfs_reset clears its table)
-		self._free()
-		h = C.c_void_p()
-		_ffi.check(_ffi.lib().rk_bfs_create(C.byref(h), capacity, self.pops))
-		self._h, self._h_cap = h, capacity
-		return h
-
-	def _free(self):
-		if getattr(self, "_h", None) is not None:
-			_ffi.lib().rk_bfs_destroy(self._h)
-			self._h = None
-
-	def __del__(self):
-		try:
-			self._free()
-		except Exception:
-			pass
+		self._h_cap = capacity
+		return self._create("rk_bfs_create", "rk_bfs_destroy", capacity, self.pops)
 
 	def _grow(self, h) -> bool:
 		if self._h_cap >= self.max_capacity:
-			self.capacity_exhausted = True
-			import warnings
-			warnings.warn(f"{self}: node pool of {self._h_cap} states cannot take the next iteration; raise max_capacity", CapacityExhausted)
+			eng.pool_exhausted(self, self._h_cap, "cannot take the next iteration")
 			return False
 		cap = min(2 * self._h_cap, self.max_capacity)
 		_ffi.check(_ffi.lib().rk_bfs_grow(h, cap, _ffi.stream_ptr()))
@@ -388,9 +369,7 @@ class DeviceBFS(Agent):
 				if not self._grow(h):
 					return False
 				continue
-			# never launch past the budget: a search grows by at most K states per iteration, so it cannot reach its budget in
-			# fewer than (budget - len) // K iterations -- launch that many (at least one, at most `poll`), as AStar does
-			_ffi.check(lib.rk_bfs_run(h, max(1, min(self.poll, room, (budget - self._n) // K)), stream))
+			_ffi.check(lib.rk_bfs_run(h, eng.burst(min(self.poll, room), budget - self._n, K), stream))
 			_ffi.check(lib.rk_bfs_status(h, status, stream))
 			self._n, self.iterations, self.popped = int(status[2]), int(status[3]), int(status[4]) - 1
 			if status[6]:
@@ -398,11 +377,7 @@ class DeviceBFS(Agent):
 			if not status[0] and time.perf_counter() - t0 >= time_limit:
 				return False
 		if status[1]:
-			path = (C.c_longlong * 4096)()
-			n = lib.rk_bfs_path(h, path, 4096, stream)
-			if n < 0:
-				_ffi.check(int(n))
-			self.action_queue = deque(int(a) for a in path[:n])
+			self.action_queue = eng.read_path(lib.rk_bfs_path, h)
 			return True
 		return False
 
@@ -542,9 +517,6 @@ class EGVM(DeepAgent):
 		return f"EGVM (e={self.epsilon}, w={self.workers}, d={self.depth})"
 
 
-_OH_CODES = {torch.float32: _ffi.OH_F32, torch.float16: _ffi.OH_F16, torch.bfloat16: _ffi.OH_BF16}
-
-
 def _load_net(loc: str, use_best: bool, loader=None):
 	"""The value/policy net of a saved model folder (reference: DeepAgent.from_saved, agents.py:72-75)."""
 	if loader is not None:
@@ -557,78 +529,7 @@ def _load_net(loc: str, use_best: bool, loader=None):
 	return Model.load(loc, load_best=use_best).to(gpu)
 
 
-def _oh_dtype(net) -> torch.dtype:
-	"""
-	The dtype the net wants its one-hot input in: that of its first floating-point parameter (a bf16/fp16 net gets a
-	bf16/fp16 one-hot straight from the kernel -- 0/1 are exact, and no cast kernel or float32 copy is needed);
-	float32 for anything that is not a torch module.
-	"""
-	params = getattr(net, "parameters", None)
-	if callable(params):
-		for prm in params():
-			if prm.dtype in _OH_CODES:
-				return prm.dtype
-	return torch.float32
-
-
-def _has_f32_weights(net) -> bool:
-	"""True for a torch module whose first floating-point parameter is float32 (a forward pass on thousands of rows then
-	costs milliseconds); False for low-precision nets and for parameter-free heuristics."""
-	params = getattr(net, "parameters", None)
-	if callable(params):
-		for prm in params():
-			if prm.dtype in _OH_CODES:
-				return prm.dtype == torch.float32
-	return False
-
-
-def _value_f32(out) -> torch.Tensor:
-	"""The net's value head as a contiguous float32 vector on the GPU."""
-	if isinstance(out, (list, tuple)):
-		out = out[-1]
-	return out.detach().to(device=gpu, dtype=torch.float32).reshape(-1).contiguous()
-
-
-def _values_for_engine(h, out) -> torch.Tensor:
-	"""
-	The net's value head as the A* engine takes it: a bfloat16 net's values go in as they are (the engine widens them,
-	exactly; rk_astar_set_values_dtype), anything else as a contiguous float32 vector.  Tells the engine which it is.
-	"""
-	v = out[-1] if isinstance(out, (list, tuple)) else out
-	if isinstance(v, torch.Tensor) and v.is_cuda and v.dtype == torch.bfloat16 and v.is_contiguous():
-		v, code = v.detach().reshape(-1), _ffi.OH_BF16
-	else:
-		v, code = _value_f32(v), _ffi.OH_F32
-	_ffi.check(_ffi.lib().rk_astar_set_values_dtype(h, code))
-	return v
-
-
-#: Rows per net forward.  A forward on B rows streams B x 4096 activations per layer through every elementwise kernel
-#: of the torch module (Linear, ELU, BatchNorm ...); while a slice's activations fit the 256 MiB Infinity Cache those
-#: kernels run out of it, beyond that every one of them goes to HBM: 64 searches x 12 000 rows in ONE forward ran four
-#: times slower PER ROW than 12 000-row forwards (profiles/r02_astar_batch.json: batch 0.22x of sequential at N = 1000).
-#: 16 384 rows x 4 096 x 2 B = 134 MB (bf16).  The reference slices its own large forwards the same way (train.py:301-311).
-NET_SLICE_ROWS = 16_384
-
-
-def _value_of(out):
-	return out[-1] if isinstance(out, (list, tuple)) else out
-
-
-def _sliced_value_forward(forward, rows: torch.Tensor, max_rows: int = None):
-	"""The value head of `forward` on `rows`, evaluated in slices of at most `max_rows` rows (see NET_SLICE_ROWS)."""
-	max_rows = max_rows or NET_SLICE_ROWS
-	n = len(rows)
-	if n <= max_rows:
-		return _value_of(forward(rows, policy=False, value=True))
-	return torch.cat([_value_of(forward(rows[i:i + max_rows], policy=False, value=True)).reshape(-1) for i in range(0, n, max_rows)])
-
-
-class CapacityExhausted(RuntimeWarning):
-	"""A search that was limited only by time stopped because its node pool was full (the reference grows its arrays)."""
-
-
-class AStar(DeepAgent):
+class AStar(DeepAgent, _ffi.Owner):
 	"""
 	Batch weighted A* (agents.py:171-413): expands the `expansions` cheapest open nodes per iteration,
 	cost = lambda_ * G + (-value).  Same results as the reference (index numbering, G, parents, action_queue)
@@ -689,23 +590,12 @@ class AStar(DeepAgent):
 	def _engine(self, capacity: int):
 		if self._h is not None and self._h_cap >= capacity and self._h_expansions == self.expansions:
 			return self._h
-		self._free()
-		h = C.c_void_p()
-		_ffi.check(_ffi.lib().rk_astar_create(C.byref(h), capacity, self.expansions))
-		self._h, self._h_cap, self._h_expansions = h, capacity, self.expansions      # (an engine is built for one batch size)
-		return h
+		self._h_cap, self._h_expansions = capacity, self.expansions                  # (an engine is built for one batch size)
+		return self._create("rk_astar_create", "rk_astar_destroy", capacity, self.expansions)
 
 	def _free(self):
 		self._graph_cache = None              # it holds the engine's addresses
-		if getattr(self, "_h", None) is not None:
-			_ffi.lib().rk_astar_destroy(self._h)
-			self._h = None
-
-	def __del__(self):
-		try:
-			self._free()
-		except Exception:
-			pass
+		super()._free()
 
 	# -- search ---------------------------------------------------------------------------------------------
 	def reset(self, time_limit: float, max_states: int):
@@ -721,13 +611,14 @@ class AStar(DeepAgent):
 	def _iteration(self, h, oh, code):
 		lib = _ffi.lib()
 		ev = self.profile_events           # measurement aid (bench.py): HIP events between the three parts of an iteration
-		if ev is not None:
-			marks = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+		if ev is not None:                 # (tested inline: this runs once per eager iteration, which is host-bound at small N)
+			marks = eng.events(4)
 			marks[0].record()
 		_ffi.check(lib.rk_astar_step_expand(h, oh.data_ptr(), code, _ffi.stream_ptr()))
 		if ev is not None:
 			marks[1].record()
-		values = _values_for_engine(h, _sliced_value_forward(self._fs or self._n686 or self.net, oh))
+		values, vcode = eng.engine_values(_sliced_value_forward(self._forward, oh))
+		_ffi.check(lib.rk_astar_set_values_dtype(h, vcode))
 		self._keep = values                # the commit kernels read it after this call returns
 		if ev is not None:
 			marks[2].record()
@@ -747,18 +638,13 @@ class AStar(DeepAgent):
 		K = 12 * self.expansions
 		cap = max(int(min(max_states, self.capacity or self.default_capacity)), K + 2)
 		lib = _ffi.lib()
-		self._begin_repr()                     # 6x8x6: the engine runs on the root's 20-byte form, the net gets 6x8x6 rows
+		forward, _, code = self._begin_net()   # 6x8x6: the engine runs on the root's 20-byte form, the net gets 6x8x6 rows
 		root = self._roots20(state, 1)[0]
-		self._fs = self._from_states           # re-copied here if the net changed since the last search
-		rows_net = self._fs or self._n686      # the net as a function of 20-byte rows, or None
-		code = _ffi.OH_STATES if rows_net is not None else _OH_CODES[_oh_dtype(self.net)]
+		# `cached` holds the kept graph until this search returns.  When the engine below is re-made for a larger pool, `_free` drops the
+		# cache; a graph that died there would hand its private memory pool back before the new capture, whose empty_cache() then
+		# returns it to the driver and whose allocations fetch it again (profiles/r07_engine_plumbing_ab.json).
 		cached = self._graph_cache
-		if cached is not None and self.use_hipgraph and cached[2][1] == code and len(cached[2][0]) == K:
-			oh = cached[2][0]                  # the buffer the kept graph was captured on (rows are rewritten before they are read)
-		elif rows_net is not None:
-			oh = torch.from_numpy(cube.repeat_state(_SOLVED20, K)).to(gpu)      # (K, 20) int8: valid codes everywhere
-		else:
-			oh = torch.zeros((K, 480), dtype=_oh_dtype(self.net), device=gpu)
+		oh = eng.net_batch(K, code, cached[2] if cached is not None and self.use_hipgraph else None)
 		status = (C.c_longlong * 8)()
 		h = self._engine(cap)
 		cap = self._h_cap
@@ -766,7 +652,7 @@ class AStar(DeepAgent):
 		_ffi.check(lib.rk_astar_set_budget(h, int(min(max_states, cap)), _ffi.stream_ptr()))
 		self._root, self._n, self._cache = state.copy(), 1, None
 		self.iterations, self.pops, self.grown = 0, [], 0
-		exact = self.exact_batch if self.exact_batch is not None else (K >= 2048 and _has_f32_weights(self.net))
+		exact = self.exact_batch if self.exact_batch is not None else (K >= 2048 and eng.has_f32_weights(self.net))
 		exact = exact and not self.use_hipgraph and not self.record_pops
 		info = (C.c_longlong * 5)()
 		while True:                                                  # one round per pool size: the pool grows in place below
@@ -777,21 +663,10 @@ class AStar(DeepAgent):
 				# rewrites.  So the graph is KEPT from search to search and captured again only when one of those changes (a grown
 				# or new engine, another net or fused copy, another lambda): capturing cost every search about 7 ms
 				# (profiles/NOTES.md section 7), as much as a hundred iterations.
-				key = (h.value, cap, float(self.lambda_), code, oh.data_ptr(), _capture_key(self.net, rows_net))
-				if self._graph_cache is not None and self._graph_cache[0] == key:
-					graph = self._graph_cache[1]
-				else:
-					self._graph_cache = None
-					side = torch.cuda.Stream()
-					side.wait_stream(torch.cuda.current_stream())
-					with torch.cuda.stream(side):
-						self._iteration(h, oh, code)               # a real iteration; also warms the allocator
-					torch.cuda.current_stream().wait_stream(side)
-					graph = torch.cuda.CUDAGraph()                 # (captured again after a growth: it holds the pool's addresses)
-					with torch.cuda.graph(graph, **CAPTURE):
-						self._iteration(h, oh, code)
-					self._graph_cache = (key, graph, (oh, code), (self.net, rows_net))     # the net stays alive with the graph that holds its addresses
-					self.captures += 1
+				# The warm-up is a real iteration; after a growth the step is captured again (the key holds the pool's size).
+				key = (h.value, cap, float(self.lambda_), code, oh.data_ptr(), eng.capture_key(self.net, forward))
+				step = lambda: self._iteration(h, oh, code)            # noqa: E731
+				graph, _ = eng.kept_graph(self, key, step, step, oh, ((self.net, forward),))
 			budget = int(min(max_states, cap))
 			done = won = err = solved_idx = 0
 			while exact:
@@ -807,13 +682,13 @@ class AStar(DeepAgent):
 				values = None
 				if n_new:
 					_ffi.check(lib.rk_astar_new_states_oh(h, oh.data_ptr(), code, _ffi.stream_ptr()))
-					values = _values_for_engine(h, _sliced_value_forward(self._fs or self._n686 or self.net, oh[:n_new]))
+					values, vcode = eng.engine_values(_sliced_value_forward(forward, oh[:n_new]))
+					_ffi.check(lib.rk_astar_set_values_dtype(h, vcode))
 				_ffi.check(lib.rk_astar_commit(h, values.data_ptr() if values is not None else None, _ffi.stream_ptr()))
 				if time.perf_counter() - t0 >= time_limit:
 					break
 			while not exact:
-				# never run past the state budget: a search grows by at most K states per iteration
-				poll = 1 if self.record_pops else max(1, min(self.poll, (budget - self._n) // K))
+				poll = 1 if self.record_pops else eng.burst(self.poll, budget - self._n, K)
 				for _ in range(poll):
 					if self.record_pops:
 						head = np.zeros(self.expansions, np.int64)
@@ -832,11 +707,7 @@ class AStar(DeepAgent):
 					break
 			self._cache = None
 			if won:
-				path = (C.c_longlong * 4096)()
-				n = lib.rk_astar_path(h, solved_idx, path, 4096, _ffi.stream_ptr())
-				if n < 0:
-					_ffi.check(int(n))
-				self.action_queue = deque(int(a) for a in path[:n])
+				self.action_queue = eng.read_path(lib.rk_astar_path, h, solved_idx)
 				return True
 			# out of budget, out of time, or nothing left to expand
 			pool_full = done and self._n + K > cap and lib.rk_astar_open_size(h) > 0
@@ -845,9 +716,7 @@ class AStar(DeepAgent):
 			# the pool, not the caller's budget, ended the search: grow it like the reference's increase_stack_size
 			# (agents.py:396-402) -- in place, the search goes on where it stood -- or say so
 			if cap >= self.max_capacity:
-				self.capacity_exhausted = True
-				import warnings
-				warnings.warn(f"{self}: node pool of {cap} states is full with time left; raise max_capacity", CapacityExhausted)
+				eng.pool_exhausted(self, cap)
 				return False
 			cap = min(2 * cap, self.max_capacity)
 			_ffi.check(lib.rk_astar_grow(h, cap, _ffi.stream_ptr()))
@@ -860,14 +729,7 @@ class AStar(DeepAgent):
 		if self._cache is None:
 			n = self._n
 			rows = max(n + 1, 1000)            # the reference's arrays start with 1000 rows (agents.py:385-394); its tests write G of a reset agent
-			states = np.zeros((rows, 20), np.int8)
-			G = np.zeros(rows, np.float64)
-			parents = np.zeros(rows, np.int64)
-			pact = np.zeros(rows, np.int64)
-			if n and self._h is not None:
-				_ffi.check(_ffi.lib().rk_astar_export(
-					self._h, 1, n, states[1:].ctypes.data, G[1:].ctypes.data, parents[1:].ctypes.data, pact[1:].ctypes.data,
-					_ffi.stream_ptr()))
+			states, G, parents, pact = eng.export_pool(_ffi.lib().rk_astar_export if self._h is not None else None, (self._h,), n, rows)
 			self._cache = (self._states_out(states, n), G, parents, pact)
 		return self._cache
 
@@ -939,7 +801,7 @@ def _policy_value_f32(out):
 PRIORS = ("kernel", "torch", "reference")
 
 
-class MCTSBatch(DeepAgent):
+class MCTSBatch(DeepAgent, _ffi.Owner):
 	"""
 	T independent Monte Carlo tree searches advanced in lock-step on the GPU (engine rk_mcts_*).  Each tree follows
 	the reference's MCTS exactly (agents.py:415-645): same node numbering, neighbors, P, V, N, W, L and action queue
@@ -999,23 +861,13 @@ class MCTSBatch(DeepAgent):
 	def _engine(self):
 		shape = (self.n_trees, self.capacity, self.max_path)
 		if self._h is None or self._shape != shape:
-			self._free()
-			h = C.c_void_p()
-			_ffi.check(_ffi.lib().rk_mcts_create(C.byref(h), *shape))
-			self._h, self._shape = h, shape
+			self._create("rk_mcts_create", "rk_mcts_destroy", *shape)
+			self._shape = shape
 		return self._h
 
 	def _free(self):
 		self._graph_cache = None              # it holds the engine's addresses
-		if getattr(self, "_h", None) is not None:
-			_ffi.lib().rk_mcts_destroy(self._h)
-			self._h = None
-
-	def __del__(self):
-		try:
-			self._free()
-		except Exception:
-			pass
+		super()._free()
 
 	_ERRORS = {1: "path longer than max_path", 2: "broken neighbour link", 3: "backup without a pending expansion (rk_mcts_expand missing from the step)"}
 
@@ -1030,15 +882,6 @@ class MCTSBatch(DeepAgent):
 		if self.on_poll is not None:
 			self.on_poll(st)
 		return st
-
-	def _kept_buffer(self, code: int):
-		"""The batch buffer of the kept graph, if it fits this search (the step rewrites its rows before the net reads them)."""
-		kept = self._graph_cache
-		if kept is None:
-			return None
-		oh = kept[2]
-		want = torch.int8 if code == _ffi.OH_STATES else {v: k for k, v in _OH_CODES.items()}[code]
-		return oh if len(oh) == 12 * self.n_trees and oh.dtype == want else None
 
 	def _step(self, oh, h, expand: bool = True):
 		lib = _ffi.lib()
@@ -1062,13 +905,13 @@ class MCTSBatch(DeepAgent):
 			# (agents.py:551) runs inside the backup kernel
 			self._keep = (p, v)        # the kernels read these after this call returns
 			if ev is not None:
-				pair = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+				pair = eng.events(2)
 				pair[0].record()
 			_ffi.check(lib.rk_mcts_backup_select_logits(h, p.data_ptr(), p.stride(0), v.data_ptr(), v.reshape(len(p), -1).stride(0),
 			                                            _OH_CODES[p.dtype], _ffi.stream_ptr()))
 			if ev is not None:
 				pair[1].record()
-				ev.append(pair)
+				ev.append(tuple(pair))
 			return
 		if self.priors == "reference":
 			# agents.py:551-552 to the letter: `p.cpu().softmax(dim=1)` -- the HOST's softmax of the logits, the same CPU kernel on
@@ -1114,7 +957,7 @@ class MCTSBatch(DeepAgent):
 	def _begin(self, states: np.ndarray, max_states, max_sims, use_graph: bool):
 		_ffi.require_gpu()
 		self.net.eval()
-		self._begin_repr()                     # 6x8x6: the trees grow in 20-byte form, the net gets 6x8x6 rows (_Net686)
+		forward, reads_states, code = self._begin_net()      # 6x8x6: the trees grow in 20-byte form, the net gets 6x8x6 rows (_Net686)
 		states = self._roots20(states, self.n_trees)
 		if max_states is None:
 			max_states = self.capacity
@@ -1122,23 +965,11 @@ class MCTSBatch(DeepAgent):
 		ms = np.minimum(self._budget, self.capacity)
 		h, lib = self._engine(), _ffi.lib()
 		_ffi.check(lib.rk_mcts_reset(h, states.ctypes.data, ms.ctypes.data, self.c, self.nu, _ffi.stream_ptr()))
-		self._fs = self._from_states           # re-copied here if the net changed since the last search
-		rows_net = self._fs or self._n686
-		if rows_net is not None:
-			root_oh = torch.empty((self.n_trees, 20), dtype=torch.int8, device=gpu)
-			_ffi.check(lib.rk_mcts_roots_oh(h, root_oh.data_ptr(), _ffi.OH_STATES, _ffi.stream_ptr()))
-			p, v = _policy_value_f32(rows_net(root_oh))
-			oh = self._kept_buffer(_ffi.OH_STATES)
-			if oh is None:
-				oh = torch.from_numpy(cube.repeat_state(_SOLVED20, 12 * self.n_trees)).to(gpu)
-		else:
-			oh_dtype = _oh_dtype(self.net)
-			root_oh = torch.empty((self.n_trees, 480), dtype=oh_dtype, device=gpu)
-			_ffi.check(lib.rk_mcts_roots_oh(h, root_oh.data_ptr(), _OH_CODES[oh_dtype], _ffi.stream_ptr()))
-			p, v = _policy_value_f32(self.net(root_oh))                  # agents.py:470-473: the root's softmax runs on the device
-			oh = self._kept_buffer(_OH_CODES[oh_dtype])
-			if oh is None:
-				oh = torch.empty((12 * self.n_trees, 480), dtype=oh_dtype, device=gpu)
+		root_oh = torch.empty((self.n_trees, 20 if reads_states else 480), dtype=eng.OH_DTYPES[code], device=gpu)
+		_ffi.check(lib.rk_mcts_roots_oh(h, root_oh.data_ptr(), code, _ffi.stream_ptr()))
+		p, v = _policy_value_f32(forward(root_oh))                       # agents.py:470-473: the root's softmax runs on the device
+		# the step's batch: the kept graph's buffer if it fits; a new one-hot stays uninitialised (the step writes every row it reads)
+		oh = eng.net_batch(12 * self.n_trees, code, self._graph_cache[2] if self._graph_cache is not None else None, zeros=False)
 		_ffi.check(lib.rk_mcts_set_root_pv(h, p.data_ptr(), v.data_ptr(), _ffi.stream_ptr()))
 		# every backup + select launch also expands the leaf it found, while another simulation is to follow
 		_ffi.check(lib.rk_mcts_set_expand_ahead(h, int(max_sims) if max_sims is not None else -1))
@@ -1159,27 +990,16 @@ class MCTSBatch(DeepAgent):
 		# simulation limit of the expand-ahead) --
 		# nothing of the trees, which live in device memory that rk_mcts_reset rewrites.  So the graph is KEPT from search to
 		# search and captured again only when one of those changes (grown or new engine, another net or fused copy).
-		key = (h.value, self._shape, self.c, self.nu, self.priors, self._max_sims, oh.data_ptr(), oh.dtype, _capture_key(self.net, self._fs or self._n686))
-		hit = self._graph_cache is not None and self._graph_cache[0] == key
+		key = (h.value, self._shape, self.c, self.nu, self.priors, self._max_sims, oh.data_ptr(), oh.dtype, eng.capture_key(self.net, self._forward))
+		self._graph, hit = eng.kept_graph(self, key, lambda: self._warm(warm), lambda: self._step(oh, h, expand=False), oh, ((self.net, self._forward),))
 		if hit:
-			for _ in range(warm):                                      # real simulations: after them every tree is expanded ahead
-				self._step(oh, h)
-				self.simulations += 1
-			self._graph = self._graph_cache[1]
-			return
-		self._graph_cache = None
-		side = torch.cuda.Stream()
-		side.wait_stream(torch.cuda.current_stream())
-		with torch.cuda.stream(side):
-			for _ in range(warm):                                      # real simulations; they also warm the allocator
-				self._step(oh, h)
-				self.simulations += 1
-		torch.cuda.current_stream().wait_stream(side)
-		self._graph = torch.cuda.CUDAGraph()
-		with torch.cuda.graph(self._graph, **CAPTURE):
-			self._step(oh, h, expand=False)
-		self._graph_cache = (key, self._graph, oh, (self.net, self._fs or self._n686))      # the net stays alive with the graph that holds its addresses
-		self.captures += 1
+			self._warm(warm)                                           # on this stream: a kept graph still wants every tree expanded ahead
+
+	def _warm(self, n: int):
+		"""`n` real simulations before the captured step runs: after them every tree is expanded ahead (they also warm the allocator)."""
+		for _ in range(n):
+			self._step(self._oh, self._h)
+			self.simulations += 1
 
 	def _net_half(self, first: int, count: int):
 		"""Raw logits and values of the trees first ... first + count - 1: the fused first layer reads their children where the engine keeps them."""
@@ -1206,34 +1026,20 @@ class MCTSBatch(DeepAgent):
 		h = self._h
 		T = self.n_trees
 		na = T // 2
-		key = ("halves", h.value, self._shape, self.c, self.nu, self._max_sims, _capture_key(self.net, self._fs))
-		hit = self._graph_cache is not None and self._graph_cache[0] == key
-		side = torch.cuda.Stream() if not hit else None
-		if hit:
-			for _ in range(warm):
-				self._step(self._oh, h)
-				self.simulations += 1
-			self._graph, self._half_bufs = self._graph_cache[1], self._graph_cache[4]
-			self._prime_halves()
-			return
-		self._graph_cache = None
-		main = torch.cuda.Stream()
-		main.wait_stream(torch.cuda.current_stream())
-		with torch.cuda.stream(main):
-			for _ in range(warm):                                      # real simulations; they also warm the allocator
-				self._step(self._oh, h)
-				self.simulations += 1
+		key = ("halves", h.value, self._shape, self.c, self.nu, self._max_sims, eng.capture_key(self.net, self._fs))
+		caller, side = torch.cuda.current_stream(), torch.cuda.Stream()      # (`side`: the captured step's second stream)
+
+		def warm_halves():
+			self._warm(warm)
 			pa, va = self._net_half(0, na)                             # shapes / dtypes of a half's outputs (and a warm-up of the half-size GEMMs)
-			pb, vb = self._net_half(na, T - na)
-			del pb, vb
-		torch.cuda.current_stream().wait_stream(main)
-		# A's outputs cross from one replay to the next (and from the eager priming into the first replay): they live in buffers
-		# of their own, copied into at the end of phase 2 (two copies of a few KB)
-		self._half_bufs = (torch.empty_like(pa), torch.empty_like(va))
-		del pa, va
-		XA, VA = self._half_bufs
-		self._graph = torch.cuda.CUDAGraph()
-		with torch.cuda.graph(self._graph, **CAPTURE):
+			self._net_half(na, T - na)
+			# A's outputs cross from one replay to the next (and from the eager priming into the first replay): they live in buffers
+			# of their own, copied into at the end of phase 2 (two copies of a few KB); allocated as memory of the caller's stream
+			with torch.cuda.stream(caller):
+				self._half_bufs = (torch.empty_like(pa), torch.empty_like(va))
+
+		def step_halves():
+			XA, VA = self._half_bufs
 			cur = torch.cuda.current_stream()
 			side.wait_stream(cur)                                      # fork
 			self._backup_half(0, na, XA, VA)                           # phase 1, this stream: backup + select A
@@ -1247,8 +1053,11 @@ class MCTSBatch(DeepAgent):
 			with torch.cuda.stream(side):
 				self._backup_half(na, T - na, pb, vb)                  # phase 2, side stream: backup + select B
 			cur.wait_stream(side)                                      # join
-		self._graph_cache = (key, self._graph, self._oh, (self.net, self._fs), self._half_bufs)
-		self.captures += 1
+
+		self._graph, hit = eng.kept_graph(self, key, warm_halves, step_halves, self._oh, lambda: ((self.net, self._fs), self._half_bufs))
+		if hit:
+			self._warm(warm)
+			self._half_bufs = self._graph_cache[4]
 		self._prime_halves()
 
 	def _prime_halves(self):
@@ -1305,15 +1114,12 @@ class MCTSBatch(DeepAgent):
 
 	# -- results ------------------------------------------------------------------------------------------------
 	def action_queue_of(self, tree: int) -> deque:
-		buf = (C.c_longlong * self.max_path)()
+		lib = _ffi.lib()
 		if getattr(self, "_graph_done", False) and self.status[tree, 1] == 1:
-			n = _ffi.lib().rk_mcts_graph_path(self._h, tree, buf, self.max_path, _ffi.stream_ptr())
-			if n >= 0:
-				return deque(int(a) for a in buf[:n])
-		n = _ffi.lib().rk_mcts_path(self._h, tree, buf, None, self.max_path, _ffi.stream_ptr())
-		if n < 0:
-			_ffi.check(int(n))
-		return deque(int(a) for a in buf[:n])
+			queue = eng.read_path(lib.rk_mcts_graph_path, self._h, tree, length=self.max_path, strict=False)
+			if queue is not None:
+				return queue
+		return eng.read_path(lambda buf, n, stream: lib.rk_mcts_path(self._h, tree, buf, None, n, stream), length=self.max_path)
 
 	def path_nodes_of(self, tree: int) -> list:
 		acts = (C.c_longlong * self.max_path)()
@@ -1402,9 +1208,7 @@ class MCTS(DeepAgent):
 		                       use_graph=self.use_hipgraph)[0])
 		self._n = int(b.status[0, 2])
 		if not solved and self._n + 12 > b.capacity and max_states > b.capacity and b.capacity >= self.max_capacity:
-			self.capacity_exhausted = True
-			import warnings
-			warnings.warn(f"{self}: node pool of {b.capacity} states is full with time left; raise max_capacity", CapacityExhausted)
+			eng.pool_exhausted(self, b.capacity)
 		self.action_queue = b.action_queue_of(0)       # with search_graph: completed and shortened on the device (agents.py:483-486)
 		return solved
 
@@ -1443,7 +1247,7 @@ class MCTS(DeepAgent):
 		return self._n
 
 
-class AStarBatch(DeepAgent):
+class AStarBatch(DeepAgent, _ffi.Owner):
 	"""
 	S independent batch weighted A* searches advanced in lock-step on the GPU (engine rk_astarb_*).  Every search
 	follows the reference's AStar exactly (agents.py:171-413): same node numbering, G, parents and action queue as
@@ -1468,18 +1272,8 @@ class AStarBatch(DeepAgent):
 
 	def _engine(self):
 		if self._h is None:
-			h = C.c_void_p()
-			_ffi.check(_ffi.lib().rk_astarb_create(C.byref(h), self.n_searches, self.capacity, self.expansions))
-			self._h = h
+			self._create("rk_astarb_create", "rk_astarb_destroy", self.n_searches, self.capacity, self.expansions)
 		return self._h
-
-	def __del__(self):
-		try:
-			if getattr(self, "_h", None) is not None:
-				_ffi.lib().rk_astarb_destroy(self._h)
-				self._h = None
-		except Exception:
-			pass
 
 	def _poll(self) -> np.ndarray:
 		st = np.zeros((self.n_searches, 7), np.int64)
@@ -1502,16 +1296,17 @@ class AStarBatch(DeepAgent):
 		if rows == 0:
 			values = self._no_values
 		else:
-			v = _sliced_value_forward(self._fs or self._n686 or self.net, oh[:min(len(oh), -(-rows // 64) * 64)], self.net_slice_rows or 12_288)
-			if isinstance(v, torch.Tensor) and v.is_cuda and v.dtype == torch.bfloat16 and v.is_contiguous():
-				values, vcode = v.detach().reshape(-1), _ffi.OH_BF16
-			else:
-				values, vcode = _value_f32(v), _ffi.OH_F32
-			if vcode != self._vcode:
-				_ffi.check(lib.rk_astarb_set_values_dtype(h, vcode, _ffi.stream_ptr()))
-				self._vcode = vcode
+			values = self._values(_sliced_value_forward(self._forward, oh[:min(len(oh), -(-rows // 64) * 64)], self.net_slice_rows or 12_288))
 		self._keep = values
 		_ffi.check(lib.rk_astarb_step_commit(h, values.data_ptr(), _ffi.stream_ptr()))
+
+	def _values(self, out) -> torch.Tensor:
+		"""The value head as the engine takes it (a bf16 net's values go in as they are); the engine is told only when the dtype changes."""
+		values, vcode = eng.engine_values(out)
+		if vcode != self._vcode:
+			_ffi.check(_ffi.lib().rk_astarb_set_values_dtype(self._h, vcode, _ffi.stream_ptr()))
+			self._vcode = vcode
+		return values
 
 	def _step(self, oh, code):
 		lib, h = _ffi.lib(), self._h
@@ -1523,14 +1318,7 @@ class AStarBatch(DeepAgent):
 		# torch's BatchNorm pick kernels for 16 384-row forwards that cost three times as much per row as for 12 000 rows)
 		K = 12 * self.expansions
 		rows = self.net_slice_rows or (K if K >= NET_SLICE_ROWS // 4 else (NET_SLICE_ROWS // K) * K)
-		v = _sliced_value_forward(self._fs or self._n686 or self.net, oh, rows)
-		if isinstance(v, torch.Tensor) and v.is_cuda and v.dtype == torch.bfloat16 and v.is_contiguous():
-			values, vcode = v.detach().reshape(-1), _ffi.OH_BF16        # a bf16 net's values go in as they are
-		else:
-			values, vcode = _value_f32(v), _ffi.OH_F32
-		if vcode != self._vcode:
-			_ffi.check(lib.rk_astarb_set_values_dtype(h, vcode, _ffi.stream_ptr()))
-			self._vcode = vcode
+		values = self._values(_sliced_value_forward(self._forward, oh, rows))
 		self._keep = values
 		_ffi.check(lib.rk_astarb_step_commit(h, values.data_ptr(), _ffi.stream_ptr()))
 
@@ -1547,7 +1335,7 @@ class AStarBatch(DeepAgent):
 		self.net.eval()
 		time_limit = time_limit or 1e10
 		S, K = self.n_searches, 12 * self.expansions
-		self._begin_repr()                     # 6x8x6: the searches run in 20-byte form, the net gets 6x8x6 rows (_Net686)
+		_, _, code = self._begin_net()         # 6x8x6: the searches run in 20-byte form, the net gets 6x8x6 rows (_Net686)
 		states = self._roots20(states, S)
 		budget = np.minimum(np.broadcast_to(np.asarray(self.capacity if max_states is None else max_states, dtype=np.int64), (S,)),
 		                    self.capacity).copy()
@@ -1555,13 +1343,7 @@ class AStarBatch(DeepAgent):
 		_ffi.check(lib.rk_astarb_reset(h, states.ctypes.data, budget.ctypes.data, self.lambda_, _ffi.stream_ptr()))
 		self._vcode = _ffi.OH_F32
 		_ffi.check(lib.rk_astarb_set_values_dtype(h, self._vcode, _ffi.stream_ptr()))
-		self._fs = self._from_states           # re-copied here if the net changed since the last search
-		if self._fs is not None or self._n686 is not None:
-			oh, code = torch.from_numpy(cube.repeat_state(_SOLVED20, S * K)).to(gpu), _ffi.OH_STATES
-		else:
-			oh_dtype = _oh_dtype(self.net)
-			oh = torch.zeros((S * K, 480), dtype=oh_dtype, device=gpu)
-			code = _OH_CODES[oh_dtype]
+		oh = eng.net_batch(S * K, code)
 		self.iterations = 0
 		self.net_rows_total = 0
 		if exact_batch is None:
@@ -1574,15 +1356,9 @@ class AStarBatch(DeepAgent):
 		step = self._step_exact if exact_batch else self._step
 		graph = None
 		if use_graph:
-			side = torch.cuda.Stream()
-			side.wait_stream(torch.cuda.current_stream())
-			with torch.cuda.stream(side):
-				self._step(oh, code)                                    # a real iteration; also warms the allocator and fixes the values' dtype
-			torch.cuda.current_stream().wait_stream(side)
+			# the warm-up is a real iteration, which also fixes the values' dtype; captured on every search, the graph is not kept
+			graph = eng.capture(lambda: self._step(oh, code), lambda: self._step(oh, code))
 			self.iterations += 1
-			graph = torch.cuda.CUDAGraph()
-			with torch.cuda.graph(graph, **CAPTURE):
-				self._step(oh, code)
 		# Steps after a search is done are no-ops on the device but still run the net on the padded batch, so the host must not
 		# poll too rarely: a search grows by at most K states per iteration, so no live search can run out of budget in fewer
 		# than (budget - states) // K iterations -- poll after that many (at most `poll`).  Round 2's harness polled every 64
@@ -1590,8 +1366,9 @@ class AStarBatch(DeepAgent):
 		n_states = np.ones(S, np.int64)
 		live = np.ones(S, bool)
 		while time.perf_counter() - t0 < time_limit:
-			safe = int(((budget[live] - n_states[live]) // K).min()) if live.any() else 1
-			burst = max(1, min(poll, safe))
+			# the live search closest to its budget decides (min over searches of room // K = (min room) // K); none live: one iteration
+			room = int((budget[live] - n_states[live]).min()) if live.any() else K
+			burst = eng.burst(poll, room, K)
 			for _ in range(burst):
 				if graph is not None:
 					graph.replay()
@@ -1608,19 +1385,12 @@ class AStarBatch(DeepAgent):
 		st = self.status[search]
 		if st[1] != 1:                                                   # unsolved, or the start was already solved
 			return deque()
-		buf = (C.c_longlong * 4096)()
-		n = _ffi.lib().rk_astarb_path(self._h, search, int(st[5]), buf, 4096, _ffi.stream_ptr())
-		if n < 0:
-			_ffi.check(int(n))
-		return deque(int(a) for a in buf[:n])
+		return eng.read_path(_ffi.lib().rk_astarb_path, self._h, search, int(st[5]))
 
 	def arrays_of(self, search: int):
 		"""(states, G, parents, parent_actions) of one search, rows 0..n (row 0 unused), in the reference's dtypes."""
 		n = int(self._poll()[search, 2])
-		states, G = np.zeros((n + 1, 20), np.int8), np.zeros(n + 1)
-		parents, pact = np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int64)
-		_ffi.check(_ffi.lib().rk_astarb_export(self._h, search, 1, n, states[1:].ctypes.data, G[1:].ctypes.data, parents[1:].ctypes.data,
-		                                       pact[1:].ctypes.data, _ffi.stream_ptr()))
+		states, G, parents, pact = eng.export_pool(_ffi.lib().rk_astarb_export, (self._h, search), n)
 		return self._states_out(states, n), G, parents, pact
 
 	def __len__(self):

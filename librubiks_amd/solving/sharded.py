@@ -55,7 +55,8 @@ import torch
 import torch.distributed as dist
 
 from librubiks_amd import gpu, no_grad, _ffi, cube
-from librubiks_amd.solving.agents import CAPTURE, DeepAgent, _capture_key, _values_for_engine, _sliced_value_forward, _oh_dtype, _OH_CODES
+from librubiks_amd.solving import _engine as eng
+from librubiks_amd.solving.agents import DeepAgent
 
 STOP_REASONS = {0: "running", 1: "won", 2: "budget", 3: "capacity", 4: "time", 5: "nothing open", 6: "engine error"}
 
@@ -113,7 +114,7 @@ class Transport:
 		return t.cpu().numpy()
 
 
-class RcclTransport:
+class RcclTransport(_ffi.Owner):
 	"""
 	The same three transfers through the C ABI's own RCCL layer (`rk_comm_*`, include/rubiks_hip.h) instead of
 	torch.distributed: what a caller of the shared library without torch.distributed uses (route B).
@@ -133,19 +134,10 @@ class RcclTransport:
 		if len(unique_id) != 128:
 			raise ValueError("the RCCL unique id is 128 bytes")
 		_ffi.require_gpu()
-		h = C.c_void_p()
-		_ffi.check(_ffi.lib().rk_comm_create(C.byref(h), unique_id, int(rank), int(world)))
-		self._h, self.rank, self.world = h, int(rank), int(world)
+		self._create("rk_comm_create", "rk_comm_destroy", unique_id, int(rank), int(world))
+		self.rank, self.world = int(rank), int(world)
 		self.shortcut = False                      # the collectives always run, also with one rank: that is how a one-GPU box tests them
 		self.collectives = 0
-
-	def __del__(self):
-		try:
-			if getattr(self, "_h", None) is not None:
-				_ffi.lib().rk_comm_destroy(self._h)
-				self._h = None
-		except Exception:
-			pass
 
 	def all_gather(self, mine: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
 		self.collectives += 1
@@ -196,7 +188,7 @@ def select_pops(heads: np.ndarray, n: int) -> np.ndarray:
 	return np.bincount(rank[take], minlength=world).astype(np.int64)
 
 
-class ShardedAStar(DeepAgent):
+class ShardedAStar(DeepAgent, _ffi.Owner):
 	"""Collective agent: every rank constructs it and calls `search` with the same arguments."""
 
 	def __init__(self, net, lambda_: float, expansions: int, capacity: int = 2_000_000, group=None, force_collectives: bool = False,
@@ -229,21 +221,14 @@ class ShardedAStar(DeepAgent):
 
 	def _engine(self):
 		if self._h is None:
-			h = C.c_void_p()
-			_ffi.check(_ffi.lib().rk_astar_create_sharded(C.byref(h), self.capacity, self.expansions, self.tp.rank, self.tp.world))
-			self._h = h
+			self._create("rk_astar_create_sharded", "rk_astar_destroy", self.capacity, self.expansions, self.tp.rank, self.tp.world)
 		return self._h
 
-	def __del__(self):
-		try:
-			self._graph_cache = None
-			if self._h is not None:
-				_ffi.lib().rk_astar_destroy(self._h)
-				self._h = None
-		except Exception:
-			pass
+	def _free(self):
+		self._graph_cache = None                                         # it holds the engine's addresses
+		super()._free()
 
-	def _buffers(self, h, code, oh_dtype):
+	def _buffers(self, h, code):
 		"""The search's device buffers, allocated once per engine and row type: a kept hipGraph holds their addresses."""
 		lib, tp, K = _ffi.lib(), self.tp, 12 * self.expansions
 		if self._bufs is not None and self._bufs["code"] == code:
@@ -252,10 +237,7 @@ class ShardedAStar(DeepAgent):
 		block, glen = int(lib.rk_astar_shard_block_bytes(h)), int(lib.rk_astar_shard_gather_len(h))
 		send = torch.zeros((tp.world, block), dtype=torch.uint8, device=gpu)
 		mine = torch.zeros(glen, dtype=torch.float64, device=gpu)
-		if code == _ffi.OH_STATES:
-			oh = torch.from_numpy(cube.repeat_state(cube.get_solved(), K)).to(gpu)                  # rows = states: valid codes everywhere
-		else:
-			oh = torch.zeros((K, 480), dtype=oh_dtype, device=gpu)
+		oh = eng.net_batch(K, code)
 		self._bufs = {"code": code, "send": send, "recv": send if tp.shortcut else torch.zeros_like(send), "mine": mine,
 		              "gathered": mine.view(1, -1) if tp.shortcut else torch.zeros((tp.world, glen), dtype=torch.float64, device=gpu), "oh": oh}
 		_ffi.check(lib.rk_astar_shard_bind(h, mine.data_ptr()))
@@ -263,28 +245,22 @@ class ShardedAStar(DeepAgent):
 
 	def _iteration(self, h, b, forward, rows, time_limit, max_states, marks=None):
 		"""One iteration: a fixed sequence of launches on fixed buffers, nothing from the host but the launches themselves."""
-		lib, tp, st = _ffi.lib(), self.tp, _ffi.stream_ptr
-
-		def mark():
-			if marks is not None:
-				e = torch.cuda.Event(enable_timing=True)
-				e.record()
-				marks.append(e)
-
-		mark()
+		lib, tp, st, mark = _ffi.lib(), self.tp, _ffi.stream_ptr, eng.mark
+		mark(marks, 0)
 		gathered = tp.all_gather(b["mine"], b["gathered"])               # collective 1: heads + status
-		mark()
+		mark(marks, 1)
 		_ffi.check(lib.rk_astar_shard_select(h, gathered.data_ptr(), float(time_limit), float(max_states), b["send"].data_ptr(), st()))
-		mark()
+		mark(marks, 2)
 		got = tp.all_to_all(b["send"], b["recv"])                        # collective 2: records (+ last iteration's offers)
-		mark()
+		mark(marks, 3)
 		_ffi.check(lib.rk_astar_shard_insert(h, got.data_ptr(), b["send"].data_ptr(), b["oh"].data_ptr(), b["code"], st()))
-		mark()
-		values = _values_for_engine(h, _sliced_value_forward(forward, b["oh"][:rows]))
+		mark(marks, 4)
+		values, vcode = eng.engine_values(eng.sliced_value_forward(forward, b["oh"][:rows]))
+		_ffi.check(lib.rk_astar_set_values_dtype(h, vcode))
 		self._keep = values                                              # the push kernels read it after this call returns
-		mark()
+		mark(marks, 5)
 		_ffi.check(lib.rk_astar_shard_push_rows(h, values.data_ptr(), rows, got.data_ptr(), b["send"].data_ptr(), st()))
-		mark()
+		mark(marks, 6)
 
 	@no_grad
 	def search(self, state: np.ndarray, time_limit: float = None, max_states: int = None) -> bool:
@@ -303,13 +279,8 @@ class ShardedAStar(DeepAgent):
 		st = _ffi.stream_ptr
 		K = 12 * N                                                       # upper bound of a rank's new states per iteration
 		rows = K if self.full_rows else min(K, self.rows_override or net_rows(K, tp.world))   # rows the net evaluates every iteration
-		self._fs = self._from_states                                     # re-copied here if the net changed since the last search
-		if self._fs is not None:
-			code, oh_dtype, forward = _ffi.OH_STATES, None, self._fs
-		else:
-			oh_dtype = _oh_dtype(self.net)
-			code, forward = _OH_CODES[oh_dtype], self.net
-		b = self._buffers(h, code, oh_dtype)
+		forward, _, code = self._begin_net()                             # (the fused copy is re-made here if the net changed since the last search)
+		b = self._buffers(h, code)
 		_ffi.check(lib.rk_astar_shard_reset(h, state.ctypes.data, float(self.lambda_), b["send"].data_ptr(), st()))
 		root_owner = lib.rk_shard_owner(state.ctypes.data, tp.world)
 		self.net_rows_max, self.net_rows_total, self.host_launches = rows, 0, 0
@@ -320,28 +291,18 @@ class ShardedAStar(DeepAgent):
 		if self.use_hipgraph and not self.profile and (tp.shortcut or tp.on_device):
 			# the captured iteration holds addresses (engine, buffers, the net's tensors) and scalars passed by value (lambda, the two
 			# limits, the row count, the values' dtype) -- nothing of the search, which lives in device memory the reset rewrites
-			key = (h.value, rows, code, float(self.lambda_), float(time_limit), float(max_states), b["oh"].data_ptr(), _capture_key(self.net, self._fs))
-			if self._graph_cache is not None and self._graph_cache[0] == key:
-				graph = self._graph_cache[1]
-			else:
-				self._graph_cache = None
-				try:
-					side = torch.cuda.Stream()
-					side.wait_stream(torch.cuda.current_stream())
-					with torch.cuda.stream(side):
-						self._iteration(h, b, forward, rows, time_limit, max_states)      # a real iteration; also warms the allocator and the collectives
-					torch.cuda.current_stream().wait_stream(side)
-					graph = torch.cuda.CUDAGraph()
-					with torch.cuda.graph(graph, **CAPTURE):
-						self._iteration(h, b, forward, rows, time_limit, max_states)
-					self._graph_cache = (key, graph, (self.net, self._fs))
-					self.captures += 1
+			key = (h.value, rows, code, float(self.lambda_), float(time_limit), float(max_states), b["oh"].data_ptr(), eng.capture_key(self.net, forward))
+			step = lambda: self._iteration(h, b, forward, rows, time_limit, max_states)      # noqa: E731
+			try:
+				# the warm-up is a real iteration (its rows count); it also warms the allocator and the collectives
+				graph, hit = eng.kept_graph(self, key, step, step, b["oh"], ((self.net, forward),))
+				if not hit:
 					self.net_rows_total += rows
-				except Exception as e:                                      # e.g. a collective this stack cannot capture: say so, run eagerly
-					self.graph_error = f"{type(e).__name__}: {e}"[:300]
-					self.use_hipgraph, graph, self._graph_cache = False, None, None
-					torch.cuda.synchronize()
-					return self.search(state, *limits)                        # the engine may be mid-iteration: start over, eagerly
+			except Exception as e:                                          # e.g. a collective this stack cannot capture: say so, run eagerly
+				self.graph_error = f"{type(e).__name__}: {e}"[:300]
+				self.use_hipgraph, graph, self._graph_cache = False, None, None
+				torch.cuda.synchronize()
+				return self.search(state, *limits)                            # the engine may be mid-iteration: start over, eagerly
 
 		stop, it = 0, 0
 		while True:
@@ -350,7 +311,7 @@ class ShardedAStar(DeepAgent):
 					graph.replay()
 					self.host_launches += 1
 				else:
-					row = [] if self.profile else None
+					row = eng.events(7) if self.profile else None
 					self._iteration(h, b, forward, rows, time_limit, max_states, row)
 					if row is not None and len(marks) < 4096:
 						marks.append(row)
@@ -407,13 +368,7 @@ class ShardedAStar(DeepAgent):
 	# -- inspection of this rank's shard ------------------------------------------------------------------------
 	def local_arrays(self):
 		"""(states, G, parents, parent_actions) of the states this rank owns, rows 1..n."""
-		n = self._n
-		states, G = np.zeros((n + 1, 20), np.int8), np.zeros(n + 1)
-		parents, pact = np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int64)
-		if n:
-			_ffi.check(_ffi.lib().rk_astar_export(self._h, 1, n, states[1:].ctypes.data, G[1:].ctypes.data, parents[1:].ctypes.data,
-			                                      pact[1:].ctypes.data, _ffi.stream_ptr()))
-		return states, G, parents, pact
+		return eng.export_pool(_ffi.lib().rk_astar_export, (self._h,), self._n)
 
 	def local_parent_ranks(self) -> np.ndarray:
 		"""Owner rank of every local node's parent, rows 1..n (row 0 unused): with `local_arrays` the whole shard."""
