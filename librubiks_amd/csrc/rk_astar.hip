@@ -53,6 +53,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/rubiks_hip.h"
@@ -60,6 +61,7 @@
 #include "rk_error.h"
 #include "rk_kernels.h"
 #include "rk_search_dev.h"
+#include "rk_search_host.h"
 
 namespace rk {
 
@@ -1116,13 +1118,7 @@ __global__ void k_set_budget(AstarDev d, int budget)
 __global__ __launch_bounds__(256)
 void k_astar_rehash(AstarDev d)
 {
-	const int n = d.ctr[C_NSTATES];
-	for (int idx = 1 + blockIdx.x * blockDim.x + threadIdx.x; idx <= n; idx += gridDim.x * blockDim.x) {
-		uint32_t s[5];
-		load5(d.states + (size_t)idx * 5, s);
-		uint32_t slot = hash_state(s) & d.mask;
-		while (atomicCAS(&d.table[slot], 0u, (uint32_t)idx) != 0u) slot = (slot + 1) & d.mask;
-	}
+	rehash_pool(d.states, d.table, d.mask, d.ctr[C_NSTATES], 1 + blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
 }
 
 // action indices from the root to node `index` by walking parents on the device (agents.py:244-251)
@@ -1399,45 +1395,85 @@ struct rk_astar {
 	bool ready = false, pending = false;
 	bool budget_explicit = false; // rk_astar_set_budget was called since the last reset
 	int last_n_new = 0, last_n_before = 0;    // sizes reported by the last rk_astar_expand
-	int32_t *ctr_host = nullptr;  // page-locked landing place of the counter block: a status poll is one direct copy, no staging
-	std::vector<void *> allocs;
+	Landing ctr_host;             // page-locked landing place of the counter block: a status poll is one direct copy, no staging
+	DevPool pool{64};
 };
 
 namespace {
 
-template <typename T>
-int dev_alloc(rk_astar *h, T **p, size_t count)
-{
-	void *q = nullptr;
-	RK_HIP(hipMalloc(&q, count * sizeof(T) + 64));
-	h->allocs.push_back(q);
-	*p = static_cast<T *>(q);
-	return RK_OK;
-}
-
-inline unsigned blocks(size_t n, unsigned per = 256) { return (unsigned)((n + per - 1) / per); }
 inline bool pop_is_wide_host(const AstarDev &d) { return d.q.levels * d.N > POP_LDS; }
 
 constexpr int WALK_MAX = 1 << 16;
 
-int read_ctr(rk_astar *h, int32_t *out, hipStream_t st)
-{
-	int32_t *dst = h->ctr_host != nullptr ? h->ctr_host : out;      // (pageable memory costs a staged copy per poll)
-	RK_HIP(hipMemcpyAsync(dst, h->d.ctr, C_COUNT * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-	RK_HIP(hipStreamSynchronize(st));
-	if (dst != out) memcpy(out, dst, C_COUNT * sizeof(int32_t));
-	return RK_OK;
-}
+int read_ctr(rk_astar *h, int32_t *out, hipStream_t st) { return h->ctr_host.read(h->d.ctr, C_COUNT, out, st); }
 
 // records an iteration is expected to push: what the open queue's level capacities are multiples of
 static inline int queue_inflow(const AstarDev &d) { return d.world == 1 ? d.K : (d.K + d.world - 1) / d.world; }
+
+// Queue levels: 4 K, 16 K, 64 K, ... records, the top level holds the whole pool (C1 = capacity + 1 rows).  K here is what an iteration
+// is expected to PUSH: 12 N on one GPU, 12 N / world on a rank of a sharded search (owner = hash).  Rounds 2-4 sized a rank's levels by
+// its incoming SLOTS, world * 12 N: at 8 ranks level 0 held 64 iterations' worth of records and every push rewrote all of it -- 183 us
+// of a rank's iteration in the weak-scaling run (benchmarks/sharded_sim8.py).  The sizes are tuning, not correctness: a push that does
+// not fit level 0 goes to the first level that holds it (make_plan).  Fills cap[] and returns the number of levels.
+int queue_plan(const AstarDev &d, size_t C1, uint32_t cap[QL])
+{
+	uint64_t c = std::max<uint64_t>(4ull * (uint64_t)queue_inflow(d), 4096ull);
+	for (int levels = 0;; c *= 4) {
+		const bool top = c >= C1 || levels == QL - 1;
+		cap[levels++] = (uint32_t)(top ? C1 : c);
+		if (top) return levels;
+	}
+}
+
+// slots of the append / offer compactions: a rank of a sharded search can receive every rank's children
+inline size_t scan_slots(const AstarDev &d) { return (size_t)(d.world == 1 ? d.K : d.KI) + 64; }
+// look-back words per class of those compactions (chain0; chain1 and chain2 hold `world` rows of them)
+inline size_t scan_blocks(const AstarDev &d) { return blocks(scan_slots(d), ASCAN) + 1; }
+
+inline unsigned pop_wide_grid(const AstarDev &d) { return blocks((size_t)d.q.levels * d.N); }
+
+// The net's input rows (about one 16-byte store per thread: the grid covers the largest possible batch) + relaxation 1.  What the
+// dtype of the rows decides: ELEM_BYTES of k_new_rows / kb_new_rows, the bit pattern of 1.0 and the 16-byte chunks per row.
+// launch(ELEM_BYTES as an integral_constant, grid, one); without rows (`rows` false) only the relaxation runs.
+template <typename Launch>
+void launch_new_rows(const AstarDev &d, bool rows, int out_dtype, Launch launch)
+{
+	const size_t chunks = (size_t)d.K * (!rows ? 1 : out_dtype == RK_OH_F32 ? 120 : out_dtype == RK_OH_STATES ? 2 : 60);
+	const unsigned grid = std::min<unsigned>(blocks(chunks), 8192u);
+	if (rows && out_dtype == RK_OH_F32) launch(std::integral_constant<int, 4>{}, grid, 0x3F800000u);
+	else if (rows && out_dtype == RK_OH_STATES) launch(std::integral_constant<int, 0>{}, grid, 0u);
+	else launch(std::integral_constant<int, 2>{}, grid, out_dtype == RK_OH_F16 ? 0x3C00u : 0x3F80u);
+}
+
+// The cost records of an iteration, sorted: sort(CHUNK as an integral_constant) sorts Kpad / CHUNK chunks with CHUNK / 2 threads each;
+// up to eight chunks go to the queue insert as they are (its merge is multi-way), more are merged into one run first by
+// merge(L, from) passes over blocks(Kpad) workgroups.  Returns which record buffer holds the result.
+template <typename Sort, typename Merge>
+int launch_sort(const AstarDev &d, Sort sort, Merge merge)
+{
+	int from = 0;
+	if (d.chunk == SMALL_CHUNK) {
+		sort(std::integral_constant<int, SMALL_CHUNK>{});
+	} else {
+		sort(std::integral_constant<int, SORT_CHUNK>{});
+		for (int L = SORT_CHUNK; L < d.Kpad && new_chunk_of(d.chunk, d.Kpad) == 0; L <<= 1) {
+			merge(L, from);
+			from ^= 1;
+		}
+	}
+	return from;
+}
+
+// The queue insert's merge is sized on the device (it is the new records most of the time and a whole queue level now and then);
+// workgroups beyond it leave after the plan.  `floor`: the fewest workgroups per search.
+inline unsigned insert_grid(const AstarDev &d, unsigned floor) { return std::min<unsigned>(1024u, std::max<unsigned>(blocks((size_t)d.Kpad * 4), floor)); }
 
 // sharded engines whose levels * N candidates do not fit one workgroup's LDS: the selection as a grid, then the candidate costs of the
 // next all-gather (k_end<true> has written the eight header doubles)
 static void launch_shard_wide_selection(const AstarDev &d, hipStream_t st)
 {
 	if (!pop_is_wide_host(d)) return;
-	hipLaunchKernelGGL(k_pop_wide, dim3(blocks((size_t)d.q.levels * d.N)), dim3(256), 0, st, d);
+	hipLaunchKernelGGL(k_pop_wide, dim3(pop_wide_grid(d)), dim3(256), 0, st, d);
 	hipLaunchKernelGGL(k_shard_heads, dim3(blocks((size_t)d.N)), dim3(256), 0, st, d);
 }
 
@@ -1445,48 +1481,31 @@ template <bool SHARDED>
 void launch_append(rk_astar *h, const uint8_t *recv, void *d_onehot, int out_dtype, hipStream_t st)
 {
 	const AstarDev &d = h->d;
-	const size_t kin = (size_t)d.K;                                    // (sharded too: at most K records arrive, see shard_stage_prefix)
-	hipLaunchKernelGGL((k_append<SHARDED>), dim3(blocks(kin, ASCAN)), dim3(ASCAN), 0, st, d, recv);
-	// the net's input rows (about one 16-byte store per thread: the grid covers the largest possible batch) + relaxation 1
-	const size_t chunks = d_onehot == nullptr ? kin : kin * (out_dtype == RK_OH_F32 ? 120 : out_dtype == RK_OH_STATES ? 2 : 60);
-	const unsigned grid = std::min<unsigned>(blocks(chunks), 8192u);
-	if (d_onehot != nullptr && out_dtype == RK_OH_F32)
-		hipLaunchKernelGGL((k_new_rows<4, SHARDED>), dim3(grid), dim3(256), 0, st, d, (u32x4 *)d_onehot, 0x3F800000u, recv);
-	else if (d_onehot != nullptr && out_dtype == RK_OH_STATES)
-		hipLaunchKernelGGL((k_new_rows<0, SHARDED>), dim3(grid), dim3(256), 0, st, d, (u32x4 *)d_onehot, 0u, recv);
-	else
-		hipLaunchKernelGGL((k_new_rows<2, SHARDED>), dim3(grid), dim3(256), 0, st, d, (u32x4 *)d_onehot, out_dtype == RK_OH_F16 ? 0x3C00u : 0x3F80u, recv);
+	// (sharded too: at most K records arrive, see shard_stage_prefix)
+	hipLaunchKernelGGL((k_append<SHARDED>), dim3(blocks((size_t)d.K, ASCAN)), dim3(ASCAN), 0, st, d, recv);
+	launch_new_rows(d, d_onehot != nullptr, out_dtype, [&](auto eb, unsigned grid, uint32_t one) {
+		hipLaunchKernelGGL((k_new_rows<decltype(eb)::value, SHARDED>), dim3(grid), dim3(256), 0, st, d, (u32x4 *)d_onehot, one, recv);
+	});
 }
 
 // records + sort + merge passes + queue insert + end of iteration; returns through the launches only
 template <bool SHARDED>
-int launch_commit(rk_astar *h, const float *d_values, const uint8_t *recv, hipStream_t st, const AstarDev *geometry = nullptr)
+int launch_commit(rk_astar *h, const float *d_values, hipStream_t st, const AstarDev *geometry = nullptr)
 {
 	const AstarDev &d = geometry ? *geometry : h->d;                    // (sharded: the sort geometry of this iteration, see shard_push_impl)
-	int from = 0;
-	if (d.chunk == SMALL_CHUNK) {
-		hipLaunchKernelGGL((k_records_sort<SMALL_CHUNK>), dim3(d.Kpad / SMALL_CHUNK), dim3(SMALL_CHUNK / 2), 0, st, d, d_values);
-	} else {
-		hipLaunchKernelGGL((k_records_sort<SORT_CHUNK>), dim3(d.Kpad / SORT_CHUNK), dim3(SORT_CHUNK / 2), 0, st, d, d_values);
-		// up to eight chunks go to the queue insert as they are (its merge is multi-way); more are merged into one run first
-		for (int L = SORT_CHUNK; L < d.Kpad && new_chunk_of(d.chunk, d.Kpad) == 0; L <<= 1) {
-			hipLaunchKernelGGL(k_merge_pass, dim3(blocks(d.Kpad)), dim3(256), 0, st, d, L, from);
-			from ^= 1;
-		}
-	}
-	// The merge's size is decided on the device (it is the new records most of the time and a whole queue level now and
-	// then); workgroups beyond it leave after the plan.  With 32 workgroups at N = 100 the occasional level merge (up to
-	// the whole open set) ran 32 records per thread, each a chain of dependent binary searches: 310 us spikes in round 2.
+	const int from = launch_sort(d,
+		[&](auto chunk) { hipLaunchKernelGGL((k_records_sort<decltype(chunk)::value>), dim3(d.Kpad / chunk), dim3(chunk / 2), 0, st, d, d_values); },
+		[&](int L, int src) { hipLaunchKernelGGL(k_merge_pass, dim3(blocks(d.Kpad)), dim3(256), 0, st, d, L, src); });
+	// With 32 workgroups at N = 100 the occasional level merge (up to the whole open set) ran 32 records per thread, each a chain of
+	// dependent binary searches: 310 us spikes in round 2.
 	static const unsigned min_grid = [] { const char *e = std::getenv("RK_INSERT_MIN_GRID"); return e ? (unsigned)std::atoi(e) : 512u; }();
 	// (512 workgroups, two per CU, also are what the usual merge at N = 1000 -- 30 000 records -- runs fastest on: 256 / 384 / 512 / 768 /
 	//  1024 workgroups: 14.3 / 13.5 / 12.2 / 12.8 / 16.8 us, every workgroup pays the plan and the coarse index before it merges)
-	const unsigned grid = std::min<unsigned>(1024u, std::max<unsigned>(blocks((size_t)d.Kpad * 4), min_grid));
-	hipLaunchKernelGGL((k_queue_insert<SHARDED>), dim3(grid), dim3(256), 0, st, d, from);
+	hipLaunchKernelGGL((k_queue_insert<SHARDED>), dim3(insert_grid(d, min_grid)), dim3(256), 0, st, d, from);
 	if (!SHARDED) {
 		hipLaunchKernelGGL((k_end<false>), dim3(1), dim3(1024), 0, st, d, from, 1, 0);
-		if (pop_is_wide_host(d)) hipLaunchKernelGGL(k_pop_wide, dim3(blocks((size_t)d.q.levels * d.N)), dim3(256), 0, st, d);
+		if (pop_is_wide_host(d)) hipLaunchKernelGGL(k_pop_wide, dim3(pop_wide_grid(d)), dim3(256), 0, st, d);
 	}
-	(void)recv;
 	return from;
 }
 
@@ -1507,50 +1526,35 @@ static int astar_create_impl(rk_astar_t **out, size_t capacity, int max_expansio
 	d.rank = rank; d.world = world;
 	d.N = max_expansions; d.K = 12 * max_expansions;
 	d.KI = d.K * world;                                   // a rank can receive every rank's children
-	const int kin = world == 1 ? d.K : d.KI;
 	// The NEW records of an iteration are at most K = 12 N on any rank, whatever the world size (all ranks together pop N nodes), so
 	// the sort / merge / insert geometry follows K.  (Rounds 2-4 sized it by the incoming SLOTS, world * K: at world 8 every
 	// iteration launched six merge passes over 33 mostly empty chunks where there are at most five chunks of records.)
 	d.chunk = d.K <= SORT_CHUNK ? SMALL_CHUNK : SORT_CHUNK;
 	d.Kpad = ((d.K + d.chunk - 1) / d.chunk) * d.chunk;
 	d.cap1 = (uint32_t)(capacity + 1);
-	uint64_t t = 1024;
-	while (t < 2 * (uint64_t)capacity + 2) t <<= 1;
+	const uint64_t t = table_slots(capacity, 1024);
 	d.mask = (uint32_t)(t - 1);
-	const size_t C1 = capacity + 1, KS = (size_t)kin + 64;
+	const size_t C1 = capacity + 1, KS = scan_slots(d);
 	int e = RK_OK;
-	#define A(ptr, cnt) if (!e) e = dev_alloc(h, &d.ptr, (cnt))
+	#define A(ptr, cnt) if (!e) e = h->pool.alloc(&d.ptr, (cnt))
 	A(states, C1 * 5); A(G, C1); A(parents, C1); A(pact, C1); A(prank, C1); A(table, (size_t)t); A(mark, C1);
 	A(ctr, C_COUNT);
 	A(exp_idx, (size_t)d.N + 8); A(cand_key, (size_t)d.N + 8); A(cand_level, (size_t)d.N + 8);
 	A(children, (size_t)d.K * 5 + 64); A(solved, (size_t)d.K + 64);
 	A(seen, KS); A(child_slot, KS); A(flags, KS); A(rank_local, 16); A(newway, KS); A(shortcut, KS); A(val1, KS); A(val2, KS);
 	A(rec0, (size_t)d.Kpad + 16); A(rec1, (size_t)d.Kpad + 16);
-	const size_t n_scan_blocks = (KS + ASCAN - 1) / ASCAN + 1;
+	const size_t n_scan_blocks = scan_blocks(d);
 	A(chain0, n_scan_blocks); A(chain1, n_scan_blocks * (size_t)world); A(chain2, n_scan_blocks * (size_t)world);
 	A(hit, KS); A(gather_in, (size_t)d.N + 16);
 	#undef A
-	// queue levels: 4 K, 16 K, 64 K, ... records, the top level holds the whole pool.  K here is what an iteration is expected to PUSH:
-	// 12 N on one GPU, 12 N / world on a rank of a sharded search (owner = hash).  Rounds 2-4 sized a rank's levels by its incoming
-	// SLOTS, world * 12 N: at 8 ranks level 0 held 64 iterations' worth of records and every push rewrote all of it -- 183 us of a
-	// rank's iteration in the weak-scaling run (benchmarks/sharded_sim8.py).  The sizes are tuning, not correctness: a push that does
-	// not fit level 0 goes to the first level that holds it (make_plan).
-	if (!e) e = dev_alloc(h, &d.q.meta, 4 * QL);
-	uint64_t c = std::max<uint64_t>(4ull * (uint64_t)queue_inflow(d), 4096ull);
-	int levels = 0;
-	for (; levels < QL && !e; levels++) {
-		const bool top = c >= C1 || levels == QL - 1;
-		const uint64_t cap_l = top ? C1 : c;
-		d.q.cap[levels] = (uint32_t)cap_l;
-		for (int k = 0; k < 2 && !e; k++) e = dev_alloc(h, &d.q.buf[levels][k], (size_t)cap_l + 16);
-		if (top) { levels++; break; }
-		c *= 4;
-	}
-	d.q.levels = levels;
-	if (!e) e = dev_alloc(h, &h->root_dev, 8);
-	if (!e) e = dev_alloc(h, &h->walk, WALK_MAX + 8);
-	if (!e) e = dev_alloc(h, &h->decision, D_COUNT);
-	if (!e && hipHostMalloc((void **)&h->ctr_host, C_COUNT * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); h->ctr_host = nullptr; }
+	if (!e) e = h->pool.alloc(&d.q.meta, 4 * QL);
+	d.q.levels = queue_plan(d, C1, d.q.cap);
+	for (int j = 0; j < d.q.levels; j++)
+		for (int k = 0; k < 2 && !e; k++) e = h->pool.alloc(&d.q.buf[j][k], (size_t)d.q.cap[j] + 16);
+	if (!e) e = h->pool.alloc(&h->root_dev, 8);
+	if (!e) e = h->pool.alloc(&h->walk, WALK_MAX + 8);
+	if (!e) e = h->pool.alloc(&h->decision, D_COUNT);
+	if (!e) h->ctr_host.reserve(C_COUNT);
 	if (!e) {
 		hipError_t he = hipMemset(d.chain0, 0, n_scan_blocks * sizeof(unsigned long long));
 		if (he == hipSuccess) he = hipMemset(d.chain1, 0, n_scan_blocks * world * sizeof(unsigned long long));
@@ -1574,10 +1578,7 @@ int rk_astar_create_sharded(rk_astar_t **out, size_t capacity, int max_expansion
 
 int rk_astar_destroy(rk_astar_t *h)
 {
-	if (!h) return RK_OK;
-	for (void *p : h->allocs) (void)hipFree(p);
-	if (h->ctr_host != nullptr) (void)hipHostFree(h->ctr_host);
-	delete h;
+	delete h;                     // the pool and the landing buffer go with it
 	return RK_OK;
 }
 
@@ -1588,7 +1589,7 @@ static int astar_reset_impl(rk_astar_t *h, const int8_t *h_start_state, double l
 	RK_HIP(hipMemsetAsync(d.table, 0, ((size_t)d.mask + 1) * sizeof(uint32_t), st));
 	RK_HIP(hipMemsetAsync(d.mark, 0xFF, (h->cap + 1) * sizeof(uint32_t), st));
 	// look-back epochs restart with the search: forget the words of the previous one
-	const size_t n_scan_blocks = ((size_t)(d.world == 1 ? d.K : d.KI) + 64 + ASCAN - 1) / ASCAN + 1;
+	const size_t n_scan_blocks = scan_blocks(d);
 	RK_HIP(hipMemsetAsync(d.chain0, 0, n_scan_blocks * sizeof(unsigned long long), st));
 	RK_HIP(hipMemsetAsync(d.chain1, 0, n_scan_blocks * d.world * sizeof(unsigned long long), st));
 	RK_HIP(hipMemsetAsync(d.chain2, 0, n_scan_blocks * d.world * sizeof(unsigned long long), st));
@@ -1640,70 +1641,41 @@ int rk_astar_grow(rk_astar_t *h, size_t new_capacity, void *stream)
 	AstarDev d = old;
 	const size_t C1 = new_capacity + 1, C1_old = h->cap + 1;
 	d.cap1 = (uint32_t)C1;
-	uint64_t t = 1024;
-	while (t < 2 * (uint64_t)new_capacity + 2) t <<= 1;
+	const uint64_t t = table_slots(new_capacity, 1024);
 	d.mask = (uint32_t)(t - 1);
-	std::vector<void *> fresh, stale;
-	auto get = [&](size_t bytes) -> void * { void *q = nullptr; if (hipMalloc(&q, bytes + 64) != hipSuccess) return nullptr; fresh.push_back(q); return q; };
-	bool ok = true;
-	#define RK_GROW(ptr, type, cnt) do { d.ptr = (type *)get((cnt) * sizeof(type)); ok = ok && d.ptr != nullptr; stale.push_back(old.ptr); } while (0)
-	RK_GROW(states, uint32_t, C1 * 5); RK_GROW(G, int32_t, C1); RK_GROW(parents, int32_t, C1); RK_GROW(pact, uint8_t, C1); RK_GROW(prank, uint8_t, C1);
-	RK_GROW(table, uint32_t, (size_t)t); RK_GROW(mark, uint32_t, C1);
-	#undef RK_GROW
-	// queue levels: capacities 4 K, 16 K, ... as at creation; a level whose capacity is unchanged keeps its buffers
-	uint64_t c = std::max<uint64_t>(4ull * (uint64_t)queue_inflow(d), 4096ull);
-	int levels = 0;
-	for (; levels < QL && ok; levels++) {
-		const bool top = c >= C1 || levels == QL - 1;
-		const uint64_t cap_l = top ? C1 : c;
-		if (levels >= old.q.levels || old.q.cap[levels] != (uint32_t)cap_l) {
-			d.q.cap[levels] = (uint32_t)cap_l;
-			for (int k = 0; k < 2; k++) {
-				d.q.buf[levels][k] = (Rec *)get(((size_t)cap_l + 16) * sizeof(Rec));
-				ok = ok && d.q.buf[levels][k] != nullptr;
-				if (levels < old.q.levels) stale.push_back(old.q.buf[levels][k]);
-			}
+	Growth g(h->pool, "rk_astar_grow");
+	g.request(&d.states, C1 * 5); g.request(&d.G, C1); g.request(&d.parents, C1); g.request(&d.pact, C1); g.request(&d.prank, C1);
+	g.request(&d.table, (size_t)t); g.request(&d.mark, C1);
+	// queue levels: capacities as at creation; a level whose capacity is unchanged keeps its buffers (a new level replaces nothing)
+	uint32_t cap[QL];
+	d.q.levels = queue_plan(d, C1, cap);
+	for (int j = 0; j < d.q.levels; j++) {
+		if (j < old.q.levels && old.q.cap[j] == cap[j]) continue;
+		d.q.cap[j] = cap[j];
+		for (int k = 0; k < 2; k++) {
+			if (j >= old.q.levels) d.q.buf[j][k] = nullptr;
+			g.request(&d.q.buf[j][k], (size_t)cap[j] + 16);
 		}
-		if (top) { levels++; break; }
-		c *= 4;
 	}
-	d.q.levels = levels;
-	if (!ok) {
-		for (void *q : fresh) (void)hipFree(q);
-		(void)hipGetLastError();
-		return fail(RK_ECAPACITY, "rk_astar_grow: no device memory for a pool of %zu states", new_capacity);
-	}
+	if (!g.granted()) return fail(RK_ECAPACITY, "rk_astar_grow: no device memory for a pool of %zu states", new_capacity);
 	// the copies and the rehash; an error in here leaves the engine as it was (the new arrays are given back)
-	auto fill = [&]() -> hipError_t {
-		#define RK_TRY(call) do { const hipError_t e_ = (call); if (e_ != hipSuccess) return e_; } while (0)
-		RK_TRY(hipMemcpyAsync(d.states, old.states, C1_old * STATE_BYTES, hipMemcpyDeviceToDevice, st));
-		RK_TRY(hipMemcpyAsync(d.G, old.G, C1_old * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-		RK_TRY(hipMemcpyAsync(d.parents, old.parents, C1_old * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-		RK_TRY(hipMemcpyAsync(d.pact, old.pact, C1_old, hipMemcpyDeviceToDevice, st));
-		RK_TRY(hipMemcpyAsync(d.prank, old.prank, C1_old, hipMemcpyDeviceToDevice, st));
-		RK_TRY(hipMemsetAsync(d.table, 0, (size_t)t * sizeof(uint32_t), st));
-		RK_TRY(hipMemsetAsync(d.mark, 0xFF, C1 * sizeof(uint32_t), st));       // between iterations every mark is NO_MARK
+	const int e = g.fill(st, [&]() -> hipError_t {
+		RK_FILL(hipMemcpyAsync(d.states, old.states, C1_old * STATE_BYTES, hipMemcpyDeviceToDevice, st));
+		RK_FILL(hipMemcpyAsync(d.G, old.G, C1_old * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+		RK_FILL(hipMemcpyAsync(d.parents, old.parents, C1_old * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+		RK_FILL(hipMemcpyAsync(d.pact, old.pact, C1_old, hipMemcpyDeviceToDevice, st));
+		RK_FILL(hipMemcpyAsync(d.prank, old.prank, C1_old, hipMemcpyDeviceToDevice, st));
+		RK_FILL(hipMemsetAsync(d.table, 0, (size_t)t * sizeof(uint32_t), st));
+		RK_FILL(hipMemsetAsync(d.mark, 0xFF, C1 * sizeof(uint32_t), st));      // between iterations every mark is NO_MARK
 		for (int j = 0; j < old.q.levels; j++)                                 // a level that moved: both halves as they are
 			for (int k = 0; k < 2; k++)
 				if (d.q.buf[j][k] != old.q.buf[j][k])
-					RK_TRY(hipMemcpyAsync(d.q.buf[j][k], old.q.buf[j][k], (size_t)old.q.cap[j] * sizeof(Rec), hipMemcpyDeviceToDevice, st));
+					RK_FILL(hipMemcpyAsync(d.q.buf[j][k], old.q.buf[j][k], (size_t)old.q.cap[j] * sizeof(Rec), hipMemcpyDeviceToDevice, st));
 		hipLaunchKernelGGL(k_astar_rehash, dim3(std::min<unsigned>(blocks(C1_old), 4096u)), dim3(256), 0, st, d);
-		RK_TRY(hipGetLastError());
-		RK_TRY(hipStreamSynchronize(st));
-		#undef RK_TRY
-		return hipSuccess;
-	};
-	if (const hipError_t e = fill(); e != hipSuccess) {
-		(void)hipStreamSynchronize(st);                                        // nothing may still write into what is freed next
-		for (void *q : fresh) (void)hipFree(q);
-		(void)hipGetLastError();
-		return fail(RK_EHIP, "rk_astar_grow: %s", hipGetErrorString(e));
-	}
-	for (void *q : stale) {
-		for (size_t i = 0; i < h->allocs.size(); i++) if (h->allocs[i] == q) { h->allocs.erase(h->allocs.begin() + (long)i); break; }
-		(void)hipFree(q);
-	}
-	for (void *q : fresh) h->allocs.push_back(q);
+		return hipGetLastError();
+	});
+	if (e) return e;
+	g.commit();
 	h->d = d;
 	h->cap = new_capacity;
 	return RK_OK;
@@ -1738,7 +1710,7 @@ int rk_astar_step_commit(rk_astar_t *h, const float *d_values, void *stream)
 	if (!h || !h->pending) return fail(RK_ESTATE, "rk_astar_step_commit: no pending iteration");
 	if (h->d.world != 1) return fail(RK_ESTATE, "rk_astar_step_commit: sharded engines use rk_astar_shard_push");
 	if (!d_values) return fail(RK_EINVAL, "rk_astar_step_commit: null values");
-	launch_commit<false>(h, d_values, nullptr, (hipStream_t)stream);
+	launch_commit<false>(h, d_values, (hipStream_t)stream);
 	RK_HIP(hipGetLastError());
 	h->pending = false;
 	return RK_OK;
@@ -1767,7 +1739,7 @@ int rk_astar_expand(rk_astar_t *h, int n_expand, long long *h_info, void *stream
 	int32_t c[C_COUNT];
 	if (n_expand != h->n_exp) {
 		hipLaunchKernelGGL(k_pop_select_only, dim3(1), dim3(1024), 0, st, h->d, n_expand);
-		if (pop_is_wide_host(h->d)) hipLaunchKernelGGL(k_pop_wide, dim3(blocks((size_t)h->d.q.levels * h->d.N)), dim3(256), 0, st, h->d);
+		if (pop_is_wide_host(h->d)) hipLaunchKernelGGL(k_pop_wide, dim3(pop_wide_grid(h->d)), dim3(256), 0, st, h->d);
 		h->n_exp = n_expand;
 	}
 	if (!h->budget_explicit) {
@@ -1820,12 +1792,7 @@ long long rk_astar_next_pops(rk_astar_t *h, long long *h_indices, size_t max_len
 	int32_t c[C_COUNT];
 	if (int e = read_ctr(h, c, st)) return e;
 	const size_t n = std::min<size_t>((size_t)c[C_NPOP], max_len);
-	std::vector<int32_t> idx(n);
-	if (n) {
-		RK_HIP(hipMemcpyAsync(idx.data(), h->d.exp_idx, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-		RK_HIP(hipStreamSynchronize(st));
-	}
-	for (size_t i = 0; i < n; i++) h_indices[i] = idx[i];
+	if (int e = export_widened(h->d.exp_idx, n, h_indices, st)) return e;
 	return (long long)n;
 }
 
@@ -1855,18 +1822,15 @@ int rk_astar_export(rk_astar_t *h, size_t first, size_t count, int8_t *h_states,
 	if (count == 0) return RK_OK;
 	hipStream_t st = (hipStream_t)stream;
 	const AstarDev &d = h->d;
-	std::vector<int32_t> g, p;
-	std::vector<uint8_t> a;
+	Widened<int32_t, double> g;
+	Widened<int32_t, long long> p;
+	Widened<uint8_t, long long> a;
 	if (h_states) RK_HIP(hipMemcpyAsync(h_states, d.states + first * 5, count * STATE_BYTES, hipMemcpyDeviceToHost, st));
-	if (h_G) { g.resize(count); RK_HIP(hipMemcpyAsync(g.data(), d.G + first, count * sizeof(int32_t), hipMemcpyDeviceToHost, st)); }
-	if (h_parents) { p.resize(count); RK_HIP(hipMemcpyAsync(p.data(), d.parents + first, count * sizeof(int32_t), hipMemcpyDeviceToHost, st)); }
-	if (h_parent_actions) { a.resize(count); RK_HIP(hipMemcpyAsync(a.data(), d.pact + first, count, hipMemcpyDeviceToHost, st)); }
+	if (int e = g.start(d.G + first, count, h_G, st)) return e;
+	if (int e = p.start(d.parents + first, count, h_parents, st)) return e;
+	if (int e = a.start(d.pact + first, count, h_parent_actions, st)) return e;
 	RK_HIP(hipStreamSynchronize(st));
-	for (size_t i = 0; i < count; i++) {
-		if (h_G) h_G[i] = (double)g[i];
-		if (h_parents) h_parents[i] = p[i];
-		if (h_parent_actions) h_parent_actions[i] = a[i];
-	}
+	g.finish(); p.finish(); a.finish();
 	return RK_OK;
 }
 
@@ -1878,16 +1842,8 @@ long long rk_astar_path(rk_astar_t *h, long long index, long long *h_actions, si
 	hipLaunchKernelGGL(k_astar_walk, dim3(1), dim3(64), 0, st, h->d, (int)index, h->walk, WALK_MAX);
 	RK_HIP(hipGetLastError());
 	int32_t len = 0;
-	RK_HIP(hipMemcpyAsync(&len, h->walk, sizeof len, hipMemcpyDeviceToHost, st));
-	RK_HIP(hipStreamSynchronize(st));
+	if (int e = read_walk(h->walk, WALK_MAX, h_actions, max_len, st, &len)) return e;
 	if (len < 0) return fail(RK_ESTATE, "rk_astar_path: broken parent chain");
-	const size_t n = std::min<size_t>(std::min<size_t>((size_t)len, max_len), (size_t)WALK_MAX);
-	std::vector<int32_t> acts(n);
-	if (n) {
-		RK_HIP(hipMemcpyAsync(acts.data(), h->walk + 1, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-		RK_HIP(hipStreamSynchronize(st));
-	}
-	for (size_t k = 0; k < n; k++) h_actions[k] = acts[k];
 	return (long long)len;
 }
 
@@ -2041,7 +1997,7 @@ static int shard_push_impl(rk_astar_t *h, const float *d_values, int rows, const
 		if (rows <= SORT_CHUNK) d.chunk = SMALL_CHUNK;
 		d.Kpad = std::min(d.Kpad, ((rows + d.chunk - 1) / d.chunk) * d.chunk);
 	}
-	const int from = launch_commit<true>(h, d_values, (const uint8_t *)d_recv, st, &d);
+	const int from = launch_commit<true>(h, d_values, st, &d);
 	hipLaunchKernelGGL(k_shard_offers, dim3(blocks((size_t)d.K, ASCAN)), dim3(ASCAN), 0, st, d, (const uint8_t *)d_recv, (uint8_t *)d_send);
 	hipLaunchKernelGGL((k_end<true>), dim3(1), dim3(1024), 0, st, d, from, 1, rows == d.K ? 0 : rows);
 	launch_shard_wide_selection(d, st);
@@ -2103,11 +2059,7 @@ int rk_astar_shard_export_ranks(rk_astar_t *h, size_t first, size_t count, long 
 	if (!h || !h_parent_ranks) return fail(RK_EINVAL, "rk_astar_shard_export_ranks: null argument");
 	if (first + count > h->cap + 1) return fail(RK_EINVAL, "rk_astar_shard_export_ranks: rows %zu..%zu outside the pool", first, first + count);
 	if (count == 0) return RK_OK;
-	std::vector<uint8_t> r(count);
-	RK_HIP(hipMemcpyAsync(r.data(), h->d.prank + first, count, hipMemcpyDeviceToHost, (hipStream_t)stream));
-	RK_HIP(hipStreamSynchronize((hipStream_t)stream));
-	for (size_t i = 0; i < count; i++) h_parent_ranks[i] = r[i];
-	return RK_OK;
+	return export_widened(h->d.prank + first, count, h_parent_ranks, (hipStream_t)stream);
 }
 
 // ================================================================================================================
@@ -2125,6 +2077,7 @@ struct rk_astarb {
 	AstarDev *devs = nullptr;                     // device copy of every engine's descriptor
 	int32_t *row_off = nullptr;                   // compact mode: S + 1 row offsets of the pending step
 	bool ready = false, pending = false, compact = false;
+	DevPool pool{0};
 };
 
 static int astarb_upload(rk_astarb *b, hipStream_t st)
@@ -2152,8 +2105,7 @@ int rk_astarb_create(rk_astarb_t **out, int n_searches, size_t capacity_per_sear
 		if (rc) { rk_astarb_destroy(b); return rc; }
 		b->eng.push_back(e);
 	}
-	if (hipMalloc((void **)&b->devs, (size_t)n_searches * sizeof(AstarDev)) != hipSuccess ||
-	    hipMalloc((void **)&b->row_off, ((size_t)n_searches + 1) * sizeof(int32_t)) != hipSuccess) {
+	if (b->pool.alloc(&b->devs, (size_t)n_searches) || b->pool.alloc(&b->row_off, (size_t)n_searches + 1)) {
 		rk_astarb_destroy(b);
 		return fail(RK_EHIP, "rk_astarb_create: hipMalloc failed");
 	}
@@ -2165,9 +2117,7 @@ int rk_astarb_destroy(rk_astarb_t *b)
 {
 	if (!b) return RK_OK;
 	for (rk_astar *e : b->eng) rk_astar_destroy(e);
-	(void)hipFree(b->devs);
-	(void)hipFree(b->row_off);
-	delete b;
+	delete b;                                     // the descriptors and row offsets go with its pool
 	return RK_OK;
 }
 
@@ -2243,14 +2193,9 @@ static int astarb_step_expand_impl(rk_astarb_t *b, void *d_onehot, int out_dtype
 		RK_HIP(hipMemcpyAsync(h_total, b->row_off + b->S, sizeof(int32_t), hipMemcpyDeviceToHost, st));
 		row_off = b->row_off;
 	}
-	const size_t chunks = (size_t)d.K * (out_dtype == RK_OH_F32 ? 120 : out_dtype == RK_OH_STATES ? 2 : 60);
-	const unsigned grid = std::min<unsigned>(blocks(chunks), 8192u);
-	if (out_dtype == RK_OH_F32)
-		hipLaunchKernelGGL((kb_new_rows<4, false>), dim3(grid, S), dim3(256), 0, st, b->devs, (u32x4 *)d_onehot, 0x3F800000u, (const uint8_t *)nullptr, row_off);
-	else if (out_dtype == RK_OH_STATES)
-		hipLaunchKernelGGL((kb_new_rows<0, false>), dim3(grid, S), dim3(256), 0, st, b->devs, (u32x4 *)d_onehot, 0u, (const uint8_t *)nullptr, row_off);
-	else
-		hipLaunchKernelGGL((kb_new_rows<2, false>), dim3(grid, S), dim3(256), 0, st, b->devs, (u32x4 *)d_onehot, out_dtype == RK_OH_F16 ? 0x3C00u : 0x3F80u, (const uint8_t *)nullptr, row_off);
+	launch_new_rows(d, true, out_dtype, [&](auto eb, unsigned grid, uint32_t one) {
+		hipLaunchKernelGGL((kb_new_rows<decltype(eb)::value, false>), dim3(grid, S), dim3(256), 0, st, b->devs, (u32x4 *)d_onehot, one, (const uint8_t *)nullptr, row_off);
+	});
 	RK_HIP(hipGetLastError());
 	b->pending = true;
 	b->compact = h_total != nullptr;
@@ -2264,21 +2209,13 @@ int rk_astarb_step_commit(rk_astarb_t *b, const float *d_values, void *stream)
 	hipStream_t st = (hipStream_t)stream;
 	const AstarDev &d = b->eng[0]->d;
 	const unsigned S = (unsigned)b->S;
-	int from = 0;
 	const int32_t *row_off = b->compact ? b->row_off : nullptr;
-	if (d.chunk == SMALL_CHUNK) {
-		hipLaunchKernelGGL((kb_records_sort<SMALL_CHUNK>), dim3(d.Kpad / SMALL_CHUNK, S), dim3(SMALL_CHUNK / 2), 0, st, b->devs, d_values, row_off);
-	} else {
-		hipLaunchKernelGGL((kb_records_sort<SORT_CHUNK>), dim3(d.Kpad / SORT_CHUNK, S), dim3(SORT_CHUNK / 2), 0, st, b->devs, d_values, row_off);
-		for (int L = SORT_CHUNK; L < d.Kpad && new_chunk_of(d.chunk, d.Kpad) == 0; L <<= 1) {
-			hipLaunchKernelGGL(kb_merge_pass, dim3(blocks(d.Kpad), S), dim3(256), 0, st, b->devs, L, from);
-			from ^= 1;
-		}
-	}
-	const unsigned grid = std::min<unsigned>(1024u, std::max<unsigned>(blocks((size_t)d.Kpad * 4), 8u));
-	hipLaunchKernelGGL((kb_queue_insert<false>), dim3(grid, S), dim3(256), 0, st, b->devs, from);
+	const int from = launch_sort(d,
+		[&](auto chunk) { hipLaunchKernelGGL((kb_records_sort<decltype(chunk)::value>), dim3(d.Kpad / chunk, S), dim3(chunk / 2), 0, st, b->devs, d_values, row_off); },
+		[&](int L, int src) { hipLaunchKernelGGL(kb_merge_pass, dim3(blocks(d.Kpad), S), dim3(256), 0, st, b->devs, L, src); });
+	hipLaunchKernelGGL((kb_queue_insert<false>), dim3(insert_grid(d, 8u), S), dim3(256), 0, st, b->devs, from);
 	hipLaunchKernelGGL((kb_end<false>), dim3(1, S), dim3(1024), 0, st, b->devs, from, 1);
-	if (pop_is_wide_host(d)) hipLaunchKernelGGL(kb_pop_wide, dim3(blocks((size_t)d.q.levels * d.N), S), dim3(256), 0, st, b->devs);
+	if (pop_is_wide_host(d)) hipLaunchKernelGGL(kb_pop_wide, dim3(pop_wide_grid(d), S), dim3(256), 0, st, b->devs);
 	RK_HIP(hipGetLastError());
 	b->pending = false;
 	return RK_OK;

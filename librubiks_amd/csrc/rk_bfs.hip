@@ -38,6 +38,7 @@
 #include "rk_device.h"
 #include "rk_error.h"
 #include "rk_search_dev.h"
+#include "rk_search_host.h"
 
 namespace rk {
 
@@ -235,13 +236,7 @@ __global__ void k_bfs_end(BfsDev d)
 __global__ __launch_bounds__(256)
 void k_bfs_rehash(BfsDev d)
 {
-	const int n = d.ctr[B_SIZE];
-	for (int idx = 1 + blockIdx.x * blockDim.x + threadIdx.x; idx <= n; idx += gridDim.x * blockDim.x) {
-		uint32_t s[5];
-		load5(d.states + (size_t)idx * 5, s);
-		uint32_t slot = hash_state(s) & d.mask;
-		while (atomicCAS(&d.table[slot], 0u, (uint32_t)idx) != 0u) slot = (slot + 1) & d.mask;
-	}
+	rehash_pool(d.states, d.table, d.mask, d.ctr[B_SIZE], 1 + blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
 }
 
 // the action queue of a won search: the path to the winner's parent, then the winner's action (agents.py:114-117).
@@ -275,44 +270,20 @@ struct rk_bfs {
 	size_t cap = 0;
 	uint32_t *root_dev = nullptr;
 	int32_t *walk = nullptr;
-	int32_t *ctr_host = nullptr;                // page-locked landing place of the counter block
+	Landing ctr_host;                           // page-locked landing place of the counter block
 	bool ready = false;
-	std::vector<void *> allocs;
+	DevPool pool{64};
 };
 
 namespace {
 
 constexpr int BFS_WALK_MAX = 1 << 12;
 
-template <typename T>
-int bfs_alloc(rk_bfs *h, T **p, size_t count)
-{
-	void *q = nullptr;
-	RK_HIP(hipMalloc(&q, count * sizeof(T) + 64));
-	h->allocs.push_back(q);
-	*p = static_cast<T *>(q);
-	return RK_OK;
-}
+uint32_t bfs_table_mask(size_t capacity) { return (uint32_t)(table_slots(capacity, 1024) - 1); }
 
-inline unsigned bfs_blocks(size_t n, unsigned per = 256) { return (unsigned)((n + per - 1) / per); }
+size_t bfs_scan_blocks(int pops) { return (size_t)blocks((size_t)12 * pops, ASCAN) + 1; }
 
-uint32_t bfs_table_mask(size_t capacity)
-{
-	uint64_t t = 1024;
-	while (t < 2 * (uint64_t)capacity + 2) t <<= 1;
-	return (uint32_t)(t - 1);
-}
-
-size_t bfs_scan_blocks(int pops) { return (size_t)bfs_blocks((size_t)12 * pops, ASCAN) + 1; }
-
-int bfs_read_ctr(rk_bfs *h, int32_t *out, hipStream_t st)
-{
-	int32_t *dst = h->ctr_host != nullptr ? h->ctr_host : out;
-	RK_HIP(hipMemcpyAsync(dst, h->d.ctr, B_COUNT * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-	RK_HIP(hipStreamSynchronize(st));
-	if (dst != out) memcpy(out, dst, B_COUNT * sizeof(int32_t));
-	return RK_OK;
-}
+int bfs_read_ctr(rk_bfs *h, int32_t *out, hipStream_t st) { return h->ctr_host.read(h->d.ctr, B_COUNT, out, st); }
 
 int bfs_budget_of(long long max_states) { return (int)std::min<long long>(std::max<long long>(max_states, 0), INT_MAX); }
 
@@ -333,13 +304,13 @@ int rk_bfs_create(rk_bfs_t **out, size_t capacity, int pops)
 	d.mask = bfs_table_mask(capacity);
 	const size_t C1 = capacity + 1, K = (size_t)12 * pops;
 	int e = RK_OK;
-	#define A(ptr, cnt) if (!e) e = bfs_alloc(h, &d.ptr, (cnt))
+	#define A(ptr, cnt) if (!e) e = h->pool.alloc(&d.ptr, (cnt))
 	A(states, C1 * 5); A(parent, C1); A(pact, C1); A(table, (size_t)d.mask + 1); A(ctr, B_COUNT);
 	A(slot, K); A(rank, K); A(first, K); A(chain, bfs_scan_blocks(pops));
 	#undef A
-	if (!e) e = bfs_alloc(h, &h->root_dev, 8);
-	if (!e) e = bfs_alloc(h, &h->walk, BFS_WALK_MAX + 8);
-	if (!e && hipHostMalloc((void **)&h->ctr_host, B_COUNT * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); h->ctr_host = nullptr; }
+	if (!e) e = h->pool.alloc(&h->root_dev, 8);
+	if (!e) e = h->pool.alloc(&h->walk, BFS_WALK_MAX + 8);
+	if (!e) h->ctr_host.reserve(B_COUNT);
 	if (e) { rk_bfs_destroy(h); return e; }
 	*out = h;
 	return RK_OK;
@@ -347,10 +318,7 @@ int rk_bfs_create(rk_bfs_t **out, size_t capacity, int pops)
 
 int rk_bfs_destroy(rk_bfs_t *h)
 {
-	if (!h) return RK_OK;
-	for (void *p : h->allocs) (void)hipFree(p);
-	if (h->ctr_host != nullptr) (void)hipHostFree(h->ctr_host);
-	delete h;
+	delete h;                                   // the pool and the landing buffer go with it
 	return RK_OK;
 }
 
@@ -380,7 +348,7 @@ int rk_bfs_set_budget(rk_bfs_t *h, long long max_states, void *stream)
 		// the table.  A search that goes on would take them for claims of ITS batch positions: rebuild the table from the pool first.
 		const BfsDev &d = h->d;
 		RK_HIP(hipMemsetAsync(d.table, 0, ((size_t)d.mask + 1) * sizeof(uint32_t), st));
-		hipLaunchKernelGGL(k_bfs_rehash, dim3(std::max<unsigned>(1u, std::min<unsigned>(bfs_blocks((size_t)c[B_SIZE] + 1), 4096u))), dim3(256), 0, st, d);
+		hipLaunchKernelGGL(k_bfs_rehash, dim3(std::max<unsigned>(1u, std::min<unsigned>(blocks((size_t)c[B_SIZE] + 1), 4096u))), dim3(256), 0, st, d);
 		RK_HIP(hipGetLastError());
 	}
 	hipLaunchKernelGGL(k_bfs_set_budget, dim3(1), dim3(64), 0, st, h->d, bfs_budget_of(max_states));
@@ -394,10 +362,10 @@ int rk_bfs_run(rk_bfs_t *h, int iterations, void *stream)
 	if (iterations < 0) return fail(RK_EINVAL, "rk_bfs_run: iterations %d < 0", iterations);
 	hipStream_t st = (hipStream_t)stream;
 	const BfsDev &d = h->d;
-	const unsigned grid = bfs_blocks((size_t)12 * d.pops);
+	const unsigned grid = blocks((size_t)12 * d.pops);
 	for (int it = 0; it < iterations; it++) {
 		hipLaunchKernelGGL(k_bfs_expand, dim3(grid), dim3(256), 0, st, d);
-		hipLaunchKernelGGL(k_bfs_scan, dim3(bfs_blocks((size_t)12 * d.pops, ASCAN)), dim3(ASCAN), 0, st, d);
+		hipLaunchKernelGGL(k_bfs_scan, dim3(blocks((size_t)12 * d.pops, ASCAN)), dim3(ASCAN), 0, st, d);
 		hipLaunchKernelGGL(k_bfs_append, dim3(grid), dim3(256), 0, st, d);
 		hipLaunchKernelGGL(k_bfs_end, dim3(1), dim3(64), 0, st, d);
 	}
@@ -426,40 +394,19 @@ int rk_bfs_grow(rk_bfs_t *h, size_t new_capacity, void *stream)
 	const size_t C1 = new_capacity + 1, C1_old = h->cap + 1;
 	d.cap1 = (uint32_t)C1;
 	d.mask = bfs_table_mask(new_capacity);
-	std::vector<void *> fresh, stale;
-	auto get = [&](size_t bytes) -> void * { void *q = nullptr; if (hipMalloc(&q, bytes + 64) != hipSuccess) return nullptr; fresh.push_back(q); return q; };
-	bool ok = true;
-	#define RK_GROW(ptr, type, cnt) do { d.ptr = (type *)get((cnt) * sizeof(type)); ok = ok && d.ptr != nullptr; stale.push_back(old.ptr); } while (0)
-	RK_GROW(states, uint32_t, C1 * 5); RK_GROW(parent, int32_t, C1); RK_GROW(pact, uint8_t, C1); RK_GROW(table, uint32_t, (size_t)d.mask + 1);
-	#undef RK_GROW
-	if (!ok) {
-		for (void *q : fresh) (void)hipFree(q);
-		(void)hipGetLastError();
-		return fail(RK_ECAPACITY, "rk_bfs_grow: no device memory for a pool of %zu states", new_capacity);
-	}
-	auto fill = [&]() -> hipError_t {
-		#define RK_TRY(call) do { const hipError_t e_ = (call); if (e_ != hipSuccess) return e_; } while (0)
-		RK_TRY(hipMemcpyAsync(d.states, old.states, C1_old * STATE_BYTES, hipMemcpyDeviceToDevice, st));
-		RK_TRY(hipMemcpyAsync(d.parent, old.parent, C1_old * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-		RK_TRY(hipMemcpyAsync(d.pact, old.pact, C1_old, hipMemcpyDeviceToDevice, st));
-		RK_TRY(hipMemsetAsync(d.table, 0, ((size_t)d.mask + 1) * sizeof(uint32_t), st));
-		hipLaunchKernelGGL(k_bfs_rehash, dim3(std::min<unsigned>(bfs_blocks(C1_old), 4096u)), dim3(256), 0, st, d);
-		RK_TRY(hipGetLastError());
-		RK_TRY(hipStreamSynchronize(st));
-		#undef RK_TRY
-		return hipSuccess;
-	};
-	if (const hipError_t e = fill(); e != hipSuccess) {
-		(void)hipStreamSynchronize(st);
-		for (void *q : fresh) (void)hipFree(q);
-		(void)hipGetLastError();
-		return fail(RK_EHIP, "rk_bfs_grow: %s", hipGetErrorString(e));
-	}
-	for (void *q : stale) {
-		for (size_t i = 0; i < h->allocs.size(); i++) if (h->allocs[i] == q) { h->allocs.erase(h->allocs.begin() + (long)i); break; }
-		(void)hipFree(q);
-	}
-	for (void *q : fresh) h->allocs.push_back(q);
+	Growth g(h->pool, "rk_bfs_grow");
+	g.request(&d.states, C1 * 5); g.request(&d.parent, C1); g.request(&d.pact, C1); g.request(&d.table, (size_t)d.mask + 1);
+	if (!g.granted()) return fail(RK_ECAPACITY, "rk_bfs_grow: no device memory for a pool of %zu states", new_capacity);
+	const int e = g.fill(st, [&]() -> hipError_t {
+		RK_FILL(hipMemcpyAsync(d.states, old.states, C1_old * STATE_BYTES, hipMemcpyDeviceToDevice, st));
+		RK_FILL(hipMemcpyAsync(d.parent, old.parent, C1_old * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+		RK_FILL(hipMemcpyAsync(d.pact, old.pact, C1_old, hipMemcpyDeviceToDevice, st));
+		RK_FILL(hipMemsetAsync(d.table, 0, ((size_t)d.mask + 1) * sizeof(uint32_t), st));
+		hipLaunchKernelGGL(k_bfs_rehash, dim3(std::min<unsigned>(blocks(C1_old), 4096u)), dim3(256), 0, st, d);
+		return hipGetLastError();
+	});
+	if (e) return e;
+	g.commit();
 	h->d = d;
 	h->cap = new_capacity;
 	return RK_OK;
@@ -481,16 +428,13 @@ int rk_bfs_export(rk_bfs_t *h, size_t first, size_t count, int8_t *h_states, lon
 	if (count == 0) return RK_OK;
 	hipStream_t st = (hipStream_t)stream;
 	const BfsDev &d = h->d;
-	std::vector<int32_t> p;
-	std::vector<uint8_t> a;
+	Widened<int32_t, long long> p;
+	Widened<uint8_t, long long> a;
 	if (h_states) RK_HIP(hipMemcpyAsync(h_states, d.states + first * 5, count * STATE_BYTES, hipMemcpyDeviceToHost, st));
-	if (h_parents) { p.resize(count); RK_HIP(hipMemcpyAsync(p.data(), d.parent + first, count * sizeof(int32_t), hipMemcpyDeviceToHost, st)); }
-	if (h_actions) { a.resize(count); RK_HIP(hipMemcpyAsync(a.data(), d.pact + first, count, hipMemcpyDeviceToHost, st)); }
+	if (int e = p.start(d.parent + first, count, h_parents, st)) return e;
+	if (int e = a.start(d.pact + first, count, h_actions, st)) return e;
 	RK_HIP(hipStreamSynchronize(st));
-	for (size_t i = 0; i < count; i++) {
-		if (h_parents) h_parents[i] = p[i];
-		if (h_actions) h_actions[i] = a[i];
-	}
+	p.finish(); a.finish();
 	return RK_OK;
 }
 
@@ -502,16 +446,8 @@ long long rk_bfs_path(rk_bfs_t *h, long long *h_actions, size_t max_len, void *s
 	hipLaunchKernelGGL(k_bfs_walk, dim3(1), dim3(64), 0, st, h->d, h->walk, BFS_WALK_MAX);
 	RK_HIP(hipGetLastError());
 	int32_t len = 0;
-	RK_HIP(hipMemcpyAsync(&len, h->walk, sizeof len, hipMemcpyDeviceToHost, st));
-	RK_HIP(hipStreamSynchronize(st));
+	if (int e = read_walk(h->walk, BFS_WALK_MAX, h_actions, max_len, st, &len)) return e;
 	if (len < 0) return fail(RK_ESTATE, "rk_bfs_path: the search has not won (or its parent chain is broken)");
-	const size_t n = std::min<size_t>(std::min<size_t>((size_t)len, max_len), (size_t)BFS_WALK_MAX);
-	std::vector<int32_t> acts(n);
-	if (n) {
-		RK_HIP(hipMemcpyAsync(acts.data(), h->walk + 1, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-		RK_HIP(hipStreamSynchronize(st));
-	}
-	for (size_t k = 0; k < n; k++) h_actions[k] = acts[k];
 	return (long long)len;
 }
 

@@ -29,6 +29,8 @@
 #include "rk_device.h"
 #include "rk_error.h"
 #include "rk_kernels.h"
+#include "rk_search_dev.h"
+#include "rk_search_host.h"
 
 namespace rk {
 
@@ -86,23 +88,6 @@ struct Node {
 __device__ __forceinline__ Node node_of(const MctsDev &d, size_t node0, int idx)
 {
 	return Node{d.nodes + (node0 + (size_t)idx) * NODE_BYTES};
-}
-
-__device__ __forceinline__ uint32_t mcts_hash(const uint32_t s[5])
-{
-	uint64_t h = 0x9E3779B97F4A7C15ull;
-	#pragma unroll
-	for (int j = 0; j < 5; j++) {
-		h ^= s[j];
-		h *= 0xFF51AFD7ED558CCDull;
-		h ^= h >> 29;
-	}
-	return (uint32_t)(h ^ (h >> 32));
-}
-
-__device__ __forceinline__ bool same5(const uint32_t a[5], const uint32_t *p)
-{
-	return ((a[0] ^ p[0]) | (a[1] ^ p[1]) | (a[2] ^ p[2]) | (a[3] ^ p[3]) | (a[4] ^ p[4])) == 0;
 }
 
 // ---- 16-lane reductions on the VALU (DPP row rotations) instead of through the LDS crossbar ----------------------
@@ -168,13 +153,12 @@ void k_mcts_root(MctsDev d, const uint32_t *starts, const int32_t *max_states)
 {
 	const int t = blockIdx.x, lane = threadIdx.x;
 	uint32_t s[5];
-	#pragma unroll
-	for (int j = 0; j < 5; j++) s[j] = starts[(size_t)t * 5 + j];
+	load5(starts + (size_t)t * 5, s);
 	if (lane == 0) {
 		uint32_t *st = d.states + ((size_t)t * d.cap1 + 1) * 5;
 		#pragma unroll
 		for (int j = 0; j < 5; j++) st[j] = s[j];
-		d.table[(size_t)t * (d.tmask + 1) + (mcts_hash(s) & d.tmask)] = 1u;
+		d.table[(size_t)t * (d.tmask + 1) + (hash_state(s) & d.tmask)] = 1u;
 		int32_t *tr = d.tree + (size_t)t * TR_INTS;
 		tr[TR_NSTATES] = 1;
 		tr[TR_MAXSTATES] = max_states[t];
@@ -221,21 +205,20 @@ __device__ __forceinline__ void expand_leaf_body(const MctsDev &d, const u32x4 *
 	}
 	const size_t node0 = (size_t)t * d.cap1;
 	uint32_t s[5];
-	#pragma unroll
-	for (int j = 0; j < 5; j++) s[j] = d.states[(node0 + leaf) * 5 + j];
+	load5(d.states + (node0 + leaf) * 5, s);
 	uint32_t tab[12];
 	load_action_table(s_act, active ? (uint32_t)lane : 0u, tab);
 	move5(s, tab);                                    // child `lane` of the leaf                  agents.py:513
 
 	// membership (agents.py:517-520)
 	uint32_t *table = d.table + (size_t)t * (d.tmask + 1);
-	uint32_t slot = mcts_hash(s) & d.tmask;
+	uint32_t slot = hash_state(s) & d.tmask;
 	int idx = 0;
 	if (active) {
 		for (;;) {
 			const uint32_t e = table[slot];
 			if (e == 0u) break;
-			if (same5(s, d.states + (node0 + e) * 5)) { idx = (int)e; break; }
+			if (equal5(s, d.states + (node0 + e) * 5)) { idx = (int)e; break; }
 			slot = (slot + 1) & d.tmask;
 		}
 	}
@@ -475,17 +458,9 @@ void k_mcts_backup_select(MctsDev d, const void *probs, const void *values, int 
 __global__ __launch_bounds__(256)
 void k_mcts_rehash(MctsDev d)
 {
-	const int t = blockIdx.y;
-	const int n = d.tree[(size_t)t * TR_INTS + TR_NSTATES];
-	const size_t node0 = (size_t)t * d.cap1;
-	uint32_t *table = d.table + (size_t)t * (d.tmask + 1);
-	for (int idx = 1 + blockIdx.x * blockDim.x + threadIdx.x; idx <= n; idx += gridDim.x * blockDim.x) {
-		uint32_t s[5];
-		#pragma unroll
-		for (int j = 0; j < 5; j++) s[j] = d.states[(node0 + idx) * 5 + j];
-		uint32_t slot = mcts_hash(s) & d.tmask;
-		while (atomicCAS(&table[slot], 0u, (uint32_t)idx) != 0u) slot = (slot + 1) & d.tmask;
-	}
+	const size_t t = blockIdx.y;
+	rehash_pool(d.states + t * d.cap1 * 5, d.table + t * (d.tmask + 1), d.tmask, d.tree[t * TR_INTS + TR_NSTATES],
+	            1 + blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
 }
 
 // New state budgets after a growth; a tree that had stopped at the loop guard only (agents.py:476: not solved, no error) and
@@ -525,17 +500,16 @@ void k_mcts_complete(MctsDev d)
 		const Node leaf = node_of(d, node0, idx);
 		if (a >= 12 || leaf.expanded()) continue;                          // np.where(self.leaves[:len(self)+1])[0][1:]
 		uint32_t s[5];
-		#pragma unroll
-		for (int j = 0; j < 5; j++) s[j] = d.states[(node0 + idx) * 5 + j];
+		load5(d.states + (node0 + idx) * 5, s);
 		uint32_t tab[12];
 		load_action_table(s_act, (uint32_t)a, tab);
 		move5(s, tab);
-		uint32_t slot = mcts_hash(s) & d.tmask;
+		uint32_t slot = hash_state(s) & d.tmask;
 		int child = 0;
 		for (;;) {
 			const uint32_t e = table[slot];
 			if (e == 0u) break;
-			if (same5(s, d.states + (node0 + e) * 5)) { child = (int)e; break; }
+			if (equal5(s, d.states + (node0 + e) * 5)) { child = (int)e; break; }
 			slot = (slot + 1) & d.tmask;
 		}
 		leaf.nb()[a] = child;                                              // agents.py:607 (0 = not in the graph)
@@ -551,7 +525,7 @@ void k_mcts_complete(MctsDev d)
 // order again and appends the winners -- in edge order, by an exclusive scan -- to the next frontier.  The first edge that
 // reaches the solved index is therefore exactly the one the reference's loop returns on.
 // Reads of words that other waves of the workgroup wrote go around the L1 (agent-scope atomic loads).
-struct BfsDev {
+struct GraphSearchDev {
 	uint32_t *claim;          // [T][cap1]  smallest edge number that reached the node (0xFFFFFFFF: none yet)
 	int32_t *from;            // [T][cap1]  BFS parent (0: not visited; the root holds -1)
 	uint8_t *act;             // [T][cap1]  action from the BFS parent
@@ -564,7 +538,7 @@ __device__ __forceinline__ int ld_i32(const int32_t *p) { return __hip_atomic_lo
 __device__ __forceinline__ uint32_t ld_u32(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 __global__ __launch_bounds__(1024)
-void k_mcts_bfs(MctsDev d, BfsDev b)
+void k_mcts_bfs(MctsDev d, GraphSearchDev b)
 {
 	__shared__ int s_wave[16];
 	__shared__ int s_count, s_found;
@@ -644,31 +618,19 @@ using namespace rk;
 struct rk_mcts {
 	MctsDev d{};
 	size_t capacity = 0;
-	std::vector<void *> allocs;
+	DevPool pool{16};
 	uint32_t *starts_dev = nullptr;
 	int32_t *max_states_dev = nullptr;
 	bool ready = false;
 	int ahead_limit = 0;          // rk_mcts_set_expand_ahead: 0 off, < 0 always, > 0 while the simulation number is below it
 	bool ahead = false;           // the last backup + select launch already expanded the leaves it found
-	int32_t *tree_host = nullptr; // page-locked landing place of the per-tree records: a status poll is one direct copy, no staging
-	BfsDev bfs{};                 // scratch of rk_mcts_search_graph, allocated at its first call (and again after a growth)
-	std::vector<void *> bfs_allocs;
+	Landing tree_host;            // page-locked landing place of the per-tree records: a status poll is one direct copy, no staging
+	GraphSearchDev bfs{};         // scratch of rk_mcts_search_graph, allocated at its first call (and again after a growth)
+	DevPool bfs_pool{16};
 	bool bfs_valid = false;       // rk_mcts_search_graph has run since the last reset / growth
 };
 
 namespace {
-
-template <typename T>
-int mcts_alloc(rk_mcts *h, T **p, size_t count)
-{
-	void *q = nullptr;
-	RK_HIP(hipMalloc(&q, count * sizeof(T) + 16));
-	h->allocs.push_back(q);
-	*p = static_cast<T *>(q);
-	return RK_OK;
-}
-
-inline unsigned nblocks(size_t n, unsigned per = 256) { return (unsigned)((n + per - 1) / per); }
 
 // is `st` recording into a hipGraph? (the legacy default stream cannot be)
 inline bool capturing(hipStream_t st)
@@ -706,22 +668,21 @@ int rk_mcts_create(rk_mcts_t **out, int n_trees, size_t capacity_per_tree, size_
 	MctsDev &d = h->d;
 	d.T = n_trees;
 	d.cap1 = (uint32_t)(capacity_per_tree + 1);
-	uint64_t ts = 64;
-	while (ts < 2ull * d.cap1) ts <<= 1;
+	const uint64_t ts = table_slots(capacity_per_tree, 64);
 	d.tmask = (uint32_t)(ts - 1);
 	d.max_path = (uint32_t)max_path;
 	const size_t T = (size_t)n_trees, rows = T * d.cap1;
 	int e = RK_OK;
-	#define A(ptr, cnt) if (!e) e = mcts_alloc(h, &d.ptr, (cnt))
+	#define A(ptr, cnt) if (!e) e = h->pool.alloc(&d.ptr, (cnt))
 	A(states, rows * 5); A(nodes, (rows + 1) * NODE_BYTES);
 	A(table, T * (size_t)ts);
 	A(path_nodes, T * max_path); A(path_actions, T * max_path);
 	A(tree, T * TR_INTS + 16);
 	A(children, T * 12 * 5 + 64); A(child_idx, T * 12); A(child_new, T * 12);
 	#undef A
-	if (!e) e = mcts_alloc(h, &h->starts_dev, T * 5);
-	if (!e) e = mcts_alloc(h, &h->max_states_dev, T);
-	if (!e && hipHostMalloc((void **)&h->tree_host, T * TR_INTS * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); h->tree_host = nullptr; }
+	if (!e) e = h->pool.alloc(&h->starts_dev, T * 5);
+	if (!e) e = h->pool.alloc(&h->max_states_dev, T);
+	if (!e) h->tree_host.reserve(T * TR_INTS);
 	if (e) { rk_mcts_destroy(h); return e; }
 	*out = h;
 	return RK_OK;
@@ -729,11 +690,7 @@ int rk_mcts_create(rk_mcts_t **out, int n_trees, size_t capacity_per_tree, size_
 
 int rk_mcts_destroy(rk_mcts_t *h)
 {
-	if (!h) return RK_OK;
-	for (void *p : h->allocs) (void)hipFree(p);
-	for (void *p : h->bfs_allocs) (void)hipFree(p);
-	if (h->tree_host != nullptr) (void)hipHostFree(h->tree_host);
-	delete h;
+	delete h;                                   // the pools and the landing buffer go with it
 	return RK_OK;
 }
 
@@ -781,28 +738,15 @@ int rk_mcts_grow(rk_mcts_t *h, size_t new_capacity, size_t new_max_path, const l
 	MctsDev d = old;
 	const size_t T = (size_t)d.T;
 	d.cap1 = (uint32_t)(new_capacity + 1);
-	uint64_t ts = 64;
-	while (ts < 2ull * d.cap1) ts <<= 1;
+	const uint64_t ts = table_slots(new_capacity, 64);
 	d.tmask = (uint32_t)(ts - 1);
 	d.max_path = (uint32_t)new_max_path;
 	const size_t rows = T * d.cap1;
-	std::vector<void *> fresh;
-	auto get = [&](size_t bytes) -> void * { void *q = nullptr; if (hipMalloc(&q, bytes + 16) != hipSuccess) return nullptr; fresh.push_back(q); return q; };
 	const bool pool = d.cap1 != old.cap1, paths = d.max_path != old.max_path;
-	if (pool) {
-		d.states = (uint32_t *)get(rows * 5 * sizeof(uint32_t));
-		d.nodes = (uint8_t *)get((rows + 1) * NODE_BYTES);
-		d.table = (uint32_t *)get(T * (size_t)ts * sizeof(uint32_t));
-	}
-	if (paths) {
-		d.path_nodes = (int32_t *)get(T * new_max_path * sizeof(int32_t));
-		d.path_actions = (uint8_t *)get(T * new_max_path);
-	}
-	if ((pool && (!d.states || !d.nodes || !d.table)) || (paths && (!d.path_nodes || !d.path_actions))) {
-		for (void *q : fresh) (void)hipFree(q);
-		(void)hipGetLastError();
-		return fail(RK_ECAPACITY, "rk_mcts_grow: no device memory for %d trees of %zu states", d.T, new_capacity);
-	}
+	Growth g(h->pool, "rk_mcts_grow");
+	if (pool) { g.request(&d.states, rows * 5); g.request(&d.nodes, (rows + 1) * NODE_BYTES); g.request(&d.table, T * (size_t)ts); }
+	if (paths) { g.request(&d.path_nodes, T * new_max_path); g.request(&d.path_actions, T * new_max_path); }
+	if (!g.granted()) return fail(RK_ECAPACITY, "rk_mcts_grow: no device memory for %d trees of %zu states", d.T, new_capacity);
 	std::vector<int32_t> ms(T);
 	for (size_t t = 0; t < T; t++) {
 		long long m = h_max_states ? h_max_states[t] : (long long)new_capacity;
@@ -810,48 +754,32 @@ int rk_mcts_grow(rk_mcts_t *h, size_t new_capacity, size_t new_max_path, const l
 		ms[t] = (int32_t)(m < 0 ? 0 : m);
 	}
 	// the copies, the rehash and the budgets; an error in here leaves the engine as it was (the new arrays are given back)
-	auto fill = [&]() -> hipError_t {
-		#define RK_TRY(call) do { const hipError_t e_ = (call); if (e_ != hipSuccess) return e_; } while (0)
+	const int e = g.fill(st, [&]() -> hipError_t {
 		if (pool) {
-			RK_TRY(hipMemsetAsync(d.nodes, 0, rows * NODE_BYTES, st));     // rows beyond the old pool: leaves, all statistics zero
-			RK_TRY(hipMemsetAsync(d.table, 0, T * (size_t)ts * sizeof(uint32_t), st));
-			RK_TRY(strided_copy(d.states, (size_t)d.cap1 * STATE_BYTES, old.states, (size_t)old.cap1 * STATE_BYTES, (size_t)old.cap1 * STATE_BYTES, T, st));
-			RK_TRY(strided_copy(d.nodes, (size_t)d.cap1 * NODE_BYTES, old.nodes, (size_t)old.cap1 * NODE_BYTES, (size_t)old.cap1 * NODE_BYTES, T, st));
+			RK_FILL(hipMemsetAsync(d.nodes, 0, rows * NODE_BYTES, st));     // rows beyond the old pool: leaves, all statistics zero
+			RK_FILL(hipMemsetAsync(d.table, 0, T * (size_t)ts * sizeof(uint32_t), st));
+			RK_FILL(strided_copy(d.states, (size_t)d.cap1 * STATE_BYTES, old.states, (size_t)old.cap1 * STATE_BYTES, (size_t)old.cap1 * STATE_BYTES, T, st));
+			RK_FILL(strided_copy(d.nodes, (size_t)d.cap1 * NODE_BYTES, old.nodes, (size_t)old.cap1 * NODE_BYTES, (size_t)old.cap1 * NODE_BYTES, T, st));
 		}
 		if (paths) {
-			RK_TRY(strided_copy(d.path_nodes, new_max_path * 4, old.path_nodes, (size_t)old.max_path * 4, (size_t)old.max_path * 4, T, st));
-			RK_TRY(strided_copy(d.path_actions, new_max_path, old.path_actions, (size_t)old.max_path, (size_t)old.max_path, T, st));
+			RK_FILL(strided_copy(d.path_nodes, new_max_path * 4, old.path_nodes, (size_t)old.max_path * 4, (size_t)old.max_path * 4, T, st));
+			RK_FILL(strided_copy(d.path_actions, new_max_path, old.path_actions, (size_t)old.max_path, (size_t)old.max_path, T, st));
 		}
 		if (pool) {
-			hipLaunchKernelGGL(k_mcts_rehash, dim3(std::min<unsigned>(nblocks(old.cap1), 4096u), d.T), dim3(256), 0, st, d);
-			RK_TRY(hipGetLastError());
+			hipLaunchKernelGGL(k_mcts_rehash, dim3(std::min<unsigned>(blocks(old.cap1), 4096u), d.T), dim3(256), 0, st, d);
+			RK_FILL(hipGetLastError());
 		}
-		RK_TRY(hipMemcpyAsync(h->max_states_dev, ms.data(), T * sizeof(int32_t), hipMemcpyHostToDevice, st));
-		hipLaunchKernelGGL(k_mcts_set_budgets, dim3(nblocks(T)), dim3(256), 0, st, d, h->max_states_dev);
-		RK_TRY(hipGetLastError());
-		RK_TRY(hipStreamSynchronize(st));                                  // `ms` and the old arrays go away now
-		#undef RK_TRY
-		return hipSuccess;
-	};
-	if (const hipError_t e = fill(); e != hipSuccess) {
-		(void)hipStreamSynchronize(st);                                    // nothing may still write into what is freed next
-		for (void *q : fresh) (void)hipFree(q);
-		(void)hipGetLastError();
-		return fail(RK_EHIP, "rk_mcts_grow: %s", hipGetErrorString(e));
-	}
-	auto drop = [&](void *q) {
-		for (size_t i = 0; i < h->allocs.size(); i++) if (h->allocs[i] == q) { h->allocs.erase(h->allocs.begin() + (long)i); break; }
-		(void)hipFree(q);
-	};
-	if (pool) { drop(old.states); drop(old.nodes); drop(old.table); }
-	if (paths) { drop(old.path_nodes); drop(old.path_actions); }
-	for (void *q : fresh) h->allocs.push_back(q);
+		RK_FILL(hipMemcpyAsync(h->max_states_dev, ms.data(), T * sizeof(int32_t), hipMemcpyHostToDevice, st));
+		hipLaunchKernelGGL(k_mcts_set_budgets, dim3(blocks(T)), dim3(256), 0, st, d, h->max_states_dev);
+		return hipGetLastError();                                          // (`ms` and the old arrays go away after the synchronisation)
+	});
+	if (e) return e;
+	g.commit();
 	h->d = d;
 	h->capacity = new_capacity;
 	h->ahead = false;                                                      // what is pending is decided on the device (TR_READY)
-	for (void *q : h->bfs_allocs) (void)hipFree(q);                        // sized by the pool: allocated again when next needed
-	h->bfs_allocs.clear();
-	h->bfs = BfsDev{};
+	h->bfs_pool.clear();                                                   // sized by the pool: allocated again when next needed
+	h->bfs = GraphSearchDev{};
 	h->bfs_valid = false;
 	return RK_OK;
 }
@@ -865,22 +793,18 @@ int rk_mcts_search_graph(rk_mcts_t *h, void *stream)
 	const MctsDev &d = h->d;
 	const size_t T = (size_t)d.T, rows = T * d.cap1;
 	if (h->bfs.claim == nullptr) {
-		BfsDev b{};
-		auto get = [&](size_t bytes) -> void * { void *q = nullptr; if (hipMalloc(&q, bytes + 16) != hipSuccess) return nullptr; h->bfs_allocs.push_back(q); return q; };
-		b.claim = (uint32_t *)get(rows * 4); b.from = (int32_t *)get(rows * 4); b.act = (uint8_t *)get(rows);
-		b.front[0] = (int32_t *)get(rows * 4); b.front[1] = (int32_t *)get(rows * 4);
-		b.len = (int32_t *)get(T * 4); b.actions = (uint8_t *)get(T * (size_t)d.max_path);
-		if (!b.claim || !b.from || !b.act || !b.front[0] || !b.front[1] || !b.len || !b.actions) {
-			for (void *q : h->bfs_allocs) (void)hipFree(q);
-			h->bfs_allocs.clear();
-			(void)hipGetLastError();
-			return fail(RK_ECAPACITY, "rk_mcts_search_graph: no device memory for the search scratch of %d trees", d.T);
-		}
+		GraphSearchDev b{};
+		Growth g(h->bfs_pool, "rk_mcts_search_graph");
+		g.request(&b.claim, rows); g.request(&b.from, rows); g.request(&b.act, rows);
+		g.request(&b.front[0], rows); g.request(&b.front[1], rows);
+		g.request(&b.len, T); g.request(&b.actions, T * (size_t)d.max_path);
+		if (!g.granted()) return fail(RK_ECAPACITY, "rk_mcts_search_graph: no device memory for the search scratch of %d trees", d.T);
+		g.commit();
 		h->bfs = b;
 	}
 	RK_HIP(hipMemsetAsync(h->bfs.claim, 0xFF, rows * 4, st));
 	RK_HIP(hipMemsetAsync(h->bfs.from, 0, rows * 4, st));
-	hipLaunchKernelGGL(k_mcts_complete, dim3(std::min<unsigned>(nblocks((size_t)d.cap1 * 16), 8192u), d.T), dim3(256), 0, st, d);
+	hipLaunchKernelGGL(k_mcts_complete, dim3(std::min<unsigned>(blocks((size_t)d.cap1 * 16), 8192u), d.T), dim3(256), 0, st, d);
 	hipLaunchKernelGGL(k_mcts_bfs, dim3(d.T), dim3(1024), 0, st, d, h->bfs);
 	RK_HIP(hipGetLastError());
 	h->bfs_valid = true;
@@ -920,11 +844,11 @@ int rk_mcts_roots_oh(rk_mcts_t *h, void *d_out, int out_dtype, void *stream)
 	MctsDev &d = h->d;
 	if (out_dtype == RK_OH_STATES) {
 		if (!d_out) return fail(RK_EINVAL, "rk_mcts_roots_oh: null output");
-		hipLaunchKernelGGL(k_mcts_gather_roots, dim3(nblocks((size_t)d.T * 5)), dim3(256), 0, (hipStream_t)stream, d, (uint32_t *)d_out);
+		hipLaunchKernelGGL(k_mcts_gather_roots, dim3(blocks((size_t)d.T * 5)), dim3(256), 0, (hipStream_t)stream, d, (uint32_t *)d_out);
 		RK_HIP(hipGetLastError());
 		return RK_OK;
 	}
-	hipLaunchKernelGGL(k_mcts_gather_roots, dim3(nblocks((size_t)d.T * 5)), dim3(256), 0, (hipStream_t)stream, d, d.children);
+	hipLaunchKernelGGL(k_mcts_gather_roots, dim3(blocks((size_t)d.T * 5)), dim3(256), 0, (hipStream_t)stream, d, d.children);
 	RK_HIP(hipGetLastError());
 	return rk_as_oh(RK_REPR_2024, (const int8_t *)d.children, d_out, out_dtype, (size_t)d.T, stream);
 }
@@ -933,7 +857,7 @@ int rk_mcts_set_root_pv(rk_mcts_t *h, const float *d_probs, const float *d_value
 {
 	if (!h || !h->ready) return fail(RK_ESTATE, "rk_mcts_set_root_pv: reset the engine first");
 	if (!d_probs || !d_values) return fail(RK_EINVAL, "rk_mcts_set_root_pv: null pointer");
-	hipLaunchKernelGGL(k_mcts_set_root_pv, dim3(nblocks((size_t)h->d.T * 12)), dim3(256), 0, (hipStream_t)stream, h->d, d_probs, d_values);
+	hipLaunchKernelGGL(k_mcts_set_root_pv, dim3(blocks((size_t)h->d.T * 12)), dim3(256), 0, (hipStream_t)stream, h->d, d_probs, d_values);
 	RK_HIP(hipGetLastError());
 	return RK_OK;
 }
@@ -1017,11 +941,9 @@ int rk_mcts_status(rk_mcts_t *h, long long *h_status, void *stream)
 	hipStream_t st = (hipStream_t)stream;
 	const MctsDev &d = h->d;
 	const size_t T = (size_t)d.T;
-	std::vector<int32_t> pageable;
-	int32_t *rec = h->tree_host;
-	if (rec == nullptr) { pageable.resize(T * TR_INTS); rec = pageable.data(); }
-	RK_HIP(hipMemcpyAsync(rec, d.tree, T * TR_INTS * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-	RK_HIP(hipStreamSynchronize(st));
+	std::vector<int32_t> pageable(h->tree_host.pinned() ? 0 : T * TR_INTS);
+	const int32_t *rec = nullptr;
+	if (int e = h->tree_host.fetch(d.tree, T * TR_INTS, pageable.data(), st, &rec)) return e;
 	for (size_t t = 0; t < T; t++) {
 		const int32_t *tr = rec + t * TR_INTS;
 		long long *r = h_status + 6 * t;

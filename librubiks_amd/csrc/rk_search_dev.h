@@ -104,6 +104,20 @@ __device__ __forceinline__ uint32_t probe_elect(uint32_t *table, uint32_t mask, 
 	}
 }
 
+// After a growth (or to drop stale claims): the stored states 1..n of one pool back into its cleared table.  No slot is tentative
+// then, so this is a plain insert; the slot a state lands in may differ from the one it had, which no result depends on (look-ups
+// compare states).  This thread takes the indices first, first + stride, ... (the kernel passes its own 1 + x position and the
+// grid's width: read in here, blockDim compiles to the general form that allows for a partial last workgroup).
+__device__ __forceinline__ void rehash_pool(const uint32_t *states, uint32_t *table, uint32_t mask, int n, int first, int stride)
+{
+	for (int idx = first; idx <= n; idx += stride) {
+		uint32_t s[5];
+		load5(states + (size_t)idx * 5, s);
+		uint32_t slot = hash_state(s) & mask;
+		while (atomicCAS(&table[slot], 0u, (uint32_t)idx) != 0u) slot = (slot + 1) & mask;
+	}
+}
+
 // ---- order-preserving compaction across workgroups in ONE launch: tickets + look-back --------------------------------
 // Every workgroup draws a ticket (so that "predecessor" means "started earlier": no deadlock whatever the dispatch
 // order), publishes its local total at once and then sums the totals of ALL its predecessors, 64 at a time with one wave

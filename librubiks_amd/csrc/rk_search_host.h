@@ -1,0 +1,209 @@
+// Host-side pieces shared by the search engines (A* single / sharded / batched, breadth-first search, MCTS): who owns a device
+// allocation, growing arrays in place as one transaction, and the small read-backs every engine needs.  The counterpart of
+// rk_search_dev.h; header-only, nothing in here is exported.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "../../include/rubiks_hip.h"
+#include "rk_error.h"
+
+namespace rk {
+namespace {
+
+class Growth;
+
+inline unsigned blocks(size_t n, unsigned per = 256) { return (unsigned)((n + per - 1) / per); }
+
+// slots of an open-addressing table for `capacity` states (+ the unused index 0): a power of two, at most half full
+inline uint64_t table_slots(size_t capacity, uint64_t floor)
+{
+	uint64_t t = floor;
+	while (t < 2 * (uint64_t)capacity + 2) t <<= 1;
+	return t;
+}
+
+// Owns device allocations: whatever alloc() handed out is freed by release(), or with the owner.  `slack` bytes are added to
+// every allocation (kernels may read a little past the last element with wide loads).
+class DevPool {
+public:
+	explicit DevPool(size_t slack) : slack_(slack) {}
+	DevPool(const DevPool &) = delete;
+	DevPool &operator=(const DevPool &) = delete;
+	~DevPool() { clear(); }
+
+	template <typename T>
+	int alloc(T **field, size_t count)
+	{
+		void *q = nullptr;
+		RK_HIP(hipMalloc(&q, count * sizeof(T) + slack_));
+		owned_.push_back(q);
+		*field = static_cast<T *>(q);
+		return RK_OK;
+	}
+	void release(void *p)
+	{
+		const auto it = std::find(owned_.begin(), owned_.end(), p);
+		if (it == owned_.end()) return;
+		owned_.erase(it);
+		(void)hipFree(p);
+	}
+	void clear()
+	{
+		for (void *p : owned_) (void)hipFree(p);
+		owned_.clear();
+	}
+
+private:
+	friend class Growth;
+	size_t slack_;
+	std::vector<void *> owned_;
+};
+
+// inside the fill step of a Growth: hand the first HIP error to the transaction
+#define RK_FILL(call) do { const hipError_t rk_fill_e_ = (call); if (rk_fill_e_ != hipSuccess) return rk_fill_e_; } while (0)
+
+// Growing arrays in place, all or nothing.  Work on a COPY of the engine's descriptor:
+//   request()  a new array for a field of the copy; the array the field held (if any) is replaced at commit
+//   granted()  false if a request failed: what was taken is given back, the caller reports RK_ECAPACITY
+//   fill()     the engine's copies / rehash on `st` (RK_FILL around every call), then one synchronisation; on an error the stream
+//              is synchronised -- nothing may still write into what is freed next --, what was taken is given back and RK_EHIP is
+//              reported as "<who>: <hip error>"
+//   commit()   frees the replaced arrays and adopts the new ones; the caller then stores the copy
+// Until commit() the engine is untouched; a transaction that is dropped gives back what it took.
+class Growth {
+public:
+	Growth(DevPool &pool, const char *who) : pool_(pool), who_(who) {}
+	~Growth() { give_back(); }
+
+	template <typename T>
+	void request(T **field, size_t count)
+	{
+		void *q = nullptr;
+		if (ok_ && hipMalloc(&q, count * sizeof(T) + pool_.slack_) == hipSuccess) fresh_.push_back(q);
+		else { ok_ = false; q = nullptr; }
+		if (*field != nullptr) stale_.push_back(*field);
+		*field = static_cast<T *>(q);
+	}
+	bool granted()
+	{
+		if (!ok_) { give_back(); (void)hipGetLastError(); }
+		return ok_;
+	}
+	template <typename Steps>
+	int fill(hipStream_t st, Steps &&steps)
+	{
+		hipError_t e = steps();
+		if (e == hipSuccess) e = hipStreamSynchronize(st);
+		if (e == hipSuccess) return RK_OK;
+		(void)hipStreamSynchronize(st);
+		give_back();
+		(void)hipGetLastError();
+		return fail(RK_EHIP, "%s: %s", who_, hipGetErrorString(e));
+	}
+	void commit()
+	{
+		for (void *q : stale_) pool_.release(q);
+		pool_.owned_.insert(pool_.owned_.end(), fresh_.begin(), fresh_.end());
+		fresh_.clear();
+		stale_.clear();
+	}
+
+private:
+	void give_back()
+	{
+		for (void *q : fresh_) (void)hipFree(q);
+		fresh_.clear();
+	}
+	DevPool &pool_;
+	const char *who_;
+	std::vector<void *> fresh_, stale_;
+	bool ok_ = true;
+};
+
+// Page-locked landing place of a small block of device counters: a poll is one direct copy, no staging (pageable memory costs a
+// staged copy per poll).  Without page-locked memory the caller's own buffer is the landing place.
+class Landing {
+public:
+	Landing() = default;
+	Landing(const Landing &) = delete;
+	Landing &operator=(const Landing &) = delete;
+	~Landing() { if (pinned_ != nullptr) (void)hipHostFree(pinned_); }
+
+	void reserve(size_t count)
+	{
+		if (hipHostMalloc((void **)&pinned_, count * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); pinned_ = nullptr; }
+	}
+	// `count` ints from `dev`, synchronising `st`; *at is where they landed (`spare`, of `count` ints, unless there is a page-locked buffer)
+	int fetch(const int32_t *dev, size_t count, int32_t *spare, hipStream_t st, const int32_t **at)
+	{
+		int32_t *dst = pinned_ != nullptr ? pinned_ : spare;
+		RK_HIP(hipMemcpyAsync(dst, dev, count * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+		RK_HIP(hipStreamSynchronize(st));
+		*at = dst;
+		return RK_OK;
+	}
+	// the same, into `out`
+	int read(const int32_t *dev, size_t count, int32_t *out, hipStream_t st)
+	{
+		const int32_t *at = nullptr;
+		if (int e = fetch(dev, count, out, st, &at)) return e;
+		if (at != out) memcpy(out, at, count * sizeof(int32_t));
+		return RK_OK;
+	}
+	bool pinned() const { return pinned_ != nullptr; }
+
+private:
+	int32_t *pinned_ = nullptr;
+};
+
+// A narrow device column (int32 / uint8) for a host that wants long long / double: start() enqueues the copy into a temporary (a
+// null `out` asks for nothing), finish() widens it once the stream has been synchronised.
+template <typename Narrow, typename Wide>
+class Widened {
+public:
+	int start(const Narrow *dev, size_t count, Wide *out, hipStream_t st)
+	{
+		out_ = out;
+		if (out == nullptr || count == 0) return RK_OK;
+		tmp_.resize(count);
+		RK_HIP(hipMemcpyAsync(tmp_.data(), dev, count * sizeof(Narrow), hipMemcpyDeviceToHost, st));
+		return RK_OK;
+	}
+	void finish()
+	{
+		for (size_t i = 0; i < tmp_.size(); i++) out_[i] = (Wide)tmp_[i];
+	}
+
+private:
+	std::vector<Narrow> tmp_;
+	Wide *out_ = nullptr;
+};
+
+// one column on its own: copy, synchronise, widen
+template <typename Narrow, typename Wide>
+int export_widened(const Narrow *dev, size_t count, Wide *out, hipStream_t st)
+{
+	Widened<Narrow, Wide> w;
+	if (int e = w.start(dev, count, out, st)) return e;
+	if (out != nullptr && count != 0) RK_HIP(hipStreamSynchronize(st));
+	w.finish();
+	return RK_OK;
+}
+
+// What a walk kernel left in `walk`: [0] = length of the action queue or -1, then the actions root -> node.  *len is that first
+// word; of a queue that exists, the first min(length, max_len, walk_max) actions go to h_actions.
+inline int read_walk(const int32_t *walk, size_t walk_max, long long *h_actions, size_t max_len, hipStream_t st, int32_t *len)
+{
+	*len = 0;
+	RK_HIP(hipMemcpyAsync(len, walk, sizeof *len, hipMemcpyDeviceToHost, st));
+	RK_HIP(hipStreamSynchronize(st));
+	if (*len < 0) return RK_OK;
+	return export_widened(walk + 1, std::min(std::min((size_t)*len, max_len), walk_max), h_actions, st);
+}
+
+}  // namespace
+}  // namespace rk
