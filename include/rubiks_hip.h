@@ -345,6 +345,50 @@ int rk_bfs_export(rk_bfs_t *h, size_t first, size_t count, int8_t *h_states, lon
  * error (RK_ESTATE: not won); writes at most max_len actions. */
 long long rk_bfs_path(rk_bfs_t *h, long long *h_actions, size_t max_len, void *stream);
 
+/* ---- device-resident epsilon-greedy value maximisation (agents.py:649-726) ---------------------------------------
+ * W = workers walkers take D = depth moves from a root (:692-715); the visited state with the best value becomes the next
+ * root (:673-677) until a walker is solved (:710-713) or another round would pass max_states (:665).  The root, the
+ * walkers, the W D visited states, their actions, a window of `burst_rounds` rounds of drawn actions and of per-round
+ * records, the counters and the two net batches live in HBM.  A round is D times [policy forward, rk_egvm_step] and once
+ * [value forward, rk_egvm_round_end], stream-ordered with no host synchronisation; the epsilon draws (:694, :698) depend on
+ * nothing the device computes and are uploaded ahead by the caller, in the reference's order.  Steps and round ends after
+ * the search is done, and steps after a round has a solved walker, are no-ops.  An engine handle is not thread-safe. */
+typedef struct rk_egvm rk_egvm_t;
+/* workers 1..65536, depth 1..4096, workers * depth <= 2^22; burst_rounds (1..4096): rounds of draws and records held at once. */
+int rk_egvm_create(rk_egvm_t **out, int workers, int depth, int burst_rounds);
+int rk_egvm_destroy(rk_egvm_t *h);
+/* The batch the engine writes for the net: which = 0 the policy batch (*rows = W: where every walker stands, states_oh of
+ * :687, :708), which = 1 the value batch (*rows = W D, row w D + d = walker w after d + 1 moves: new_states_oh of :715), as
+ * (rows, 480) one-hot rows of out_dtype (RK_OH_F32 / _F16 / _BF16; cube.py:265-277) or, with RK_OH_STATES, the (rows, 20)
+ * int8 states themselves.  The engine owns both (zeroed when made, 16-byte aligned, alive until rk_egvm_destroy) and writes
+ * them in the form asked for last; asking for another form needs a new rk_egvm_reset.  Call before rk_egvm_reset. */
+int rk_egvm_net_in(rk_egvm_t *h, int which, int out_dtype, void **d_ptr, size_t *rows);
+/* `state` of :658-667: a host 20-byte state that is not solved (:662 is the caller's), with max_states of :665.  Puts every
+ * walker on it and writes the policy batch.  Synchronises. */
+int rk_egvm_reset(rk_egvm_t *h, const int8_t *h_root, long long max_states, void *stream);
+/* The draws of the next `rounds` (<= burst_rounds) rounds, int8 (rounds, D, W) on the host: the action 0..11 where the
+ * reference acts at random (:694, :698), -1 where it follows the policy (:700-701).  The first of them belongs to the round
+ * that is open when the call is made; records of earlier rounds are gone after it.  Synchronises. */
+int rk_egvm_set_draws(rk_egvm_t *h, const int8_t *h_draws, int rounds, void *stream);
+/* One move of every walker (:694-715): d_logits (W, 12) contiguous, float32 or bfloat16 (dtype RK_OH_F32 / RK_OH_BF16), the
+ * policy head on the policy batch; a walker without a drawn action takes the first maximum of its row, a NaN counting as
+ * the maximum (ndarray.argmax, :701).  Moves, tests the goal (:709), stores state and action (:703, :714) and writes the
+ * walker's rows of both net batches.  No synchronisation. */
+int rk_egvm_step(rk_egvm_t *h, const void *d_logits, int dtype, void *stream);
+/* Closes the round: with a solved walker, the first depth and there the lowest walker (:710-713), its path (:670) and
+ * explored += (d + 1) W (:711), done; else d_values (W D) contiguous, float32 or bfloat16, the value head on the value batch:
+ * the first maximum (torch.argmax on the CPU, :674) is the next root (:675), its path is recorded (:677), explored += W D
+ * (:716), and the search is done when explored + W D > max_states (:665), else the next round starts.  No synchronisation. */
+int rk_egvm_round_end(rk_egvm_t *h, const void *d_values, int dtype, void *stream);
+/* Synchronises; h_status[8] = done, solved, rounds closed, explored states (len(agent), :711, :716), the solved walker and
+ * its depth (:713; -1 while unsolved), error (0 none, 1 a round beyond the uploaded draws, 2 a round closed before its walk
+ * ended), first round of the window of draws. */
+int rk_egvm_status(rk_egvm_t *h, long long *h_status, void *stream);
+/* The records of closed rounds first_round .. first_round + rounds - 1 of the current window, int64 (rounds, D + 2) on the
+ * host: the number n of actions the round appended to the action queue (:670, :677), 1 if it ended by a solve, then the n
+ * actions (the rest of a row is undefined).  Synchronises. */
+int rk_egvm_records(rk_egvm_t *h, long long first_round, int rounds, long long *h_out, void *stream);
+
 /* ---- batched A*: S independent searches in lock-step, no host synchronisation inside an iteration -------------
  * Every search is a complete rk_astar_* engine (agents.py:171-413: its own pool, hash table, open queue, counter block);
  * the batch launches the same kernels with a second grid dimension (search), so one iteration of ALL searches is the

@@ -92,6 +92,15 @@ SIGNATURES = {
 	"rk_bfs_size": (C.c_longlong, [_vp]),
 	"rk_bfs_export": (_i, [_vp, _sz, _sz, _vp, _vp, _vp, _vp]),
 	"rk_bfs_path": (C.c_longlong, [_vp, _vp, _sz, _vp]),
+	"rk_egvm_create": (_i, [C.POINTER(_vp), _i, _i, _i]),
+	"rk_egvm_destroy": (_i, [_vp]),
+	"rk_egvm_net_in": (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_sz)]),
+	"rk_egvm_reset": (_i, [_vp, _vp, C.c_longlong, _vp]),
+	"rk_egvm_set_draws": (_i, [_vp, _vp, _i, _vp]),
+	"rk_egvm_step": (_i, [_vp, _vp, _i, _vp]),
+	"rk_egvm_round_end": (_i, [_vp, _vp, _i, _vp]),
+	"rk_egvm_status": (_i, [_vp, _vp, _vp]),
+	"rk_egvm_records": (_i, [_vp, C.c_longlong, _i, _vp, _vp]),
 	"rk_astarb_create": (_i, [C.POINTER(_vp), _i, _sz, _i]),
 	"rk_astarb_destroy": (_i, [_vp]),
 	"rk_astarb_reset": (_i, [_vp, _vp, _vp, C.c_double, _vp]),

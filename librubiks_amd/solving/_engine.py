@@ -1,5 +1,5 @@
 """
-What the agents that drive a device engine (`rk_astar_*`, `rk_astarb_*`, `rk_mcts_*`, `rk_bfs_*`, the sharded `rk_astar_*`) share on
+What the agents that drive a device engine (`rk_astar_*`, `rk_astarb_*`, `rk_mcts_*`, `rk_bfs_*`, `rk_egvm_*`, the sharded `rk_astar_*`) share on
 the host, each concern defined once: how the net is fed and read, how a step becomes a kept hipGraph, and how a finished search
 is read back (the lifetime of a library object is `_ffi.Owner`).  agents.py and sharded.py hold what differs between the engines.
 """
@@ -93,6 +93,32 @@ def engine_values(out):
 	if isinstance(v, torch.Tensor) and v.is_cuda and v.dtype == torch.bfloat16 and v.is_contiguous():
 		return v.detach().reshape(-1), _ffi.OH_BF16
 	return v.detach().to(device=gpu, dtype=torch.float32).reshape(-1).contiguous(), _ffi.OH_F32
+
+
+def engine_logits(out):
+	"""-> (logits (rows, 12) contiguous, RK_OH_* code): the net's policy head as an engine takes it, bfloat16 as it is, anything
+	else as float32 (widening is exact)."""
+	p = (out[0] if isinstance(out, (list, tuple)) else out).detach()
+	if p.is_cuda and p.dtype == torch.bfloat16:
+		return p.reshape(-1, 12).contiguous(), _ffi.OH_BF16
+	return p.to(device=gpu, dtype=torch.float32).reshape(-1, 12).contiguous(), _ffi.OH_F32
+
+
+class _DeviceBytes:
+	"""`nbytes` bytes of device memory that the library owns, for torch.as_tensor (the CUDA array interface)."""
+	def __init__(self, ptr: int, nbytes: int):
+		self.__cuda_array_interface__ = {"shape": (nbytes,), "typestr": "|u1", "data": (ptr, False), "version": 2}
+
+
+def engine_batch(ptr: int, rows: int, code: int) -> torch.Tensor:
+	"""A net batch that an ENGINE owns (rk_egvm_net_in) as a tensor, no copy: (rows, 20) int8 for RK_OH_STATES, else (rows, 480)
+	in the dtype of `code`.  The memory lives as long as the engine: whoever holds the tensor drops it before the engine goes."""
+	dtype = OH_DTYPES[code]
+	cols = 20 if code == _ffi.OH_STATES else 480
+	raw = torch.as_tensor(_DeviceBytes(ptr, rows * cols * dtype.itemsize))
+	if raw.data_ptr() != ptr or not raw.is_cuda:
+		raise _ffi.RubiksHipError("torch copied the engine's batch instead of wrapping it")
+	return raw.view(dtype).reshape(rows, cols)
 
 
 # -- a step as a hipGraph ---------------------------------------------------------------------------------------------

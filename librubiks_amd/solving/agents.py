@@ -517,6 +517,185 @@ class EGVM(DeepAgent):
 		return f"EGVM (e={self.epsilon}, w={self.workers}, d={self.depth})"
 
 
+def egvm_draw_round(epsilon: float, workers: int, depth: int) -> np.ndarray:
+	"""The epsilon-greedy draws of `depth` moves of one EGVM walk, made with the reference's calls in the reference's order on the
+	global NumPy generator (agents.py:694, :698) -- both calls at every depth, also when nobody acts at random.  -> int8
+	(depth, workers): the action 0..11 where the reference acts at random, -1 where it follows the policy."""
+	table = np.full((depth, workers), -1, np.int8)
+	for d in range(depth):
+		use_random = np.random.choice(2, workers, p=[1 - epsilon, epsilon]).astype(bool)
+		table[d, use_random] = np.random.randint(0, cube.action_dim, use_random.sum())
+	return table
+
+
+def egvm_draw_rounds(epsilon: float, workers: int, depth: int, rounds: int):
+	"""`rounds` full rounds of draws ahead of the device -> (int8 (rounds, depth, workers), the generator's state before each round)."""
+	table, before = np.empty((rounds, depth, workers), np.int8), []
+	for r in range(rounds):
+		before.append(np.random.get_state())
+		table[r] = egvm_draw_round(epsilon, workers, depth)
+	return table, before
+
+
+def egvm_rewind(before_round, epsilon: float, workers: int, moves: int) -> np.ndarray:
+	"""A search that ended by a solve after `moves` moves of a round: the reference returned inside that walk (agents.py:710-713)
+	and drew nothing further.  Back to the generator's state before the round, then the draws of those moves again: the global
+	generator is left exactly where the reference leaves it."""
+	np.random.set_state(before_round)
+	return egvm_draw_round(epsilon, workers, moves)
+
+
+class _KeptGraph:
+	"""One kept hipGraph of an agent that keeps several (what _engine.kept_graph reads and writes of its agent)."""
+	def __init__(self):
+		self._graph_cache, self.captures = None, 0
+
+
+class DeviceEGVM(DeepAgent, _ffi.Owner):
+	"""
+	Epsilon-greedy value maximisation (agents.py:649-726) with the whole round on the device (engine rk_egvm_*, csrc/rk_egvm.hip):
+	the walkers, the states they visit, their actions and the two net batches live in HBM.  One move of all walkers is the policy
+	forward and one launch (argmax or drawn action, move, goal test, the rows of both net batches); a round ends with the value
+	forward and one launch (the solve, or the argmax over the workers x depth values, the new root and the loop guard).  Both are
+	captured once as hipGraphs and kept from search to search; the host enqueues `poll` rounds, then reads the status and the
+	rounds' action records.  The epsilon draws stay on the host: they depend on nothing the device computes, and made with the
+	reference's calls in the reference's order (egvm_draw_rounds) they leave the action queue, len(agent) and the global NumPy
+	generator exactly as the reference does -- a search that ends by a solve rewinds the generator to where the reference stopped
+	drawing (egvm_rewind), and no more than max_states // (workers * depth) rounds are ever drawn.
+
+	Two differences from the reference.  The time limit is checked where the host polls (before every `poll` rounds), not before
+	every round, so a time-limited search does not stop where the reference would.  And the policy forward runs on ALL workers,
+	not on the subset that follows the policy (agents.py:700): for a net whose GEMM results depend on the batch size in the last
+	bit, a near-tie between two logits may resolve differently.
+
+	The representation follows cube.get_is2024() when a search starts (6x8x6 nets read the engine's 20-byte rows through _Net686).
+	"""
+	MAX_WORKERS, MAX_DEPTH, MAX_POLL = 1 << 16, 1 << 12, 1 << 12          # rk_egvm_create's limits
+	MAX_STATES = 1 << 22                                                    # ... on workers * depth
+
+	def __init__(self, net, epsilon: float, workers: int, depth: int, poll: int = 4, fused_first_layer=False):
+		super().__init__(net, fused_first_layer)
+		for name, v, top in (("workers", workers, self.MAX_WORKERS), ("depth", depth, self.MAX_DEPTH), ("poll", poll, self.MAX_POLL)):
+			if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= top:
+				raise ValueError(f"{name} must be an integer in 1..{top}, got {v!r}")
+		if int(workers) * int(depth) > self.MAX_STATES:
+			raise ValueError(f"workers * depth must not exceed {self.MAX_STATES}, got {int(workers) * int(depth)}")
+		if int(workers) * int(depth) * int(poll) > 1 << 28:
+			raise ValueError(f"workers * depth * poll must not exceed {1 << 28}, got {int(workers) * int(depth) * int(poll)}")
+		if isinstance(epsilon, bool) or not isinstance(epsilon, (int, float, np.floating, np.integer)) or not 0 <= float(epsilon) <= 1:
+			raise ValueError(f"epsilon must be a number in 0..1, got {epsilon!r}")
+		self.epsilon, self.workers, self.depth, self.poll = epsilon, int(workers), int(depth), int(poll)
+		self._h, self._shape = None, None
+		self._walk, self._close = _KeptGraph(), _KeptGraph()       # policy forward + rk_egvm_step; value forward + rk_egvm_round_end
+		self._batches = None                                       # (code, policy batch, value batch): the engine's own memory as tensors
+		self.rounds = 0                                            # rounds the last search closed
+
+	@property
+	def captures(self) -> int:
+		"""hipGraph captures so far (a search on an unchanged engine and net replays the previous search's two graphs)."""
+		return self._walk.captures + self._close.captures
+
+	# -- engine lifetime ------------------------------------------------------------------------------------
+	def _engine(self):
+		shape = (self.workers, self.depth, self.poll)
+		if self._h is None or self._shape != shape:
+			self._create("rk_egvm_create", "rk_egvm_destroy", *shape)
+			self._shape = shape
+		return self._h
+
+	def _free(self):
+		self._walk._graph_cache = self._close._graph_cache = None      # they hold the engine's addresses,
+		self._batches = None                                           # and these are the engine's memory
+		super()._free()
+
+	def _net_in(self, h, code: int):
+		if self._batches is None or self._batches[0] != code:
+			got = []
+			for which in (0, 1):
+				ptr, rows = C.c_void_p(), C.c_size_t()
+				_ffi.check(_ffi.lib().rk_egvm_net_in(h, which, code, C.byref(ptr), C.byref(rows)))
+				got.append(eng.engine_batch(ptr.value, rows.value, code))
+			self._batches = (code, *got)       # (the engine goes on writing the form it was asked for last)
+		return self._batches[1], self._batches[2]
+
+	# -- the two captured steps -------------------------------------------------------------------------------
+	def _walk_step(self, h, pol_in):
+		logits, code = eng.engine_logits(self._forward(pol_in, policy=True, value=False))
+		self._keep_p = logits              # the kernel reads it after this call returns
+		_ffi.check(_ffi.lib().rk_egvm_step(h, logits.data_ptr(), code, _ffi.stream_ptr()))
+
+	def _close_step(self, h, val_in):
+		values, code = eng.engine_values(_sliced_value_forward(self._forward, val_in))
+		self._keep_v = values
+		_ffi.check(_ffi.lib().rk_egvm_round_end(h, values.data_ptr(), code, _ffi.stream_ptr()))
+
+	# -- search -------------------------------------------------------------------------------------------------
+	@no_grad
+	def search(self, state: np.ndarray, time_limit: float = None, max_states: int = None) -> bool:
+		_ffi.require_gpu()
+		t0 = time.perf_counter()
+		time_limit, max_states = self.reset(time_limit, max_states)
+		self.rounds = 0
+		forward, _, code = self._begin_net()
+		root = self._roots20(state, 1)[0]                      # ValueError for an illegal 6x8x6 state
+		if (root == _SOLVED20).all():
+			return True
+		W, D = self.workers, self.depth
+		max_rounds = int(max_states) // (W * D)                # the loop guard of agents.py:665 holds for exactly this many rounds
+		if max_rounds == 0:
+			return False
+		lib, stream = _ffi.lib(), _ffi.stream_ptr()
+		h = self._engine()
+		pol_in, val_in = self._net_in(h, code)
+		# The captured steps hold addresses (the engine's arrays and batches, the net's tensors) and the dtype codes -- nothing of a
+		# search, which lives in device memory that rk_egvm_reset rewrites: both graphs are kept from search to search.  They are
+		# captured on an engine that has been reset but has no draws yet, where the warm-up's launches change nothing that the reset
+		# below does not rewrite.
+		key = (h.value, code, pol_in.data_ptr(), val_in.data_ptr(), eng.capture_key(self.net, forward))
+		if any(g._graph_cache is None or g._graph_cache[0] != key for g in (self._walk, self._close)):
+			_ffi.check(lib.rk_egvm_reset(h, root.ctypes.data, int(max_states), stream))
+		walk_step = lambda: self._walk_step(h, pol_in)         # noqa: E731
+		close_step = lambda: self._close_step(h, val_in)       # noqa: E731
+		walk, _ = eng.kept_graph(self._walk, key, walk_step, walk_step, pol_in, ((self.net, forward),))
+		close, _ = eng.kept_graph(self._close, key, close_step, close_step, val_in, ((self.net, forward),))
+		_ffi.check(lib.rk_egvm_reset(h, root.ctypes.data, int(max_states), stream))
+		status = (C.c_longlong * 8)()
+		drawn = 0
+		while time.perf_counter() - t0 < time_limit:
+			n = min(self.poll, max_rounds - drawn)             # >= 1: the engine is done when round max_rounds closes
+			draws, before = egvm_draw_rounds(self.epsilon, W, D, n)
+			_ffi.check(lib.rk_egvm_set_draws(h, draws.ctypes.data, n, stream))
+			for _ in range(n):
+				for _ in range(D):
+					walk.replay()
+				close.replay()
+			_ffi.check(lib.rk_egvm_status(h, status, stream))
+			done, solved, rounds, explored, _, moves, err = (int(status[i]) for i in range(7))
+			if err:
+				raise _ffi.RubiksHipError(f"EGVM engine error code {err}")
+			closed = rounds - drawn                            # rounds of this burst that ran
+			if closed > 0:
+				rec = np.zeros((closed, D + 2), np.int64)
+				_ffi.check(lib.rk_egvm_records(h, drawn, closed, rec.ctypes.data, stream))
+				for row in rec:
+					self.action_queue.extend(int(a) for a in row[2:2 + int(row[0])])         # agents.py:670, :677
+			self.rounds, self._explored_states = rounds, explored
+			if solved:
+				egvm_rewind(before[closed - 1], self.epsilon, W, moves)
+				return True
+			drawn += n
+			if done:
+				return False
+		return False
+
+	@classmethod
+	def from_saved(cls, loc: str, use_best: bool, epsilon: float, workers: int, depth: int, loader=None):
+		return cls(_load_net(loc, use_best, loader), epsilon=epsilon, workers=workers, depth=depth)
+
+	def __str__(self):
+		return f"EGVM (device, e={self.epsilon}, w={self.workers}, d={self.depth})"
+
+
 def _load_net(loc: str, use_best: bool, loader=None):
 	"""The value/policy net of a saved model folder (reference: DeepAgent.from_saved, agents.py:72-75)."""
 	if loader is not None:
