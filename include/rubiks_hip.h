@@ -389,6 +389,42 @@ int rk_egvm_status(rk_egvm_t *h, long long *h_status, void *stream);
  * actions (the rest of a row is undefined).  Synchronises. */
 int rk_egvm_records(rk_egvm_t *h, long long first_round, int rounds, long long *h_out, void *stream);
 
+/* ---- device-resident greedy one-step games (agents.py:132-169 inside the loop of :22-38), G games in lock-step ----
+ * Every game is one PolicySearch (greedy) or ValueSearch search: a move per step until the state is solved or the game has
+ * made max_states moves (this repository's Agent.search counts the moves of the running search against max_states; in the
+ * reference len(self) stays 0 until search returns).  The games' states, status (0 running, 1 solved, 2 budget spent,
+ * 3 handed back), move counts, actions, the counters and the net batch live in HBM.  A move of all games is
+ * [net forward, rk_greedy_step], stream-ordered with no host synchronisation; games that are not running are skipped and
+ * their rows of the batch stay as they are.  An engine handle is not thread-safe. */
+typedef struct rk_greedy rk_greedy_t;
+/* games 1..65536, max_steps >= 1 (the most moves a game may make: the width of the action record), games * max_steps <= 2^30;
+ * mode 0 = policy (agents.py:138-142 with sample_policy false), 1 = value (:156-166). */
+int rk_greedy_create(rk_greedy_t **out, int games, int max_steps, int mode);
+int rk_greedy_destroy(rk_greedy_t *h);
+/* The batch the engine writes for the net: *rows = G in policy mode (row g: where game g stands), 12 G in value mode (row
+ * 12 g + a: child a of game g's state), as (rows, 480) one-hot rows of out_dtype (RK_OH_F32 / _F16 / _BF16; cube.py:265-277)
+ * or, with RK_OH_STATES, the (rows, 20) int8 states themselves.  The engine owns it (zeroed when made, 16-byte aligned, alive
+ * until rk_greedy_destroy) and writes the form asked for last; asking for another form needs a new rk_greedy_reset.  Call
+ * before rk_greedy_reset. */
+int rk_greedy_net_in(rk_greedy_t *h, int out_dtype, void **d_ptr, size_t *rows);
+/* n_games (1..games) host 20-byte states, each with a budget of max_states (1..max_steps) moves.  A root that is solved ends
+ * at once with status 1 and 0 moves (:29); games n_games.. of the engine stay idle.  Writes the first batch.  Synchronises. */
+int rk_greedy_reset(rk_greedy_t *h, const int8_t *h_roots, int n_games, int max_states, void *stream);
+/* One move of every running game.  d_out is the net's output on the batch, contiguous, float32 or bfloat16 (dtype RK_OH_F32 /
+ * RK_OH_BF16, widened exactly).  Policy mode: (G, 12) logits; the action is the first maximum of the game's row, but a game
+ * with a logit less than 2^-20 below the maximum, a NaN logit or an infinite maximum -- where argmax(softmax(logits)) on the
+ * host (:139-140) might choose otherwise -- is not moved and gets status 3.  Value mode: (12 G) values; the first solved
+ * child (:159-161), else the first maximum, a NaN counting as the maximum (ndarray.argmax, :165).  Then the move, the goal
+ * test, the action record, status 1 or -- after max_states moves -- 2, and the game's rows of the next batch.  No
+ * synchronisation. */
+int rk_greedy_step(rk_greedy_t *h, const void *d_out, int dtype, void *stream);
+/* Synchronises; h_status[8] = running games, moves launched since the reset, error (0 none, 1 a running game without room in
+ * its action record), games and max_states of the reset, three zeros. */
+int rk_greedy_status(rk_greedy_t *h, long long *h_status, void *stream);
+/* The games of the last reset to HOST buffers (any may be NULL): status int64 (n_games), moves made int64 (n_games), actions
+ * uint8 (n_games, max_states) of which the first `moves made` of a row are defined.  Synchronises. */
+int rk_greedy_export(rk_greedy_t *h, long long *h_status, long long *h_steps, uint8_t *h_actions, void *stream);
+
 /* ---- batched A*: S independent searches in lock-step, no host synchronisation inside an iteration -------------
  * Every search is a complete rk_astar_* engine (agents.py:171-413: its own pool, hash table, open queue, counter block);
  * the batch launches the same kernels with a second grid dimension (search), so one iteration of ALL searches is the

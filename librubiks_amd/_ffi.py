@@ -101,6 +101,13 @@ SIGNATURES = {
 	"rk_egvm_round_end": (_i, [_vp, _vp, _i, _vp]),
 	"rk_egvm_status": (_i, [_vp, _vp, _vp]),
 	"rk_egvm_records": (_i, [_vp, C.c_longlong, _i, _vp, _vp]),
+	"rk_greedy_create": (_i, [C.POINTER(_vp), _i, _i, _i]),
+	"rk_greedy_destroy": (_i, [_vp]),
+	"rk_greedy_net_in": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_sz)]),
+	"rk_greedy_reset": (_i, [_vp, _vp, _i, _i, _vp]),
+	"rk_greedy_step": (_i, [_vp, _vp, _i, _vp]),
+	"rk_greedy_status": (_i, [_vp, _vp, _vp]),
+	"rk_greedy_export": (_i, [_vp, _vp, _vp, _vp, _vp]),
 	"rk_astarb_create": (_i, [C.POINTER(_vp), _i, _sz, _i]),
 	"rk_astarb_destroy": (_i, [_vp]),
 	"rk_astarb_reset": (_i, [_vp, _vp, _vp, C.c_double, _vp]),

@@ -54,57 +54,6 @@ struct EgvmDev {
 
 __device__ __forceinline__ long long *egvm_big(const EgvmDev &d) { return reinterpret_cast<long long *>(d.ctr + E_COUNT); }
 
-// dword j of a state held in registers, j not known at compile time (no indexed register array)
-__device__ __forceinline__ uint32_t dword_of(const uint32_t s[5], int j)
-{
-	return j == 0 ? s[0] : j == 1 ? s[1] : j == 2 ? s[2] : j == 3 ? s[3] : s[4];
-}
-
-// Row `row` of a net batch from state s, written by `n` threads of which this is thread `t`: (rows, 480) one-hot of 4- or 2-byte
-// elements, oh[24 i + s[i]] = 1 (cube.py:265-277), in 16-byte chunks, or the 20 bytes themselves.
-__device__ __forceinline__ void write_row(void *buf, int code, size_t row, const uint32_t s[5], int t, int n)
-{
-	if (code == RK_OH_STATES) {
-		uint32_t *dst = reinterpret_cast<uint32_t *>(buf) + row * 5;
-		for (int j = t; j < 5; j += n) dst[j] = dword_of(s, j);
-		return;
-	}
-	const bool wide = code == RK_OH_F32;
-	const uint32_t one_bits = wide ? 0x3F800000u : code == RK_OH_F16 ? 0x3C00u : 0x3F80u;
-	const int E = wide ? 4 : 8, CPR = 480 / E, CPC = 24 / E;
-	u32x4 *dst = reinterpret_cast<u32x4 *>(buf) + row * CPR;
-	for (int g = t; g < CPR; g += n) {
-		const int cubie = g / CPC, base = (g - cubie * CPC) * E;
-		const int rel = (int)((dword_of(s, cubie >> 2) >> (8 * (cubie & 3))) & 0xFFu) - base;
-		u32x4 val = {0u, 0u, 0u, 0u};
-		if (wide) {
-			val.x = rel == 0 ? one_bits : 0u; val.y = rel == 1 ? one_bits : 0u;
-			val.z = rel == 2 ? one_bits : 0u; val.w = rel == 3 ? one_bits : 0u;
-		} else if (rel >= 0 && rel < 8) {
-			const uint32_t one = one_bits << (16 * (rel & 1));
-			val.x = (rel >> 1) == 0 ? one : 0u; val.y = (rel >> 1) == 1 ? one : 0u;
-			val.z = (rel >> 1) == 2 ? one : 0u; val.w = (rel >> 1) == 3 ? one : 0u;
-		}
-		dst[g] = val;
-	}
-}
-
-// element i of a float32 or bfloat16 vector, widened exactly
-__device__ __forceinline__ float net_out(const void *p, bool bf16, size_t i)
-{
-	if (!bf16) return reinterpret_cast<const float *>(p)[i];
-	return __uint_as_float((uint32_t)reinterpret_cast<const uint16_t *>(p)[i] << 16);
-}
-
-// (v, i) beats (bv, bi) under "first index of the maximum, NaN counts as the maximum" (ndarray.argmax, torch.argmax on the CPU)
-__device__ __forceinline__ bool beats(float v, int i, float bv, int bi)
-{
-	const bool vn = v != v, bn = bv != bv;
-	if (vn != bn) return vn;
-	if (!vn && v != bv) return v > bv;
-	return i < bi;
-}
-
 // The start of a round, by one workgroup: every walker on `from`, and its row of the policy batch.
 __device__ __forceinline__ void egvm_restart(const EgvmDev &d, const uint32_t *from)
 {

@@ -696,6 +696,163 @@ class DeviceEGVM(DeepAgent, _ffi.Owner):
 		return f"EGVM (device, e={self.epsilon}, w={self.workers}, d={self.depth})"
 
 
+class GreedyBatch(DeepAgent, _ffi.Owner):
+	"""
+	Up to `games` independent games of a one-step agent advanced in lock-step on the device (engine rk_greedy_*,
+	csrc/rk_greedy.hip): `mode` "policy" plays every game as `PolicySearch(net)` does (greedy, agents.py:138-142), "value" as
+	`ValueSearch(net)` does (agents.py:156-166).  The games' states, status, move counts, actions and the net batch live in HBM; a
+	move of all games is one net forward on `games` (policy) or 12 x `games` (value) rows and one launch, captured once as a
+	hipGraph and kept from search to search.  The host enqueues `poll` moves (never more than the budget has left), then reads the
+	number of running games; games that have ended are skipped on the device and keep their rows, so the net's batch never
+	changes shape.
+
+	Every game follows THIS repository's host agents, which differ from the reference in one respect: their loop counts a game's
+	moves against `max_states` at every step (Agent.search above), so a game that is not solved after `max_states` moves ends with
+	status 2.  In the reference len(self) stays 0 until search returns (agents.py:30-38), so `max_states` never stops a one-step
+	agent there -- only the time limit does.  `max_states` is required here: it sizes the action record.  The time limit is
+	checked where the host polls, not before every move.
+
+	Policy mode takes the first maximum of the logits where the host agent takes argmax(softmax(logits)) on the CPU.  Where the two
+	might differ -- a logit less than 2^-20 below the maximum, a NaN logit, an infinite maximum; csrc/rk_greedy.hip has the proof
+	that nothing else can -- the engine does not move the game: it gets status 3 and is listed in `handed_back`, for the caller
+	to play on the host (`Evaluator` does).  With a real-valued net a forward on `games` rows need not equal a forward on one row bit
+	for bit, so a near-tie between two logits or values may resolve differently than in a game played alone; with nets whose
+	outputs are exact the games are the host agents' move for move.
+
+	Not here: `PolicySearch(sample_policy=True)` and `RandomSearch` draw from the global NumPy generator once per move, and the
+	number of draws a game makes decides where the next game's scramble is drawn from; such games cannot advance together and
+	leave the reference's stream of draws intact, so they stay sequential.
+
+	After a search: `status` (0 still running when the time ran out, 1 solved, 2 budget spent, 3 handed back), `steps`,
+	`action_queue_of(i)`, `handed_back`; len(agent) is the sum of `steps`.  The representation follows cube.get_is2024() when a
+	search starts (6x8x6 nets read the engine's 20-byte rows through _Net686).
+	"""
+	MODES = {"policy": 0, "value": 1}
+	MAX_GAMES, MAX_POLL = 1 << 16, 1 << 12
+	MAX_RECORD = 1 << 30                                                    # rk_greedy_create's limit on games * max_states
+
+	def __init__(self, net, mode: str, games: int, poll: int = 8, fused_first_layer=False):
+		super().__init__(net, fused_first_layer)
+		if not isinstance(mode, str) or mode not in self.MODES:
+			raise ValueError(f'mode is "policy" or "value", got {mode!r}')
+		for name, v, top in (("games", games, self.MAX_GAMES), ("poll", poll, self.MAX_POLL)):
+			if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= top:
+				raise ValueError(f"{name} must be an integer in 1..{top}, got {v!r}")
+		self.mode, self.games, self.poll = mode, int(games), int(poll)
+		self._h, self._room = None, 0                                       # the engine and the moves per game it has room for
+		self._graph_cache, self.captures = None, 0                          # [net forward, rk_greedy_step], kept (_engine.kept_graph)
+		self._batch = None                                                  # (code, the engine's net batch as a tensor)
+		self.status = np.zeros(0, np.int64)
+		self.steps = np.zeros(0, np.int64)
+		self._actions = np.zeros((0, 0), np.uint8)
+		self.launched = 0                                                   # moves the last search enqueued
+		self.on_poll = None                                                 # callable(status): called with every per-game status the search reads
+
+	# -- engine lifetime ------------------------------------------------------------------------------------
+	def _budget(self, max_states) -> int:
+		if max_states is None:
+			raise ValueError("GreedyBatch needs max_states: it sizes every game's action record")
+		if isinstance(max_states, bool) or not isinstance(max_states, (int, np.integer)) or int(max_states) < 1:
+			raise ValueError(f"max_states must be a positive integer, got {max_states!r}")
+		if self.games * int(max_states) > self.MAX_RECORD:
+			raise ValueError(f"games * max_states must not exceed {self.MAX_RECORD}, got {self.games * int(max_states)}")
+		return int(max_states)
+
+	def _engine(self, max_states: int):
+		if self._h is None or self._room < max_states:
+			self._create("rk_greedy_create", "rk_greedy_destroy", self.games, max_states, self.MODES[self.mode])
+			self._room = max_states
+		return self._h
+
+	def _free(self):
+		self._graph_cache = None               # it holds the engine's addresses,
+		self._batch = None                     # and this is the engine's memory
+		super()._free()
+
+	def _net_in(self, h, code: int):
+		if self._batch is None or self._batch[0] != code:
+			ptr, rows = C.c_void_p(), C.c_size_t()
+			_ffi.check(_ffi.lib().rk_greedy_net_in(h, code, C.byref(ptr), C.byref(rows)))
+			self._batch = (code, eng.engine_batch(ptr.value, rows.value, code))      # (the engine goes on writing the form it was asked for last)
+		return self._batch[1]
+
+	# -- the captured step ------------------------------------------------------------------------------------
+	def _move(self, h, batch):
+		if self.mode == "policy":
+			out, code = eng.engine_logits(self._forward(batch, policy=True, value=False))
+		else:
+			out, code = eng.engine_values(_sliced_value_forward(self._forward, batch))
+		self._keep = out                       # the kernel reads it after this call returns
+		_ffi.check(_ffi.lib().rk_greedy_step(h, out.data_ptr(), code, _ffi.stream_ptr()))
+
+	def _read(self, h, n: int, actions: bool):
+		self.status, self.steps = np.zeros(n, np.int64), np.zeros(n, np.int64)
+		if actions:
+			self._actions = np.zeros((n, self._max_states), np.uint8)
+		_ffi.check(_ffi.lib().rk_greedy_export(h, self.status.ctypes.data, self.steps.ctypes.data, self._actions.ctypes.data if actions else None,
+		                                       _ffi.stream_ptr()))
+		self._explored_states = int(self.steps.sum())
+
+	# -- search -------------------------------------------------------------------------------------------------
+	@no_grad
+	def search(self, states: np.ndarray, time_limit: float = None, max_states: int = None) -> np.ndarray:
+		"""Plays the games (at most `games` start states) until each is solved, has made `max_states` moves or was handed back, or
+		until a poll after `time_limit`; returns the bool vector `solved` over the games."""
+		max_states = self._budget(max_states)                  # before anything asks for a device
+		_ffi.require_gpu()
+		t0 = time.perf_counter()
+		time_limit, _ = self.reset(time_limit, max_states)
+		forward, _, code = self._begin_net()
+		states = np.asarray(states, dtype=np.int8)
+		n = states.size // (20 if self._is2024 else 288)
+		if not 1 <= n <= self.games or n * (20 if self._is2024 else 288) != states.size:
+			raise ValueError(f"between 1 and {self.games} start states are played at once, got an array of shape {states.shape}")
+		roots = self._roots20(states, n)                       # ValueError for an illegal 6x8x6 state
+		self._max_states, self.launched = max_states, 0
+		self.status, self.steps, self._actions = np.zeros(n, np.int64), np.zeros(n, np.int64), np.zeros((n, 0), np.uint8)
+		lib, stream = _ffi.lib(), _ffi.stream_ptr()
+		h = self._engine(max_states)
+		batch = self._net_in(h, code)
+		# The captured step holds addresses (the engine's arrays and batch, the net's tensors) and the dtype code -- nothing of a
+		# search, which lives in device memory that rk_greedy_reset rewrites: the graph is kept from search to search.  It is captured
+		# on an engine that has been reset; the warm-up's move is undone by the reset below.
+		key = (h.value, code, batch.data_ptr(), self.mode, self.games, eng.capture_key(self.net, forward))
+		if self._graph_cache is None or self._graph_cache[0] != key:
+			_ffi.check(lib.rk_greedy_reset(h, roots.ctypes.data, n, max_states, stream))
+		move = lambda: self._move(h, batch)                    # noqa: E731
+		graph, _ = eng.kept_graph(self, key, move, move, batch, ((self.net, forward),))
+		_ffi.check(lib.rk_greedy_reset(h, roots.ctypes.data, n, max_states, stream))
+		status = (C.c_longlong * 8)()
+		running = int((roots != _SOLVED20).any(axis=1).sum())
+		while running and self.launched < max_states and time.perf_counter() - t0 < time_limit:
+			burst = min(self.poll, max_states - self.launched)  # a running game moves at every launch: none is left after max_states of them
+			for _ in range(burst):
+				graph.replay()
+			self.launched += burst
+			_ffi.check(lib.rk_greedy_status(h, status, stream))
+			running, err = int(status[0]), int(status[2])
+			if err:
+				raise _ffi.RubiksHipError(f"greedy engine error code {err}")
+			if self.on_poll is not None:
+				self._read(h, n, False)
+				self.on_poll(self.status)
+		self._read(h, n, True)
+		if self.on_poll is not None:
+			self.on_poll(self.status)
+		return self.status == 1
+
+	@property
+	def handed_back(self) -> np.ndarray:
+		"""Indices of the games the engine would not decide (status 3): play them with the host agent."""
+		return np.flatnonzero(self.status == 3)
+
+	def action_queue_of(self, game: int) -> deque:
+		return deque(int(a) for a in self._actions[game, :int(self.steps[game])])
+
+	def __str__(self):
+		return f"Greedy {self.mode} x{self.games} (device)"
+
+
 def _load_net(loc: str, use_best: bool, loader=None):
 	"""The value/policy net of a saved model folder (reference: DeepAgent.from_saved, agents.py:72-75)."""
 	if loader is not None:

@@ -15,6 +15,11 @@ Two ways to play the games:
     (tests/test_evaluation_gpu.py, against the unmodified reference's own Evaluator through tests/golden/evaluator_trace.npz).
     `times[i, j]` is then the time from the start of the game's batch to the poll that saw it finished -- games share the
     device, a per-game stopwatch does not exist.
+    The one-step agents `ValueSearch` and greedy `PolicySearch` play the same way on `GreedyBatch`: one net batch and one launch
+    per move of all games.  A game the engine hands back (a near-tie between two logits that the host's softmax might resolve
+    differently) is played again from its stored scramble by the agent's own `search` -- these agents draw nothing, so the order
+    does not matter -- and `replayed` counts such games.  A sampled `PolicySearch` and `RandomSearch` draw from the global
+    generator at every move, between one game's scramble and the next: their games stay sequential.
 """
 import time
 
@@ -51,7 +56,10 @@ class Evaluator:
 		self.max_time = max_time
 		self.max_states = max_states
 		self.log = logger or NullLogger()
-		self.batch_games = int(batch_games)          # games advanced together in batched mode (memory: a pool of max_states per game)
+		# games advanced together in batched mode.  Memory: for A* and MCTS a pool of max_states nodes per game; for the one-step agents
+		# max_states BYTES per game, so there all games at once (batch_games = n_games x depths) is the setting to use
+		self.batch_games = int(batch_games)
+		self.replayed = 0                            # games of the last batched eval() that the engine handed back and the agent played itself
 		# evaluation.py:30: an empty range means "deep": every game's depth is drawn uniformly from [100, 999]
 		self.scrambling_depths = np.array(scrambling_depths) if scrambling_depths != range(0) else np.array([0])
 		self.last_mode = None                        # "sequential" or "batched": how the last eval() played its games
@@ -75,12 +83,15 @@ class Evaluator:
 
 	@staticmethod
 	def can_batch(agent) -> bool:
-		return type(agent) in (agents.AStar, agents.MCTS)
+		"""Exactly these classes (a subclass may search differently): AStar, MCTS, ValueSearch, and PolicySearch unless it samples."""
+		if type(agent) is agents.PolicySearch:
+			return not agent.sample_policy
+		return type(agent) in (agents.AStar, agents.MCTS, agents.ValueSearch)
 
 	def eval(self, agent, batched: bool = None):
 		"""
 		Returns (res, states, times), each len(scrambling_depths) x n_games (evaluation.py:56-96).
-		batched: None = lock-step on the device when the agent can (AStar, MCTS) and the games are bounded by max_states alone.
+		batched: None = lock-step on the device when the agent can (can_batch) and the games are bounded by max_states alone.
 		"""
 		assert self.max_time or self.max_states
 		if batched is None:
@@ -89,6 +100,7 @@ class Evaluator:
 			raise TypeError(f"{agent} has no batched engine; play its games one after the other")
 		if batched and self.max_states is None:
 			raise ValueError("batched games need max_states: it sizes every game's node pool (max_time, if given, then limits the whole batch)")
+		self.replayed = 0
 		self.log.section(f"Evaluation of {agent}")
 		D, G = len(self.scrambling_depths), self.n_games
 		self.last_mode = "batched" if batched else "sequential"
@@ -120,14 +132,15 @@ class Evaluator:
 				if self._isdeep():
 					d = np.random.randint(100, 1000)
 				starts.append(cube.scramble(d, True)[0])
-		starts = np.array(starts, dtype=np.int8).reshape(-1, 20)
 		total = len(starts)
+		starts = np.array(starts, dtype=np.int8).reshape(total, -1)
+		shape = cube.shape()
 		res, states, times = np.full(total, -1, np.int64), np.zeros(total, np.int64), np.zeros(total)
 		b, b_games = None, 0
 		for lo in range(0, total, self.batch_games):
 			hi = min(total, lo + self.batch_games)
 			n = hi - lo
-			if n != b_games:                                          # (the last group may be smaller)
+			if n != b_games and not (isinstance(b, agents.GreedyBatch) and n < b_games):      # (the last group may be smaller; GreedyBatch plays fewer)
 				b = None                                              # at most one engine alive: its pools are n x max_states nodes
 				b, b_games = self._batch_agent(agent, n), n
 			t0 = time.perf_counter()
@@ -135,13 +148,21 @@ class Evaluator:
 			for i in range(n):
 				if solved[i]:
 					res[lo + i] = len(b.action_queue_of(i))
-			states[lo:hi] = b.status[:, 2]
+			states[lo:hi] = b.steps if isinstance(b, agents.GreedyBatch) else b.status[:, 2]
 			times[lo:hi] = seen
+			for i in (b.handed_back if isinstance(b, agents.GreedyBatch) else ()):
+				t1 = time.perf_counter()
+				won = agent.search(starts[lo + i].reshape(shape), self.max_time, self.max_states)
+				res[lo + i], states[lo + i] = (len(agent.action_queue) if won else -1), len(agent)
+				times[lo + i] += time.perf_counter() - t1
+				self.replayed += 1
 		return res, states, times
 
 	def _batch_agent(self, agent, n: int):
 		cap = int(self.max_states)
-		if isinstance(agent, agents.AStar):
+		if isinstance(agent, (agents.PolicySearch, agents.ValueSearch)):
+			b = agents.GreedyBatch(agent.net, "policy" if isinstance(agent, agents.PolicySearch) else "value", n, fused_first_layer=agent._fused_mode)
+		elif isinstance(agent, agents.AStar):
 			b = agents.AStarBatch(agent.net, agent.lambda_, agent.expansions, n, capacity=cap, fused_first_layer=agent._fused_mode)
 		else:
 			b = agents.MCTSBatch(agent.net, agent.c, n, capacity=max(cap, 13), nu=agent.nu, priors=agent.priors,
@@ -152,13 +173,13 @@ class Evaluator:
 		"""Runs one batch; returns (solved, seconds until each game was seen finished)."""
 		seen = np.zeros(len(starts))
 		def on_poll(st):
-			fresh = (st[:, 0] != 0) & (seen == 0)
+			fresh = ((st if st.ndim == 1 else st[:, 0]) != 0) & (seen == 0)      # (GreedyBatch reports one status word per game)
 			seen[fresh] = time.perf_counter() - t0
 		b.on_poll = on_poll
 		try:
 			# max_time, if given, is every game's limit on the batch's one clock (the games share the device: each gets less of it
 			# than a game played alone would -- which is why eval() only chooses this form by itself for games without a time limit)
-			if isinstance(b, agents.AStarBatch):
+			if isinstance(b, (agents.AStarBatch, agents.GreedyBatch)):
 				solved = b.search(starts, self.max_time, self.max_states)
 			else:
 				solved = b.search(starts, self.max_time, max_states=self.max_states, use_graph=b.priors != "reference")
