@@ -107,6 +107,127 @@ class NoisyStubNet(StubNet):
 		return out if len(out) > 1 else out[0]
 
 
+def _round_bf16(a: np.ndarray) -> np.ndarray:
+	"""float32 array rounded to the nearest bfloat16 (ties to even), returned as float32.  No NaN expected; +-inf stay."""
+	u = np.ascontiguousarray(a, np.float32).view(np.uint32).astype(np.uint64)
+	u = (u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000
+	return u.astype(np.uint32).view(np.float32).reshape(np.shape(a))
+
+
+class LookupNet(StubNet):
+	"""
+	A net whose outputs are ARBITRARY float32 (or bfloat16) bit patterns and still the same bits on NumPy, torch-CPU and torch-GPU
+	for any batch shape: h = (one-hot . w) mod M with small integer weights w (a sum of twenty integers below 2^24, exact in float32
+	in any order, as in NoisyStubNet) and k = number of cubies off their solved code (StubNet's -value, 0..20) select one entry of
+	tables made once on the host, and a gather copies bits.
+	  value  = value_table[h, k], where value_table[h, k] = float32(float32(noise[h] + stub_weight * (-k)) + offset) with
+	           noise ~ N(0, scale^2): StubNet's value scaled by `stub_weight` keeps the search going somewhere, the noise misleads it
+	           (states are rediscovered over shorter ways: both relaxation passes of A* run), `offset` > 0 makes A* costs negative;
+	  logits = logit_table[h], shape (M, 12): normal rows of scale 0.01 .. 20, and every third row a NEAR TIE: a maximum of magnitude
+	           0.01 .. 20 and one logit a gap of 1 ulp .. 2^-16 below it at a lower or a higher index (`near_ties` lists them).
+	Planted after that, whole rows of the value table (so they reach the output whatever k): exact duplicates, pairs one ulp apart
+	(`dtype`'s ulp), +0.0 and -0.0; with `special` also float32 denormals, +-1e30, +inf and -inf.  No NaN anywhere: heapq on NaN
+	tuples has no defined order.  dtype "bfloat16": both tables are rounded to bfloat16 once on the host; torch outputs are then
+	bfloat16 tensors, NumPy outputs float32 arrays holding the same numbers.
+	Test infrastructure only.
+	"""
+	M = 4093
+	GAPS = (0.0, 2.0 ** -26, 2.0 ** -24, 2.0 ** -23, 2.0 ** -22, 2.0 ** -21, 1.5 * 2.0 ** -21, 2.0 ** -20, 1.5 * 2.0 ** -20, 2.0 ** -19,
+	        1.5 * 2.0 ** -19, 2.0 ** -18, 2.0 ** -17, 2.0 ** -16)          # 0.0 stands for "one ulp of the maximum"
+	MAGNITUDES = (0.01, 0.3, 3.0, 20.0)
+
+	def __init__(self, seed: int = 0, scale: float = 3.0, offset: float = 0.0, dtype: str = "float32", special: bool = False,
+	             stub_weight: float = 0.5):
+		super().__init__()
+		if dtype not in ("float32", "bfloat16"):
+			raise ValueError('dtype is "float32" or "bfloat16"')
+		self.dtype, self.special = dtype, bool(special)
+		M = self.M
+		rng = np.random.RandomState(seed)
+		self.w = rng.randint(0, M, 480).astype(np.float32)
+		noise = (rng.standard_normal(M) * scale).astype(np.float32)
+		stub = (np.float32(stub_weight) * -np.arange(21, dtype=np.float32)).astype(np.float32)
+		vt = ((noise[:, None] + stub[None, :]).astype(np.float32) + np.float32(offset)).astype(np.float32)
+		# logits
+		row_scale = np.array(self.MAGNITUDES, np.float32)[rng.randint(0, 4, M)]
+		lt = (rng.standard_normal((M, 12)) * row_scale[:, None]).astype(np.float32)
+		lt[1::97, 3] = lt[1::97, 7]                                     # exact ties in ordinary rows
+		lt[2::101, 5] = 0.0
+		lt[2::101, 6] = -0.0
+		self.near_ties = []                                             # (h, index of the maximum, index of the runner-up)
+		for h in range(0, M, 3):
+			mag = self.MAGNITUDES[rng.randint(4)] * (1 + rng.rand())
+			m = np.float32(mag if rng.rand() < 0.5 else -mag)
+			gap = self.GAPS[rng.randint(len(self.GAPS))]
+			j, i = rng.choice(12, 2, replace=False)
+			row = (m - np.float32(1) - np.abs(rng.standard_normal(12))).astype(np.float32)
+			row[j] = m
+			row[i] = np.nextafter(m, np.float32(-np.inf)) if gap == 0.0 else np.float32(np.float64(m) - gap)
+			lt[h] = row
+			self.near_ties.append((h, int(j), int(i)))
+		if dtype == "bfloat16":
+			vt, lt = _round_bf16(vt), _round_bf16(lt)
+		# planted rows of the value table
+		pick = rng.permutation(M)
+		step = np.uint32(1 << 16 if dtype == "bfloat16" else 1)
+		vt[pick[0:64]] = vt[pick[64:128]]                               # exact duplicates
+		vt[pick[128:192]] = (vt[pick[192:256]].view(np.uint32) + step).view(np.float32)      # one ulp further from zero
+		vt[pick[256:264]] = 0.0
+		vt[pick[264:272]] = -0.0
+		self.planted = {"duplicates": (pick[0:64], pick[64:128]), "ulp_pairs": (pick[128:192], pick[192:256]),
+		                "plus_zero": pick[256:264], "minus_zero": pick[264:272]}
+		if self.special:
+			values = [1e-40, -1e-40, 1.4e-45, -1.4e-45, 1e30, -1e30, np.inf, -np.inf]
+			for n, v in enumerate(values):
+				vt[pick[272 + 4 * n:276 + 4 * n]] = np.float32(v)
+			self.planted["special"] = (pick[272:272 + 4 * len(values)], np.repeat(np.array(values, np.float32), 4))
+			if dtype == "bfloat16":
+				vt = _round_bf16(vt)
+		assert not np.isnan(vt).any() and not np.isnan(lt).any()
+		self.value_table = np.ascontiguousarray(vt.reshape(-1))         # entry 21 h + k
+		self.logit_table = np.ascontiguousarray(lt)
+		self._tables_dev = {}                                           # device -> (w, value table, logit table, solved one-hot)
+
+	def _tables(self, device):
+		import torch
+		if device not in self._tables_dev:
+			dt = torch.bfloat16 if self.dtype == "bfloat16" else torch.float32
+			self._tables_dev[device] = (torch.from_numpy(self.w).to(device), torch.from_numpy(self.value_table).to(device).to(dt),
+			                            torch.from_numpy(self.logit_table).to(device).to(dt), torch.from_numpy(self.solved_oh).to(device))
+		return self._tables_dev[device]
+
+	def rows(self, x):
+		"""(h, k) of every row of a one-hot batch, as integer arrays (NumPy) or tensors (torch)."""
+		import torch
+		if isinstance(x, torch.Tensor):
+			w, _, _, sol = self._tables(x.device)
+			xf = x.float()
+			h = torch.remainder((xf * w).sum(dim=1), float(self.M)).long()
+			k = (20 - (xf * sol).sum(dim=1)).long()
+		else:
+			x = np.asarray(x, np.float32)
+			h = np.mod((x * self.w).sum(axis=1), np.float32(self.M)).astype(np.int64)
+			k = (20 - (x * self.solved_oh).sum(axis=1)).astype(np.int64)
+		return h, k
+
+	def __call__(self, x, policy=True, value=True):
+		import torch
+		h, k = self.rows(x)
+		out = []
+		if isinstance(x, torch.Tensor):
+			_, vt, lt, _ = self._tables(x.device)
+			if policy:
+				out.append(lt[h])
+			if value:
+				out.append(vt[21 * h + k].reshape(-1, 1))
+		else:
+			if policy:
+				out.append(self.logit_table[h])
+			if value:
+				out.append(self.value_table[21 * h + k].reshape(-1, 1))
+		return out if len(out) > 1 else out[0]
+
+
 def adi_traindata_oracle(net, games: int, depth: int, alpha: float, method: str):
 	"""
 	`Train.ADI_traindata` (train.py:256-339) on the CPU oracle: scramble (:277), 12-child fan-out (:285), rewards
@@ -284,8 +405,12 @@ class AStarOracle:
 class MCTSOracle:
 	"""agents.py:415-645.  One tree; arrays 1-based like the reference's."""
 
-	def __init__(self, net, c: float, search_graph: bool, nu: float = 100.0):
-		self.net, self.c, self.search_graph, self.nu = net, c, search_graph, nu
+	def __init__(self, net, c: float, search_graph: bool, nu: float = 100.0, priors=None):
+		"""`priors`: optional callable(states (n, 20) int8, root: bool) -> (n, 12) priors of those states, used instead of the
+		float32 softmax of the net's logits (`root`: the call is for the start state, whose softmax the reference takes on the
+		net's device, agents.py:472; every other call stands for the host's, :551-552).  It lets a test feed the tree arithmetic
+		the very P bits another implementation stored, whoever's exp made them."""
+		self.net, self.c, self.search_graph, self.nu, self.priors = net, c, search_graph, nu, priors
 
 	def reset(self, cap: int):
 		self.index = {}
@@ -303,8 +428,11 @@ class MCTSOracle:
 	def __len__(self):
 		return len(self.index)
 
-	def _policy_value(self, states):
+	def _policy_value(self, states, root=False):
 		import torch
+		if self.priors is not None:
+			p = np.asarray(self.priors(states, root), dtype=np.float64).reshape(len(states), 12)
+			return p, _values(self.net, states).astype(np.float64)
 		p, v = self.net(orc.as_oh(states))
 		p = torch.as_tensor(np.asarray(p)).float().softmax(dim=1).numpy()       # float32 softmax, as agents.py:552
 		return p.astype(np.float64), np.asarray(v, dtype=np.float32).reshape(-1).astype(np.float64)
@@ -316,7 +444,7 @@ class MCTSOracle:
 		self.states[1] = start
 		if orc.is_solved(start):
 			return True
-		p, v = self._policy_value(start[None])
+		p, v = self._policy_value(start[None], root=True)
 		self.P[1], self.V[1] = p[0], v[0]
 		path, actions = [1], []
 		while len(self) + 12 <= max_states and (max_sims is None or self.sims < max_sims):
@@ -356,7 +484,7 @@ class MCTSOracle:
 		self.W[leaf] = self.V[self.neighbors[leaf]]                          # :560
 		self.W[new_idx] = v[:, None]                                         # :561
 		for node, a in zip(path[:-1], actions):                              # :562 max-backup
-			self.W[node, a] = max(self.W[node, a], best)
+			self.W[node, a] = np.maximum(self.W[node, a], best)              # (of -0.0 and +0.0 either may come back)
 		if actions:                                                          # :567-570
 			for node, a in set(zip(path[:-1], actions)):                     # fancy `+=` counts a repeated pair once
 				self.N[node, a] += 1
