@@ -345,6 +345,45 @@ int rk_bfs_export(rk_bfs_t *h, size_t first, size_t count, int8_t *h_states, lon
  * error (RK_ESTATE: not won); writes at most max_len actions. */
 long long rk_bfs_path(rk_bfs_t *h, long long *h_actions, size_t max_len, void *stream);
 
+/* ---- device-resident two-sided breadth-first search: shortest solutions (quarter-turn metric) ---------------------
+ * One pool in index order holds two balls: side S around the start (node 1) and side G around the solved state (node 2).
+ * f and b count their complete levels.  One level grows at a time, S if f == b, else G; its parents are popped in index
+ * order, their children taken in action order 0..11.  Before every pop: n_states >= max_states ends the search (not
+ * won).  A child that the growing side already holds is skipped; one that the other side holds is the meeting: the
+ * search ends (won) and the child is not stored; any other is appended with its parent, action and side.  With f and b
+ * complete levels every solution has at least f + b + 1 moves and a meeting in the next level has exactly that many, so
+ * the first meeting is a shortest solution.  Results do not depend on `pops`.  The time limit is the caller's (checked
+ * between calls).  An engine handle is not thread-safe. */
+typedef struct rk_bibfs rk_bibfs_t;
+/* capacity: node pool size C (>= 2, both sides together); pops: the most nodes one iteration pops. */
+int rk_bibfs_create(rk_bibfs_t **out, size_t capacity, int pops);
+int rk_bibfs_destroy(rk_bibfs_t *h);
+/* Nodes 1 and 2, f = b = 0, with the state budget max_states.  The start is a host 20-byte state that is not solved
+ * (RK_EINVAL if it is: the answer is the empty queue).  Clears the table; synchronises. */
+int rk_bibfs_reset(rk_bibfs_t *h, const int8_t *h_start_state, long long max_states, void *stream);
+/* `iterations` iterations, stream-ordered, no synchronisation: each pops up to `pops` parents of the level that grows
+ * and never crosses a level boundary; iterations after the search is done are no-ops.  The caller keeps
+ * size + 12 * pops * iterations <= C (rk_bibfs_grow); an iteration whose children might not fit is skipped and reported
+ * as error 1. */
+int rk_bibfs_run(rk_bibfs_t *h, int iterations, void *stream);
+/* Synchronises; h_status[12] = done, won, n_states (both sides), iterations, nodes popped, stop reason (0 running,
+ * 1 met, 2 budget, 3 graph exhausted, 4 error), error, nodes the next iteration pops, f, b, the meeting node (the
+ * stored node of the other side that the meeting child equals; 0 if none), the side that grows (0 = S, 1 = G). */
+int rk_bibfs_status(rk_bibfs_t *h, long long *h_status, void *stream);
+/* Grows the node pool to new_capacity states in place between iterations, as rk_bfs_grow does. */
+int rk_bibfs_grow(rk_bibfs_t *h, size_t new_capacity, void *stream);
+/* Number of stored states on both sides together.  Synchronises. */
+long long rk_bibfs_size(const rk_bibfs_t *h);
+/* Rows [first, first+count) of the pool to HOST buffers (any may be NULL): states int8 (count, 20), parent index int64
+ * (0 for nodes 1 and 2), action int64 (the move from the parent, on side G away from solved) and side int64 (0 = S,
+ * 1 = G) of every node. */
+int rk_bibfs_export(rk_bibfs_t *h, size_t first, size_t count, int8_t *h_states, long long *h_parents, long long *h_actions,
+                    long long *h_sides, void *stream);
+/* The action queue of a search that met, start -> solved: the path to the S node of the meeting, the joining move, then
+ * the inverses of side G's actions from its node back to node 2; walked on the device.  Returns its length or a
+ * negative error (RK_ESTATE: not met); writes at most max_len actions. */
+long long rk_bibfs_path(rk_bibfs_t *h, long long *h_actions, size_t max_len, void *stream);
+
 /* ---- device-resident epsilon-greedy value maximisation (agents.py:649-726) ---------------------------------------
  * W = workers walkers take D = depth moves from a root (:692-715); the visited state with the best value becomes the next
  * root (:673-677) until a walker is solved (:710-713) or another round would pass max_states (:665).  The root, the

@@ -92,6 +92,15 @@ SIGNATURES = {
 	"rk_bfs_size": (C.c_longlong, [_vp]),
 	"rk_bfs_export": (_i, [_vp, _sz, _sz, _vp, _vp, _vp, _vp]),
 	"rk_bfs_path": (C.c_longlong, [_vp, _vp, _sz, _vp]),
+	"rk_bibfs_create": (_i, [C.POINTER(_vp), _sz, _i]),
+	"rk_bibfs_destroy": (_i, [_vp]),
+	"rk_bibfs_reset": (_i, [_vp, _vp, C.c_longlong, _vp]),
+	"rk_bibfs_run": (_i, [_vp, _i, _vp]),
+	"rk_bibfs_status": (_i, [_vp, _vp, _vp]),
+	"rk_bibfs_grow": (_i, [_vp, _sz, _vp]),
+	"rk_bibfs_size": (C.c_longlong, [_vp]),
+	"rk_bibfs_export": (_i, [_vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp]),
+	"rk_bibfs_path": (C.c_longlong, [_vp, _vp, _sz, _vp]),
 	"rk_egvm_create": (_i, [C.POINTER(_vp), _i, _i, _i]),
 	"rk_egvm_destroy": (_i, [_vp]),
 	"rk_egvm_net_in": (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_sz)]),

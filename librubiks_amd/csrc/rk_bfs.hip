@@ -49,7 +49,6 @@ enum {
 enum { BFS_STOP_NO = 0, BFS_STOP_WON = 1, BFS_STOP_BUDGET = 2, BFS_STOP_EMPTY = 3, BFS_STOP_ERROR = 4 };
 enum { BFS_ERR_NONE = 0, BFS_ERR_CAPACITY = 1 };
 
-constexpr uint32_t NO_SLOT = 0xFFFFFFFFu;       // the child's state is already stored: it takes no slot
 constexpr uint32_t NO_WIN = 0x7FFFFFFFu;
 
 struct BfsDev {
@@ -134,29 +133,9 @@ void k_bfs_expand(BfsDev d)
 __global__ __launch_bounds__(ASCAN)
 void k_bfs_scan(BfsDev d)
 {
-	__shared__ int s_wave[4];
-	__shared__ int s_ticket, s_base;
 	const int P = bfs_pops(d);
 	if (P == 0) return;                                                  // done: no ticket drawn, nothing to reset
-	const int b = scan_ticket(&d.ctr[B_TICKET], &s_ticket);
-	const int K = 12 * P, last = (K - 1) / ASCAN;
-	if (b > last) return;
-	const int c = b * ASCAN + threadIdx.x;
-	const bool valid = c < K;
-	bool fu = false;
-	if (valid) {
-		const uint32_t slot = d.slot[c];
-		fu = slot != NO_SLOT && __hip_atomic_load(&d.table[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (TENT | (uint32_t)c);
-	}
-	int total;
-	const int r = block_rank256(fu, s_wave, &total);
-	const uint32_t epoch = (uint32_t)d.ctr[B_EPOCH] + 1u;
-	const int base = scan_lookback(d.chain, b, total, epoch, &s_base);
-	if (valid) {
-		d.rank[c] = base + r;
-		d.first[c] = fu ? 1 : 0;
-	}
-	if (b == last && threadIdx.x == 0) d.ctr[B_TOTAL] = base + total;
+	frontier_scan(d.slot, d.table, d.rank, d.first, d.chain, &d.ctr[B_TICKET], (uint32_t)d.ctr[B_EPOCH] + 1u, &d.ctr[B_TOTAL], 12 * P);
 }
 
 // the cut and the append: child c is stored iff it is a first occurrence, lies before the winning position and its pop
@@ -200,11 +179,7 @@ __global__ void k_bfs_end(BfsDev d)
 	}
 	const int32_t size0 = d.ctr[B_SIZE], head = d.ctr[B_HEAD];
 	const long long budget = d.ctr[B_BUDGET];
-	int lo = 0, hi = P;                                                  // the first pop that fails the budget check (P: none)
-	while (lo < hi) {
-		const int mid = (lo + hi) >> 1;
-		if ((long long)size0 + d.rank[12 * mid] >= budget) hi = mid; else lo = mid + 1;
-	}
+	const int lo = first_refused_pop(d.rank, P, size0, budget);         // the first pop that fails the budget check (P: none)
 	const int cut_b = 12 * lo;
 	const int win = d.ctr[B_WINPOS];
 	const int cut = min(cut_b, win);
@@ -281,11 +256,7 @@ constexpr int BFS_WALK_MAX = 1 << 12;
 
 uint32_t bfs_table_mask(size_t capacity) { return (uint32_t)(table_slots(capacity, 1024) - 1); }
 
-size_t bfs_scan_blocks(int pops) { return (size_t)blocks((size_t)12 * pops, ASCAN) + 1; }
-
 int bfs_read_ctr(rk_bfs *h, int32_t *out, hipStream_t st) { return h->ctr_host.read(h->d.ctr, B_COUNT, out, st); }
-
-int bfs_budget_of(long long max_states) { return (int)std::min<long long>(std::max<long long>(max_states, 0), INT_MAX); }
 
 }  // namespace
 
@@ -306,7 +277,7 @@ int rk_bfs_create(rk_bfs_t **out, size_t capacity, int pops)
 	int e = RK_OK;
 	#define A(ptr, cnt) if (!e) e = h->pool.alloc(&d.ptr, (cnt))
 	A(states, C1 * 5); A(parent, C1); A(pact, C1); A(table, (size_t)d.mask + 1); A(ctr, B_COUNT);
-	A(slot, K); A(rank, K); A(first, K); A(chain, bfs_scan_blocks(pops));
+	A(slot, K); A(rank, K); A(first, K); A(chain, frontier_scan_blocks(pops));
 	#undef A
 	if (!e) e = h->pool.alloc(&h->root_dev, 8);
 	if (!e) e = h->pool.alloc(&h->walk, BFS_WALK_MAX + 8);
@@ -328,9 +299,9 @@ int rk_bfs_reset(rk_bfs_t *h, const int8_t *h_start_state, long long max_states,
 	hipStream_t st = (hipStream_t)stream;
 	BfsDev &d = h->d;
 	RK_HIP(hipMemsetAsync(d.table, 0, ((size_t)d.mask + 1) * sizeof(uint32_t), st));
-	RK_HIP(hipMemsetAsync(d.chain, 0, bfs_scan_blocks(d.pops) * sizeof(unsigned long long), st));      // look-back epochs restart
+	RK_HIP(hipMemsetAsync(d.chain, 0, frontier_scan_blocks(d.pops) * sizeof(unsigned long long), st));      // look-back epochs restart
 	RK_HIP(hipMemcpyAsync(h->root_dev, h_start_state, STATE_BYTES, hipMemcpyHostToDevice, st));
-	hipLaunchKernelGGL(k_bfs_root, dim3(1), dim3(64), 0, st, d, h->root_dev, bfs_budget_of(max_states));
+	hipLaunchKernelGGL(k_bfs_root, dim3(1), dim3(64), 0, st, d, h->root_dev, budget_of(max_states));
 	RK_HIP(hipGetLastError());
 	RK_HIP(hipStreamSynchronize(st));       // the host buffer may go away after return
 	h->ready = true;
@@ -351,7 +322,7 @@ int rk_bfs_set_budget(rk_bfs_t *h, long long max_states, void *stream)
 		hipLaunchKernelGGL(k_bfs_rehash, dim3(std::max<unsigned>(1u, std::min<unsigned>(blocks((size_t)c[B_SIZE] + 1), 4096u))), dim3(256), 0, st, d);
 		RK_HIP(hipGetLastError());
 	}
-	hipLaunchKernelGGL(k_bfs_set_budget, dim3(1), dim3(64), 0, st, h->d, bfs_budget_of(max_states));
+	hipLaunchKernelGGL(k_bfs_set_budget, dim3(1), dim3(64), 0, st, h->d, budget_of(max_states));
 	RK_HIP(hipGetLastError());
 	return RK_OK;
 }

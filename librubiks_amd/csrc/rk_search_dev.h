@@ -288,6 +288,50 @@ __device__ __forceinline__ int scan_lookback_classes(unsigned long long *words, 
 	return (cls < (uint32_t)W ? s_base[cls] : 0) + my;
 }
 
+// ---- what the breadth-first engines share (one-sided rk_bfs, two-sided rk_bibfs): a batch of K children in pop order ----
+constexpr uint32_t NO_SLOT = 0xFFFFFFFFu;       // slot[c] of a child that takes part in no claim (any value with the TENT bit)
+
+// First-occurrence flags of the batch and their exclusive prefix in batch order, one launch of ASCAN-thread workgroups: child c
+// is a first occurrence iff the slot it claimed (slot[c], TENT bit clear) still holds TENT | c once every child has probed.
+// Writes first[c] and rank[c] for c < K and the number of first occurrences to *total_out; `epoch` is the launch's (the
+// end-of-iteration kernel resets *ticket and moves the epoch on).  Call from ALL threads of the workgroup.
+__device__ __forceinline__ void frontier_scan(const uint32_t *slot, const uint32_t *table, int32_t *rank, uint8_t *first,
+                                              unsigned long long *chain, int32_t *ticket, uint32_t epoch, int32_t *total_out, int K)
+{
+	__shared__ int s_wave[4];
+	__shared__ int s_ticket, s_base;
+	const int b = scan_ticket(ticket, &s_ticket);
+	const int last = (K - 1) / ASCAN;
+	if (b > last) return;
+	const int c = b * ASCAN + threadIdx.x;
+	const bool valid = c < K;
+	bool fu = false;
+	if (valid) {
+		const uint32_t sl = slot[c];
+		fu = (sl & TENT) == 0u && __hip_atomic_load(&table[sl], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (TENT | (uint32_t)c);
+	}
+	int total;
+	const int r = block_rank256(fu, s_wave, &total);
+	const int base = scan_lookback(chain, b, total, epoch, &s_base);
+	if (valid) {
+		rank[c] = base + r;
+		first[c] = fu ? 1 : 0;
+	}
+	if (b == last && threadIdx.x == 0) *total_out = base + total;
+}
+
+// The first of the P pops of a batch that the state budget refuses, P when none is: pop j runs only if size0 + (new states of
+// the pops before j) < budget, and rank[12 j] is that count.  It only grows along the batch, hence the bisection.
+__device__ __forceinline__ int first_refused_pop(const int32_t *rank, int P, int32_t size0, long long budget)
+{
+	int lo = 0, hi = P;
+	while (lo < hi) {
+		const int mid = (lo + hi) >> 1;
+		if ((long long)size0 + rank[12 * mid] >= budget) hi = mid; else lo = mid + 1;
+	}
+	return lo;
+}
+
 __device__ __forceinline__ int lower_bound_rec(const Rec *a, int n, const Rec &x)
 {
 	int lo = 0, hi = n;

@@ -26,6 +26,12 @@ inline uint64_t table_slots(size_t capacity, uint64_t floor)
 	return t;
 }
 
+// look-back words of frontier_scan (rk_search_dev.h) over the 12 x pops children of a breadth-first batch, 256 per workgroup
+inline size_t frontier_scan_blocks(int pops) { return (size_t)blocks((size_t)12 * pops, 256) + 1; }
+
+// a caller's max_states as the int32 the device counters hold
+inline int budget_of(long long max_states) { return (int)std::min<long long>(std::max<long long>(max_states, 0), INT32_MAX); }
+
 // Owns device allocations: whatever alloc() handed out is freed by release(), or with the owner.  `slack` bytes are added to
 // every allocation (kernels may read a little past the last element with wide loads).
 class DevPool {

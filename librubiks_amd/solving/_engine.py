@@ -1,5 +1,5 @@
 """
-What the agents that drive a device engine (`rk_astar_*`, `rk_astarb_*`, `rk_mcts_*`, `rk_bfs_*`, `rk_egvm_*`, the sharded `rk_astar_*`) share on
+What the agents that drive a device engine (`rk_astar_*`, `rk_astarb_*`, `rk_mcts_*`, `rk_bfs_*`, `rk_bibfs_*`, `rk_egvm_*`, the sharded `rk_astar_*`) share on
 the host, each concern defined once: how the net is fed and read, how a step becomes a kept hipGraph, and how a finished search
 is read back (the lifetime of a library object is `_ffi.Owner`).  agents.py and sharded.py hold what differs between the engines.
 """

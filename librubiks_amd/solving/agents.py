@@ -411,6 +411,135 @@ class DeviceBFS(Agent, _ffi.Owner):
 		return f"Breadth-first search (device, pops={self.pops})"
 
 
+class DeviceBiBFS(Agent, _ffi.Owner):
+	"""
+	Two-sided breadth-first search with the whole search in HBM (engine rk_bibfs_*, csrc/rk_bibfs.hip): a SHORTEST solution in
+	the quarter-turn metric.  One pool in index order holds two balls, side S around the start (node 1) and side G around the
+	solved state (node 2); they grow one level at a time, S when both have as many complete levels, else G.  A level's parents
+	are popped in index order, their children taken in action order: a child its own side holds is skipped, a child the other
+	side holds is the meeting (the search ends, the child is not stored), any other is appended.  With `f` and `b` complete
+	levels every solution has at least f + b + 1 moves and a meeting in the next level has exactly that many, so the first
+	meeting is optimal.  The state budget is checked before every pop, as in `DeviceBFS`; the time limit when the host polls
+	(every `poll` iterations).  `action_queue`, len(agent), the pool and `depths` do not depend on `pops`.
+
+	`capacity`, `max_capacity`, `grown` and `capacity_exhausted` are `DeviceBFS`'s, for the pool of both sides together.  The
+	representation follows cube.get_is2024() when a search starts; the engine always runs on 20-byte states.
+	"""
+	default_capacity = 8_000_000
+	max_capacity = 400_000_000
+	MAX_POPS = 1 << 22                      # rk_bibfs_create's limit
+	MAX_CAPACITY = 0x3FFFFFF0
+
+	def __init__(self, pops: int = 16_384, capacity: int = None, max_capacity: int = None, poll: int = 8):
+		super().__init__()
+		if isinstance(pops, bool) or int(pops) != pops or not 1 <= int(pops) <= self.MAX_POPS:
+			raise ValueError(f"pops must be an integer in 1..{self.MAX_POPS}, got {pops!r}")
+		for name, v in (("capacity", capacity), ("max_capacity", max_capacity)):
+			if v is not None and (isinstance(v, bool) or int(v) != v or not 2 <= int(v) <= self.MAX_CAPACITY):
+				raise ValueError(f"{name} must be an integer in 2..{self.MAX_CAPACITY}, got {v!r}")
+		if isinstance(poll, bool) or int(poll) != poll or int(poll) < 1:
+			raise ValueError(f"poll must be a positive integer, got {poll!r}")
+		self.pops, self.poll = int(pops), int(poll)
+		self.capacity = int(capacity) if capacity is not None else None
+		if max_capacity is not None:
+			self.max_capacity = int(max_capacity)
+		self._h, self._h_cap = None, 0
+		self._n = 0
+		self._is2024 = True
+		self._cache = None
+		self._meet = 0                      # the stored node that the meeting child equals
+		self.depths = (0, 0)                # complete levels (f, b) of sides S and G after the last search
+		self.iterations = 0
+		self.popped = 0                     # nodes the last search popped, both sides together (each has 12 children)
+		self.grown = 0
+		self.capacity_exhausted = False
+
+	def _engine(self, capacity: int):
+		if self._h is not None and self._h_cap >= capacity:
+			return self._h                  # (a pool that grew in an earlier search is kept: rk_bibfs_reset clears its table)
+		self._h_cap = capacity
+		return self._create("rk_bibfs_create", "rk_bibfs_destroy", capacity, self.pops)
+
+	def _grow(self, h) -> bool:
+		if self._h_cap >= self.max_capacity:
+			eng.pool_exhausted(self, self._h_cap, "cannot take the next iteration")
+			return False
+		cap = min(2 * self._h_cap, self.max_capacity)
+		_ffi.check(_ffi.lib().rk_bibfs_grow(h, cap, _ffi.stream_ptr()))
+		self._h_cap = cap
+		self.grown += 1
+		return True
+
+	@no_grad
+	def search(self, state: np.ndarray, time_limit: float = None, max_states: int = None) -> bool:
+		_ffi.require_gpu()
+		t0 = time.perf_counter()
+		time_limit, max_states = self.reset(time_limit or 1e10, max_states)        # (an exact search may run without either limit)
+		self._n, self._cache, self.iterations, self.grown, self.capacity_exhausted = 0, None, 0, 0, False
+		self.popped, self._meet, self.depths = 0, 0, (0, 0)
+		self._is2024 = cube.get_is2024()
+		root = _roots20(self._is2024, state, 1)[0]          # ValueError for an illegal 6x8x6 state
+		if (root == _SOLVED20).all():
+			return True
+		lib, stream = _ffi.lib(), _ffi.stream_ptr()
+		K = 12 * self.pops
+		budget = int(min(max_states, 2 ** 31 - 1))
+		cap = self.capacity or min(budget + K, self.default_capacity)
+		cap = max(2, min(cap, self.max_capacity, self.MAX_CAPACITY))
+		h = self._engine(cap)
+		_ffi.check(lib.rk_bibfs_reset(h, root.ctypes.data, budget, stream))
+		self._n = 2
+		status = (C.c_longlong * 12)()
+		_ffi.check(lib.rk_bibfs_status(h, status, stream))
+		while not status[0]:
+			room = (self._h_cap - self._n) // K              # iterations the pool takes whatever they find
+			if room == 0:
+				if not self._grow(h):
+					return False
+				continue
+			_ffi.check(lib.rk_bibfs_run(h, eng.burst(min(self.poll, room), budget - self._n, K), stream))
+			_ffi.check(lib.rk_bibfs_status(h, status, stream))
+			self._n, self.iterations, self.popped = int(status[2]), int(status[3]), int(status[4])
+			self.depths, self._meet = (int(status[8]), int(status[9])), int(status[10])
+			if status[6]:
+				raise _ffi.RubiksHipError(f"two-sided BFS engine error code {int(status[6])}")
+			if not status[0] and time.perf_counter() - t0 >= time_limit:
+				return False
+		if status[1]:
+			self.action_queue = eng.read_path(lib.rk_bibfs_path, h)
+			return True
+		return False
+
+	def arrays(self):
+		"""(states, parents, actions, sides) of nodes 1 .. len(agent) in index order: states (n, 20) int8, or (n, 6, 8, 6) in 6x8x6
+		mode; parents int64 node indices (0 for nodes 1 and 2); actions int64, the move from the parent -- on side G away from
+		solved -- (-1 for nodes 1 and 2); sides int64, 0 = around the start, 1 = around the solved state."""
+		if self._cache is None:
+			n = self._n
+			states = np.zeros((n + 1, 20), np.int8)
+			parents, actions, sides = np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int64)
+			if n and self._h is not None:
+				_ffi.check(_ffi.lib().rk_bibfs_export(self._h, 1, n, states[1:].ctypes.data, parents[1:].ctypes.data,
+				                                       actions[1:].ctypes.data, sides[1:].ctypes.data, _ffi.stream_ptr()))
+			actions[1:3] = -1
+			self._cache = (_states_out(self._is2024, states, n)[1:], parents[1:], actions[1:], sides[1:])
+		return self._cache
+
+	@property
+	def meeting(self):
+		"""The state where the sides met -- the child that was not stored, held by the other side -- in the representation of the
+		search; None when the last search did not meet."""
+		if not self._meet:
+			return None
+		return self.arrays()[0][self._meet - 1].copy()
+
+	def __len__(self):
+		return self._n
+
+	def __str__(self):
+		return f"Two-sided breadth-first search (device, pops={self.pops})"
+
+
 class PolicySearch(DeepAgent):
 	"""Follow (or sample from) the policy head (agents.py:132-151)."""
 	def __init__(self, net, sample_policy=False):
