@@ -384,6 +384,69 @@ int rk_bibfs_export(rk_bibfs_t *h, size_t first, size_t count, int8_t *h_states,
  * negative error (RK_ESTATE: not met); writes at most max_len actions. */
 long long rk_bibfs_path(rk_bibfs_t *h, long long *h_actions, size_t max_len, void *stream);
 
+/* ---- the goal ball: exact distances and shortest solutions from a kept table (quarter-turn metric) -----------------
+ * Every state within `radius` moves of the solved state, built once and kept in HBM.  Node 1 is the solved state, the pool
+ * is in index order: a level's parents are popped in index order, never across a level boundary, their children taken in
+ * action order 0..11; a child the pool holds is skipped, every other is appended with its parent and its action, the move
+ * AWAY from solved.  Level `radius` is stored and never expanded.  Level l is the index range level_start[l] ..
+ * level_start[l + 1] - 1, so a node's depth follows from its index.  The capacity is exact (level sizes 1, 12, 114, 1 068,
+ * 10 011, 93 840, 878 880, 8 221 632, 76 843 595) and every completed level is checked against them.  The pool does not
+ * depend on `pops`.  After the build the ball is read-only; any number of queries and searches may read it. */
+typedef struct rk_ball rk_ball_t;
+/* radius 0..8; pops: the most parents one iteration of the build pops.  Allocates nothing. */
+int rk_ball_create(rk_ball_t **out, int radius, int pops);
+/* RK_ESTATE while a search (rk_bsearch_*) is attached to the ball. */
+int rk_ball_destroy(rk_ball_t *h);
+/* Builds the ball (nothing if it is built): iterations of four launches, the host looks every `poll` of them.  A level of
+ * the wrong size or a state too many is an engine error (RK_ESTATE); RK_ECAPACITY when the device has no room.  Afterwards
+ * no table slot is tentative.  Synchronises. */
+int rk_ball_build(rk_ball_t *h, int poll, void *stream);
+/* h_status[16] = built, n_states, iterations of the build, radius, capacity, attached searches, then level_start[0 ..
+ * radius + 1] (zeros before the build and beyond radius + 1).  Touches no device. */
+int rk_ball_status(rk_ball_t *h, long long *h_status);
+/* Rows [first, first+count) of the pool to HOST buffers (any may be NULL): states int8 (count, 20), parent index int64
+ * (0 for node 1) and action int64 of every node. */
+int rk_ball_export(rk_ball_t *h, size_t first, size_t count, int8_t *h_states, long long *h_parents, long long *h_actions,
+                   void *stream);
+/* d_depth[q] = exact distance to solved of DEVICE state q of d_states int8 (n, 20), -1 for a state outside the ball.  One
+ * launch, one thread per query, nothing of the ball is written; stream-ordered, no synchronisation. */
+int rk_ball_depth(rk_ball_t *h, const int8_t *d_states, size_t n, int32_t *d_depth, void *stream);
+/* The shortest solution of every DEVICE state of d_states: d_lengths[q] moves (-1 outside the ball), row q of d_actions
+ * int8 (n, radius) holds them, padded with -1.  One launch; stream-ordered, no synchronisation. */
+int rk_ball_solve(rk_ball_t *h, const int8_t *d_states, size_t n, int32_t *d_lengths, int8_t *d_actions, void *stream);
+
+/* ---- shortest solutions by a one-sided breadth-first search from the start that ends at the ball ------------------------
+ * rk_bfs's protocol in a pool of its own (node 1 = the start), one level at a time: a child the own pool holds is skipped,
+ * a child the BALL holds is the meeting -- the search ends (won), the child is not stored, the lowest batch position wins
+ * --, any other is appended.  Before every pop: n_states >= max_states ends the search (not won).  A start at distance
+ * D > radius meets at level D - radius in a node of ball depth `radius`, so the first meeting is a shortest solution.  A
+ * start that the ball holds is answered at the reset, without a pop.  Results do not depend on `pops`.  Several searches may
+ * share one ball; a handle is not thread-safe. */
+typedef struct rk_bsearch rk_bsearch_t;
+/* capacity: size C (>= 2) of the own pool, whose table is sized to it; attaches to `ball` (built or not). */
+int rk_bsearch_create(rk_bsearch_t **out, rk_ball_t *ball, size_t capacity, int pops);
+int rk_bsearch_destroy(rk_bsearch_t *h);
+/* Node 1 = the host 20-byte start state, with the state budget max_states.  Clears the own table, never the ball's;
+ * RK_ESTATE if the ball is not built.  Synchronises. */
+int rk_bsearch_reset(rk_bsearch_t *h, const int8_t *h_start_state, long long max_states, void *stream);
+/* As rk_bibfs_run. */
+int rk_bsearch_run(rk_bsearch_t *h, int iterations, void *stream);
+/* Synchronises; h_status[10] = done, won, n_states, iterations, nodes popped, stop reason (0 running, 1 met, 2 budget,
+ * 3 graph exhausted, 4 error), error, nodes the next iteration pops, complete levels, the meeting node IN THE BALL (0 if
+ * none; the start's own node when the ball holds the start). */
+int rk_bsearch_status(rk_bsearch_t *h, long long *h_status, void *stream);
+/* Grows the own pool to new_capacity states in place between iterations, as rk_bfs_grow does. */
+int rk_bsearch_grow(rk_bsearch_t *h, size_t new_capacity, void *stream);
+/* Number of stored states of the own pool.  Synchronises. */
+long long rk_bsearch_size(const rk_bsearch_t *h);
+/* Rows [first, first+count) of the own pool to HOST buffers (any may be NULL), as rk_bfs_export. */
+int rk_bsearch_export(rk_bsearch_t *h, size_t first, size_t count, int8_t *h_states, long long *h_parents, long long *h_actions,
+                      void *stream);
+/* The action queue of a search that met, start -> solved: the path to the popped parent, the meeting action, then the
+ * ball's path from the meeting node; walked on the device.  Returns its length or a negative error (RK_ESTATE: not met);
+ * writes at most max_len actions. */
+long long rk_bsearch_path(rk_bsearch_t *h, long long *h_actions, size_t max_len, void *stream);
+
 /* ---- device-resident epsilon-greedy value maximisation (agents.py:649-726) ---------------------------------------
  * W = workers walkers take D = depth moves from a root (:692-715); the visited state with the best value becomes the next
  * root (:673-677) until a walker is solved (:710-713) or another round would pass max_states (:665).  The root, the

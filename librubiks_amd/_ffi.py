@@ -101,6 +101,22 @@ SIGNATURES = {
 	"rk_bibfs_size": (C.c_longlong, [_vp]),
 	"rk_bibfs_export": (_i, [_vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp]),
 	"rk_bibfs_path": (C.c_longlong, [_vp, _vp, _sz, _vp]),
+	"rk_ball_create": (_i, [C.POINTER(_vp), _i, _i]),
+	"rk_ball_destroy": (_i, [_vp]),
+	"rk_ball_build": (_i, [_vp, _i, _vp]),
+	"rk_ball_status": (_i, [_vp, _vp]),
+	"rk_ball_export": (_i, [_vp, _sz, _sz, _vp, _vp, _vp, _vp]),
+	"rk_ball_depth": (_i, [_vp, _vp, _sz, _vp, _vp]),
+	"rk_ball_solve": (_i, [_vp, _vp, _sz, _vp, _vp, _vp]),
+	"rk_bsearch_create": (_i, [C.POINTER(_vp), _vp, _sz, _i]),
+	"rk_bsearch_destroy": (_i, [_vp]),
+	"rk_bsearch_reset": (_i, [_vp, _vp, C.c_longlong, _vp]),
+	"rk_bsearch_run": (_i, [_vp, _i, _vp]),
+	"rk_bsearch_status": (_i, [_vp, _vp, _vp]),
+	"rk_bsearch_grow": (_i, [_vp, _sz, _vp]),
+	"rk_bsearch_size": (C.c_longlong, [_vp]),
+	"rk_bsearch_export": (_i, [_vp, _sz, _sz, _vp, _vp, _vp, _vp]),
+	"rk_bsearch_path": (C.c_longlong, [_vp, _vp, _sz, _vp]),
 	"rk_egvm_create": (_i, [C.POINTER(_vp), _i, _i, _i]),
 	"rk_egvm_destroy": (_i, [_vp]),
 	"rk_egvm_net_in": (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_sz)]),

@@ -1,0 +1,747 @@
+// The goal ball: every state within `radius` quarter turns of the solved state, built once and kept in HBM, and what reads it --
+// exact distances and shortest solutions of batches of states in one launch, and a one-sided breadth-first search from a start
+// that ends at the first child the ball holds.  (rk_bibfs.hip rebuilds the solved side's ball for every search; it is the same
+// for every start.)
+//
+// The ball (rk_ball_*).  Node 1 is the solved state, the pool is in index order.  A level's parents are popped in index order,
+// never across a level boundary, their children taken in action order 0..11; a child the pool holds (an earlier child of the
+// batch included) is skipped, every other is appended with its parent and its action -- the move AWAY from solved.  The build
+// ends when level `radius` is complete; that level is stored and never expanded.  Level l is the index range lstart[l] ..
+// lstart[l + 1] - 1, so a node's depth follows from its index: there is no depth array.  The capacity is exact, from the level
+// sizes of the quarter-turn Cayley graph (BALL_LEVELS), and every completed level is checked against them.
+//   states  int8 (C+1, 20), parent int32 (C+1), pact uint8 (C+1), table uint32 (T = pow2 >= 2C)       as in rk_bfs.hip
+// An iteration is the four launches of rk_bfs.hip (expand with election, scan, append, end) without goal test, budget or cut:
+// every claim of a batch is appended, so between iterations -- and once the build is over -- no table slot is tentative.  The
+// pool is never too small for a batch unless the engine is wrong; the append checks every index all the same.
+// After the build the ball is read-only:
+//   k_ball_depth   one thread per query: read-only probe (probe_find), 20-byte compare, depth from the level boundaries; -1 outside
+//   k_ball_solve   the same, then the walk along the parents: the inverse of every stored action leads back to solved
+//
+// The search (rk_bsearch_*) is rk_bfs.hip's protocol from the start (node 1 of a pool of its own) with rk_bibfs.hip's level
+// bookkeeping and meeting: a child the own pool holds is skipped, a child the BALL holds is the meeting -- not stored, the lowest
+// batch position wins --, every other is appended.  The budget is checked before every pop; the cut is min(12 x the first
+// refused pop, the lowest batch position of a meeting); nothing at or after it is stored.  A start at distance D > R has no
+// state of a level k < D - R in the ball, and every hit at level D - R has ball depth exactly R: the first meeting in index and
+// action order is a shortest solution.  A start that the ball holds is answered by the ball's path without a pop.  The own
+// table is sized to the own pool; a reset clears it and never the ball's.
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <climits>
+#include <cstring>
+#include <vector>
+
+#include "../../include/rubiks_hip.h"
+#include "rk_device.h"
+#include "rk_error.h"
+#include "rk_search_dev.h"
+#include "rk_search_host.h"
+
+namespace rk {
+
+constexpr int BALL_MAX_RADIUS = 8;
+// states at distance 0 .. 8 from solved in the quarter-turn metric
+constexpr int32_t BALL_LEVELS[BALL_MAX_RADIUS + 1] = {1, 12, 114, 1068, 10011, 93840, 878880, 8221632, 76843595};
+static __constant__ int32_t D_BALL_LEVELS[BALL_MAX_RADIUS + 1] = {1, 12, 114, 1068, 10011, 93840, 878880, 8221632, 76843595};
+
+enum {
+	G_SIZE = 0, G_HEAD, G_DONE, G_STOP, G_ITERS, G_ERROR, G_NPOP, G_TOTAL, G_EPOCH, G_TICKET, G_LEVEL, G_HI,
+	G_LSTART /* [BALL_MAX_RADIUS + 2] */, G_COUNT = 32
+};
+enum { BALL_STOP_NO = 0, BALL_STOP_BUILT = 1, BALL_STOP_ERROR = 4 };
+enum { BALL_ERR_NONE = 0, BALL_ERR_CAPACITY = 1, BALL_ERR_LEVEL = 2 };
+
+struct BallDev {
+	uint32_t mask, cap1;                        // table slots - 1, capacity + 1
+	int pops, radius;
+	uint32_t *states; int32_t *parent; uint8_t *pact; uint32_t *table;
+	int32_t *ctr;
+	uint32_t *slot; int32_t *rank; uint8_t *first;                   // per child of the batch (freed after the build)
+	unsigned long long *chain;
+};
+
+// What the readers of a built ball get, by value: nothing in it changes any more.
+struct BallView {
+	uint32_t mask, cap1;
+	int radius;
+	int32_t lstart[BALL_MAX_RADIUS + 2];        // level l = lstart[l] .. lstart[l + 1] - 1; INT32_MAX beyond radius + 1
+	const uint32_t *states; const int32_t *parent; const uint8_t *pact; const uint32_t *table;
+};
+
+__device__ __forceinline__ int ball_depth_of(const BallView &b, uint32_t idx)
+{
+	int depth = 0;
+	#pragma unroll
+	for (int l = 1; l <= BALL_MAX_RADIUS; l++) depth += (int32_t)idx >= b.lstart[l] ? 1 : 0;
+	return depth;
+}
+
+// After the pops of an iteration (or the root): the end of a level with its size check, the end of the build, the next P.  One thread.
+__device__ __forceinline__ void ball_next(const BallDev &d)
+{
+	const int32_t size = d.ctr[G_SIZE], head = d.ctr[G_HEAD];
+	int level = d.ctr[G_LEVEL];
+	int32_t hi = d.ctr[G_HI];
+	int stop = BALL_STOP_NO;
+	if (head > hi) {                                                     // every parent of `level` was popped: level + 1 is complete
+		level += 1;
+		if (size - hi != D_BALL_LEVELS[level]) { d.ctr[G_ERROR] = BALL_ERR_LEVEL; stop = BALL_STOP_ERROR; }
+		d.ctr[G_LSTART + level + 1] = size + 1;
+		d.ctr[G_LEVEL] = level;
+		d.ctr[G_HI] = hi = size;
+	}
+	if (!stop && level >= d.radius) stop = BALL_STOP_BUILT;              // level `radius` is stored and never expanded
+	d.ctr[G_STOP] = stop;
+	d.ctr[G_DONE] = stop ? 1 : 0;
+	d.ctr[G_NPOP] = stop ? 0 : min(d.pops, hi - head + 1);
+}
+
+__global__ void k_ball_root(BallDev d)
+{
+	const int tid = threadIdx.x;
+	if (tid < G_COUNT) d.ctr[tid] = 0;
+	__syncthreads();
+	if (tid != 0) return;
+	uint32_t s[5];
+	#pragma unroll
+	for (int j = 0; j < 5; j++) { s[j] = SOLVED_DW[j]; d.states[5 + j] = s[j]; }
+	d.parent[1] = 0; d.pact[1] = 0;
+	d.table[hash_state(s) & d.mask] = 1u;
+	d.ctr[G_SIZE] = 1; d.ctr[G_HEAD] = 1; d.ctr[G_HI] = 1;
+	d.ctr[G_LSTART] = 1; d.ctr[G_LSTART + 1] = 2;
+	ball_next(d);
+}
+
+__global__ __launch_bounds__(256)
+void k_ball_expand(BallDev d)
+{
+	__shared__ u32x4 s_act[36];
+	stage_action_tables(s_act, threadIdx.x);
+	__syncthreads();
+	const int P = d.ctr[G_NPOP];
+	const int c = blockIdx.x * blockDim.x + threadIdx.x;
+	if (c >= 12 * P) return;
+	const int32_t head = d.ctr[G_HEAD];
+	const int i = c / 12, a = c - 12 * i;
+	uint32_t s[5];
+	child_state(d.states, head + i, s_act, (uint32_t)a, s);
+	uint32_t slot = 0;
+	const uint32_t e = probe_elect(d.table, d.mask, d.states, s, c,
+	                               [&](int c2, uint32_t o[5]) { child_state(d.states, head + c2 / 12, s_act, (uint32_t)(c2 % 12), o); }, &slot);
+	d.slot[c] = e == 0u ? slot : NO_SLOT;
+}
+
+__global__ __launch_bounds__(ASCAN)
+void k_ball_scan(BallDev d)
+{
+	const int P = d.ctr[G_NPOP];
+	if (P == 0) return;                                                  // done: no ticket drawn, nothing to reset
+	frontier_scan(d.slot, d.table, d.rank, d.first, d.chain, &d.ctr[G_TICKET], (uint32_t)d.ctr[G_EPOCH] + 1u, &d.ctr[G_TOTAL], 12 * P);
+}
+
+// every first occurrence is stored: there is no cut, so every claim of the batch becomes an index
+__global__ __launch_bounds__(256)
+void k_ball_append(BallDev d)
+{
+	__shared__ u32x4 s_act[36];
+	stage_action_tables(s_act, threadIdx.x);
+	__syncthreads();
+	const int P = d.ctr[G_NPOP];
+	const int c = blockIdx.x * blockDim.x + threadIdx.x;
+	if (c >= 12 * P || !d.first[c]) return;
+	const int i = c / 12, a = c - 12 * i;
+	const uint32_t idx = (uint32_t)d.ctr[G_SIZE] + 1u + (uint32_t)d.rank[c];
+	if (idx >= d.cap1) { d.ctr[G_ERROR] = BALL_ERR_CAPACITY; return; }   // more states than the level sizes allow: an engine error
+	const int32_t p = d.ctr[G_HEAD] + i;
+	uint32_t s[5];
+	child_state(d.states, p, s_act, (uint32_t)a, s);
+	#pragma unroll
+	for (int j = 0; j < 5; j++) d.states[(size_t)idx * 5 + j] = s[j];
+	d.parent[idx] = p;
+	d.pact[idx] = (uint8_t)a;
+	d.table[d.slot[c]] = idx;
+}
+
+__global__ void k_ball_end(BallDev d)
+{
+	if (threadIdx.x != 0 || blockIdx.x != 0) return;
+	const int P = d.ctr[G_NPOP];
+	if (P == 0) return;
+	d.ctr[G_ITERS] += 1;
+	d.ctr[G_TICKET] = 0;
+	d.ctr[G_EPOCH] += 1;
+	if (d.ctr[G_ERROR]) {
+		d.ctr[G_STOP] = BALL_STOP_ERROR; d.ctr[G_DONE] = 1; d.ctr[G_NPOP] = 0;
+		return;
+	}
+	d.ctr[G_SIZE] += d.ctr[G_TOTAL];
+	d.ctr[G_HEAD] += P;
+	ball_next(d);
+}
+
+// exact distance to solved of query q, -1 outside the ball: one thread per query, nothing is written but the answer
+__global__ __launch_bounds__(256)
+void k_ball_depth(BallView b, const uint32_t *queries, size_t n, int32_t *depth)
+{
+	const size_t q = (size_t)blockIdx.x * 256 + threadIdx.x;
+	if (q >= n) return;
+	uint32_t s[5];
+	load5(queries + q * 5, s);
+	const uint32_t e = probe_find(b.table, b.mask, b.states, s);
+	depth[q] = e ? ball_depth_of(b, e) : -1;
+}
+
+// the shortest solution of query q: from its node along the parents, the inverse of every stored action (those lead away from
+// solved); row q of `actions` (n, radius) is padded with -1, lengths[q] = -1 outside the ball
+__global__ __launch_bounds__(256)
+void k_ball_solve(BallView b, const uint32_t *queries, size_t n, int32_t *lengths, int8_t *actions)
+{
+	const size_t q = (size_t)blockIdx.x * 256 + threadIdx.x;
+	if (q >= n) return;
+	uint32_t s[5];
+	load5(queries + q * 5, s);
+	uint32_t i = probe_find(b.table, b.mask, b.states, s);
+	int8_t *row = actions + q * (size_t)b.radius;
+	int len = 0;
+	bool ok = i != 0u;
+	while (ok && i != 1u) {
+		if (len >= b.radius) { ok = false; break; }                      // (a chain longer than the radius: never in a ball that passed its build)
+		row[len++] = (int8_t)(b.pact[i] ^ 1);                            // cube.rev_action: the two turns of a face are a, a ^ 1
+		i = (uint32_t)b.parent[i];
+		ok = i >= 1u && i < b.cap1;
+	}
+	lengths[q] = ok ? len : -1;
+	for (int k = ok ? len : 0; k < b.radius; k++) row[k] = -1;
+}
+
+// ---- the search from a start towards the ball -------------------------------------------------------------------------------
+enum {
+	S_SIZE = 0, S_HEAD, S_DONE, S_WON, S_WPARENT, S_WACT, S_STOP, S_ITERS, S_ERROR, S_NPOP, S_BUDGET, S_WINPOS, S_TOTAL, S_EPOCH,
+	S_TICKET, S_DEPTH, S_HI, S_MEET, S_POPPED, S_COUNT = 32
+};
+enum { BS_STOP_NO = 0, BS_STOP_WON = 1, BS_STOP_BUDGET = 2, BS_STOP_EMPTY = 3, BS_STOP_ERROR = 4 };
+enum { BS_ERR_NONE = 0, BS_ERR_CAPACITY = 1 };
+
+constexpr uint32_t BS_NO_WIN = 0x7FFFFFFFu;
+
+struct SrchDev {
+	uint32_t mask, cap1;                        // table slots - 1, capacity + 1 of the OWN pool
+	int pops;
+	uint32_t *states; int32_t *parent; uint8_t *pact; uint32_t *table;
+	int32_t *ctr;
+	uint32_t *slot; int32_t *rank; uint8_t *first;                   // per child of the batch: claimed slot (or TENT | meeting node), exclusive prefix, first occurrence
+	unsigned long long *chain;
+};
+
+// After a pop count change: the end of a level, the done flags and the next P (rk_bibfs.hip: bibfs_next, one side).  One thread.
+__device__ __forceinline__ void srch_next(const SrchDev &d)
+{
+	const int32_t size = d.ctr[S_SIZE], head = d.ctr[S_HEAD];
+	int32_t hi = d.ctr[S_HI];
+	if (head > hi) {                                                     // the level is exhausted and nothing met: it is complete
+		d.ctr[S_DEPTH] += 1;
+		d.ctr[S_HI] = hi = size;
+	}
+	int stop = BS_STOP_NO;
+	if (head > hi) stop = BS_STOP_EMPTY;                                 // a level without a state: the whole graph was seen
+	else if (size >= d.ctr[S_BUDGET]) stop = BS_STOP_BUDGET;            // checked before the next pop
+	d.ctr[S_STOP] = stop;
+	d.ctr[S_DONE] = stop ? 1 : 0;
+	d.ctr[S_NPOP] = stop ? 0 : min(d.pops, hi - head + 1);
+}
+
+// The pops of this iteration, or 0 when it is done or its children might not fit the pool (rk_bfs.hip: bfs_pops).
+__device__ __forceinline__ int srch_pops(const SrchDev &d)
+{
+	const int P = d.ctr[S_NPOP];
+	return (uint64_t)d.ctr[S_SIZE] + 12ull * (uint64_t)P <= (uint64_t)d.cap1 - 1u ? P : 0;
+}
+
+__global__ void k_bsearch_root(SrchDev d, BallView b, const uint32_t *root, int budget)
+{
+	const int tid = threadIdx.x;
+	if (tid < S_COUNT) d.ctr[tid] = 0;
+	__syncthreads();
+	if (tid != 0) return;
+	uint32_t s[5];
+	load5(root, s);
+	#pragma unroll
+	for (int j = 0; j < 5; j++) d.states[5 + j] = s[j];
+	d.parent[1] = 0; d.pact[1] = 0;
+	d.table[hash_state(s) & d.mask] = 1u;
+	d.ctr[S_SIZE] = 1; d.ctr[S_HEAD] = 1; d.ctr[S_HI] = 1;
+	d.ctr[S_BUDGET] = budget;
+	d.ctr[S_WINPOS] = (int32_t)BS_NO_WIN;
+	const uint32_t e = probe_find(b.table, b.mask, b.states, s);
+	if (e != 0u) {                                                       // the ball holds the start: its path is the answer, nothing is popped
+		d.ctr[S_WON] = 1; d.ctr[S_MEET] = (int32_t)e;
+		d.ctr[S_STOP] = BS_STOP_WON; d.ctr[S_DONE] = 1;
+		return;
+	}
+	srch_next(d);
+}
+
+// fan-out, the look-up in the ball (read-only), then membership / election in the own table: one thread per child
+__global__ __launch_bounds__(256)
+void k_bsearch_expand(SrchDev d, BallView b)
+{
+	__shared__ u32x4 s_act[36];
+	stage_action_tables(s_act, threadIdx.x);
+	__syncthreads();
+	const int P = srch_pops(d);
+	const int c = blockIdx.x * blockDim.x + threadIdx.x;
+	if (c >= 12 * P) return;
+	const int32_t head = d.ctr[S_HEAD];
+	const int i = c / 12, a = c - 12 * i;
+	uint32_t s[5];
+	child_state(d.states, head + i, s_act, (uint32_t)a, s);
+	// no state is in both pools (the start is outside the ball and nothing the ball holds is ever stored), so the order of the two
+	// look-ups decides nothing; the ball first, so that a meeting child leaves no claim in the own table
+	const uint32_t m = probe_find(b.table, b.mask, b.states, s);
+	if (m != 0u) {
+		atomicMin(reinterpret_cast<uint32_t *>(&d.ctr[S_WINPOS]), (uint32_t)c);
+		d.slot[c] = TENT | m;                                            // no claim (TENT bit); k_bsearch_end reads the meeting node here
+		return;
+	}
+	uint32_t slot = 0;
+	const uint32_t e = probe_elect(d.table, d.mask, d.states, s, c,
+	                               [&](int c2, uint32_t o[5]) { child_state(d.states, head + c2 / 12, s_act, (uint32_t)(c2 % 12), o); }, &slot);
+	d.slot[c] = e == 0u ? slot : NO_SLOT;
+}
+
+__global__ __launch_bounds__(ASCAN)
+void k_bsearch_scan(SrchDev d)
+{
+	const int P = srch_pops(d);
+	if (P == 0) return;                                                  // done: no ticket drawn, nothing to reset
+	frontier_scan(d.slot, d.table, d.rank, d.first, d.chain, &d.ctr[S_TICKET], (uint32_t)d.ctr[S_EPOCH] + 1u, &d.ctr[S_TOTAL], 12 * P);
+}
+
+// child c is stored iff it is a first occurrence before the cut (rk_bfs.hip: k_bfs_append)
+__global__ __launch_bounds__(256)
+void k_bsearch_append(SrchDev d)
+{
+	__shared__ u32x4 s_act[36];
+	stage_action_tables(s_act, threadIdx.x);
+	__syncthreads();
+	const int P = srch_pops(d);
+	const int c = blockIdx.x * blockDim.x + threadIdx.x;
+	if (c >= 12 * P || !d.first[c]) return;
+	if ((uint32_t)c >= (uint32_t)d.ctr[S_WINPOS]) return;
+	const int i = c / 12, a = c - 12 * i;
+	const int32_t size0 = d.ctr[S_SIZE];
+	if ((long long)size0 + d.rank[12 * i] >= (long long)d.ctr[S_BUDGET]) return;
+	const uint32_t idx = (uint32_t)size0 + 1u + (uint32_t)d.rank[c];
+	if (idx >= d.cap1) { d.ctr[S_ERROR] = BS_ERR_CAPACITY; return; }
+	const int32_t p = d.ctr[S_HEAD] + i;
+	uint32_t s[5];
+	child_state(d.states, p, s_act, (uint32_t)a, s);
+	#pragma unroll
+	for (int j = 0; j < 5; j++) d.states[(size_t)idx * 5 + j] = s[j];
+	d.parent[idx] = p;
+	d.pact[idx] = (uint8_t)a;
+	d.table[d.slot[c]] = idx;
+}
+
+// where the cut fell, the new size / head, the meeting, the end of a level, the next P.  One thread, ordinary stores.
+__global__ void k_bsearch_end(SrchDev d)
+{
+	if (threadIdx.x != 0 || blockIdx.x != 0) return;
+	if (d.ctr[S_NPOP] == 0) return;
+	const int P = srch_pops(d);
+	if (P == 0) {
+		d.ctr[S_ERROR] = BS_ERR_CAPACITY;
+		d.ctr[S_STOP] = BS_STOP_ERROR; d.ctr[S_DONE] = 1; d.ctr[S_NPOP] = 0;
+		return;
+	}
+	const int32_t size0 = d.ctr[S_SIZE], head = d.ctr[S_HEAD];
+	const int lo = first_refused_pop(d.rank, P, size0, d.ctr[S_BUDGET]);
+	const int cut_b = 12 * lo;
+	const int win = d.ctr[S_WINPOS];
+	const int cut = min(cut_b, win);
+	const int n_new = cut < 12 * P ? d.rank[cut] : d.ctr[S_TOTAL];
+	d.ctr[S_SIZE] = size0 + n_new;
+	d.ctr[S_ITERS] += 1;
+	d.ctr[S_TICKET] = 0;
+	d.ctr[S_EPOCH] += 1;
+	d.ctr[S_WINPOS] = (int32_t)BS_NO_WIN;
+	if (d.ctr[S_ERROR]) {
+		d.ctr[S_STOP] = BS_STOP_ERROR; d.ctr[S_DONE] = 1; d.ctr[S_NPOP] = 0;
+	} else if (win < cut_b) {                                            // the first meeting among the pops that run
+		d.ctr[S_WON] = 1;
+		d.ctr[S_WPARENT] = head + win / 12;
+		d.ctr[S_WACT] = win % 12;
+		d.ctr[S_MEET] = (int32_t)(d.slot[win] & ~TENT);
+		d.ctr[S_HEAD] = head + win / 12 + 1;
+		d.ctr[S_POPPED] += win / 12 + 1;
+		d.ctr[S_STOP] = BS_STOP_WON; d.ctr[S_DONE] = 1; d.ctr[S_NPOP] = 0;
+	} else if (lo < P) {                                                 // the budget refused pop `lo`
+		d.ctr[S_HEAD] = head + lo;
+		d.ctr[S_POPPED] += lo;
+		d.ctr[S_STOP] = BS_STOP_BUDGET; d.ctr[S_DONE] = 1; d.ctr[S_NPOP] = 0;
+	} else {
+		d.ctr[S_HEAD] = head + P;
+		d.ctr[S_POPPED] += P;
+		srch_next(d);
+	}
+}
+
+__global__ __launch_bounds__(256)
+void k_bsearch_rehash(SrchDev d)
+{
+	rehash_pool(d.states, d.table, d.mask, d.ctr[S_SIZE], 1 + blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
+}
+
+// The action queue of a won search: the path from the start to the popped parent and the meeting action (none of either when
+// the ball holds the start itself), then the ball's path from the meeting node.  out[0] = length or -1.
+__global__ void k_bsearch_walk(SrchDev d, BallView b, int32_t *out, int max_len)
+{
+	if (threadIdx.x != 0 || blockIdx.x != 0) return;
+	out[0] = -1;
+	if (!d.ctr[S_WON]) return;
+	const int p = d.ctr[S_WPARENT];
+	int ls = 0;
+	for (int i = p; p != 0 && i != 1; ls++) {
+		if (i < 1 || (uint32_t)i >= d.cap1 || ls > (int)d.cap1) return;
+		i = d.parent[i];
+	}
+	int i = p;
+	for (int k = ls - 1; k >= 0; k--) {
+		if (k < max_len) out[1 + k] = d.pact[i];
+		i = d.parent[i];
+	}
+	int len = ls;
+	if (p != 0) {
+		if (len < max_len) out[1 + len] = d.ctr[S_WACT];
+		len++;
+	}
+	for (uint32_t g = (uint32_t)d.ctr[S_MEET]; g != 1u; len++) {
+		if (g < 1u || g >= b.cap1 || len > ls + 1 + b.radius) return;
+		if (len < max_len) out[1 + len] = b.pact[g] ^ 1;
+		g = (uint32_t)b.parent[g];
+	}
+	out[0] = len;
+}
+
+}  // namespace rk
+
+using namespace rk;
+
+struct rk_ball {
+	BallDev d{};
+	BallView view{};
+	size_t cap = 0;
+	long long size = 0, iterations = 0;
+	int attached = 0;                           // searches that hold this ball's arrays
+	bool built = false;
+	Landing ctr_host;
+	DevPool pool{64};
+};
+
+struct rk_bsearch {
+	SrchDev d{};
+	rk_ball *ball = nullptr;
+	size_t cap = 0;
+	uint32_t *root_dev = nullptr;
+	int32_t *walk = nullptr;
+	Landing ctr_host;
+	bool ready = false;
+	DevPool pool{64};
+};
+
+namespace {
+
+constexpr int BS_WALK_MAX = 1 << 12;
+constexpr size_t BS_MAX_CAPACITY = 0x3FFFFFF0ull;
+
+size_t ball_capacity(int radius)
+{
+	size_t n = 0;
+	for (int l = 0; l <= radius; l++) n += (size_t)BALL_LEVELS[l];
+	return n;
+}
+
+uint32_t ball_table_mask(size_t capacity) { return (uint32_t)(table_slots(capacity, 1024) - 1); }
+
+int bsearch_read_ctr(rk_bsearch *h, int32_t *out, hipStream_t st) { return h->ctr_host.read(h->d.ctr, S_COUNT, out, st); }
+
+// queries: n 20-byte rows on the device, read as dwords
+int check_queries(const char *who, const rk_ball *h, const void *d_states, size_t n, const void *out)
+{
+	if (!h) return fail(RK_EINVAL, "%s: null ball", who);
+	if (!h->built) return fail(RK_ESTATE, "%s: build the ball first", who);
+	if (n > (size_t)INT32_MAX) return fail(RK_EINVAL, "%s: %zu queries in one launch", who, n);
+	if (n != 0 && (!d_states || !out)) return fail(RK_EINVAL, "%s: null pointer", who);
+	if (((uintptr_t)d_states | (uintptr_t)out) & 3u) return fail(RK_EINVAL, "%s: device pointers must be 4-byte aligned", who);
+	return RK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rk_ball_create(rk_ball_t **out, int radius, int pops)
+{
+	if (!out) return fail(RK_EINVAL, "rk_ball_create: null out pointer");
+	if (radius < 0 || radius > BALL_MAX_RADIUS) return fail(RK_EINVAL, "rk_ball_create: radius %d outside 0..%d", radius, BALL_MAX_RADIUS);
+	if (pops < 1 || pops > (1 << 22)) return fail(RK_EINVAL, "rk_ball_create: pops %d outside 1..%d", pops, 1 << 22);
+	rk_ball *h = new rk_ball();
+	h->cap = ball_capacity(radius);
+	BallDev &d = h->d;
+	d.pops = pops;
+	d.radius = radius;
+	d.cap1 = (uint32_t)(h->cap + 1);
+	d.mask = ball_table_mask(h->cap);
+	*out = h;                                   // the arrays are made by rk_ball_build: creating a ball costs nothing
+	return RK_OK;
+}
+
+int rk_ball_destroy(rk_ball_t *h)
+{
+	if (h && h->attached > 0) return fail(RK_ESTATE, "rk_ball_destroy: %d searches still hold this ball", h->attached);
+	delete h;
+	return RK_OK;
+}
+
+int rk_ball_build(rk_ball_t *h, int poll, void *stream)
+{
+	if (!h) return fail(RK_EINVAL, "rk_ball_build: null ball");
+	if (poll < 1) return fail(RK_EINVAL, "rk_ball_build: poll %d < 1", poll);
+	if (h->built) return RK_OK;
+	hipStream_t st = (hipStream_t)stream;
+	BallDev &d = h->d;
+	const size_t C1 = h->cap + 1, K = (size_t)12 * d.pops;
+	h->pool.clear();                            // (what a failed build left)
+	int e = RK_OK;
+	#define A(ptr, cnt) if (!e) e = h->pool.alloc(&d.ptr, (cnt))
+	A(states, C1 * 5); A(parent, C1); A(pact, C1); A(table, (size_t)d.mask + 1); A(ctr, G_COUNT);
+	A(slot, K); A(rank, K); A(first, K); A(chain, frontier_scan_blocks(d.pops));
+	#undef A
+	if (e) { (void)hipGetLastError(); h->pool.clear(); return fail(RK_ECAPACITY, "rk_ball_build: no device memory for a ball of %zu states", h->cap); }
+	h->ctr_host.reserve(G_COUNT);
+	RK_HIP(hipMemsetAsync(d.table, 0, ((size_t)d.mask + 1) * sizeof(uint32_t), st));
+	RK_HIP(hipMemsetAsync(d.chain, 0, frontier_scan_blocks(d.pops) * sizeof(unsigned long long), st));
+	hipLaunchKernelGGL(k_ball_root, dim3(1), dim3(64), 0, st, d);
+	RK_HIP(hipGetLastError());
+	const unsigned grid = blocks(K);
+	int32_t c[G_COUNT];
+	for (;;) {
+		if (int r = h->ctr_host.read(d.ctr, G_COUNT, c, st)) return r;
+		if (c[G_DONE]) break;
+		for (int it = 0; it < poll; it++) {
+			hipLaunchKernelGGL(k_ball_expand, dim3(grid), dim3(256), 0, st, d);
+			hipLaunchKernelGGL(k_ball_scan, dim3(blocks(K, ASCAN)), dim3(ASCAN), 0, st, d);
+			hipLaunchKernelGGL(k_ball_append, dim3(grid), dim3(256), 0, st, d);
+			hipLaunchKernelGGL(k_ball_end, dim3(1), dim3(64), 0, st, d);
+		}
+		RK_HIP(hipGetLastError());
+	}
+	if (c[G_ERROR] || c[G_STOP] != BALL_STOP_BUILT || (size_t)c[G_SIZE] != h->cap)
+		return fail(RK_ESTATE, "rk_ball_build: engine error %d: %d states after level %d, %zu expected in all", c[G_ERROR], c[G_SIZE], c[G_LEVEL], h->cap);
+	h->pool.release(d.slot); h->pool.release(d.rank); h->pool.release(d.first); h->pool.release(d.chain);
+	d.slot = nullptr; d.rank = nullptr; d.first = nullptr; d.chain = nullptr;
+	BallView &v = h->view;
+	v.mask = d.mask; v.cap1 = d.cap1; v.radius = d.radius;
+	for (int l = 0; l < BALL_MAX_RADIUS + 2; l++) v.lstart[l] = l <= d.radius + 1 ? c[G_LSTART + l] : INT32_MAX;
+	v.states = d.states; v.parent = d.parent; v.pact = d.pact; v.table = d.table;
+	h->size = c[G_SIZE];
+	h->iterations = c[G_ITERS];
+	h->built = true;
+	return RK_OK;
+}
+
+int rk_ball_status(rk_ball_t *h, long long *h_status)
+{
+	if (!h || !h_status) return fail(RK_EINVAL, "rk_ball_status: null argument");
+	h_status[0] = h->built ? 1 : 0; h_status[1] = h->size; h_status[2] = h->iterations; h_status[3] = h->d.radius;
+	h_status[4] = (long long)h->cap; h_status[5] = h->attached;
+	for (int l = 0; l < BALL_MAX_RADIUS + 2; l++) h_status[6 + l] = h->built && l <= h->d.radius + 1 ? h->view.lstart[l] : 0;
+	return RK_OK;
+}
+
+int rk_ball_export(rk_ball_t *h, size_t first, size_t count, int8_t *h_states, long long *h_parents, long long *h_actions, void *stream)
+{
+	if (!h) return fail(RK_EINVAL, "rk_ball_export: null ball");
+	if (!h->built) return fail(RK_ESTATE, "rk_ball_export: build the ball first");
+	if (first + count > h->cap + 1) return fail(RK_EINVAL, "rk_ball_export: rows %zu..%zu outside the pool", first, first + count);
+	if (count == 0) return RK_OK;
+	hipStream_t st = (hipStream_t)stream;
+	const BallDev &d = h->d;
+	Widened<int32_t, long long> p;
+	Widened<uint8_t, long long> a;
+	if (h_states) RK_HIP(hipMemcpyAsync(h_states, d.states + first * 5, count * STATE_BYTES, hipMemcpyDeviceToHost, st));
+	if (int e = p.start(d.parent + first, count, h_parents, st)) return e;
+	if (int e = a.start(d.pact + first, count, h_actions, st)) return e;
+	RK_HIP(hipStreamSynchronize(st));
+	p.finish(); a.finish();
+	return RK_OK;
+}
+
+int rk_ball_depth(rk_ball_t *h, const int8_t *d_states, size_t n, int32_t *d_depth, void *stream)
+{
+	if (int e = check_queries("rk_ball_depth", h, d_states, n, d_depth)) return e;
+	if (n == 0) return RK_OK;
+	hipLaunchKernelGGL(k_ball_depth, dim3(blocks(n)), dim3(256), 0, (hipStream_t)stream, h->view,
+	                   reinterpret_cast<const uint32_t *>(d_states), n, d_depth);
+	RK_HIP(hipGetLastError());
+	return RK_OK;
+}
+
+int rk_ball_solve(rk_ball_t *h, const int8_t *d_states, size_t n, int32_t *d_lengths, int8_t *d_actions, void *stream)
+{
+	if (int e = check_queries("rk_ball_solve", h, d_states, n, d_lengths)) return e;
+	if (n == 0) return RK_OK;
+	if (!d_actions && h->d.radius > 0) return fail(RK_EINVAL, "rk_ball_solve: null pointer");
+	hipLaunchKernelGGL(k_ball_solve, dim3(blocks(n)), dim3(256), 0, (hipStream_t)stream, h->view,
+	                   reinterpret_cast<const uint32_t *>(d_states), n, d_lengths, d_actions);
+	RK_HIP(hipGetLastError());
+	return RK_OK;
+}
+
+int rk_bsearch_create(rk_bsearch_t **out, rk_ball_t *ball, size_t capacity, int pops)
+{
+	if (!out || !ball) return fail(RK_EINVAL, "rk_bsearch_create: null argument");
+	if (capacity < 2 || capacity > BS_MAX_CAPACITY) return fail(RK_EINVAL, "rk_bsearch_create: capacity %zu out of range", capacity);
+	if (pops < 1 || pops > (1 << 22)) return fail(RK_EINVAL, "rk_bsearch_create: pops %d outside 1..%d", pops, 1 << 22);
+	rk_bsearch *h = new rk_bsearch();
+	h->cap = capacity;
+	SrchDev &d = h->d;
+	d.pops = pops;
+	d.cap1 = (uint32_t)(capacity + 1);
+	d.mask = ball_table_mask(capacity);
+	const size_t C1 = capacity + 1, K = (size_t)12 * pops;
+	int e = RK_OK;
+	#define A(ptr, cnt) if (!e) e = h->pool.alloc(&d.ptr, (cnt))
+	A(states, C1 * 5); A(parent, C1); A(pact, C1); A(table, (size_t)d.mask + 1); A(ctr, S_COUNT);
+	A(slot, K); A(rank, K); A(first, K); A(chain, frontier_scan_blocks(pops));
+	#undef A
+	if (!e) e = h->pool.alloc(&h->root_dev, 8);
+	if (!e) e = h->pool.alloc(&h->walk, BS_WALK_MAX + 8);
+	if (!e) h->ctr_host.reserve(S_COUNT);
+	if (e) { delete h; return e; }
+	h->ball = ball;
+	ball->attached += 1;
+	*out = h;
+	return RK_OK;
+}
+
+int rk_bsearch_destroy(rk_bsearch_t *h)
+{
+	if (h && h->ball) h->ball->attached -= 1;
+	delete h;
+	return RK_OK;
+}
+
+int rk_bsearch_reset(rk_bsearch_t *h, const int8_t *h_start_state, long long max_states, void *stream)
+{
+	if (!h || !h_start_state) return fail(RK_EINVAL, "rk_bsearch_reset: null argument");
+	if (!h->ball->built) return fail(RK_ESTATE, "rk_bsearch_reset: build the ball first");
+	hipStream_t st = (hipStream_t)stream;
+	SrchDev &d = h->d;
+	RK_HIP(hipMemsetAsync(d.table, 0, ((size_t)d.mask + 1) * sizeof(uint32_t), st));                        // the own table only
+	RK_HIP(hipMemsetAsync(d.chain, 0, frontier_scan_blocks(d.pops) * sizeof(unsigned long long), st));
+	RK_HIP(hipMemcpyAsync(h->root_dev, h_start_state, STATE_BYTES, hipMemcpyHostToDevice, st));
+	hipLaunchKernelGGL(k_bsearch_root, dim3(1), dim3(64), 0, st, d, h->ball->view, h->root_dev, budget_of(max_states));
+	RK_HIP(hipGetLastError());
+	RK_HIP(hipStreamSynchronize(st));       // the host buffer may go away after return
+	h->ready = true;
+	return RK_OK;
+}
+
+int rk_bsearch_run(rk_bsearch_t *h, int iterations, void *stream)
+{
+	if (!h || !h->ready) return fail(RK_ESTATE, "rk_bsearch_run: reset the engine first");
+	if (iterations < 0) return fail(RK_EINVAL, "rk_bsearch_run: iterations %d < 0", iterations);
+	hipStream_t st = (hipStream_t)stream;
+	const SrchDev &d = h->d;
+	const BallView &b = h->ball->view;
+	const unsigned grid = blocks((size_t)12 * d.pops);
+	for (int it = 0; it < iterations; it++) {
+		hipLaunchKernelGGL(k_bsearch_expand, dim3(grid), dim3(256), 0, st, d, b);
+		hipLaunchKernelGGL(k_bsearch_scan, dim3(blocks((size_t)12 * d.pops, ASCAN)), dim3(ASCAN), 0, st, d);
+		hipLaunchKernelGGL(k_bsearch_append, dim3(grid), dim3(256), 0, st, d);
+		hipLaunchKernelGGL(k_bsearch_end, dim3(1), dim3(64), 0, st, d);
+	}
+	RK_HIP(hipGetLastError());
+	return RK_OK;
+}
+
+int rk_bsearch_status(rk_bsearch_t *h, long long *h_status, void *stream)
+{
+	if (!h || !h->ready || !h_status) return fail(RK_EINVAL, "rk_bsearch_status: bad argument");
+	int32_t c[S_COUNT];
+	if (int e = bsearch_read_ctr(h, c, (hipStream_t)stream)) return e;
+	h_status[0] = c[S_DONE]; h_status[1] = c[S_WON]; h_status[2] = c[S_SIZE]; h_status[3] = c[S_ITERS];
+	h_status[4] = c[S_POPPED]; h_status[5] = c[S_STOP]; h_status[6] = c[S_ERROR]; h_status[7] = c[S_NPOP];
+	h_status[8] = c[S_DEPTH]; h_status[9] = c[S_MEET];
+	return RK_OK;
+}
+
+int rk_bsearch_grow(rk_bsearch_t *h, size_t new_capacity, void *stream)
+{
+	if (!h || !h->ready) return fail(RK_ESTATE, "rk_bsearch_grow: reset the engine first");
+	if (new_capacity <= h->cap) return new_capacity == h->cap ? RK_OK : fail(RK_EINVAL, "rk_bsearch_grow: %zu is below the current capacity %zu", new_capacity, h->cap);
+	if (new_capacity > BS_MAX_CAPACITY) return fail(RK_EINVAL, "rk_bsearch_grow: capacity %zu out of range", new_capacity);
+	hipStream_t st = (hipStream_t)stream;
+	const SrchDev old = h->d;
+	SrchDev d = old;
+	const size_t C1 = new_capacity + 1, C1_old = h->cap + 1;
+	d.cap1 = (uint32_t)C1;
+	d.mask = ball_table_mask(new_capacity);
+	Growth g(h->pool, "rk_bsearch_grow");
+	g.request(&d.states, C1 * 5); g.request(&d.parent, C1); g.request(&d.pact, C1); g.request(&d.table, (size_t)d.mask + 1);
+	if (!g.granted()) return fail(RK_ECAPACITY, "rk_bsearch_grow: no device memory for a pool of %zu states", new_capacity);
+	const int e = g.fill(st, [&]() -> hipError_t {
+		RK_FILL(hipMemcpyAsync(d.states, old.states, C1_old * STATE_BYTES, hipMemcpyDeviceToDevice, st));
+		RK_FILL(hipMemcpyAsync(d.parent, old.parent, C1_old * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+		RK_FILL(hipMemcpyAsync(d.pact, old.pact, C1_old, hipMemcpyDeviceToDevice, st));
+		RK_FILL(hipMemsetAsync(d.table, 0, ((size_t)d.mask + 1) * sizeof(uint32_t), st));
+		hipLaunchKernelGGL(k_bsearch_rehash, dim3(std::min<unsigned>(blocks(C1_old), 4096u)), dim3(256), 0, st, d);
+		return hipGetLastError();
+	});
+	if (e) return e;
+	g.commit();
+	h->d = d;
+	h->cap = new_capacity;
+	return RK_OK;
+}
+
+long long rk_bsearch_size(const rk_bsearch_t *hc)
+{
+	rk_bsearch_t *h = const_cast<rk_bsearch_t *>(hc);
+	if (!h || !h->ready) return 0;
+	int32_t c[S_COUNT];
+	if (bsearch_read_ctr(h, c, nullptr)) return RK_EHIP;
+	return c[S_SIZE];
+}
+
+int rk_bsearch_export(rk_bsearch_t *h, size_t first, size_t count, int8_t *h_states, long long *h_parents, long long *h_actions, void *stream)
+{
+	if (!h || !h->ready) return fail(RK_ESTATE, "rk_bsearch_export: reset the engine first");
+	if (first + count > h->cap + 1) return fail(RK_EINVAL, "rk_bsearch_export: rows %zu..%zu outside the pool", first, first + count);
+	if (count == 0) return RK_OK;
+	hipStream_t st = (hipStream_t)stream;
+	const SrchDev &d = h->d;
+	Widened<int32_t, long long> p;
+	Widened<uint8_t, long long> a;
+	if (h_states) RK_HIP(hipMemcpyAsync(h_states, d.states + first * 5, count * STATE_BYTES, hipMemcpyDeviceToHost, st));
+	if (int e = p.start(d.parent + first, count, h_parents, st)) return e;
+	if (int e = a.start(d.pact + first, count, h_actions, st)) return e;
+	RK_HIP(hipStreamSynchronize(st));
+	p.finish(); a.finish();
+	return RK_OK;
+}
+
+long long rk_bsearch_path(rk_bsearch_t *h, long long *h_actions, size_t max_len, void *stream)
+{
+	if (!h || !h->ready) return fail(RK_ESTATE, "rk_bsearch_path: reset the engine first");
+	if (!h_actions && max_len > 0) return fail(RK_EINVAL, "rk_bsearch_path: null h_actions with max_len %zu", max_len);
+	hipStream_t st = (hipStream_t)stream;
+	hipLaunchKernelGGL(k_bsearch_walk, dim3(1), dim3(64), 0, st, h->d, h->ball->view, h->walk, BS_WALK_MAX);
+	RK_HIP(hipGetLastError());
+	int32_t len = 0;
+	if (int e = read_walk(h->walk, BS_WALK_MAX, h_actions, max_len, st, &len)) return e;
+	if (len < 0) return fail(RK_ESTATE, "rk_bsearch_path: the search has not met the ball (or a parent chain is broken)");
+	return (long long)len;
+}
+
+}  // extern "C"

@@ -106,6 +106,20 @@ __device__ __forceinline__ uint32_t probe_elect(uint32_t *table, uint32_t mask, 
 	}
 }
 
+// Membership test that writes nothing: the stored index (> 0) of state s in a table that other kernels may read at the same
+// time, or 0.  For a table that is final (rk_ball.hip: a built ball holds no tentative slot); a tentative slot, should one be
+// met, is passed over without being followed.  The table is at most half full, so an empty slot ends every probe.
+__device__ __forceinline__ uint32_t probe_find(const uint32_t *table, uint32_t mask, const uint32_t *states, const uint32_t s[5])
+{
+	uint32_t slot = hash_state(s) & mask;
+	for (;;) {
+		const uint32_t e = table[slot];
+		if (e == 0u) return 0u;
+		if ((e & TENT) == 0u && equal5(s, states + (size_t)e * 5)) return e;
+		slot = (slot + 1) & mask;
+	}
+}
+
 // After a growth (or to drop stale claims): the stored states 1..n of one pool back into its cleared table.  No slot is tentative
 // then, so this is a plain insert; the slot a state lands in may differ from the one it had, which no result depends on (look-ups
 // compare states).  This thread takes the indices first, first + stride, ... (the kernel passes its own 1 + x position and the

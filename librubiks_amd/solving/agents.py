@@ -540,6 +540,256 @@ class DeviceBiBFS(Agent, _ffi.Owner):
 		return f"Two-sided breadth-first search (device, pops={self.pops})"
 
 
+class DeviceGoalBall(_ffi.Owner):
+	"""
+	The ball around the solved state, built once and kept in HBM (engine rk_ball_*, csrc/rk_ball.hip): every state within `radius`
+	quarter turns, in `DeviceBFS`'s order without goal test or budget.  Node 1 is the solved state; a level's parents are popped in
+	index order, their children taken in action order, a child the pool holds is skipped, any other appended with its parent and
+	its action (the move away from solved).  Level `radius` is stored and never expanded.  Level l is the index range
+	`level_start[l] .. level_start[l + 1] - 1`, so depths come from indices.  The pool does not depend on `pops`.
+
+	The ball is built at first use (or by `build()`) and read-only from then on: `depth` and `solve` answer a batch of states in
+	one launch each, and any number of `DeviceBallSearch` agents may share it.  States are in the representation cube.get_is2024()
+	names when a method is called.  Radius 8 holds 86.0 M states in about 3.2 GB.
+	"""
+	LEVELS = (1, 12, 114, 1_068, 10_011, 93_840, 878_880, 8_221_632, 76_843_595)    # states at distance 0 .. 8, quarter turns
+	MAX_RADIUS = len(LEVELS) - 1
+	MAX_POPS = 1 << 22                      # rk_ball_create's limit
+	poll = 8                                # iterations of the build between two looks of the host
+
+	def __init__(self, radius: int, pops: int = 16_384):
+		if isinstance(radius, bool) or int(radius) != radius or not 0 <= int(radius) <= self.MAX_RADIUS:
+			raise ValueError(f"radius must be an integer in 0..{self.MAX_RADIUS}, got {radius!r}")
+		if isinstance(pops, bool) or int(pops) != pops or not 1 <= int(pops) <= self.MAX_POPS:
+			raise ValueError(f"pops must be an integer in 1..{self.MAX_POPS}, got {pops!r}")
+		self.radius, self.pops = int(radius), int(pops)
+		self._h = None
+		self._n = 0
+		self._level_start = None
+		self._cache = {}
+		self.iterations = 0                 # of the build
+
+	@property
+	def built(self) -> bool:
+		return self._level_start is not None
+
+	def build(self):
+		"""Builds the ball on the device (nothing if it is built)."""
+		if self.built:
+			return self
+		_ffi.require_gpu()
+		lib = _ffi.lib()
+		if self._h is None:
+			self._create("rk_ball_create", "rk_ball_destroy", self.radius, self.pops)
+		_ffi.check(lib.rk_ball_build(self._h, self.poll, _ffi.stream_ptr()))
+		status = (C.c_longlong * 16)()
+		_ffi.check(lib.rk_ball_status(self._h, status))
+		self._n, self.iterations = int(status[1]), int(status[2])
+		self._level_start = np.array(status[6:6 + self.radius + 2], np.int64)
+		return self
+
+	@property
+	def level_start(self) -> np.ndarray:
+		"""int64 (radius + 2,): level l holds the nodes level_start[l] .. level_start[l + 1] - 1."""
+		return self.build()._level_start
+
+	def __len__(self):
+		return self.build()._n
+
+	def _rows(self, states) -> np.ndarray:
+		"""Query states in the current representation as (n, 20) int8 rows."""
+		is2024 = cube.get_is2024()
+		arr = np.asarray(states, dtype=np.int8)
+		width = 20 if is2024 else 288
+		if arr.size % width or (arr.ndim and arr.shape[-1] != (20 if is2024 else 6)):
+			raise ValueError(f"states must be (n, 20), or (n, 6, 8, 6) in 6x8x6 mode, got shape {arr.shape}")
+		return _roots20(is2024, arr, arr.size // width)
+
+	def depth(self, states) -> np.ndarray:
+		"""int64 (n,): the exact distance to solved of every state the ball holds, -1 for the others.  One launch."""
+		self.build()
+		rows = self._rows(states)                            # ValueError for an illegal 6x8x6 state
+		n = len(rows)
+		if n == 0:
+			return np.zeros(0, np.int64)
+		q = torch.from_numpy(rows).to(gpu)
+		out = torch.empty(n, dtype=torch.int32, device=gpu)
+		_ffi.check(_ffi.lib().rk_ball_depth(self._h, q.data_ptr(), n, out.data_ptr(), _ffi.stream_ptr()))
+		return out.cpu().numpy().astype(np.int64)
+
+	def solve(self, states):
+		"""(lengths int64 (n,), actions int64 (n, radius)): the shortest solution of every state the ball holds, rows padded with
+		-1; length -1 for a state outside the ball.  One launch."""
+		self.build()
+		rows = self._rows(states)
+		n = len(rows)
+		if n == 0:
+			return np.zeros(0, np.int64), np.zeros((0, self.radius), np.int64)
+		q = torch.from_numpy(rows).to(gpu)
+		lengths = torch.empty(n, dtype=torch.int32, device=gpu)
+		actions = torch.empty((n, max(self.radius, 1)), dtype=torch.int8, device=gpu)
+		_ffi.check(_ffi.lib().rk_ball_solve(self._h, q.data_ptr(), n, lengths.data_ptr(), actions.data_ptr(), _ffi.stream_ptr()))
+		return lengths.cpu().numpy().astype(np.int64), actions.cpu().numpy().astype(np.int64)[:, :self.radius]
+
+	def arrays(self):
+		"""(states, parents, actions) of nodes 1 .. len(ball) in index order, like `DeviceBFS.arrays()`: parent 0 and action -1 for
+		the solved state; an action is the move from the parent, away from solved."""
+		is2024 = cube.get_is2024()
+		if is2024 not in self._cache:
+			n = len(self)
+			states = np.zeros((n + 1, 20), np.int8)
+			parents, actions = np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int64)
+			_ffi.check(_ffi.lib().rk_ball_export(self._h, 1, n, states[1:].ctypes.data, parents[1:].ctypes.data,
+			                                      actions[1:].ctypes.data, _ffi.stream_ptr()))
+			actions[1] = -1
+			self._cache = {is2024: (_states_out(is2024, states, n)[1:], parents[1:], actions[1:])}
+		return self._cache[is2024]
+
+	def depth_of_node(self, node: int) -> int:
+		"""The depth of node `node` (1 .. len(ball)), from the level boundaries."""
+		return int(np.searchsorted(self.level_start, node, side="right")) - 1
+
+	def __str__(self):
+		return f"Goal ball (device, radius={self.radius})"
+
+
+class DeviceBallSearch(Agent, _ffi.Owner):
+	"""
+	A SHORTEST solution (quarter-turn metric) by a one-sided breadth-first search from the start that ends at the first child a
+	kept `DeviceGoalBall` holds (engine rk_bsearch_*, csrc/rk_ball.hip).  Node 1 of the own pool is the start; levels grow as in
+	`DeviceBiBFS`: a child the own pool holds is skipped, a child the ball holds is the meeting (the search ends, the child is
+	not stored, the lowest batch position wins), any other is appended.  A start at distance D > radius meets while level
+	D - radius grows, in a node of ball depth `radius`, so the first meeting is optimal.  A start the ball holds is answered by
+	the ball's path: then len(agent) == 1 and nothing is popped.  The state budget is checked before every pop, the time limit
+	when the host polls.  `action_queue`, len(agent), the pool, `depth` and the meeting do not depend on `pops`.
+
+	`capacity`, `max_capacity`, `grown` and `capacity_exhausted` are `DeviceBFS`'s, for the own pool; its table is sized to it and
+	a new search clears that table, never the ball's.  Several agents may share one ball; each holds a reference to it.
+	"""
+	default_capacity = 8_000_000
+	max_capacity = 400_000_000
+	MAX_POPS = 1 << 22                      # rk_bsearch_create's limit
+	MAX_CAPACITY = 0x3FFFFFF0
+
+	def __init__(self, ball: DeviceGoalBall, pops: int = 16_384, capacity: int = None, max_capacity: int = None, poll: int = 8):
+		super().__init__()
+		if not isinstance(ball, DeviceGoalBall):
+			raise TypeError(f"ball must be a DeviceGoalBall, got {type(ball).__name__}")
+		if isinstance(pops, bool) or int(pops) != pops or not 1 <= int(pops) <= self.MAX_POPS:
+			raise ValueError(f"pops must be an integer in 1..{self.MAX_POPS}, got {pops!r}")
+		for name, v in (("capacity", capacity), ("max_capacity", max_capacity)):
+			if v is not None and (isinstance(v, bool) or int(v) != v or not 2 <= int(v) <= self.MAX_CAPACITY):
+				raise ValueError(f"{name} must be an integer in 2..{self.MAX_CAPACITY}, got {v!r}")
+		if isinstance(poll, bool) or int(poll) != poll or int(poll) < 1:
+			raise ValueError(f"poll must be a positive integer, got {poll!r}")
+		self.ball = ball
+		self.pops, self.poll = int(pops), int(poll)
+		self.capacity = int(capacity) if capacity is not None else None
+		if max_capacity is not None:
+			self.max_capacity = int(max_capacity)
+		self._h, self._h_cap = None, 0
+		self._n = 0
+		self._is2024 = True
+		self._cache = None
+		self._meet = 0                      # the ball's node that the meeting child (or the start itself) equals
+		self.depth = 0                      # complete levels around the start after the last search
+		self.iterations = 0
+		self.popped = 0                     # nodes the last search popped (each has 12 children)
+		self.grown = 0
+		self.capacity_exhausted = False
+
+	def _engine(self, capacity: int):
+		if self._h is not None and self._h_cap >= capacity:
+			return self._h                  # (a pool that grew in an earlier search is kept: rk_bsearch_reset clears its table)
+		self._h_cap = capacity
+		return self._create("rk_bsearch_create", "rk_bsearch_destroy", self.ball._h, capacity, self.pops)
+
+	def _grow(self, h) -> bool:
+		if self._h_cap >= self.max_capacity:
+			eng.pool_exhausted(self, self._h_cap, "cannot take the next iteration")
+			return False
+		cap = min(2 * self._h_cap, self.max_capacity)
+		_ffi.check(_ffi.lib().rk_bsearch_grow(h, cap, _ffi.stream_ptr()))
+		self._h_cap = cap
+		self.grown += 1
+		return True
+
+	@no_grad
+	def search(self, state: np.ndarray, time_limit: float = None, max_states: int = None) -> bool:
+		_ffi.require_gpu()
+		t0 = time.perf_counter()
+		time_limit, max_states = self.reset(time_limit or 1e10, max_states)        # (an exact search may run without either limit)
+		self._n, self._cache, self.iterations, self.grown, self.capacity_exhausted = 0, None, 0, 0, False
+		self.popped, self._meet, self.depth = 0, 0, 0
+		self._is2024 = cube.get_is2024()
+		root = _roots20(self._is2024, state, 1)[0]          # ValueError for an illegal 6x8x6 state
+		self.ball.build()
+		lib, stream = _ffi.lib(), _ffi.stream_ptr()
+		K = 12 * self.pops
+		budget = int(min(max_states, 2 ** 31 - 1))
+		cap = self.capacity or min(budget + K, self.default_capacity)
+		cap = max(2, min(cap, self.max_capacity, self.MAX_CAPACITY))
+		h = self._engine(cap)
+		_ffi.check(lib.rk_bsearch_reset(h, root.ctypes.data, budget, stream))
+		self._n = 1
+		status = (C.c_longlong * 10)()
+		_ffi.check(lib.rk_bsearch_status(h, status, stream))
+		self._meet = int(status[9])
+		while not status[0]:
+			room = (self._h_cap - self._n) // K              # iterations the pool takes whatever they find
+			if room == 0:
+				if not self._grow(h):
+					return False
+				continue
+			_ffi.check(lib.rk_bsearch_run(h, eng.burst(min(self.poll, room), budget - self._n, K), stream))
+			_ffi.check(lib.rk_bsearch_status(h, status, stream))
+			self._n, self.iterations, self.popped = int(status[2]), int(status[3]), int(status[4])
+			self.depth, self._meet = int(status[8]), int(status[9])
+			if status[6]:
+				raise _ffi.RubiksHipError(f"ball search engine error code {int(status[6])}")
+			if not status[0] and time.perf_counter() - t0 >= time_limit:
+				return False
+		if status[1]:
+			self.action_queue = eng.read_path(lib.rk_bsearch_path, h)
+			return True
+		return False
+
+	def arrays(self):
+		"""(states, parents, actions) of the own pool's nodes 1 .. len(agent) in index order, as `DeviceBFS.arrays()`."""
+		if self._cache is None:
+			n = self._n
+			states = np.zeros((n + 1, 20), np.int8)
+			parents, actions = np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int64)
+			if n and self._h is not None:
+				_ffi.check(_ffi.lib().rk_bsearch_export(self._h, 1, n, states[1:].ctypes.data, parents[1:].ctypes.data,
+				                                         actions[1:].ctypes.data, _ffi.stream_ptr()))
+			if n:
+				actions[1] = -1
+			self._cache = (_states_out(self._is2024, states, n)[1:], parents[1:], actions[1:])
+		return self._cache
+
+	@property
+	def meeting(self):
+		"""The state where the search met the ball -- the child that was not stored, or the start itself when the ball holds it --
+		in the representation of the search; None when the last search did not meet."""
+		if not self._meet:
+			return None
+		state = np.zeros((2, 20), np.int8)
+		_ffi.check(_ffi.lib().rk_ball_export(self.ball._h, self._meet, 1, state[1:].ctypes.data, None, None, _ffi.stream_ptr()))
+		return _states_out(self._is2024, state, 1)[1]
+
+	@property
+	def meeting_depth(self):
+		"""The depth in the ball of the node the search met; None when the last search did not meet."""
+		return self.ball.depth_of_node(self._meet) if self._meet else None
+
+	def __len__(self):
+		return self._n
+
+	def __str__(self):
+		return f"Breadth-first search to a goal ball (device, radius={self.ball.radius}, pops={self.pops})"
+
+
 class PolicySearch(DeepAgent):
 	"""Follow (or sample from) the policy head (agents.py:132-151)."""
 	def __init__(self, net, sample_policy=False):
