@@ -96,16 +96,22 @@ __device__ __forceinline__ uint32_t code_of(const uint32_t s5[5], int cubie)
 // Optional epilogue  y = scale * act(x W^T + b) + shift  per output column: the activation that follows the layer
 // (model.py:157: ELU by default) and the eval-mode BatchNorm1d behind it (model.py:158-159) as its affine map
 // scale = gamma / sqrt(var + eps), shift = beta - mean * scale -- two more passes over the (n, H) activations that never
-// happen.  ACT: 0 none, 1 ELU(alpha) = x > 0 ? x : alpha (exp(x) - 1), 2 ReLU.  FAST: v_exp_f32 (bf16 outputs keep 8 bits).
+// happen.  ACT: 0 none, 1 ELU(alpha) = x > 0 ? x : alpha expm1(x), 2 ReLU.
+// A NaN stays a NaN, as in torch.nn.ELU / ReLU: both selects are written so that an unordered compare keeps v (`!(v <= 0)`, `v < 0 ? 0 : v`).
+// Written as `v > 0 ? v : ...` a NaN took the other arm and came out as alpha * 0 = 0 (ReLU: 0), behind the affine map a healthy-looking
+// `shift` -- a diverged net hidden from whoever reads the layer's output.
+// The exact float32 route (FAST = false) takes expm1f: expf(v) - 1 carries the absolute error of a value near 1 (2^-24) whatever the size
+// of the result, 1e-4 relative at v = -1e-3 where torch's ELU (expm1) is good to an ulp.  FAST: v_exp_f32 and the subtraction; its
+// absolute error (below 2^-21) is inside the half ulp of every bf16 result it feeds, which keeps 8 bits.
 template <int ACT, bool FAST>
 __device__ __forceinline__ float ohl_act(float v, float alpha)
 {
 	if (ACT == 1) {
 		const float neg = v < 0.0f ? v : 0.0f;
-		const float e = (FAST ? __expf(neg) : expf(neg)) - 1.0f;
-		return v > 0.0f ? v : alpha * e;
+		const float e = FAST ? __expf(neg) - 1.0f : expm1f(neg);
+		return !(v <= 0.0f) ? v : alpha * e;
 	}
-	if (ACT == 2) return v > 0.0f ? v : 0.0f;
+	if (ACT == 2) return v < 0.0f ? 0.0f : v;
 	return v;
 }
 
@@ -591,6 +597,9 @@ int rk_ohl_forward(rk_ohl_t *h, const int8_t *d_states, void *d_out, int out_dty
 	// Three tiles per wave and pass instead of two where that balances the chip: 3 072 rows (an MCTS step of 256 trees) are 6 row groups of
 	// 512 rows with two tiles -- 384 workgroups, half of the CUs with two of them and half with one, 18.3 us -- and 8 groups of 384 rows with
 	// three: one workgroup per slot, one pass each (profiles/r05_oh_linear_small.json).  Same accumulation order per output: same bits.
+	// tests/test_oh_linear_exact_gpu.py (test_mfma_tiled_three_tiles_per_wave_against_float64) relies on 3 072 x 4 096 and 66 000 x 64 taking
+	// this form and works the costs out in its docstring: after a change to plan() or to this condition, recompute them there, or the test
+	// goes on passing on the two-tile kernel alone.
 	bool three = false;
 	if (route == RK_OHL_MFMA && !wide) {
 		size_t g3, r3;

@@ -8,6 +8,12 @@ Tolerances (floating point, stated here as the scope contract asks):
     terms in another order) the difference is rounding of a 21-term float32 sum: |diff| <= 2e-6 * (|b| + sum |w_i|).
   * MFMA route, bf16: weights rounded to bf16, float32 accumulation, result rounded to bf16 (nearest even): within one
     bf16 unit in the last place of the float32 reference computed from the SAME bf16 weights: rtol 2^-7, atol 1e-6.
+These compare with torch on the same device and are deliberately loose: a whole bf16 ulp admits a truncating kernel, and the
+epilogue test's atol of 2e-6 swallows the float32 ELU's last digits.  The tight statements live in tests/test_oh_linear_exact_gpu.py:
+every route against a float64 reference built by indexing, at HALF a bf16 ulp (2^-8) plus the float32 sum's error, the float32
+epilogue on its own at 16 u of its product (expm1, not exp - 1), NaN in = NaN out behind every activation, bias=None and the
+activations' boundary inputs; tests/oh_linear_ref.py derives the bounds and tests/test_oh_linear_ref_cpu.py proves on the CPU
+that they reject the kernels' plausible defects.
 """
 import numpy as np
 import pytest
