@@ -395,7 +395,7 @@ long long rk_bibfs_path(rk_bibfs_t *h, long long *h_actions, size_t max_len, voi
 typedef struct rk_ball rk_ball_t;
 /* radius 0..8; pops: the most parents one iteration of the build pops.  Allocates nothing. */
 int rk_ball_create(rk_ball_t **out, int radius, int pops);
-/* RK_ESTATE while a search (rk_bsearch_*) is attached to the ball. */
+/* RK_ESTATE while a search (rk_bsearch_*, rk_bsearchb_*) is attached to the ball. */
 int rk_ball_destroy(rk_ball_t *h);
 /* Builds the ball (nothing if it is built): iterations of four launches, the host looks every `poll` of them.  A level of
  * the wrong size or a state too many is an engine error (RK_ESTATE); RK_ECAPACITY when the device has no room.  Afterwards
@@ -446,6 +446,33 @@ int rk_bsearch_export(rk_bsearch_t *h, size_t first, size_t count, int8_t *h_sta
  * ball's path from the meeting node; walked on the device.  Returns its length or a negative error (RK_ESTATE: not met);
  * writes at most max_len actions. */
 long long rk_bsearch_path(rk_bsearch_t *h, long long *h_actions, size_t max_len, void *stream);
+
+/* ---- many such searches in lock-step (rk_bsearchb_*) --------------------------------------------------------------------
+ * n_slots slots, each a whole rk_bsearch of its own -- pool, table sized to it, counters, batch scratch --, advanced by the
+ * same four launches with the slot in the grid's second dimension; all read one ball.  Every slot computes exactly what
+ * rk_bsearch computes for its start.  A slot that is done or was never started costs one counter read per launch.  The
+ * capacity is fixed per slot: a slot whose next iteration might not fit (n_states + 12 * pops of it > capacity) stops before
+ * that iteration with stop reason 5 = pool full: done, not won, no error, the other slots undisturbed. */
+typedef struct rk_bsearchb rk_bsearchb_t;
+/* n_slots 1..1024, capacity_per_slot >= 2, pops 1..2^22; attaches to `ball` (built or not): rk_ball_destroy refuses meanwhile. */
+int rk_bsearchb_create(rk_bsearchb_t **out, rk_ball_t *ball, int n_slots, size_t capacity_per_slot, int pops);
+int rk_bsearchb_destroy(rk_bsearchb_t *h);
+/* Between iterations: slot slots[j] (all different, 0 .. n_slots - 1) starts again from HOST state j of h_start_states int8
+ * (n, 20) with the budget max_states[j].  Clears the tables and counters of the named slots only; every other slot stays
+ * exactly where it was.  A start the ball holds is answered here.  RK_ESTATE if the ball is not built.  Synchronises. */
+int rk_bsearchb_reset(rk_bsearchb_t *h, int n, const int32_t *slots, const int8_t *h_start_states, const long long *max_states,
+                      void *stream);
+/* `iterations` iterations of all slots, four launches each; stream-ordered, no synchronisation. */
+int rk_bsearchb_run(rk_bsearchb_t *h, int iterations, void *stream);
+/* Synchronises; h_status (n_slots, 10): rk_bsearch_status's ten words of every slot (zeros for a slot never started), read
+ * with one copy.  Stop reason 5 = pool full. */
+int rk_bsearchb_status(rk_bsearchb_t *h, long long *h_status, void *stream);
+/* Row s of HOST h_out int32 (n_slots, 1 + max_len): the length of slot s's action queue, or -1 if it has not met, then its
+ * first max_len actions.  max_len 0..4096.  One launch, one thread per slot, and one copy.  Synchronises. */
+int rk_bsearchb_paths(rk_bsearchb_t *h, int32_t *h_out, int max_len, void *stream);
+/* Rows [first, first+count) of slot `slot`'s pool to HOST buffers (any may be NULL), as rk_bsearch_export. */
+int rk_bsearchb_export(rk_bsearchb_t *h, int slot, size_t first, size_t count, int8_t *h_states, long long *h_parents,
+                       long long *h_actions, void *stream);
 
 /* ---- device-resident epsilon-greedy value maximisation (agents.py:649-726) ---------------------------------------
  * W = workers walkers take D = depth moves from a root (:692-715); the visited state with the best value becomes the next

@@ -117,6 +117,13 @@ SIGNATURES = {
 	"rk_bsearch_size": (C.c_longlong, [_vp]),
 	"rk_bsearch_export": (_i, [_vp, _sz, _sz, _vp, _vp, _vp, _vp]),
 	"rk_bsearch_path": (C.c_longlong, [_vp, _vp, _sz, _vp]),
+	"rk_bsearchb_create": (_i, [C.POINTER(_vp), _vp, _i, _sz, _i]),
+	"rk_bsearchb_destroy": (_i, [_vp]),
+	"rk_bsearchb_reset": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
+	"rk_bsearchb_run": (_i, [_vp, _i, _vp]),
+	"rk_bsearchb_status": (_i, [_vp, _vp, _vp]),
+	"rk_bsearchb_paths": (_i, [_vp, _vp, _i, _vp]),
+	"rk_bsearchb_export": (_i, [_vp, _i, _sz, _sz, _vp, _vp, _vp, _vp]),
 	"rk_egvm_create": (_i, [C.POINTER(_vp), _i, _i, _i]),
 	"rk_egvm_destroy": (_i, [_vp]),
 	"rk_egvm_net_in": (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_sz)]),

@@ -24,6 +24,11 @@
 // state of a level k < D - R in the ball, and every hit at level D - R has ball depth exactly R: the first meeting in index and
 // action order is a shortest solution.  A start that the ball holds is answered by the ball's path without a pop.  The own
 // table is sized to the own pool; a reset clears it and never the ball's.
+//
+// The batch (rk_bsearchb_*) is S such searches in lock-step.  The kernels' bodies are __device__ functions of a SrchDev; the single
+// engine's kernels pass theirs by value, the batch's (kb_bsearch_*) pick devs[blockIdx.y] from an array in device memory, so an
+// iteration of all slots is the same four launches with S in the grid's second dimension.  Every kind of array is one block sliced
+// per slot.  A slot's pool is fixed: it stops with reason 5 before an iteration that might not fit.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <climits>
@@ -256,7 +261,8 @@ __device__ __forceinline__ int srch_pops(const SrchDev &d)
 	return (uint64_t)d.ctr[S_SIZE] + 12ull * (uint64_t)P <= (uint64_t)d.cap1 - 1u ? P : 0;
 }
 
-__global__ void k_bsearch_root(SrchDev d, BallView b, const uint32_t *root, int budget)
+// ---- the bodies: what one search does in a launch, for the single engine (k_bsearch_*) and for one slot of a batch (kb_bsearch_*) ----
+__device__ __forceinline__ void bsearch_root(const SrchDev &d, const BallView &b, const uint32_t *root, int budget)
 {
 	const int tid = threadIdx.x;
 	if (tid < S_COUNT) d.ctr[tid] = 0;
@@ -281,8 +287,7 @@ __global__ void k_bsearch_root(SrchDev d, BallView b, const uint32_t *root, int 
 }
 
 // fan-out, the look-up in the ball (read-only), then membership / election in the own table: one thread per child
-__global__ __launch_bounds__(256)
-void k_bsearch_expand(SrchDev d, BallView b)
+__device__ __forceinline__ void bsearch_expand(const SrchDev &d, const BallView &b)
 {
 	__shared__ u32x4 s_act[36];
 	stage_action_tables(s_act, threadIdx.x);
@@ -308,8 +313,7 @@ void k_bsearch_expand(SrchDev d, BallView b)
 	d.slot[c] = e == 0u ? slot : NO_SLOT;
 }
 
-__global__ __launch_bounds__(ASCAN)
-void k_bsearch_scan(SrchDev d)
+__device__ __forceinline__ void bsearch_scan(const SrchDev &d)
 {
 	const int P = srch_pops(d);
 	if (P == 0) return;                                                  // done: no ticket drawn, nothing to reset
@@ -317,8 +321,7 @@ void k_bsearch_scan(SrchDev d)
 }
 
 // child c is stored iff it is a first occurrence before the cut (rk_bfs.hip: k_bfs_append)
-__global__ __launch_bounds__(256)
-void k_bsearch_append(SrchDev d)
+__device__ __forceinline__ void bsearch_append(const SrchDev &d)
 {
 	__shared__ u32x4 s_act[36];
 	stage_action_tables(s_act, threadIdx.x);
@@ -343,9 +346,8 @@ void k_bsearch_append(SrchDev d)
 }
 
 // where the cut fell, the new size / head, the meeting, the end of a level, the next P.  One thread, ordinary stores.
-__global__ void k_bsearch_end(SrchDev d)
+__device__ __forceinline__ void bsearch_end(const SrchDev &d)
 {
-	if (threadIdx.x != 0 || blockIdx.x != 0) return;
 	if (d.ctr[S_NPOP] == 0) return;
 	const int P = srch_pops(d);
 	if (P == 0) {
@@ -393,9 +395,8 @@ void k_bsearch_rehash(SrchDev d)
 
 // The action queue of a won search: the path from the start to the popped parent and the meeting action (none of either when
 // the ball holds the start itself), then the ball's path from the meeting node.  out[0] = length or -1.
-__global__ void k_bsearch_walk(SrchDev d, BallView b, int32_t *out, int max_len)
+__device__ __forceinline__ void bsearch_walk(const SrchDev &d, const BallView &b, int32_t *out, int max_len)
 {
-	if (threadIdx.x != 0 || blockIdx.x != 0) return;
 	out[0] = -1;
 	if (!d.ctr[S_WON]) return;
 	const int p = d.ctr[S_WPARENT];
@@ -420,6 +421,103 @@ __global__ void k_bsearch_walk(SrchDev d, BallView b, int32_t *out, int max_len)
 		g = (uint32_t)b.parent[g];
 	}
 	out[0] = len;
+}
+
+// ---- the single engine: one search per launch ----
+__global__ void k_bsearch_root(SrchDev d, BallView b, const uint32_t *root, int budget) { bsearch_root(d, b, root, budget); }
+
+__global__ __launch_bounds__(256)
+void k_bsearch_expand(SrchDev d, BallView b) { bsearch_expand(d, b); }
+
+__global__ __launch_bounds__(ASCAN)
+void k_bsearch_scan(SrchDev d) { bsearch_scan(d); }
+
+__global__ __launch_bounds__(256)
+void k_bsearch_append(SrchDev d) { bsearch_append(d); }
+
+__global__ void k_bsearch_end(SrchDev d) { if (threadIdx.x == 0 && blockIdx.x == 0) bsearch_end(d); }
+
+__global__ void k_bsearch_walk(SrchDev d, BallView b, int32_t *out, int max_len) { if (threadIdx.x == 0 && blockIdx.x == 0) bsearch_walk(d, b, out, max_len); }
+
+// ---- the batch: S searches in lock-step, slot blockIdx.y of `devs` per workgroup row (rk_astar.hip: kb_merge_pass) ----
+// Every slot is a whole search of its own -- pool, table, counters, batch scratch, look-back words, ticket and epoch --, so a
+// launch reads and writes through devs[blockIdx.y] alone.  A slot that is done, or was never started, has S_NPOP == 0: it leaves
+// at that read, draws no ticket and leaves its epoch alone.  The pool of a slot never grows: a slot whose next iteration might
+// not fit (size + 12 P > capacity) stops BEFORE that iteration with BS_STOP_FULL, so srch_pops() of a slot with P > 0 is P and
+// the single engine's BS_ERR_CAPACITY path is never taken.
+enum { BS_STOP_FULL = 5 };
+
+// after the root or the end of an iteration of a slot: does the next iteration fit the pool whatever it finds?  One thread.
+__device__ __forceinline__ void srch_fit(const SrchDev &d)
+{
+	const int P = d.ctr[S_NPOP];
+	if (P == 0 || (uint64_t)d.ctr[S_SIZE] + 12ull * (uint64_t)P <= (uint64_t)d.cap1 - 1u) return;
+	d.ctr[S_STOP] = BS_STOP_FULL; d.ctr[S_DONE] = 1; d.ctr[S_NPOP] = 0;
+}
+
+// the named slots' tables and look-back words, zeroed: slot slots[blockIdx.y], 16 bytes per thread and step (a table is a power of
+// two >= 1024 dwords, every slice 16-byte aligned)
+__global__ __launch_bounds__(256)
+void kb_bsearch_clear(const SrchDev *devs, const int32_t *slots, int chain_words)
+{
+	const SrchDev d = devs[slots[blockIdx.y]];
+	u32x4 *t4 = reinterpret_cast<u32x4 *>(d.table);
+	const size_t n4 = ((size_t)d.mask + 1) / 4;
+	const u32x4 zero = {0u, 0u, 0u, 0u};
+	for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) t4[i] = zero;
+	if (blockIdx.x == 0)
+		for (int i = threadIdx.x; i < chain_words; i += 256) d.chain[i] = 0ull;
+}
+
+// row j of roots / budgets starts slot slots[j]
+__global__ void kb_bsearch_root(const SrchDev *devs, BallView b, const int32_t *slots, const uint32_t *roots, const int32_t *budgets)
+{
+	const SrchDev d = devs[slots[blockIdx.y]];
+	bsearch_root(d, b, roots + (size_t)blockIdx.y * 5, budgets[blockIdx.y]);
+	if (threadIdx.x == 0) srch_fit(d);
+}
+
+__global__ __launch_bounds__(256)
+void kb_bsearch_expand(const SrchDev *devs, BallView b)
+{
+	const SrchDev d = devs[blockIdx.y];
+	if (blockIdx.x * 256 >= 12 * d.ctr[S_NPOP]) return;                  // done, never started, or a workgroup past the batch
+	bsearch_expand(d, b);
+}
+
+__global__ __launch_bounds__(ASCAN)
+void kb_bsearch_scan(const SrchDev *devs)
+{
+	const SrchDev d = devs[blockIdx.y];
+	if (d.ctr[S_NPOP] == 0) return;                                      // (every workgroup of a live slot draws a ticket)
+	bsearch_scan(d);
+}
+
+__global__ __launch_bounds__(256)
+void kb_bsearch_append(const SrchDev *devs)
+{
+	const SrchDev d = devs[blockIdx.y];
+	if (blockIdx.x * 256 >= 12 * d.ctr[S_NPOP]) return;
+	bsearch_append(d);
+}
+
+__global__ void kb_bsearch_end(const SrchDev *devs)
+{
+	if (threadIdx.x != 0 || blockIdx.x != 0) return;
+	const SrchDev d = devs[blockIdx.y];
+	if (d.ctr[S_NPOP] == 0) return;
+	bsearch_end(d);
+	srch_fit(d);
+}
+
+// one thread per slot: row s of `out` (n_slots, 1 + max_len) = length or -1, then the queue
+__global__ __launch_bounds__(64)
+void kb_bsearch_walk(const SrchDev *devs, BallView b, int n_slots, int32_t *out, int max_len)
+{
+	const int s = blockIdx.x * 64 + threadIdx.x;
+	if (s >= n_slots) return;
+	const SrchDev d = devs[s];
+	bsearch_walk(d, b, out + (size_t)s * (1 + max_len), max_len);
 }
 
 }  // namespace rk
@@ -448,9 +546,27 @@ struct rk_bsearch {
 	DevPool pool{64};
 };
 
+// S searches in lock-step: one block of every kind of array, sliced per slot; devs[s] on the device describes slot s
+struct rk_bsearchb {
+	rk_ball *ball = nullptr;
+	int n_slots = 0, pops = 0;
+	size_t cap = 0;                             // per slot
+	uint32_t mask = 0;
+	SrchDev d{};                                // slot 0: the blocks' base addresses
+	SrchDev *devs = nullptr;
+	int32_t *slots_dev = nullptr, *budgets_dev = nullptr;
+	uint32_t *roots_dev = nullptr;
+	int32_t *walk = nullptr;
+	int walk_len = 0;                           // `walk` holds n_slots rows of 1 + walk_len words
+	std::vector<int32_t> ctr_spare;
+	Landing ctr_host;
+	DevPool pool{64};
+};
+
 namespace {
 
 constexpr int BS_WALK_MAX = 1 << 12;
+constexpr int BSB_MAX_SLOTS = 1024;
 constexpr size_t BS_MAX_CAPACITY = 0x3FFFFFF0ull;
 
 size_t ball_capacity(int radius)
@@ -726,6 +842,151 @@ int rk_bsearch_export(rk_bsearch_t *h, size_t first, size_t count, int8_t *h_sta
 	if (h_states) RK_HIP(hipMemcpyAsync(h_states, d.states + first * 5, count * STATE_BYTES, hipMemcpyDeviceToHost, st));
 	if (int e = p.start(d.parent + first, count, h_parents, st)) return e;
 	if (int e = a.start(d.pact + first, count, h_actions, st)) return e;
+	RK_HIP(hipStreamSynchronize(st));
+	p.finish(); a.finish();
+	return RK_OK;
+}
+
+int rk_bsearchb_create(rk_bsearchb_t **out, rk_ball_t *ball, int n_slots, size_t capacity_per_slot, int pops)
+{
+	if (!out || !ball) return fail(RK_EINVAL, "rk_bsearchb_create: null argument");
+	if (n_slots < 1 || n_slots > BSB_MAX_SLOTS) return fail(RK_EINVAL, "rk_bsearchb_create: n_slots %d outside 1..%d", n_slots, BSB_MAX_SLOTS);
+	if (capacity_per_slot < 2 || capacity_per_slot > BS_MAX_CAPACITY) return fail(RK_EINVAL, "rk_bsearchb_create: capacity %zu out of range", capacity_per_slot);
+	if (pops < 1 || pops > (1 << 22)) return fail(RK_EINVAL, "rk_bsearchb_create: pops %d outside 1..%d", pops, 1 << 22);
+	rk_bsearchb *h = new rk_bsearchb();
+	h->n_slots = n_slots; h->pops = pops; h->cap = capacity_per_slot;
+	h->mask = ball_table_mask(capacity_per_slot);
+	const size_t S = (size_t)n_slots, C1 = capacity_per_slot + 1, T = (size_t)h->mask + 1, K = (size_t)12 * pops, W = frontier_scan_blocks(pops);
+	SrchDev &d = h->d;
+	d.pops = pops;
+	d.cap1 = (uint32_t)C1;
+	d.mask = h->mask;
+	int e = RK_OK;
+	#define A(ptr, cnt) if (!e) e = h->pool.alloc(&d.ptr, S * (cnt))
+	A(states, C1 * 5); A(parent, C1); A(pact, C1); A(table, T); A(ctr, S_COUNT);
+	A(slot, K); A(rank, K); A(first, K); A(chain, W);
+	#undef A
+	if (!e) e = h->pool.alloc(&h->devs, S);
+	if (!e) e = h->pool.alloc(&h->slots_dev, S);
+	if (!e) e = h->pool.alloc(&h->budgets_dev, S);
+	if (!e) e = h->pool.alloc(&h->roots_dev, S * 5);
+	if (e) { (void)hipGetLastError(); delete h; return fail(RK_ECAPACITY, "rk_bsearchb_create: no device memory for %d pools of %zu states", n_slots, capacity_per_slot); }
+	std::vector<SrchDev> devs(S, d);
+	for (size_t s = 0; s < S; s++) {
+		SrchDev &x = devs[s];
+		x.states += s * C1 * 5; x.parent += s * C1; x.pact += s * C1; x.table += s * T; x.ctr += s * S_COUNT;
+		x.slot += s * K; x.rank += s * K; x.first += s * K; x.chain += s * W;
+	}
+	hipError_t he = hipMemcpy(h->devs, devs.data(), S * sizeof(SrchDev), hipMemcpyHostToDevice);
+	if (he == hipSuccess) he = hipMemset(d.ctr, 0, S * S_COUNT * sizeof(int32_t));      // never started: S_NPOP == 0, every launch passes it by
+	if (he != hipSuccess) { delete h; return fail(RK_EHIP, "rk_bsearchb_create: %s", hipGetErrorString(he)); }
+	h->ctr_host.reserve(S * S_COUNT);
+	h->ctr_spare.resize(S * S_COUNT);
+	h->ball = ball;
+	ball->attached += 1;
+	*out = h;
+	return RK_OK;
+}
+
+int rk_bsearchb_destroy(rk_bsearchb_t *h)
+{
+	if (h && h->ball) h->ball->attached -= 1;
+	delete h;
+	return RK_OK;
+}
+
+int rk_bsearchb_reset(rk_bsearchb_t *h, int n, const int32_t *slots, const int8_t *h_start_states, const long long *max_states, void *stream)
+{
+	if (!h) return fail(RK_EINVAL, "rk_bsearchb_reset: null engine");
+	if (!h->ball->built) return fail(RK_ESTATE, "rk_bsearchb_reset: build the ball first");
+	if (n < 0 || n > h->n_slots) return fail(RK_EINVAL, "rk_bsearchb_reset: %d slots of %d", n, h->n_slots);
+	if (n == 0) return RK_OK;
+	if (!slots || !h_start_states || !max_states) return fail(RK_EINVAL, "rk_bsearchb_reset: null argument");
+	std::vector<char> named((size_t)h->n_slots, 0);
+	std::vector<int32_t> budgets((size_t)n);
+	for (int j = 0; j < n; j++) {
+		if (slots[j] < 0 || slots[j] >= h->n_slots) return fail(RK_EINVAL, "rk_bsearchb_reset: slot %d outside 0..%d", slots[j], h->n_slots - 1);
+		if (named[slots[j]]) return fail(RK_EINVAL, "rk_bsearchb_reset: slot %d is named twice", slots[j]);
+		named[slots[j]] = 1;
+		budgets[j] = budget_of(max_states[j]);
+	}
+	hipStream_t st = (hipStream_t)stream;
+	RK_HIP(hipMemcpyAsync(h->slots_dev, slots, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+	RK_HIP(hipMemcpyAsync(h->budgets_dev, budgets.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+	RK_HIP(hipMemcpyAsync(h->roots_dev, h_start_states, (size_t)n * STATE_BYTES, hipMemcpyHostToDevice, st));
+	const unsigned gx = std::min<unsigned>(blocks(((size_t)h->mask + 1) / 4), 1024u);
+	hipLaunchKernelGGL(kb_bsearch_clear, dim3(gx, n), dim3(256), 0, st, h->devs, h->slots_dev, (int)frontier_scan_blocks(h->pops));   // the named slots' own tables only
+	hipLaunchKernelGGL(kb_bsearch_root, dim3(1, n), dim3(64), 0, st, h->devs, h->ball->view, h->slots_dev, h->roots_dev, h->budgets_dev);
+	RK_HIP(hipGetLastError());
+	RK_HIP(hipStreamSynchronize(st));       // the host buffers may go away after return
+	return RK_OK;
+}
+
+int rk_bsearchb_run(rk_bsearchb_t *h, int iterations, void *stream)
+{
+	if (!h) return fail(RK_EINVAL, "rk_bsearchb_run: null engine");
+	if (!h->ball->built) return fail(RK_ESTATE, "rk_bsearchb_run: build the ball first");
+	if (iterations < 0) return fail(RK_EINVAL, "rk_bsearchb_run: iterations %d < 0", iterations);
+	hipStream_t st = (hipStream_t)stream;
+	const BallView &b = h->ball->view;
+	const size_t K = (size_t)12 * h->pops;
+	const dim3 grid(blocks(K), h->n_slots), grid_scan(blocks(K, ASCAN), h->n_slots);
+	for (int it = 0; it < iterations; it++) {
+		hipLaunchKernelGGL(kb_bsearch_expand, grid, dim3(256), 0, st, h->devs, b);
+		hipLaunchKernelGGL(kb_bsearch_scan, grid_scan, dim3(ASCAN), 0, st, h->devs);
+		hipLaunchKernelGGL(kb_bsearch_append, grid, dim3(256), 0, st, h->devs);
+		hipLaunchKernelGGL(kb_bsearch_end, dim3(1, h->n_slots), dim3(64), 0, st, h->devs);
+	}
+	RK_HIP(hipGetLastError());
+	return RK_OK;
+}
+
+int rk_bsearchb_status(rk_bsearchb_t *h, long long *h_status, void *stream)
+{
+	if (!h || !h_status) return fail(RK_EINVAL, "rk_bsearchb_status: null argument");
+	const int32_t *c = nullptr;
+	if (int e = h->ctr_host.fetch(h->d.ctr, (size_t)h->n_slots * S_COUNT, h->ctr_spare.data(), (hipStream_t)stream, &c)) return e;
+	for (int s = 0; s < h->n_slots; s++, c += S_COUNT) {
+		long long *o = h_status + (size_t)s * 10;
+		o[0] = c[S_DONE]; o[1] = c[S_WON]; o[2] = c[S_SIZE]; o[3] = c[S_ITERS]; o[4] = c[S_POPPED]; o[5] = c[S_STOP]; o[6] = c[S_ERROR];
+		o[7] = c[S_NPOP]; o[8] = c[S_DEPTH]; o[9] = c[S_MEET];
+	}
+	return RK_OK;
+}
+
+int rk_bsearchb_paths(rk_bsearchb_t *h, int32_t *h_out, int max_len, void *stream)
+{
+	if (!h || !h_out) return fail(RK_EINVAL, "rk_bsearchb_paths: null argument");
+	if (!h->ball->built) return fail(RK_ESTATE, "rk_bsearchb_paths: build the ball first");
+	if (max_len < 0 || max_len > BS_WALK_MAX) return fail(RK_EINVAL, "rk_bsearchb_paths: max_len %d outside 0..%d", max_len, BS_WALK_MAX);
+	hipStream_t st = (hipStream_t)stream;
+	const size_t words = (size_t)h->n_slots * (size_t)(1 + max_len);
+	if (h->walk == nullptr || h->walk_len < max_len) {
+		RK_HIP(hipStreamSynchronize(st));
+		if (h->walk != nullptr) { h->pool.release(h->walk); h->walk = nullptr; }
+		if (h->pool.alloc(&h->walk, words) != RK_OK) { (void)hipGetLastError(); return fail(RK_ECAPACITY, "rk_bsearchb_paths: no device memory for %zu words", words); }
+		h->walk_len = max_len;
+	}
+	hipLaunchKernelGGL(kb_bsearch_walk, dim3(blocks((size_t)h->n_slots, 64)), dim3(64), 0, st, h->devs, h->ball->view, h->n_slots, h->walk, max_len);
+	RK_HIP(hipGetLastError());
+	RK_HIP(hipMemcpyAsync(h_out, h->walk, words * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+	RK_HIP(hipStreamSynchronize(st));
+	return RK_OK;
+}
+
+int rk_bsearchb_export(rk_bsearchb_t *h, int slot, size_t first, size_t count, int8_t *h_states, long long *h_parents, long long *h_actions, void *stream)
+{
+	if (!h) return fail(RK_EINVAL, "rk_bsearchb_export: null engine");
+	if (slot < 0 || slot >= h->n_slots) return fail(RK_EINVAL, "rk_bsearchb_export: slot %d outside 0..%d", slot, h->n_slots - 1);
+	if (first + count > h->cap + 1) return fail(RK_EINVAL, "rk_bsearchb_export: rows %zu..%zu outside the pool", first, first + count);
+	if (count == 0) return RK_OK;
+	hipStream_t st = (hipStream_t)stream;
+	const size_t at = (size_t)slot * (h->cap + 1) + first;
+	Widened<int32_t, long long> p;
+	Widened<uint8_t, long long> a;
+	if (h_states) RK_HIP(hipMemcpyAsync(h_states, h->d.states + at * 5, count * STATE_BYTES, hipMemcpyDeviceToHost, st));
+	if (int e = p.start(h->d.parent + at, count, h_parents, st)) return e;
+	if (int e = a.start(h->d.pact + at, count, h_actions, st)) return e;
 	RK_HIP(hipStreamSynchronize(st));
 	p.finish(); a.finish();
 	return RK_OK;

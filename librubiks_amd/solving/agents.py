@@ -790,6 +790,203 @@ class DeviceBallSearch(Agent, _ffi.Owner):
 		return f"Breadth-first search to a goal ball (device, radius={self.ball.radius}, pops={self.pops})"
 
 
+class DeviceBallSearchBatch(_ffi.Owner):
+	"""
+	Shortest solutions of many states at once: `searches` slots, each a whole `DeviceBallSearch` of its own (pool, table,
+	counters), advanced in lock-step by the same four launches with the slot in the grid's second dimension (engine
+	rk_bsearchb_*, csrc/rk_ball.hip).  A single search is latency-bound -- four launches per iteration on a few per cent of the
+	card --; the batch pays those launches once for all slots.  Every state gets exactly what `DeviceBallSearch` gives it alone:
+	result, queue, states stored, depth, nodes popped, meeting and pool, whatever slot it ran in and whenever it was started.
+
+	`search(states)` takes any number of states.  Slots take them in input order; every `poll` iterations the host reads all
+	slots' status, records the searches that finished (their queues; their pools with `keep_arrays`) and starts the next waiting
+	states in the slots that became free, so short searches do not leave the card idle beside long ones.
+
+	The pool of a slot does not grow: `capacity` states per slot (default: `DeviceBallSearch`'s rule from the largest budget of
+	the call, at most `default_capacity`).  A search whose next iteration might not fit -- states + 12 x (nodes it would pop) >
+	capacity -- stops before that iteration: False, stop reason 5, `capacity_exhausted[i]` set, the other searches undisturbed.
+
+	After a call, indexed by input position: `lengths` (-1: not met), `status` (n, 10) -- rk_bsearch_status's words: done, won,
+	states, iterations, popped, stop reason, error, next pops, complete levels, meeting node --, `sizes`, `depths`, `popped`,
+	`iterations`, `meeting_depths` (-1: none), `stops`, `capacity_exhausted`, `action_queue_of(i)` and `arrays(i)`.
+	`on_poll(status)`, if set, is called at every poll with the status of the states seen finished so far (zeros for the others).
+
+	`pops` = 2 048 by default is provisional, not measured yet: 64 slots x 12 x 2 048 children fill an iteration with 1.6 M threads,
+	eight times a single search's 16 384 pops, while a level of a few thousand nodes still takes few iterations.
+	benchmarks/ball_batch.py sweeps 512 / 2 048 / 16 384 at 16 / 64 / 256 searches and names the value it favours at 64.
+	"""
+	default_capacity = 8_000_000
+	MAX_SEARCHES = 1024                     # rk_bsearchb_create's limits
+	MAX_POPS = 1 << 22
+	MAX_CAPACITY = 0x3FFFFFF0
+	PATH_WORDS = 64                         # actions read per slot at a poll (a longer queue is read again, whole)
+
+	def __init__(self, ball: DeviceGoalBall, searches: int = 64, pops: int = 2_048, capacity: int = None, poll: int = 8):
+		if not isinstance(ball, DeviceGoalBall):
+			raise TypeError(f"ball must be a DeviceGoalBall, got {type(ball).__name__}")
+		if isinstance(searches, bool) or int(searches) != searches or not 1 <= int(searches) <= self.MAX_SEARCHES:
+			raise ValueError(f"searches must be an integer in 1..{self.MAX_SEARCHES}, got {searches!r}")
+		if isinstance(pops, bool) or int(pops) != pops or not 1 <= int(pops) <= self.MAX_POPS:
+			raise ValueError(f"pops must be an integer in 1..{self.MAX_POPS}, got {pops!r}")
+		if capacity is not None and (isinstance(capacity, bool) or int(capacity) != capacity or not 2 <= int(capacity) <= self.MAX_CAPACITY):
+			raise ValueError(f"capacity must be an integer in 2..{self.MAX_CAPACITY}, got {capacity!r}")
+		if isinstance(poll, bool) or int(poll) != poll or int(poll) < 1:
+			raise ValueError(f"poll must be a positive integer, got {poll!r}")
+		self.ball = ball
+		self.searches, self.pops, self.poll = int(searches), int(pops), int(poll)
+		self.capacity = int(capacity) if capacity is not None else None
+		self._h, self._h_cap = None, 0
+		self._is2024 = True
+		self.on_poll = None                 # callable(status (n, 10)): called at every poll
+		self.lockstep_iterations = 0        # iterations of all slots the last call launched
+		self._results(0, False)
+
+	def _results(self, n: int, keep_arrays: bool):
+		self.status = np.zeros((n, 10), np.int64)
+		self.lengths = np.full(n, -1, np.int64)
+		self._queues = [deque() for _ in range(n)]
+		self._arrays = [None] * n if keep_arrays else None
+
+	sizes = property(lambda self: self.status[:, 2])
+	iterations = property(lambda self: self.status[:, 3])
+	popped = property(lambda self: self.status[:, 4])
+	stops = property(lambda self: self.status[:, 5])
+	depths = property(lambda self: self.status[:, 8])
+	capacity_exhausted = property(lambda self: self.status[:, 5] == 5)
+
+	@property
+	def meeting_depths(self) -> np.ndarray:
+		"""int64 (n,): the depth in the ball of the node every search met, -1 for a search that did not meet."""
+		meet = self.status[:, 9]
+		if not meet.any():
+			return np.full(len(meet), -1, np.int64)
+		return np.where(meet > 0, np.searchsorted(self.ball.level_start, meet, side="right") - 1, -1).astype(np.int64)
+
+	def _engine(self, capacity: int):
+		if self._h is not None and self._h_cap >= capacity:
+			return self._h
+		self._free()                        # the old pools go before the new ones are made
+		self._h_cap = capacity
+		return self._create("rk_bsearchb_create", "rk_bsearchb_destroy", self.ball._h, self.searches, capacity, self.pops)
+
+	def _start(self, h, slots: list, rows: np.ndarray, budgets: np.ndarray):
+		sl = np.ascontiguousarray(slots, dtype=np.int32)
+		rows, budgets = np.ascontiguousarray(rows, dtype=np.int8), np.ascontiguousarray(budgets, dtype=np.int64)
+		_ffi.check(_ffi.lib().rk_bsearchb_reset(h, len(sl), sl.ctypes.data, rows.ctypes.data, budgets.ctypes.data, _ffi.stream_ptr()))
+
+	def _paths(self, h, max_len: int) -> np.ndarray:
+		out = np.zeros((self.searches, 1 + max_len), np.int32)
+		_ffi.check(_ffi.lib().rk_bsearchb_paths(h, out.ctypes.data, max_len, _ffi.stream_ptr()))
+		return out
+
+	def _export(self, h, slot: int, n: int):
+		states = np.zeros((n + 1, 20), np.int8)
+		parents, actions = np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int64)
+		if n:
+			_ffi.check(_ffi.lib().rk_bsearchb_export(h, slot, 1, n, states[1:].ctypes.data, parents[1:].ctypes.data,
+			                                          actions[1:].ctypes.data, _ffi.stream_ptr()))
+			actions[1] = -1
+		return _states_out(self._is2024, states, n)[1:], parents[1:], actions[1:]
+
+	@no_grad
+	def search(self, states, time_limit: float = None, max_states=None, keep_arrays: bool = False) -> np.ndarray:
+		"""bool (n,): whether each state's search met the ball.  `max_states`: one budget for all, or one per state (n,);
+		`time_limit` bounds the whole call: searches still running or waiting when it passes come back False with stop reason 0."""
+		t0 = time.perf_counter()
+		time_limit = time_limit or 1e10         # (an exact search may run without either limit)
+		self._is2024 = cube.get_is2024()
+		arr = np.asarray(states, dtype=np.int8)
+		width = 20 if self._is2024 else 288
+		if arr.size % width:
+			raise ValueError(f"states must be (n, 20), or (n, 6, 8, 6) in 6x8x6 mode, got shape {arr.shape}")
+		n = arr.size // width
+		budgets = np.asarray(int(1e10) if max_states is None else max_states)
+		if budgets.ndim > 1 or (budgets.ndim == 1 and len(budgets) != n):
+			raise ValueError(f"max_states must be a number or one per state, got shape {budgets.shape}")
+		budgets = np.minimum(np.broadcast_to(budgets, (n,)).astype(np.int64), 2 ** 31 - 1)
+		rows = _roots20(self._is2024, arr, n)   # ValueError for an illegal 6x8x6 state, before anything runs
+		self._results(n, keep_arrays)
+		self.lockstep_iterations = 0
+		if n == 0:
+			return np.zeros(0, bool)
+		_ffi.require_gpu()
+		self.ball.build()
+		lib, stream = _ffi.lib(), _ffi.stream_ptr()
+		S, K = self.searches, 12 * self.pops
+		cap = self.capacity or min(int(budgets.max()) + K, self.default_capacity)
+		h = self._engine(max(2, min(cap, self.MAX_CAPACITY)))
+		holds = np.full(S, -1, np.int64)        # the input position every slot runs, -1: free
+		waiting = 0                             # the next input position to start
+		st = np.zeros((S, 10), np.int64)
+		try:
+			while True:
+				_ffi.check(lib.rk_bsearchb_status(h, st.ctypes.data, stream))
+				if st[holds >= 0, 6].any():
+					raise _ffi.RubiksHipError(f"ball search engine error codes {st[holds >= 0, 6].tolist()}")
+				done = np.nonzero((holds >= 0) & (st[:, 0] != 0))[0]
+				if len(done):
+					paths = self._paths(h, self.PATH_WORDS) if st[done, 1].any() else None
+					if paths is not None and paths[done, 0].max() > self.PATH_WORDS:
+						paths = self._paths(h, 4096)
+					for s in done.tolist():
+						i = int(holds[s])
+						self.status[i] = st[s]
+						if st[s, 1]:
+							self.lengths[i] = paths[s, 0]
+							self._queues[i] = deque(paths[s, 1:1 + paths[s, 0]].tolist())
+						if keep_arrays:
+							self._arrays[i] = self._export(h, s, int(st[s, 2]))
+						holds[s] = -1
+				if self.on_poll is not None:
+					self.on_poll(self.status)
+				late = time.perf_counter() - t0 >= time_limit
+				free = np.nonzero(holds < 0)[0]
+				if waiting < n and len(free) and not late:
+					free = free[:n - waiting]
+					took = np.arange(waiting, waiting + len(free))
+					self._start(h, free, rows[took], budgets[took])
+					holds[free] = took
+					waiting += len(free)
+					continue                    # a start the ball holds is done already: look before running
+				live = holds >= 0
+				if late or not live.any():
+					break
+				room = int((budgets[holds[live]] - st[live, 2]).min())
+				burst = eng.burst(self.poll, room, K)
+				_ffi.check(lib.rk_bsearchb_run(h, burst, stream))
+				self.lockstep_iterations += burst
+			live = np.nonzero(holds >= 0)[0]
+			if len(live):                       # out of time: what the searches had reached, stop reason 0; then the slots are put to rest
+				for s in live.tolist():
+					i = int(holds[s])
+					self.status[i] = st[s]
+					if keep_arrays:
+						self._arrays[i] = self._export(h, s, int(st[s, 2]))
+				if keep_arrays:
+					for i in range(waiting, n):
+						self._arrays[i] = self._export(h, 0, 0)
+				self._start(h, live, np.repeat(_SOLVED20[None], len(live), axis=0), np.ones(len(live), np.int64))
+		except Exception:
+			self._free()                        # slots in an unknown state: the next call starts from a new engine
+			raise
+		return self.status[:, 1] != 0
+
+	def action_queue_of(self, i: int) -> deque:
+		return deque(self._queues[i])
+
+	def arrays(self, i: int):
+		"""(states, parents, actions) of the pool of state i's search, as `DeviceBallSearch.arrays()`; needs `keep_arrays`."""
+		if self._arrays is None:
+			raise ValueError("the pools were not kept: search(..., keep_arrays=True)")
+		return self._arrays[i]
+
+	def __len__(self):
+		return int(self.status[:, 2].sum())
+
+	def __str__(self):
+		return f"Breadth-first searches to a goal ball x{self.searches} (device, radius={self.ball.radius}, pops={self.pops})"
+
+
 class PolicySearch(DeepAgent):
 	"""Follow (or sample from) the policy head (agents.py:132-151)."""
 	def __init__(self, net, sample_policy=False):
