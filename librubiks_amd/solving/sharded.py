@@ -171,20 +171,24 @@ def net_rows(K: int, world: int) -> int:
 	return min(K, -(-int(rows + 0.999999) // 64) * 64)
 
 
-def select_pops(heads: np.ndarray, n: int) -> np.ndarray:
+def select_pops(heads: np.ndarray, n: int, counts=None) -> np.ndarray:
 	"""
 	Host statement of the selection rule the device kernel `k_shard_decide` implements (used by the tests as its spec):
 	heads is (world, n) float64, row r = the n cheapest open costs of rank r in ascending order, padded with +inf.
 	Returns how many head entries each rank pops so that together they are the n globally cheapest by
 	(cost, rank, position).
+	`counts` (world,): how many entries of every row are candidates (slot 4 of a rank's all-gather contribution), which is how the
+	kernel tells the padding from an open node whose cost IS +inf (a net may return -inf): such a node is popped like any other
+	when it is among the n cheapest.  Without `counts` every +inf is taken for padding.
 	"""
 	world = heads.shape[0]
 	cost = heads.ravel()
 	rank = np.repeat(np.arange(world), heads.shape[1])
 	pos = np.tile(np.arange(heads.shape[1]), world)
-	order = np.lexsort((pos, rank, cost))
+	real = ~np.isposinf(cost) if counts is None else pos < np.repeat(np.asarray(counts, np.int64), heads.shape[1])
+	order = np.lexsort((pos, rank, cost, ~real))                         # the padding last, whatever it holds
 	take = order[:n]
-	take = take[np.isfinite(cost[take])]
+	take = take[real[take]]
 	return np.bincount(rank[take], minlength=world).astype(np.int64)
 
 

@@ -112,6 +112,7 @@ class ShardedAStarOracle:
 		heapq.heappush(root.open, (0.0, 1))                                 # heappush(open_queue, (0, 1)), agents.py:234
 		self.pops = []              # per iteration: list over ranks of the node indices popped, in pop order
 		self.new_counts = []        # per iteration: list over ranks of the number of states appended
+		self.cand_costs = []        # per iteration: list over ranks of the costs the rank publishes (its candidates in order), float64
 		self.iterations = 0
 		self.winner = None
 		self.action_queue = deque()
@@ -119,6 +120,8 @@ class ShardedAStarOracle:
 		while True:
 			# ---- all-gather + k_shard_decide -------------------------------------------------------------------
 			cands = [rk.candidates(N) for rk in self.ranks]
+			# what the ranks publish, the gather of the iteration that takes the stop decision included: iterations + 1 entries
+			self.cand_costs.append([np.array([cost + 0.0 for cost, _ in c], dtype=np.float64) for c in cands])
 			total = sum(len(rk) for rk in self.ranks)
 			biggest = max(len(rk) for rk in self.ranks)
 			winner = next((r for r, rk in enumerate(self.ranks) if rk.won), None)

@@ -19,6 +19,21 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 ASTAR_CASES = ["a_solve17", "a_offset1000", "a_special128", "a_bf16_3", "a_budget128", "a_solve3"]
 MCTS_CASES = ["m_half", "m_one_graph", "m_five", "m_five_graph"]
 _CACHE = {}
+# the LookupNets of the searches that have no fixture (tests/test_real_valued_search_gpu.py, tests/test_sharded_real_valued_*.py)
+VARIANTS = {
+	"plain": dict(),                                           # costs positive, a misleading heuristic: both relaxation passes run
+	"offset": dict(offset=9.0),                                # costs on both sides of zero
+	"special": dict(offset=9.0, special=True),                 # ... and denormals, +-1e30, +-inf
+	"bf16": dict(dtype="bfloat16", offset=9.0),                # bfloat16 outputs: the engine widens them itself
+	"misleading": dict(scale=6.0, stub_weight=0.25),           # noise far above the signal, as NoisyStubNet's
+}
+_NETS = {}
+
+
+def variant(name: str, seed: int = 30) -> LookupNet:
+	if (name, seed) not in _NETS:
+		_NETS[name, seed] = LookupNet(seed=seed, **VARIANTS[name])
+	return _NETS[name, seed]
 
 
 def load_trace() -> dict:

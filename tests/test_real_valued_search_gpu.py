@@ -23,24 +23,9 @@ from oracle import cube_oracle as orc
 from oracle.search_oracle import AStarOracle, LookupNet, MCTSOracle
 from tests.test_greedy_batch_gpu import STARTS, host_search, move, value_step
 from tests.test_mcts_gpu import _same_tree
-from tests.test_real_valued_oracle_cpu import ASTAR_CASES, MCTS_CASES, astar_oracle, load_trace, net_of
+from tests.test_real_valued_oracle_cpu import ASTAR_CASES, MCTS_CASES, VARIANTS, astar_oracle, load_trace, net_of, variant  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-VARIANTS = {
-	"plain": dict(),                                           # costs positive, a misleading heuristic: both relaxation passes run
-	"offset": dict(offset=9.0),                                # costs on both sides of zero
-	"special": dict(offset=9.0, special=True),                 # ... and denormals, +-1e30, +-inf
-	"bf16": dict(dtype="bfloat16", offset=9.0),                # bfloat16 outputs: the engine widens them itself
-	"misleading": dict(scale=6.0, stub_weight=0.25),           # noise far above the signal, as NoisyStubNet's
-}
-_NETS = {}
-
-
-def variant(name: str, seed: int = 30) -> LookupNet:
-	if (name, seed) not in _NETS:
-		_NETS[name, seed] = LookupNet(seed=seed, **VARIANTS[name])
-	return _NETS[name, seed]
 
 
 # ---- A* ---------------------------------------------------------------------------------------------------------------------

@@ -53,14 +53,16 @@ def test_world1_equals_oracle(seed, depth, lam, n, budget):
 	assert list(agent.action_queue) == list(ref.action_queue)
 
 
-def _simulate_ranks(world, start, lam, N, budget, capacity, oracle=None, net=None):
+def _simulate_ranks(world, start, lam, N, budget, capacity, oracle=None, net=None, values_bf16=False):
 	"""
 	All `world` ranks of a sharded search in ONE process on one GPU: one engine per rank, the two collectives done by hand
 	(all-gather = stack the contributions, all-to-all = transpose the send blocks).  Checks on the way that every rank takes
 	the same stop decision and that the device's global top-N selection equals the host statement of the rule.
 	With `oracle` (a ShardedAStarOracle that has run the same search on the CPU) every iteration's pops and new-state counts
 	of every rank, and at the end every rank's whole shard -- states, G, parents, parent ranks, actions, open queue -- are
-	compared with it BIT FOR BIT (VERDICT r3 #1b).
+	compared with it BIT FOR BIT (VERDICT r3 #1b) -- and every all-gather contribution: the candidate costs a rank publishes are the
+	oracle's float64 costs bit for bit, +inf behind them.
+	`values_bf16`: the net returns bfloat16 values; the engines are told so (rk_astar_set_values_dtype) and read the tensor as it is.
 	"""
 	import ctypes as C
 	from librubiks_amd.solving.sharded import net_rows, select_pops
@@ -69,6 +71,7 @@ def _simulate_ranks(world, start, lam, N, budget, capacity, oracle=None, net=Non
 	for r in range(world):
 		h = C.c_void_p()
 		_ffi.check(lib.rk_astar_create_sharded(C.byref(h), capacity, N, r, world))
+		_ffi.check(lib.rk_astar_set_values_dtype(h, _ffi.OH_BF16 if values_bf16 else _ffi.OH_F32))
 		send = torch.zeros((world, int(lib.rk_astar_shard_block_bytes(h))), dtype=torch.uint8, device="cuda")
 		mine = torch.zeros(int(lib.rk_astar_shard_gather_len(h)), dtype=torch.float64, device="cuda")
 		_ffi.check(lib.rk_astar_shard_bind(h, mine.data_ptr()))
@@ -82,6 +85,15 @@ def _simulate_ranks(world, start, lam, N, budget, capacity, oracle=None, net=Non
 	iters = 0
 	while True:
 		gathered = torch.stack(mines).contiguous()
+		heads = gathered.cpu().numpy()
+		if oracle is not None:
+			# what every rank publishes -- also in the gather that takes the stop decision: its n_r candidate costs, then +inf up to N
+			assert iters < len(oracle.cand_costs), "the device goes on where the oracle stopped"
+			for r in range(world):
+				n_r, cost = int(heads[r, 4]), oracle.cand_costs[iters][r]
+				assert heads[r, 4] == len(cost) <= N, (iters, r, heads[r, 4], len(cost))
+				assert (heads[r, 8:8 + n_r].view(np.uint64) == cost.view(np.uint64)).all(), (iters, r)
+				assert np.isposinf(heads[r, 8 + n_r:]).all() and heads.shape[1] == 8 + N, (iters, r)
 		decisions = []
 		for r in range(world):
 			_ffi.check(lib.rk_astar_shard_select(hs[r], gathered.data_ptr(), 1e10, float(budget), sends[r].data_ptr(), st()))
@@ -91,7 +103,7 @@ def _simulate_ranks(world, start, lam, N, budget, capacity, oracle=None, net=Non
 		assert all(d[:4] == decisions[0][:4] for d in decisions)          # same stop, winner and total everywhere
 		if stop:
 			break
-		want = select_pops(gathered[:, 8:].cpu().numpy(), N)
+		want = select_pops(heads[:, 8:], N, heads[:, 4])                  # (slot 4: the candidates of a row; an open node may cost +inf)
 		assert [d[4] for d in decisions] == want.tolist(), (iters, [d[4] for d in decisions], want)
 		if oracle is not None:
 			assert iters < len(oracle.pops), "the device goes on where the oracle stopped"
@@ -107,6 +119,7 @@ def _simulate_ranks(world, start, lam, N, budget, capacity, oracle=None, net=Non
 			assert 0 <= n_new[0] <= 12 * N, (iters, r, n_new[0])            # a rank never appends more than 12 N states
 			news.append(n_new[0])
 			values = net(oh, policy=False, value=True).reshape(-1).contiguous()
+			assert values.dtype == (torch.bfloat16 if values_bf16 else torch.float32) and values.is_cuda     # bfloat16 goes in unconverted
 			# what the driver does: values promised for a fixed number of rows (the rank's expected share + 6 sigma + 64), which also
 			# sizes this iteration's sort / insert launches (shard_push_impl); the whole-batch entry on every third iteration
 			if iters % 3 == 2:
@@ -151,6 +164,8 @@ def _simulate_ranks(world, start, lam, N, budget, capacity, oracle=None, net=Non
 			costs, idx = np.zeros(n_open), np.zeros(n_open, np.int64)
 			got = lib.rk_astar_export_open(hs[r], costs.ctypes.data, idx.ctypes.data, n_open, st())
 			assert list(zip(costs[:got].tolist(), idx[:got].tolist())) == [(c, i) for c, i in oracle.open_queue(r)], r
+			want_costs = np.array([float(c) for c, _ in oracle.open_queue(r)], np.float64)
+			assert got == n_open == len(want_costs) and (costs.view(np.uint64) == want_costs.view(np.uint64)).all(), r     # bits: a -0.0 the engine kept would show
 		lib.rk_astar_destroy(hs[r])
 	if oracle is not None:
 		assert iters == oracle.iterations and stop == oracle.stop
