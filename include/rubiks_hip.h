@@ -415,6 +415,30 @@ int rk_ball_depth(rk_ball_t *h, const int8_t *d_states, size_t n, int32_t *d_dep
  * int8 (n, radius) holds them, padded with -1.  One launch; stream-ordered, no synchronisation. */
 int rk_ball_solve(rk_ball_t *h, const int8_t *d_states, size_t n, int32_t *d_lengths, int8_t *d_actions, void *stream);
 
+/* ---- shortening action queues against the ball (rk_bshorten_*) ----------------------------------------------------------
+ * One pass over a batch of action queues; neither their start states nor a net is needed.  The moves a[i .. j-1] of a queue,
+ * applied to the solved state, give a state X(i, j); cube states are a group, so the distance between the queue's states s_i
+ * and s_j is the distance of X(i, j) to solved, and any word that reaches X(i, j) from solved leads from s_i to s_j.  For
+ * every 0 <= i < j <= len with j - i <= window, d(i, j) is the ball depth of X(i, j) (no edge outside the ball, except that a
+ * single move outside a radius-0 ball costs 1).  cost[0] = 0, cost[j] = min over i of cost[i] + d(i, j), ties to the LARGEST
+ * i; along the best path a window with d(i, j) = j - i is copied, any other is replaced by the ball's word for X(i, j): the
+ * stored actions from node 1 down to the node.  The output has cost[len] <= len moves and reaches the same state from any
+ * start; a queue whose every window is as short as the ball knows comes back byte for byte.  Three launches: d(i, j) of all
+ * windows (a wave per queue and i), the shortest path (a workgroup per queue), the rewritten queue (a wave per queue).  The
+ * ball is only read. */
+/* Bytes of scratch one rk_bshorten call of this shape needs: n * max_len * window for d(i, j), n * (max_len + 1) * 2 for the
+ * path.  RK_EINVAL unless 1 <= window <= max_len <= 4096 and n * max_len <= 2^30.  Touches no device. */
+long long rk_bshorten_scratch_bytes(size_t n, int max_len, int window);
+/* DEVICE d_actions int8 (n, max_len), row q holding d_len[q] actions 0..11 (what follows is ignored; -1 by convention), to
+ * d_out_actions int8 (n, max_len), padded with -1, and d_out_len int32 (n); the output may not be the input.  d_scratch:
+ * 16-byte aligned, scratch_bytes >= rk_bshorten_scratch_bytes(n, max_len, window).  d_error[0] is cleared, then set to
+ * RK_EINVAL if a queue holds an action outside 0..11 before its length, or a length outside 0..max_len: no such action
+ * indexes a table, and that queue comes back as it is (its first min(max(len, 0), max_len) bytes) while the others are
+ * rewritten.  (RK_ESTATE there: a parent chain of the ball is broken.)  RK_ESTATE if the ball is not built, RK_EINVAL for a
+ * null pointer or a size out of range.  Stream-ordered, no synchronisation. */
+int rk_bshorten(rk_ball_t *h, const int8_t *d_actions, const int32_t *d_len, size_t n, int max_len, int window, int8_t *d_out_actions,
+                int32_t *d_out_len, int32_t *d_error, void *d_scratch, size_t scratch_bytes, void *stream);
+
 /* ---- shortest solutions by a one-sided breadth-first search from the start that ends at the ball ------------------------
  * rk_bfs's protocol in a pool of its own (node 1 = the start), one level at a time: a child the own pool holds is skipped,
  * a child the BALL holds is the meeting -- the search ends (won), the child is not stored, the lowest batch position wins

@@ -108,6 +108,8 @@ SIGNATURES = {
 	"rk_ball_export": (_i, [_vp, _sz, _sz, _vp, _vp, _vp, _vp]),
 	"rk_ball_depth": (_i, [_vp, _vp, _sz, _vp, _vp]),
 	"rk_ball_solve": (_i, [_vp, _vp, _sz, _vp, _vp, _vp]),
+	"rk_bshorten_scratch_bytes": (C.c_longlong, [_sz, _i, _i]),
+	"rk_bshorten": (_i, [_vp, _vp, _vp, _sz, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
 	"rk_bsearch_create": (_i, [C.POINTER(_vp), _vp, _sz, _i]),
 	"rk_bsearch_destroy": (_i, [_vp]),
 	"rk_bsearch_reset": (_i, [_vp, _vp, C.c_longlong, _vp]),

@@ -17,6 +17,18 @@
 //   k_ball_depth   one thread per query: read-only probe (probe_find), 20-byte compare, depth from the level boundaries; -1 outside
 //   k_ball_solve   the same, then the walk along the parents: the inverse of every stored action leads back to solved
 //
+// Shortening (rk_bshorten_*): one pass over a batch of action queues, the start states not needed.  The moves a[i .. j-1] of a
+// queue, applied to the solved state, give X(i, j); the distance between the queue's states s_i and s_j is the ball depth d(i, j)
+// of X(i, j), and the ball's word for X(i, j) leads from s_i to s_j as well (the states are a group).  So a queue is a DAG over
+// 0 .. L with an edge i -> j of weight d(i, j) for every window j - i <= W that the ball holds, and its best rewrite a shortest path:
+//   k_shorten_windows   a WAVE per (queue, i), the lane is the offset: the window's moves composed by scan_moves in chunks of 64
+//                       with a carried state (rk_cube_kernels.hip: k_apply_sequences_scan), probe_find, d(i, j) as one byte
+//   k_shorten_dp        a workgroup per queue: cost[j] = min cost[i] + w(i, j), the candidates of one j reduced in parallel,
+//                       ties to the largest i; cost in LDS, pred to scratch
+//   k_shorten_emit      a wave per queue: back along pred, then forward; an edge with d < j - i is replaced by the ball's word
+//                       for X(i, j) (found again by one scan and one probe), the stored actions from node 1 down to the node
+// Nothing of the ball is written.
+//
 // The search (rk_bsearch_*) is rk_bfs.hip's protocol from the start (node 1 of a pool of its own) with rk_bibfs.hip's level
 // bookkeeping and meeting: a child the own pool holds is skipped, a child the BALL holds is the meeting -- not stored, the lowest
 // batch position wins --, every other is appended.  The budget is checked before every pop; the cut is min(12 x the first
@@ -216,6 +228,188 @@ void k_ball_solve(BallView b, const uint32_t *queries, size_t n, int32_t *length
 	}
 	lengths[q] = ok ? len : -1;
 	for (int k = ok ? len : 0; k < b.radius; k++) row[k] = -1;
+}
+
+// ---- shortening action queues against the ball ---------------------------------------------------------------------------------
+constexpr int SHORTEN_MAX_LEN = 1 << 12;
+constexpr uint16_t SHORTEN_KEPT = 0xFFFFu;      // pred[0] of a queue that is not rewritten (an action outside 0..11, a length outside 0..max_len)
+constexpr int SHORTEN_DP_THREADS = 256;
+
+__device__ __forceinline__ int shorten_len(const int32_t *len, size_t p, int max_len)
+{
+	const int L = len[p];
+	return L < 0 ? 0 : L > max_len ? max_len : L;
+}
+
+// One chunk of up to 64 consecutive moves, one per lane (`a`; lanes >= n hold none): st = the state after the moves of lanes
+// 0 .. lane applied to s.  An action outside 0..11 indexes no table (it counts as action 0; its queue is never rewritten).
+// All 64 lanes call it.
+__device__ __forceinline__ void chunk_states(const u32x4 *s_act, uint32_t a, int lane, int n, const uint32_t s[5], uint32_t st[5])
+{
+	uint32_t X[12];
+	if (lane < n) load_action_table(s_act, a < 12u ? a : 0u, X);
+	else identity_moves(X);
+	scan_moves(X, lane, lane, n);
+	#pragma unroll
+	for (int j = 0; j < 5; j++) st[j] = s[j];
+	move5(st, X);
+}
+
+// d(i, j) of every window of queue p that starts at i: wave (p, i), lane = offset inside a chunk of 64 moves.  The byte of window
+// (i, j) is depth[(p * max_len + j - 1) * window + (j - i - 1)]: the row of an END j is contiguous, which is how the DP reads it.
+__global__ __launch_bounds__(256)
+void k_shorten_windows(BallView b, const int8_t *__restrict__ actions, const int32_t *__restrict__ len, size_t n, int max_len, int window,
+                       int8_t *__restrict__ depth)
+{
+	__shared__ u32x4 s_act[36];
+	stage_action_tables(s_act, threadIdx.x);
+	__syncthreads();
+	const int lane = threadIdx.x & 63;
+	const size_t w = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+	if (w >= n * (size_t)max_len) return;                                // (whole waves)
+	const size_t p = w / (size_t)max_len;
+	const int i = (int)(w - p * (size_t)max_len);
+	const int L = shorten_len(len, p, max_len);
+	if (i >= L) return;
+	const int8_t *row = actions + p * (size_t)max_len;
+	const int moves = min(window, L - i);                                // windows (i, i + 1) .. (i, i + moves)
+	uint32_t s[5] = {SOLVED_DW[0], SOLVED_DW[1], SOLVED_DW[2], SOLVED_DW[3], SOLVED_DW[4]};
+	uint32_t a_next = lane < moves ? (uint32_t)(uint8_t)row[i + lane] : 0xFFu;
+	for (int d0 = 0; d0 < moves; d0 += 64) {
+		const int nc = min(64, moves - d0);
+		const uint32_t a = a_next;
+		a_next = d0 + 64 + lane < moves ? (uint32_t)(uint8_t)row[i + d0 + 64 + lane] : 0xFFu;    // behind the six scan steps
+		uint32_t st[5];
+		chunk_states(s_act, a, lane, nc, s, st);
+		if (lane < nc) {
+			const uint32_t e = probe_find(b.table, b.mask, b.states, st);
+			const int k = d0 + lane;                                         // j - i - 1
+			depth[(p * (size_t)max_len + (size_t)(i + k)) * (size_t)window + (size_t)k] = (int8_t)(e ? ball_depth_of(b, e) : -1);
+		}
+		#pragma unroll
+		for (int j = 0; j < 5; j++) s[j] = (uint32_t)__builtin_amdgcn_readlane((int)st[j], nc - 1);   // carries into the next chunk
+	}
+}
+
+// The shortest path 0 -> L of queue blockIdx.x.  key = cost << 12 | (j - i - 1): the minimum is the least cost and, among equal
+// costs, the largest i.  One barrier per j: the partial minima alternate between two rows, and cost[j] is read by the thread
+// that wrote it (k = 1) or two barriers later.
+__global__ __launch_bounds__(SHORTEN_DP_THREADS)
+void k_shorten_dp(const int8_t *__restrict__ actions, const int32_t *__restrict__ len, int max_len, int window,
+                  const int8_t *__restrict__ depth, uint16_t *__restrict__ pred, int32_t *error)
+{
+	__shared__ uint16_t cost[SHORTEN_MAX_LEN + 1];
+	__shared__ uint32_t part[2][SHORTEN_DP_THREADS / 64];
+	const size_t p = blockIdx.x;
+	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+	const int L = shorten_len(len, p, max_len);
+	const int8_t *row = actions + p * (size_t)max_len;
+	uint16_t *pr = pred + p * (size_t)(max_len + 1);
+	int bad = len[p] != L;
+	for (int k = tid; k < L; k += SHORTEN_DP_THREADS) bad |= (uint8_t)row[k] >= 12u;
+	if (__syncthreads_or(bad)) {                                         // reported; the queue comes back as it is
+		if (tid == 0) { pr[0] = SHORTEN_KEPT; *error = RK_EINVAL; }
+		return;
+	}
+	if (tid == 0) { cost[0] = 0; pr[0] = 0; }
+	__syncthreads();
+	for (int j = 1; j <= L; j++) {
+		const int8_t *dj = depth + (p * (size_t)max_len + (size_t)(j - 1)) * (size_t)window;
+		const int kmax = min(window, j);
+		uint32_t best = 0xFFFFFFFFu;
+		for (int k = tid + 1; k <= kmax; k += SHORTEN_DP_THREADS) {          // i = j - k
+			const int d = dj[k - 1];
+			const int wgt = d >= 0 ? d : k == 1 ? 1 : -1;                        // a single move outside the ball (radius 0) costs itself
+			if (wgt >= 0) best = min(best, (((uint32_t)cost[j - k] + (uint32_t)wgt) << 12) | (uint32_t)(k - 1));
+		}
+		#pragma unroll
+		for (int off = 32; off >= 1; off >>= 1) best = min(best, (uint32_t)__shfl_xor((int)best, off, 64));
+		if (lane == 0) part[j & 1][wave] = best;
+		__syncthreads();
+		if (tid == 0) {
+			uint32_t m = part[j & 1][0];
+			#pragma unroll
+			for (int v = 1; v < SHORTEN_DP_THREADS / 64; v++) m = min(m, part[j & 1][v]);
+			cost[j] = (uint16_t)(m >> 12);                                   // (k = 1 is always a candidate: m is a real key)
+			pr[j] = (uint16_t)(j - 1 - (int)(m & 0xFFFu));
+		}
+	}
+}
+
+// The rewritten queue of queue blockIdx.x: one wave.  Lane 0 turns the pred chain from L into a chain of successors from 0, then
+// the wave takes the edges in order.  An edge of weight j - i (or a single move outside the ball) is copied; any other is the
+// ball's word for X(i, j), d(i, j) moves.  The output is never longer than the input; every index is checked all the same.
+__global__ __launch_bounds__(64)
+void k_shorten_emit(BallView b, const int8_t *__restrict__ actions, const int32_t *__restrict__ len, int max_len, int window,
+                    const int8_t *__restrict__ depth, const uint16_t *__restrict__ pred, int8_t *__restrict__ out_actions,
+                    int32_t *__restrict__ out_len, int32_t *error)
+{
+	__shared__ u32x4 s_act[36];
+	__shared__ uint16_t nxt[SHORTEN_MAX_LEN + 1];
+	__shared__ int s_ok;
+	const size_t p = blockIdx.x;
+	const int lane = threadIdx.x;
+	stage_action_tables(s_act, lane);
+	const int L = shorten_len(len, p, max_len);
+	const int8_t *row = actions + p * (size_t)max_len;
+	int8_t *out = out_actions + p * (size_t)max_len;
+	const uint16_t *pr = pred + p * (size_t)(max_len + 1);
+	bool ok = pr[0] != SHORTEN_KEPT;
+	int pos = 0;
+	if (ok) {
+		for (int k = lane; k <= L; k += 64) nxt[k] = pr[k];
+		__syncthreads();
+		if (lane == 0) {
+			int good = 1;
+			int j = L, i = L > 0 ? nxt[L] : 0;
+			while (j > 0) {
+				if (i >= j || j - i > window) { good = 0; break; }              // (never: the DP wrote pred[j] in j - window .. j - 1)
+				const int ii = i > 0 ? nxt[i] : 0;
+				nxt[i] = (uint16_t)j;
+				j = i; i = ii;
+			}
+			s_ok = good;
+		}
+		__syncthreads();
+		ok = s_ok != 0;
+		for (int i = 0; ok && i < L; ) {
+			const int j = nxt[i], span = j - i;
+			if (span < 1 || span > window || j > L) { ok = false; break; }
+			const int d = depth[(p * (size_t)max_len + (size_t)(j - 1)) * (size_t)window + (size_t)(span - 1)];
+			if (d < 0 || d >= span) {                                        // as short as the ball knows: copied
+				if (pos + span > max_len) { ok = false; break; }
+				for (int k = lane; k < span; k += 64) out[pos + k] = row[i + k];
+				pos += span;
+			} else if (d > 0) {
+				uint32_t s[5] = {SOLVED_DW[0], SOLVED_DW[1], SOLVED_DW[2], SOLVED_DW[3], SOLVED_DW[4]};
+				for (int d0 = 0; d0 < span; d0 += 64) {
+					const int nc = min(64, span - d0);
+					const uint32_t a = lane < nc ? (uint32_t)(uint8_t)row[i + d0 + lane] : 0xFFu;
+					uint32_t st[5];
+					chunk_states(s_act, a, lane, nc, s, st);
+					#pragma unroll
+					for (int q = 0; q < 5; q++) s[q] = (uint32_t)__builtin_amdgcn_readlane((int)st[q], nc - 1);
+				}
+				uint32_t g = probe_find(b.table, b.mask, b.states, s);       // X(i, j): the same in every lane
+				if (g == 0u || ball_depth_of(b, g) != d || d > b.radius || pos + d > max_len) { ok = false; break; }
+				for (int k = d - 1; k >= 0; k--) {                              // the stored actions lead away from solved: the last one first
+					if (g <= 1u || g >= b.cap1) { ok = false; break; }
+					if (lane == 0) out[pos + k] = (int8_t)b.pact[g];
+					g = (uint32_t)b.parent[g];
+				}
+				if (!ok || g != 1u) { ok = false; break; }
+				pos += d;
+			}
+			i = j;
+		}
+		if (!ok && lane == 0) *error = RK_ESTATE;                           // an engine error: the queue comes back as it is
+	}
+	if (!ok) {
+		for (int k = lane; k < L; k += 64) out[k] = row[k];
+		pos = L;
+	}
+	for (int k = pos + lane; k < max_len; k += 64) out[k] = -1;
+	if (lane == 0) out_len[p] = pos;
 }
 
 // ---- the search from a start towards the ball -------------------------------------------------------------------------------
@@ -576,6 +770,11 @@ size_t ball_capacity(int radius)
 	return n;
 }
 
+constexpr size_t SHORTEN_MAX_WAVES = (size_t)1 << 30;    // queues x max_len of one rk_bshorten call: a wave each, four to a workgroup
+
+// the d(i, j) bytes of a call, rounded up so that the pred rows behind them are aligned
+size_t shorten_depth_bytes(size_t n, int max_len, int window) { return (n * (size_t)max_len * (size_t)window + 15) & ~(size_t)15; }
+
 uint32_t ball_table_mask(size_t capacity) { return (uint32_t)(table_slots(capacity, 1024) - 1); }
 
 int bsearch_read_ctr(rk_bsearch *h, int32_t *out, hipStream_t st) { return h->ctr_host.read(h->d.ctr, S_COUNT, out, st); }
@@ -709,6 +908,40 @@ int rk_ball_solve(rk_ball_t *h, const int8_t *d_states, size_t n, int32_t *d_len
 	if (!d_actions && h->d.radius > 0) return fail(RK_EINVAL, "rk_ball_solve: null pointer");
 	hipLaunchKernelGGL(k_ball_solve, dim3(blocks(n)), dim3(256), 0, (hipStream_t)stream, h->view,
 	                   reinterpret_cast<const uint32_t *>(d_states), n, d_lengths, d_actions);
+	RK_HIP(hipGetLastError());
+	return RK_OK;
+}
+
+long long rk_bshorten_scratch_bytes(size_t n, int max_len, int window)
+{
+	if (max_len < 1 || max_len > SHORTEN_MAX_LEN || window < 1 || window > max_len)
+		return fail(RK_EINVAL, "rk_bshorten_scratch_bytes: need 1 <= window <= max_len <= %d, got window %d, max_len %d", SHORTEN_MAX_LEN, window, max_len);
+	if (n > SHORTEN_MAX_WAVES / (size_t)max_len) return fail(RK_EINVAL, "rk_bshorten_scratch_bytes: %zu queues of %d moves in one call", n, max_len);
+	return (long long)(shorten_depth_bytes(n, max_len, window) + n * (size_t)(max_len + 1) * sizeof(uint16_t));
+}
+
+int rk_bshorten(rk_ball_t *h, const int8_t *d_actions, const int32_t *d_len, size_t n, int max_len, int window, int8_t *d_out_actions,
+                int32_t *d_out_len, int32_t *d_error, void *d_scratch, size_t scratch_bytes, void *stream)
+{
+	if (!h) return fail(RK_EINVAL, "rk_bshorten: null ball");
+	if (!h->built) return fail(RK_ESTATE, "rk_bshorten: build the ball first");
+	const long long need = rk_bshorten_scratch_bytes(n, max_len, window);
+	if (need < 0) return (int)need;
+	if (!d_error) return fail(RK_EINVAL, "rk_bshorten: null pointer");
+	if (n != 0 && (!d_actions || !d_len || !d_out_actions || !d_out_len || !d_scratch)) return fail(RK_EINVAL, "rk_bshorten: null pointer");
+	if (((uintptr_t)d_len | (uintptr_t)d_out_len | (uintptr_t)d_error) & 3u) return fail(RK_EINVAL, "rk_bshorten: device pointers must be 4-byte aligned");
+	if ((uintptr_t)d_scratch & 15u) return fail(RK_EINVAL, "rk_bshorten: the scratch must be 16-byte aligned");
+	if (n != 0 && d_actions == d_out_actions) return fail(RK_EINVAL, "rk_bshorten: the output may not be the input");
+	if (scratch_bytes < (size_t)need) return fail(RK_EINVAL, "rk_bshorten: %zu bytes of scratch, %lld needed", scratch_bytes, need);
+	hipStream_t st = (hipStream_t)stream;
+	RK_HIP(hipMemsetAsync(d_error, 0, sizeof(int32_t), st));
+	if (n == 0) return RK_OK;
+	int8_t *depth = static_cast<int8_t *>(d_scratch);
+	uint16_t *pred = reinterpret_cast<uint16_t *>(depth + shorten_depth_bytes(n, max_len, window));
+	hipLaunchKernelGGL(k_shorten_windows, dim3(blocks(n * (size_t)max_len, 4)), dim3(256), 0, st, h->view, d_actions, d_len, n, max_len, window, depth);
+	hipLaunchKernelGGL(k_shorten_dp, dim3((unsigned)n), dim3(SHORTEN_DP_THREADS), 0, st, d_actions, d_len, max_len, window, depth, pred, d_error);
+	hipLaunchKernelGGL(k_shorten_emit, dim3((unsigned)n), dim3(64), 0, st, h->view, d_actions, d_len, max_len, window, depth, pred, d_out_actions,
+	                   d_out_len, d_error);
 	RK_HIP(hipGetLastError());
 	return RK_OK;
 }

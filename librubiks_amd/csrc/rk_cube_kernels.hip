@@ -879,32 +879,7 @@ void k_apply_sequences(const uint8_t *__restrict__ actions, int moves, int games
 	if (worst >= 12u) atomicOr(&g_bad_actions, 1u);                      // never taken on valid input
 }
 
-// A move is a permutation of the 24 corner codes and of the 24 edge codes: a 48-byte table, twelve dwords.  Moves COMPOSE --
-// (B after A)[v] = B[A[v]], four codes per lut4 -- so the composition of consecutive moves is an inclusive prefix scan over lanes that hold
-// one move each: after the scan lane l holds the composition of the moves of lanes l0 ... l, l0 = the first lane of its segment (`seg` =
-// the lane's position inside its segment of length `len`: a game's rows, or a 64-move chunk of one long game).  log2(len) steps of twelve
-// cross-lane dwords and twelve lut4 each, all in registers.  All 64 lanes call it (ds_bpermute).
-__device__ __forceinline__ void scan_moves(uint32_t (&X)[12], int lane, int seg, int len)
-{
-	for (int off = 1; off < len; off <<= 1) {
-		uint32_t Y[12];
-		const int src = (lane - off) & 63;
-		#pragma unroll
-		for (int j = 0; j < 12; j++) Y[j] = (uint32_t)__builtin_amdgcn_ds_bpermute(src << 2, (int)X[j]);
-		if (seg >= off) {                                                // the lane `off` back belongs to the SAME segment
-			uint32_t Z[12];
-			#pragma unroll
-			for (int j = 0; j < 6; j++) { Z[j] = lut4(Y[j], X); Z[6 + j] = lut4(Y[6 + j], X + 6); }   // the earlier moves first, then mine
-			#pragma unroll
-			for (int j = 0; j < 12; j++) X[j] = Z[j];
-		}
-	}
-}
-__device__ __forceinline__ void identity_moves(uint32_t (&X)[12])
-{
-	#pragma unroll
-	for (int j = 0; j < 6; j++) X[j] = X[6 + j] = 0x03020100u + 0x04040404u * (uint32_t)j;
-}
+// (scan_moves and identity_moves, the prefix scan over the moves' permutation tables: rk_device.h, shared with rk_ball.hip)
 
 // The scramblers for FEW games (one `scramble(depth)` of the evaluation loop, depth 100-999; `sequence_scrambler` of a few thousand
 // games): a WAVE per game, lane l holds move d0 + l of a 64-move chunk, the chunk's states come out of one scan_moves, the last one

@@ -89,6 +89,33 @@ __device__ __forceinline__ void load_action_table(const u32x4 *lds, uint32_t a, 
 	tab[8] = r2.x; tab[9] = r2.y; tab[10] = r2.z; tab[11] = r2.w;
 }
 
+// A move is a permutation of the 24 corner codes and of the 24 edge codes: a 48-byte table, twelve dwords.  Moves COMPOSE --
+// (B after A)[v] = B[A[v]], four codes per lut4 -- so the composition of consecutive moves is an inclusive prefix scan over lanes that hold
+// one move each: after the scan lane l holds the composition of the moves of lanes l0 ... l, l0 = the first lane of its segment (`seg` =
+// the lane's position inside its segment of length `len`: a game's rows, or a 64-move chunk of one long game).  log2(len) steps of twelve
+// cross-lane dwords and twelve lut4 each, all in registers.  All 64 lanes call it (ds_bpermute).
+__device__ __forceinline__ void scan_moves(uint32_t (&X)[12], int lane, int seg, int len)
+{
+	for (int off = 1; off < len; off <<= 1) {
+		uint32_t Y[12];
+		const int src = (lane - off) & 63;
+		#pragma unroll
+		for (int j = 0; j < 12; j++) Y[j] = (uint32_t)__builtin_amdgcn_ds_bpermute(src << 2, (int)X[j]);
+		if (seg >= off) {                                                // the lane `off` back belongs to the SAME segment
+			uint32_t Z[12];
+			#pragma unroll
+			for (int j = 0; j < 6; j++) { Z[j] = lut4(Y[j], X); Z[6 + j] = lut4(Y[6 + j], X + 6); }   // the earlier moves first, then mine
+			#pragma unroll
+			for (int j = 0; j < 12; j++) X[j] = Z[j];
+		}
+	}
+}
+__device__ __forceinline__ void identity_moves(uint32_t (&X)[12])
+{
+	#pragma unroll
+	for (int j = 0; j < 6; j++) X[j] = X[6 + j] = 0x03020100u + 0x04040404u * (uint32_t)j;
+}
+
 // LDS traffic between lanes of ONE wave needs no s_barrier (a wave's DS operations execute in order); this only
 // stops the compiler from moving LDS accesses across the hand-off.
 __device__ __forceinline__ void wave_lds_fence()

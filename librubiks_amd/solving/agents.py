@@ -645,6 +645,70 @@ class DeviceGoalBall(_ffi.Owner):
 			self._cache = {is2024: (_states_out(is2024, states, n)[1:], parents[1:], actions[1:])}
 		return self._cache[is2024]
 
+	MAX_QUEUE = 4096                        # rk_bshorten's longest queue
+	shorten_scratch_bytes = 256 << 20       # the most scratch one rk_bshorten call is given; a batch is cut into calls to fit
+
+	def shorten(self, action_queues, window: int = None, passes: int = None) -> list:
+		"""
+		Every action queue (a sequence of actions 0..11, at most 4096 of them; any agent's solution) made locally optimal against
+		the ball, on the device (engine rk_bshorten_*): a list of int64 arrays, each no longer than its queue and with the same
+		effect on any state.  Neither start states nor a net are needed: the moves i .. j-1 of a queue, applied to the solved state,
+		give a state whose ball depth is the distance between the queue's states i and j, so every window of at most `window` moves
+		is looked up in the ball, and the best set of replacements by the ball's own words is a shortest path through a small DAG
+		(DESIGN 3.58).  A pass runs on all queues, further passes on those that got shorter, until none does or `passes` passes are
+		done.  Then every window of at most `window` moves whose net effect the ball holds has exactly that state's depth in moves.
+		`window=None`: every window of every queue.
+		"""
+		queues = [np.asarray(q, dtype=np.int64).reshape(-1) for q in action_queues]
+		if window is not None and (isinstance(window, bool) or int(window) != window or int(window) < 1):
+			raise ValueError(f"window must be an integer >= 1 or None, got {window!r}")
+		if passes is not None and (isinstance(passes, bool) or int(passes) != passes or int(passes) < 0):
+			raise ValueError(f"passes must be an integer >= 0 or None, got {passes!r}")
+		for q in queues:
+			if len(q) > self.MAX_QUEUE:
+				raise ValueError(f"an action queue of {len(q)} moves: at most {self.MAX_QUEUE}")
+			if len(q) and not (0 <= q.min() and q.max() < 12):
+				raise ValueError("actions must be in 0..11")
+		self.build()
+		lib, stream = _ffi.lib(), _ffi.stream_ptr()
+		active = [i for i, q in enumerate(queues) if len(q)]
+		done = 0
+		while active and (passes is None or done < passes):
+			longest = max(len(queues[i]) for i in active)
+			w = longest if window is None else min(int(window), longest)
+			per_queue = longest * w + 2 * (longest + 1)
+			step = max(1, self.shorten_scratch_bytes // per_queue)
+			shorter = []
+			for at in range(0, len(active), step):
+				part = active[at:at + step]
+				n = len(part)
+				max_len = max(len(queues[i]) for i in part)
+				wc = max_len if window is None else min(int(window), max_len)
+				acts = np.full((n, max_len), -1, np.int8)
+				for r, i in enumerate(part):
+					acts[r, :len(queues[i])] = queues[i]
+				lens = np.array([len(queues[i]) for i in part], np.int32)
+				need = lib.rk_bshorten_scratch_bytes(n, max_len, wc)
+				if need < 0:
+					_ffi.check(need)
+				d_acts, d_lens = torch.from_numpy(acts).to(gpu), torch.from_numpy(lens).to(gpu)
+				d_out = torch.empty((n, max_len), dtype=torch.int8, device=gpu)
+				d_out_len = torch.empty(n, dtype=torch.int32, device=gpu)
+				d_err = torch.empty(1, dtype=torch.int32, device=gpu)
+				scratch = torch.empty(need, dtype=torch.uint8, device=gpu)
+				_ffi.check(lib.rk_bshorten(self._h, d_acts.data_ptr(), d_lens.data_ptr(), n, max_len, wc, d_out.data_ptr(),
+				                           d_out_len.data_ptr(), d_err.data_ptr(), scratch.data_ptr(), need, stream))
+				out, out_len, err = d_out.cpu().numpy(), d_out_len.cpu().numpy(), int(d_err.item())
+				if err:
+					raise _ffi.RubiksHipError(f"rk_bshorten reported error {err} for queues that passed the host's checks")
+				for r, i in enumerate(part):
+					if out_len[r] < len(queues[i]):
+						shorter.append(i)
+					queues[i] = out[r, :out_len[r]].astype(np.int64)
+			active = [i for i in shorter if len(queues[i])]
+			done += 1
+		return queues
+
 	def depth_of_node(self, node: int) -> int:
 		"""The depth of node `node` (1 .. len(ball)), from the level boundaries."""
 		return int(np.searchsorted(self.level_start, node, side="right")) - 1
