@@ -498,6 +498,56 @@ int rk_bsearchb_paths(rk_bsearchb_t *h, int32_t *h_out, int max_len, void *strea
 int rk_bsearchb_export(rk_bsearchb_t *h, int slot, size_t first, size_t count, int8_t *h_states, long long *h_parents,
                        long long *h_actions, void *stream);
 
+/* ---- the 48 symmetries of the cube: conjugates and canonical representatives (rk_sym_*) ------------------------------------
+ * A face is 2 * axis + side (F B | T D | L R).  Symmetry s = 8 * p + m sends axis ax to P[p][ax], P = the six permutations of
+ * 0 1 2 in lexicographic order, and swaps the two faces of source axis ax when bit ax of m is set; s = 0 is the identity.  A
+ * symmetry relabels the actions (a turn of face f becomes a turn of its image, in the opposite sense under a reflection) and the
+ * relabelling keeps the distance to solved.  The conjugate of a 20-byte state x is
+ *     conj_s(x)[c] = map[s][c][x[src[s][c]]]            conj_s(rotate(x, a)) = rotate(conj_s(x), actions[s][a])
+ * and the canonical representative of x the smallest of its 48 conjugates, compared as the tuple of the state's five
+ * little-endian dwords, dword 0 first.  All tables are derived from the face definitions and the move table at compile time. */
+/* HOST: actions uint8 (48, 12), src uint8 (48, 20), map uint8 (48, 20, 24); any may be NULL, not all.  Touches no device. */
+int rk_sym_tables(uint8_t *h_actions, uint8_t *h_src, uint8_t *h_map);
+/* Of every DEVICE state of d_states int8 (n, 20): d_rep int8 (n, 20) the representative, d_sym uint8 (n) the lowest symmetry
+ * that gives it, d_orbit uint8 (n) the size of the state's orbit = 48 / the number of symmetries that give it.  Any output may
+ * be NULL.  One launch, a wave per state; stream-ordered, no synchronisation. */
+int rk_sym_canonical(const int8_t *d_states, size_t n, int8_t *d_rep, uint8_t *d_sym, uint8_t *d_orbit, void *stream);
+/* d_out int8 (n, 20) = conj_sym of every DEVICE state of d_states, sym 0..47.  One launch; stream-ordered. */
+int rk_sym_conjugate(const int8_t *d_states, size_t n, int sym, int8_t *d_out, void *stream);
+
+/* ---- the symmetry-reduced goal ball: one representative per orbit (rk_symball_*) -------------------------------------------
+ * The canonical representatives of the states within `radius` quarter turns of solved, built once and kept in HBM; the depth of
+ * a representative is the depth of the up to 48 states of its orbit.  Node 1 is the solved state, the pool is in index order: a
+ * level's representatives are popped in index order, never across a level boundary, their children taken in action order 0..11
+ * and canonicalised; a representative the pool holds is skipped, every other is appended.  Level `radius` is stored and never
+ * expanded; level l is the index range level_start[l] .. level_start[l + 1] - 1.  There are no parents and no actions: a
+ * solution is found by descent.  The orbit sizes of every level are added up; the sums of levels 0..8 are checked against the
+ * level sizes of the graph (see rk_ball_*), those of levels 9 and 10 are only reported.  The pool does not depend on `pops`. */
+typedef struct rk_symball rk_symball_t;
+/* radius 0..10; pops 1..2^22; capacity: orbits the pool can hold, 0 = the sum over the levels of ceil(level size / 48 * 1.02)
+ * + 64.  Allocates nothing. */
+int rk_symball_create(rk_symball_t **out, int radius, int pops, size_t capacity);
+int rk_symball_destroy(rk_symball_t *h);
+/* Builds the ball (nothing if it is built): iterations of five launches, the host looks every `poll` of them.  An iteration pops
+ * only as many representatives as fit the pool whatever their children are; when not one fits, the build stops before that
+ * iteration with RK_ECAPACITY (nothing is written out of bounds, the ball stays unbuilt and its arrays are freed).  RK_ECAPACITY
+ * also when the device has no room; a level whose orbit sizes do not add up is an engine error (RK_ESTATE).  Synchronises. */
+int rk_symball_build(rk_symball_t *h, int poll, void *stream);
+/* h_status[32] = built, orbits stored, iterations of the build, radius, capacity, table slots, level_start[0 .. 11] (zeros
+ * before the build and beyond radius + 1), then at [18 .. 28] the orbit sizes of levels 0 .. 10 added up.  Touches no device. */
+int rk_symball_status(rk_symball_t *h, long long *h_status);
+/* Rows [first, first+count) of the pool to HOST h_states int8 (count, 20). */
+int rk_symball_export(rk_symball_t *h, size_t first, size_t count, int8_t *h_states, void *stream);
+/* d_depth[q] = exact distance to solved of DEVICE state q of d_states int8 (n, 20), -1 for a state outside the ball.  One
+ * launch, a wave per query, nothing of the ball is written; stream-ordered, no synchronisation. */
+int rk_symball_depth(rk_symball_t *h, const int8_t *d_states, size_t n, int32_t *d_depth, void *stream);
+/* A shortest solution of every DEVICE state of d_states by descent -- at each step the lowest action whose child lies one level
+ * nearer --: d_lengths[q] moves (-1 outside the ball), row q of d_actions int8 (n, radius) holds them, padded with -1.
+ * d_error[0] is cleared, then set to RK_ESTATE if a state inside the ball has no such child (its length is -1 then; never in a
+ * ball that passed its build).  One launch; stream-ordered, no synchronisation. */
+int rk_symball_solve(rk_symball_t *h, const int8_t *d_states, size_t n, int32_t *d_lengths, int8_t *d_actions, int32_t *d_error,
+                     void *stream);
+
 /* ---- device-resident epsilon-greedy value maximisation (agents.py:649-726) ---------------------------------------
  * W = workers walkers take D = depth moves from a root (:692-715); the visited state with the best value becomes the next
  * root (:673-677) until a walker is solved (:710-713) or another round would pass max_states (:665).  The root, the

@@ -126,6 +126,16 @@ SIGNATURES = {
 	"rk_bsearchb_status": (_i, [_vp, _vp, _vp]),
 	"rk_bsearchb_paths": (_i, [_vp, _vp, _i, _vp]),
 	"rk_bsearchb_export": (_i, [_vp, _i, _sz, _sz, _vp, _vp, _vp, _vp]),
+	"rk_sym_tables": (_i, [_vp, _vp, _vp]),
+	"rk_sym_canonical": (_i, [_vp, _sz, _vp, _vp, _vp, _vp]),
+	"rk_sym_conjugate": (_i, [_vp, _sz, _i, _vp, _vp]),
+	"rk_symball_create": (_i, [C.POINTER(_vp), _i, _i, _sz]),
+	"rk_symball_destroy": (_i, [_vp]),
+	"rk_symball_build": (_i, [_vp, _i, _vp]),
+	"rk_symball_status": (_i, [_vp, _vp]),
+	"rk_symball_export": (_i, [_vp, _sz, _sz, _vp, _vp]),
+	"rk_symball_depth": (_i, [_vp, _vp, _sz, _vp, _vp]),
+	"rk_symball_solve": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp]),
 	"rk_egvm_create": (_i, [C.POINTER(_vp), _i, _i, _i]),
 	"rk_egvm_destroy": (_i, [_vp]),
 	"rk_egvm_net_in": (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_sz)]),

@@ -24,6 +24,7 @@ FLAGS = [
 	"--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
 	"-ffp-contract=off",          # search statistics must round like NumPy (no fused multiply-add)
 	"-Wall", "-Wno-unused-function",
+	"-fconstexpr-steps=100000000",  # csrc/rk_sym_tables.h derives the 48 symmetries at compile time (the default limit is 2^20 steps)
 	"-Wl,-rpath,/opt/rocm/lib",
 ]
 

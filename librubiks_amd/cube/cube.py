@@ -518,6 +518,74 @@ def as2024(states686: np.ndarray) -> np.ndarray:
 	return out[0] if one else out
 
 
+##############
+# Symmetries #   (csrc/rk_sym_tables.h; not in the reference)
+##############
+N_SYMMETRIES = 48
+
+
+def sym_tables():
+	"""(actions (48, 12), src (48, 20), map (48, 20, 24)) uint8: the library's symmetry tables.  Symmetry s = 8 p + m sends axis ax
+	(faces 2 ax, 2 ax + 1) to the ax-th entry of the p-th permutation of 0 1 2 (lexicographic) and swaps the two faces of source
+	axis ax when bit ax of m is set; conj_s(x)[c] = map[s][c][x[src[s][c]]].  Needs no GPU."""
+	act, src, m = np.empty((48, 12), np.uint8), np.empty((48, 20), np.uint8), np.empty((48, 20, 24), np.uint8)
+	_ffi.check(_ffi.lib().rk_sym_tables(act.ctypes.data, src.ctypes.data, m.ctypes.data))
+	return act, src, m
+
+
+def sym_actions() -> np.ndarray:
+	"""int64 (48, 12): symmetry s relabels action a as sym_actions()[s, a]; conjugate(rotate(x, a), s) = rotate(conjugate(x, s), that)."""
+	return sym_tables()[0].astype(np.int64)
+
+
+def _rows2024(states) -> np.ndarray:
+	"""States in the current representation as (n, 20) int8 rows (ValueError for a shape that is none, or an illegal 6x8x6 state)."""
+	arr = np.asarray(states, dtype=np.int8)
+	width = 20 if _is2024 else 288
+	if arr.size % width or (arr.ndim and arr.shape[-1] != (20 if _is2024 else 6)):
+		raise ValueError(f"states must be (n, 20), or (n, 6, 8, 6) in 6x8x6 mode, got shape {arr.shape}")
+	n = arr.size // width
+	if _is2024:
+		return np.ascontiguousarray(arr).reshape(n, 20)
+	return np.ascontiguousarray(as2024(arr.reshape(n, 6, 8, 6))).reshape(n, 20)
+
+
+def _rows_out(rows20: np.ndarray) -> np.ndarray:
+	return rows20 if _is2024 else as686(rows20).reshape(len(rows20), 6, 8, 6)
+
+
+def canonical(states):
+	"""(reps, syms int64 (n,), orbit_sizes int64 (n,)) of n states in the current representation: the smallest of each state's 48
+	conjugates -- compared as the tuple of the 20-byte state's five little-endian dwords --, the lowest symmetry that gives it,
+	and the number of distinct conjugates.  One launch, a wave per state (engine rk_sym_canonical)."""
+	_ffi.require_gpu()
+	rows = _rows2024(states)
+	n = len(rows)
+	if n == 0:
+		return _rows_out(rows), np.zeros(0, np.int64), np.zeros(0, np.int64)
+	q = torch.from_numpy(rows).to(gpu)
+	rep = torch.empty((n, 20), dtype=torch.int8, device=gpu)
+	sym = torch.empty(n, dtype=torch.uint8, device=gpu)
+	orbit = torch.empty(n, dtype=torch.uint8, device=gpu)
+	_ffi.check(_ffi.lib().rk_sym_canonical(q.data_ptr(), n, rep.data_ptr(), sym.data_ptr(), orbit.data_ptr(), _ffi.stream_ptr()))
+	return _rows_out(_to_host(rep)), sym.cpu().numpy().astype(np.int64), orbit.cpu().numpy().astype(np.int64)
+
+
+def conjugate(states, sym: int):
+	"""The conjugates of n states in the current representation under symmetry `sym` (0..47, 0 = the identity)."""
+	if isinstance(sym, bool) or int(sym) != sym or not 0 <= int(sym) < N_SYMMETRIES:
+		raise ValueError(f"sym must be an integer in 0..{N_SYMMETRIES - 1}, got {sym!r}")
+	_ffi.require_gpu()
+	rows = _rows2024(states)
+	n = len(rows)
+	if n == 0:
+		return _rows_out(rows)
+	q = torch.from_numpy(rows).to(gpu)
+	out = torch.empty((n, 20), dtype=torch.int8, device=gpu)
+	_ffi.check(_ffi.lib().rk_sym_conjugate(q.data_ptr(), n, int(sym), out.data_ptr(), _ffi.stream_ptr()))
+	return _rows_out(_to_host(out))
+
+
 ################
 # Rotate logic #   (cube.py:41-52)
 ################

@@ -717,6 +717,126 @@ class DeviceGoalBall(_ffi.Owner):
 		return f"Goal ball (device, radius={self.radius})"
 
 
+class DeviceSymBall(_ffi.Owner):
+	"""
+	The goal ball reduced by the 48 whole-cube symmetries (engine rk_symball_*, csrc/rk_sym.hip): one canonical representative
+	(`cube.canonical`) per orbit of the states within `radius` quarter turns of solved.  Conjugation keeps the distance to solved,
+	so a representative's depth is the depth of the up to 48 states of its orbit; nearly every orbit has 48.  Node 1 is the solved
+	state; a level's representatives are popped in index order, their children taken in action order and canonicalised, a
+	representative the pool holds is skipped, any other appended.  Level l is the index range `level_start[l] ..
+	level_start[l + 1] - 1`.  The pool holds states only -- no parents, no actions: `solve` descends, at each step the lowest
+	action whose child lies one level nearer.  The pool does not depend on `pops`.
+
+	`capacity` is the number of orbits the pool can hold (None: the sum over the levels of ceil(level size / 48 * 1.02) + 64);
+	a build that does not fit stops cleanly with a RubiksHipError (RK_ECAPACITY).  `states_covered[l]` is the sum of the orbit
+	sizes of level l: the number of states of the plain ball's level (checked by the engine for levels 0..8).  States are in the
+	representation cube.get_is2024() names when a method is called.
+	"""
+	LEVELS = DeviceGoalBall.LEVELS                                  # states at distance 0 .. 8: what states_covered is checked against
+	MAX_RADIUS = 10
+	MAX_POPS = 1 << 22                      # rk_symball_create's limit
+	MAX_CAPACITY = 0x3FFFFFF0
+	poll = 8                                # iterations of the build between two looks of the host
+
+	def __init__(self, radius: int, pops: int = 16_384, capacity: int = None):
+		if isinstance(radius, bool) or int(radius) != radius or not 0 <= int(radius) <= self.MAX_RADIUS:
+			raise ValueError(f"radius must be an integer in 0..{self.MAX_RADIUS}, got {radius!r}")
+		if isinstance(pops, bool) or int(pops) != pops or not 1 <= int(pops) <= self.MAX_POPS:
+			raise ValueError(f"pops must be an integer in 1..{self.MAX_POPS}, got {pops!r}")
+		if capacity is not None and (isinstance(capacity, bool) or int(capacity) != capacity or not 1 <= int(capacity) <= self.MAX_CAPACITY):
+			raise ValueError(f"capacity must be an integer in 1..{self.MAX_CAPACITY} or None, got {capacity!r}")
+		self.radius, self.pops = int(radius), int(pops)
+		self.capacity = None if capacity is None else int(capacity)
+		self._h = None
+		self._n = 0
+		self._level_start = None
+		self._covered = None
+		self._cache = {}
+		self.iterations = 0                 # of the build
+
+	@property
+	def built(self) -> bool:
+		return self._level_start is not None
+
+	def build(self):
+		"""Builds the ball on the device (nothing if it is built)."""
+		if self.built:
+			return self
+		_ffi.require_gpu()
+		lib = _ffi.lib()
+		if self._h is None:
+			self._create("rk_symball_create", "rk_symball_destroy", self.radius, self.pops, self.capacity or 0)
+		_ffi.check(lib.rk_symball_build(self._h, self.poll, _ffi.stream_ptr()))
+		status = (C.c_longlong * 32)()
+		_ffi.check(lib.rk_symball_status(self._h, status))
+		self._n, self.iterations, self.capacity = int(status[1]), int(status[2]), int(status[4])
+		self._level_start = np.array(status[6:6 + self.radius + 2], np.int64)
+		self._covered = np.array(status[18:18 + self.radius + 1], np.int64)
+		return self
+
+	@property
+	def level_start(self) -> np.ndarray:
+		"""int64 (radius + 2,): level l holds the nodes level_start[l] .. level_start[l + 1] - 1."""
+		return self.build()._level_start
+
+	@property
+	def states_covered(self) -> np.ndarray:
+		"""int64 (radius + 1,): the orbit sizes of every level added up = the states at that distance from solved."""
+		return self.build()._covered
+
+	def __len__(self):
+		return self.build()._n
+
+	def _queries(self, states):
+		rows = cube.cube._rows2024(states)                   # ValueError for an illegal 6x8x6 state
+		return rows, len(rows)
+
+	def depth(self, states) -> np.ndarray:
+		"""int64 (n,): the exact distance to solved of every state whose orbit the ball holds, -1 for the others.  One launch."""
+		self.build()
+		rows, n = self._queries(states)
+		if n == 0:
+			return np.zeros(0, np.int64)
+		q = torch.from_numpy(rows).to(gpu)
+		out = torch.empty(n, dtype=torch.int32, device=gpu)
+		_ffi.check(_ffi.lib().rk_symball_depth(self._h, q.data_ptr(), n, out.data_ptr(), _ffi.stream_ptr()))
+		return out.cpu().numpy().astype(np.int64)
+
+	def solve(self, states):
+		"""(lengths int64 (n,), actions int64 (n, radius)): a shortest solution of every state whose orbit the ball holds -- at each
+		step the lowest action that gets one level nearer --, rows padded with -1; length -1 for a state outside.  One launch."""
+		self.build()
+		rows, n = self._queries(states)
+		if n == 0:
+			return np.zeros(0, np.int64), np.zeros((0, self.radius), np.int64)
+		q = torch.from_numpy(rows).to(gpu)
+		lengths = torch.empty(n, dtype=torch.int32, device=gpu)
+		actions = torch.empty((n, max(self.radius, 1)), dtype=torch.int8, device=gpu)
+		err = torch.empty(1, dtype=torch.int32, device=gpu)
+		_ffi.check(_ffi.lib().rk_symball_solve(self._h, q.data_ptr(), n, lengths.data_ptr(), actions.data_ptr(), err.data_ptr(),
+		                                       _ffi.stream_ptr()))
+		if int(err.item()):
+			raise _ffi.RubiksHipError(f"rk_symball_solve reported error {int(err.item())}: a state of the ball has no child one level nearer")
+		return lengths.cpu().numpy().astype(np.int64), actions.cpu().numpy().astype(np.int64)[:, :self.radius]
+
+	def arrays(self):
+		"""The representatives of nodes 1 .. len(ball) in index order."""
+		is2024 = cube.get_is2024()
+		if is2024 not in self._cache:
+			n = len(self)
+			states = np.zeros((n + 1, 20), np.int8)
+			_ffi.check(_ffi.lib().rk_symball_export(self._h, 1, n, states[1:].ctypes.data, _ffi.stream_ptr()))
+			self._cache = {is2024: _states_out(is2024, states, n)[1:]}
+		return self._cache[is2024]
+
+	def depth_of_node(self, node: int) -> int:
+		"""The depth of node `node` (1 .. len(ball)), from the level boundaries."""
+		return int(np.searchsorted(self.level_start, node, side="right")) - 1
+
+	def __str__(self):
+		return f"Symmetry-reduced goal ball (device, radius={self.radius})"
+
+
 class DeviceBallSearch(Agent, _ffi.Owner):
 	"""
 	A SHORTEST solution (quarter-turn metric) by a one-sided breadth-first search from the start that ends at the first child a
