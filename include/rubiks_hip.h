@@ -527,6 +527,7 @@ typedef struct rk_symball rk_symball_t;
 /* radius 0..10; pops 1..2^22; capacity: orbits the pool can hold, 0 = the sum over the levels of ceil(level size / 48 * 1.02)
  * + 64.  Allocates nothing. */
 int rk_symball_create(rk_symball_t **out, int radius, int pops, size_t capacity);
+/* RK_ESTATE while a search (rk_ssearch_*) is attached to the ball. */
 int rk_symball_destroy(rk_symball_t *h);
 /* Builds the ball (nothing if it is built): iterations of five launches, the host looks every `poll` of them.  An iteration pops
  * only as many representatives as fit the pool whatever their children are; when not one fits, the build stops before that
@@ -547,6 +548,42 @@ int rk_symball_depth(rk_symball_t *h, const int8_t *d_states, size_t n, int32_t 
  * ball that passed its build).  One launch; stream-ordered, no synchronisation. */
 int rk_symball_solve(rk_symball_t *h, const int8_t *d_states, size_t n, int32_t *d_lengths, int8_t *d_actions, int32_t *d_error,
                      void *stream);
+
+/* ---- shortest solutions by a one-sided breadth-first search from the start that ends at the symmetry ball (rk_ssearch_*) ----
+ * rk_bsearch_* with one difference: "the ball holds this child" is "the symmetry ball holds the child's canonical
+ * representative".  The own pool holds RAW states with parent and action (node 1 = the start); a child the own pool holds is
+ * skipped, a child whose ORBIT the ball holds is the meeting -- the search ends (won), the child is not stored, the lowest batch
+ * position wins --, any other is appended; the budget is checked before every pop.  A state lies in the plain ball of radius R
+ * exactly when its representative lies in the symmetry ball of radius R, so the own pool, the complete levels, the nodes popped,
+ * the iterations and the meeting child are those of rk_bsearch_* on a plain ball of the same radius; the ball's half of the
+ * path is found by descent and has the same length.  An iteration is five launches: a wave per child for the canonical form and
+ * the read-only probe of the ball, then rk_bsearch's four.  Entry for entry, arguments, limits, return codes and the status
+ * words are rk_bsearch_*'s; several searches may share one ball; a handle is not thread-safe. */
+typedef struct rk_ssearch rk_ssearch_t;
+/* capacity: size C (>= 2) of the own pool, whose table is sized to it; pops 1..2^22.  RK_ESTATE if the ball is not built (the
+ * search holds the built ball's arrays); attaches to `ball`: rk_symball_destroy refuses meanwhile. */
+int rk_ssearch_create(rk_ssearch_t **out, rk_symball_t *ball, size_t capacity, int pops);
+int rk_ssearch_destroy(rk_ssearch_t *h);
+/* Node 1 = the host 20-byte start state, with the state budget max_states.  Clears the own table, never the ball's.  A start
+ * whose orbit the ball holds is answered here, without a pop.  Synchronises. */
+int rk_ssearch_reset(rk_ssearch_t *h, const int8_t *h_start_state, long long max_states, void *stream);
+/* As rk_bsearch_run, five launches per iteration. */
+int rk_ssearch_run(rk_ssearch_t *h, int iterations, void *stream);
+/* Synchronises; h_status[10] as rk_bsearch_status; the meeting node is the node of the REPRESENTATIVE of the meeting child (or
+ * of the start) in the symmetry ball. */
+int rk_ssearch_status(rk_ssearch_t *h, long long *h_status, void *stream);
+/* Grows the own pool to new_capacity states in place between iterations, as rk_bsearch_grow. */
+int rk_ssearch_grow(rk_ssearch_t *h, size_t new_capacity, void *stream);
+/* Number of stored states of the own pool.  Synchronises. */
+long long rk_ssearch_size(const rk_ssearch_t *h);
+/* Rows [first, first+count) of the own pool to HOST buffers (any may be NULL), as rk_bsearch_export. */
+int rk_ssearch_export(rk_ssearch_t *h, size_t first, size_t count, int8_t *h_states, long long *h_parents, long long *h_actions,
+                      void *stream);
+/* The action queue of a search that met, start -> solved: the path to the popped parent, the meeting action, then the descent
+ * from the meeting state through the ball -- at each step the lowest action whose child's representative lies one level nearer,
+ * at most `radius` steps; walked on the device by one wave.  Returns its length or a negative error (RK_ESTATE: not met, or a
+ * state on the way down has no such child); writes at most max_len actions. */
+long long rk_ssearch_path(rk_ssearch_t *h, long long *h_actions, size_t max_len, void *stream);
 
 /* ---- device-resident epsilon-greedy value maximisation (agents.py:649-726) ---------------------------------------
  * W = workers walkers take D = depth moves from a root (:692-715); the visited state with the best value becomes the next

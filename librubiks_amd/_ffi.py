@@ -136,6 +136,15 @@ SIGNATURES = {
 	"rk_symball_export": (_i, [_vp, _sz, _sz, _vp, _vp]),
 	"rk_symball_depth": (_i, [_vp, _vp, _sz, _vp, _vp]),
 	"rk_symball_solve": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+	"rk_ssearch_create": (_i, [C.POINTER(_vp), _vp, _sz, _i]),
+	"rk_ssearch_destroy": (_i, [_vp]),
+	"rk_ssearch_reset": (_i, [_vp, _vp, C.c_longlong, _vp]),
+	"rk_ssearch_run": (_i, [_vp, _i, _vp]),
+	"rk_ssearch_status": (_i, [_vp, _vp, _vp]),
+	"rk_ssearch_grow": (_i, [_vp, _sz, _vp]),
+	"rk_ssearch_size": (C.c_longlong, [_vp]),
+	"rk_ssearch_export": (_i, [_vp, _sz, _sz, _vp, _vp, _vp, _vp]),
+	"rk_ssearch_path": (C.c_longlong, [_vp, _vp, _sz, _vp]),
 	"rk_egvm_create": (_i, [C.POINTER(_vp), _i, _i, _i]),
 	"rk_egvm_destroy": (_i, [_vp]),
 	"rk_egvm_net_in": (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_sz)]),

@@ -31,12 +31,25 @@
 //   k_sb_depth    a wave per query: canonical form, read-only probe (probe_find), depth from the level boundaries; -1 outside
 //   k_sb_solve    the same, then the descent: at each step the lowest action whose child lies one level nearer (12 canonical
 //                 forms and probes at most), bounded by the radius; a step without such a child sets the error word
+//
+// The search (rk_ssearch_*) is rk_ball.hip's rk_bsearch_* -- a one-sided breadth-first search from a start, in a pool and table of
+// its own that hold RAW states with parent and action -- with one difference: "the ball holds this child" is "the symmetry ball
+// holds this child's representative".  A state lies in the plain ball of radius R exactly when its representative lies in this
+// one, so the own pool, the depth, the pops and the meeting child are rk_bsearch's on a plain ball of the same radius, bit for
+// bit.  The election among the children of a batch is on the raw child, so no representative goes to scratch: a canonical form
+// takes a wave, the election a thread, hence one launch more than rk_bsearch, the rest is shared (rk_bsearch_dev.h)
+//   k_ss_probe    a wave per child: fan-out, canonical form, read-only probe of the ball  -> hit (12 P): the ball's node or 0
+//   k_ss_expand   a thread per child: hit != 0 is a meeting (atomicMin on the win position, no claim), else membership / election
+//                 in the own table on the raw child
+//   k_ss_scan, k_ss_append, k_ss_end   bsearch_scan, bsearch_append, bsearch_end; S_MEET is the node in THIS ball
+//   k_ss_walk     one wave: the own path and the meeting action, then the descent from the meeting state (sb_descend)
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <climits>
 #include <cstring>
 
 #include "../../include/rubiks_hip.h"
+#include "rk_bsearch_dev.h"
 #include "rk_device.h"
 #include "rk_error.h"
 #include "rk_search_dev.h"
@@ -45,7 +58,6 @@
 
 namespace rk {
 
-constexpr int SB_MAX_RADIUS = 10;
 constexpr int SB_CHECKED = 8;                       // the last level whose size is compared
 // states at distance 0 .. 8 from solved in the quarter-turn metric (rk_ball.hip: BALL_LEVELS)
 constexpr long long SB_LEVELS[SB_CHECKED + 1] = {1, 12, 114, 1068, 10011, 93840, 878880, 8221632, 76843595};
@@ -71,22 +83,6 @@ struct SymBallDev {
 	uint32_t *slot; int32_t *rank; uint8_t *first;
 	unsigned long long *chain;
 };
-
-// What the readers of a built ball get, by value.
-struct SymBallView {
-	uint32_t mask, cap1;
-	int radius;
-	int32_t lstart[SB_MAX_RADIUS + 2];          // level l = lstart[l] .. lstart[l + 1] - 1; INT32_MAX beyond radius + 1
-	const uint32_t *states; const uint32_t *table;
-};
-
-__device__ __forceinline__ int sb_depth_of(const SymBallView &b, uint32_t idx)
-{
-	int depth = 0;
-	#pragma unroll
-	for (int l = 1; l <= SB_MAX_RADIUS; l++) depth += (int32_t)idx >= b.lstart[l] ? 1 : 0;
-	return depth;
-}
 
 // After the pops of an iteration (or the root): the end of a level with its check, the end of the build, the next P.  One thread.
 __device__ __forceinline__ void sb_next(const SymBallDev &d)
@@ -257,32 +253,156 @@ void k_sb_solve(SymBallView b, const uint32_t *queries, size_t n, int32_t *lengt
 		const uint32_t e = probe_find(b.table, b.mask, b.states, rep);
 		int8_t *row = actions + q * (size_t)b.radius;
 		const int depth = e ? sb_depth_of(b, e) : -1;
-		int len = 0;
-		bool ok = depth >= 0 && depth <= b.radius;
-		while (ok && len < depth) {                                      // (everything here is the same in every lane)
-			int found = -1;
-			for (int a = 0; a < N_ACTIONS && found < 0; a++) {
-				uint32_t y[5], tab[12];
-				#pragma unroll
-				for (int j = 0; j < 5; j++) y[j] = x[j];
-				load_action_table(s_act, (uint32_t)a, tab);
-				move5(y, tab);
-				sym_canonical(s_sym, L, lane, y, rep, &sym, &count);
-				const uint32_t g = probe_find(b.table, b.mask, b.states, rep);
-				if (g != 0u && sb_depth_of(b, g) == depth - len - 1) {
-					found = a;
-					#pragma unroll
-					for (int j = 0; j < 5; j++) x[j] = y[j];
-				}
-			}
-			if (found < 0) { ok = false; break; }                        // a node without a child one level nearer: the ball is broken
-			if (lane == 0) row[len] = (int8_t)found;
-			len++;
-		}
+		bool ok;
+		const int len = sb_descend(b, s_sym, s_act, L, lane, x, depth, [&](int k, int a) { if (lane == 0) row[k] = (int8_t)a; }, &ok);
 		if (depth >= 0 && !ok && lane == 0) *error = RK_ESTATE;
 		if (lane == 0) lengths[q] = ok ? len : -1;
 		for (int k = (ok ? len : 0) + lane; k < b.radius; k += 64) row[k] = -1;
 	}
+}
+
+// ---- the search from a start towards the symmetry ball ----------------------------------------------------------------------
+// One wave: node 1 = the start, whose representative is looked up in the ball (bsearch_root with that one difference).
+__global__ __launch_bounds__(64)
+void k_ss_root(SrchDev d, SymBallView b, const uint32_t *root, int budget)
+{
+	__shared__ uint32_t s_sym[SYM_LDS_DWORDS];
+	const int lane = threadIdx.x;
+	sym_stage(s_sym, lane, 64);
+	if (lane < S_COUNT) d.ctr[lane] = 0;
+	__syncthreads();
+	const SymLane L = sym_lane(min(lane, N_SYM - 1));
+	uint32_t s[5], rep[5];
+	load5(root, s);
+	int sym, count;
+	sym_canonical(s_sym, L, lane, s, rep, &sym, &count);
+	const uint32_t e = probe_find(b.table, b.mask, b.states, rep);
+	if (lane != 0) return;
+	#pragma unroll
+	for (int j = 0; j < 5; j++) d.states[5 + j] = s[j];
+	d.parent[1] = 0; d.pact[1] = 0;
+	d.table[hash_state(s) & d.mask] = 1u;
+	d.ctr[S_SIZE] = 1; d.ctr[S_HEAD] = 1; d.ctr[S_HI] = 1;
+	d.ctr[S_BUDGET] = budget;
+	d.ctr[S_WINPOS] = (int32_t)BS_NO_WIN;
+	if (e != 0u) {                                                       // the ball holds the start's orbit: nothing is popped
+		d.ctr[S_WON] = 1; d.ctr[S_MEET] = (int32_t)e;
+		d.ctr[S_STOP] = BS_STOP_WON; d.ctr[S_DONE] = 1;
+		return;
+	}
+	srch_next(d);
+}
+
+// hit[c] = the ball's node of the representative of child c of the batch, 0 when the ball does not hold it: waves stride over
+// the children (k_sb_canon's grid), nothing but hit is written
+__global__ __launch_bounds__(256)
+void k_ss_probe(SrchDev d, SymBallView b, uint32_t *hit)
+{
+	__shared__ uint32_t s_sym[SYM_LDS_DWORDS];
+	__shared__ u32x4 s_act[36];
+	const int K = 12 * srch_pops(d);
+	if ((int)blockIdx.x * 4 >= K) return;                                // done, or a workgroup past the batch: nothing staged
+	sym_stage(s_sym, threadIdx.x, 256);
+	stage_action_tables(s_act, threadIdx.x);
+	__syncthreads();
+	const int lane = threadIdx.x & 63;
+	const SymLane L = sym_lane(min(lane, N_SYM - 1));
+	const int32_t head = d.ctr[S_HEAD];
+	for (int c = blockIdx.x * 4 + (threadIdx.x >> 6); c < K; c += gridDim.x * 4) {       // (whole waves)
+		const int i = c / 12, a = c - 12 * i;
+		uint32_t x[5], rep[5];
+		child_state(d.states, head + i, s_act, (uint32_t)a, x);
+		int sym, count;
+		sym_canonical(s_sym, L, lane, x, rep, &sym, &count);
+		const uint32_t e = probe_find(b.table, b.mask, b.states, rep);
+		if (lane == 0) hit[c] = e;
+	}
+}
+
+// a meeting child leaves no claim; any other: membership / election in the own table on the raw child (bsearch_expand)
+__global__ __launch_bounds__(256)
+void k_ss_expand(SrchDev d, const uint32_t *hit)
+{
+	__shared__ u32x4 s_act[36];
+	stage_action_tables(s_act, threadIdx.x);
+	__syncthreads();
+	const int P = srch_pops(d);
+	const int c = blockIdx.x * blockDim.x + threadIdx.x;
+	if (c >= 12 * P) return;
+	const uint32_t m = hit[c];
+	if (m != 0u) {
+		atomicMin(reinterpret_cast<uint32_t *>(&d.ctr[S_WINPOS]), (uint32_t)c);
+		d.slot[c] = TENT | m;                                            // no claim (TENT bit); bsearch_end reads the meeting node here
+		return;
+	}
+	const int32_t head = d.ctr[S_HEAD];
+	const int i = c / 12, a = c - 12 * i;
+	uint32_t s[5];
+	child_state(d.states, head + i, s_act, (uint32_t)a, s);
+	uint32_t slot = 0;
+	const uint32_t e = probe_elect(d.table, d.mask, d.states, s, c,
+	                               [&](int c2, uint32_t o[5]) { child_state(d.states, head + c2 / 12, s_act, (uint32_t)(c2 % 12), o); }, &slot);
+	d.slot[c] = e == 0u ? slot : NO_SLOT;
+}
+
+__global__ __launch_bounds__(ASCAN)
+void k_ss_scan(SrchDev d) { bsearch_scan(d); }
+
+__global__ __launch_bounds__(256)
+void k_ss_append(SrchDev d) { bsearch_append(d); }
+
+__global__ void k_ss_end(SrchDev d) { if (threadIdx.x == 0 && blockIdx.x == 0) bsearch_end(d); }
+
+__global__ __launch_bounds__(256)
+void k_ss_rehash(SrchDev d) { bsearch_rehash(d); }
+
+// The action queue of a won search, one wave: the path from the start to the popped parent and the meeting action (none of either
+// when the ball holds the start's orbit), then the descent from the meeting state.  out[0] = length, -1 when the search has not
+// met or a parent chain is broken, -2 when the meeting state is not where S_MEET says or the descent finds no way on.  Every lane
+// computes the same; lane 0 writes.
+__global__ __launch_bounds__(64)
+void k_ss_walk(SrchDev d, SymBallView b, int32_t *out, int max_len)
+{
+	__shared__ uint32_t s_sym[SYM_LDS_DWORDS];
+	__shared__ u32x4 s_act[36];
+	const int lane = threadIdx.x;
+	sym_stage(s_sym, lane, 64);
+	stage_action_tables(s_act, lane);
+	__syncthreads();
+	if (lane == 0) out[0] = -1;
+	if (!d.ctr[S_WON]) return;
+	const int p = d.ctr[S_WPARENT];
+	int ls = 0;
+	for (int i = p; p != 0 && i != 1; ls++) {
+		if (i < 1 || (uint32_t)i >= d.cap1 || ls > (int)d.cap1) return;
+		i = d.parent[i];
+	}
+	int i = p;
+	for (int k = ls - 1; k >= 0; k--) {
+		if (k < max_len && lane == 0) out[1 + k] = d.pact[i];
+		i = d.parent[i];
+	}
+	int len = ls;
+	uint32_t x[5];
+	if (p != 0) {
+		const int a = d.ctr[S_WACT];
+		if ((uint32_t)a >= (uint32_t)N_ACTIONS) return;
+		if (len < max_len && lane == 0) out[1 + len] = a;
+		len++;
+		child_state(d.states, p, s_act, (uint32_t)a, x);
+	} else {
+		load5(d.states + 5, x);
+	}
+	const SymLane L = sym_lane(min(lane, N_SYM - 1));
+	uint32_t rep[5];
+	int sym, count;
+	sym_canonical(s_sym, L, lane, x, rep, &sym, &count);
+	const uint32_t g = probe_find(b.table, b.mask, b.states, rep);
+	bool ok = g != 0u && g == (uint32_t)d.ctr[S_MEET];
+	const int own = len;                                                 // moves before the meeting state
+	if (ok) len = own + sb_descend(b, s_sym, s_act, L, lane, x, sb_depth_of(b, g),
+	                               [&](int k, int a) { if (own + k < max_len && lane == 0) out[1 + own + k] = a; }, &ok);
+	if (lane == 0) out[0] = ok ? len : -2;
 }
 
 __global__ __launch_bounds__(256)
@@ -330,8 +450,21 @@ struct rk_symball {
 	size_t cap = 0;
 	long long size = 0, iterations = 0;
 	long long cover[SB_MAX_RADIUS + 1] = {};
+	int attached = 0;                           // searches that hold this ball's arrays
 	bool built = false;
 	Landing ctr_host;
+	DevPool pool{64};
+};
+
+struct rk_ssearch {
+	SrchDev d{};
+	uint32_t *hit = nullptr;                    // per child of the batch: the ball's node of its representative, or 0
+	rk_symball *ball = nullptr;
+	size_t cap = 0;
+	uint32_t *root_dev = nullptr;
+	int32_t *walk = nullptr;
+	Landing ctr_host;
+	bool ready = false;
 	DevPool pool{64};
 };
 
@@ -359,6 +492,8 @@ int check_sym_states(const char *who, const void *d_states, size_t n)
 	if ((uintptr_t)d_states & 3u) return fail(RK_EINVAL, "%s: device pointers must be 4-byte aligned", who);
 	return RK_OK;
 }
+
+int ssearch_read_ctr(rk_ssearch *h, int32_t *out, hipStream_t st) { return h->ctr_host.read(h->d.ctr, S_COUNT, out, st); }
 
 int check_sb_queries(const char *who, const rk_symball *h, const void *d_states, size_t n, const void *out)
 {
@@ -427,6 +562,7 @@ int rk_symball_create(rk_symball_t **out, int radius, int pops, size_t capacity)
 
 int rk_symball_destroy(rk_symball_t *h)
 {
+	if (h && h->attached > 0) return fail(RK_ESTATE, "rk_symball_destroy: %d searches still hold this ball", h->attached);
 	delete h;
 	return RK_OK;
 }
@@ -535,6 +671,158 @@ int rk_symball_solve(rk_symball_t *h, const int8_t *d_states, size_t n, int32_t 
 	                   d_actions, d_error);
 	RK_HIP(hipGetLastError());
 	return RK_OK;
+}
+
+int rk_ssearch_create(rk_ssearch_t **out, rk_symball_t *ball, size_t capacity, int pops)
+{
+	if (!out || !ball) return fail(RK_EINVAL, "rk_ssearch_create: null argument");
+	if (capacity < 2 || capacity > BS_MAX_CAPACITY) return fail(RK_EINVAL, "rk_ssearch_create: capacity %zu out of range", capacity);
+	if (pops < 1 || pops > (1 << 22)) return fail(RK_EINVAL, "rk_ssearch_create: pops %d outside 1..%d", pops, 1 << 22);
+	if (!ball->built) return fail(RK_ESTATE, "rk_ssearch_create: build the ball first");
+	rk_ssearch *h = new rk_ssearch();
+	h->cap = capacity;
+	SrchDev &d = h->d;
+	d.pops = pops;
+	d.cap1 = (uint32_t)(capacity + 1);
+	d.mask = (uint32_t)(table_slots(capacity, 1024) - 1);
+	const size_t C1 = capacity + 1, K = (size_t)12 * pops;
+	int e = RK_OK;
+	#define A(ptr, cnt) if (!e) e = h->pool.alloc(&d.ptr, (cnt))
+	A(states, C1 * 5); A(parent, C1); A(pact, C1); A(table, (size_t)d.mask + 1); A(ctr, S_COUNT);
+	A(slot, K); A(rank, K); A(first, K); A(chain, frontier_scan_blocks(pops));
+	#undef A
+	if (!e) e = h->pool.alloc(&h->hit, K);
+	if (!e) e = h->pool.alloc(&h->root_dev, 8);
+	if (!e) e = h->pool.alloc(&h->walk, BS_WALK_MAX + 8);
+	if (!e) h->ctr_host.reserve(S_COUNT);
+	if (e) { delete h; return e; }
+	h->ball = ball;
+	ball->attached += 1;
+	*out = h;
+	return RK_OK;
+}
+
+int rk_ssearch_destroy(rk_ssearch_t *h)
+{
+	if (h && h->ball) h->ball->attached -= 1;
+	delete h;
+	return RK_OK;
+}
+
+int rk_ssearch_reset(rk_ssearch_t *h, const int8_t *h_start_state, long long max_states, void *stream)
+{
+	if (!h || !h_start_state) return fail(RK_EINVAL, "rk_ssearch_reset: null argument");
+	if (!h->ball->built) return fail(RK_ESTATE, "rk_ssearch_reset: build the ball first");
+	hipStream_t st = (hipStream_t)stream;
+	SrchDev &d = h->d;
+	RK_HIP(hipMemsetAsync(d.table, 0, ((size_t)d.mask + 1) * sizeof(uint32_t), st));                        // the own table only
+	RK_HIP(hipMemsetAsync(d.chain, 0, frontier_scan_blocks(d.pops) * sizeof(unsigned long long), st));
+	RK_HIP(hipMemcpyAsync(h->root_dev, h_start_state, STATE_BYTES, hipMemcpyHostToDevice, st));
+	hipLaunchKernelGGL(k_ss_root, dim3(1), dim3(64), 0, st, d, h->ball->view, h->root_dev, budget_of(max_states));
+	RK_HIP(hipGetLastError());
+	RK_HIP(hipStreamSynchronize(st));       // the host buffer may go away after return
+	h->ready = true;
+	return RK_OK;
+}
+
+int rk_ssearch_run(rk_ssearch_t *h, int iterations, void *stream)
+{
+	if (!h || !h->ready) return fail(RK_ESTATE, "rk_ssearch_run: reset the engine first");
+	if (iterations < 0) return fail(RK_EINVAL, "rk_ssearch_run: iterations %d < 0", iterations);
+	hipStream_t st = (hipStream_t)stream;
+	const SrchDev &d = h->d;
+	const SymBallView &b = h->ball->view;
+	const size_t K = (size_t)12 * d.pops;
+	const unsigned grid = blocks(K);
+	for (int it = 0; it < iterations; it++) {
+		hipLaunchKernelGGL(k_ss_probe, dim3(sym_grid(K)), dim3(256), 0, st, d, b, h->hit);
+		hipLaunchKernelGGL(k_ss_expand, dim3(grid), dim3(256), 0, st, d, h->hit);
+		hipLaunchKernelGGL(k_ss_scan, dim3(blocks(K, ASCAN)), dim3(ASCAN), 0, st, d);
+		hipLaunchKernelGGL(k_ss_append, dim3(grid), dim3(256), 0, st, d);
+		hipLaunchKernelGGL(k_ss_end, dim3(1), dim3(64), 0, st, d);
+	}
+	RK_HIP(hipGetLastError());
+	return RK_OK;
+}
+
+int rk_ssearch_status(rk_ssearch_t *h, long long *h_status, void *stream)
+{
+	if (!h || !h->ready || !h_status) return fail(RK_EINVAL, "rk_ssearch_status: bad argument");
+	int32_t c[S_COUNT];
+	if (int e = ssearch_read_ctr(h, c, (hipStream_t)stream)) return e;
+	h_status[0] = c[S_DONE]; h_status[1] = c[S_WON]; h_status[2] = c[S_SIZE]; h_status[3] = c[S_ITERS];
+	h_status[4] = c[S_POPPED]; h_status[5] = c[S_STOP]; h_status[6] = c[S_ERROR]; h_status[7] = c[S_NPOP];
+	h_status[8] = c[S_DEPTH]; h_status[9] = c[S_MEET];
+	return RK_OK;
+}
+
+int rk_ssearch_grow(rk_ssearch_t *h, size_t new_capacity, void *stream)
+{
+	if (!h || !h->ready) return fail(RK_ESTATE, "rk_ssearch_grow: reset the engine first");
+	if (new_capacity <= h->cap) return new_capacity == h->cap ? RK_OK : fail(RK_EINVAL, "rk_ssearch_grow: %zu is below the current capacity %zu", new_capacity, h->cap);
+	if (new_capacity > BS_MAX_CAPACITY) return fail(RK_EINVAL, "rk_ssearch_grow: capacity %zu out of range", new_capacity);
+	hipStream_t st = (hipStream_t)stream;
+	const SrchDev old = h->d;
+	SrchDev d = old;
+	const size_t C1 = new_capacity + 1, C1_old = h->cap + 1;
+	d.cap1 = (uint32_t)C1;
+	d.mask = (uint32_t)(table_slots(new_capacity, 1024) - 1);
+	Growth g(h->pool, "rk_ssearch_grow");
+	g.request(&d.states, C1 * 5); g.request(&d.parent, C1); g.request(&d.pact, C1); g.request(&d.table, (size_t)d.mask + 1);
+	if (!g.granted()) return fail(RK_ECAPACITY, "rk_ssearch_grow: no device memory for a pool of %zu states", new_capacity);
+	const int e = g.fill(st, [&]() -> hipError_t {
+		RK_FILL(hipMemcpyAsync(d.states, old.states, C1_old * STATE_BYTES, hipMemcpyDeviceToDevice, st));
+		RK_FILL(hipMemcpyAsync(d.parent, old.parent, C1_old * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+		RK_FILL(hipMemcpyAsync(d.pact, old.pact, C1_old, hipMemcpyDeviceToDevice, st));
+		RK_FILL(hipMemsetAsync(d.table, 0, ((size_t)d.mask + 1) * sizeof(uint32_t), st));
+		hipLaunchKernelGGL(k_ss_rehash, dim3(std::min<unsigned>(blocks(C1_old), 4096u)), dim3(256), 0, st, d);
+		return hipGetLastError();
+	});
+	if (e) return e;
+	g.commit();
+	h->d = d;
+	h->cap = new_capacity;
+	return RK_OK;
+}
+
+long long rk_ssearch_size(const rk_ssearch_t *hc)
+{
+	rk_ssearch_t *h = const_cast<rk_ssearch_t *>(hc);
+	if (!h || !h->ready) return 0;
+	int32_t c[S_COUNT];
+	if (ssearch_read_ctr(h, c, nullptr)) return RK_EHIP;
+	return c[S_SIZE];
+}
+
+int rk_ssearch_export(rk_ssearch_t *h, size_t first, size_t count, int8_t *h_states, long long *h_parents, long long *h_actions, void *stream)
+{
+	if (!h || !h->ready) return fail(RK_ESTATE, "rk_ssearch_export: reset the engine first");
+	if (first + count > h->cap + 1) return fail(RK_EINVAL, "rk_ssearch_export: rows %zu..%zu outside the pool", first, first + count);
+	if (count == 0) return RK_OK;
+	hipStream_t st = (hipStream_t)stream;
+	const SrchDev &d = h->d;
+	Widened<int32_t, long long> p;
+	Widened<uint8_t, long long> a;
+	if (h_states) RK_HIP(hipMemcpyAsync(h_states, d.states + first * 5, count * STATE_BYTES, hipMemcpyDeviceToHost, st));
+	if (int e = p.start(d.parent + first, count, h_parents, st)) return e;
+	if (int e = a.start(d.pact + first, count, h_actions, st)) return e;
+	RK_HIP(hipStreamSynchronize(st));
+	p.finish(); a.finish();
+	return RK_OK;
+}
+
+long long rk_ssearch_path(rk_ssearch_t *h, long long *h_actions, size_t max_len, void *stream)
+{
+	if (!h || !h->ready) return fail(RK_ESTATE, "rk_ssearch_path: reset the engine first");
+	if (!h_actions && max_len > 0) return fail(RK_EINVAL, "rk_ssearch_path: null h_actions with max_len %zu", max_len);
+	hipStream_t st = (hipStream_t)stream;
+	hipLaunchKernelGGL(k_ss_walk, dim3(1), dim3(64), 0, st, h->d, h->ball->view, h->walk, BS_WALK_MAX);
+	RK_HIP(hipGetLastError());
+	int32_t len = 0;
+	if (int e = read_walk(h->walk, BS_WALK_MAX, h_actions, max_len, st, &len)) return e;
+	if (len == -2) return fail(RK_ESTATE, "rk_ssearch_path: the meeting state has no way down the ball (or is not where the search met)");
+	if (len < 0) return fail(RK_ESTATE, "rk_ssearch_path: the search has not met the ball (or a parent chain is broken)");
+	return (long long)len;
 }
 
 }  // extern "C"

@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "rk_device.h"
+#include "rk_search_dev.h"
 #include "rk_sym_tables.h"
 
 namespace rk {
@@ -119,6 +120,61 @@ __device__ __forceinline__ void sym_canonical(const uint32_t *lds, const SymLane
 	const unsigned long long who = __ballot(tied);
 	*sym = __ffsll((long long)who) - 1;
 	*count = __popcll(who);
+}
+
+// ---- what the readers of a built symmetry ball share (rk_sym.hip: the queries of rk_symball_*, the search of rk_ssearch_*) ----
+constexpr int SB_MAX_RADIUS = 10;
+
+// What the readers of a built ball get, by value.
+struct SymBallView {
+	uint32_t mask, cap1;
+	int radius;
+	int32_t lstart[SB_MAX_RADIUS + 2];          // level l = lstart[l] .. lstart[l + 1] - 1; INT32_MAX beyond radius + 1
+	const uint32_t *states; const uint32_t *table;
+};
+
+__device__ __forceinline__ int sb_depth_of(const SymBallView &b, uint32_t idx)
+{
+	int depth = 0;
+	#pragma unroll
+	for (int l = 1; l <= SB_MAX_RADIUS; l++) depth += (int32_t)idx >= b.lstart[l] ? 1 : 0;
+	return depth;
+}
+
+// The descent from x, a state whose representative lies at level `depth` of the ball, to the solved state: at each step the lowest
+// action whose child's representative lies one level nearer, emit(step, action) for every step, x moved along.  Returns the
+// steps taken; *ok = false when a state has no such child (the ball is broken) or depth is outside 0..radius.  ALL 64 lanes of a
+// wave call it with the same x (lane l with the SymLane of symmetry l); everything in it is the same in every lane.
+template <typename Emit>
+__device__ __forceinline__ int sb_descend(const SymBallView &b, const uint32_t *s_sym, const u32x4 *s_act, const SymLane &L, int lane,
+                                          uint32_t x[5], int depth, Emit emit, bool *ok_out)
+{
+	uint32_t rep[5];
+	int sym, count;
+	int len = 0;
+	bool ok = depth >= 0 && depth <= b.radius;
+	while (ok && len < depth) {                                      // (everything here is the same in every lane)
+		int found = -1;
+		for (int a = 0; a < N_ACTIONS && found < 0; a++) {
+			uint32_t y[5], tab[12];
+			#pragma unroll
+			for (int j = 0; j < 5; j++) y[j] = x[j];
+			load_action_table(s_act, (uint32_t)a, tab);
+			move5(y, tab);
+			sym_canonical(s_sym, L, lane, y, rep, &sym, &count);
+			const uint32_t g = probe_find(b.table, b.mask, b.states, rep);
+			if (g != 0u && sb_depth_of(b, g) == depth - len - 1) {
+				found = a;
+				#pragma unroll
+				for (int j = 0; j < 5; j++) x[j] = y[j];
+			}
+		}
+		if (found < 0) { ok = false; break; }                        // a node without a child one level nearer: the ball is broken
+		emit(len, found);
+		len++;
+	}
+	*ok_out = ok;
+	return len;
 }
 
 }  // namespace rk

@@ -837,28 +837,21 @@ class DeviceSymBall(_ffi.Owner):
 		return f"Symmetry-reduced goal ball (device, radius={self.radius})"
 
 
-class DeviceBallSearch(Agent, _ffi.Owner):
-	"""
-	A SHORTEST solution (quarter-turn metric) by a one-sided breadth-first search from the start that ends at the first child a
-	kept `DeviceGoalBall` holds (engine rk_bsearch_*, csrc/rk_ball.hip).  Node 1 of the own pool is the start; levels grow as in
-	`DeviceBiBFS`: a child the own pool holds is skipped, a child the ball holds is the meeting (the search ends, the child is
-	not stored, the lowest batch position wins), any other is appended.  A start at distance D > radius meets while level
-	D - radius grows, in a node of ball depth `radius`, so the first meeting is optimal.  A start the ball holds is answered by
-	the ball's path: then len(agent) == 1 and nothing is popped.  The state budget is checked before every pop, the time limit
-	when the host polls.  `action_queue`, len(agent), the pool, `depth` and the meeting do not depend on `pops`.
-
-	`capacity`, `max_capacity`, `grown` and `capacity_exhausted` are `DeviceBFS`'s, for the own pool; its table is sized to it and
-	a new search clears that table, never the ball's.  Several agents may share one ball; each holds a reference to it.
-	"""
+class _BallSearch(Agent, _ffi.Owner):
+	"""What `DeviceBallSearch` and `DeviceSymBallSearch` share: the arguments, the host loop of a search with its pool growth, and
+	the export of the own pool.  `_entries` is the prefix of the engine's entry points (they have one argument list and one status
+	layout), `_ball_type` the kind of ball it ends at."""
 	default_capacity = 8_000_000
 	max_capacity = 400_000_000
-	MAX_POPS = 1 << 22                      # rk_bsearch_create's limit
+	MAX_POPS = 1 << 22                      # rk_bsearch_create's and rk_ssearch_create's limit
 	MAX_CAPACITY = 0x3FFFFFF0
+	_entries = None
+	_ball_type = None
 
-	def __init__(self, ball: DeviceGoalBall, pops: int = 16_384, capacity: int = None, max_capacity: int = None, poll: int = 8):
+	def __init__(self, ball, pops: int = 16_384, capacity: int = None, max_capacity: int = None, poll: int = 8):
 		super().__init__()
-		if not isinstance(ball, DeviceGoalBall):
-			raise TypeError(f"ball must be a DeviceGoalBall, got {type(ball).__name__}")
+		if not isinstance(ball, self._ball_type):
+			raise TypeError(f"ball must be a {self._ball_type.__name__}, got {type(ball).__name__}")
 		if isinstance(pops, bool) or int(pops) != pops or not 1 <= int(pops) <= self.MAX_POPS:
 			raise ValueError(f"pops must be an integer in 1..{self.MAX_POPS}, got {pops!r}")
 		for name, v in (("capacity", capacity), ("max_capacity", max_capacity)):
@@ -875,6 +868,7 @@ class DeviceBallSearch(Agent, _ffi.Owner):
 		self._n = 0
 		self._is2024 = True
 		self._cache = None
+		self._root = None                   # the start of the last search, 20 bytes
 		self._meet = 0                      # the ball's node that the meeting child (or the start itself) equals
 		self.depth = 0                      # complete levels around the start after the last search
 		self.iterations = 0
@@ -882,18 +876,21 @@ class DeviceBallSearch(Agent, _ffi.Owner):
 		self.grown = 0
 		self.capacity_exhausted = False
 
+	def _entry(self, name: str):
+		return getattr(_ffi.lib(), f"{self._entries}_{name}")
+
 	def _engine(self, capacity: int):
 		if self._h is not None and self._h_cap >= capacity:
-			return self._h                  # (a pool that grew in an earlier search is kept: rk_bsearch_reset clears its table)
+			return self._h                  # (a pool that grew in an earlier search is kept: the reset clears its table)
 		self._h_cap = capacity
-		return self._create("rk_bsearch_create", "rk_bsearch_destroy", self.ball._h, capacity, self.pops)
+		return self._create(f"{self._entries}_create", f"{self._entries}_destroy", self.ball._h, capacity, self.pops)
 
 	def _grow(self, h) -> bool:
 		if self._h_cap >= self.max_capacity:
 			eng.pool_exhausted(self, self._h_cap, "cannot take the next iteration")
 			return False
 		cap = min(2 * self._h_cap, self.max_capacity)
-		_ffi.check(_ffi.lib().rk_bsearch_grow(h, cap, _ffi.stream_ptr()))
+		_ffi.check(self._entry("grow")(h, cap, _ffi.stream_ptr()))
 		self._h_cap = cap
 		self.grown += 1
 		return True
@@ -906,18 +903,19 @@ class DeviceBallSearch(Agent, _ffi.Owner):
 		self._n, self._cache, self.iterations, self.grown, self.capacity_exhausted = 0, None, 0, 0, False
 		self.popped, self._meet, self.depth = 0, 0, 0
 		self._is2024 = cube.get_is2024()
-		root = _roots20(self._is2024, state, 1)[0]          # ValueError for an illegal 6x8x6 state
+		root = self._root = _roots20(self._is2024, state, 1)[0]          # ValueError for an illegal 6x8x6 state
 		self.ball.build()
-		lib, stream = _ffi.lib(), _ffi.stream_ptr()
+		stream = _ffi.stream_ptr()
+		run, read_status = self._entry("run"), self._entry("status")
 		K = 12 * self.pops
 		budget = int(min(max_states, 2 ** 31 - 1))
 		cap = self.capacity or min(budget + K, self.default_capacity)
 		cap = max(2, min(cap, self.max_capacity, self.MAX_CAPACITY))
 		h = self._engine(cap)
-		_ffi.check(lib.rk_bsearch_reset(h, root.ctypes.data, budget, stream))
+		_ffi.check(self._entry("reset")(h, root.ctypes.data, budget, stream))
 		self._n = 1
 		status = (C.c_longlong * 10)()
-		_ffi.check(lib.rk_bsearch_status(h, status, stream))
+		_ffi.check(read_status(h, status, stream))
 		self._meet = int(status[9])
 		while not status[0]:
 			room = (self._h_cap - self._n) // K              # iterations the pool takes whatever they find
@@ -925,8 +923,8 @@ class DeviceBallSearch(Agent, _ffi.Owner):
 				if not self._grow(h):
 					return False
 				continue
-			_ffi.check(lib.rk_bsearch_run(h, eng.burst(min(self.poll, room), budget - self._n, K), stream))
-			_ffi.check(lib.rk_bsearch_status(h, status, stream))
+			_ffi.check(run(h, eng.burst(min(self.poll, room), budget - self._n, K), stream))
+			_ffi.check(read_status(h, status, stream))
 			self._n, self.iterations, self.popped = int(status[2]), int(status[3]), int(status[4])
 			self.depth, self._meet = int(status[8]), int(status[9])
 			if status[6]:
@@ -934,7 +932,7 @@ class DeviceBallSearch(Agent, _ffi.Owner):
 			if not status[0] and time.perf_counter() - t0 >= time_limit:
 				return False
 		if status[1]:
-			self.action_queue = eng.read_path(lib.rk_bsearch_path, h)
+			self.action_queue = eng.read_path(self._entry("path"), h)
 			return True
 		return False
 
@@ -945,12 +943,40 @@ class DeviceBallSearch(Agent, _ffi.Owner):
 			states = np.zeros((n + 1, 20), np.int8)
 			parents, actions = np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int64)
 			if n and self._h is not None:
-				_ffi.check(_ffi.lib().rk_bsearch_export(self._h, 1, n, states[1:].ctypes.data, parents[1:].ctypes.data,
-				                                         actions[1:].ctypes.data, _ffi.stream_ptr()))
+				_ffi.check(self._entry("export")(self._h, 1, n, states[1:].ctypes.data, parents[1:].ctypes.data,
+				                                 actions[1:].ctypes.data, _ffi.stream_ptr()))
 			if n:
 				actions[1] = -1
 			self._cache = (_states_out(self._is2024, states, n)[1:], parents[1:], actions[1:])
 		return self._cache
+
+	@property
+	def meeting_depth(self):
+		"""The depth in the ball of the node the search met; None when the last search did not meet."""
+		return self.ball.depth_of_node(self._meet) if self._meet else None
+
+	def __len__(self):
+		return self._n
+
+
+class DeviceBallSearch(_BallSearch):
+	"""
+	A SHORTEST solution (quarter-turn metric) by a one-sided breadth-first search from the start that ends at the first child a
+	kept `DeviceGoalBall` holds (engine rk_bsearch_*, csrc/rk_ball.hip).  Node 1 of the own pool is the start; levels grow as in
+	`DeviceBiBFS`: a child the own pool holds is skipped, a child the ball holds is the meeting (the search ends, the child is
+	not stored, the lowest batch position wins), any other is appended.  A start at distance D > radius meets while level
+	D - radius grows, in a node of ball depth `radius`, so the first meeting is optimal.  A start the ball holds is answered by
+	the ball's path: then len(agent) == 1 and nothing is popped.  The state budget is checked before every pop, the time limit
+	when the host polls.  `action_queue`, len(agent), the pool, `depth` and the meeting do not depend on `pops`.
+
+	`capacity`, `max_capacity`, `grown` and `capacity_exhausted` are `DeviceBFS`'s, for the own pool; its table is sized to it and
+	a new search clears that table, never the ball's.  Several agents may share one ball; each holds a reference to it.
+	"""
+	_entries = "rk_bsearch"
+	_ball_type = DeviceGoalBall
+
+	def __init__(self, ball: DeviceGoalBall, pops: int = 16_384, capacity: int = None, max_capacity: int = None, poll: int = 8):
+		super().__init__(ball, pops, capacity, max_capacity, poll)
 
 	@property
 	def meeting(self):
@@ -962,16 +988,53 @@ class DeviceBallSearch(Agent, _ffi.Owner):
 		_ffi.check(_ffi.lib().rk_ball_export(self.ball._h, self._meet, 1, state[1:].ctypes.data, None, None, _ffi.stream_ptr()))
 		return _states_out(self._is2024, state, 1)[1]
 
-	@property
-	def meeting_depth(self):
-		"""The depth in the ball of the node the search met; None when the last search did not meet."""
-		return self.ball.depth_of_node(self._meet) if self._meet else None
-
-	def __len__(self):
-		return self._n
-
 	def __str__(self):
 		return f"Breadth-first search to a goal ball (device, radius={self.ball.radius}, pops={self.pops})"
+
+
+class DeviceSymBallSearch(_BallSearch):
+	"""
+	`DeviceBallSearch` that ends at a kept `DeviceSymBall` (engine rk_ssearch_*, csrc/rk_sym.hip): the own pool holds raw states
+	with parent and action, and a child is the meeting when the symmetry ball holds its canonical representative.  A state lies
+	in the plain ball of radius R exactly when its representative lies in the symmetry ball of radius R, so `arrays()`, len(agent),
+	`depth`, `popped`, `iterations` and `meeting` equal `DeviceBallSearch`'s on a `DeviceGoalBall(R)`; the ball's half of
+	`action_queue` is the descent of `DeviceSymBall.solve` from the meeting state and has the same length.  The symmetry ball
+	reaches radius 10 where the plain one ends at 8, and every level of radius saves the search a level of its own (x 9.3 states).
+	An iteration costs one launch more than `DeviceBallSearch`'s: the canonical forms of the batch, a wave per child.
+
+	`meeting` is the RAW state that met (the child that was not stored, or the start), `meeting_node` the node of its
+	representative in the ball, `meeting_depth` that node's depth.  Several agents may share one ball.
+	"""
+	_entries = "rk_ssearch"
+	_ball_type = DeviceSymBall
+
+	def __init__(self, ball: DeviceSymBall, pops: int = 16_384, capacity: int = None, max_capacity: int = None, poll: int = 8):
+		super().__init__(ball, pops, capacity, max_capacity, poll)
+
+	@property
+	def meeting_node(self):
+		"""The node in the ball of the representative of the state that met; None when the last search did not meet."""
+		return self._meet or None
+
+	@property
+	def meeting(self):
+		"""The state where the search met the ball -- the child that was not stored, or the start itself when the ball holds its
+		orbit -- in the representation of the search; None when the last search did not meet.  The ball keeps representatives
+		only, so this is the start moved along the own half of `action_queue`."""
+		if not self._meet:
+			return None
+		state = np.zeros((2, 20), np.int8)
+		state[1] = self._root
+		own = np.asarray(list(self.action_queue)[:len(self.action_queue) - self.meeting_depth], np.uint8)      # (a deque)
+		moved = np.empty(20, np.int8)
+		for a in own:                                        # (a handful of moves, on 20-byte states whatever the representation)
+			_ffi.check(_ffi.lib().rk_multi_rotate_host(_ffi.REPR_2024, state[1:].ctypes.data, a.reshape(1).ctypes.data, moved.ctypes.data, 1,
+			                                           _ffi.stream_ptr()))
+			state[1] = moved
+		return _states_out(self._is2024, state, 1)[1]
+
+	def __str__(self):
+		return f"Breadth-first search to a symmetry-reduced goal ball (device, radius={self.ball.radius}, pops={self.pops})"
 
 
 class DeviceBallSearchBatch(_ffi.Owner):
