@@ -37,7 +37,7 @@
 // action order is a shortest solution.  A start that the ball holds is answered by the ball's path without a pop.  The own
 // table is sized to the own pool; a reset clears it and never the ball's.
 //
-// The batch (rk_bsearchb_*) is S such searches in lock-step.  The kernels' bodies are __device__ functions of a SrchDev; the single
+// The batch (rk_bsearchb_*) is S such searches in lock-step.  The kernels' bodies are __device__ functions of a FrontierDev; the single
 // engine's kernels pass theirs by value, the batch's (kb_bsearch_*) pick devs[blockIdx.y] from an array in device memory, so an
 // iteration of all slots is the same four launches with S in the grid's second dimension.  Every kind of array is one block sliced
 // per slot.  A slot's pool is fixed: it stops with reason 5 before an iteration that might not fit.
@@ -48,10 +48,9 @@
 #include <vector>
 
 #include "../../include/rubiks_hip.h"
-#include "rk_bsearch_dev.h"
 #include "rk_device.h"
 #include "rk_error.h"
-#include "rk_search_dev.h"
+#include "rk_frontier_dev.h"
 #include "rk_search_host.h"
 
 namespace rk {
@@ -414,10 +413,10 @@ void k_shorten_emit(BallView b, const int8_t *__restrict__ actions, const int32_
 }
 
 // ---- the search from a start towards the ball -------------------------------------------------------------------------------
-// (the counters, SrchDev, the level bookkeeping and the scan, append, end and rehash bodies are in rk_bsearch_dev.h: rk_sym.hip's
-// search to the symmetry-reduced ball runs the same ones)
+// (the pool, the counters, the level bookkeeping and the scan, append, end and rehash bodies are in rk_frontier_dev.h: every
+// breadth-first engine runs the same ones)
 // ---- the bodies: what one search does in a launch, for the single engine (k_bsearch_*) and for one slot of a batch (kb_bsearch_*) ----
-__device__ __forceinline__ void bsearch_root(const SrchDev &d, const BallView &b, const uint32_t *root, int budget)
+__device__ __forceinline__ void bsearch_root(const FrontierDev &d, const BallView &b, const uint32_t *root, int budget)
 {
 	const int tid = threadIdx.x;
 	if (tid < S_COUNT) d.ctr[tid] = 0;
@@ -429,28 +428,28 @@ __device__ __forceinline__ void bsearch_root(const SrchDev &d, const BallView &b
 	for (int j = 0; j < 5; j++) d.states[5 + j] = s[j];
 	d.parent[1] = 0; d.pact[1] = 0;
 	d.table[hash_state(s) & d.mask] = 1u;
-	d.ctr[S_SIZE] = 1; d.ctr[S_HEAD] = 1; d.ctr[S_HI] = 1;
-	d.ctr[S_BUDGET] = budget;
-	d.ctr[S_WINPOS] = (int32_t)BS_NO_WIN;
+	d.ctr[F_SIZE] = 1; d.ctr[F_HEAD] = 1; d.ctr[S_HI] = 1;
+	d.ctr[F_BUDGET] = budget;
+	d.ctr[F_WINPOS] = (int32_t)F_NO_WIN;
 	const uint32_t e = probe_find(b.table, b.mask, b.states, s);
 	if (e != 0u) {                                                       // the ball holds the start: its path is the answer, nothing is popped
-		d.ctr[S_WON] = 1; d.ctr[S_MEET] = (int32_t)e;
-		d.ctr[S_STOP] = BS_STOP_WON; d.ctr[S_DONE] = 1;
+		d.ctr[F_WON] = 1; d.ctr[S_MEET] = (int32_t)e;
+		d.ctr[F_STOP] = F_STOP_WON; d.ctr[F_DONE] = 1;
 		return;
 	}
 	srch_next(d);
 }
 
 // fan-out, the look-up in the ball (read-only), then membership / election in the own table: one thread per child
-__device__ __forceinline__ void bsearch_expand(const SrchDev &d, const BallView &b)
+__device__ __forceinline__ void bsearch_expand(const FrontierDev &d, const BallView &b)
 {
 	__shared__ u32x4 s_act[36];
 	stage_action_tables(s_act, threadIdx.x);
 	__syncthreads();
-	const int P = srch_pops(d);
+	const int P = fr_pops(d);
 	const int c = blockIdx.x * blockDim.x + threadIdx.x;
 	if (c >= 12 * P) return;
-	const int32_t head = d.ctr[S_HEAD];
+	const int32_t head = d.ctr[F_HEAD];
 	const int i = c / 12, a = c - 12 * i;
 	uint32_t s[5];
 	child_state(d.states, head + i, s_act, (uint32_t)a, s);
@@ -458,7 +457,7 @@ __device__ __forceinline__ void bsearch_expand(const SrchDev &d, const BallView 
 	// look-ups decides nothing; the ball first, so that a meeting child leaves no claim in the own table
 	const uint32_t m = probe_find(b.table, b.mask, b.states, s);
 	if (m != 0u) {
-		atomicMin(reinterpret_cast<uint32_t *>(&d.ctr[S_WINPOS]), (uint32_t)c);
+		atomicMin(reinterpret_cast<uint32_t *>(&d.ctr[F_WINPOS]), (uint32_t)c);
 		d.slot[c] = TENT | m;                                            // no claim (TENT bit); k_bsearch_end reads the meeting node here
 		return;
 	}
@@ -469,15 +468,15 @@ __device__ __forceinline__ void bsearch_expand(const SrchDev &d, const BallView 
 }
 
 __global__ __launch_bounds__(256)
-void k_bsearch_rehash(SrchDev d) { bsearch_rehash(d); }
+void k_bsearch_rehash(FrontierDev d) { fr_rehash(d); }
 
 // The action queue of a won search: the path from the start to the popped parent and the meeting action (none of either when
 // the ball holds the start itself), then the ball's path from the meeting node.  out[0] = length or -1.
-__device__ __forceinline__ void bsearch_walk(const SrchDev &d, const BallView &b, int32_t *out, int max_len)
+__device__ __forceinline__ void bsearch_walk(const FrontierDev &d, const BallView &b, int32_t *out, int max_len)
 {
 	out[0] = -1;
-	if (!d.ctr[S_WON]) return;
-	const int p = d.ctr[S_WPARENT];
+	if (!d.ctr[F_WON]) return;
+	const int p = d.ctr[F_WPARENT];
 	int ls = 0;
 	for (int i = p; p != 0 && i != 1; ls++) {
 		if (i < 1 || (uint32_t)i >= d.cap1 || ls > (int)d.cap1) return;
@@ -490,7 +489,7 @@ __device__ __forceinline__ void bsearch_walk(const SrchDev &d, const BallView &b
 	}
 	int len = ls;
 	if (p != 0) {
-		if (len < max_len) out[1 + len] = d.ctr[S_WACT];
+		if (len < max_len) out[1 + len] = d.ctr[F_WACT];
 		len++;
 	}
 	for (uint32_t g = (uint32_t)d.ctr[S_MEET]; g != 1u; len++) {
@@ -502,43 +501,43 @@ __device__ __forceinline__ void bsearch_walk(const SrchDev &d, const BallView &b
 }
 
 // ---- the single engine: one search per launch ----
-__global__ void k_bsearch_root(SrchDev d, BallView b, const uint32_t *root, int budget) { bsearch_root(d, b, root, budget); }
+__global__ void k_bsearch_root(FrontierDev d, BallView b, const uint32_t *root, int budget) { bsearch_root(d, b, root, budget); }
 
 __global__ __launch_bounds__(256)
-void k_bsearch_expand(SrchDev d, BallView b) { bsearch_expand(d, b); }
+void k_bsearch_expand(FrontierDev d, BallView b) { bsearch_expand(d, b); }
 
 __global__ __launch_bounds__(ASCAN)
-void k_bsearch_scan(SrchDev d) { bsearch_scan(d); }
+void k_bsearch_scan(FrontierDev d) { fr_scan(d); }
 
 __global__ __launch_bounds__(256)
-void k_bsearch_append(SrchDev d) { bsearch_append(d); }
+void k_bsearch_append(FrontierDev d) { fr_append(d); }
 
-__global__ void k_bsearch_end(SrchDev d) { if (threadIdx.x == 0 && blockIdx.x == 0) bsearch_end(d); }
+__global__ void k_bsearch_end(FrontierDev d) { if (threadIdx.x == 0 && blockIdx.x == 0) bsearch_end(d); }
 
-__global__ void k_bsearch_walk(SrchDev d, BallView b, int32_t *out, int max_len) { if (threadIdx.x == 0 && blockIdx.x == 0) bsearch_walk(d, b, out, max_len); }
+__global__ void k_bsearch_walk(FrontierDev d, BallView b, int32_t *out, int max_len) { if (threadIdx.x == 0 && blockIdx.x == 0) bsearch_walk(d, b, out, max_len); }
 
 // ---- the batch: S searches in lock-step, slot blockIdx.y of `devs` per workgroup row (rk_astar.hip: kb_merge_pass) ----
 // Every slot is a whole search of its own -- pool, table, counters, batch scratch, look-back words, ticket and epoch --, so a
-// launch reads and writes through devs[blockIdx.y] alone.  A slot that is done, or was never started, has S_NPOP == 0: it leaves
+// launch reads and writes through devs[blockIdx.y] alone.  A slot that is done, or was never started, has F_NPOP == 0: it leaves
 // at that read, draws no ticket and leaves its epoch alone.  The pool of a slot never grows: a slot whose next iteration might
-// not fit (size + 12 P > capacity) stops BEFORE that iteration with BS_STOP_FULL, so srch_pops() of a slot with P > 0 is P and
-// the single engine's BS_ERR_CAPACITY path is never taken.
+// not fit (size + 12 P > capacity) stops BEFORE that iteration with BS_STOP_FULL, so fr_pops() of a slot with P > 0 is P and
+// the single engine's F_ERR_CAPACITY path is never taken.
 enum { BS_STOP_FULL = 5 };
 
 // after the root or the end of an iteration of a slot: does the next iteration fit the pool whatever it finds?  One thread.
-__device__ __forceinline__ void srch_fit(const SrchDev &d)
+__device__ __forceinline__ void srch_fit(const FrontierDev &d)
 {
-	const int P = d.ctr[S_NPOP];
-	if (P == 0 || (uint64_t)d.ctr[S_SIZE] + 12ull * (uint64_t)P <= (uint64_t)d.cap1 - 1u) return;
-	d.ctr[S_STOP] = BS_STOP_FULL; d.ctr[S_DONE] = 1; d.ctr[S_NPOP] = 0;
+	const int P = d.ctr[F_NPOP];
+	if (P == 0 || (uint64_t)d.ctr[F_SIZE] + 12ull * (uint64_t)P <= (uint64_t)d.cap1 - 1u) return;
+	d.ctr[F_STOP] = BS_STOP_FULL; d.ctr[F_DONE] = 1; d.ctr[F_NPOP] = 0;
 }
 
 // the named slots' tables and look-back words, zeroed: slot slots[blockIdx.y], 16 bytes per thread and step (a table is a power of
 // two >= 1024 dwords, every slice 16-byte aligned)
 __global__ __launch_bounds__(256)
-void kb_bsearch_clear(const SrchDev *devs, const int32_t *slots, int chain_words)
+void kb_bsearch_clear(const FrontierDev *devs, const int32_t *slots, int chain_words)
 {
-	const SrchDev d = devs[slots[blockIdx.y]];
+	const FrontierDev d = devs[slots[blockIdx.y]];
 	u32x4 *t4 = reinterpret_cast<u32x4 *>(d.table);
 	const size_t n4 = ((size_t)d.mask + 1) / 4;
 	const u32x4 zero = {0u, 0u, 0u, 0u};
@@ -548,53 +547,53 @@ void kb_bsearch_clear(const SrchDev *devs, const int32_t *slots, int chain_words
 }
 
 // row j of roots / budgets starts slot slots[j]
-__global__ void kb_bsearch_root(const SrchDev *devs, BallView b, const int32_t *slots, const uint32_t *roots, const int32_t *budgets)
+__global__ void kb_bsearch_root(const FrontierDev *devs, BallView b, const int32_t *slots, const uint32_t *roots, const int32_t *budgets)
 {
-	const SrchDev d = devs[slots[blockIdx.y]];
+	const FrontierDev d = devs[slots[blockIdx.y]];
 	bsearch_root(d, b, roots + (size_t)blockIdx.y * 5, budgets[blockIdx.y]);
 	if (threadIdx.x == 0) srch_fit(d);
 }
 
 __global__ __launch_bounds__(256)
-void kb_bsearch_expand(const SrchDev *devs, BallView b)
+void kb_bsearch_expand(const FrontierDev *devs, BallView b)
 {
-	const SrchDev d = devs[blockIdx.y];
-	if (blockIdx.x * 256 >= 12 * d.ctr[S_NPOP]) return;                  // done, never started, or a workgroup past the batch
+	const FrontierDev d = devs[blockIdx.y];
+	if (blockIdx.x * 256 >= 12 * d.ctr[F_NPOP]) return;                  // done, never started, or a workgroup past the batch
 	bsearch_expand(d, b);
 }
 
 __global__ __launch_bounds__(ASCAN)
-void kb_bsearch_scan(const SrchDev *devs)
+void kb_bsearch_scan(const FrontierDev *devs)
 {
-	const SrchDev d = devs[blockIdx.y];
-	if (d.ctr[S_NPOP] == 0) return;                                      // (every workgroup of a live slot draws a ticket)
-	bsearch_scan(d);
+	const FrontierDev d = devs[blockIdx.y];
+	if (d.ctr[F_NPOP] == 0) return;                                      // (every workgroup of a live slot draws a ticket)
+	fr_scan(d);
 }
 
 __global__ __launch_bounds__(256)
-void kb_bsearch_append(const SrchDev *devs)
+void kb_bsearch_append(const FrontierDev *devs)
 {
-	const SrchDev d = devs[blockIdx.y];
-	if (blockIdx.x * 256 >= 12 * d.ctr[S_NPOP]) return;
-	bsearch_append(d);
+	const FrontierDev d = devs[blockIdx.y];
+	if (blockIdx.x * 256 >= 12 * d.ctr[F_NPOP]) return;
+	fr_append(d);
 }
 
-__global__ void kb_bsearch_end(const SrchDev *devs)
+__global__ void kb_bsearch_end(const FrontierDev *devs)
 {
 	if (threadIdx.x != 0 || blockIdx.x != 0) return;
-	const SrchDev d = devs[blockIdx.y];
-	if (d.ctr[S_NPOP] == 0) return;
+	const FrontierDev d = devs[blockIdx.y];
+	if (d.ctr[F_NPOP] == 0) return;
 	bsearch_end(d);
 	srch_fit(d);
 }
 
 // one thread per slot: row s of `out` (n_slots, 1 + max_len) = length or -1, then the queue
 __global__ __launch_bounds__(64)
-void kb_bsearch_walk(const SrchDev *devs, BallView b, int n_slots, int32_t *out, int max_len)
+void kb_bsearch_walk(const FrontierDev *devs, BallView b, int n_slots, int32_t *out, int max_len)
 {
 	const int s = blockIdx.x * 64 + threadIdx.x;
 	if (s >= n_slots) return;
-	const SrchDev d = devs[s];
+	const FrontierDev d = devs[s];
 	bsearch_walk(d, b, out + (size_t)s * (1 + max_len), max_len);
 }
 
@@ -613,15 +612,8 @@ struct rk_ball {
 	DevPool pool{64};
 };
 
-struct rk_bsearch {
-	SrchDev d{};
+struct rk_bsearch : FrontierPool {
 	rk_ball *ball = nullptr;
-	size_t cap = 0;
-	uint32_t *root_dev = nullptr;
-	int32_t *walk = nullptr;
-	Landing ctr_host;
-	bool ready = false;
-	DevPool pool{64};
 };
 
 // S searches in lock-step: one block of every kind of array, sliced per slot; devs[s] on the device describes slot s
@@ -630,8 +622,8 @@ struct rk_bsearchb {
 	int n_slots = 0, pops = 0;
 	size_t cap = 0;                             // per slot
 	uint32_t mask = 0;
-	SrchDev d{};                                // slot 0: the blocks' base addresses
-	SrchDev *devs = nullptr;
+	FrontierDev d{};                                // slot 0: the blocks' base addresses
+	FrontierDev *devs = nullptr;
 	int32_t *slots_dev = nullptr, *budgets_dev = nullptr;
 	uint32_t *roots_dev = nullptr;
 	int32_t *walk = nullptr;
@@ -657,9 +649,7 @@ constexpr size_t SHORTEN_MAX_WAVES = (size_t)1 << 30;    // queues x max_len of 
 // the d(i, j) bytes of a call, rounded up so that the pred rows behind them are aligned
 size_t shorten_depth_bytes(size_t n, int max_len, int window) { return (n * (size_t)max_len * (size_t)window + 15) & ~(size_t)15; }
 
-uint32_t ball_table_mask(size_t capacity) { return (uint32_t)(table_slots(capacity, 1024) - 1); }
-
-int bsearch_read_ctr(rk_bsearch *h, int32_t *out, hipStream_t st) { return h->ctr_host.read(h->d.ctr, S_COUNT, out, st); }
+uint32_t ball_table_mask(size_t capacity) { return FrontierPool::table_mask(capacity); }
 
 // queries: n 20-byte rows on the device, read as dwords
 int check_queries(const char *who, const rk_ball *h, const void *d_states, size_t n, const void *out)
@@ -760,17 +750,7 @@ int rk_ball_export(rk_ball_t *h, size_t first, size_t count, int8_t *h_states, l
 	if (!h) return fail(RK_EINVAL, "rk_ball_export: null ball");
 	if (!h->built) return fail(RK_ESTATE, "rk_ball_export: build the ball first");
 	if (first + count > h->cap + 1) return fail(RK_EINVAL, "rk_ball_export: rows %zu..%zu outside the pool", first, first + count);
-	if (count == 0) return RK_OK;
-	hipStream_t st = (hipStream_t)stream;
-	const BallDev &d = h->d;
-	Widened<int32_t, long long> p;
-	Widened<uint8_t, long long> a;
-	if (h_states) RK_HIP(hipMemcpyAsync(h_states, d.states + first * 5, count * STATE_BYTES, hipMemcpyDeviceToHost, st));
-	if (int e = p.start(d.parent + first, count, h_parents, st)) return e;
-	if (int e = a.start(d.pact + first, count, h_actions, st)) return e;
-	RK_HIP(hipStreamSynchronize(st));
-	p.finish(); a.finish();
-	return RK_OK;
+	return export_pool_rows(h->d.states, h->d.parent, h->d.pact, first, count, h_states, h_parents, h_actions, nullptr, (hipStream_t)stream);
 }
 
 int rk_ball_depth(rk_ball_t *h, const int8_t *d_states, size_t n, int32_t *d_depth, void *stream)
@@ -831,24 +811,9 @@ int rk_bshorten(rk_ball_t *h, const int8_t *d_actions, const int32_t *d_len, siz
 int rk_bsearch_create(rk_bsearch_t **out, rk_ball_t *ball, size_t capacity, int pops)
 {
 	if (!out || !ball) return fail(RK_EINVAL, "rk_bsearch_create: null argument");
-	if (capacity < 2 || capacity > BS_MAX_CAPACITY) return fail(RK_EINVAL, "rk_bsearch_create: capacity %zu out of range", capacity);
-	if (pops < 1 || pops > (1 << 22)) return fail(RK_EINVAL, "rk_bsearch_create: pops %d outside 1..%d", pops, 1 << 22);
+	if (int e = FrontierPool::check_create("rk_bsearch_create", capacity, pops)) return e;
 	rk_bsearch *h = new rk_bsearch();
-	h->cap = capacity;
-	SrchDev &d = h->d;
-	d.pops = pops;
-	d.cap1 = (uint32_t)(capacity + 1);
-	d.mask = ball_table_mask(capacity);
-	const size_t C1 = capacity + 1, K = (size_t)12 * pops;
-	int e = RK_OK;
-	#define A(ptr, cnt) if (!e) e = h->pool.alloc(&d.ptr, (cnt))
-	A(states, C1 * 5); A(parent, C1); A(pact, C1); A(table, (size_t)d.mask + 1); A(ctr, S_COUNT);
-	A(slot, K); A(rank, K); A(first, K); A(chain, frontier_scan_blocks(pops));
-	#undef A
-	if (!e) e = h->pool.alloc(&h->root_dev, 8);
-	if (!e) e = h->pool.alloc(&h->walk, BS_WALK_MAX + 8);
-	if (!e) h->ctr_host.reserve(S_COUNT);
-	if (e) { delete h; return e; }
+	if (int e = h->alloc(capacity, pops, S_COUNT)) { delete h; return e; }
 	h->ball = ball;
 	ball->attached += 1;
 	*out = h;
@@ -867,112 +832,54 @@ int rk_bsearch_reset(rk_bsearch_t *h, const int8_t *h_start_state, long long max
 	if (!h || !h_start_state) return fail(RK_EINVAL, "rk_bsearch_reset: null argument");
 	if (!h->ball->built) return fail(RK_ESTATE, "rk_bsearch_reset: build the ball first");
 	hipStream_t st = (hipStream_t)stream;
-	SrchDev &d = h->d;
-	RK_HIP(hipMemsetAsync(d.table, 0, ((size_t)d.mask + 1) * sizeof(uint32_t), st));                        // the own table only
-	RK_HIP(hipMemsetAsync(d.chain, 0, frontier_scan_blocks(d.pops) * sizeof(unsigned long long), st));
-	RK_HIP(hipMemcpyAsync(h->root_dev, h_start_state, STATE_BYTES, hipMemcpyHostToDevice, st));
-	hipLaunchKernelGGL(k_bsearch_root, dim3(1), dim3(64), 0, st, d, h->ball->view, h->root_dev, budget_of(max_states));
-	RK_HIP(hipGetLastError());
-	RK_HIP(hipStreamSynchronize(st));       // the host buffer may go away after return
-	h->ready = true;
-	return RK_OK;
+	return h->reset(h_start_state, st, [&] {
+		hipLaunchKernelGGL(k_bsearch_root, dim3(1), dim3(64), 0, st, h->d, h->ball->view, h->root_dev, budget_of(max_states));
+	});
 }
 
 int rk_bsearch_run(rk_bsearch_t *h, int iterations, void *stream)
 {
-	if (!h || !h->ready) return fail(RK_ESTATE, "rk_bsearch_run: reset the engine first");
-	if (iterations < 0) return fail(RK_EINVAL, "rk_bsearch_run: iterations %d < 0", iterations);
+	if (int e = FrontierPool::check_ready(h, "rk_bsearch_run")) return e;
 	hipStream_t st = (hipStream_t)stream;
-	const SrchDev &d = h->d;
-	const BallView &b = h->ball->view;
-	const unsigned grid = blocks((size_t)12 * d.pops);
-	for (int it = 0; it < iterations; it++) {
-		hipLaunchKernelGGL(k_bsearch_expand, dim3(grid), dim3(256), 0, st, d, b);
-		hipLaunchKernelGGL(k_bsearch_scan, dim3(blocks((size_t)12 * d.pops, ASCAN)), dim3(ASCAN), 0, st, d);
-		hipLaunchKernelGGL(k_bsearch_append, dim3(grid), dim3(256), 0, st, d);
-		hipLaunchKernelGGL(k_bsearch_end, dim3(1), dim3(64), 0, st, d);
-	}
-	RK_HIP(hipGetLastError());
-	return RK_OK;
+	return h->run("rk_bsearch_run", iterations, st,
+	              [&](unsigned grid) { hipLaunchKernelGGL(k_bsearch_expand, dim3(grid), dim3(256), 0, st, h->d, h->ball->view); },
+	              k_bsearch_scan, k_bsearch_append, k_bsearch_end);
 }
 
 int rk_bsearch_status(rk_bsearch_t *h, long long *h_status, void *stream)
 {
 	if (!h || !h->ready || !h_status) return fail(RK_EINVAL, "rk_bsearch_status: bad argument");
 	int32_t c[S_COUNT];
-	if (int e = bsearch_read_ctr(h, c, (hipStream_t)stream)) return e;
-	h_status[0] = c[S_DONE]; h_status[1] = c[S_WON]; h_status[2] = c[S_SIZE]; h_status[3] = c[S_ITERS];
-	h_status[4] = c[S_POPPED]; h_status[5] = c[S_STOP]; h_status[6] = c[S_ERROR]; h_status[7] = c[S_NPOP];
-	h_status[8] = c[S_DEPTH]; h_status[9] = c[S_MEET];
+	if (int e = h->read_ctr(c, (hipStream_t)stream)) return e;
+	bsearch_status_words(c, h_status);
 	return RK_OK;
 }
 
 int rk_bsearch_grow(rk_bsearch_t *h, size_t new_capacity, void *stream)
 {
-	if (!h || !h->ready) return fail(RK_ESTATE, "rk_bsearch_grow: reset the engine first");
-	if (new_capacity <= h->cap) return new_capacity == h->cap ? RK_OK : fail(RK_EINVAL, "rk_bsearch_grow: %zu is below the current capacity %zu", new_capacity, h->cap);
-	if (new_capacity > BS_MAX_CAPACITY) return fail(RK_EINVAL, "rk_bsearch_grow: capacity %zu out of range", new_capacity);
-	hipStream_t st = (hipStream_t)stream;
-	const SrchDev old = h->d;
-	SrchDev d = old;
-	const size_t C1 = new_capacity + 1, C1_old = h->cap + 1;
-	d.cap1 = (uint32_t)C1;
-	d.mask = ball_table_mask(new_capacity);
-	Growth g(h->pool, "rk_bsearch_grow");
-	g.request(&d.states, C1 * 5); g.request(&d.parent, C1); g.request(&d.pact, C1); g.request(&d.table, (size_t)d.mask + 1);
-	if (!g.granted()) return fail(RK_ECAPACITY, "rk_bsearch_grow: no device memory for a pool of %zu states", new_capacity);
-	const int e = g.fill(st, [&]() -> hipError_t {
-		RK_FILL(hipMemcpyAsync(d.states, old.states, C1_old * STATE_BYTES, hipMemcpyDeviceToDevice, st));
-		RK_FILL(hipMemcpyAsync(d.parent, old.parent, C1_old * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-		RK_FILL(hipMemcpyAsync(d.pact, old.pact, C1_old, hipMemcpyDeviceToDevice, st));
-		RK_FILL(hipMemsetAsync(d.table, 0, ((size_t)d.mask + 1) * sizeof(uint32_t), st));
-		hipLaunchKernelGGL(k_bsearch_rehash, dim3(std::min<unsigned>(blocks(C1_old), 4096u)), dim3(256), 0, st, d);
-		return hipGetLastError();
-	});
-	if (e) return e;
-	g.commit();
-	h->d = d;
-	h->cap = new_capacity;
-	return RK_OK;
+	if (int e = FrontierPool::check_ready(h, "rk_bsearch_grow")) return e;
+	return h->grow("rk_bsearch_grow", new_capacity, k_bsearch_rehash, (hipStream_t)stream);
 }
 
-long long rk_bsearch_size(const rk_bsearch_t *hc)
-{
-	rk_bsearch_t *h = const_cast<rk_bsearch_t *>(hc);
-	if (!h || !h->ready) return 0;
-	int32_t c[S_COUNT];
-	if (bsearch_read_ctr(h, c, nullptr)) return RK_EHIP;
-	return c[S_SIZE];
-}
+long long rk_bsearch_size(const rk_bsearch_t *h) { return FrontierPool::size(h); }
 
 int rk_bsearch_export(rk_bsearch_t *h, size_t first, size_t count, int8_t *h_states, long long *h_parents, long long *h_actions, void *stream)
 {
-	if (!h || !h->ready) return fail(RK_ESTATE, "rk_bsearch_export: reset the engine first");
-	if (first + count > h->cap + 1) return fail(RK_EINVAL, "rk_bsearch_export: rows %zu..%zu outside the pool", first, first + count);
-	if (count == 0) return RK_OK;
-	hipStream_t st = (hipStream_t)stream;
-	const SrchDev &d = h->d;
-	Widened<int32_t, long long> p;
-	Widened<uint8_t, long long> a;
-	if (h_states) RK_HIP(hipMemcpyAsync(h_states, d.states + first * 5, count * STATE_BYTES, hipMemcpyDeviceToHost, st));
-	if (int e = p.start(d.parent + first, count, h_parents, st)) return e;
-	if (int e = a.start(d.pact + first, count, h_actions, st)) return e;
-	RK_HIP(hipStreamSynchronize(st));
-	p.finish(); a.finish();
-	return RK_OK;
+	if (int e = FrontierPool::check_ready(h, "rk_bsearch_export")) return e;
+	return h->export_rows("rk_bsearch_export", first, count, h_states, h_parents, h_actions, nullptr, (hipStream_t)stream);
 }
 
 int rk_bsearchb_create(rk_bsearchb_t **out, rk_ball_t *ball, int n_slots, size_t capacity_per_slot, int pops)
 {
 	if (!out || !ball) return fail(RK_EINVAL, "rk_bsearchb_create: null argument");
 	if (n_slots < 1 || n_slots > BSB_MAX_SLOTS) return fail(RK_EINVAL, "rk_bsearchb_create: n_slots %d outside 1..%d", n_slots, BSB_MAX_SLOTS);
-	if (capacity_per_slot < 2 || capacity_per_slot > BS_MAX_CAPACITY) return fail(RK_EINVAL, "rk_bsearchb_create: capacity %zu out of range", capacity_per_slot);
+	if (capacity_per_slot < 2 || capacity_per_slot > FRONTIER_MAX_CAPACITY) return fail(RK_EINVAL, "rk_bsearchb_create: capacity %zu out of range", capacity_per_slot);
 	if (pops < 1 || pops > (1 << 22)) return fail(RK_EINVAL, "rk_bsearchb_create: pops %d outside 1..%d", pops, 1 << 22);
 	rk_bsearchb *h = new rk_bsearchb();
 	h->n_slots = n_slots; h->pops = pops; h->cap = capacity_per_slot;
 	h->mask = ball_table_mask(capacity_per_slot);
 	const size_t S = (size_t)n_slots, C1 = capacity_per_slot + 1, T = (size_t)h->mask + 1, K = (size_t)12 * pops, W = frontier_scan_blocks(pops);
-	SrchDev &d = h->d;
+	FrontierDev &d = h->d;
 	d.pops = pops;
 	d.cap1 = (uint32_t)C1;
 	d.mask = h->mask;
@@ -986,14 +893,14 @@ int rk_bsearchb_create(rk_bsearchb_t **out, rk_ball_t *ball, int n_slots, size_t
 	if (!e) e = h->pool.alloc(&h->budgets_dev, S);
 	if (!e) e = h->pool.alloc(&h->roots_dev, S * 5);
 	if (e) { (void)hipGetLastError(); delete h; return fail(RK_ECAPACITY, "rk_bsearchb_create: no device memory for %d pools of %zu states", n_slots, capacity_per_slot); }
-	std::vector<SrchDev> devs(S, d);
+	std::vector<FrontierDev> devs(S, d);
 	for (size_t s = 0; s < S; s++) {
-		SrchDev &x = devs[s];
+		FrontierDev &x = devs[s];
 		x.states += s * C1 * 5; x.parent += s * C1; x.pact += s * C1; x.table += s * T; x.ctr += s * S_COUNT;
 		x.slot += s * K; x.rank += s * K; x.first += s * K; x.chain += s * W;
 	}
-	hipError_t he = hipMemcpy(h->devs, devs.data(), S * sizeof(SrchDev), hipMemcpyHostToDevice);
-	if (he == hipSuccess) he = hipMemset(d.ctr, 0, S * S_COUNT * sizeof(int32_t));      // never started: S_NPOP == 0, every launch passes it by
+	hipError_t he = hipMemcpy(h->devs, devs.data(), S * sizeof(FrontierDev), hipMemcpyHostToDevice);
+	if (he == hipSuccess) he = hipMemset(d.ctr, 0, S * S_COUNT * sizeof(int32_t));      // never started: F_NPOP == 0, every launch passes it by
 	if (he != hipSuccess) { delete h; return fail(RK_EHIP, "rk_bsearchb_create: %s", hipGetErrorString(he)); }
 	h->ctr_host.reserve(S * S_COUNT);
 	h->ctr_spare.resize(S * S_COUNT);
@@ -1061,11 +968,8 @@ int rk_bsearchb_status(rk_bsearchb_t *h, long long *h_status, void *stream)
 	if (!h || !h_status) return fail(RK_EINVAL, "rk_bsearchb_status: null argument");
 	const int32_t *c = nullptr;
 	if (int e = h->ctr_host.fetch(h->d.ctr, (size_t)h->n_slots * S_COUNT, h->ctr_spare.data(), (hipStream_t)stream, &c)) return e;
-	for (int s = 0; s < h->n_slots; s++, c += S_COUNT) {
-		long long *o = h_status + (size_t)s * 10;
-		o[0] = c[S_DONE]; o[1] = c[S_WON]; o[2] = c[S_SIZE]; o[3] = c[S_ITERS]; o[4] = c[S_POPPED]; o[5] = c[S_STOP]; o[6] = c[S_ERROR];
-		o[7] = c[S_NPOP]; o[8] = c[S_DEPTH]; o[9] = c[S_MEET];
-	}
+	for (int s = 0; s < h->n_slots; s++, c += S_COUNT)
+		bsearch_status_words(c, h_status + (size_t)s * 10);
 	return RK_OK;
 }
 
@@ -1073,7 +977,7 @@ int rk_bsearchb_paths(rk_bsearchb_t *h, int32_t *h_out, int max_len, void *strea
 {
 	if (!h || !h_out) return fail(RK_EINVAL, "rk_bsearchb_paths: null argument");
 	if (!h->ball->built) return fail(RK_ESTATE, "rk_bsearchb_paths: build the ball first");
-	if (max_len < 0 || max_len > BS_WALK_MAX) return fail(RK_EINVAL, "rk_bsearchb_paths: max_len %d outside 0..%d", max_len, BS_WALK_MAX);
+	if (max_len < 0 || max_len > FRONTIER_WALK_MAX) return fail(RK_EINVAL, "rk_bsearchb_paths: max_len %d outside 0..%d", max_len, FRONTIER_WALK_MAX);
 	hipStream_t st = (hipStream_t)stream;
 	const size_t words = (size_t)h->n_slots * (size_t)(1 + max_len);
 	if (h->walk == nullptr || h->walk_len < max_len) {
@@ -1094,28 +998,20 @@ int rk_bsearchb_export(rk_bsearchb_t *h, int slot, size_t first, size_t count, i
 	if (!h) return fail(RK_EINVAL, "rk_bsearchb_export: null engine");
 	if (slot < 0 || slot >= h->n_slots) return fail(RK_EINVAL, "rk_bsearchb_export: slot %d outside 0..%d", slot, h->n_slots - 1);
 	if (first + count > h->cap + 1) return fail(RK_EINVAL, "rk_bsearchb_export: rows %zu..%zu outside the pool", first, first + count);
-	if (count == 0) return RK_OK;
-	hipStream_t st = (hipStream_t)stream;
-	const size_t at = (size_t)slot * (h->cap + 1) + first;
-	Widened<int32_t, long long> p;
-	Widened<uint8_t, long long> a;
-	if (h_states) RK_HIP(hipMemcpyAsync(h_states, h->d.states + at * 5, count * STATE_BYTES, hipMemcpyDeviceToHost, st));
-	if (int e = p.start(h->d.parent + at, count, h_parents, st)) return e;
-	if (int e = a.start(h->d.pact + at, count, h_actions, st)) return e;
-	RK_HIP(hipStreamSynchronize(st));
-	p.finish(); a.finish();
-	return RK_OK;
+	const size_t at = (size_t)slot * (h->cap + 1);
+	return export_pool_rows(h->d.states + at * 5, h->d.parent + at, h->d.pact + at, first, count, h_states, h_parents, h_actions, nullptr,
+	                        (hipStream_t)stream);
 }
 
 long long rk_bsearch_path(rk_bsearch_t *h, long long *h_actions, size_t max_len, void *stream)
 {
-	if (!h || !h->ready) return fail(RK_ESTATE, "rk_bsearch_path: reset the engine first");
+	if (int e = FrontierPool::check_ready(h, "rk_bsearch_path")) return e;
 	if (!h_actions && max_len > 0) return fail(RK_EINVAL, "rk_bsearch_path: null h_actions with max_len %zu", max_len);
 	hipStream_t st = (hipStream_t)stream;
-	hipLaunchKernelGGL(k_bsearch_walk, dim3(1), dim3(64), 0, st, h->d, h->ball->view, h->walk, BS_WALK_MAX);
+	hipLaunchKernelGGL(k_bsearch_walk, dim3(1), dim3(64), 0, st, h->d, h->ball->view, h->walk, FRONTIER_WALK_MAX);
 	RK_HIP(hipGetLastError());
 	int32_t len = 0;
-	if (int e = read_walk(h->walk, BS_WALK_MAX, h_actions, max_len, st, &len)) return e;
+	if (int e = read_walk(h->walk, FRONTIER_WALK_MAX, h_actions, max_len, st, &len)) return e;
 	if (len < 0) return fail(RK_ESTATE, "rk_bsearch_path: the search has not met the ball (or a parent chain is broken)");
 	return (long long)len;
 }

@@ -1,0 +1,167 @@
+// The frontier pool: what every breadth-first engine that keeps its whole search in HBM shares on the device -- rk_bfs.hip,
+// rk_bibfs.hip, rk_ball.hip's search from a start (rk_bsearch_*) and its batch (rk_bsearchb_*), and rk_sym.hip's search that ends
+// at the symmetry-reduced ball (rk_ssearch_*).  One descriptor, the common counter words, and the launches of an iteration that
+// do not look at what the engine searches for: the scan, the append, the end of an iteration with the cut, and the rehash after
+// a growth.  An engine keeps what makes it different: its counter words behind F_COMMON, its `next` (what follows a pop count
+// change: the end of a level, the done flags, the next P), its root, its expand launch -- the membership rule -- and its walk.
+// The host side is FrontierPool (rk_search_host.h).
+//
+// An iteration pops the P = F_NPOP nodes head .. head + P - 1 and is expand, scan, append, end; none synchronises with the host.
+// Pop j of the batch runs only if size_before + (new states of the pops before j) < budget, and the winning child is the lowest
+// batch position the expand launch entered in F_WINPOS among the pops that run.  The cut is min(12 x the first refused pop, the
+// winning position); no child at or after it is appended or counted.  Claims at or after the cut stay in the table only when the
+// search has ended.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "rk_device.h"
+#include "rk_search_dev.h"
+
+namespace rk {
+
+// the counter words every engine has; an engine's own words start at F_COMMON
+enum {
+	F_SIZE = 0, F_HEAD, F_DONE, F_WON, F_WPARENT, F_WACT, F_STOP, F_ITERS, F_ERROR, F_NPOP, F_BUDGET, F_WINPOS, F_TOTAL, F_EPOCH,
+	F_TICKET, F_COMMON
+};
+enum { F_STOP_NO = 0, F_STOP_WON = 1, F_STOP_BUDGET = 2, F_STOP_EMPTY = 3, F_STOP_ERROR = 4 };
+enum { F_ERR_NONE = 0, F_ERR_CAPACITY = 1 };
+enum { F_UNRECORDED = -1 };                     // fr_end: the engine has no such counter word
+
+constexpr uint32_t F_NO_WIN = 0x7FFFFFFFu;
+constexpr uint32_t PACT_TAG_SHIFT = 4;          // pact = action | tag << 4 (the tag is rk_bibfs.hip's side; 0 everywhere else)
+constexpr uint32_t PACT_ACTION = 15u;
+
+struct FrontierDev {
+	uint32_t mask, cap1;                        // table slots - 1, capacity + 1
+	int pops;                                   // the most nodes an iteration pops (grid size)
+	uint32_t *states; int32_t *parent; uint8_t *pact; uint32_t *table;
+	int32_t *ctr;
+	uint32_t *slot; int32_t *rank; uint8_t *first;                   // per child of the batch: claimed slot (or TENT | meeting node), exclusive prefix, first occurrence
+	unsigned long long *chain;                                        // look-back words {epoch, total} of the scan
+};
+
+// The pops of this iteration, or 0 when it is done -- or when its children might not fit the pool: the host grows the pool
+// before such an iteration, so that never cuts one; should it happen every kernel skips the iteration and fr_end reports
+// an error.  Every kernel of the iteration reads the same counters, so they agree.
+__device__ __forceinline__ int fr_pops(const FrontierDev &d)
+{
+	const int P = d.ctr[F_NPOP];
+	return (uint64_t)d.ctr[F_SIZE] + 12ull * (uint64_t)P <= (uint64_t)d.cap1 - 1u ? P : 0;
+}
+
+// first-occurrence flags and their exclusive prefix in batch order (tickets + look-back: rk_search_dev.h)
+__device__ __forceinline__ void fr_scan(const FrontierDev &d)
+{
+	const int P = fr_pops(d);
+	if (P == 0) return;                                                  // done: no ticket drawn, nothing to reset
+	frontier_scan(d.slot, d.table, d.rank, d.first, d.chain, &d.ctr[F_TICKET], (uint32_t)d.ctr[F_EPOCH] + 1u, &d.ctr[F_TOTAL], 12 * P);
+}
+
+// The cut and the append: child c is stored iff it is a first occurrence, lies before the winning position and its pop runs --
+// size_before + (new states of the earlier pops) < budget.  That prefix only grows along the batch, so this is exactly "c is
+// before the cut".  New states get the indices size + 1 ... in batch order with their parent and action; their tentative claims
+// become those indices.  tag() is read for a child that is stored: what goes into pact above the action.
+template <typename Tag>
+__device__ __forceinline__ void fr_append(const FrontierDev &d, Tag &&tag)
+{
+	__shared__ u32x4 s_act[36];
+	stage_action_tables(s_act, threadIdx.x);
+	__syncthreads();
+	const int P = fr_pops(d);
+	const int c = blockIdx.x * blockDim.x + threadIdx.x;
+	if (c >= 12 * P || !d.first[c]) return;
+	if ((uint32_t)c >= (uint32_t)d.ctr[F_WINPOS]) return;
+	const int i = c / 12, a = c - 12 * i;
+	const int32_t size0 = d.ctr[F_SIZE];
+	if ((long long)size0 + d.rank[12 * i] >= (long long)d.ctr[F_BUDGET]) return;
+	const uint32_t idx = (uint32_t)size0 + 1u + (uint32_t)d.rank[c];
+	if (idx >= d.cap1) { d.ctr[F_ERROR] = F_ERR_CAPACITY; return; }
+	const int32_t p = d.ctr[F_HEAD] + i;
+	uint32_t s[5];
+	child_state(d.states, p, s_act, (uint32_t)a, s);
+	#pragma unroll
+	for (int j = 0; j < 5; j++) d.states[(size_t)idx * 5 + j] = s[j];
+	d.parent[idx] = p;
+	d.pact[idx] = (uint8_t)((uint32_t)a | (tag() << PACT_TAG_SHIFT));
+	d.table[d.slot[c]] = idx;
+}
+__device__ __forceinline__ void fr_append(const FrontierDev &d) { fr_append(d, [] { return 0u; }); }
+
+// Where the cut fell, the new size / head, the win, then next(d): the done flags and the next P; resets the per-iteration
+// counters.  One thread, ordinary stores.  MEET and POPPED are the engine's counter words for the node a winning child met
+// (slot[win] without the TENT bit) and the nodes popped so far, or F_UNRECORDED for an engine without them.
+template <int MEET, int POPPED, typename Next>
+__device__ __forceinline__ void fr_end(const FrontierDev &d, Next &&next)
+{
+	if (d.ctr[F_NPOP] == 0) return;
+	const int P = fr_pops(d);
+	if (P == 0) {
+		d.ctr[F_ERROR] = F_ERR_CAPACITY;
+		d.ctr[F_STOP] = F_STOP_ERROR; d.ctr[F_DONE] = 1; d.ctr[F_NPOP] = 0;
+		return;
+	}
+	const int32_t size0 = d.ctr[F_SIZE], head = d.ctr[F_HEAD];
+	const int lo = first_refused_pop(d.rank, P, size0, d.ctr[F_BUDGET]); // the first pop that fails the budget check (P: none)
+	const int cut_b = 12 * lo;
+	const int win = d.ctr[F_WINPOS];
+	const int cut = min(cut_b, win);
+	const int n_new = cut < 12 * P ? d.rank[cut] : d.ctr[F_TOTAL];
+	d.ctr[F_SIZE] = size0 + n_new;
+	d.ctr[F_ITERS] += 1;
+	d.ctr[F_TICKET] = 0;
+	d.ctr[F_EPOCH] += 1;
+	d.ctr[F_WINPOS] = (int32_t)F_NO_WIN;
+	if (d.ctr[F_ERROR]) {
+		d.ctr[F_STOP] = F_STOP_ERROR; d.ctr[F_DONE] = 1; d.ctr[F_NPOP] = 0;
+	} else if (win < cut_b) {                                            // the first win among the pops that run
+		d.ctr[F_WON] = 1;
+		d.ctr[F_WPARENT] = head + win / 12;
+		d.ctr[F_WACT] = win % 12;
+		if constexpr (MEET != F_UNRECORDED) d.ctr[MEET] = (int32_t)(d.slot[win] & ~TENT);
+		d.ctr[F_HEAD] = head + win / 12 + 1;
+		if constexpr (POPPED != F_UNRECORDED) d.ctr[POPPED] += win / 12 + 1;
+		d.ctr[F_STOP] = F_STOP_WON; d.ctr[F_DONE] = 1; d.ctr[F_NPOP] = 0;
+	} else if (lo < P) {                                                 // the budget refused pop `lo`
+		d.ctr[F_HEAD] = head + lo;
+		if constexpr (POPPED != F_UNRECORDED) d.ctr[POPPED] += lo;
+		d.ctr[F_STOP] = F_STOP_BUDGET; d.ctr[F_DONE] = 1; d.ctr[F_NPOP] = 0;
+	} else {
+		d.ctr[F_HEAD] = head + P;
+		if constexpr (POPPED != F_UNRECORDED) d.ctr[POPPED] += P;
+		next(d);
+	}
+}
+
+// after a growth: every stored state back into the larger, cleared table (grid-stride).  Between iterations of a running search
+// no slot is tentative, so this is a plain insert of indices 1..size.
+__device__ __forceinline__ void fr_rehash(const FrontierDev &d)
+{
+	rehash_pool(d.states, d.table, d.mask, d.ctr[F_SIZE], 1 + blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
+}
+
+// ---- the searches that end at a kept ball (rk_bsearch_*, rk_bsearchb_*, rk_ssearch_*): one side, level by level ----
+enum { S_DEPTH = F_COMMON, S_HI, S_MEET, S_POPPED, S_COUNT = 32 };
+
+// After a pop count change: the end of a level, the done flags and the next P (rk_bibfs.hip: bibfs_next, one side).  One thread.
+__device__ __forceinline__ void srch_next(const FrontierDev &d)
+{
+	const int32_t size = d.ctr[F_SIZE], head = d.ctr[F_HEAD];
+	int32_t hi = d.ctr[S_HI];
+	if (head > hi) {                                                     // the level is exhausted and nothing met: it is complete
+		d.ctr[S_DEPTH] += 1;
+		d.ctr[S_HI] = hi = size;
+	}
+	int stop = F_STOP_NO;
+	if (head > hi) stop = F_STOP_EMPTY;                                  // a level without a state: the whole graph was seen
+	else if (size >= d.ctr[F_BUDGET]) stop = F_STOP_BUDGET;             // checked before the next pop
+	d.ctr[F_STOP] = stop;
+	d.ctr[F_DONE] = stop ? 1 : 0;
+	d.ctr[F_NPOP] = stop ? 0 : min(d.pops, hi - head + 1);
+}
+
+__device__ __forceinline__ void bsearch_end(const FrontierDev &d) { fr_end<S_MEET, S_POPPED>(d, [](const FrontierDev &x) { srch_next(x); }); }
+
+constexpr int FRONTIER_WALK_MAX = 1 << 12;
+
+}  // namespace rk

@@ -1,6 +1,7 @@
 // Host-side pieces shared by the search engines (A* single / sharded / batched, breadth-first search, MCTS): who owns a device
-// allocation, growing arrays in place as one transaction, and the small read-backs every engine needs.  The counterpart of
-// rk_search_dev.h; header-only, nothing in here is exported.
+// allocation, growing arrays in place as one transaction, the small read-backs every engine needs, and FrontierPool, the host
+// half of the breadth-first engines' pool (rk_frontier_dev.h).  The counterpart of rk_search_dev.h; header-only, nothing in
+// here is exported.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -10,6 +11,7 @@
 
 #include "../../include/rubiks_hip.h"
 #include "rk_error.h"
+#include "rk_frontier_dev.h"
 
 namespace rk {
 namespace {
@@ -209,6 +211,174 @@ inline int read_walk(const int32_t *walk, size_t walk_max, long long *h_actions,
 	RK_HIP(hipStreamSynchronize(st));
 	if (*len < 0) return RK_OK;
 	return export_widened(walk + 1, std::min(std::min((size_t)*len, max_len), walk_max), h_actions, st);
+}
+
+// Rows first .. first + count - 1 of a breadth-first pool for the host: states as they are, parents widened, pact split into the
+// action and the tag above it (rk_frontier_dev.h: PACT_TAG_SHIFT).  A null column asks for nothing.
+inline int export_pool_rows(const uint32_t *states, const int32_t *parent, const uint8_t *pact, size_t first, size_t count, int8_t *h_states,
+                            long long *h_parents, long long *h_actions, long long *h_tags, hipStream_t st)
+{
+	if (count == 0) return RK_OK;
+	Widened<int32_t, long long> p;
+	std::vector<uint8_t> pa;
+	if (h_states) RK_HIP(hipMemcpyAsync(h_states, states + first * 5, count * STATE_BYTES, hipMemcpyDeviceToHost, st));
+	if (int e = p.start(parent + first, count, h_parents, st)) return e;
+	if (h_actions || h_tags) {
+		pa.resize(count);
+		RK_HIP(hipMemcpyAsync(pa.data(), pact + first, count, hipMemcpyDeviceToHost, st));
+	}
+	RK_HIP(hipStreamSynchronize(st));
+	p.finish();
+	for (size_t i = 0; i < pa.size(); i++) {
+		if (h_actions) h_actions[i] = pa[i] & PACT_ACTION;
+		if (h_tags) h_tags[i] = pa[i] >> PACT_TAG_SHIFT;
+	}
+	return RK_OK;
+}
+
+// The host half of a frontier pool (rk_frontier_dev.h): the descriptor and what the engines rk_bfs, rk_bibfs, rk_bsearch and
+// rk_ssearch do with it in the same way.  An engine's handle is this plus its own members; its entries check their arguments
+// and call one of these with their own name as `who`, the prefix of every error text.
+constexpr size_t FRONTIER_MAX_CAPACITY = 0x3FFFFFF0ull;
+constexpr int FRONTIER_MAX_POPS = 1 << 22;
+constexpr int FRONTIER_MAX_COUNTERS = 32;
+
+struct FrontierPool {
+	using Kernel = void (*)(FrontierDev);
+
+	FrontierDev d{};
+	size_t cap = 0;
+	uint32_t *root_dev = nullptr;
+	int32_t *walk = nullptr;                    // what the walk kernel writes: FRONTIER_WALK_MAX actions behind the length
+	Landing ctr_host;                           // page-locked landing place of the counter block
+	int n_ctr = 0;
+	bool ready = false;
+	DevPool pool{64};
+
+	static uint32_t table_mask(size_t capacity) { return (uint32_t)(table_slots(capacity, 1024) - 1); }
+
+	// the range checks of a *_create
+	static int check_create(const char *who, size_t capacity, int pops)
+	{
+		if (capacity < 2 || capacity > FRONTIER_MAX_CAPACITY) return fail(RK_EINVAL, "%s: capacity %zu out of range", who, capacity);
+		if (pops < 1 || pops > FRONTIER_MAX_POPS) return fail(RK_EINVAL, "%s: pops %d outside 1..%d", who, pops, FRONTIER_MAX_POPS);
+		return RK_OK;
+	}
+	// *_run, *_grow, *_export, *_path of a handle that was never reset
+	static int check_ready(const FrontierPool *h, const char *who)
+	{
+		return h && h->ready ? RK_OK : fail(RK_ESTATE, "%s: reset the engine first", who);
+	}
+
+	// every array of a pool of `capacity` states that pops `pops` nodes per iteration and has `counters` counter words
+	int alloc(size_t capacity, int pops, int counters)
+	{
+		cap = capacity;
+		n_ctr = counters;
+		d.pops = pops;
+		d.cap1 = (uint32_t)(capacity + 1);
+		d.mask = table_mask(capacity);
+		const size_t C1 = capacity + 1, K = (size_t)12 * pops;
+		int e = RK_OK;
+		#define A(ptr, cnt) if (!e) e = pool.alloc(&ptr, (cnt))
+		A(d.states, C1 * 5); A(d.parent, C1); A(d.pact, C1); A(d.table, (size_t)d.mask + 1); A(d.ctr, (size_t)counters);
+		A(d.slot, K); A(d.rank, K); A(d.first, K); A(d.chain, frontier_scan_blocks(pops));
+		A(root_dev, 8); A(walk, FRONTIER_WALK_MAX + 8);
+		#undef A
+		if (!e) ctr_host.reserve((size_t)counters);
+		return e;
+	}
+
+	// a new search: the table and the look-back words cleared, the start on the device, then the engine's root launch
+	template <typename Root>
+	int reset(const int8_t *h_start_state, hipStream_t st, Root &&launch_root)
+	{
+		RK_HIP(hipMemsetAsync(d.table, 0, ((size_t)d.mask + 1) * sizeof(uint32_t), st));                        // the own table only
+		RK_HIP(hipMemsetAsync(d.chain, 0, frontier_scan_blocks(d.pops) * sizeof(unsigned long long), st));      // look-back epochs restart
+		RK_HIP(hipMemcpyAsync(root_dev, h_start_state, STATE_BYTES, hipMemcpyHostToDevice, st));
+		launch_root();
+		RK_HIP(hipGetLastError());
+		RK_HIP(hipStreamSynchronize(st));       // the host buffer may go away after return
+		ready = true;
+		return RK_OK;
+	}
+
+	// `iterations` iterations: the engine's expand launch(es) on a grid of `grid` workgroups of 256, then scan, append and end
+	template <typename Expand>
+	int run(const char *who, int iterations, hipStream_t st, Expand &&launch_expand, Kernel scan, Kernel append, Kernel end)
+	{
+		if (iterations < 0) return fail(RK_EINVAL, "%s: iterations %d < 0", who, iterations);
+		const size_t K = (size_t)12 * d.pops;
+		const unsigned grid = blocks(K);
+		for (int it = 0; it < iterations; it++) {
+			launch_expand(grid);
+			hipLaunchKernelGGL(scan, dim3(blocks(K, ASCAN)), dim3(ASCAN), 0, st, d);
+			hipLaunchKernelGGL(append, dim3(grid), dim3(256), 0, st, d);
+			hipLaunchKernelGGL(end, dim3(1), dim3(64), 0, st, d);
+		}
+		RK_HIP(hipGetLastError());
+		return RK_OK;
+	}
+
+	// the table cleared and every stored state entered again
+	static hipError_t rebuild_table(const FrontierDev &x, size_t rows, Kernel rehash, hipStream_t st)
+	{
+		RK_FILL(hipMemsetAsync(x.table, 0, ((size_t)x.mask + 1) * sizeof(uint32_t), st));
+		hipLaunchKernelGGL(rehash, dim3(std::max<unsigned>(1u, std::min<unsigned>(blocks(rows), 4096u))), dim3(256), 0, st, x);
+		return hipGetLastError();
+	}
+
+	// the pool, its parents and actions and its table in place at `new_capacity`, all or nothing
+	int grow(const char *who, size_t new_capacity, Kernel rehash, hipStream_t st)
+	{
+		if (new_capacity <= cap) return new_capacity == cap ? RK_OK : fail(RK_EINVAL, "%s: %zu is below the current capacity %zu", who, new_capacity, cap);
+		if (new_capacity > FRONTIER_MAX_CAPACITY) return fail(RK_EINVAL, "%s: capacity %zu out of range", who, new_capacity);
+		const FrontierDev old = d;
+		FrontierDev x = old;
+		const size_t C1 = new_capacity + 1, C1_old = cap + 1;
+		x.cap1 = (uint32_t)C1;
+		x.mask = table_mask(new_capacity);
+		Growth g(pool, who);
+		g.request(&x.states, C1 * 5); g.request(&x.parent, C1); g.request(&x.pact, C1); g.request(&x.table, (size_t)x.mask + 1);
+		if (!g.granted()) return fail(RK_ECAPACITY, "%s: no device memory for a pool of %zu states", who, new_capacity);
+		const int e = g.fill(st, [&]() -> hipError_t {
+			RK_FILL(hipMemcpyAsync(x.states, old.states, C1_old * STATE_BYTES, hipMemcpyDeviceToDevice, st));
+			RK_FILL(hipMemcpyAsync(x.parent, old.parent, C1_old * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+			RK_FILL(hipMemcpyAsync(x.pact, old.pact, C1_old, hipMemcpyDeviceToDevice, st));
+			return rebuild_table(x, C1_old, rehash, st);
+		});
+		if (e) return e;
+		g.commit();
+		d = x;
+		cap = new_capacity;
+		return RK_OK;
+	}
+
+	int read_ctr(int32_t *out, hipStream_t st) { return ctr_host.read(d.ctr, (size_t)n_ctr, out, st); }
+
+	// *_size: the states stored, 0 before the first reset
+	static long long size(const FrontierPool *hc)
+	{
+		FrontierPool *h = const_cast<FrontierPool *>(hc);
+		if (!h || !h->ready) return 0;
+		int32_t c[FRONTIER_MAX_COUNTERS];
+		if (h->read_ctr(c, nullptr)) return RK_EHIP;
+		return c[F_SIZE];
+	}
+
+	int export_rows(const char *who, size_t first, size_t count, int8_t *h_states, long long *h_parents, long long *h_actions, long long *h_tags,
+	                hipStream_t st)
+	{
+		if (first + count > cap + 1) return fail(RK_EINVAL, "%s: rows %zu..%zu outside the pool", who, first, first + count);
+		return export_pool_rows(d.states, d.parent, d.pact, first, count, h_states, h_parents, h_actions, h_tags, st);
+	}
+};
+
+// the ten status words of a search that ends at a kept ball (rk_bsearch_status, a slot of rk_bsearchb_status, rk_ssearch_status)
+inline void bsearch_status_words(const int32_t *c, long long *o)
+{
+	o[0] = c[F_DONE]; o[1] = c[F_WON]; o[2] = c[F_SIZE]; o[3] = c[F_ITERS]; o[4] = c[S_POPPED]; o[5] = c[F_STOP]; o[6] = c[F_ERROR];
+	o[7] = c[F_NPOP]; o[8] = c[S_DEPTH]; o[9] = c[S_MEET];
 }
 
 }  // namespace

@@ -37,11 +37,11 @@
 // holds this child's representative".  A state lies in the plain ball of radius R exactly when its representative lies in this
 // one, so the own pool, the depth, the pops and the meeting child are rk_bsearch's on a plain ball of the same radius, bit for
 // bit.  The election among the children of a batch is on the raw child, so no representative goes to scratch: a canonical form
-// takes a wave, the election a thread, hence one launch more than rk_bsearch, the rest is shared (rk_bsearch_dev.h)
+// takes a wave, the election a thread, hence one launch more than rk_bsearch, the rest is shared (rk_frontier_dev.h)
 //   k_ss_probe    a wave per child: fan-out, canonical form, read-only probe of the ball  -> hit (12 P): the ball's node or 0
 //   k_ss_expand   a thread per child: hit != 0 is a meeting (atomicMin on the win position, no claim), else membership / election
 //                 in the own table on the raw child
-//   k_ss_scan, k_ss_append, k_ss_end   bsearch_scan, bsearch_append, bsearch_end; S_MEET is the node in THIS ball
+//   k_ss_scan, k_ss_append, k_ss_end   fr_scan, fr_append, bsearch_end; S_MEET is the node in THIS ball
 //   k_ss_walk     one wave: the own path and the meeting action, then the descent from the meeting state (sb_descend)
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -49,7 +49,7 @@
 #include <cstring>
 
 #include "../../include/rubiks_hip.h"
-#include "rk_bsearch_dev.h"
+#include "rk_frontier_dev.h"
 #include "rk_device.h"
 #include "rk_error.h"
 #include "rk_search_dev.h"
@@ -264,7 +264,7 @@ void k_sb_solve(SymBallView b, const uint32_t *queries, size_t n, int32_t *lengt
 // ---- the search from a start towards the symmetry ball ----------------------------------------------------------------------
 // One wave: node 1 = the start, whose representative is looked up in the ball (bsearch_root with that one difference).
 __global__ __launch_bounds__(64)
-void k_ss_root(SrchDev d, SymBallView b, const uint32_t *root, int budget)
+void k_ss_root(FrontierDev d, SymBallView b, const uint32_t *root, int budget)
 {
 	__shared__ uint32_t s_sym[SYM_LDS_DWORDS];
 	const int lane = threadIdx.x;
@@ -282,12 +282,12 @@ void k_ss_root(SrchDev d, SymBallView b, const uint32_t *root, int budget)
 	for (int j = 0; j < 5; j++) d.states[5 + j] = s[j];
 	d.parent[1] = 0; d.pact[1] = 0;
 	d.table[hash_state(s) & d.mask] = 1u;
-	d.ctr[S_SIZE] = 1; d.ctr[S_HEAD] = 1; d.ctr[S_HI] = 1;
-	d.ctr[S_BUDGET] = budget;
-	d.ctr[S_WINPOS] = (int32_t)BS_NO_WIN;
+	d.ctr[F_SIZE] = 1; d.ctr[F_HEAD] = 1; d.ctr[S_HI] = 1;
+	d.ctr[F_BUDGET] = budget;
+	d.ctr[F_WINPOS] = (int32_t)F_NO_WIN;
 	if (e != 0u) {                                                       // the ball holds the start's orbit: nothing is popped
-		d.ctr[S_WON] = 1; d.ctr[S_MEET] = (int32_t)e;
-		d.ctr[S_STOP] = BS_STOP_WON; d.ctr[S_DONE] = 1;
+		d.ctr[F_WON] = 1; d.ctr[S_MEET] = (int32_t)e;
+		d.ctr[F_STOP] = F_STOP_WON; d.ctr[F_DONE] = 1;
 		return;
 	}
 	srch_next(d);
@@ -296,18 +296,18 @@ void k_ss_root(SrchDev d, SymBallView b, const uint32_t *root, int budget)
 // hit[c] = the ball's node of the representative of child c of the batch, 0 when the ball does not hold it: waves stride over
 // the children (k_sb_canon's grid), nothing but hit is written
 __global__ __launch_bounds__(256)
-void k_ss_probe(SrchDev d, SymBallView b, uint32_t *hit)
+void k_ss_probe(FrontierDev d, SymBallView b, uint32_t *hit)
 {
 	__shared__ uint32_t s_sym[SYM_LDS_DWORDS];
 	__shared__ u32x4 s_act[36];
-	const int K = 12 * srch_pops(d);
+	const int K = 12 * fr_pops(d);
 	if ((int)blockIdx.x * 4 >= K) return;                                // done, or a workgroup past the batch: nothing staged
 	sym_stage(s_sym, threadIdx.x, 256);
 	stage_action_tables(s_act, threadIdx.x);
 	__syncthreads();
 	const int lane = threadIdx.x & 63;
 	const SymLane L = sym_lane(min(lane, N_SYM - 1));
-	const int32_t head = d.ctr[S_HEAD];
+	const int32_t head = d.ctr[F_HEAD];
 	for (int c = blockIdx.x * 4 + (threadIdx.x >> 6); c < K; c += gridDim.x * 4) {       // (whole waves)
 		const int i = c / 12, a = c - 12 * i;
 		uint32_t x[5], rep[5];
@@ -321,21 +321,21 @@ void k_ss_probe(SrchDev d, SymBallView b, uint32_t *hit)
 
 // a meeting child leaves no claim; any other: membership / election in the own table on the raw child (bsearch_expand)
 __global__ __launch_bounds__(256)
-void k_ss_expand(SrchDev d, const uint32_t *hit)
+void k_ss_expand(FrontierDev d, const uint32_t *hit)
 {
 	__shared__ u32x4 s_act[36];
 	stage_action_tables(s_act, threadIdx.x);
 	__syncthreads();
-	const int P = srch_pops(d);
+	const int P = fr_pops(d);
 	const int c = blockIdx.x * blockDim.x + threadIdx.x;
 	if (c >= 12 * P) return;
 	const uint32_t m = hit[c];
 	if (m != 0u) {
-		atomicMin(reinterpret_cast<uint32_t *>(&d.ctr[S_WINPOS]), (uint32_t)c);
+		atomicMin(reinterpret_cast<uint32_t *>(&d.ctr[F_WINPOS]), (uint32_t)c);
 		d.slot[c] = TENT | m;                                            // no claim (TENT bit); bsearch_end reads the meeting node here
 		return;
 	}
-	const int32_t head = d.ctr[S_HEAD];
+	const int32_t head = d.ctr[F_HEAD];
 	const int i = c / 12, a = c - 12 * i;
 	uint32_t s[5];
 	child_state(d.states, head + i, s_act, (uint32_t)a, s);
@@ -346,22 +346,22 @@ void k_ss_expand(SrchDev d, const uint32_t *hit)
 }
 
 __global__ __launch_bounds__(ASCAN)
-void k_ss_scan(SrchDev d) { bsearch_scan(d); }
+void k_ss_scan(FrontierDev d) { fr_scan(d); }
 
 __global__ __launch_bounds__(256)
-void k_ss_append(SrchDev d) { bsearch_append(d); }
+void k_ss_append(FrontierDev d) { fr_append(d); }
 
-__global__ void k_ss_end(SrchDev d) { if (threadIdx.x == 0 && blockIdx.x == 0) bsearch_end(d); }
+__global__ void k_ss_end(FrontierDev d) { if (threadIdx.x == 0 && blockIdx.x == 0) bsearch_end(d); }
 
 __global__ __launch_bounds__(256)
-void k_ss_rehash(SrchDev d) { bsearch_rehash(d); }
+void k_ss_rehash(FrontierDev d) { fr_rehash(d); }
 
 // The action queue of a won search, one wave: the path from the start to the popped parent and the meeting action (none of either
 // when the ball holds the start's orbit), then the descent from the meeting state.  out[0] = length, -1 when the search has not
 // met or a parent chain is broken, -2 when the meeting state is not where S_MEET says or the descent finds no way on.  Every lane
 // computes the same; lane 0 writes.
 __global__ __launch_bounds__(64)
-void k_ss_walk(SrchDev d, SymBallView b, int32_t *out, int max_len)
+void k_ss_walk(FrontierDev d, SymBallView b, int32_t *out, int max_len)
 {
 	__shared__ uint32_t s_sym[SYM_LDS_DWORDS];
 	__shared__ u32x4 s_act[36];
@@ -370,8 +370,8 @@ void k_ss_walk(SrchDev d, SymBallView b, int32_t *out, int max_len)
 	stage_action_tables(s_act, lane);
 	__syncthreads();
 	if (lane == 0) out[0] = -1;
-	if (!d.ctr[S_WON]) return;
-	const int p = d.ctr[S_WPARENT];
+	if (!d.ctr[F_WON]) return;
+	const int p = d.ctr[F_WPARENT];
 	int ls = 0;
 	for (int i = p; p != 0 && i != 1; ls++) {
 		if (i < 1 || (uint32_t)i >= d.cap1 || ls > (int)d.cap1) return;
@@ -385,7 +385,7 @@ void k_ss_walk(SrchDev d, SymBallView b, int32_t *out, int max_len)
 	int len = ls;
 	uint32_t x[5];
 	if (p != 0) {
-		const int a = d.ctr[S_WACT];
+		const int a = d.ctr[F_WACT];
 		if ((uint32_t)a >= (uint32_t)N_ACTIONS) return;
 		if (len < max_len && lane == 0) out[1 + len] = a;
 		len++;
@@ -456,16 +456,9 @@ struct rk_symball {
 	DevPool pool{64};
 };
 
-struct rk_ssearch {
-	SrchDev d{};
+struct rk_ssearch : FrontierPool {
 	uint32_t *hit = nullptr;                    // per child of the batch: the ball's node of its representative, or 0
 	rk_symball *ball = nullptr;
-	size_t cap = 0;
-	uint32_t *root_dev = nullptr;
-	int32_t *walk = nullptr;
-	Landing ctr_host;
-	bool ready = false;
-	DevPool pool{64};
 };
 
 namespace {
@@ -492,8 +485,6 @@ int check_sym_states(const char *who, const void *d_states, size_t n)
 	if ((uintptr_t)d_states & 3u) return fail(RK_EINVAL, "%s: device pointers must be 4-byte aligned", who);
 	return RK_OK;
 }
-
-int ssearch_read_ctr(rk_ssearch *h, int32_t *out, hipStream_t st) { return h->ctr_host.read(h->d.ctr, S_COUNT, out, st); }
 
 int check_sb_queries(const char *who, const rk_symball *h, const void *d_states, size_t n, const void *out)
 {
@@ -676,25 +667,11 @@ int rk_symball_solve(rk_symball_t *h, const int8_t *d_states, size_t n, int32_t 
 int rk_ssearch_create(rk_ssearch_t **out, rk_symball_t *ball, size_t capacity, int pops)
 {
 	if (!out || !ball) return fail(RK_EINVAL, "rk_ssearch_create: null argument");
-	if (capacity < 2 || capacity > BS_MAX_CAPACITY) return fail(RK_EINVAL, "rk_ssearch_create: capacity %zu out of range", capacity);
-	if (pops < 1 || pops > (1 << 22)) return fail(RK_EINVAL, "rk_ssearch_create: pops %d outside 1..%d", pops, 1 << 22);
+	if (int e = FrontierPool::check_create("rk_ssearch_create", capacity, pops)) return e;
 	if (!ball->built) return fail(RK_ESTATE, "rk_ssearch_create: build the ball first");
 	rk_ssearch *h = new rk_ssearch();
-	h->cap = capacity;
-	SrchDev &d = h->d;
-	d.pops = pops;
-	d.cap1 = (uint32_t)(capacity + 1);
-	d.mask = (uint32_t)(table_slots(capacity, 1024) - 1);
-	const size_t C1 = capacity + 1, K = (size_t)12 * pops;
-	int e = RK_OK;
-	#define A(ptr, cnt) if (!e) e = h->pool.alloc(&d.ptr, (cnt))
-	A(states, C1 * 5); A(parent, C1); A(pact, C1); A(table, (size_t)d.mask + 1); A(ctr, S_COUNT);
-	A(slot, K); A(rank, K); A(first, K); A(chain, frontier_scan_blocks(pops));
-	#undef A
-	if (!e) e = h->pool.alloc(&h->hit, K);
-	if (!e) e = h->pool.alloc(&h->root_dev, 8);
-	if (!e) e = h->pool.alloc(&h->walk, BS_WALK_MAX + 8);
-	if (!e) h->ctr_host.reserve(S_COUNT);
+	int e = h->alloc(capacity, pops, S_COUNT);
+	if (!e) e = h->pool.alloc(&h->hit, (size_t)12 * pops);
 	if (e) { delete h; return e; }
 	h->ball = ball;
 	ball->attached += 1;
@@ -714,112 +691,56 @@ int rk_ssearch_reset(rk_ssearch_t *h, const int8_t *h_start_state, long long max
 	if (!h || !h_start_state) return fail(RK_EINVAL, "rk_ssearch_reset: null argument");
 	if (!h->ball->built) return fail(RK_ESTATE, "rk_ssearch_reset: build the ball first");
 	hipStream_t st = (hipStream_t)stream;
-	SrchDev &d = h->d;
-	RK_HIP(hipMemsetAsync(d.table, 0, ((size_t)d.mask + 1) * sizeof(uint32_t), st));                        // the own table only
-	RK_HIP(hipMemsetAsync(d.chain, 0, frontier_scan_blocks(d.pops) * sizeof(unsigned long long), st));
-	RK_HIP(hipMemcpyAsync(h->root_dev, h_start_state, STATE_BYTES, hipMemcpyHostToDevice, st));
-	hipLaunchKernelGGL(k_ss_root, dim3(1), dim3(64), 0, st, d, h->ball->view, h->root_dev, budget_of(max_states));
-	RK_HIP(hipGetLastError());
-	RK_HIP(hipStreamSynchronize(st));       // the host buffer may go away after return
-	h->ready = true;
-	return RK_OK;
+	return h->reset(h_start_state, st, [&] {
+		hipLaunchKernelGGL(k_ss_root, dim3(1), dim3(64), 0, st, h->d, h->ball->view, h->root_dev, budget_of(max_states));
+	});
 }
 
 int rk_ssearch_run(rk_ssearch_t *h, int iterations, void *stream)
 {
-	if (!h || !h->ready) return fail(RK_ESTATE, "rk_ssearch_run: reset the engine first");
-	if (iterations < 0) return fail(RK_EINVAL, "rk_ssearch_run: iterations %d < 0", iterations);
+	if (int e = FrontierPool::check_ready(h, "rk_ssearch_run")) return e;
 	hipStream_t st = (hipStream_t)stream;
-	const SrchDev &d = h->d;
-	const SymBallView &b = h->ball->view;
-	const size_t K = (size_t)12 * d.pops;
-	const unsigned grid = blocks(K);
-	for (int it = 0; it < iterations; it++) {
-		hipLaunchKernelGGL(k_ss_probe, dim3(sym_grid(K)), dim3(256), 0, st, d, b, h->hit);
-		hipLaunchKernelGGL(k_ss_expand, dim3(grid), dim3(256), 0, st, d, h->hit);
-		hipLaunchKernelGGL(k_ss_scan, dim3(blocks(K, ASCAN)), dim3(ASCAN), 0, st, d);
-		hipLaunchKernelGGL(k_ss_append, dim3(grid), dim3(256), 0, st, d);
-		hipLaunchKernelGGL(k_ss_end, dim3(1), dim3(64), 0, st, d);
-	}
-	RK_HIP(hipGetLastError());
-	return RK_OK;
+	const unsigned probe_grid = sym_grid((size_t)12 * h->d.pops);
+	return h->run("rk_ssearch_run", iterations, st,
+	              [&](unsigned grid) {
+		              hipLaunchKernelGGL(k_ss_probe, dim3(probe_grid), dim3(256), 0, st, h->d, h->ball->view, h->hit);
+		              hipLaunchKernelGGL(k_ss_expand, dim3(grid), dim3(256), 0, st, h->d, h->hit);
+	              },
+	              k_ss_scan, k_ss_append, k_ss_end);
 }
 
 int rk_ssearch_status(rk_ssearch_t *h, long long *h_status, void *stream)
 {
 	if (!h || !h->ready || !h_status) return fail(RK_EINVAL, "rk_ssearch_status: bad argument");
 	int32_t c[S_COUNT];
-	if (int e = ssearch_read_ctr(h, c, (hipStream_t)stream)) return e;
-	h_status[0] = c[S_DONE]; h_status[1] = c[S_WON]; h_status[2] = c[S_SIZE]; h_status[3] = c[S_ITERS];
-	h_status[4] = c[S_POPPED]; h_status[5] = c[S_STOP]; h_status[6] = c[S_ERROR]; h_status[7] = c[S_NPOP];
-	h_status[8] = c[S_DEPTH]; h_status[9] = c[S_MEET];
+	if (int e = h->read_ctr(c, (hipStream_t)stream)) return e;
+	bsearch_status_words(c, h_status);
 	return RK_OK;
 }
 
 int rk_ssearch_grow(rk_ssearch_t *h, size_t new_capacity, void *stream)
 {
-	if (!h || !h->ready) return fail(RK_ESTATE, "rk_ssearch_grow: reset the engine first");
-	if (new_capacity <= h->cap) return new_capacity == h->cap ? RK_OK : fail(RK_EINVAL, "rk_ssearch_grow: %zu is below the current capacity %zu", new_capacity, h->cap);
-	if (new_capacity > BS_MAX_CAPACITY) return fail(RK_EINVAL, "rk_ssearch_grow: capacity %zu out of range", new_capacity);
-	hipStream_t st = (hipStream_t)stream;
-	const SrchDev old = h->d;
-	SrchDev d = old;
-	const size_t C1 = new_capacity + 1, C1_old = h->cap + 1;
-	d.cap1 = (uint32_t)C1;
-	d.mask = (uint32_t)(table_slots(new_capacity, 1024) - 1);
-	Growth g(h->pool, "rk_ssearch_grow");
-	g.request(&d.states, C1 * 5); g.request(&d.parent, C1); g.request(&d.pact, C1); g.request(&d.table, (size_t)d.mask + 1);
-	if (!g.granted()) return fail(RK_ECAPACITY, "rk_ssearch_grow: no device memory for a pool of %zu states", new_capacity);
-	const int e = g.fill(st, [&]() -> hipError_t {
-		RK_FILL(hipMemcpyAsync(d.states, old.states, C1_old * STATE_BYTES, hipMemcpyDeviceToDevice, st));
-		RK_FILL(hipMemcpyAsync(d.parent, old.parent, C1_old * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-		RK_FILL(hipMemcpyAsync(d.pact, old.pact, C1_old, hipMemcpyDeviceToDevice, st));
-		RK_FILL(hipMemsetAsync(d.table, 0, ((size_t)d.mask + 1) * sizeof(uint32_t), st));
-		hipLaunchKernelGGL(k_ss_rehash, dim3(std::min<unsigned>(blocks(C1_old), 4096u)), dim3(256), 0, st, d);
-		return hipGetLastError();
-	});
-	if (e) return e;
-	g.commit();
-	h->d = d;
-	h->cap = new_capacity;
-	return RK_OK;
+	if (int e = FrontierPool::check_ready(h, "rk_ssearch_grow")) return e;
+	return h->grow("rk_ssearch_grow", new_capacity, k_ss_rehash, (hipStream_t)stream);
 }
 
-long long rk_ssearch_size(const rk_ssearch_t *hc)
-{
-	rk_ssearch_t *h = const_cast<rk_ssearch_t *>(hc);
-	if (!h || !h->ready) return 0;
-	int32_t c[S_COUNT];
-	if (ssearch_read_ctr(h, c, nullptr)) return RK_EHIP;
-	return c[S_SIZE];
-}
+long long rk_ssearch_size(const rk_ssearch_t *h) { return FrontierPool::size(h); }
 
 int rk_ssearch_export(rk_ssearch_t *h, size_t first, size_t count, int8_t *h_states, long long *h_parents, long long *h_actions, void *stream)
 {
-	if (!h || !h->ready) return fail(RK_ESTATE, "rk_ssearch_export: reset the engine first");
-	if (first + count > h->cap + 1) return fail(RK_EINVAL, "rk_ssearch_export: rows %zu..%zu outside the pool", first, first + count);
-	if (count == 0) return RK_OK;
-	hipStream_t st = (hipStream_t)stream;
-	const SrchDev &d = h->d;
-	Widened<int32_t, long long> p;
-	Widened<uint8_t, long long> a;
-	if (h_states) RK_HIP(hipMemcpyAsync(h_states, d.states + first * 5, count * STATE_BYTES, hipMemcpyDeviceToHost, st));
-	if (int e = p.start(d.parent + first, count, h_parents, st)) return e;
-	if (int e = a.start(d.pact + first, count, h_actions, st)) return e;
-	RK_HIP(hipStreamSynchronize(st));
-	p.finish(); a.finish();
-	return RK_OK;
+	if (int e = FrontierPool::check_ready(h, "rk_ssearch_export")) return e;
+	return h->export_rows("rk_ssearch_export", first, count, h_states, h_parents, h_actions, nullptr, (hipStream_t)stream);
 }
 
 long long rk_ssearch_path(rk_ssearch_t *h, long long *h_actions, size_t max_len, void *stream)
 {
-	if (!h || !h->ready) return fail(RK_ESTATE, "rk_ssearch_path: reset the engine first");
+	if (int e = FrontierPool::check_ready(h, "rk_ssearch_path")) return e;
 	if (!h_actions && max_len > 0) return fail(RK_EINVAL, "rk_ssearch_path: null h_actions with max_len %zu", max_len);
 	hipStream_t st = (hipStream_t)stream;
-	hipLaunchKernelGGL(k_ss_walk, dim3(1), dim3(64), 0, st, h->d, h->ball->view, h->walk, BS_WALK_MAX);
+	hipLaunchKernelGGL(k_ss_walk, dim3(1), dim3(64), 0, st, h->d, h->ball->view, h->walk, FRONTIER_WALK_MAX);
 	RK_HIP(hipGetLastError());
 	int32_t len = 0;
-	if (int e = read_walk(h->walk, BS_WALK_MAX, h_actions, max_len, st, &len)) return e;
+	if (int e = read_walk(h->walk, FRONTIER_WALK_MAX, h_actions, max_len, st, &len)) return e;
 	if (len == -2) return fail(RK_ESTATE, "rk_ssearch_path: the meeting state has no way down the ball (or is not where the search met)");
 	if (len < 0) return fail(RK_ESTATE, "rk_ssearch_path: the search has not met the ball (or a parent chain is broken)");
 	return (long long)len;

@@ -172,6 +172,17 @@ def kept_graph(agent, key: tuple, warm, step, oh: torch.Tensor, keep):
 	return graph, False
 
 
+# -- arguments ---------------------------------------------------------------------------------------------------------
+def int_in(name: str, value, lo: int, hi: int = None, none_ok: bool = False, what: str = None):
+	"""`value` as an int when it is an integer (no bool, no fraction) in lo..hi -- `hi` None: no upper limit --, None for a None
+	that `none_ok` allows; else ValueError "<name> must be <what>, got <value>", `what` by default "an integer in lo..hi"."""
+	if value is None and none_ok:
+		return None
+	if isinstance(value, bool) or int(value) != value or int(value) < lo or (hi is not None and int(value) > hi):
+		raise ValueError(f"{name} must be {what or f'an integer in {lo}..{hi}'}, got {value!r}")
+	return int(value)
+
+
 # -- the search loop and its results ----------------------------------------------------------------------------------------
 def burst(poll: int, room: int, K: int) -> int:
 	"""Iterations to launch before the host looks again.  Never launch past the budget: a search grows by at most K states per
@@ -221,3 +232,15 @@ def export_pool(entry, lead: tuple, n: int, rows: int = None):
 	if n and entry is not None:
 		_ffi.check(entry(*lead, 1, n, states[1:].ctypes.data, G[1:].ctypes.data, parents[1:].ctypes.data, pact[1:].ctypes.data, _ffi.stream_ptr()))
 	return states, G, parents, pact
+
+
+def export_frontier(entry, lead: tuple, n: int, firsts: int = 1, tags: bool = False) -> tuple:
+	"""(states, parents, actions[, tags]) with n + 1 rows of a breadth-first pool (the frontier pool of DESIGN 3.5): rows 1..n are
+	filled by `entry(*lead, 1, n, ...)`, an engine's `*_export` (None: there is no engine yet), row 0 stays zero.  The first `firsts`
+	nodes have no parent: their action is -1.  `tags`: the export has a fourth column (DeviceBiBFS's sides)."""
+	states = np.zeros((n + 1, 20), np.int8)
+	cols = [np.zeros(n + 1, np.int64) for _ in range(3 if tags else 2)]
+	if n and entry is not None:
+		_ffi.check(entry(*lead, 1, n, states[1:].ctypes.data, *(c[1:].ctypes.data for c in cols), _ffi.stream_ptr()))
+	cols[1][1:1 + min(firsts, n)] = -1
+	return (states, *cols)

@@ -282,7 +282,126 @@ class BFS(Agent):
 		return len(self.states)
 
 
-class DeviceBFS(Agent, _ffi.Owner):
+class _PoolSearch(Agent, _ffi.Owner):
+	"""What the agents that drive a frontier pool share -- `DeviceBFS`, `DeviceBiBFS` and the searches that end at a
+	kept ball: the arguments and their checks, the engine that is kept between searches, the pool growth, the host loop of a
+	search and the export of the pool.  A subclass names its engine and maps the status words that are its own."""
+	default_capacity = 8_000_000
+	max_capacity = 400_000_000
+	MAX_POPS = 1 << 22                      # the limit of every rk_*_create
+	MAX_CAPACITY = 0x3FFFFFF0
+	_entries = None                         # the prefix of the engine's entry points
+	_status_words = 8                       # what its *_status writes
+	_first_nodes = 1                        # nodes a reset stores (they have no parent)
+	_unlimited = False                      # a search may run without either limit (an exact search)
+	_engine_name = None                     # in the text of an engine error
+
+	def __init__(self, pops: int = 16_384, capacity: int = None, max_capacity: int = None, poll: int = 8):
+		super().__init__()
+		self.pops = eng.int_in("pops", pops, 1, self.MAX_POPS)
+		self.capacity = eng.int_in("capacity", capacity, 2, self.MAX_CAPACITY, none_ok=True)
+		if eng.int_in("max_capacity", max_capacity, 2, self.MAX_CAPACITY, none_ok=True) is not None:
+			self.max_capacity = int(max_capacity)
+		self.poll = eng.int_in("poll", poll, 1, what="a positive integer")
+		self._h, self._h_cap = None, 0
+		self._n = 0
+		self._is2024 = True
+		self._cache = None
+		self.iterations = 0
+		self.popped = 0                     # nodes the last search popped (each has 12 children)
+		self.grown = 0
+		self.capacity_exhausted = False
+
+	def _entry(self, name: str):
+		return getattr(_ffi.lib(), f"{self._entries}_{name}")
+
+	def _create_args(self) -> tuple:
+		"""What the engine's create takes before the capacity and the pops."""
+		return ()
+
+	def _engine(self, capacity: int):
+		if self._h is not None and self._h_cap >= capacity:
+			return self._h                  # (a pool that grew in an earlier search is kept: the reset clears its table)
+		self._h_cap = capacity
+		return self._create(f"{self._entries}_create", f"{self._entries}_destroy", *self._create_args(), capacity, self.pops)
+
+	def _grow(self, h) -> bool:
+		if self._h_cap >= self.max_capacity:
+			eng.pool_exhausted(self, self._h_cap, "cannot take the next iteration")
+			return False
+		cap = min(2 * self._h_cap, self.max_capacity)
+		_ffi.check(self._entry("grow")(h, cap, _ffi.stream_ptr()))
+		self._h_cap = cap
+		self.grown += 1
+		return True
+
+	def _begin(self, root: np.ndarray) -> bool:
+		"""Before the engine is touched: clears the subclass's results; True when `root` needs no search."""
+		raise NotImplementedError
+
+	def _read(self, status):
+		"""The status words beyond states and iterations, to their attributes."""
+		raise NotImplementedError
+
+	@no_grad
+	def search(self, state: np.ndarray, time_limit: float = None, max_states: int = None) -> bool:
+		_ffi.require_gpu()
+		t0 = time.perf_counter()
+		time_limit, max_states = self.reset(time_limit or 1e10 if self._unlimited else time_limit, max_states)
+		self._n, self._cache, self.iterations, self.grown, self.capacity_exhausted = 0, None, 0, 0, False
+		self.popped = 0
+		self._is2024 = cube.get_is2024()
+		root = _roots20(self._is2024, state, 1)[0]          # ValueError for an illegal 6x8x6 state
+		if self._begin(root):
+			return True
+		stream = _ffi.stream_ptr()
+		run, read_status = self._entry("run"), self._entry("status")
+		K = 12 * self.pops
+		budget = int(min(max_states, 2 ** 31 - 1))
+		cap = self.capacity or min(budget + K, self.default_capacity)
+		cap = max(2, min(cap, self.max_capacity, self.MAX_CAPACITY))
+		h = self._engine(cap)
+		_ffi.check(self._entry("reset")(h, root.ctypes.data, budget, stream))
+		self._n = self._first_nodes
+		status = (C.c_longlong * self._status_words)()
+		_ffi.check(read_status(h, status, stream))
+		self._read(status)                                   # (a start that is answered at once: done, with its meeting)
+		while not status[0]:
+			room = (self._h_cap - self._n) // K              # iterations the pool takes whatever they find
+			if room == 0:
+				if not self._grow(h):
+					return False
+				continue
+			_ffi.check(run(h, eng.burst(min(self.poll, room), budget - self._n, K), stream))
+			_ffi.check(read_status(h, status, stream))
+			self._n, self.iterations = int(status[2]), int(status[3])
+			self._read(status)
+			if status[6]:
+				raise _ffi.RubiksHipError(f"{self._engine_name} engine error code {int(status[6])}")
+			if not status[0] and time.perf_counter() - t0 >= time_limit:
+				return False
+		if status[1]:
+			self.action_queue = eng.read_path(self._entry("path"), h)
+			return True
+		return False
+
+	def _pool(self, tags: bool = False) -> tuple:
+		"""arrays() of the pool: rows 1 .. len(agent), the states in the search's representation."""
+		if self._cache is None:
+			n = self._n
+			states, *cols = eng.export_frontier(self._entry("export") if self._h is not None else None, (self._h,), n, self._first_nodes, tags)
+			self._cache = (_states_out(self._is2024, states, n)[1:], *(c[1:] for c in cols))
+		return self._cache
+
+	def arrays(self):
+		"""(states, parents, actions) of the pool's nodes 1 .. len(agent) in index order, as `DeviceBFS.arrays()`."""
+		return self._pool()
+
+	def __len__(self):
+		return self._n
+
+
+class DeviceBFS(_PoolSearch):
 	"""
 	Breadth-first search (agents.py:92-129) with the whole search in HBM (engine rk_bfs_*, csrc/rk_bfs.hip): the node pool, the
 	parent and action of every node, and a hash table of the states seen.  The FIFO queue is the pool in index order.  One
@@ -299,102 +418,22 @@ class DeviceBFS(Agent, _ffi.Owner):
 	The representation follows cube.get_is2024() when a search starts; the engine always runs on 20-byte states (the two forms
 	map one to one under the same moves), so `states` and `arrays()` convert on the way out.
 	"""
-	default_capacity = 8_000_000
-	max_capacity = 400_000_000
-	MAX_POPS = 1 << 22                      # rk_bfs_create's limit
-	MAX_CAPACITY = 0x3FFFFFF0
+	_entries = "rk_bfs"
+	_engine_name = "BFS"
 
 	def __init__(self, pops: int = 16_384, capacity: int = None, max_capacity: int = None, poll: int = 8):
-		super().__init__()
-		if isinstance(pops, bool) or int(pops) != pops or not 1 <= int(pops) <= self.MAX_POPS:
-			raise ValueError(f"pops must be an integer in 1..{self.MAX_POPS}, got {pops!r}")
-		for name, v in (("capacity", capacity), ("max_capacity", max_capacity)):
-			if v is not None and (isinstance(v, bool) or int(v) != v or not 2 <= int(v) <= self.MAX_CAPACITY):
-				raise ValueError(f"{name} must be an integer in 2..{self.MAX_CAPACITY}, got {v!r}")
-		if isinstance(poll, bool) or int(poll) != poll or int(poll) < 1:
-			raise ValueError(f"poll must be a positive integer, got {poll!r}")
-		self.pops, self.poll = int(pops), int(poll)
-		self.capacity = int(capacity) if capacity is not None else None
-		if max_capacity is not None:
-			self.max_capacity = int(max_capacity)
-		self._h, self._h_cap = None, 0
-		self._n = 0
-		self._is2024 = True
-		self._cache = None
-		self.iterations = 0
-		self.popped = 0                     # queued nodes the last search popped (each has 12 children)
-		self.grown = 0
-		self.capacity_exhausted = False
+		super().__init__(pops, capacity, max_capacity, poll)
 
-	def _engine(self, capacity: int):
-		if self._h is not None and self._h_cap >= capacity:
-			return self._h                  # (a pool that grew in an earlier search is kept: rk_bfs_reset clears its table)
-		self._h_cap = capacity
-		return self._create("rk_bfs_create", "rk_bfs_destroy", capacity, self.pops)
+	def _begin(self, root) -> bool:
+		return bool((root == _SOLVED20).all())
 
-	def _grow(self, h) -> bool:
-		if self._h_cap >= self.max_capacity:
-			eng.pool_exhausted(self, self._h_cap, "cannot take the next iteration")
-			return False
-		cap = min(2 * self._h_cap, self.max_capacity)
-		_ffi.check(_ffi.lib().rk_bfs_grow(h, cap, _ffi.stream_ptr()))
-		self._h_cap = cap
-		self.grown += 1
-		return True
-
-	@no_grad
-	def search(self, state: np.ndarray, time_limit: float = None, max_states: int = None) -> bool:
-		_ffi.require_gpu()
-		t0 = time.perf_counter()
-		time_limit, max_states = self.reset(time_limit, max_states)
-		self._n, self._cache, self.iterations, self.grown, self.capacity_exhausted = 0, None, 0, 0, False
-		self.popped = 0
-		self._is2024 = cube.get_is2024()
-		root = _roots20(self._is2024, state, 1)[0]          # ValueError for an illegal 6x8x6 state
-		if (root == _SOLVED20).all():
-			return True
-		lib, stream = _ffi.lib(), _ffi.stream_ptr()
-		K = 12 * self.pops
-		budget = int(min(max_states, 2 ** 31 - 1))
-		cap = self.capacity or min(budget + K, self.default_capacity)
-		cap = max(2, min(cap, self.max_capacity, self.MAX_CAPACITY))
-		h = self._engine(cap)
-		_ffi.check(lib.rk_bfs_reset(h, root.ctypes.data, budget, stream))
-		self._n = 1
-		status = (C.c_longlong * 8)()
-		_ffi.check(lib.rk_bfs_status(h, status, stream))
-		while not status[0]:
-			room = (self._h_cap - self._n) // K              # iterations the pool takes whatever they find
-			if room == 0:
-				if not self._grow(h):
-					return False
-				continue
-			_ffi.check(lib.rk_bfs_run(h, eng.burst(min(self.poll, room), budget - self._n, K), stream))
-			_ffi.check(lib.rk_bfs_status(h, status, stream))
-			self._n, self.iterations, self.popped = int(status[2]), int(status[3]), int(status[4]) - 1
-			if status[6]:
-				raise _ffi.RubiksHipError(f"BFS engine error code {int(status[6])}")
-			if not status[0] and time.perf_counter() - t0 >= time_limit:
-				return False
-		if status[1]:
-			self.action_queue = eng.read_path(lib.rk_bfs_path, h)
-			return True
-		return False
+	def _read(self, status):
+		self.popped = int(status[4]) - 1                    # word 4 is the head of the queue: the nodes before it were popped
 
 	def arrays(self):
 		"""(states, parents, actions) of nodes 1 .. len(agent) in index order = the reference's dict in insertion order: states
 		(n, 20) int8, or (n, 6, 8, 6) in 6x8x6 mode; parents int64 node indices (0 for the start); actions int64 (-1 for the start)."""
-		if self._cache is None:
-			n = self._n
-			states = np.zeros((n + 1, 20), np.int8)
-			parents, actions = np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int64)
-			if n and self._h is not None:
-				_ffi.check(_ffi.lib().rk_bfs_export(self._h, 1, n, states[1:].ctypes.data, parents[1:].ctypes.data,
-				                                     actions[1:].ctypes.data, _ffi.stream_ptr()))
-			if n:
-				actions[1] = -1
-			self._cache = (_states_out(self._is2024, states, n)[1:], parents[1:], actions[1:])
-		return self._cache
+		return self._pool()
 
 	@property
 	def states(self) -> dict:
@@ -404,14 +443,11 @@ class DeviceBFS(Agent, _ffi.Owner):
 		keys = [s.tobytes() for s in states]
 		return {k: (None, None) if p == 0 else (keys[p - 1], int(a)) for k, p, a in zip(keys, parents.tolist(), actions.tolist())}
 
-	def __len__(self):
-		return self._n
-
 	def __str__(self):
 		return f"Breadth-first search (device, pops={self.pops})"
 
 
-class DeviceBiBFS(Agent, _ffi.Owner):
+class DeviceBiBFS(_PoolSearch):
 	"""
 	Two-sided breadth-first search with the whole search in HBM (engine rk_bibfs_*, csrc/rk_bibfs.hip): a SHORTEST solution in
 	the quarter-turn metric.  One pool in index order holds two balls, side S around the start (node 1) and side G around the
@@ -425,105 +461,30 @@ class DeviceBiBFS(Agent, _ffi.Owner):
 	`capacity`, `max_capacity`, `grown` and `capacity_exhausted` are `DeviceBFS`'s, for the pool of both sides together.  The
 	representation follows cube.get_is2024() when a search starts; the engine always runs on 20-byte states.
 	"""
-	default_capacity = 8_000_000
-	max_capacity = 400_000_000
-	MAX_POPS = 1 << 22                      # rk_bibfs_create's limit
-	MAX_CAPACITY = 0x3FFFFFF0
+	_entries = "rk_bibfs"
+	_status_words = 12
+	_first_nodes = 2
+	_unlimited = True
+	_engine_name = "two-sided BFS"
 
 	def __init__(self, pops: int = 16_384, capacity: int = None, max_capacity: int = None, poll: int = 8):
-		super().__init__()
-		if isinstance(pops, bool) or int(pops) != pops or not 1 <= int(pops) <= self.MAX_POPS:
-			raise ValueError(f"pops must be an integer in 1..{self.MAX_POPS}, got {pops!r}")
-		for name, v in (("capacity", capacity), ("max_capacity", max_capacity)):
-			if v is not None and (isinstance(v, bool) or int(v) != v or not 2 <= int(v) <= self.MAX_CAPACITY):
-				raise ValueError(f"{name} must be an integer in 2..{self.MAX_CAPACITY}, got {v!r}")
-		if isinstance(poll, bool) or int(poll) != poll or int(poll) < 1:
-			raise ValueError(f"poll must be a positive integer, got {poll!r}")
-		self.pops, self.poll = int(pops), int(poll)
-		self.capacity = int(capacity) if capacity is not None else None
-		if max_capacity is not None:
-			self.max_capacity = int(max_capacity)
-		self._h, self._h_cap = None, 0
-		self._n = 0
-		self._is2024 = True
-		self._cache = None
+		super().__init__(pops, capacity, max_capacity, poll)
 		self._meet = 0                      # the stored node that the meeting child equals
 		self.depths = (0, 0)                # complete levels (f, b) of sides S and G after the last search
-		self.iterations = 0
-		self.popped = 0                     # nodes the last search popped, both sides together (each has 12 children)
-		self.grown = 0
-		self.capacity_exhausted = False
 
-	def _engine(self, capacity: int):
-		if self._h is not None and self._h_cap >= capacity:
-			return self._h                  # (a pool that grew in an earlier search is kept: rk_bibfs_reset clears its table)
-		self._h_cap = capacity
-		return self._create("rk_bibfs_create", "rk_bibfs_destroy", capacity, self.pops)
+	def _begin(self, root) -> bool:
+		self._meet, self.depths = 0, (0, 0)
+		return bool((root == _SOLVED20).all())
 
-	def _grow(self, h) -> bool:
-		if self._h_cap >= self.max_capacity:
-			eng.pool_exhausted(self, self._h_cap, "cannot take the next iteration")
-			return False
-		cap = min(2 * self._h_cap, self.max_capacity)
-		_ffi.check(_ffi.lib().rk_bibfs_grow(h, cap, _ffi.stream_ptr()))
-		self._h_cap = cap
-		self.grown += 1
-		return True
-
-	@no_grad
-	def search(self, state: np.ndarray, time_limit: float = None, max_states: int = None) -> bool:
-		_ffi.require_gpu()
-		t0 = time.perf_counter()
-		time_limit, max_states = self.reset(time_limit or 1e10, max_states)        # (an exact search may run without either limit)
-		self._n, self._cache, self.iterations, self.grown, self.capacity_exhausted = 0, None, 0, 0, False
-		self.popped, self._meet, self.depths = 0, 0, (0, 0)
-		self._is2024 = cube.get_is2024()
-		root = _roots20(self._is2024, state, 1)[0]          # ValueError for an illegal 6x8x6 state
-		if (root == _SOLVED20).all():
-			return True
-		lib, stream = _ffi.lib(), _ffi.stream_ptr()
-		K = 12 * self.pops
-		budget = int(min(max_states, 2 ** 31 - 1))
-		cap = self.capacity or min(budget + K, self.default_capacity)
-		cap = max(2, min(cap, self.max_capacity, self.MAX_CAPACITY))
-		h = self._engine(cap)
-		_ffi.check(lib.rk_bibfs_reset(h, root.ctypes.data, budget, stream))
-		self._n = 2
-		status = (C.c_longlong * 12)()
-		_ffi.check(lib.rk_bibfs_status(h, status, stream))
-		while not status[0]:
-			room = (self._h_cap - self._n) // K              # iterations the pool takes whatever they find
-			if room == 0:
-				if not self._grow(h):
-					return False
-				continue
-			_ffi.check(lib.rk_bibfs_run(h, eng.burst(min(self.poll, room), budget - self._n, K), stream))
-			_ffi.check(lib.rk_bibfs_status(h, status, stream))
-			self._n, self.iterations, self.popped = int(status[2]), int(status[3]), int(status[4])
-			self.depths, self._meet = (int(status[8]), int(status[9])), int(status[10])
-			if status[6]:
-				raise _ffi.RubiksHipError(f"two-sided BFS engine error code {int(status[6])}")
-			if not status[0] and time.perf_counter() - t0 >= time_limit:
-				return False
-		if status[1]:
-			self.action_queue = eng.read_path(lib.rk_bibfs_path, h)
-			return True
-		return False
+	def _read(self, status):
+		self.popped = int(status[4])                         # both sides together
+		self.depths, self._meet = (int(status[8]), int(status[9])), int(status[10])
 
 	def arrays(self):
 		"""(states, parents, actions, sides) of nodes 1 .. len(agent) in index order: states (n, 20) int8, or (n, 6, 8, 6) in 6x8x6
 		mode; parents int64 node indices (0 for nodes 1 and 2); actions int64, the move from the parent -- on side G away from
 		solved -- (-1 for nodes 1 and 2); sides int64, 0 = around the start, 1 = around the solved state."""
-		if self._cache is None:
-			n = self._n
-			states = np.zeros((n + 1, 20), np.int8)
-			parents, actions, sides = np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int64)
-			if n and self._h is not None:
-				_ffi.check(_ffi.lib().rk_bibfs_export(self._h, 1, n, states[1:].ctypes.data, parents[1:].ctypes.data,
-				                                       actions[1:].ctypes.data, sides[1:].ctypes.data, _ffi.stream_ptr()))
-			actions[1:3] = -1
-			self._cache = (_states_out(self._is2024, states, n)[1:], parents[1:], actions[1:], sides[1:])
-		return self._cache
+		return self._pool(tags=True)
 
 	@property
 	def meeting(self):
@@ -533,14 +494,107 @@ class DeviceBiBFS(Agent, _ffi.Owner):
 			return None
 		return self.arrays()[0][self._meet - 1].copy()
 
-	def __len__(self):
-		return self._n
-
 	def __str__(self):
 		return f"Two-sided breadth-first search (device, pops={self.pops})"
 
 
-class DeviceGoalBall(_ffi.Owner):
+class _KeptBall(_ffi.Owner):
+	"""What `DeviceGoalBall` and `DeviceSymBall` share: a ball around the solved state that is built once, at first use, and
+	read-only from then on, its level boundaries, and the one-launch answers `depth` and `solve`.  `_entries` is the prefix of the
+	engine's entry points, `_status_words` what its status writes."""
+	MAX_POPS = 1 << 22                      # the limit of rk_ball_create and rk_symball_create
+	poll = 8                                # iterations of the build between two looks of the host
+	_entries = None
+	_status_words = 16
+
+	def __init__(self, radius: int, pops: int):
+		self.radius = eng.int_in("radius", radius, 0, self.MAX_RADIUS)
+		self.pops = eng.int_in("pops", pops, 1, self.MAX_POPS)
+		self._h = None
+		self._n = 0
+		self._level_start = None
+		self._cache = {}
+		self.iterations = 0                 # of the build
+
+	def _entry(self, name: str):
+		return getattr(_ffi.lib(), f"{self._entries}_{name}")
+
+	def _create_args(self) -> tuple:
+		"""What the engine's create takes behind the radius and the pops."""
+		return ()
+
+	def _built(self, status):
+		"""The status words of a built ball that are the subclass's own."""
+
+	@property
+	def built(self) -> bool:
+		return self._level_start is not None
+
+	def build(self):
+		"""Builds the ball on the device (nothing if it is built)."""
+		if self.built:
+			return self
+		_ffi.require_gpu()
+		if self._h is None:
+			self._create(f"{self._entries}_create", f"{self._entries}_destroy", self.radius, self.pops, *self._create_args())
+		_ffi.check(self._entry("build")(self._h, self.poll, _ffi.stream_ptr()))
+		status = (C.c_longlong * self._status_words)()
+		_ffi.check(self._entry("status")(self._h, status))
+		self._n, self.iterations = int(status[1]), int(status[2])
+		self._built(status)
+		self._level_start = np.array(status[6:6 + self.radius + 2], np.int64)
+		return self
+
+	@property
+	def level_start(self) -> np.ndarray:
+		"""int64 (radius + 2,): level l holds the nodes level_start[l] .. level_start[l + 1] - 1."""
+		return self.build()._level_start
+
+	def __len__(self):
+		return self.build()._n
+
+	def _rows(self, states) -> np.ndarray:
+		"""Query states in the current representation as (n, 20) int8 rows (ValueError for an illegal 6x8x6 state)."""
+		raise NotImplementedError
+
+	def depth(self, states) -> np.ndarray:
+		"""int64 (n,): the exact distance to solved of every state the ball holds (`DeviceSymBall`: whose orbit it holds), -1 for
+		the others.  One launch."""
+		self.build()
+		rows = self._rows(states)
+		n = len(rows)
+		if n == 0:
+			return np.zeros(0, np.int64)
+		q = torch.from_numpy(rows).to(gpu)
+		out = torch.empty(n, dtype=torch.int32, device=gpu)
+		_ffi.check(self._entry("depth")(self._h, q.data_ptr(), n, out.data_ptr(), _ffi.stream_ptr()))
+		return out.cpu().numpy().astype(np.int64)
+
+	def _solve(self, q, n: int, lengths, actions):
+		"""The engine's solve launch on device tensors."""
+		_ffi.check(self._entry("solve")(self._h, q.data_ptr(), n, lengths.data_ptr(), actions.data_ptr(), _ffi.stream_ptr()))
+
+	def solve(self, states):
+		"""(lengths int64 (n,), actions int64 (n, radius)): a shortest solution of every state the ball holds (`DeviceSymBall`: whose
+		orbit it holds, at each step the lowest action that gets one level nearer), rows padded with -1; length -1 for a state
+		outside the ball.  One launch."""
+		self.build()
+		rows = self._rows(states)
+		n = len(rows)
+		if n == 0:
+			return np.zeros(0, np.int64), np.zeros((0, self.radius), np.int64)
+		q = torch.from_numpy(rows).to(gpu)
+		lengths = torch.empty(n, dtype=torch.int32, device=gpu)
+		actions = torch.empty((n, max(self.radius, 1)), dtype=torch.int8, device=gpu)
+		self._solve(q, n, lengths, actions)
+		return lengths.cpu().numpy().astype(np.int64), actions.cpu().numpy().astype(np.int64)[:, :self.radius]
+
+	def depth_of_node(self, node: int) -> int:
+		"""The depth of node `node` (1 .. len(ball)), from the level boundaries."""
+		return int(np.searchsorted(self.level_start, node, side="right")) - 1
+
+
+class DeviceGoalBall(_KeptBall):
 	"""
 	The ball around the solved state, built once and kept in HBM (engine rk_ball_*, csrc/rk_ball.hip): every state within `radius`
 	quarter turns, in `DeviceBFS`'s order without goal test or budget.  Node 1 is the solved state; a level's parents are popped in
@@ -554,50 +608,12 @@ class DeviceGoalBall(_ffi.Owner):
 	"""
 	LEVELS = (1, 12, 114, 1_068, 10_011, 93_840, 878_880, 8_221_632, 76_843_595)    # states at distance 0 .. 8, quarter turns
 	MAX_RADIUS = len(LEVELS) - 1
-	MAX_POPS = 1 << 22                      # rk_ball_create's limit
-	poll = 8                                # iterations of the build between two looks of the host
+	_entries = "rk_ball"
 
 	def __init__(self, radius: int, pops: int = 16_384):
-		if isinstance(radius, bool) or int(radius) != radius or not 0 <= int(radius) <= self.MAX_RADIUS:
-			raise ValueError(f"radius must be an integer in 0..{self.MAX_RADIUS}, got {radius!r}")
-		if isinstance(pops, bool) or int(pops) != pops or not 1 <= int(pops) <= self.MAX_POPS:
-			raise ValueError(f"pops must be an integer in 1..{self.MAX_POPS}, got {pops!r}")
-		self.radius, self.pops = int(radius), int(pops)
-		self._h = None
-		self._n = 0
-		self._level_start = None
-		self._cache = {}
-		self.iterations = 0                 # of the build
-
-	@property
-	def built(self) -> bool:
-		return self._level_start is not None
-
-	def build(self):
-		"""Builds the ball on the device (nothing if it is built)."""
-		if self.built:
-			return self
-		_ffi.require_gpu()
-		lib = _ffi.lib()
-		if self._h is None:
-			self._create("rk_ball_create", "rk_ball_destroy", self.radius, self.pops)
-		_ffi.check(lib.rk_ball_build(self._h, self.poll, _ffi.stream_ptr()))
-		status = (C.c_longlong * 16)()
-		_ffi.check(lib.rk_ball_status(self._h, status))
-		self._n, self.iterations = int(status[1]), int(status[2])
-		self._level_start = np.array(status[6:6 + self.radius + 2], np.int64)
-		return self
-
-	@property
-	def level_start(self) -> np.ndarray:
-		"""int64 (radius + 2,): level l holds the nodes level_start[l] .. level_start[l + 1] - 1."""
-		return self.build()._level_start
-
-	def __len__(self):
-		return self.build()._n
+		super().__init__(radius, pops)
 
 	def _rows(self, states) -> np.ndarray:
-		"""Query states in the current representation as (n, 20) int8 rows."""
 		is2024 = cube.get_is2024()
 		arr = np.asarray(states, dtype=np.int8)
 		width = 20 if is2024 else 288
@@ -605,43 +621,13 @@ class DeviceGoalBall(_ffi.Owner):
 			raise ValueError(f"states must be (n, 20), or (n, 6, 8, 6) in 6x8x6 mode, got shape {arr.shape}")
 		return _roots20(is2024, arr, arr.size // width)
 
-	def depth(self, states) -> np.ndarray:
-		"""int64 (n,): the exact distance to solved of every state the ball holds, -1 for the others.  One launch."""
-		self.build()
-		rows = self._rows(states)                            # ValueError for an illegal 6x8x6 state
-		n = len(rows)
-		if n == 0:
-			return np.zeros(0, np.int64)
-		q = torch.from_numpy(rows).to(gpu)
-		out = torch.empty(n, dtype=torch.int32, device=gpu)
-		_ffi.check(_ffi.lib().rk_ball_depth(self._h, q.data_ptr(), n, out.data_ptr(), _ffi.stream_ptr()))
-		return out.cpu().numpy().astype(np.int64)
-
-	def solve(self, states):
-		"""(lengths int64 (n,), actions int64 (n, radius)): the shortest solution of every state the ball holds, rows padded with
-		-1; length -1 for a state outside the ball.  One launch."""
-		self.build()
-		rows = self._rows(states)
-		n = len(rows)
-		if n == 0:
-			return np.zeros(0, np.int64), np.zeros((0, self.radius), np.int64)
-		q = torch.from_numpy(rows).to(gpu)
-		lengths = torch.empty(n, dtype=torch.int32, device=gpu)
-		actions = torch.empty((n, max(self.radius, 1)), dtype=torch.int8, device=gpu)
-		_ffi.check(_ffi.lib().rk_ball_solve(self._h, q.data_ptr(), n, lengths.data_ptr(), actions.data_ptr(), _ffi.stream_ptr()))
-		return lengths.cpu().numpy().astype(np.int64), actions.cpu().numpy().astype(np.int64)[:, :self.radius]
-
 	def arrays(self):
 		"""(states, parents, actions) of nodes 1 .. len(ball) in index order, like `DeviceBFS.arrays()`: parent 0 and action -1 for
 		the solved state; an action is the move from the parent, away from solved."""
 		is2024 = cube.get_is2024()
 		if is2024 not in self._cache:
 			n = len(self)
-			states = np.zeros((n + 1, 20), np.int8)
-			parents, actions = np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int64)
-			_ffi.check(_ffi.lib().rk_ball_export(self._h, 1, n, states[1:].ctypes.data, parents[1:].ctypes.data,
-			                                      actions[1:].ctypes.data, _ffi.stream_ptr()))
-			actions[1] = -1
+			states, parents, actions = eng.export_frontier(_ffi.lib().rk_ball_export, (self._h,), n)
 			self._cache = {is2024: (_states_out(is2024, states, n)[1:], parents[1:], actions[1:])}
 		return self._cache[is2024]
 
@@ -660,10 +646,8 @@ class DeviceGoalBall(_ffi.Owner):
 		`window=None`: every window of every queue.
 		"""
 		queues = [np.asarray(q, dtype=np.int64).reshape(-1) for q in action_queues]
-		if window is not None and (isinstance(window, bool) or int(window) != window or int(window) < 1):
-			raise ValueError(f"window must be an integer >= 1 or None, got {window!r}")
-		if passes is not None and (isinstance(passes, bool) or int(passes) != passes or int(passes) < 0):
-			raise ValueError(f"passes must be an integer >= 0 or None, got {passes!r}")
+		eng.int_in("window", window, 1, none_ok=True, what="an integer >= 1 or None")
+		eng.int_in("passes", passes, 0, none_ok=True, what="an integer >= 0 or None")
 		for q in queues:
 			if len(q) > self.MAX_QUEUE:
 				raise ValueError(f"an action queue of {len(q)} moves: at most {self.MAX_QUEUE}")
@@ -709,15 +693,11 @@ class DeviceGoalBall(_ffi.Owner):
 			done += 1
 		return queues
 
-	def depth_of_node(self, node: int) -> int:
-		"""The depth of node `node` (1 .. len(ball)), from the level boundaries."""
-		return int(np.searchsorted(self.level_start, node, side="right")) - 1
-
 	def __str__(self):
 		return f"Goal ball (device, radius={self.radius})"
 
 
-class DeviceSymBall(_ffi.Owner):
+class DeviceSymBall(_KeptBall):
 	"""
 	The goal ball reduced by the 48 whole-cube symmetries (engine rk_symball_*, csrc/rk_sym.hip): one canonical representative
 	(`cube.canonical`) per orbit of the states within `radius` quarter turns of solved.  Conjugation keeps the distance to solved,
@@ -734,90 +714,36 @@ class DeviceSymBall(_ffi.Owner):
 	"""
 	LEVELS = DeviceGoalBall.LEVELS                                  # states at distance 0 .. 8: what states_covered is checked against
 	MAX_RADIUS = 10
-	MAX_POPS = 1 << 22                      # rk_symball_create's limit
 	MAX_CAPACITY = 0x3FFFFFF0
-	poll = 8                                # iterations of the build between two looks of the host
+	_entries = "rk_symball"
+	_status_words = 32
 
 	def __init__(self, radius: int, pops: int = 16_384, capacity: int = None):
-		if isinstance(radius, bool) or int(radius) != radius or not 0 <= int(radius) <= self.MAX_RADIUS:
-			raise ValueError(f"radius must be an integer in 0..{self.MAX_RADIUS}, got {radius!r}")
-		if isinstance(pops, bool) or int(pops) != pops or not 1 <= int(pops) <= self.MAX_POPS:
-			raise ValueError(f"pops must be an integer in 1..{self.MAX_POPS}, got {pops!r}")
-		if capacity is not None and (isinstance(capacity, bool) or int(capacity) != capacity or not 1 <= int(capacity) <= self.MAX_CAPACITY):
-			raise ValueError(f"capacity must be an integer in 1..{self.MAX_CAPACITY} or None, got {capacity!r}")
-		self.radius, self.pops = int(radius), int(pops)
-		self.capacity = None if capacity is None else int(capacity)
-		self._h = None
-		self._n = 0
-		self._level_start = None
+		super().__init__(radius, pops)
+		self.capacity = eng.int_in("capacity", capacity, 1, self.MAX_CAPACITY, none_ok=True, what=f"an integer in 1..{self.MAX_CAPACITY} or None")
 		self._covered = None
-		self._cache = {}
-		self.iterations = 0                 # of the build
 
-	@property
-	def built(self) -> bool:
-		return self._level_start is not None
+	def _create_args(self) -> tuple:
+		return (self.capacity or 0,)
 
-	def build(self):
-		"""Builds the ball on the device (nothing if it is built)."""
-		if self.built:
-			return self
-		_ffi.require_gpu()
-		lib = _ffi.lib()
-		if self._h is None:
-			self._create("rk_symball_create", "rk_symball_destroy", self.radius, self.pops, self.capacity or 0)
-		_ffi.check(lib.rk_symball_build(self._h, self.poll, _ffi.stream_ptr()))
-		status = (C.c_longlong * 32)()
-		_ffi.check(lib.rk_symball_status(self._h, status))
-		self._n, self.iterations, self.capacity = int(status[1]), int(status[2]), int(status[4])
-		self._level_start = np.array(status[6:6 + self.radius + 2], np.int64)
+	def _built(self, status):
+		self.capacity = int(status[4])
 		self._covered = np.array(status[18:18 + self.radius + 1], np.int64)
-		return self
-
-	@property
-	def level_start(self) -> np.ndarray:
-		"""int64 (radius + 2,): level l holds the nodes level_start[l] .. level_start[l + 1] - 1."""
-		return self.build()._level_start
 
 	@property
 	def states_covered(self) -> np.ndarray:
 		"""int64 (radius + 1,): the orbit sizes of every level added up = the states at that distance from solved."""
 		return self.build()._covered
 
-	def __len__(self):
-		return self.build()._n
+	def _rows(self, states) -> np.ndarray:
+		return cube.cube._rows2024(states)
 
-	def _queries(self, states):
-		rows = cube.cube._rows2024(states)                   # ValueError for an illegal 6x8x6 state
-		return rows, len(rows)
-
-	def depth(self, states) -> np.ndarray:
-		"""int64 (n,): the exact distance to solved of every state whose orbit the ball holds, -1 for the others.  One launch."""
-		self.build()
-		rows, n = self._queries(states)
-		if n == 0:
-			return np.zeros(0, np.int64)
-		q = torch.from_numpy(rows).to(gpu)
-		out = torch.empty(n, dtype=torch.int32, device=gpu)
-		_ffi.check(_ffi.lib().rk_symball_depth(self._h, q.data_ptr(), n, out.data_ptr(), _ffi.stream_ptr()))
-		return out.cpu().numpy().astype(np.int64)
-
-	def solve(self, states):
-		"""(lengths int64 (n,), actions int64 (n, radius)): a shortest solution of every state whose orbit the ball holds -- at each
-		step the lowest action that gets one level nearer --, rows padded with -1; length -1 for a state outside.  One launch."""
-		self.build()
-		rows, n = self._queries(states)
-		if n == 0:
-			return np.zeros(0, np.int64), np.zeros((0, self.radius), np.int64)
-		q = torch.from_numpy(rows).to(gpu)
-		lengths = torch.empty(n, dtype=torch.int32, device=gpu)
-		actions = torch.empty((n, max(self.radius, 1)), dtype=torch.int8, device=gpu)
+	def _solve(self, q, n: int, lengths, actions):
 		err = torch.empty(1, dtype=torch.int32, device=gpu)
 		_ffi.check(_ffi.lib().rk_symball_solve(self._h, q.data_ptr(), n, lengths.data_ptr(), actions.data_ptr(), err.data_ptr(),
 		                                       _ffi.stream_ptr()))
 		if int(err.item()):
 			raise _ffi.RubiksHipError(f"rk_symball_solve reported error {int(err.item())}: a state of the ball has no child one level nearer")
-		return lengths.cpu().numpy().astype(np.int64), actions.cpu().numpy().astype(np.int64)[:, :self.radius]
 
 	def arrays(self):
 		"""The representatives of nodes 1 .. len(ball) in index order."""
@@ -829,134 +755,44 @@ class DeviceSymBall(_ffi.Owner):
 			self._cache = {is2024: _states_out(is2024, states, n)[1:]}
 		return self._cache[is2024]
 
-	def depth_of_node(self, node: int) -> int:
-		"""The depth of node `node` (1 .. len(ball)), from the level boundaries."""
-		return int(np.searchsorted(self.level_start, node, side="right")) - 1
-
 	def __str__(self):
 		return f"Symmetry-reduced goal ball (device, radius={self.radius})"
 
 
-class _BallSearch(Agent, _ffi.Owner):
-	"""What `DeviceBallSearch` and `DeviceSymBallSearch` share: the arguments, the host loop of a search with its pool growth, and
-	the export of the own pool.  `_entries` is the prefix of the engine's entry points (they have one argument list and one status
-	layout), `_ball_type` the kind of ball it ends at."""
-	default_capacity = 8_000_000
-	max_capacity = 400_000_000
-	MAX_POPS = 1 << 22                      # rk_bsearch_create's and rk_ssearch_create's limit
-	MAX_CAPACITY = 0x3FFFFFF0
-	_entries = None
+class _BallSearch(_PoolSearch):
+	"""What `DeviceBallSearch` and `DeviceSymBallSearch` share on top of `_PoolSearch`: the ball they end at (`_ball_type` is its
+	kind), the meeting and the levels around the start.  Their engines have one argument list and one status layout."""
+	_status_words = 10
+	_unlimited = True
+	_engine_name = "ball search"
 	_ball_type = None
 
 	def __init__(self, ball, pops: int = 16_384, capacity: int = None, max_capacity: int = None, poll: int = 8):
-		super().__init__()
 		if not isinstance(ball, self._ball_type):
 			raise TypeError(f"ball must be a {self._ball_type.__name__}, got {type(ball).__name__}")
-		if isinstance(pops, bool) or int(pops) != pops or not 1 <= int(pops) <= self.MAX_POPS:
-			raise ValueError(f"pops must be an integer in 1..{self.MAX_POPS}, got {pops!r}")
-		for name, v in (("capacity", capacity), ("max_capacity", max_capacity)):
-			if v is not None and (isinstance(v, bool) or int(v) != v or not 2 <= int(v) <= self.MAX_CAPACITY):
-				raise ValueError(f"{name} must be an integer in 2..{self.MAX_CAPACITY}, got {v!r}")
-		if isinstance(poll, bool) or int(poll) != poll or int(poll) < 1:
-			raise ValueError(f"poll must be a positive integer, got {poll!r}")
+		super().__init__(pops, capacity, max_capacity, poll)
 		self.ball = ball
-		self.pops, self.poll = int(pops), int(poll)
-		self.capacity = int(capacity) if capacity is not None else None
-		if max_capacity is not None:
-			self.max_capacity = int(max_capacity)
-		self._h, self._h_cap = None, 0
-		self._n = 0
-		self._is2024 = True
-		self._cache = None
 		self._root = None                   # the start of the last search, 20 bytes
 		self._meet = 0                      # the ball's node that the meeting child (or the start itself) equals
 		self.depth = 0                      # complete levels around the start after the last search
-		self.iterations = 0
-		self.popped = 0                     # nodes the last search popped (each has 12 children)
-		self.grown = 0
-		self.capacity_exhausted = False
 
-	def _entry(self, name: str):
-		return getattr(_ffi.lib(), f"{self._entries}_{name}")
+	def _create_args(self) -> tuple:
+		return (self.ball._h,)
 
-	def _engine(self, capacity: int):
-		if self._h is not None and self._h_cap >= capacity:
-			return self._h                  # (a pool that grew in an earlier search is kept: the reset clears its table)
-		self._h_cap = capacity
-		return self._create(f"{self._entries}_create", f"{self._entries}_destroy", self.ball._h, capacity, self.pops)
-
-	def _grow(self, h) -> bool:
-		if self._h_cap >= self.max_capacity:
-			eng.pool_exhausted(self, self._h_cap, "cannot take the next iteration")
-			return False
-		cap = min(2 * self._h_cap, self.max_capacity)
-		_ffi.check(self._entry("grow")(h, cap, _ffi.stream_ptr()))
-		self._h_cap = cap
-		self.grown += 1
-		return True
-
-	@no_grad
-	def search(self, state: np.ndarray, time_limit: float = None, max_states: int = None) -> bool:
-		_ffi.require_gpu()
-		t0 = time.perf_counter()
-		time_limit, max_states = self.reset(time_limit or 1e10, max_states)        # (an exact search may run without either limit)
-		self._n, self._cache, self.iterations, self.grown, self.capacity_exhausted = 0, None, 0, 0, False
-		self.popped, self._meet, self.depth = 0, 0, 0
-		self._is2024 = cube.get_is2024()
-		root = self._root = _roots20(self._is2024, state, 1)[0]          # ValueError for an illegal 6x8x6 state
+	def _begin(self, root) -> bool:
+		self._meet, self.depth = 0, 0
+		self._root = root
 		self.ball.build()
-		stream = _ffi.stream_ptr()
-		run, read_status = self._entry("run"), self._entry("status")
-		K = 12 * self.pops
-		budget = int(min(max_states, 2 ** 31 - 1))
-		cap = self.capacity or min(budget + K, self.default_capacity)
-		cap = max(2, min(cap, self.max_capacity, self.MAX_CAPACITY))
-		h = self._engine(cap)
-		_ffi.check(self._entry("reset")(h, root.ctypes.data, budget, stream))
-		self._n = 1
-		status = (C.c_longlong * 10)()
-		_ffi.check(read_status(h, status, stream))
-		self._meet = int(status[9])
-		while not status[0]:
-			room = (self._h_cap - self._n) // K              # iterations the pool takes whatever they find
-			if room == 0:
-				if not self._grow(h):
-					return False
-				continue
-			_ffi.check(run(h, eng.burst(min(self.poll, room), budget - self._n, K), stream))
-			_ffi.check(read_status(h, status, stream))
-			self._n, self.iterations, self.popped = int(status[2]), int(status[3]), int(status[4])
-			self.depth, self._meet = int(status[8]), int(status[9])
-			if status[6]:
-				raise _ffi.RubiksHipError(f"ball search engine error code {int(status[6])}")
-			if not status[0] and time.perf_counter() - t0 >= time_limit:
-				return False
-		if status[1]:
-			self.action_queue = eng.read_path(self._entry("path"), h)
-			return True
-		return False
+		return False                        # (a solved start is the ball's node 1: the engine answers it without a pop)
 
-	def arrays(self):
-		"""(states, parents, actions) of the own pool's nodes 1 .. len(agent) in index order, as `DeviceBFS.arrays()`."""
-		if self._cache is None:
-			n = self._n
-			states = np.zeros((n + 1, 20), np.int8)
-			parents, actions = np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int64)
-			if n and self._h is not None:
-				_ffi.check(self._entry("export")(self._h, 1, n, states[1:].ctypes.data, parents[1:].ctypes.data,
-				                                 actions[1:].ctypes.data, _ffi.stream_ptr()))
-			if n:
-				actions[1] = -1
-			self._cache = (_states_out(self._is2024, states, n)[1:], parents[1:], actions[1:])
-		return self._cache
+	def _read(self, status):
+		self.popped = int(status[4])
+		self.depth, self._meet = int(status[8]), int(status[9])
 
 	@property
 	def meeting_depth(self):
 		"""The depth in the ball of the node the search met; None when the last search did not meet."""
 		return self.ball.depth_of_node(self._meet) if self._meet else None
-
-	def __len__(self):
-		return self._n
 
 
 class DeviceBallSearch(_BallSearch):
@@ -1071,17 +907,11 @@ class DeviceBallSearchBatch(_ffi.Owner):
 	def __init__(self, ball: DeviceGoalBall, searches: int = 64, pops: int = 2_048, capacity: int = None, poll: int = 8):
 		if not isinstance(ball, DeviceGoalBall):
 			raise TypeError(f"ball must be a DeviceGoalBall, got {type(ball).__name__}")
-		if isinstance(searches, bool) or int(searches) != searches or not 1 <= int(searches) <= self.MAX_SEARCHES:
-			raise ValueError(f"searches must be an integer in 1..{self.MAX_SEARCHES}, got {searches!r}")
-		if isinstance(pops, bool) or int(pops) != pops or not 1 <= int(pops) <= self.MAX_POPS:
-			raise ValueError(f"pops must be an integer in 1..{self.MAX_POPS}, got {pops!r}")
-		if capacity is not None and (isinstance(capacity, bool) or int(capacity) != capacity or not 2 <= int(capacity) <= self.MAX_CAPACITY):
-			raise ValueError(f"capacity must be an integer in 2..{self.MAX_CAPACITY}, got {capacity!r}")
-		if isinstance(poll, bool) or int(poll) != poll or int(poll) < 1:
-			raise ValueError(f"poll must be a positive integer, got {poll!r}")
+		self.searches = eng.int_in("searches", searches, 1, self.MAX_SEARCHES)
+		self.pops = eng.int_in("pops", pops, 1, self.MAX_POPS)
+		self.capacity = eng.int_in("capacity", capacity, 2, self.MAX_CAPACITY, none_ok=True)
+		self.poll = eng.int_in("poll", poll, 1, what="a positive integer")
 		self.ball = ball
-		self.searches, self.pops, self.poll = int(searches), int(pops), int(poll)
-		self.capacity = int(capacity) if capacity is not None else None
 		self._h, self._h_cap = None, 0
 		self._is2024 = True
 		self.on_poll = None                 # callable(status (n, 10)): called at every poll
@@ -1127,12 +957,7 @@ class DeviceBallSearchBatch(_ffi.Owner):
 		return out
 
 	def _export(self, h, slot: int, n: int):
-		states = np.zeros((n + 1, 20), np.int8)
-		parents, actions = np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int64)
-		if n:
-			_ffi.check(_ffi.lib().rk_bsearchb_export(h, slot, 1, n, states[1:].ctypes.data, parents[1:].ctypes.data,
-			                                          actions[1:].ctypes.data, _ffi.stream_ptr()))
-			actions[1] = -1
+		states, parents, actions = eng.export_frontier(_ffi.lib().rk_bsearchb_export, (h, slot), n)
 		return _states_out(self._is2024, states, n)[1:], parents[1:], actions[1:]
 
 	@no_grad
