@@ -3,16 +3,12 @@
 // that ends at the first child the ball holds.  (rk_bibfs.hip rebuilds the solved side's ball for every search; it is the same
 // for every start.)
 //
-// The ball (rk_ball_*).  Node 1 is the solved state, the pool is in index order.  A level's parents are popped in index order,
-// never across a level boundary, their children taken in action order 0..11; a child the pool holds (an earlier child of the
-// batch included) is skipped, every other is appended with its parent and its action -- the move AWAY from solved.  The build
-// ends when level `radius` is complete; that level is stored and never expanded.  Level l is the index range lstart[l] ..
-// lstart[l + 1] - 1, so a node's depth follows from its index: there is no depth array.  The capacity is exact, from the level
-// sizes of the quarter-turn Cayley graph (BALL_LEVELS), and every completed level is checked against them.
-//   states  int8 (C+1, 20), parent int32 (C+1), pact uint8 (C+1), table uint32 (T = pow2 >= 2C)       as in rk_bfs.hip
-// An iteration is the four launches of rk_bfs.hip (expand with election, scan, append, end) without goal test, budget or cut:
-// every claim of a batch is appended, so between iterations -- and once the build is over -- no table slot is tentative.  The
-// pool is never too small for a batch unless the engine is wrong; the append checks every index all the same.
+// The ball (rk_ball_*) is the level-by-level build of rk_ballbuild_dev.h (counters, root, next, expand, scan, append, end) over
+// raw states: the state of batch position c is recomputed from its parent, and every node is stored with its parent and its
+// action -- the move AWAY from solved.  There is no depth array: a node's depth follows from its index.  The capacity is exact,
+// from the level sizes of the quarter-turn Cayley graph (BALL_LEVELS), and every completed level is checked against them.
+//   states  int8 (C+1, 20), parent int32 (C+1), pact uint8 (C+1), table uint32 (T = pow2 >= 2C)
+// The pool is never too small for a batch unless the engine is wrong; the append checks every index all the same.
 // After the build the ball is read-only:
 //   k_ball_depth   one thread per query: read-only probe (probe_find), 20-byte compare, depth from the level boundaries; -1 outside
 //   k_ball_solve   the same, then the walk along the parents: the inverse of every stored action leads back to solved
@@ -49,31 +45,17 @@
 
 #include "../../include/rubiks_hip.h"
 #include "rk_device.h"
+#include "rk_ballbuild_dev.h"
 #include "rk_error.h"
 #include "rk_frontier_dev.h"
 #include "rk_search_host.h"
 
 namespace rk {
 
-constexpr int BALL_MAX_RADIUS = 8;
-// states at distance 0 .. 8 from solved in the quarter-turn metric
-constexpr int32_t BALL_LEVELS[BALL_MAX_RADIUS + 1] = {1, 12, 114, 1068, 10011, 93840, 878880, 8221632, 76843595};
-static __constant__ int32_t D_BALL_LEVELS[BALL_MAX_RADIUS + 1] = {1, 12, 114, 1068, 10011, 93840, 878880, 8221632, 76843595};
+constexpr int BALL_MAX_RADIUS = BALL_CHECKED;   // the capacity is exact, so every level must be a known one
 
-enum {
-	G_SIZE = 0, G_HEAD, G_DONE, G_STOP, G_ITERS, G_ERROR, G_NPOP, G_TOTAL, G_EPOCH, G_TICKET, G_LEVEL, G_HI,
-	G_LSTART /* [BALL_MAX_RADIUS + 2] */, G_COUNT = 32
-};
-enum { BALL_STOP_NO = 0, BALL_STOP_BUILT = 1, BALL_STOP_ERROR = 4 };
-enum { BALL_ERR_NONE = 0, BALL_ERR_CAPACITY = 1, BALL_ERR_LEVEL = 2 };
-
-struct BallDev {
-	uint32_t mask, cap1;                        // table slots - 1, capacity + 1
-	int pops, radius;
-	uint32_t *states; int32_t *parent; uint8_t *pact; uint32_t *table;
-	int32_t *ctr;
-	uint32_t *slot; int32_t *rank; uint8_t *first;                   // per child of the batch (freed after the build)
-	unsigned long long *chain;
+struct BallDev : BuildDev {
+	int32_t *parent; uint8_t *pact;             // of every node: where it came from and by which action, the move AWAY from solved
 };
 
 // What the readers of a built ball get, by value: nothing in it changes any more.
@@ -84,116 +66,51 @@ struct BallView {
 	const uint32_t *states; const int32_t *parent; const uint8_t *pact; const uint32_t *table;
 };
 
-__device__ __forceinline__ int ball_depth_of(const BallView &b, uint32_t idx)
-{
-	int depth = 0;
-	#pragma unroll
-	for (int l = 1; l <= BALL_MAX_RADIUS; l++) depth += (int32_t)idx >= b.lstart[l] ? 1 : 0;
-	return depth;
-}
-
-// After the pops of an iteration (or the root): the end of a level with its size check, the end of the build, the next P.  One thread.
+// a closed level has the size of the graph's; P is never cut: the capacity is the sum of those sizes
 __device__ __forceinline__ void ball_next(const BallDev &d)
 {
-	const int32_t size = d.ctr[G_SIZE], head = d.ctr[G_HEAD];
-	int level = d.ctr[G_LEVEL];
-	int32_t hi = d.ctr[G_HI];
-	int stop = BALL_STOP_NO;
-	if (head > hi) {                                                     // every parent of `level` was popped: level + 1 is complete
-		level += 1;
-		if (size - hi != D_BALL_LEVELS[level]) { d.ctr[G_ERROR] = BALL_ERR_LEVEL; stop = BALL_STOP_ERROR; }
-		d.ctr[G_LSTART + level + 1] = size + 1;
-		d.ctr[G_LEVEL] = level;
-		d.ctr[G_HI] = hi = size;
-	}
-	if (!stop && level >= d.radius) stop = BALL_STOP_BUILT;              // level `radius` is stored and never expanded
-	d.ctr[G_STOP] = stop;
-	d.ctr[G_DONE] = stop ? 1 : 0;
-	d.ctr[G_NPOP] = stop ? 0 : min(d.pops, hi - head + 1);
+	bb_next<false>(d, [](int level, int32_t nodes) { return nodes == D_BALL_LEVELS[level]; });
 }
 
 __global__ void k_ball_root(BallDev d)
 {
-	const int tid = threadIdx.x;
-	if (tid < G_COUNT) d.ctr[tid] = 0;
-	__syncthreads();
-	if (tid != 0) return;
-	uint32_t s[5];
-	#pragma unroll
-	for (int j = 0; j < 5; j++) { s[j] = SOLVED_DW[j]; d.states[5 + j] = s[j]; }
-	d.parent[1] = 0; d.pact[1] = 0;
-	d.table[hash_state(s) & d.mask] = 1u;
-	d.ctr[G_SIZE] = 1; d.ctr[G_HEAD] = 1; d.ctr[G_HI] = 1;
-	d.ctr[G_LSTART] = 1; d.ctr[G_LSTART + 1] = 2;
-	ball_next(d);
+	bb_root(d, [&](int tid) { if (tid == 0) { d.parent[1] = 0; d.pact[1] = 0; } }, [&] { ball_next(d); });
 }
 
+// the state of batch position c is recomputed from its parent
 __global__ __launch_bounds__(256)
 void k_ball_expand(BallDev d)
 {
 	__shared__ u32x4 s_act[36];
 	stage_action_tables(s_act, threadIdx.x);
 	__syncthreads();
-	const int P = d.ctr[G_NPOP];
-	const int c = blockIdx.x * blockDim.x + threadIdx.x;
-	if (c >= 12 * P) return;
-	const int32_t head = d.ctr[G_HEAD];
-	const int i = c / 12, a = c - 12 * i;
-	uint32_t s[5];
-	child_state(d.states, head + i, s_act, (uint32_t)a, s);
-	uint32_t slot = 0;
-	const uint32_t e = probe_elect(d.table, d.mask, d.states, s, c,
-	                               [&](int c2, uint32_t o[5]) { child_state(d.states, head + c2 / 12, s_act, (uint32_t)(c2 % 12), o); }, &slot);
-	d.slot[c] = e == 0u ? slot : NO_SLOT;
+	const int32_t head = d.ctr[BB_HEAD];
+	bb_expand(d, [&](int c, uint32_t o[5]) { child_state(d.states, head + c / 12, s_act, (uint32_t)(c % 12), o); });
 }
 
 __global__ __launch_bounds__(ASCAN)
-void k_ball_scan(BallDev d)
-{
-	const int P = d.ctr[G_NPOP];
-	if (P == 0) return;                                                  // done: no ticket drawn, nothing to reset
-	frontier_scan(d.slot, d.table, d.rank, d.first, d.chain, &d.ctr[G_TICKET], (uint32_t)d.ctr[G_EPOCH] + 1u, &d.ctr[G_TOTAL], 12 * P);
-}
+void k_ball_scan(BallDev d) { bb_scan(d); }
 
-// every first occurrence is stored: there is no cut, so every claim of the batch becomes an index
+// every first occurrence is stored with its parent and its action
 __global__ __launch_bounds__(256)
 void k_ball_append(BallDev d)
 {
 	__shared__ u32x4 s_act[36];
 	stage_action_tables(s_act, threadIdx.x);
 	__syncthreads();
-	const int P = d.ctr[G_NPOP];
+	const int P = d.ctr[BB_NPOP];
 	const int c = blockIdx.x * blockDim.x + threadIdx.x;
 	if (c >= 12 * P || !d.first[c]) return;
 	const int i = c / 12, a = c - 12 * i;
-	const uint32_t idx = (uint32_t)d.ctr[G_SIZE] + 1u + (uint32_t)d.rank[c];
-	if (idx >= d.cap1) { d.ctr[G_ERROR] = BALL_ERR_CAPACITY; return; }   // more states than the level sizes allow: an engine error
-	const int32_t p = d.ctr[G_HEAD] + i;
-	uint32_t s[5];
-	child_state(d.states, p, s_act, (uint32_t)a, s);
-	#pragma unroll
-	for (int j = 0; j < 5; j++) d.states[(size_t)idx * 5 + j] = s[j];
-	d.parent[idx] = p;
-	d.pact[idx] = (uint8_t)a;
-	d.table[d.slot[c]] = idx;
+	const int32_t p = d.ctr[BB_HEAD] + i;
+	bb_append(d, c, [&](uint32_t idx, uint32_t s[5]) {
+		child_state(d.states, p, s_act, (uint32_t)a, s);
+		d.parent[idx] = p;
+		d.pact[idx] = (uint8_t)a;
+	});
 }
 
-__global__ void k_ball_end(BallDev d)
-{
-	if (threadIdx.x != 0 || blockIdx.x != 0) return;
-	const int P = d.ctr[G_NPOP];
-	if (P == 0) return;
-	d.ctr[G_ITERS] += 1;
-	d.ctr[G_TICKET] = 0;
-	d.ctr[G_EPOCH] += 1;
-	if (d.ctr[G_ERROR]) {
-		d.ctr[G_STOP] = BALL_STOP_ERROR; d.ctr[G_DONE] = 1; d.ctr[G_NPOP] = 0;
-		return;
-	}
-	d.ctr[G_SIZE] += d.ctr[G_TOTAL];
-	d.ctr[G_HEAD] += P;
-	ball_next(d);
-}
+__global__ void k_ball_end(BallDev d) { bb_end(d, [&] { ball_next(d); }); }
 
 // exact distance to solved of query q, -1 outside the ball: one thread per query, nothing is written but the answer
 __global__ __launch_bounds__(256)
@@ -204,7 +121,7 @@ void k_ball_depth(BallView b, const uint32_t *queries, size_t n, int32_t *depth)
 	uint32_t s[5];
 	load5(queries + q * 5, s);
 	const uint32_t e = probe_find(b.table, b.mask, b.states, s);
-	depth[q] = e ? ball_depth_of(b, e) : -1;
+	depth[q] = e ? level_of(b.lstart, e) : -1;
 }
 
 // the shortest solution of query q: from its node along the parents, the inverse of every stored action (those lead away from
@@ -284,7 +201,7 @@ void k_shorten_windows(BallView b, const int8_t *__restrict__ actions, const int
 		if (lane < nc) {
 			const uint32_t e = probe_find(b.table, b.mask, b.states, st);
 			const int k = d0 + lane;                                         // j - i - 1
-			depth[(p * (size_t)max_len + (size_t)(i + k)) * (size_t)window + (size_t)k] = (int8_t)(e ? ball_depth_of(b, e) : -1);
+			depth[(p * (size_t)max_len + (size_t)(i + k)) * (size_t)window + (size_t)k] = (int8_t)(e ? level_of(b.lstart, e) : -1);
 		}
 		#pragma unroll
 		for (int j = 0; j < 5; j++) s[j] = (uint32_t)__builtin_amdgcn_readlane((int)st[j], nc - 1);   // carries into the next chunk
@@ -391,7 +308,7 @@ void k_shorten_emit(BallView b, const int8_t *__restrict__ actions, const int32_
 					for (int q = 0; q < 5; q++) s[q] = (uint32_t)__builtin_amdgcn_readlane((int)st[q], nc - 1);
 				}
 				uint32_t g = probe_find(b.table, b.mask, b.states, s);       // X(i, j): the same in every lane
-				if (g == 0u || ball_depth_of(b, g) != d || d > b.radius || pos + d > max_len) { ok = false; break; }
+				if (g == 0u || level_of(b.lstart, g) != d || d > b.radius || pos + d > max_len) { ok = false; break; }
 				for (int k = d - 1; k >= 0; k--) {                              // the stored actions lead away from solved: the last one first
 					if (g <= 1u || g >= b.cap1) { ok = false; break; }
 					if (lane == 0) out[pos + k] = (int8_t)b.pact[g];
@@ -601,15 +518,9 @@ void kb_bsearch_walk(const FrontierDev *devs, BallView b, int n_slots, int32_t *
 
 using namespace rk;
 
-struct rk_ball {
+struct rk_ball : KeptBall {
 	BallDev d{};
 	BallView view{};
-	size_t cap = 0;
-	long long size = 0, iterations = 0;
-	int attached = 0;                           // searches that hold this ball's arrays
-	bool built = false;
-	Landing ctr_host;
-	DevPool pool{64};
 };
 
 struct rk_bsearch : FrontierPool {
@@ -649,99 +560,57 @@ constexpr size_t SHORTEN_MAX_WAVES = (size_t)1 << 30;    // queues x max_len of 
 // the d(i, j) bytes of a call, rounded up so that the pred rows behind them are aligned
 size_t shorten_depth_bytes(size_t n, int max_len, int window) { return (n * (size_t)max_len * (size_t)window + 15) & ~(size_t)15; }
 
-uint32_t ball_table_mask(size_t capacity) { return FrontierPool::table_mask(capacity); }
-
-// queries: n 20-byte rows on the device, read as dwords
-int check_queries(const char *who, const rk_ball *h, const void *d_states, size_t n, const void *out)
-{
-	if (!h) return fail(RK_EINVAL, "%s: null ball", who);
-	if (!h->built) return fail(RK_ESTATE, "%s: build the ball first", who);
-	if (n > (size_t)INT32_MAX) return fail(RK_EINVAL, "%s: %zu queries in one launch", who, n);
-	if (n != 0 && (!d_states || !out)) return fail(RK_EINVAL, "%s: null pointer", who);
-	if (((uintptr_t)d_states | (uintptr_t)out) & 3u) return fail(RK_EINVAL, "%s: device pointers must be 4-byte aligned", who);
-	return RK_OK;
-}
-
 }  // namespace
 
 extern "C" {
 
 int rk_ball_create(rk_ball_t **out, int radius, int pops)
 {
-	if (!out) return fail(RK_EINVAL, "rk_ball_create: null out pointer");
-	if (radius < 0 || radius > BALL_MAX_RADIUS) return fail(RK_EINVAL, "rk_ball_create: radius %d outside 0..%d", radius, BALL_MAX_RADIUS);
-	if (pops < 1 || pops > (1 << 22)) return fail(RK_EINVAL, "rk_ball_create: pops %d outside 1..%d", pops, 1 << 22);
+	if (int e = KeptBall::check_create("rk_ball_create", out, radius, BALL_MAX_RADIUS, pops)) return e;
 	rk_ball *h = new rk_ball();
-	h->cap = ball_capacity(radius);
-	BallDev &d = h->d;
-	d.pops = pops;
-	d.radius = radius;
-	d.cap1 = (uint32_t)(h->cap + 1);
-	d.mask = ball_table_mask(h->cap);
-	*out = h;                                   // the arrays are made by rk_ball_build: creating a ball costs nothing
+	h->describe(h->d, ball_capacity(radius), radius, pops);
+	*out = h;
 	return RK_OK;
 }
 
 int rk_ball_destroy(rk_ball_t *h)
 {
-	if (h && h->attached > 0) return fail(RK_ESTATE, "rk_ball_destroy: %d searches still hold this ball", h->attached);
+	if (int e = KeptBall::check_destroy("rk_ball_destroy", h)) return e;
 	delete h;
 	return RK_OK;
 }
 
 int rk_ball_build(rk_ball_t *h, int poll, void *stream)
 {
-	if (!h) return fail(RK_EINVAL, "rk_ball_build: null ball");
-	if (poll < 1) return fail(RK_EINVAL, "rk_ball_build: poll %d < 1", poll);
+	if (int e = KeptBall::check_build("rk_ball_build", h, poll)) return e;
 	if (h->built) return RK_OK;
 	hipStream_t st = (hipStream_t)stream;
 	BallDev &d = h->d;
 	const size_t C1 = h->cap + 1, K = (size_t)12 * d.pops;
-	h->pool.clear();                            // (what a failed build left)
-	int e = RK_OK;
-	#define A(ptr, cnt) if (!e) e = h->pool.alloc(&d.ptr, (cnt))
-	A(states, C1 * 5); A(parent, C1); A(pact, C1); A(table, (size_t)d.mask + 1); A(ctr, G_COUNT);
-	A(slot, K); A(rank, K); A(first, K); A(chain, frontier_scan_blocks(d.pops));
-	#undef A
-	if (e) { (void)hipGetLastError(); h->pool.clear(); return fail(RK_ECAPACITY, "rk_ball_build: no device memory for a ball of %zu states", h->cap); }
-	h->ctr_host.reserve(G_COUNT);
-	RK_HIP(hipMemsetAsync(d.table, 0, ((size_t)d.mask + 1) * sizeof(uint32_t), st));
-	RK_HIP(hipMemsetAsync(d.chain, 0, frontier_scan_blocks(d.pops) * sizeof(unsigned long long), st));
-	hipLaunchKernelGGL(k_ball_root, dim3(1), dim3(64), 0, st, d);
-	RK_HIP(hipGetLastError());
 	const unsigned grid = blocks(K);
-	int32_t c[G_COUNT];
-	for (;;) {
-		if (int r = h->ctr_host.read(d.ctr, G_COUNT, c, st)) return r;
-		if (c[G_DONE]) break;
-		for (int it = 0; it < poll; it++) {
-			hipLaunchKernelGGL(k_ball_expand, dim3(grid), dim3(256), 0, st, d);
-			hipLaunchKernelGGL(k_ball_scan, dim3(blocks(K, ASCAN)), dim3(ASCAN), 0, st, d);
-			hipLaunchKernelGGL(k_ball_append, dim3(grid), dim3(256), 0, st, d);
-			hipLaunchKernelGGL(k_ball_end, dim3(1), dim3(64), 0, st, d);
-		}
-		RK_HIP(hipGetLastError());
-	}
-	if (c[G_ERROR] || c[G_STOP] != BALL_STOP_BUILT || (size_t)c[G_SIZE] != h->cap)
-		return fail(RK_ESTATE, "rk_ball_build: engine error %d: %d states after level %d, %zu expected in all", c[G_ERROR], c[G_SIZE], c[G_LEVEL], h->cap);
-	h->pool.release(d.slot); h->pool.release(d.rank); h->pool.release(d.first); h->pool.release(d.chain);
-	d.slot = nullptr; d.rank = nullptr; d.first = nullptr; d.chain = nullptr;
-	BallView &v = h->view;
-	v.mask = d.mask; v.cap1 = d.cap1; v.radius = d.radius;
-	for (int l = 0; l < BALL_MAX_RADIUS + 2; l++) v.lstart[l] = l <= d.radius + 1 ? c[G_LSTART + l] : INT32_MAX;
-	v.states = d.states; v.parent = d.parent; v.pact = d.pact; v.table = d.table;
-	h->size = c[G_SIZE];
-	h->iterations = c[G_ITERS];
-	h->built = true;
+	int32_t c[BB_COUNT];
+	if (int e = h->run_build("rk_ball_build", "states", d, poll, st, c,
+	                         [&] { const int e = h->pool.alloc(&d.parent, C1); return e ? e : h->pool.alloc(&d.pact, C1); },
+	                         [&] { hipLaunchKernelGGL(k_ball_root, dim3(1), dim3(64), 0, st, d); },
+	                         [&] {
+		                         hipLaunchKernelGGL(k_ball_expand, dim3(grid), dim3(256), 0, st, d);
+		                         hipLaunchKernelGGL(k_ball_scan, dim3(blocks(K, ASCAN)), dim3(ASCAN), 0, st, d);
+		                         hipLaunchKernelGGL(k_ball_append, dim3(grid), dim3(256), 0, st, d);
+		                         hipLaunchKernelGGL(k_ball_end, dim3(1), dim3(64), 0, st, d);
+	                         }))
+		return e;
+	if (c[BB_ERROR] || c[BB_STOP] != BB_STOP_BUILT || (size_t)c[BB_SIZE] != h->cap)      // (the arrays stay until the next build clears them)
+		return fail(RK_ESTATE, "rk_ball_build: engine error %d: %d states after level %d, %zu expected in all", c[BB_ERROR], c[BB_SIZE], c[BB_LEVEL], h->cap);
+	h->finish_build(d, c, h->view);
+	h->view.parent = d.parent; h->view.pact = d.pact;
 	return RK_OK;
 }
 
 int rk_ball_status(rk_ball_t *h, long long *h_status)
 {
 	if (!h || !h_status) return fail(RK_EINVAL, "rk_ball_status: null argument");
-	h_status[0] = h->built ? 1 : 0; h_status[1] = h->size; h_status[2] = h->iterations; h_status[3] = h->d.radius;
-	h_status[4] = (long long)h->cap; h_status[5] = h->attached;
-	for (int l = 0; l < BALL_MAX_RADIUS + 2; l++) h_status[6 + l] = h->built && l <= h->d.radius + 1 ? h->view.lstart[l] : 0;
+	h->status_words(h_status, h->d.radius, h->view.lstart);
+	h_status[5] = h->attached;
 	return RK_OK;
 }
 
@@ -755,7 +624,7 @@ int rk_ball_export(rk_ball_t *h, size_t first, size_t count, int8_t *h_states, l
 
 int rk_ball_depth(rk_ball_t *h, const int8_t *d_states, size_t n, int32_t *d_depth, void *stream)
 {
-	if (int e = check_queries("rk_ball_depth", h, d_states, n, d_depth)) return e;
+	if (int e = KeptBall::check_queries("rk_ball_depth", "queries", h, d_states, n, d_depth)) return e;
 	if (n == 0) return RK_OK;
 	hipLaunchKernelGGL(k_ball_depth, dim3(blocks(n)), dim3(256), 0, (hipStream_t)stream, h->view,
 	                   reinterpret_cast<const uint32_t *>(d_states), n, d_depth);
@@ -765,7 +634,7 @@ int rk_ball_depth(rk_ball_t *h, const int8_t *d_states, size_t n, int32_t *d_dep
 
 int rk_ball_solve(rk_ball_t *h, const int8_t *d_states, size_t n, int32_t *d_lengths, int8_t *d_actions, void *stream)
 {
-	if (int e = check_queries("rk_ball_solve", h, d_states, n, d_lengths)) return e;
+	if (int e = KeptBall::check_queries("rk_ball_solve", "queries", h, d_states, n, d_lengths)) return e;
 	if (n == 0) return RK_OK;
 	if (!d_actions && h->d.radius > 0) return fail(RK_EINVAL, "rk_ball_solve: null pointer");
 	hipLaunchKernelGGL(k_ball_solve, dim3(blocks(n)), dim3(256), 0, (hipStream_t)stream, h->view,
@@ -877,7 +746,7 @@ int rk_bsearchb_create(rk_bsearchb_t **out, rk_ball_t *ball, int n_slots, size_t
 	if (pops < 1 || pops > (1 << 22)) return fail(RK_EINVAL, "rk_bsearchb_create: pops %d outside 1..%d", pops, 1 << 22);
 	rk_bsearchb *h = new rk_bsearchb();
 	h->n_slots = n_slots; h->pops = pops; h->cap = capacity_per_slot;
-	h->mask = ball_table_mask(capacity_per_slot);
+	h->mask = FrontierPool::table_mask(capacity_per_slot);
 	const size_t S = (size_t)n_slots, C1 = capacity_per_slot + 1, T = (size_t)h->mask + 1, K = (size_t)12 * pops, W = frontier_scan_blocks(pops);
 	FrontierDev &d = h->d;
 	d.pops = pops;

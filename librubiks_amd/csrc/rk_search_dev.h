@@ -302,7 +302,7 @@ __device__ __forceinline__ int scan_lookback_classes(unsigned long long *words, 
 	return (cls < (uint32_t)W ? s_base[cls] : 0) + my;
 }
 
-// ---- what the breadth-first engines share (one-sided rk_bfs, two-sided rk_bibfs): a batch of K children in pop order ----
+// ---- a batch of K children in pop order: what the frontier pool (rk_frontier_dev.h) and the ball builds (rk_ballbuild_dev.h) scan ----
 constexpr uint32_t NO_SLOT = 0xFFFFFFFFu;       // slot[c] of a child that takes part in no claim (any value with the TENT bit)
 
 // First-occurrence flags of the batch and their exclusive prefix in batch order, one launch of ASCAN-thread workgroups: child c

@@ -1,6 +1,7 @@
 // Host-side pieces shared by the search engines (A* single / sharded / batched, breadth-first search, MCTS): who owns a device
-// allocation, growing arrays in place as one transaction, the small read-backs every engine needs, and FrontierPool, the host
-// half of the breadth-first engines' pool (rk_frontier_dev.h).  The counterpart of rk_search_dev.h; header-only, nothing in
+// allocation, growing arrays in place as one transaction, the small read-backs every engine needs, FrontierPool, the host
+// half of the breadth-first engines' pool (rk_frontier_dev.h), and KeptBall, the host half of the two ball builds
+// (rk_ballbuild_dev.h).  The counterpart of rk_search_dev.h; header-only, nothing in
 // here is exported.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -10,6 +11,7 @@
 #include <vector>
 
 #include "../../include/rubiks_hip.h"
+#include "rk_ballbuild_dev.h"
 #include "rk_error.h"
 #include "rk_frontier_dev.h"
 
@@ -371,6 +373,110 @@ struct FrontierPool {
 	{
 		if (first + count > cap + 1) return fail(RK_EINVAL, "%s: rows %zu..%zu outside the pool", who, first, first + count);
 		return export_pool_rows(d.states, d.parent, d.pact, first, count, h_states, h_parents, h_actions, h_tags, st);
+	}
+};
+
+// The host half of a kept ball (rk_ballbuild_dev.h): what rk_ball and rk_symball hold and do in the same way.  A ball's handle is
+// this plus its descriptor, its view and what it reports of its own; its entries pass their own name as `who`, the prefix of
+// every error text.  Creating a ball costs nothing: the arrays are made by the build.
+struct KeptBall {
+	size_t cap = 0;
+	long long size = 0, iterations = 0;
+	int attached = 0;                           // searches that hold this ball's arrays
+	bool built = false;
+	Landing ctr_host;
+	DevPool pool{64};
+
+	static int check_create(const char *who, const void *out, int radius, int max_radius, int pops)
+	{
+		if (!out) return fail(RK_EINVAL, "%s: null out pointer", who);
+		if (radius < 0 || radius > max_radius) return fail(RK_EINVAL, "%s: radius %d outside 0..%d", who, radius, max_radius);
+		if (pops < 1 || pops > FRONTIER_MAX_POPS) return fail(RK_EINVAL, "%s: pops %d outside 1..%d", who, pops, FRONTIER_MAX_POPS);
+		return RK_OK;
+	}
+	static int check_destroy(const char *who, const KeptBall *h)
+	{
+		return h && h->attached > 0 ? fail(RK_ESTATE, "%s: %d searches still hold this ball", who, h->attached) : RK_OK;
+	}
+	static int check_build(const char *who, const KeptBall *h, int poll)
+	{
+		if (!h) return fail(RK_EINVAL, "%s: null ball", who);
+		if (poll < 1) return fail(RK_EINVAL, "%s: poll %d < 1", who, poll);
+		return RK_OK;
+	}
+	// queries: n 20-byte rows on the device, read as dwords (`rows`: what the entry calls them)
+	static int check_queries(const char *who, const char *rows, const KeptBall *h, const void *d_states, size_t n, const void *out)
+	{
+		if (!h) return fail(RK_EINVAL, "%s: null ball", who);
+		if (!h->built) return fail(RK_ESTATE, "%s: build the ball first", who);
+		if (n > (size_t)INT32_MAX) return fail(RK_EINVAL, "%s: %zu %s in one launch", who, n, rows);
+		if (n != 0 && (!d_states || !out)) return fail(RK_EINVAL, "%s: null pointer", who);
+		if (((uintptr_t)d_states | (uintptr_t)out) & 3u) return fail(RK_EINVAL, "%s: device pointers must be 4-byte aligned", who);
+		return RK_OK;
+	}
+
+	void describe(BuildDev &d, size_t capacity, int radius, int pops)
+	{
+		cap = capacity;
+		d.pops = pops;
+		d.radius = radius;
+		d.cap1 = (uint32_t)(capacity + 1);
+		d.mask = FrontierPool::table_mask(capacity);
+	}
+
+	// The build up to the counter block it ends with, `c` (BB_COUNT words): what a failed build left is cleared, the common arrays
+	// and the ball's own (alloc_own) are made, table and look-back words cleared, the root launched, then `poll` iterations (the
+	// ball's four or five launches) per read of the counters until the device says done.  Whether the build passed is the ball's
+	// to judge.  `nodes`: what the ball calls what it stores.
+	template <typename Alloc, typename Root, typename Iteration>
+	int run_build(const char *who, const char *nodes, BuildDev &d, int poll, hipStream_t st, int32_t *c, Alloc &&alloc_own, Root &&launch_root,
+	              Iteration &&launch_iteration)
+	{
+		const size_t K = (size_t)12 * d.pops;
+		pool.clear();
+		int e = RK_OK;
+		#define A(ptr, cnt) if (!e) e = pool.alloc(&d.ptr, (cnt))
+		A(states, (cap + 1) * 5); A(table, (size_t)d.mask + 1); A(ctr, BB_COUNT);
+		A(slot, K); A(rank, K); A(first, K); A(chain, frontier_scan_blocks(d.pops));
+		#undef A
+		if (!e) e = alloc_own();
+		if (e) { (void)hipGetLastError(); pool.clear(); return fail(RK_ECAPACITY, "%s: no device memory for a ball of %zu %s", who, cap, nodes); }
+		if (!ctr_host.pinned()) ctr_host.reserve(BB_COUNT);
+		RK_HIP(hipMemsetAsync(d.table, 0, ((size_t)d.mask + 1) * sizeof(uint32_t), st));
+		RK_HIP(hipMemsetAsync(d.chain, 0, frontier_scan_blocks(d.pops) * sizeof(unsigned long long), st));
+		launch_root();
+		RK_HIP(hipGetLastError());
+		for (;;) {
+			if (int r = ctr_host.read(d.ctr, BB_COUNT, c, st)) return r;
+			if (c[BB_DONE]) break;
+			for (int it = 0; it < poll; it++) launch_iteration();
+			RK_HIP(hipGetLastError());
+		}
+		return RK_OK;
+	}
+
+	// after a build that passed: the per-batch scratch given back, the common part of the view (the level boundaries from the
+	// counters) and the sizes
+	template <typename View, typename... Own>
+	void finish_build(BuildDev &d, const int32_t *c, View &v, Own *&... own_scratch)
+	{
+		for (void *p : {(void *)d.slot, (void *)d.rank, (void *)d.first, (void *)d.chain, (void *)own_scratch...}) pool.release(p);
+		d.slot = nullptr; d.rank = nullptr; d.first = nullptr; d.chain = nullptr;
+		((own_scratch = nullptr), ...);
+		v.mask = d.mask; v.cap1 = d.cap1; v.radius = d.radius;
+		v.states = d.states; v.table = d.table;
+		for (int l = 0; l < (int)(sizeof v.lstart / sizeof v.lstart[0]); l++) v.lstart[l] = l <= d.radius + 1 ? c[BB_LSTART + l] : INT32_MAX;
+		size = c[BB_SIZE];
+		iterations = c[BB_ITERS];
+		built = true;
+	}
+
+	// status words 0..4 and 6..: built, nodes, iterations, radius, capacity; the level boundaries (0 beyond radius + 1).  Word 5 is the ball's own.
+	template <int N>
+	void status_words(long long *o, int radius, const int32_t (&lstart)[N]) const
+	{
+		o[0] = built ? 1 : 0; o[1] = size; o[2] = iterations; o[3] = radius; o[4] = (long long)cap;
+		for (int l = 0; l < N; l++) o[6 + l] = built && l <= radius + 1 ? lstart[l] : 0;
 	}
 };
 

@@ -9,23 +9,21 @@
 //   k_sym_canonical   waves stride over the states: representative, lowest symmetry that gives it, orbit size
 //   k_sym_conjugate   one given symmetry, a thread per state (every lane reads the same table rows)
 //
-// The ball.  Node 1 is the solved state, the pool is in index order.  A level's representatives are popped in index order, never
-// across a level boundary, their children taken in action order 0..11 and canonicalised; a representative the pool holds (an
-// earlier child of the batch included) is skipped, every other is appended.  Level `radius` is stored and never expanded; level l
-// is the index range lstart[l] .. lstart[l + 1] - 1.
-//   states  int8 (C+1, 20), table uint32 (T = pow2 >= 2C)                                            as in rk_ball.hip
-// An iteration is the four launches of rk_ball.hip behind one more: the election compares a child with OTHER children of the
-// batch, one thread per child, and a canonical form takes a wave, so the representatives of a batch are written to scratch first
+// The ball is the level-by-level build of rk_ballbuild_dev.h (counters, root, next, expand, scan, append, end) over
+// representatives: the children of a level's representatives are canonicalised before the election.
+//   states  int8 (C+1, 20), table uint32 (T = pow2 >= 2C); no parent, no action
+// The election compares a child with OTHER children of the batch, one thread per child, and a canonical form takes a wave, so
+// an iteration has one launch in front that writes the representatives of the batch to scratch
 //   k_sb_canon    a wave per child: fan-out, canonical form, orbit size          -> cstate (12 P, 5), corbit (12 P)
-//   k_sb_expand   a thread per child: membership / election on the representative (probe_elect)
-//   k_sb_scan     first occurrences and their prefix (frontier_scan)
-//   k_sb_append   every first occurrence is stored; its orbit size is added to the sum of the level
-//   k_sb_end      size, head, the end of a level with its check, the end of the build, the next P
+//   k_sb_expand   bb_expand; the state of batch position c is cstate[c]
+//   k_sb_scan     bb_scan
+//   k_sb_append   bb_append from cstate; the orbit sizes of what a wave stored are added to the sum of the level
+//   k_sb_end      bb_end, then sb_next
 // Level check: the orbit sizes of a level add up to the level size of the quarter-turn Cayley graph; a closed level 0..8 is
-// compared with the sizes rk_ball.hip builds by (SB_ERR_LEVEL otherwise).  Levels 9 and 10 are summed (64 bits) and reported but
-// not compared: the project holds no published table for them.
+// compared with BALL_LEVELS (BB_ERR_LEVEL otherwise).  Levels 9 and 10 are summed (64 bits) and reported but not compared: the
+// project holds no published table for them.
 // Capacity: orbit counts are not known in advance, so the pool has the size the caller asks for.  P is cut to what fits whatever
-// the batch finds (size + 12 P <= C); when not even one pop fits, the build stops BEFORE the iteration with SB_STOP_FULL.  The
+// the batch finds (size + 12 P <= C); when not even one pop fits, the build stops BEFORE the iteration with BB_STOP_FULL.  The
 // append checks every index all the same.
 // After the build the ball is read-only:
 //   k_sb_depth    a wave per query: canonical form, read-only probe (probe_find), depth from the level boundaries; -1 outside
@@ -58,72 +56,24 @@
 
 namespace rk {
 
-constexpr int SB_CHECKED = 8;                       // the last level whose size is compared
-// states at distance 0 .. 8 from solved in the quarter-turn metric (rk_ball.hip: BALL_LEVELS)
-constexpr long long SB_LEVELS[SB_CHECKED + 1] = {1, 12, 114, 1068, 10011, 93840, 878880, 8221632, 76843595};
-static __constant__ long long D_SB_LEVELS[SB_CHECKED + 1] = {1, 12, 114, 1068, 10011, 93840, 878880, 8221632, 76843595};
 // levels 9 and 10 as the literature is recalled to give them: used for the default capacity only, never compared
 constexpr long long SB_LEVELS_UNCHECKED[2] = {717789576ll, 6701836858ll};
+static_assert(BB_LSTART + SB_MAX_RADIUS + 2 <= BB_COUNT, "the level boundaries do not fit the counter block");
 
-enum {
-	B_SIZE = 0, B_HEAD, B_DONE, B_STOP, B_ITERS, B_ERROR, B_NPOP, B_TOTAL, B_EPOCH, B_TICKET, B_LEVEL, B_HI,
-	B_LSTART /* [SB_MAX_RADIUS + 2] */, B_COUNT = 32
-};
-static_assert(B_LSTART + SB_MAX_RADIUS + 2 <= B_COUNT, "the level boundaries do not fit the counter block");
-enum { SB_STOP_NO = 0, SB_STOP_BUILT = 1, SB_STOP_ERROR = 4, SB_STOP_FULL = 5 };
-enum { SB_ERR_NONE = 0, SB_ERR_CAPACITY = 1, SB_ERR_LEVEL = 2 };
-
-struct SymBallDev {
-	uint32_t mask, cap1;                        // table slots - 1, capacity + 1
-	int pops, radius;
-	uint32_t *states; uint32_t *table;
-	int32_t *ctr;
+struct SymBallDev : BuildDev {
 	unsigned long long *cover;                  // [SB_MAX_RADIUS + 1]: the orbit sizes of every level added up
 	uint32_t *cstate; uint8_t *corbit;          // per child of the batch: its representative and its orbit size (freed after the build)
-	uint32_t *slot; int32_t *rank; uint8_t *first;
-	unsigned long long *chain;
 };
 
-// After the pops of an iteration (or the root): the end of a level with its check, the end of the build, the next P.  One thread.
+// the orbit sizes of a closed level 0..8 add up to the level's size in the graph; P is cut to what fits the caller's capacity
 __device__ __forceinline__ void sb_next(const SymBallDev &d)
 {
-	const int32_t size = d.ctr[B_SIZE], head = d.ctr[B_HEAD];
-	int level = d.ctr[B_LEVEL];
-	int32_t hi = d.ctr[B_HI];
-	int stop = SB_STOP_NO;
-	if (head > hi) {                                                     // every representative of `level` was popped: level + 1 is complete
-		level += 1;
-		if (level <= SB_CHECKED && d.cover[level] != (unsigned long long)D_SB_LEVELS[level]) { d.ctr[B_ERROR] = SB_ERR_LEVEL; stop = SB_STOP_ERROR; }
-		d.ctr[B_LSTART + level + 1] = size + 1;
-		d.ctr[B_LEVEL] = level;
-		d.ctr[B_HI] = hi = size;
-	}
-	if (!stop && level >= d.radius) stop = SB_STOP_BUILT;                // level `radius` is stored and never expanded
-	int P = 0;
-	if (!stop) {
-		const uint32_t fit = (d.cap1 - 1u - (uint32_t)size) / 12u;       // pops whose children fit whatever they are
-		P = min(min(d.pops, hi - head + 1), (int)min(fit, (uint32_t)INT32_MAX));
-		if (P < 1) { d.ctr[B_ERROR] = SB_ERR_CAPACITY; stop = SB_STOP_FULL; P = 0; }
-	}
-	d.ctr[B_STOP] = stop;
-	d.ctr[B_DONE] = stop ? 1 : 0;
-	d.ctr[B_NPOP] = P;
+	bb_next<true>(d, [&](int level, int32_t) { return level > BALL_CHECKED || d.cover[level] == (unsigned long long)D_BALL_LEVELS[level]; });
 }
 
 __global__ void k_sb_root(SymBallDev d)
 {
-	const int tid = threadIdx.x;
-	if (tid < B_COUNT) d.ctr[tid] = 0;
-	if (tid <= SB_MAX_RADIUS) d.cover[tid] = tid == 0 ? 1ull : 0ull;
-	__syncthreads();
-	if (tid != 0) return;
-	uint32_t s[5];
-	#pragma unroll
-	for (int j = 0; j < 5; j++) { s[j] = SOLVED_DW[j]; d.states[5 + j] = s[j]; }
-	d.table[hash_state(s) & d.mask] = 1u;
-	d.ctr[B_SIZE] = 1; d.ctr[B_HEAD] = 1; d.ctr[B_HI] = 1;
-	d.ctr[B_LSTART] = 1; d.ctr[B_LSTART + 1] = 2;
-	sb_next(d);
+	bb_root(d, [&](int tid) { if (tid <= SB_MAX_RADIUS) d.cover[tid] = tid == 0 ? 1ull : 0ull; }, [&] { sb_next(d); });
 }
 
 // the representative and the orbit size of every child of the batch: waves stride over the children
@@ -132,14 +82,14 @@ void k_sb_canon(SymBallDev d)
 {
 	__shared__ uint32_t s_sym[SYM_LDS_DWORDS];
 	__shared__ u32x4 s_act[36];
-	const int K = 12 * d.ctr[B_NPOP];
+	const int K = 12 * d.ctr[BB_NPOP];
 	if ((int)blockIdx.x * 4 >= K) return;                                // done, or a workgroup past the batch: nothing staged
 	sym_stage(s_sym, threadIdx.x, 256);
 	stage_action_tables(s_act, threadIdx.x);
 	__syncthreads();
 	const int lane = threadIdx.x & 63;
 	const SymLane L = sym_lane(min(lane, N_SYM - 1));
-	const int32_t head = d.ctr[B_HEAD];
+	const int32_t head = d.ctr[BB_HEAD];
 	for (int c = blockIdx.x * 4 + (threadIdx.x >> 6); c < K; c += gridDim.x * 4) {       // (whole waves)
 		const int i = c / 12, a = c - 12 * i;
 		uint32_t x[5], rep[5];
@@ -151,69 +101,32 @@ void k_sb_canon(SymBallDev d)
 	}
 }
 
+// the state of batch position c is its representative, from the scratch k_sb_canon wrote
 __global__ __launch_bounds__(256)
 void k_sb_expand(SymBallDev d)
 {
-	const int P = d.ctr[B_NPOP];
-	const int c = blockIdx.x * blockDim.x + threadIdx.x;
-	if (c >= 12 * P) return;
-	uint32_t s[5];
-	load5(d.cstate + (size_t)c * 5, s);
-	uint32_t slot = 0;
-	const uint32_t e = probe_elect(d.table, d.mask, d.states, s, c, [&](int c2, uint32_t o[5]) { load5(d.cstate + (size_t)c2 * 5, o); }, &slot);
-	d.slot[c] = e == 0u ? slot : NO_SLOT;
+	bb_expand(d, [&](int c, uint32_t o[5]) { load5(d.cstate + (size_t)c * 5, o); });
 }
 
 __global__ __launch_bounds__(ASCAN)
-void k_sb_scan(SymBallDev d)
-{
-	const int P = d.ctr[B_NPOP];
-	if (P == 0) return;                                                  // done: no ticket drawn, nothing to reset
-	frontier_scan(d.slot, d.table, d.rank, d.first, d.chain, &d.ctr[B_TICKET], (uint32_t)d.ctr[B_EPOCH] + 1u, &d.ctr[B_TOTAL], 12 * P);
-}
+void k_sb_scan(SymBallDev d) { bb_scan(d); }
 
 // every first occurrence is stored, and its orbit size added to the sum of the level that is being filled
 __global__ __launch_bounds__(256)
 void k_sb_append(SymBallDev d)
 {
-	const int K = 12 * d.ctr[B_NPOP];
+	const int K = 12 * d.ctr[BB_NPOP];
 	if ((int)blockIdx.x * 256 >= K) return;                              // (whole workgroups: every lane of a wave reaches the sum)
 	const int c = blockIdx.x * 256 + threadIdx.x;
 	uint32_t orbit = 0;
-	if (c < K && d.first[c]) {
-		const uint32_t idx = (uint32_t)d.ctr[B_SIZE] + 1u + (uint32_t)d.rank[c];
-		if (idx >= d.cap1) {
-			d.ctr[B_ERROR] = SB_ERR_CAPACITY;                            // (never: P was cut to what fits)
-		} else {
-			uint32_t s[5];
-			load5(d.cstate + (size_t)c * 5, s);
-			#pragma unroll
-			for (int j = 0; j < 5; j++) d.states[(size_t)idx * 5 + j] = s[j];
-			d.table[d.slot[c]] = idx;
-			orbit = d.corbit[c];
-		}
-	}
+	if (c < K && d.first[c] && bb_append(d, c, [&](uint32_t, uint32_t s[5]) { load5(d.cstate + (size_t)c * 5, s); }))
+		orbit = d.corbit[c];                                             // (never refused: P was cut to what fits)
 	#pragma unroll
 	for (int m = 32; m > 0; m >>= 1) orbit += (uint32_t)__shfl_xor((int)orbit, m, 64);
-	if ((threadIdx.x & 63) == 0 && orbit != 0u) atomicAdd(&d.cover[d.ctr[B_LEVEL] + 1], (unsigned long long)orbit);
+	if ((threadIdx.x & 63) == 0 && orbit != 0u) atomicAdd(&d.cover[d.ctr[BB_LEVEL] + 1], (unsigned long long)orbit);
 }
 
-__global__ void k_sb_end(SymBallDev d)
-{
-	if (threadIdx.x != 0 || blockIdx.x != 0) return;
-	const int P = d.ctr[B_NPOP];
-	if (P == 0) return;
-	d.ctr[B_ITERS] += 1;
-	d.ctr[B_TICKET] = 0;
-	d.ctr[B_EPOCH] += 1;
-	if (d.ctr[B_ERROR]) {
-		d.ctr[B_STOP] = SB_STOP_ERROR; d.ctr[B_DONE] = 1; d.ctr[B_NPOP] = 0;
-		return;
-	}
-	d.ctr[B_SIZE] += d.ctr[B_TOTAL];
-	d.ctr[B_HEAD] += P;
-	sb_next(d);
-}
+__global__ void k_sb_end(SymBallDev d) { bb_end(d, [&] { sb_next(d); }); }
 
 // exact distance to solved of query q, -1 outside the ball: waves stride over the queries, nothing is written but the answer
 __global__ __launch_bounds__(256)
@@ -230,7 +143,7 @@ void k_sb_depth(SymBallView b, const uint32_t *queries, size_t n, int32_t *depth
 		int sym, count;
 		sym_canonical(s_sym, L, lane, x, rep, &sym, &count);
 		const uint32_t e = probe_find(b.table, b.mask, b.states, rep);
-		if (lane == 0) depth[q] = e ? sb_depth_of(b, e) : -1;
+		if (lane == 0) depth[q] = e ? level_of(b.lstart, e) : -1;
 	}
 }
 
@@ -252,7 +165,7 @@ void k_sb_solve(SymBallView b, const uint32_t *queries, size_t n, int32_t *lengt
 		sym_canonical(s_sym, L, lane, x, rep, &sym, &count);
 		const uint32_t e = probe_find(b.table, b.mask, b.states, rep);
 		int8_t *row = actions + q * (size_t)b.radius;
-		const int depth = e ? sb_depth_of(b, e) : -1;
+		const int depth = e ? level_of(b.lstart, e) : -1;
 		bool ok;
 		const int len = sb_descend(b, s_sym, s_act, L, lane, x, depth, [&](int k, int a) { if (lane == 0) row[k] = (int8_t)a; }, &ok);
 		if (depth >= 0 && !ok && lane == 0) *error = RK_ESTATE;
@@ -400,7 +313,7 @@ void k_ss_walk(FrontierDev d, SymBallView b, int32_t *out, int max_len)
 	const uint32_t g = probe_find(b.table, b.mask, b.states, rep);
 	bool ok = g != 0u && g == (uint32_t)d.ctr[S_MEET];
 	const int own = len;                                                 // moves before the meeting state
-	if (ok) len = own + sb_descend(b, s_sym, s_act, L, lane, x, sb_depth_of(b, g),
+	if (ok) len = own + sb_descend(b, s_sym, s_act, L, lane, x, level_of(b.lstart, g),
 	                               [&](int k, int a) { if (own + k < max_len && lane == 0) out[1 + own + k] = a; }, &ok);
 	if (lane == 0) out[0] = ok ? len : -2;
 }
@@ -444,16 +357,10 @@ void k_sym_conjugate(const uint32_t *states, size_t n, int sym, uint32_t *out)
 
 using namespace rk;
 
-struct rk_symball {
+struct rk_symball : KeptBall {
 	SymBallDev d{};
 	SymBallView view{};
-	size_t cap = 0;
-	long long size = 0, iterations = 0;
 	long long cover[SB_MAX_RADIUS + 1] = {};
-	int attached = 0;                           // searches that hold this ball's arrays
-	bool built = false;
-	Landing ctr_host;
-	DevPool pool{64};
 };
 
 struct rk_ssearch : FrontierPool {
@@ -466,7 +373,7 @@ namespace {
 constexpr size_t SB_MAX_CAPACITY = 0x3FFFFFF0ull;
 constexpr unsigned SYM_GRID = 2048;              // workgroups of the wave-per-state launches: eight to a CU, the tables staged once each
 
-long long sb_level_size(int l) { return l <= SB_CHECKED ? SB_LEVELS[l] : SB_LEVELS_UNCHECKED[l - SB_CHECKED - 1]; }
+long long sb_level_size(int l) { return l <= BALL_CHECKED ? BALL_LEVELS[l] : SB_LEVELS_UNCHECKED[l - BALL_CHECKED - 1]; }
 
 // the sum over the levels of ceil(level / 48 * 1.02) + 64
 size_t sb_default_capacity(int radius)
@@ -483,16 +390,6 @@ int check_sym_states(const char *who, const void *d_states, size_t n)
 	if (n > (size_t)INT32_MAX) return fail(RK_EINVAL, "%s: %zu states in one launch", who, n);
 	if (n != 0 && !d_states) return fail(RK_EINVAL, "%s: null pointer", who);
 	if ((uintptr_t)d_states & 3u) return fail(RK_EINVAL, "%s: device pointers must be 4-byte aligned", who);
-	return RK_OK;
-}
-
-int check_sb_queries(const char *who, const rk_symball *h, const void *d_states, size_t n, const void *out)
-{
-	if (!h) return fail(RK_EINVAL, "%s: null ball", who);
-	if (!h->built) return fail(RK_ESTATE, "%s: build the ball first", who);
-	if (int e = check_sym_states(who, d_states, n)) return e;
-	if (n != 0 && !out) return fail(RK_EINVAL, "%s: null pointer", who);
-	if ((uintptr_t)out & 3u) return fail(RK_EINVAL, "%s: device pointers must be 4-byte aligned", who);
 	return RK_OK;
 }
 
@@ -535,93 +432,69 @@ int rk_sym_conjugate(const int8_t *d_states, size_t n, int sym, int8_t *d_out, v
 
 int rk_symball_create(rk_symball_t **out, int radius, int pops, size_t capacity)
 {
-	if (!out) return fail(RK_EINVAL, "rk_symball_create: null out pointer");
-	if (radius < 0 || radius > SB_MAX_RADIUS) return fail(RK_EINVAL, "rk_symball_create: radius %d outside 0..%d", radius, SB_MAX_RADIUS);
-	if (pops < 1 || pops > (1 << 22)) return fail(RK_EINVAL, "rk_symball_create: pops %d outside 1..%d", pops, 1 << 22);
+	if (int e = KeptBall::check_create("rk_symball_create", out, radius, SB_MAX_RADIUS, pops)) return e;
 	if (capacity == 0) capacity = sb_default_capacity(radius);
 	if (capacity > SB_MAX_CAPACITY) return fail(RK_EINVAL, "rk_symball_create: capacity %zu out of range", capacity);
 	rk_symball *h = new rk_symball();
-	h->cap = capacity;
-	SymBallDev &d = h->d;
-	d.pops = pops;
-	d.radius = radius;
-	d.cap1 = (uint32_t)(capacity + 1);
-	d.mask = (uint32_t)(table_slots(capacity, 1024) - 1);
-	*out = h;                                   // the arrays are made by rk_symball_build: creating a ball costs nothing
+	h->describe(h->d, capacity, radius, pops);
+	*out = h;
 	return RK_OK;
 }
 
 int rk_symball_destroy(rk_symball_t *h)
 {
-	if (h && h->attached > 0) return fail(RK_ESTATE, "rk_symball_destroy: %d searches still hold this ball", h->attached);
+	if (int e = KeptBall::check_destroy("rk_symball_destroy", h)) return e;
 	delete h;
 	return RK_OK;
 }
 
 int rk_symball_build(rk_symball_t *h, int poll, void *stream)
 {
-	if (!h) return fail(RK_EINVAL, "rk_symball_build: null ball");
-	if (poll < 1) return fail(RK_EINVAL, "rk_symball_build: poll %d < 1", poll);
+	if (int e = KeptBall::check_build("rk_symball_build", h, poll)) return e;
 	if (h->built) return RK_OK;
 	hipStream_t st = (hipStream_t)stream;
 	SymBallDev &d = h->d;
-	const size_t C1 = h->cap + 1, K = (size_t)12 * d.pops;
-	h->pool.clear();                            // (what a failed build left)
-	int e = RK_OK;
-	#define A(ptr, cnt) if (!e) e = h->pool.alloc(&d.ptr, (cnt))
-	A(states, C1 * 5); A(table, (size_t)d.mask + 1); A(ctr, B_COUNT); A(cover, SB_MAX_RADIUS + 1);
-	A(cstate, K * 5); A(corbit, K); A(slot, K); A(rank, K); A(first, K); A(chain, frontier_scan_blocks(d.pops));
-	#undef A
-	if (e) { (void)hipGetLastError(); h->pool.clear(); return fail(RK_ECAPACITY, "rk_symball_build: no device memory for a ball of %zu orbits", h->cap); }
-	h->ctr_host.reserve(B_COUNT);
-	RK_HIP(hipMemsetAsync(d.table, 0, ((size_t)d.mask + 1) * sizeof(uint32_t), st));
-	RK_HIP(hipMemsetAsync(d.chain, 0, frontier_scan_blocks(d.pops) * sizeof(unsigned long long), st));
-	hipLaunchKernelGGL(k_sb_root, dim3(1), dim3(64), 0, st, d);
-	RK_HIP(hipGetLastError());
+	const size_t K = (size_t)12 * d.pops;
 	const unsigned grid = blocks(K);
-	int32_t c[B_COUNT];
-	for (;;) {
-		if (int r = h->ctr_host.read(d.ctr, B_COUNT, c, st)) return r;
-		if (c[B_DONE]) break;
-		for (int it = 0; it < poll; it++) {
-			hipLaunchKernelGGL(k_sb_canon, dim3(sym_grid(K)), dim3(256), 0, st, d);
-			hipLaunchKernelGGL(k_sb_expand, dim3(grid), dim3(256), 0, st, d);
-			hipLaunchKernelGGL(k_sb_scan, dim3(blocks(K, ASCAN)), dim3(ASCAN), 0, st, d);
-			hipLaunchKernelGGL(k_sb_append, dim3(grid), dim3(256), 0, st, d);
-			hipLaunchKernelGGL(k_sb_end, dim3(1), dim3(64), 0, st, d);
-		}
-		RK_HIP(hipGetLastError());
-	}
+	int32_t c[BB_COUNT];
+	if (int e = h->run_build("rk_symball_build", "orbits", d, poll, st, c,
+	                         [&] {
+		                         int e = h->pool.alloc(&d.cover, SB_MAX_RADIUS + 1);
+		                         if (!e) e = h->pool.alloc(&d.cstate, K * 5);
+		                         return e ? e : h->pool.alloc(&d.corbit, K);
+	                         },
+	                         [&] { hipLaunchKernelGGL(k_sb_root, dim3(1), dim3(64), 0, st, d); },
+	                         [&] {
+		                         hipLaunchKernelGGL(k_sb_canon, dim3(sym_grid(K)), dim3(256), 0, st, d);
+		                         hipLaunchKernelGGL(k_sb_expand, dim3(grid), dim3(256), 0, st, d);
+		                         hipLaunchKernelGGL(k_sb_scan, dim3(blocks(K, ASCAN)), dim3(ASCAN), 0, st, d);
+		                         hipLaunchKernelGGL(k_sb_append, dim3(grid), dim3(256), 0, st, d);
+		                         hipLaunchKernelGGL(k_sb_end, dim3(1), dim3(64), 0, st, d);
+	                         }))
+		return e;
 	unsigned long long cover[SB_MAX_RADIUS + 1];
 	RK_HIP(hipMemcpyAsync(cover, d.cover, sizeof cover, hipMemcpyDeviceToHost, st));
 	RK_HIP(hipStreamSynchronize(st));
-	h->size = c[B_SIZE];
-	h->iterations = c[B_ITERS];
-	if (c[B_STOP] != SB_STOP_BUILT || c[B_ERROR]) { h->pool.clear(); d.states = nullptr; d.table = nullptr; }       // the ball stays unbuilt
-	if (c[B_STOP] == SB_STOP_FULL)
-		return fail(RK_ECAPACITY, "rk_symball_build: a capacity of %zu orbits is too small for radius %d: %d orbits stored, level %d complete", h->cap,
-		            d.radius, c[B_SIZE], c[B_LEVEL]);
-	if (c[B_ERROR] || c[B_STOP] != SB_STOP_BUILT)
-		return fail(RK_ESTATE, "rk_symball_build: engine error %d: %d orbits after level %d, whose orbit sizes add up to %llu", c[B_ERROR], c[B_SIZE],
-		            c[B_LEVEL], cover[std::min(std::max(c[B_LEVEL], 0), SB_MAX_RADIUS)]);
-	h->pool.release(d.cstate); h->pool.release(d.corbit); h->pool.release(d.slot); h->pool.release(d.rank); h->pool.release(d.first);
-	h->pool.release(d.chain);
-	d.cstate = nullptr; d.corbit = nullptr; d.slot = nullptr; d.rank = nullptr; d.first = nullptr; d.chain = nullptr;
-	SymBallView &v = h->view;
-	v.mask = d.mask; v.cap1 = d.cap1; v.radius = d.radius;
-	for (int l = 0; l < SB_MAX_RADIUS + 2; l++) v.lstart[l] = l <= d.radius + 1 ? c[B_LSTART + l] : INT32_MAX;
-	v.states = d.states; v.table = d.table;
+	if (c[BB_STOP] != BB_STOP_BUILT || c[BB_ERROR]) {                    // the ball stays unbuilt and says how far it came; its arrays go at once
+		h->size = c[BB_SIZE];
+		h->iterations = c[BB_ITERS];
+		h->pool.clear(); d.states = nullptr; d.table = nullptr;
+		if (c[BB_STOP] == BB_STOP_FULL)
+			return fail(RK_ECAPACITY, "rk_symball_build: a capacity of %zu orbits is too small for radius %d: %d orbits stored, level %d complete", h->cap,
+			            d.radius, c[BB_SIZE], c[BB_LEVEL]);
+		return fail(RK_ESTATE, "rk_symball_build: engine error %d: %d orbits after level %d, whose orbit sizes add up to %llu", c[BB_ERROR], c[BB_SIZE],
+		            c[BB_LEVEL], cover[std::min(std::max(c[BB_LEVEL], 0), SB_MAX_RADIUS)]);
+	}
+	h->finish_build(d, c, h->view, d.cstate, d.corbit);
 	for (int l = 0; l <= SB_MAX_RADIUS; l++) h->cover[l] = l <= d.radius ? (long long)cover[l] : 0;
-	h->built = true;
 	return RK_OK;
 }
 
 int rk_symball_status(rk_symball_t *h, long long *h_status)
 {
 	if (!h || !h_status) return fail(RK_EINVAL, "rk_symball_status: null argument");
-	h_status[0] = h->built ? 1 : 0; h_status[1] = h->size; h_status[2] = h->iterations; h_status[3] = h->d.radius;
-	h_status[4] = (long long)h->cap; h_status[5] = (long long)h->d.mask + 1;
-	for (int l = 0; l < SB_MAX_RADIUS + 2; l++) h_status[6 + l] = h->built && l <= h->d.radius + 1 ? h->view.lstart[l] : 0;
+	h->status_words(h_status, h->d.radius, h->view.lstart);
+	h_status[5] = (long long)h->d.mask + 1;
 	for (int l = 0; l <= SB_MAX_RADIUS; l++) h_status[18 + l] = h->built ? h->cover[l] : 0;
 	for (int k = 29; k < 32; k++) h_status[k] = 0;
 	return RK_OK;
@@ -642,7 +515,7 @@ int rk_symball_export(rk_symball_t *h, size_t first, size_t count, int8_t *h_sta
 
 int rk_symball_depth(rk_symball_t *h, const int8_t *d_states, size_t n, int32_t *d_depth, void *stream)
 {
-	if (int e = check_sb_queries("rk_symball_depth", h, d_states, n, d_depth)) return e;
+	if (int e = KeptBall::check_queries("rk_symball_depth", "states", h, d_states, n, d_depth)) return e;
 	if (n == 0) return RK_OK;
 	hipLaunchKernelGGL(k_sb_depth, dim3(sym_grid(n)), dim3(256), 0, (hipStream_t)stream, h->view, reinterpret_cast<const uint32_t *>(d_states), n,
 	                   d_depth);
@@ -652,7 +525,7 @@ int rk_symball_depth(rk_symball_t *h, const int8_t *d_states, size_t n, int32_t 
 
 int rk_symball_solve(rk_symball_t *h, const int8_t *d_states, size_t n, int32_t *d_lengths, int8_t *d_actions, int32_t *d_error, void *stream)
 {
-	if (int e = check_sb_queries("rk_symball_solve", h, d_states, n, d_lengths)) return e;
+	if (int e = KeptBall::check_queries("rk_symball_solve", "states", h, d_states, n, d_lengths)) return e;
 	if (!d_error || ((uintptr_t)d_error & 3u)) return fail(RK_EINVAL, "rk_symball_solve: the error word must be a 4-byte aligned device pointer");
 	hipStream_t st = (hipStream_t)stream;
 	RK_HIP(hipMemsetAsync(d_error, 0, sizeof(int32_t), st));

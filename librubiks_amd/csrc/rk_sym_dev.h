@@ -21,6 +21,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "rk_ballbuild_dev.h"
 #include "rk_device.h"
 #include "rk_search_dev.h"
 #include "rk_sym_tables.h"
@@ -133,14 +134,6 @@ struct SymBallView {
 	const uint32_t *states; const uint32_t *table;
 };
 
-__device__ __forceinline__ int sb_depth_of(const SymBallView &b, uint32_t idx)
-{
-	int depth = 0;
-	#pragma unroll
-	for (int l = 1; l <= SB_MAX_RADIUS; l++) depth += (int32_t)idx >= b.lstart[l] ? 1 : 0;
-	return depth;
-}
-
 // The descent from x, a state whose representative lies at level `depth` of the ball, to the solved state: at each step the lowest
 // action whose child's representative lies one level nearer, emit(step, action) for every step, x moved along.  Returns the
 // steps taken; *ok = false when a state has no such child (the ball is broken) or depth is outside 0..radius.  ALL 64 lanes of a
@@ -163,7 +156,7 @@ __device__ __forceinline__ int sb_descend(const SymBallView &b, const uint32_t *
 			move5(y, tab);
 			sym_canonical(s_sym, L, lane, y, rep, &sym, &count);
 			const uint32_t g = probe_find(b.table, b.mask, b.states, rep);
-			if (g != 0u && sb_depth_of(b, g) == depth - len - 1) {
+			if (g != 0u && level_of(b.lstart, g) == depth - len - 1) {
 				found = a;
 				#pragma unroll
 				for (int j = 0; j < 5; j++) x[j] = y[j];
