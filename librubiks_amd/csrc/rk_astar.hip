@@ -88,6 +88,7 @@ struct QueueDev {
 struct AstarDev {
 	uint32_t mask, cap1;
 	int N, K, Kpad, chunk;                      // expansions, 12 N, K rounded up to the sort chunk, sort chunk (256 or 2048)
+	int rows;                                   // sharded push with a short net batch: values exist for the first `rows` new states only (0: for all)
 	int world, rank, KI;                        // sharded: ranks, this rank, incoming child slots = world * K
 	double lambda;
 	int values_bf16;                            // the net's values arrive as bfloat16 instead of float32 (rk_astar_set_values_dtype)
@@ -605,6 +606,16 @@ void kb_append(const AstarDev *__restrict__ devs, const uint8_t *recv)
 }
 
 
+// The new states of this iteration that get a cost record: never more than the sort / merge / insert launches were sized for, and never
+// more than the caller has values for (shard_push_impl; `rows` is below Kpad there, which it rounds UP to a whole chunk).  Records past
+// this count are padding in every kernel of the sequence -- the sort, the merge pass, the insert and the end derive the same number --
+// so values[j] is read for j < rows only; k_end<true> reports the states left without a record as ERR_NET_ROWS.
+__device__ __forceinline__ int new_covered(const AstarDev &d, int n_new_all)
+{
+	const int n = min(n_new_all, d.Kpad);
+	return d.rows > 0 ? min(n, d.rows) : n;
+}
+
 // cost record of new state j: cost = lambda * G + (-value), float64, no fused multiply-add (agents.py:380-383).
 // Padding records carry distinct maximal keys.
 __device__ __forceinline__ Rec cost_record(const AstarDev &d, const float *values, int j, int n_new, uint32_t n_before)
@@ -652,7 +663,7 @@ __device__ __forceinline__ void records_sort_body(const AstarDev &d, const float
 	__shared__ uint32_t sp[CHUNK];
 	constexpr int T = CHUNK / 2;
 	const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-	const int n_new = min(d.ctr[C_NNEW], d.Kpad);                       // (never more than the launches were sized for: see shard_push_impl)
+	const int n_new = new_covered(d, d.ctr[C_NNEW]);
 	const uint32_t n_before = (uint32_t)d.ctr[C_NBEFORE];
 	const int base = blockIdx.x * CHUNK;
 	if (base >= n_new) return;                                          // uniform for the workgroup
@@ -731,7 +742,7 @@ void kb_records_sort(const AstarDev *__restrict__ devs, const float *values, con
 __device__ __forceinline__ void merge_pass_body(const AstarDev &d, int L, int from)
 {
 	const int e = blockIdx.x * blockDim.x + threadIdx.x;
-	const int n_new = min(d.ctr[C_NNEW], d.Kpad);
+	const int n_new = new_covered(d, d.ctr[C_NNEW]);
 	if (e >= d.Kpad || n_new <= SORT_CHUNK) return;                     // a single chunk is already sorted (only launched when K > 2048)
 	const int used = ((n_new + SORT_CHUNK - 1) / SORT_CHUNK) * SORT_CHUNK;
 	const Rec *src = from ? d.rec1 : d.rec0;
@@ -800,7 +811,7 @@ __device__ __forceinline__ void queue_insert_body(const AstarDev &d, int new_in_
 		}
 	}
 	if (threadIdx.x < 4 * QL) s_qmeta[threadIdx.x] = d.q.meta[threadIdx.x];     // one parallel load instead of a dependent chain
-	else if (threadIdx.x == 64) s_nnew = min(d.ctr[C_NNEW], d.Kpad);            // (in the same round trip, and so are the queue's capacities and buffers)
+	else if (threadIdx.x == 64) s_nnew = new_covered(d, d.ctr[C_NNEW]);          // (in the same round trip, and so are the queue's capacities and buffers)
 	else if (threadIdx.x >= 128 && threadIdx.x < 128 + QL) s_cap[threadIdx.x - 128] = d.q.cap[threadIdx.x - 128];
 	else if (threadIdx.x >= 192 && threadIdx.x < 192 + 2 * QL) s_buf[threadIdx.x - 192] = d.q.buf[(threadIdx.x - 192) >> 1][(threadIdx.x - 192) & 1];
 	__syncthreads();
@@ -953,7 +964,7 @@ __device__ __forceinline__ void end_body(const AstarDev &d, int new_in_rec1, int
 	if (tid < 64) {
 		const int lane = tid, levels = d.q.levels;
 		const int n_new_all = s_ctr[C_NNEW];
-		const int n_new = min(n_new_all, d.Kpad);                          // what the sort / insert launches of this iteration covered
+		const int n_new = new_covered(d, n_new_all);                       // what the sort / insert launches of this iteration covered
 		const bool is_level = lane < levels;
 		const int lv = is_level ? lane : 0;
 		int head = s_old[Q_HEAD * QL + lv] + s_old[Q_TAKE * QL + lv], len = s_old[Q_LEN * QL + lv], cur = s_old[Q_CUR * QL + lv];
@@ -1990,12 +2001,13 @@ static int shard_push_impl(rk_astar_t *h, const float *d_values, int rows, const
 	// iteration's sort / merge / insert need not be sized for K = 12 N records: `rows` of them at most.  At world 8, N = 700 that is one
 	// pass over 1 344 records in 256-record chunks staged in LDS (the K <= 2048 form) instead of five 2 048-record chunks; at
 	// N = 5 600 (weak) five chunks handed to the insert as they are instead of 33 chunks and five merge passes.  Every kernel of the
-	// sequence receives the same geometry by value; should the promise break, they cover `Kpad` records and no more (clamped), and
-	// k_end<true> reports it.
+	// sequence receives the same geometry by value; should the promise break, they cover `rows` records and no more (new_covered: Kpad is
+	// `rows` rounded up to a whole chunk, and the caller's tensor ends at values[rows - 1]), and k_end<true> reports it.
 	AstarDev d = h->d;
 	if (rows > 0 && rows < d.K) {
 		if (rows <= SORT_CHUNK) d.chunk = SMALL_CHUNK;
 		d.Kpad = std::min(d.Kpad, ((rows + d.chunk - 1) / d.chunk) * d.chunk);
+		d.rows = rows;
 	}
 	const int from = launch_commit<true>(h, d_values, st, &d);
 	hipLaunchKernelGGL(k_shard_offers, dim3(blocks((size_t)d.K, ASCAN)), dim3(ASCAN), 0, st, d, (const uint8_t *)d_recv, (uint8_t *)d_send);
