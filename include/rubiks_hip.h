@@ -427,7 +427,8 @@ int rk_ball_solve(rk_ball_t *h, const int8_t *d_states, size_t n, int32_t *d_len
  * windows (a wave per queue and i), the shortest path (a workgroup per queue), the rewritten queue (a wave per queue).  The
  * ball is only read. */
 /* Bytes of scratch one rk_bshorten call of this shape needs: n * max_len * window for d(i, j), n * (max_len + 1) * 2 for the
- * path.  RK_EINVAL unless 1 <= window <= max_len <= 4096 and n * max_len <= 2^30.  Touches no device. */
+ * path.  RK_EINVAL unless 1 <= window <= max_len <= 4096 and n * max_len <= 2^30.  Touches no device.  rk_sshorten (the
+ * symmetry ball's pass, below) takes scratch of the same size and layout: this function serves both. */
 long long rk_bshorten_scratch_bytes(size_t n, int max_len, int window);
 /* DEVICE d_actions int8 (n, max_len), row q holding d_len[q] actions 0..11 (what follows is ignored; -1 by convention), to
  * d_out_actions int8 (n, max_len), padded with -1, and d_out_len int32 (n); the output may not be the input.  d_scratch:
@@ -548,6 +549,19 @@ int rk_symball_depth(rk_symball_t *h, const int8_t *d_states, size_t n, int32_t 
  * ball that passed its build).  One launch; stream-ordered, no synchronisation. */
 int rk_symball_solve(rk_symball_t *h, const int8_t *d_states, size_t n, int32_t *d_lengths, int8_t *d_actions, int32_t *d_error,
                      void *stream);
+/* rk_bshorten against the symmetry ball: one pass over a batch of action queues, with rk_bshorten's contract (above) -- the
+ * same arguments, limits, return codes and d_error semantics, scratch of rk_bshorten_scratch_bytes(n, max_len, window) bytes --
+ * and d(i, j) = the symmetry ball's depth of X(i, j), i.e. the level of its representative.  That is the plain ball's d(i, j)
+ * at the same radius, so the cost, the ties to the largest i and the copy rule give output lengths equal to rk_bshorten's
+ * queue for queue; the radius may be 9 or 10.  The ball stores no word: a replaced window gets the INVERSE OF THE DESCENT --
+ * with w = rk_symball_solve's word for X(i, j) (at each step the lowest action whose child's representative lies one level
+ * nearer), w reversed with every action ^ 1, which leads from solved to X(i, j) and hence from s_i to s_j.  It may differ
+ * from the plain ball's word for the same window; it has the same length.  d_error[0] = RK_ESTATE: a descent found no way on
+ * or a level differs from the stored one (never in a ball that passed its build); that queue comes back as it is.  Three
+ * launches: d(i, j) of all windows (a persistent grid, one canonical form and probe per window), the shortest path, the
+ * rewritten queue.  The ball is only read.  Stream-ordered, no synchronisation. */
+int rk_sshorten(rk_symball_t *h, const int8_t *d_actions, const int32_t *d_len, size_t n, int max_len, int window, int8_t *d_out_actions,
+                int32_t *d_out_len, int32_t *d_error, void *d_scratch, size_t scratch_bytes, void *stream);
 
 /* ---- shortest solutions by a one-sided breadth-first search from the start that ends at the symmetry ball (rk_ssearch_*) ----
  * rk_bsearch_* with one difference: "the ball holds this child" is "the symmetry ball holds the child's canonical

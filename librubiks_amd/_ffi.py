@@ -136,6 +136,7 @@ SIGNATURES = {
 	"rk_symball_export": (_i, [_vp, _sz, _sz, _vp, _vp]),
 	"rk_symball_depth": (_i, [_vp, _vp, _sz, _vp, _vp]),
 	"rk_symball_solve": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+	"rk_sshorten": (_i, [_vp, _vp, _vp, _sz, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
 	"rk_ssearch_create": (_i, [C.POINTER(_vp), _vp, _sz, _i]),
 	"rk_ssearch_destroy": (_i, [_vp]),
 	"rk_ssearch_reset": (_i, [_vp, _vp, C.c_longlong, _vp]),

@@ -49,6 +49,7 @@
 #include "rk_error.h"
 #include "rk_frontier_dev.h"
 #include "rk_search_host.h"
+#include "rk_shorten_dev.h"
 
 namespace rk {
 
@@ -148,30 +149,8 @@ void k_ball_solve(BallView b, const uint32_t *queries, size_t n, int32_t *length
 }
 
 // ---- shortening action queues against the ball ---------------------------------------------------------------------------------
-constexpr int SHORTEN_MAX_LEN = 1 << 12;
-constexpr uint16_t SHORTEN_KEPT = 0xFFFFu;      // pred[0] of a queue that is not rewritten (an action outside 0..11, a length outside 0..max_len)
-constexpr int SHORTEN_DP_THREADS = 256;
-
-__device__ __forceinline__ int shorten_len(const int32_t *len, size_t p, int max_len)
-{
-	const int L = len[p];
-	return L < 0 ? 0 : L > max_len ? max_len : L;
-}
-
-// One chunk of up to 64 consecutive moves, one per lane (`a`; lanes >= n hold none): st = the state after the moves of lanes
-// 0 .. lane applied to s.  An action outside 0..11 indexes no table (it counts as action 0; its queue is never rewritten).
-// All 64 lanes call it.
-__device__ __forceinline__ void chunk_states(const u32x4 *s_act, uint32_t a, int lane, int n, const uint32_t s[5], uint32_t st[5])
-{
-	uint32_t X[12];
-	if (lane < n) load_action_table(s_act, a < 12u ? a : 0u, X);
-	else identity_moves(X);
-	scan_moves(X, lane, lane, n);
-	#pragma unroll
-	for (int j = 0; j < 5; j++) st[j] = s[j];
-	move5(st, X);
-}
-
+// (the limits, chunk_states, the DP, the reversal of the pred chain and the argument checks are in rk_shorten_dev.h: rk_sym.hip's
+// rk_sshorten runs the same ones)
 // d(i, j) of every window of queue p that starts at i: wave (p, i), lane = offset inside a chunk of 64 moves.  The byte of window
 // (i, j) is depth[(p * max_len + j - 1) * window + (j - i - 1)]: the row of an END j is contiguous, which is how the DP reads it.
 __global__ __launch_bounds__(256)
@@ -208,54 +187,18 @@ void k_shorten_windows(BallView b, const int8_t *__restrict__ actions, const int
 	}
 }
 
-// The shortest path 0 -> L of queue blockIdx.x.  key = cost << 12 | (j - i - 1): the minimum is the least cost and, among equal
-// costs, the largest i.  One barrier per j: the partial minima alternate between two rows, and cost[j] is read by the thread
-// that wrote it (k = 1) or two barriers later.
+// The shortest path 0 -> L of queue blockIdx.x (shorten_dp).
 __global__ __launch_bounds__(SHORTEN_DP_THREADS)
 void k_shorten_dp(const int8_t *__restrict__ actions, const int32_t *__restrict__ len, int max_len, int window,
                   const int8_t *__restrict__ depth, uint16_t *__restrict__ pred, int32_t *error)
 {
-	__shared__ uint16_t cost[SHORTEN_MAX_LEN + 1];
-	__shared__ uint32_t part[2][SHORTEN_DP_THREADS / 64];
-	const size_t p = blockIdx.x;
-	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-	const int L = shorten_len(len, p, max_len);
-	const int8_t *row = actions + p * (size_t)max_len;
-	uint16_t *pr = pred + p * (size_t)(max_len + 1);
-	int bad = len[p] != L;
-	for (int k = tid; k < L; k += SHORTEN_DP_THREADS) bad |= (uint8_t)row[k] >= 12u;
-	if (__syncthreads_or(bad)) {                                         // reported; the queue comes back as it is
-		if (tid == 0) { pr[0] = SHORTEN_KEPT; *error = RK_EINVAL; }
-		return;
-	}
-	if (tid == 0) { cost[0] = 0; pr[0] = 0; }
-	__syncthreads();
-	for (int j = 1; j <= L; j++) {
-		const int8_t *dj = depth + (p * (size_t)max_len + (size_t)(j - 1)) * (size_t)window;
-		const int kmax = min(window, j);
-		uint32_t best = 0xFFFFFFFFu;
-		for (int k = tid + 1; k <= kmax; k += SHORTEN_DP_THREADS) {          // i = j - k
-			const int d = dj[k - 1];
-			const int wgt = d >= 0 ? d : k == 1 ? 1 : -1;                        // a single move outside the ball (radius 0) costs itself
-			if (wgt >= 0) best = min(best, (((uint32_t)cost[j - k] + (uint32_t)wgt) << 12) | (uint32_t)(k - 1));
-		}
-		#pragma unroll
-		for (int off = 32; off >= 1; off >>= 1) best = min(best, (uint32_t)__shfl_xor((int)best, off, 64));
-		if (lane == 0) part[j & 1][wave] = best;
-		__syncthreads();
-		if (tid == 0) {
-			uint32_t m = part[j & 1][0];
-			#pragma unroll
-			for (int v = 1; v < SHORTEN_DP_THREADS / 64; v++) m = min(m, part[j & 1][v]);
-			cost[j] = (uint16_t)(m >> 12);                                   // (k = 1 is always a candidate: m is a real key)
-			pr[j] = (uint16_t)(j - 1 - (int)(m & 0xFFFu));
-		}
-	}
+	shorten_dp(actions, len, max_len, window, depth, pred, error);
 }
 
-// The rewritten queue of queue blockIdx.x: one wave.  Lane 0 turns the pred chain from L into a chain of successors from 0, then
-// the wave takes the edges in order.  An edge of weight j - i (or a single move outside the ball) is copied; any other is the
-// ball's word for X(i, j), d(i, j) moves.  The output is never longer than the input; every index is checked all the same.
+// The rewritten queue of queue blockIdx.x: one wave.  Lane 0 turns the pred chain from L into a chain of successors from 0
+// (shorten_successors), then the wave takes the edges in order.  An edge of weight j - i (or a single move outside the ball) is
+// copied; any other is the ball's word for X(i, j), d(i, j) moves.  The output is never longer than the input; every index is
+// checked all the same.
 __global__ __launch_bounds__(64)
 void k_shorten_emit(BallView b, const int8_t *__restrict__ actions, const int32_t *__restrict__ len, int max_len, int window,
                     const int8_t *__restrict__ depth, const uint16_t *__restrict__ pred, int8_t *__restrict__ out_actions,
@@ -274,21 +217,7 @@ void k_shorten_emit(BallView b, const int8_t *__restrict__ actions, const int32_
 	bool ok = pr[0] != SHORTEN_KEPT;
 	int pos = 0;
 	if (ok) {
-		for (int k = lane; k <= L; k += 64) nxt[k] = pr[k];
-		__syncthreads();
-		if (lane == 0) {
-			int good = 1;
-			int j = L, i = L > 0 ? nxt[L] : 0;
-			while (j > 0) {
-				if (i >= j || j - i > window) { good = 0; break; }              // (never: the DP wrote pred[j] in j - window .. j - 1)
-				const int ii = i > 0 ? nxt[i] : 0;
-				nxt[i] = (uint16_t)j;
-				j = i; i = ii;
-			}
-			s_ok = good;
-		}
-		__syncthreads();
-		ok = s_ok != 0;
+		ok = shorten_successors(pr, L, window, lane, nxt, &s_ok);
 		for (int i = 0; ok && i < L; ) {
 			const int j = nxt[i], span = j - i;
 			if (span < 1 || span > window || j > L) { ok = false; break; }
@@ -555,11 +484,6 @@ size_t ball_capacity(int radius)
 	return n;
 }
 
-constexpr size_t SHORTEN_MAX_WAVES = (size_t)1 << 30;    // queues x max_len of one rk_bshorten call: a wave each, four to a workgroup
-
-// the d(i, j) bytes of a call, rounded up so that the pred rows behind them are aligned
-size_t shorten_depth_bytes(size_t n, int max_len, int window) { return (n * (size_t)max_len * (size_t)window + 15) & ~(size_t)15; }
-
 }  // namespace
 
 extern "C" {
@@ -654,16 +578,9 @@ long long rk_bshorten_scratch_bytes(size_t n, int max_len, int window)
 int rk_bshorten(rk_ball_t *h, const int8_t *d_actions, const int32_t *d_len, size_t n, int max_len, int window, int8_t *d_out_actions,
                 int32_t *d_out_len, int32_t *d_error, void *d_scratch, size_t scratch_bytes, void *stream)
 {
-	if (!h) return fail(RK_EINVAL, "rk_bshorten: null ball");
-	if (!h->built) return fail(RK_ESTATE, "rk_bshorten: build the ball first");
-	const long long need = rk_bshorten_scratch_bytes(n, max_len, window);
-	if (need < 0) return (int)need;
-	if (!d_error) return fail(RK_EINVAL, "rk_bshorten: null pointer");
-	if (n != 0 && (!d_actions || !d_len || !d_out_actions || !d_out_len || !d_scratch)) return fail(RK_EINVAL, "rk_bshorten: null pointer");
-	if (((uintptr_t)d_len | (uintptr_t)d_out_len | (uintptr_t)d_error) & 3u) return fail(RK_EINVAL, "rk_bshorten: device pointers must be 4-byte aligned");
-	if ((uintptr_t)d_scratch & 15u) return fail(RK_EINVAL, "rk_bshorten: the scratch must be 16-byte aligned");
-	if (n != 0 && d_actions == d_out_actions) return fail(RK_EINVAL, "rk_bshorten: the output may not be the input");
-	if (scratch_bytes < (size_t)need) return fail(RK_EINVAL, "rk_bshorten: %zu bytes of scratch, %lld needed", scratch_bytes, need);
+	if (int e = shorten_check("rk_bshorten", h, h && h->built, d_actions, d_len, n, max_len, window, d_out_actions, d_out_len, d_error, d_scratch,
+	                          scratch_bytes))
+		return e;
 	hipStream_t st = (hipStream_t)stream;
 	RK_HIP(hipMemsetAsync(d_error, 0, sizeof(int32_t), st));
 	if (n == 0) return RK_OK;

@@ -41,6 +41,16 @@
 //                 in the own table on the raw child
 //   k_ss_scan, k_ss_append, k_ss_end   fr_scan, fr_append, bsearch_end; S_MEET is the node in THIS ball
 //   k_ss_walk     one wave: the own path and the meeting action, then the descent from the meeting state (sb_descend)
+//
+// Shortening (rk_sshorten) is rk_ball.hip's rk_bshorten -- the same contract, scratch, DP and copy rule (rk_shorten_dev.h) -- with
+// d(i, j) = the depth of the REPRESENTATIVE of X(i, j), which is the plain ball's d(i, j) at the same radius, so the lengths are
+// rk_bshorten's queue for queue.  There is no stored word for a replaced edge: it gets the inverse of the descent from X(i, j),
+// i.e. rk_symball_solve's word reversed with every action ^ 1, which may differ from the plain ball's word of the same length.
+//   k_ss_windows  a persistent grid, waves stride over the (queue, i) pairs, the tables staged once per workgroup: the windows
+//                 composed with lane = offset, then one canonical form (lane = symmetry) and one probe per window
+//   k_ss_dp       shorten_dp
+//   k_ss_emit     a wave per queue: a replaced edge is composed again, canonicalised, probed, descended and written inverted
+// Three launches; nothing of the ball is written.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <climits>
@@ -52,6 +62,7 @@
 #include "rk_error.h"
 #include "rk_search_dev.h"
 #include "rk_search_host.h"
+#include "rk_shorten_dev.h"
 #include "rk_sym_dev.h"
 
 namespace rk {
@@ -172,6 +183,139 @@ void k_sb_solve(SymBallView b, const uint32_t *queries, size_t n, int32_t *lengt
 		if (lane == 0) lengths[q] = ok ? len : -1;
 		for (int k = (ok ? len : 0) + lane; k < b.radius; k += 64) row[k] = -1;
 	}
+}
+
+// ---- shortening action queues against the symmetry ball (rk_sshorten; the DP and everything ball-independent: rk_shorten_dev.h) ----
+// d(i, j) of every window of every queue, at rk_ball.hip's k_shorten_windows' addresses: the byte of window (i, j) is
+// depth[(p * max_len + j - 1) * window + (j - i - 1)].  A persistent grid: every workgroup stages s_act (576 B) and the symmetry
+// tables (23 232 B) ONCE, then its four waves stride over the (queue, i) pairs.  A workgroup per four pairs, as in
+// k_shorten_windows, would stage 23 KB again for a handful of probes -- most pairs of a padded batch have no window at all.
+// Per pair the windows are composed as there: lane = offset, chunk_states in chunks of 64 with the carried state, the next
+// chunk's actions loaded ahead.  Then the chunk's states are taken one at a time: lane k's state is broadcast (five v_readlane),
+// canonicalised with lane = symmetry as everywhere in this file (so the table reads bank as rk_sym_dev.h describes), its
+// representative probed once, and lane k keeps the level.  The wave index goes through readfirstlane: the pair, the queue's
+// length, every trip count and the broadcast lane are wave-uniform, so all 64 lanes reach every sym_canonical.
+__global__ __launch_bounds__(256)
+void k_ss_windows(SymBallView b, const int8_t *__restrict__ actions, const int32_t *__restrict__ len, size_t n, int max_len, int window,
+                  int8_t *__restrict__ depth)
+{
+	__shared__ uint32_t s_sym[SYM_LDS_DWORDS];
+	__shared__ u32x4 s_act[36];
+	sym_stage(s_sym, threadIdx.x, 256);
+	stage_action_tables(s_act, threadIdx.x);
+	__syncthreads();
+	const int lane = threadIdx.x & 63;
+	const SymLane SL = sym_lane(min(lane, N_SYM - 1));
+	const size_t pairs = n * (size_t)max_len;
+	for (size_t w = (size_t)blockIdx.x * 4 + (size_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); w < pairs; w += (size_t)gridDim.x * 4) {
+		const size_t p = w / (size_t)max_len;
+		const int i = (int)(w - p * (size_t)max_len);
+		const int L = shorten_len(len, p, max_len);
+		if (i >= L) continue;
+		const int8_t *row = actions + p * (size_t)max_len;
+		const int moves = min(window, L - i);                                // windows (i, i + 1) .. (i, i + moves)
+		uint32_t s[5] = {SOLVED_DW[0], SOLVED_DW[1], SOLVED_DW[2], SOLVED_DW[3], SOLVED_DW[4]};
+		uint32_t a_next = lane < moves ? (uint32_t)(uint8_t)row[i + lane] : 0xFFu;
+		for (int d0 = 0; d0 < moves; d0 += 64) {
+			const int nc = min(64, moves - d0);
+			const uint32_t a = a_next;
+			a_next = d0 + 64 + lane < moves ? (uint32_t)(uint8_t)row[i + d0 + 64 + lane] : 0xFFu;    // behind the scan and the probes
+			uint32_t st[5];
+			chunk_states(s_act, a, lane, nc, s, st);
+			int mine = -1;
+			for (int k = 0; k < nc; k++) {
+				uint32_t x[5], rep[5];
+				#pragma unroll
+				for (int j = 0; j < 5; j++) x[j] = (uint32_t)__builtin_amdgcn_readlane((int)st[j], k);
+				int sym, count;
+				sym_canonical(s_sym, SL, lane, x, rep, &sym, &count);
+				const uint32_t e = probe_find(b.table, b.mask, b.states, rep);
+				const int lvl = e ? level_of(b.lstart, e) : -1;
+				if (lane == k) mine = lvl;
+			}
+			if (lane < nc) {
+				const int k = d0 + lane;                                         // j - i - 1
+				depth[(p * (size_t)max_len + (size_t)(i + k)) * (size_t)window + (size_t)k] = (int8_t)mine;
+			}
+			#pragma unroll
+			for (int j = 0; j < 5; j++) s[j] = (uint32_t)__builtin_amdgcn_readlane((int)st[j], nc - 1);   // carries into the next chunk
+		}
+	}
+}
+
+__global__ __launch_bounds__(SHORTEN_DP_THREADS)
+void k_ss_dp(const int8_t *__restrict__ actions, const int32_t *__restrict__ len, int max_len, int window, const int8_t *__restrict__ depth,
+             uint16_t *__restrict__ pred, int32_t *error)
+{
+	shorten_dp(actions, len, max_len, window, depth, pred, error);
+}
+
+// The rewritten queue of queue blockIdx.x: one wave, as rk_ball.hip's k_shorten_emit but for the word of a replaced edge.  The
+// ball keeps no parents, so X(i, j) is composed again, canonicalised and probed (its level must be the stored d), and the word
+// is the INVERSE of the descent from X(i, j): sb_descend's step k, action a, is written as a ^ 1 at place d - 1 - k, which leads
+// from solved to X(i, j), hence from s_i to s_j.  A failed descent, a level that differs or an index out of range is RK_ESTATE
+// and the queue comes back as it is.  Everything is the same in every lane; lane 0 writes the replaced words.
+__global__ __launch_bounds__(64)
+void k_ss_emit(SymBallView b, const int8_t *__restrict__ actions, const int32_t *__restrict__ len, int max_len, int window,
+               const int8_t *__restrict__ depth, const uint16_t *__restrict__ pred, int8_t *__restrict__ out_actions,
+               int32_t *__restrict__ out_len, int32_t *error)
+{
+	__shared__ uint32_t s_sym[SYM_LDS_DWORDS];
+	__shared__ u32x4 s_act[36];
+	__shared__ uint16_t nxt[SHORTEN_MAX_LEN + 1];
+	__shared__ int s_ok;
+	const size_t p = blockIdx.x;
+	const int lane = threadIdx.x;
+	sym_stage(s_sym, lane, 64);
+	stage_action_tables(s_act, lane);
+	const SymLane SL = sym_lane(min(lane, N_SYM - 1));
+	const int L = shorten_len(len, p, max_len);
+	const int8_t *row = actions + p * (size_t)max_len;
+	int8_t *out = out_actions + p * (size_t)max_len;
+	const uint16_t *pr = pred + p * (size_t)(max_len + 1);
+	bool ok = pr[0] != SHORTEN_KEPT;
+	int pos = 0;
+	if (ok) {
+		ok = shorten_successors(pr, L, window, lane, nxt, &s_ok);            // (its barriers are behind the staging as well)
+		for (int i = 0; ok && i < L; ) {
+			const int j = nxt[i], span = j - i;
+			if (span < 1 || span > window || j > L) { ok = false; break; }
+			const int d = depth[(p * (size_t)max_len + (size_t)(j - 1)) * (size_t)window + (size_t)(span - 1)];
+			if (d < 0 || d >= span) {                                        // as short as the ball knows: copied
+				if (pos + span > max_len) { ok = false; break; }
+				for (int k = lane; k < span; k += 64) out[pos + k] = row[i + k];
+				pos += span;
+			} else if (d > 0) {
+				uint32_t s[5] = {SOLVED_DW[0], SOLVED_DW[1], SOLVED_DW[2], SOLVED_DW[3], SOLVED_DW[4]};
+				for (int d0 = 0; d0 < span; d0 += 64) {
+					const int nc = min(64, span - d0);
+					const uint32_t a = lane < nc ? (uint32_t)(uint8_t)row[i + d0 + lane] : 0xFFu;
+					uint32_t st[5];
+					chunk_states(s_act, a, lane, nc, s, st);
+					#pragma unroll
+					for (int q = 0; q < 5; q++) s[q] = (uint32_t)__builtin_amdgcn_readlane((int)st[q], nc - 1);
+				}
+				uint32_t rep[5];                                             // X(i, j) = s: the same in every lane
+				int sym, count;
+				sym_canonical(s_sym, SL, lane, s, rep, &sym, &count);
+				const uint32_t g = probe_find(b.table, b.mask, b.states, rep);
+				if (g == 0u || level_of(b.lstart, g) != d || d > b.radius || pos + d > max_len) { ok = false; break; }
+				bool down;
+				const int steps = sb_descend(b, s_sym, s_act, SL, lane, s, d, [&](int k, int a) { if (lane == 0) out[pos + d - 1 - k] = (int8_t)(a ^ 1); },
+				                             &down);
+				if (!down || steps != d) { ok = false; break; }
+				pos += d;
+			}
+			i = j;
+		}
+		if (!ok && lane == 0) *error = RK_ESTATE;                           // an engine error: the queue comes back as it is
+	}
+	if (!ok) {
+		for (int k = lane; k < L; k += 64) out[k] = row[k];
+		pos = L;
+	}
+	for (int k = pos + lane; k < max_len; k += 64) out[k] = -1;
+	if (lane == 0) out_len[p] = pos;
 }
 
 // ---- the search from a start towards the symmetry ball ----------------------------------------------------------------------
@@ -533,6 +677,25 @@ int rk_symball_solve(rk_symball_t *h, const int8_t *d_states, size_t n, int32_t 
 	if (!d_actions && h->d.radius > 0) return fail(RK_EINVAL, "rk_symball_solve: null pointer");
 	hipLaunchKernelGGL(k_sb_solve, dim3(sym_grid(n)), dim3(256), 0, st, h->view, reinterpret_cast<const uint32_t *>(d_states), n, d_lengths,
 	                   d_actions, d_error);
+	RK_HIP(hipGetLastError());
+	return RK_OK;
+}
+
+int rk_sshorten(rk_symball_t *h, const int8_t *d_actions, const int32_t *d_len, size_t n, int max_len, int window, int8_t *d_out_actions,
+                int32_t *d_out_len, int32_t *d_error, void *d_scratch, size_t scratch_bytes, void *stream)
+{
+	if (int e = shorten_check("rk_sshorten", h, h && h->built, d_actions, d_len, n, max_len, window, d_out_actions, d_out_len, d_error, d_scratch,
+	                          scratch_bytes))
+		return e;
+	hipStream_t st = (hipStream_t)stream;
+	RK_HIP(hipMemsetAsync(d_error, 0, sizeof(int32_t), st));
+	if (n == 0) return RK_OK;
+	int8_t *depth = static_cast<int8_t *>(d_scratch);
+	uint16_t *pred = reinterpret_cast<uint16_t *>(depth + shorten_depth_bytes(n, max_len, window));
+	hipLaunchKernelGGL(k_ss_windows, dim3(sym_grid(n * (size_t)max_len)), dim3(256), 0, st, h->view, d_actions, d_len, n, max_len, window, depth);
+	hipLaunchKernelGGL(k_ss_dp, dim3((unsigned)n), dim3(SHORTEN_DP_THREADS), 0, st, d_actions, d_len, max_len, window, depth, pred, d_error);
+	hipLaunchKernelGGL(k_ss_emit, dim3((unsigned)n), dim3(64), 0, st, h->view, d_actions, d_len, max_len, window, depth, pred, d_out_actions, d_out_len,
+	                   d_error);
 	RK_HIP(hipGetLastError());
 	return RK_OK;
 }

@@ -589,61 +589,32 @@ class _KeptBall(_ffi.Owner):
 		self._solve(q, n, lengths, actions)
 		return lengths.cpu().numpy().astype(np.int64), actions.cpu().numpy().astype(np.int64)[:, :self.radius]
 
-	def depth_of_node(self, node: int) -> int:
-		"""The depth of node `node` (1 .. len(ball)), from the level boundaries."""
-		return int(np.searchsorted(self.level_start, node, side="right")) - 1
+	MAX_QUEUE = 4096                        # the longest queue of rk_bshorten and rk_sshorten
+	shorten_scratch_bytes = 256 << 20       # the most scratch one call of the engine is given; a batch is cut into calls to fit
+	_shorten_entry = None                   # the engine's shortening entry
 
-
-class DeviceGoalBall(_KeptBall):
-	"""
-	The ball around the solved state, built once and kept in HBM (engine rk_ball_*, csrc/rk_ball.hip): every state within `radius`
-	quarter turns, in `DeviceBFS`'s order without goal test or budget.  Node 1 is the solved state; a level's parents are popped in
-	index order, their children taken in action order, a child the pool holds is skipped, any other appended with its parent and
-	its action (the move away from solved).  Level `radius` is stored and never expanded.  Level l is the index range
-	`level_start[l] .. level_start[l + 1] - 1`, so depths come from indices.  The pool does not depend on `pops`.
-
-	The ball is built at first use (or by `build()`) and read-only from then on: `depth` and `solve` answer a batch of states in
-	one launch each, and any number of `DeviceBallSearch` agents may share it.  States are in the representation cube.get_is2024()
-	names when a method is called.  Radius 8 holds 86.0 M states in about 3.2 GB.
-	"""
-	LEVELS = (1, 12, 114, 1_068, 10_011, 93_840, 878_880, 8_221_632, 76_843_595)    # states at distance 0 .. 8, quarter turns
-	MAX_RADIUS = len(LEVELS) - 1
-	_entries = "rk_ball"
-
-	def __init__(self, radius: int, pops: int = 16_384):
-		super().__init__(radius, pops)
-
-	def _rows(self, states) -> np.ndarray:
-		is2024 = cube.get_is2024()
-		arr = np.asarray(states, dtype=np.int8)
-		width = 20 if is2024 else 288
-		if arr.size % width or (arr.ndim and arr.shape[-1] != (20 if is2024 else 6)):
-			raise ValueError(f"states must be (n, 20), or (n, 6, 8, 6) in 6x8x6 mode, got shape {arr.shape}")
-		return _roots20(is2024, arr, arr.size // width)
-
-	def arrays(self):
-		"""(states, parents, actions) of nodes 1 .. len(ball) in index order, like `DeviceBFS.arrays()`: parent 0 and action -1 for
-		the solved state; an action is the move from the parent, away from solved."""
-		is2024 = cube.get_is2024()
-		if is2024 not in self._cache:
-			n = len(self)
-			states, parents, actions = eng.export_frontier(_ffi.lib().rk_ball_export, (self._h,), n)
-			self._cache = {is2024: (_states_out(is2024, states, n)[1:], parents[1:], actions[1:])}
-		return self._cache[is2024]
-
-	MAX_QUEUE = 4096                        # rk_bshorten's longest queue
-	shorten_scratch_bytes = 256 << 20       # the most scratch one rk_bshorten call is given; a batch is cut into calls to fit
+	def _shorten(self, *args):
+		"""The engine's shortening pass on device pointers: what follows the handle in rk_bshorten's argument list."""
+		_ffi.check(getattr(_ffi.lib(), self._shorten_entry)(self._h, *args))
 
 	def shorten(self, action_queues, window: int = None, passes: int = None) -> list:
 		"""
 		Every action queue (a sequence of actions 0..11, at most 4096 of them; any agent's solution) made locally optimal against
-		the ball, on the device (engine rk_bshorten_*): a list of int64 arrays, each no longer than its queue and with the same
-		effect on any state.  Neither start states nor a net are needed: the moves i .. j-1 of a queue, applied to the solved state,
-		give a state whose ball depth is the distance between the queue's states i and j, so every window of at most `window` moves
-		is looked up in the ball, and the best set of replacements by the ball's own words is a shortest path through a small DAG
-		(DESIGN 3.58).  A pass runs on all queues, further passes on those that got shorter, until none does or `passes` passes are
-		done.  Then every window of at most `window` moves whose net effect the ball holds has exactly that state's depth in moves.
-		`window=None`: every window of every queue.
+		the ball, on the device (engine rk_bshorten_* for `DeviceGoalBall`, rk_sshorten for `DeviceSymBall`): a list of int64 arrays,
+		each no longer than its queue and with the same effect on any state.  Neither start states nor a net are needed: the moves
+		i .. j-1 of a queue, applied to the solved state, give a state whose ball depth is the distance between the queue's states i
+		and j, so every window of at most `window` moves is looked up in the ball, and the best set of replacements by the ball's own
+		words is a shortest path through a small DAG.  A pass runs on all queues, further passes on those that
+		got shorter, until none does or `passes` passes are done.  Then every window of at most `window` moves whose net effect the
+		ball holds has exactly that state's depth in moves.  `window=None`: every window of every queue.
+
+		Which word a replaced window gets depends on the ball; its length does not.  `DeviceGoalBall`: the ball's stored word for the
+		window's net effect X, the stored actions from node 1 down to X's node.  `DeviceSymBall`: the inverse of the descent -- `solve`'s
+		word for X (at each step the lowest action whose child lies one level nearer) reversed, every action replaced by its
+		opposite turn.  Both lead from solved to X, so a pass of either ball over the same queues gives equal lengths at equal radius,
+		queue for queue, and the same states; the symmetry ball does it from 1/60 of the memory, and at radius 9 and 10 as well.
+		(Later passes start from words that may differ where a window has several shortest words, so the two fixed points of a
+		narrow window -- both locally optimal -- need not have equal lengths in every queue.)
 		"""
 		queues = [np.asarray(q, dtype=np.int64).reshape(-1) for q in action_queues]
 		eng.int_in("window", window, 1, none_ok=True, what="an integer >= 1 or None")
@@ -680,11 +651,11 @@ class DeviceGoalBall(_KeptBall):
 				d_out_len = torch.empty(n, dtype=torch.int32, device=gpu)
 				d_err = torch.empty(1, dtype=torch.int32, device=gpu)
 				scratch = torch.empty(need, dtype=torch.uint8, device=gpu)
-				_ffi.check(lib.rk_bshorten(self._h, d_acts.data_ptr(), d_lens.data_ptr(), n, max_len, wc, d_out.data_ptr(),
-				                           d_out_len.data_ptr(), d_err.data_ptr(), scratch.data_ptr(), need, stream))
+				self._shorten(d_acts.data_ptr(), d_lens.data_ptr(), n, max_len, wc, d_out.data_ptr(), d_out_len.data_ptr(), d_err.data_ptr(),
+				              scratch.data_ptr(), need, stream)
 				out, out_len, err = d_out.cpu().numpy(), d_out_len.cpu().numpy(), int(d_err.item())
 				if err:
-					raise _ffi.RubiksHipError(f"rk_bshorten reported error {err} for queues that passed the host's checks")
+					raise _ffi.RubiksHipError(f"{self._shorten_entry} reported error {err} for queues that passed the host's checks")
 				for r, i in enumerate(part):
 					if out_len[r] < len(queues[i]):
 						shorter.append(i)
@@ -692,6 +663,49 @@ class DeviceGoalBall(_KeptBall):
 			active = [i for i in shorter if len(queues[i])]
 			done += 1
 		return queues
+
+	def depth_of_node(self, node: int) -> int:
+		"""The depth of node `node` (1 .. len(ball)), from the level boundaries."""
+		return int(np.searchsorted(self.level_start, node, side="right")) - 1
+
+
+class DeviceGoalBall(_KeptBall):
+	"""
+	The ball around the solved state, built once and kept in HBM (engine rk_ball_*, csrc/rk_ball.hip): every state within `radius`
+	quarter turns, in `DeviceBFS`'s order without goal test or budget.  Node 1 is the solved state; a level's parents are popped in
+	index order, their children taken in action order, a child the pool holds is skipped, any other appended with its parent and
+	its action (the move away from solved).  Level `radius` is stored and never expanded.  Level l is the index range
+	`level_start[l] .. level_start[l + 1] - 1`, so depths come from indices.  The pool does not depend on `pops`.
+
+	The ball is built at first use (or by `build()`) and read-only from then on: `depth` and `solve` answer a batch of states in
+	one launch each, and any number of `DeviceBallSearch` agents may share it.  States are in the representation cube.get_is2024()
+	names when a method is called.  Radius 8 holds 86.0 M states in about 3.2 GB.
+	"""
+	LEVELS = (1, 12, 114, 1_068, 10_011, 93_840, 878_880, 8_221_632, 76_843_595)    # states at distance 0 .. 8, quarter turns
+	MAX_RADIUS = len(LEVELS) - 1
+	_entries = "rk_ball"
+	_shorten_entry = "rk_bshorten"          # a replaced window gets the stored actions from node 1 down to the window's node
+
+	def __init__(self, radius: int, pops: int = 16_384):
+		super().__init__(radius, pops)
+
+	def _rows(self, states) -> np.ndarray:
+		is2024 = cube.get_is2024()
+		arr = np.asarray(states, dtype=np.int8)
+		width = 20 if is2024 else 288
+		if arr.size % width or (arr.ndim and arr.shape[-1] != (20 if is2024 else 6)):
+			raise ValueError(f"states must be (n, 20), or (n, 6, 8, 6) in 6x8x6 mode, got shape {arr.shape}")
+		return _roots20(is2024, arr, arr.size // width)
+
+	def arrays(self):
+		"""(states, parents, actions) of nodes 1 .. len(ball) in index order, like `DeviceBFS.arrays()`: parent 0 and action -1 for
+		the solved state; an action is the move from the parent, away from solved."""
+		is2024 = cube.get_is2024()
+		if is2024 not in self._cache:
+			n = len(self)
+			states, parents, actions = eng.export_frontier(_ffi.lib().rk_ball_export, (self._h,), n)
+			self._cache = {is2024: (_states_out(is2024, states, n)[1:], parents[1:], actions[1:])}
+		return self._cache[is2024]
 
 	def __str__(self):
 		return f"Goal ball (device, radius={self.radius})"
@@ -707,6 +721,11 @@ class DeviceSymBall(_KeptBall):
 	level_start[l + 1] - 1`.  The pool holds states only -- no parents, no actions: `solve` descends, at each step the lowest
 	action whose child lies one level nearer.  The pool does not depend on `pops`.
 
+	`shorten` makes action queues locally optimal against this ball as `DeviceGoalBall.shorten` does against the plain one, a pass
+	giving the same lengths at the same radius -- radius 8 from about 53 MB instead of 3.2 GB -- and windows whose net effect lies 9
+	or 10 quarter turns from solved at radius 9 or 10.  With no stored word, a replaced window gets the inverse of the descent (`solve`'s
+	word for the window's net effect, reversed, every turn the opposite one).
+
 	`capacity` is the number of orbits the pool can hold (None: the sum over the levels of ceil(level size / 48 * 1.02) + 64);
 	a build that does not fit stops cleanly with a RubiksHipError (RK_ECAPACITY).  `states_covered[l]` is the sum of the orbit
 	sizes of level l: the number of states of the plain ball's level (checked by the engine for levels 0..8).  States are in the
@@ -717,6 +736,7 @@ class DeviceSymBall(_KeptBall):
 	MAX_CAPACITY = 0x3FFFFFF0
 	_entries = "rk_symball"
 	_status_words = 32
+	_shorten_entry = "rk_sshorten"          # a replaced window gets the inverse of the descent from the window's net effect
 
 	def __init__(self, radius: int, pops: int = 16_384, capacity: int = None):
 		super().__init__(radius, pops)
