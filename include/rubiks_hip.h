@@ -528,7 +528,7 @@ typedef struct rk_symball rk_symball_t;
 /* radius 0..10; pops 1..2^22; capacity: orbits the pool can hold, 0 = the sum over the levels of ceil(level size / 48 * 1.02)
  * + 64.  Allocates nothing. */
 int rk_symball_create(rk_symball_t **out, int radius, int pops, size_t capacity);
-/* RK_ESTATE while a search (rk_ssearch_*) is attached to the ball. */
+/* RK_ESTATE while a search (rk_ssearch_*, rk_ssearchb_*) is attached to the ball. */
 int rk_symball_destroy(rk_symball_t *h);
 /* Builds the ball (nothing if it is built): iterations of five launches, the host looks every `poll` of them.  An iteration pops
  * only as many representatives as fit the pool whatever their children are; when not one fits, the build stops before that
@@ -598,6 +598,40 @@ int rk_ssearch_export(rk_ssearch_t *h, size_t first, size_t count, int8_t *h_sta
  * at most `radius` steps; walked on the device by one wave.  Returns its length or a negative error (RK_ESTATE: not met, or a
  * state on the way down has no such child); writes at most max_len actions. */
 long long rk_ssearch_path(rk_ssearch_t *h, long long *h_actions, size_t max_len, void *stream);
+
+/* ---- many such searches in lock-step (rk_ssearchb_*) --------------------------------------------------------------------
+ * rk_bsearchb_* for rk_ssearch: n_slots slots, each a whole rk_ssearch of its own -- pool, table sized to it, counters, batch
+ * scratch, the words of the probe launch --, advanced by the same five launches with the slot in the grid's second dimension;
+ * all read one symmetry ball.  Every slot computes exactly what rk_ssearch computes for its start, hence what a slot of
+ * rk_bsearchb computes on a plain ball of the same radius (but for the ball's half of the queue, which has the same length).  A
+ * slot that is done or was never started costs one counter read per launch and stages no table.  The capacity is fixed per
+ * slot, with rk_bsearchb's rule: a slot whose next iteration might not fit (n_states + 12 * pops of it > capacity) stops before
+ * that iteration with stop reason 5 = pool full: done, not won, no error, the other slots undisturbed.  Entry for entry the
+ * arguments, limits and return codes are rk_bsearchb_*'s. */
+typedef struct rk_ssearchb rk_ssearchb_t;
+/* n_slots 1..1024, capacity_per_slot 2..0x3FFFFFF0, pops 1..2^22.  RK_ESTATE if the ball is not built (nothing is made or
+ * attached); attaches to `ball`: rk_symball_destroy refuses meanwhile. */
+int rk_ssearchb_create(rk_ssearchb_t **out, rk_symball_t *ball, int n_slots, size_t capacity_per_slot, int pops);
+int rk_ssearchb_destroy(rk_ssearchb_t *h);
+/* Between iterations: slot slots[j] (all different, 0 .. n_slots - 1) starts again from HOST state j of h_start_states int8
+ * (n, 20) with the budget max_states[j].  Clears the tables and counters of the named slots only; every other slot stays
+ * exactly where it was.  A start whose orbit the ball holds is answered here, with nothing popped.  One wave per named slot.
+ * Synchronises. */
+int rk_ssearchb_reset(rk_ssearchb_t *h, int n, const int32_t *slots, const int8_t *h_start_states, const long long *max_states,
+                      void *stream);
+/* `iterations` iterations of all slots, five launches each; stream-ordered, no synchronisation. */
+int rk_ssearchb_run(rk_ssearchb_t *h, int iterations, void *stream);
+/* Synchronises; h_status (n_slots, 10): rk_ssearch_status's ten words of every slot (zeros for a slot never started), read with
+ * one copy; word 9 is the node of the meeting's representative in the symmetry ball.  Stop reason 5 = pool full. */
+int rk_ssearchb_status(rk_ssearchb_t *h, long long *h_status, void *stream);
+/* Row s of HOST h_out int32 (n_slots, 1 + max_len): the length of slot s's action queue, then its first max_len actions; -1 for
+ * a slot that has not met, -2 where rk_ssearch_path reports RK_ESTATE for a search that met (the meeting state is not where the
+ * search says, or a state on the way down has no child one level nearer).  max_len 0..4096.  One launch, one wave per slot, and
+ * one copy.  Synchronises. */
+int rk_ssearchb_paths(rk_ssearchb_t *h, int32_t *h_out, int max_len, void *stream);
+/* Rows [first, first+count) of slot `slot`'s pool to HOST buffers (any may be NULL), as rk_ssearch_export. */
+int rk_ssearchb_export(rk_ssearchb_t *h, int slot, size_t first, size_t count, int8_t *h_states, long long *h_parents,
+                       long long *h_actions, void *stream);
 
 /* ---- device-resident epsilon-greedy value maximisation (agents.py:649-726) ---------------------------------------
  * W = workers walkers take D = depth moves from a root (:692-715); the visited state with the best value becomes the next

@@ -146,6 +146,13 @@ SIGNATURES = {
 	"rk_ssearch_size": (C.c_longlong, [_vp]),
 	"rk_ssearch_export": (_i, [_vp, _sz, _sz, _vp, _vp, _vp, _vp]),
 	"rk_ssearch_path": (C.c_longlong, [_vp, _vp, _sz, _vp]),
+	"rk_ssearchb_create": (_i, [C.POINTER(_vp), _vp, _i, _sz, _i]),
+	"rk_ssearchb_destroy": (_i, [_vp]),
+	"rk_ssearchb_reset": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
+	"rk_ssearchb_run": (_i, [_vp, _i, _vp]),
+	"rk_ssearchb_status": (_i, [_vp, _vp, _vp]),
+	"rk_ssearchb_paths": (_i, [_vp, _vp, _i, _vp]),
+	"rk_ssearchb_export": (_i, [_vp, _i, _sz, _sz, _vp, _vp, _vp, _vp]),
 	"rk_egvm_create": (_i, [C.POINTER(_vp), _i, _i, _i]),
 	"rk_egvm_destroy": (_i, [_vp]),
 	"rk_egvm_net_in": (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_sz)]),

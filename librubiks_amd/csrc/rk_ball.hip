@@ -365,32 +365,12 @@ __global__ void k_bsearch_walk(FrontierDev d, BallView b, int32_t *out, int max_
 // ---- the batch: S searches in lock-step, slot blockIdx.y of `devs` per workgroup row (rk_astar.hip: kb_merge_pass) ----
 // Every slot is a whole search of its own -- pool, table, counters, batch scratch, look-back words, ticket and epoch --, so a
 // launch reads and writes through devs[blockIdx.y] alone.  A slot that is done, or was never started, has F_NPOP == 0: it leaves
-// at that read, draws no ticket and leaves its epoch alone.  The pool of a slot never grows: a slot whose next iteration might
-// not fit (size + 12 P > capacity) stops BEFORE that iteration with BS_STOP_FULL, so fr_pops() of a slot with P > 0 is P and
-// the single engine's F_ERR_CAPACITY path is never taken.
-enum { BS_STOP_FULL = 5 };
+// at that read, draws no ticket and leaves its epoch alone.  The pool of a slot never grows: the pool-full rule (srch_fit,
+// BS_STOP_FULL) and the clearing of a slot (srch_clear) are rk_frontier_dev.h's, shared with rk_sym.hip's rk_ssearchb_*.
 
-// after the root or the end of an iteration of a slot: does the next iteration fit the pool whatever it finds?  One thread.
-__device__ __forceinline__ void srch_fit(const FrontierDev &d)
-{
-	const int P = d.ctr[F_NPOP];
-	if (P == 0 || (uint64_t)d.ctr[F_SIZE] + 12ull * (uint64_t)P <= (uint64_t)d.cap1 - 1u) return;
-	d.ctr[F_STOP] = BS_STOP_FULL; d.ctr[F_DONE] = 1; d.ctr[F_NPOP] = 0;
-}
-
-// the named slots' tables and look-back words, zeroed: slot slots[blockIdx.y], 16 bytes per thread and step (a table is a power of
-// two >= 1024 dwords, every slice 16-byte aligned)
+// the named slots' tables and look-back words, zeroed: slot slots[blockIdx.y]
 __global__ __launch_bounds__(256)
-void kb_bsearch_clear(const FrontierDev *devs, const int32_t *slots, int chain_words)
-{
-	const FrontierDev d = devs[slots[blockIdx.y]];
-	u32x4 *t4 = reinterpret_cast<u32x4 *>(d.table);
-	const size_t n4 = ((size_t)d.mask + 1) / 4;
-	const u32x4 zero = {0u, 0u, 0u, 0u};
-	for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) t4[i] = zero;
-	if (blockIdx.x == 0)
-		for (int i = threadIdx.x; i < chain_words; i += 256) d.chain[i] = 0ull;
-}
+void kb_bsearch_clear(const FrontierDev *devs, const int32_t *slots, int chain_words) { srch_clear(devs[slots[blockIdx.y]], chain_words); }
 
 // row j of roots / budgets starts slot slots[j]
 __global__ void kb_bsearch_root(const FrontierDev *devs, BallView b, const int32_t *slots, const uint32_t *roots, const int32_t *budgets)
@@ -456,26 +436,12 @@ struct rk_bsearch : FrontierPool {
 	rk_ball *ball = nullptr;
 };
 
-// S searches in lock-step: one block of every kind of array, sliced per slot; devs[s] on the device describes slot s
-struct rk_bsearchb {
+// S searches in lock-step: the slots (rk_search_host.h: FrontierSlots) and the ball they all read
+struct rk_bsearchb : FrontierSlots {
 	rk_ball *ball = nullptr;
-	int n_slots = 0, pops = 0;
-	size_t cap = 0;                             // per slot
-	uint32_t mask = 0;
-	FrontierDev d{};                                // slot 0: the blocks' base addresses
-	FrontierDev *devs = nullptr;
-	int32_t *slots_dev = nullptr, *budgets_dev = nullptr;
-	uint32_t *roots_dev = nullptr;
-	int32_t *walk = nullptr;
-	int walk_len = 0;                           // `walk` holds n_slots rows of 1 + walk_len words
-	std::vector<int32_t> ctr_spare;
-	Landing ctr_host;
-	DevPool pool{64};
 };
 
 namespace {
-
-constexpr int BSB_MAX_SLOTS = 1024;
 
 size_t ball_capacity(int radius)
 {
@@ -657,39 +623,9 @@ int rk_bsearch_export(rk_bsearch_t *h, size_t first, size_t count, int8_t *h_sta
 
 int rk_bsearchb_create(rk_bsearchb_t **out, rk_ball_t *ball, int n_slots, size_t capacity_per_slot, int pops)
 {
-	if (!out || !ball) return fail(RK_EINVAL, "rk_bsearchb_create: null argument");
-	if (n_slots < 1 || n_slots > BSB_MAX_SLOTS) return fail(RK_EINVAL, "rk_bsearchb_create: n_slots %d outside 1..%d", n_slots, BSB_MAX_SLOTS);
-	if (capacity_per_slot < 2 || capacity_per_slot > FRONTIER_MAX_CAPACITY) return fail(RK_EINVAL, "rk_bsearchb_create: capacity %zu out of range", capacity_per_slot);
-	if (pops < 1 || pops > (1 << 22)) return fail(RK_EINVAL, "rk_bsearchb_create: pops %d outside 1..%d", pops, 1 << 22);
+	if (int e = FrontierSlots::check_create("rk_bsearchb_create", out, ball, n_slots, capacity_per_slot, pops)) return e;
 	rk_bsearchb *h = new rk_bsearchb();
-	h->n_slots = n_slots; h->pops = pops; h->cap = capacity_per_slot;
-	h->mask = FrontierPool::table_mask(capacity_per_slot);
-	const size_t S = (size_t)n_slots, C1 = capacity_per_slot + 1, T = (size_t)h->mask + 1, K = (size_t)12 * pops, W = frontier_scan_blocks(pops);
-	FrontierDev &d = h->d;
-	d.pops = pops;
-	d.cap1 = (uint32_t)C1;
-	d.mask = h->mask;
-	int e = RK_OK;
-	#define A(ptr, cnt) if (!e) e = h->pool.alloc(&d.ptr, S * (cnt))
-	A(states, C1 * 5); A(parent, C1); A(pact, C1); A(table, T); A(ctr, S_COUNT);
-	A(slot, K); A(rank, K); A(first, K); A(chain, W);
-	#undef A
-	if (!e) e = h->pool.alloc(&h->devs, S);
-	if (!e) e = h->pool.alloc(&h->slots_dev, S);
-	if (!e) e = h->pool.alloc(&h->budgets_dev, S);
-	if (!e) e = h->pool.alloc(&h->roots_dev, S * 5);
-	if (e) { (void)hipGetLastError(); delete h; return fail(RK_ECAPACITY, "rk_bsearchb_create: no device memory for %d pools of %zu states", n_slots, capacity_per_slot); }
-	std::vector<FrontierDev> devs(S, d);
-	for (size_t s = 0; s < S; s++) {
-		FrontierDev &x = devs[s];
-		x.states += s * C1 * 5; x.parent += s * C1; x.pact += s * C1; x.table += s * T; x.ctr += s * S_COUNT;
-		x.slot += s * K; x.rank += s * K; x.first += s * K; x.chain += s * W;
-	}
-	hipError_t he = hipMemcpy(h->devs, devs.data(), S * sizeof(FrontierDev), hipMemcpyHostToDevice);
-	if (he == hipSuccess) he = hipMemset(d.ctr, 0, S * S_COUNT * sizeof(int32_t));      // never started: F_NPOP == 0, every launch passes it by
-	if (he != hipSuccess) { delete h; return fail(RK_EHIP, "rk_bsearchb_create: %s", hipGetErrorString(he)); }
-	h->ctr_host.reserve(S * S_COUNT);
-	h->ctr_spare.resize(S * S_COUNT);
+	if (int e = h->alloc("rk_bsearchb_create", n_slots, capacity_per_slot, pops, [] { return RK_OK; })) { delete h; return e; }
 	h->ball = ball;
 	ball->attached += 1;
 	*out = h;
@@ -706,35 +642,16 @@ int rk_bsearchb_destroy(rk_bsearchb_t *h)
 int rk_bsearchb_reset(rk_bsearchb_t *h, int n, const int32_t *slots, const int8_t *h_start_states, const long long *max_states, void *stream)
 {
 	if (!h) return fail(RK_EINVAL, "rk_bsearchb_reset: null engine");
-	if (!h->ball->built) return fail(RK_ESTATE, "rk_bsearchb_reset: build the ball first");
-	if (n < 0 || n > h->n_slots) return fail(RK_EINVAL, "rk_bsearchb_reset: %d slots of %d", n, h->n_slots);
-	if (n == 0) return RK_OK;
-	if (!slots || !h_start_states || !max_states) return fail(RK_EINVAL, "rk_bsearchb_reset: null argument");
-	std::vector<char> named((size_t)h->n_slots, 0);
-	std::vector<int32_t> budgets((size_t)n);
-	for (int j = 0; j < n; j++) {
-		if (slots[j] < 0 || slots[j] >= h->n_slots) return fail(RK_EINVAL, "rk_bsearchb_reset: slot %d outside 0..%d", slots[j], h->n_slots - 1);
-		if (named[slots[j]]) return fail(RK_EINVAL, "rk_bsearchb_reset: slot %d is named twice", slots[j]);
-		named[slots[j]] = 1;
-		budgets[j] = budget_of(max_states[j]);
-	}
 	hipStream_t st = (hipStream_t)stream;
-	RK_HIP(hipMemcpyAsync(h->slots_dev, slots, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
-	RK_HIP(hipMemcpyAsync(h->budgets_dev, budgets.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
-	RK_HIP(hipMemcpyAsync(h->roots_dev, h_start_states, (size_t)n * STATE_BYTES, hipMemcpyHostToDevice, st));
-	const unsigned gx = std::min<unsigned>(blocks(((size_t)h->mask + 1) / 4), 1024u);
-	hipLaunchKernelGGL(kb_bsearch_clear, dim3(gx, n), dim3(256), 0, st, h->devs, h->slots_dev, (int)frontier_scan_blocks(h->pops));   // the named slots' own tables only
-	hipLaunchKernelGGL(kb_bsearch_root, dim3(1, n), dim3(64), 0, st, h->devs, h->ball->view, h->slots_dev, h->roots_dev, h->budgets_dev);
-	RK_HIP(hipGetLastError());
-	RK_HIP(hipStreamSynchronize(st));       // the host buffers may go away after return
-	return RK_OK;
+	return h->reset("rk_bsearchb_reset", h->ball->built, n, slots, h_start_states, max_states, st, kb_bsearch_clear, [&] {
+		hipLaunchKernelGGL(kb_bsearch_root, dim3(1, n), dim3(64), 0, st, h->devs, h->ball->view, h->slots_dev, h->roots_dev, h->budgets_dev);
+	});
 }
 
 int rk_bsearchb_run(rk_bsearchb_t *h, int iterations, void *stream)
 {
 	if (!h) return fail(RK_EINVAL, "rk_bsearchb_run: null engine");
-	if (!h->ball->built) return fail(RK_ESTATE, "rk_bsearchb_run: build the ball first");
-	if (iterations < 0) return fail(RK_EINVAL, "rk_bsearchb_run: iterations %d < 0", iterations);
+	if (int e = h->check_run("rk_bsearchb_run", h->ball->built, iterations)) return e;
 	hipStream_t st = (hipStream_t)stream;
 	const BallView &b = h->ball->view;
 	const size_t K = (size_t)12 * h->pops;
@@ -752,41 +669,22 @@ int rk_bsearchb_run(rk_bsearchb_t *h, int iterations, void *stream)
 int rk_bsearchb_status(rk_bsearchb_t *h, long long *h_status, void *stream)
 {
 	if (!h || !h_status) return fail(RK_EINVAL, "rk_bsearchb_status: null argument");
-	const int32_t *c = nullptr;
-	if (int e = h->ctr_host.fetch(h->d.ctr, (size_t)h->n_slots * S_COUNT, h->ctr_spare.data(), (hipStream_t)stream, &c)) return e;
-	for (int s = 0; s < h->n_slots; s++, c += S_COUNT)
-		bsearch_status_words(c, h_status + (size_t)s * 10);
-	return RK_OK;
+	return h->status(h_status, (hipStream_t)stream);
 }
 
 int rk_bsearchb_paths(rk_bsearchb_t *h, int32_t *h_out, int max_len, void *stream)
 {
 	if (!h || !h_out) return fail(RK_EINVAL, "rk_bsearchb_paths: null argument");
-	if (!h->ball->built) return fail(RK_ESTATE, "rk_bsearchb_paths: build the ball first");
-	if (max_len < 0 || max_len > FRONTIER_WALK_MAX) return fail(RK_EINVAL, "rk_bsearchb_paths: max_len %d outside 0..%d", max_len, FRONTIER_WALK_MAX);
 	hipStream_t st = (hipStream_t)stream;
-	const size_t words = (size_t)h->n_slots * (size_t)(1 + max_len);
-	if (h->walk == nullptr || h->walk_len < max_len) {
-		RK_HIP(hipStreamSynchronize(st));
-		if (h->walk != nullptr) { h->pool.release(h->walk); h->walk = nullptr; }
-		if (h->pool.alloc(&h->walk, words) != RK_OK) { (void)hipGetLastError(); return fail(RK_ECAPACITY, "rk_bsearchb_paths: no device memory for %zu words", words); }
-		h->walk_len = max_len;
-	}
-	hipLaunchKernelGGL(kb_bsearch_walk, dim3(blocks((size_t)h->n_slots, 64)), dim3(64), 0, st, h->devs, h->ball->view, h->n_slots, h->walk, max_len);
-	RK_HIP(hipGetLastError());
-	RK_HIP(hipMemcpyAsync(h_out, h->walk, words * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-	RK_HIP(hipStreamSynchronize(st));
-	return RK_OK;
+	return h->paths("rk_bsearchb_paths", h->ball->built, h_out, max_len, st, [&] {
+		hipLaunchKernelGGL(kb_bsearch_walk, dim3(blocks((size_t)h->n_slots, 64)), dim3(64), 0, st, h->devs, h->ball->view, h->n_slots, h->walk, max_len);
+	});
 }
 
 int rk_bsearchb_export(rk_bsearchb_t *h, int slot, size_t first, size_t count, int8_t *h_states, long long *h_parents, long long *h_actions, void *stream)
 {
 	if (!h) return fail(RK_EINVAL, "rk_bsearchb_export: null engine");
-	if (slot < 0 || slot >= h->n_slots) return fail(RK_EINVAL, "rk_bsearchb_export: slot %d outside 0..%d", slot, h->n_slots - 1);
-	if (first + count > h->cap + 1) return fail(RK_EINVAL, "rk_bsearchb_export: rows %zu..%zu outside the pool", first, first + count);
-	const size_t at = (size_t)slot * (h->cap + 1);
-	return export_pool_rows(h->d.states + at * 5, h->d.parent + at, h->d.pact + at, first, count, h_states, h_parents, h_actions, nullptr,
-	                        (hipStream_t)stream);
+	return h->export_rows("rk_bsearchb_export", slot, first, count, h_states, h_parents, h_actions, (hipStream_t)stream);
 }
 
 long long rk_bsearch_path(rk_bsearch_t *h, long long *h_actions, size_t max_len, void *stream)

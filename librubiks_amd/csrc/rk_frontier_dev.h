@@ -1,10 +1,10 @@
 // The frontier pool: what every breadth-first engine that keeps its whole search in HBM shares on the device -- rk_bfs.hip,
 // rk_bibfs.hip, rk_ball.hip's search from a start (rk_bsearch_*) and its batch (rk_bsearchb_*), and rk_sym.hip's search that ends
-// at the symmetry-reduced ball (rk_ssearch_*).  One descriptor, the common counter words, and the launches of an iteration that
-// do not look at what the engine searches for: the scan, the append, the end of an iteration with the cut, and the rehash after
-// a growth.  An engine keeps what makes it different: its counter words behind F_COMMON, its `next` (what follows a pop count
+// at the symmetry-reduced ball (rk_ssearch_*) and its batch (rk_ssearchb_*).  One descriptor, the common counter words, and the
+// launches of an iteration that do not look at what the engine searches for: the scan, the append, the end of an iteration with
+// the cut, and the rehash after a growth.  An engine keeps what makes it different: its counter words behind F_COMMON, its `next` (what follows a pop count
 // change: the end of a level, the done flags, the next P), its root, its expand launch -- the membership rule -- and its walk.
-// The host side is FrontierPool (rk_search_host.h).
+// The host side is FrontierPool (rk_search_host.h), and FrontierSlots for the two batches.
 //
 // An iteration pops the P = F_NPOP nodes head .. head + P - 1 and is expand, scan, append, end; none synchronises with the host.
 // Pop j of the batch runs only if size_before + (new states of the pops before j) < budget, and the winning child is the lowest
@@ -161,6 +161,31 @@ __device__ __forceinline__ void srch_next(const FrontierDev &d)
 }
 
 __device__ __forceinline__ void bsearch_end(const FrontierDev &d) { fr_end<S_MEET, S_POPPED>(d, [](const FrontierDev &x) { srch_next(x); }); }
+
+// ---- such searches in lock-step (rk_bsearchb_*, rk_ssearchb_*): a slot's pool never grows ----
+// A slot whose next iteration might not fit (size + 12 P > capacity) stops BEFORE that iteration with BS_STOP_FULL, so fr_pops()
+// of a slot with P > 0 is P and the single engine's F_ERR_CAPACITY path is never taken.
+enum { BS_STOP_FULL = 5 };
+
+// after the root or the end of an iteration of a slot: does the next iteration fit the pool whatever it finds?  One thread.
+__device__ __forceinline__ void srch_fit(const FrontierDev &d)
+{
+	const int P = d.ctr[F_NPOP];
+	if (P == 0 || (uint64_t)d.ctr[F_SIZE] + 12ull * (uint64_t)P <= (uint64_t)d.cap1 - 1u) return;
+	d.ctr[F_STOP] = BS_STOP_FULL; d.ctr[F_DONE] = 1; d.ctr[F_NPOP] = 0;
+}
+
+// the table and the look-back words of one slot, zeroed by the workgroups (blockIdx.x, gridDim.x) of 256: 16 bytes per thread and
+// step (a table is a power of two >= 1024 dwords, every slice 16-byte aligned)
+__device__ __forceinline__ void srch_clear(const FrontierDev &d, int chain_words)
+{
+	u32x4 *t4 = reinterpret_cast<u32x4 *>(d.table);
+	const size_t n4 = ((size_t)d.mask + 1) / 4;
+	const u32x4 zero = {0u, 0u, 0u, 0u};
+	for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) t4[i] = zero;
+	if (blockIdx.x == 0)
+		for (int i = threadIdx.x; i < chain_words; i += 256) d.chain[i] = 0ull;
+}
 
 constexpr int FRONTIER_WALK_MAX = 1 << 12;
 

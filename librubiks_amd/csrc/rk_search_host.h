@@ -1,8 +1,8 @@
 // Host-side pieces shared by the search engines (A* single / sharded / batched, breadth-first search, MCTS): who owns a device
 // allocation, growing arrays in place as one transaction, the small read-backs every engine needs, FrontierPool, the host
-// half of the breadth-first engines' pool (rk_frontier_dev.h), and KeptBall, the host half of the two ball builds
-// (rk_ballbuild_dev.h).  The counterpart of rk_search_dev.h; header-only, nothing in
-// here is exported.
+// half of the breadth-first engines' pool (rk_frontier_dev.h), FrontierSlots, the host half of the two lock-step batches of such
+// searches, and KeptBall, the host half of the two ball builds (rk_ballbuild_dev.h).  The counterpart of rk_search_dev.h;
+// header-only, nothing in here is exported.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -486,6 +486,149 @@ inline void bsearch_status_words(const int32_t *c, long long *o)
 	o[0] = c[F_DONE]; o[1] = c[F_WON]; o[2] = c[F_SIZE]; o[3] = c[F_ITERS]; o[4] = c[S_POPPED]; o[5] = c[F_STOP]; o[6] = c[F_ERROR];
 	o[7] = c[F_NPOP]; o[8] = c[S_DEPTH]; o[9] = c[S_MEET];
 }
+
+// The host half of S searches in lock-step (rk_bsearchb, rk_ssearchb), as FrontierPool is of one: a block of every kind of array,
+// sliced per slot, and devs[s] on the device describes slot s.  An engine's handle is this plus its ball and its own blocks; its
+// entries pass their own name as `who`, the prefix of every error text, and their kernels.
+constexpr int FRONTIER_MAX_SLOTS = 1024;
+
+struct FrontierSlots {
+	using Clear = void (*)(const FrontierDev *, const int32_t *, int);
+
+	int n_slots = 0, pops = 0;
+	size_t cap = 0;                             // per slot
+	uint32_t mask = 0;
+	FrontierDev d{};                            // slot 0: the blocks' base addresses
+	FrontierDev *devs = nullptr;
+	int32_t *slots_dev = nullptr, *budgets_dev = nullptr;
+	uint32_t *roots_dev = nullptr;
+	int32_t *walk = nullptr;
+	int walk_len = 0;                           // `walk` holds n_slots rows of 1 + walk_len words
+	std::vector<int32_t> ctr_spare;
+	Landing ctr_host;
+	DevPool pool{64};
+
+	// the null and range checks of a *_create
+	static int check_create(const char *who, const void *out, const void *ball, int n_slots, size_t capacity_per_slot, int pops)
+	{
+		if (!out || !ball) return fail(RK_EINVAL, "%s: null argument", who);
+		if (n_slots < 1 || n_slots > FRONTIER_MAX_SLOTS) return fail(RK_EINVAL, "%s: n_slots %d outside 1..%d", who, n_slots, FRONTIER_MAX_SLOTS);
+		if (capacity_per_slot < 2 || capacity_per_slot > FRONTIER_MAX_CAPACITY) return fail(RK_EINVAL, "%s: capacity %zu out of range", who, capacity_per_slot);
+		if (pops < 1 || pops > FRONTIER_MAX_POPS) return fail(RK_EINVAL, "%s: pops %d outside 1..%d", who, pops, FRONTIER_MAX_POPS);
+		return RK_OK;
+	}
+
+	// every block (the engine's own through alloc_own), the table of descriptors, and counters that say "never started": F_NPOP == 0,
+	// every launch passes such a slot by
+	template <typename Own>
+	int alloc(const char *who, int slots, size_t capacity_per_slot, int pops_, Own &&alloc_own)
+	{
+		n_slots = slots; pops = pops_; cap = capacity_per_slot;
+		mask = FrontierPool::table_mask(capacity_per_slot);
+		const size_t S = (size_t)n_slots, C1 = capacity_per_slot + 1, T = (size_t)mask + 1, K = (size_t)12 * pops, W = frontier_scan_blocks(pops);
+		d.pops = pops;
+		d.cap1 = (uint32_t)C1;
+		d.mask = mask;
+		int e = RK_OK;
+		#define A(ptr, cnt) if (!e) e = pool.alloc(&d.ptr, S * (cnt))
+		A(states, C1 * 5); A(parent, C1); A(pact, C1); A(table, T); A(ctr, S_COUNT);
+		A(slot, K); A(rank, K); A(first, K); A(chain, W);
+		#undef A
+		if (!e) e = pool.alloc(&devs, S);
+		if (!e) e = pool.alloc(&slots_dev, S);
+		if (!e) e = pool.alloc(&budgets_dev, S);
+		if (!e) e = pool.alloc(&roots_dev, S * 5);
+		if (!e) e = alloc_own();
+		if (e) { (void)hipGetLastError(); return fail(RK_ECAPACITY, "%s: no device memory for %d pools of %zu states", who, n_slots, capacity_per_slot); }
+		std::vector<FrontierDev> table(S, d);
+		for (size_t s = 0; s < S; s++) {
+			FrontierDev &x = table[s];
+			x.states += s * C1 * 5; x.parent += s * C1; x.pact += s * C1; x.table += s * T; x.ctr += s * S_COUNT;
+			x.slot += s * K; x.rank += s * K; x.first += s * K; x.chain += s * W;
+		}
+		hipError_t he = hipMemcpy(devs, table.data(), S * sizeof(FrontierDev), hipMemcpyHostToDevice);
+		if (he == hipSuccess) he = hipMemset(d.ctr, 0, S * S_COUNT * sizeof(int32_t));
+		if (he != hipSuccess) return fail(RK_EHIP, "%s: %s", who, hipGetErrorString(he));
+		ctr_host.reserve(S * S_COUNT);
+		ctr_spare.resize(S * S_COUNT);
+		return RK_OK;
+	}
+
+	// slot slots[j] starts again from host state j: the checks, the uploads, the named slots' own tables and look-back words
+	// cleared, then the engine's root launch over the n named slots
+	template <typename Root>
+	int reset(const char *who, bool ball_built, int n, const int32_t *slots, const int8_t *h_start_states, const long long *max_states, hipStream_t st,
+	          Clear clear, Root &&launch_root)
+	{
+		if (!ball_built) return fail(RK_ESTATE, "%s: build the ball first", who);
+		if (n < 0 || n > n_slots) return fail(RK_EINVAL, "%s: %d slots of %d", who, n, n_slots);
+		if (n == 0) return RK_OK;
+		if (!slots || !h_start_states || !max_states) return fail(RK_EINVAL, "%s: null argument", who);
+		std::vector<char> named((size_t)n_slots, 0);
+		std::vector<int32_t> budgets((size_t)n);
+		for (int j = 0; j < n; j++) {
+			if (slots[j] < 0 || slots[j] >= n_slots) return fail(RK_EINVAL, "%s: slot %d outside 0..%d", who, slots[j], n_slots - 1);
+			if (named[slots[j]]) return fail(RK_EINVAL, "%s: slot %d is named twice", who, slots[j]);
+			named[slots[j]] = 1;
+			budgets[j] = budget_of(max_states[j]);
+		}
+		RK_HIP(hipMemcpyAsync(slots_dev, slots, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+		RK_HIP(hipMemcpyAsync(budgets_dev, budgets.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+		RK_HIP(hipMemcpyAsync(roots_dev, h_start_states, (size_t)n * STATE_BYTES, hipMemcpyHostToDevice, st));
+		const unsigned gx = std::min<unsigned>(blocks(((size_t)mask + 1) / 4), 1024u);
+		hipLaunchKernelGGL(clear, dim3(gx, n), dim3(256), 0, st, devs, slots_dev, (int)frontier_scan_blocks(pops));   // the named slots' own tables only
+		launch_root();
+		RK_HIP(hipGetLastError());
+		RK_HIP(hipStreamSynchronize(st));       // the host buffers may go away after return
+		return RK_OK;
+	}
+
+	// the checks of a *_run
+	int check_run(const char *who, bool ball_built, int iterations) const
+	{
+		if (!ball_built) return fail(RK_ESTATE, "%s: build the ball first", who);
+		if (iterations < 0) return fail(RK_EINVAL, "%s: iterations %d < 0", who, iterations);
+		return RK_OK;
+	}
+
+	// bsearch_status_words of every slot, the counters read with one copy
+	int status(long long *h_status, hipStream_t st)
+	{
+		const int32_t *c = nullptr;
+		if (int e = ctr_host.fetch(d.ctr, (size_t)n_slots * S_COUNT, ctr_spare.data(), st, &c)) return e;
+		for (int s = 0; s < n_slots; s++, c += S_COUNT)
+			bsearch_status_words(c, h_status + (size_t)s * 10);
+		return RK_OK;
+	}
+
+	// the engine's walk launch into rows of 1 + max_len words, one per slot, then one copy to h_out
+	template <typename Walk>
+	int paths(const char *who, bool ball_built, int32_t *h_out, int max_len, hipStream_t st, Walk &&launch_walk)
+	{
+		if (!ball_built) return fail(RK_ESTATE, "%s: build the ball first", who);
+		if (max_len < 0 || max_len > FRONTIER_WALK_MAX) return fail(RK_EINVAL, "%s: max_len %d outside 0..%d", who, max_len, FRONTIER_WALK_MAX);
+		const size_t words = (size_t)n_slots * (size_t)(1 + max_len);
+		if (walk == nullptr || walk_len < max_len) {
+			RK_HIP(hipStreamSynchronize(st));
+			if (walk != nullptr) { pool.release(walk); walk = nullptr; }
+			if (pool.alloc(&walk, words) != RK_OK) { (void)hipGetLastError(); return fail(RK_ECAPACITY, "%s: no device memory for %zu words", who, words); }
+			walk_len = max_len;
+		}
+		launch_walk();
+		RK_HIP(hipGetLastError());
+		RK_HIP(hipMemcpyAsync(h_out, walk, words * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+		RK_HIP(hipStreamSynchronize(st));
+		return RK_OK;
+	}
+
+	int export_rows(const char *who, int slot, size_t first, size_t count, int8_t *h_states, long long *h_parents, long long *h_actions, hipStream_t st)
+	{
+		if (slot < 0 || slot >= n_slots) return fail(RK_EINVAL, "%s: slot %d outside 0..%d", who, slot, n_slots - 1);
+		if (first + count > cap + 1) return fail(RK_EINVAL, "%s: rows %zu..%zu outside the pool", who, first, first + count);
+		const size_t at = (size_t)slot * (cap + 1);
+		return export_pool_rows(d.states + at * 5, d.parent + at, d.pact + at, first, count, h_states, h_parents, h_actions, nullptr, st);
+	}
+};
 
 }  // namespace
 }  // namespace rk

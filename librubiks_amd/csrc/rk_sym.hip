@@ -42,6 +42,21 @@
 //   k_ss_scan, k_ss_append, k_ss_end   fr_scan, fr_append, bsearch_end; S_MEET is the node in THIS ball
 //   k_ss_walk     one wave: the own path and the meeting action, then the descent from the meeting state (sb_descend)
 //
+// The batch (rk_ssearchb_*) is S such searches in lock-step, as rk_ball.hip's rk_bsearchb_* is of rk_bsearch_*.  The bodies of the root,
+// the probe, the expand and the walk are __device__ functions of a FrontierDev (ssearch_*); the single engine's kernels pass theirs
+// by value, the batch's (kb_ss_*) pick devs[blockIdx.y], so an iteration of all slots is the same five launches with S in the
+// grid's second dimension.  Every kind of array is one block sliced per slot -- pool, parents, actions, table, counters, batch
+// scratch, look-back words and 12 P words of `hit` --; all slots read one ball.
+//   kb_ss_probe   grid (k_ss_probe's x, S): a workgroup whose first child is past 12 * F_NPOP of its slot -- done, never started, a
+//                 short batch -- returns BEFORE it stages the tables; writes nothing but the slot's hit
+//   kb_ss_expand, kb_ss_scan, kb_ss_append, kb_ss_end   ssearch_expand, fr_scan, fr_append, bsearch_end behind kb_bsearch_*'s early
+//                 exits (a slot with F_NPOP == 0 draws no ticket and leaves its epoch alone); srch_fit follows the end
+//   kb_ss_root    one wave per named slot, then srch_fit; kb_ss_clear zeroes the named slots' tables and look-back words first
+//   kb_ss_walk    one wave per slot (the descent needs lane = symmetry) into row s of (S, 1 + max_len)
+// A slot's pool is fixed: it stops with reason 5 before an iteration that might not fit (rk_frontier_dev.h: srch_fit).  The host
+// side -- the slot block, the reset's checks, the status fetch, the paths buffer, the export -- is FrontierSlots (rk_search_host.h),
+// shared with rk_bsearchb; this engine adds the hit block.
+//
 // Shortening (rk_sshorten) is rk_ball.hip's rk_bshorten -- the same contract, scratch, DP and copy rule (rk_shorten_dev.h) -- with
 // d(i, j) = the depth of the REPRESENTATIVE of X(i, j), which is the plain ball's d(i, j) at the same radius, so the lengths are
 // rk_bshorten's queue for queue.  There is no stored word for a replaced edge: it gets the inverse of the descent from X(i, j),
@@ -319,9 +334,9 @@ void k_ss_emit(SymBallView b, const int8_t *__restrict__ actions, const int32_t 
 }
 
 // ---- the search from a start towards the symmetry ball ----------------------------------------------------------------------
+// (the bodies: what one search does in a launch, for the single engine (k_ss_*) and for one slot of a batch (kb_ss_*))
 // One wave: node 1 = the start, whose representative is looked up in the ball (bsearch_root with that one difference).
-__global__ __launch_bounds__(64)
-void k_ss_root(FrontierDev d, SymBallView b, const uint32_t *root, int budget)
+__device__ __forceinline__ void ssearch_root(const FrontierDev &d, const SymBallView &b, const uint32_t *root, int budget)
 {
 	__shared__ uint32_t s_sym[SYM_LDS_DWORDS];
 	const int lane = threadIdx.x;
@@ -352,8 +367,7 @@ void k_ss_root(FrontierDev d, SymBallView b, const uint32_t *root, int budget)
 
 // hit[c] = the ball's node of the representative of child c of the batch, 0 when the ball does not hold it: waves stride over
 // the children (k_sb_canon's grid), nothing but hit is written
-__global__ __launch_bounds__(256)
-void k_ss_probe(FrontierDev d, SymBallView b, uint32_t *hit)
+__device__ __forceinline__ void ssearch_probe(const FrontierDev &d, const SymBallView &b, uint32_t *hit)
 {
 	__shared__ uint32_t s_sym[SYM_LDS_DWORDS];
 	__shared__ u32x4 s_act[36];
@@ -377,8 +391,7 @@ void k_ss_probe(FrontierDev d, SymBallView b, uint32_t *hit)
 }
 
 // a meeting child leaves no claim; any other: membership / election in the own table on the raw child (bsearch_expand)
-__global__ __launch_bounds__(256)
-void k_ss_expand(FrontierDev d, const uint32_t *hit)
+__device__ __forceinline__ void ssearch_expand(const FrontierDev &d, const uint32_t *hit)
 {
 	__shared__ u32x4 s_act[36];
 	stage_action_tables(s_act, threadIdx.x);
@@ -402,23 +415,11 @@ void k_ss_expand(FrontierDev d, const uint32_t *hit)
 	d.slot[c] = e == 0u ? slot : NO_SLOT;
 }
 
-__global__ __launch_bounds__(ASCAN)
-void k_ss_scan(FrontierDev d) { fr_scan(d); }
-
-__global__ __launch_bounds__(256)
-void k_ss_append(FrontierDev d) { fr_append(d); }
-
-__global__ void k_ss_end(FrontierDev d) { if (threadIdx.x == 0 && blockIdx.x == 0) bsearch_end(d); }
-
-__global__ __launch_bounds__(256)
-void k_ss_rehash(FrontierDev d) { fr_rehash(d); }
-
 // The action queue of a won search, one wave: the path from the start to the popped parent and the meeting action (none of either
 // when the ball holds the start's orbit), then the descent from the meeting state.  out[0] = length, -1 when the search has not
 // met or a parent chain is broken, -2 when the meeting state is not where S_MEET says or the descent finds no way on.  Every lane
 // computes the same; lane 0 writes.
-__global__ __launch_bounds__(64)
-void k_ss_walk(FrontierDev d, SymBallView b, int32_t *out, int max_len)
+__device__ __forceinline__ void ssearch_walk(const FrontierDev &d, const SymBallView &b, int32_t *out, int max_len)
 {
 	__shared__ uint32_t s_sym[SYM_LDS_DWORDS];
 	__shared__ u32x4 s_act[36];
@@ -460,6 +461,99 @@ void k_ss_walk(FrontierDev d, SymBallView b, int32_t *out, int max_len)
 	if (ok) len = own + sb_descend(b, s_sym, s_act, L, lane, x, level_of(b.lstart, g),
 	                               [&](int k, int a) { if (own + k < max_len && lane == 0) out[1 + own + k] = a; }, &ok);
 	if (lane == 0) out[0] = ok ? len : -2;
+}
+
+// ---- the single engine: one search per launch ----
+__global__ __launch_bounds__(64)
+void k_ss_root(FrontierDev d, SymBallView b, const uint32_t *root, int budget) { ssearch_root(d, b, root, budget); }
+
+__global__ __launch_bounds__(256)
+void k_ss_probe(FrontierDev d, SymBallView b, uint32_t *hit) { ssearch_probe(d, b, hit); }
+
+__global__ __launch_bounds__(256)
+void k_ss_expand(FrontierDev d, const uint32_t *hit) { ssearch_expand(d, hit); }
+
+__global__ __launch_bounds__(ASCAN)
+void k_ss_scan(FrontierDev d) { fr_scan(d); }
+
+__global__ __launch_bounds__(256)
+void k_ss_append(FrontierDev d) { fr_append(d); }
+
+__global__ void k_ss_end(FrontierDev d) { if (threadIdx.x == 0 && blockIdx.x == 0) bsearch_end(d); }
+
+__global__ __launch_bounds__(256)
+void k_ss_rehash(FrontierDev d) { fr_rehash(d); }
+
+__global__ __launch_bounds__(64)
+void k_ss_walk(FrontierDev d, SymBallView b, int32_t *out, int max_len) { ssearch_walk(d, b, out, max_len); }
+
+// ---- the batch: S searches in lock-step, slot blockIdx.y of `devs` per workgroup row (rk_ball.hip: kb_bsearch_*) ----
+// Every slot is a whole search of its own -- pool, table, counters, batch scratch, look-back words, ticket, epoch and the 12 P
+// words of `hit` --, so a launch reads and writes through devs[blockIdx.y] and that slot's slice of `hits` alone; the ball is read
+// by all.  A slot that is done, or was never started, has F_NPOP == 0: it leaves at that read, draws no ticket and leaves its
+// epoch alone.  The pool-full rule is the plain batch's (rk_frontier_dev.h: srch_fit), so fr_pops() of a slot with P > 0 is P.
+
+// the named slots' tables and look-back words, zeroed: slot slots[blockIdx.y]
+__global__ __launch_bounds__(256)
+void kb_ss_clear(const FrontierDev *devs, const int32_t *slots, int chain_words) { srch_clear(devs[slots[blockIdx.y]], chain_words); }
+
+// row j of roots / budgets starts slot slots[j]: one wave per named slot
+__global__ __launch_bounds__(64)
+void kb_ss_root(const FrontierDev *devs, SymBallView b, const int32_t *slots, const uint32_t *roots, const int32_t *budgets)
+{
+	const FrontierDev d = devs[slots[blockIdx.y]];
+	ssearch_root(d, b, roots + (size_t)blockIdx.y * 5, budgets[blockIdx.y]);
+	if (threadIdx.x == 0) srch_fit(d);                                   // (the thread that wrote the counters)
+}
+
+// slot blockIdx.y's children, its waves striding over them; a workgroup whose first child is past the slot's batch -- a slot that
+// is done, never started, or has a short batch -- returns before the tables are staged (ssearch_probe's first lines)
+__global__ __launch_bounds__(256)
+void kb_ss_probe(const FrontierDev *devs, SymBallView b, uint32_t *hits)
+{
+	const FrontierDev d = devs[blockIdx.y];
+	ssearch_probe(d, b, hits + (size_t)blockIdx.y * 12u * (size_t)d.pops);
+}
+
+__global__ __launch_bounds__(256)
+void kb_ss_expand(const FrontierDev *devs, const uint32_t *hits)
+{
+	const FrontierDev d = devs[blockIdx.y];
+	if (blockIdx.x * 256 >= 12 * d.ctr[F_NPOP]) return;                  // done, never started, or a workgroup past the batch
+	ssearch_expand(d, hits + (size_t)blockIdx.y * 12u * (size_t)d.pops);
+}
+
+__global__ __launch_bounds__(ASCAN)
+void kb_ss_scan(const FrontierDev *devs)
+{
+	const FrontierDev d = devs[blockIdx.y];
+	if (d.ctr[F_NPOP] == 0) return;                                      // (every workgroup of a live slot draws a ticket)
+	fr_scan(d);
+}
+
+__global__ __launch_bounds__(256)
+void kb_ss_append(const FrontierDev *devs)
+{
+	const FrontierDev d = devs[blockIdx.y];
+	if (blockIdx.x * 256 >= 12 * d.ctr[F_NPOP]) return;
+	fr_append(d);
+}
+
+__global__ void kb_ss_end(const FrontierDev *devs)
+{
+	if (threadIdx.x != 0 || blockIdx.x != 0) return;
+	const FrontierDev d = devs[blockIdx.y];
+	if (d.ctr[F_NPOP] == 0) return;
+	bsearch_end(d);
+	srch_fit(d);
+}
+
+// one WAVE per slot (the descent needs lane = symmetry): row s of `out` (n_slots, 1 + max_len) = length, -1 or -2, then the queue
+__global__ __launch_bounds__(64)
+void kb_ss_walk(const FrontierDev *devs, SymBallView b, int32_t *out, int max_len)
+{
+	const FrontierDev d = devs[blockIdx.x];
+	ssearch_walk(d, b, out + (size_t)blockIdx.x * (size_t)(1 + max_len), max_len);
 }
 
 __global__ __launch_bounds__(256)
@@ -509,6 +603,12 @@ struct rk_symball : KeptBall {
 
 struct rk_ssearch : FrontierPool {
 	uint32_t *hit = nullptr;                    // per child of the batch: the ball's node of its representative, or 0
+	rk_symball *ball = nullptr;
+};
+
+// S searches in lock-step: the slots (rk_search_host.h: FrontierSlots), their `hit` block and the ball they all read
+struct rk_ssearchb : FrontierSlots {
+	uint32_t *hit = nullptr;                    // (n_slots, 12 x pops): slot s's words are its own
 	rk_symball *ball = nullptr;
 };
 
@@ -780,6 +880,77 @@ long long rk_ssearch_path(rk_ssearch_t *h, long long *h_actions, size_t max_len,
 	if (len == -2) return fail(RK_ESTATE, "rk_ssearch_path: the meeting state has no way down the ball (or is not where the search met)");
 	if (len < 0) return fail(RK_ESTATE, "rk_ssearch_path: the search has not met the ball (or a parent chain is broken)");
 	return (long long)len;
+}
+
+int rk_ssearchb_create(rk_ssearchb_t **out, rk_symball_t *ball, int n_slots, size_t capacity_per_slot, int pops)
+{
+	if (int e = FrontierSlots::check_create("rk_ssearchb_create", out, ball, n_slots, capacity_per_slot, pops)) return e;
+	if (!ball->built) return fail(RK_ESTATE, "rk_ssearchb_create: build the ball first");
+	rk_ssearchb *h = new rk_ssearchb();
+	if (int e = h->alloc("rk_ssearchb_create", n_slots, capacity_per_slot, pops, [&] { return h->pool.alloc(&h->hit, (size_t)n_slots * 12 * (size_t)pops); })) {
+		delete h;
+		return e;
+	}
+	h->ball = ball;
+	ball->attached += 1;
+	*out = h;
+	return RK_OK;
+}
+
+int rk_ssearchb_destroy(rk_ssearchb_t *h)
+{
+	if (h && h->ball) h->ball->attached -= 1;
+	delete h;
+	return RK_OK;
+}
+
+int rk_ssearchb_reset(rk_ssearchb_t *h, int n, const int32_t *slots, const int8_t *h_start_states, const long long *max_states, void *stream)
+{
+	if (!h) return fail(RK_EINVAL, "rk_ssearchb_reset: null engine");
+	hipStream_t st = (hipStream_t)stream;
+	return h->reset("rk_ssearchb_reset", h->ball->built, n, slots, h_start_states, max_states, st, kb_ss_clear, [&] {
+		hipLaunchKernelGGL(kb_ss_root, dim3(1, n), dim3(64), 0, st, h->devs, h->ball->view, h->slots_dev, h->roots_dev, h->budgets_dev);
+	});
+}
+
+int rk_ssearchb_run(rk_ssearchb_t *h, int iterations, void *stream)
+{
+	if (!h) return fail(RK_EINVAL, "rk_ssearchb_run: null engine");
+	if (int e = h->check_run("rk_ssearchb_run", h->ball->built, iterations)) return e;
+	hipStream_t st = (hipStream_t)stream;
+	const SymBallView &b = h->ball->view;
+	const size_t K = (size_t)12 * h->pops;
+	const dim3 grid_probe(sym_grid(K), h->n_slots), grid(blocks(K), h->n_slots), grid_scan(blocks(K, ASCAN), h->n_slots);
+	for (int it = 0; it < iterations; it++) {
+		hipLaunchKernelGGL(kb_ss_probe, grid_probe, dim3(256), 0, st, h->devs, b, h->hit);
+		hipLaunchKernelGGL(kb_ss_expand, grid, dim3(256), 0, st, h->devs, h->hit);
+		hipLaunchKernelGGL(kb_ss_scan, grid_scan, dim3(ASCAN), 0, st, h->devs);
+		hipLaunchKernelGGL(kb_ss_append, grid, dim3(256), 0, st, h->devs);
+		hipLaunchKernelGGL(kb_ss_end, dim3(1, h->n_slots), dim3(64), 0, st, h->devs);
+	}
+	RK_HIP(hipGetLastError());
+	return RK_OK;
+}
+
+int rk_ssearchb_status(rk_ssearchb_t *h, long long *h_status, void *stream)
+{
+	if (!h || !h_status) return fail(RK_EINVAL, "rk_ssearchb_status: null argument");
+	return h->status(h_status, (hipStream_t)stream);
+}
+
+int rk_ssearchb_paths(rk_ssearchb_t *h, int32_t *h_out, int max_len, void *stream)
+{
+	if (!h || !h_out) return fail(RK_EINVAL, "rk_ssearchb_paths: null argument");
+	hipStream_t st = (hipStream_t)stream;
+	return h->paths("rk_ssearchb_paths", h->ball->built, h_out, max_len, st, [&] {
+		hipLaunchKernelGGL(kb_ss_walk, dim3(h->n_slots), dim3(64), 0, st, h->devs, h->ball->view, h->walk, max_len);
+	});
+}
+
+int rk_ssearchb_export(rk_ssearchb_t *h, int slot, size_t first, size_t count, int8_t *h_states, long long *h_parents, long long *h_actions, void *stream)
+{
+	if (!h) return fail(RK_EINVAL, "rk_ssearchb_export: null engine");
+	return h->export_rows("rk_ssearchb_export", slot, first, count, h_states, h_parents, h_actions, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -893,40 +893,22 @@ class DeviceSymBallSearch(_BallSearch):
 		return f"Breadth-first search to a symmetry-reduced goal ball (device, radius={self.ball.radius}, pops={self.pops})"
 
 
-class DeviceBallSearchBatch(_ffi.Owner):
-	"""
-	Shortest solutions of many states at once: `searches` slots, each a whole `DeviceBallSearch` of its own (pool, table,
-	counters), advanced in lock-step by the same four launches with the slot in the grid's second dimension (engine
-	rk_bsearchb_*, csrc/rk_ball.hip).  A single search is latency-bound -- four launches per iteration on a few per cent of the
-	card --; the batch pays those launches once for all slots.  Every state gets exactly what `DeviceBallSearch` gives it alone:
-	result, queue, states stored, depth, nodes popped, meeting and pool, whatever slot it ran in and whenever it was started.
-
-	`search(states)` takes any number of states.  Slots take them in input order; every `poll` iterations the host reads all
-	slots' status, records the searches that finished (their queues; their pools with `keep_arrays`) and starts the next waiting
-	states in the slots that became free, so short searches do not leave the card idle beside long ones.
-
-	The pool of a slot does not grow: `capacity` states per slot (default: `DeviceBallSearch`'s rule from the largest budget of
-	the call, at most `default_capacity`).  A search whose next iteration might not fit -- states + 12 x (nodes it would pop) >
-	capacity -- stops before that iteration: False, stop reason 5, `capacity_exhausted[i]` set, the other searches undisturbed.
-
-	After a call, indexed by input position: `lengths` (-1: not met), `status` (n, 10) -- rk_bsearch_status's words: done, won,
-	states, iterations, popped, stop reason, error, next pops, complete levels, meeting node --, `sizes`, `depths`, `popped`,
-	`iterations`, `meeting_depths` (-1: none), `stops`, `capacity_exhausted`, `action_queue_of(i)` and `arrays(i)`.
-	`on_poll(status)`, if set, is called at every poll with the status of the states seen finished so far (zeros for the others).
-
-	`pops` = 2 048 by default is provisional, not measured yet: 64 slots x 12 x 2 048 children fill an iteration with 1.6 M threads,
-	eight times a single search's 16 384 pops, while a level of a few thousand nodes still takes few iterations.
-	benchmarks/ball_batch.py sweeps 512 / 2 048 / 16 384 at 16 / 64 / 256 searches and names the value it favours at 64.
-	"""
+class _BallSearchBatch(_ffi.Owner):
+	"""What `DeviceBallSearchBatch` and `DeviceSymBallSearchBatch` share, as `_BallSearch` serves the two single agents: the arguments
+	and their checks, the engine that is kept between calls, and the host loop of a call -- slots, refill at every poll, budgets,
+	the time limit, `keep_arrays`, `on_poll`, and putting live slots to rest.  `_entries` is the prefix of the engine's entry points
+	(one argument list and one status layout for both), `_ball_type` the kind of ball it ends at."""
 	default_capacity = 8_000_000
-	MAX_SEARCHES = 1024                     # rk_bsearchb_create's limits
+	MAX_SEARCHES = 1024                     # the limits of rk_bsearchb_create and rk_ssearchb_create
 	MAX_POPS = 1 << 22
 	MAX_CAPACITY = 0x3FFFFFF0
 	PATH_WORDS = 64                         # actions read per slot at a poll (a longer queue is read again, whole)
+	_entries = None
+	_ball_type = None
 
-	def __init__(self, ball: DeviceGoalBall, searches: int = 64, pops: int = 2_048, capacity: int = None, poll: int = 8):
-		if not isinstance(ball, DeviceGoalBall):
-			raise TypeError(f"ball must be a DeviceGoalBall, got {type(ball).__name__}")
+	def __init__(self, ball, searches: int = 64, pops: int = 2_048, capacity: int = None, poll: int = 8):
+		if not isinstance(ball, self._ball_type):
+			raise TypeError(f"ball must be a {self._ball_type.__name__}, got {type(ball).__name__}")
 		self.searches = eng.int_in("searches", searches, 1, self.MAX_SEARCHES)
 		self.pops = eng.int_in("pops", pops, 1, self.MAX_POPS)
 		self.capacity = eng.int_in("capacity", capacity, 2, self.MAX_CAPACITY, none_ok=True)
@@ -951,9 +933,13 @@ class DeviceBallSearchBatch(_ffi.Owner):
 	depths = property(lambda self: self.status[:, 8])
 	capacity_exhausted = property(lambda self: self.status[:, 5] == 5)
 
+	def _entry(self, name: str):
+		return getattr(_ffi.lib(), f"{self._entries}_{name}")
+
 	@property
 	def meeting_depths(self) -> np.ndarray:
-		"""int64 (n,): the depth in the ball of the node every search met, -1 for a search that did not meet."""
+		"""int64 (n,): the depth in the ball of the node every search met, from the ball's level boundaries; -1 for a search that did
+		not meet."""
 		meet = self.status[:, 9]
 		if not meet.any():
 			return np.full(len(meet), -1, np.int64)
@@ -964,20 +950,20 @@ class DeviceBallSearchBatch(_ffi.Owner):
 			return self._h
 		self._free()                        # the old pools go before the new ones are made
 		self._h_cap = capacity
-		return self._create("rk_bsearchb_create", "rk_bsearchb_destroy", self.ball._h, self.searches, capacity, self.pops)
+		return self._create(f"{self._entries}_create", f"{self._entries}_destroy", self.ball._h, self.searches, capacity, self.pops)
 
 	def _start(self, h, slots: list, rows: np.ndarray, budgets: np.ndarray):
 		sl = np.ascontiguousarray(slots, dtype=np.int32)
 		rows, budgets = np.ascontiguousarray(rows, dtype=np.int8), np.ascontiguousarray(budgets, dtype=np.int64)
-		_ffi.check(_ffi.lib().rk_bsearchb_reset(h, len(sl), sl.ctypes.data, rows.ctypes.data, budgets.ctypes.data, _ffi.stream_ptr()))
+		_ffi.check(self._entry("reset")(h, len(sl), sl.ctypes.data, rows.ctypes.data, budgets.ctypes.data, _ffi.stream_ptr()))
 
 	def _paths(self, h, max_len: int) -> np.ndarray:
 		out = np.zeros((self.searches, 1 + max_len), np.int32)
-		_ffi.check(_ffi.lib().rk_bsearchb_paths(h, out.ctypes.data, max_len, _ffi.stream_ptr()))
+		_ffi.check(self._entry("paths")(h, out.ctypes.data, max_len, _ffi.stream_ptr()))
 		return out
 
 	def _export(self, h, slot: int, n: int):
-		states, parents, actions = eng.export_frontier(_ffi.lib().rk_bsearchb_export, (h, slot), n)
+		states, parents, actions = eng.export_frontier(self._entry("export"), (h, slot), n)
 		return _states_out(self._is2024, states, n)[1:], parents[1:], actions[1:]
 
 	@no_grad
@@ -1003,7 +989,8 @@ class DeviceBallSearchBatch(_ffi.Owner):
 			return np.zeros(0, bool)
 		_ffi.require_gpu()
 		self.ball.build()
-		lib, stream = _ffi.lib(), _ffi.stream_ptr()
+		stream = _ffi.stream_ptr()
+		run, read_status = self._entry("run"), self._entry("status")
 		S, K = self.searches, 12 * self.pops
 		cap = self.capacity or min(int(budgets.max()) + K, self.default_capacity)
 		h = self._engine(max(2, min(cap, self.MAX_CAPACITY)))
@@ -1012,7 +999,7 @@ class DeviceBallSearchBatch(_ffi.Owner):
 		st = np.zeros((S, 10), np.int64)
 		try:
 			while True:
-				_ffi.check(lib.rk_bsearchb_status(h, st.ctypes.data, stream))
+				_ffi.check(read_status(h, st.ctypes.data, stream))
 				if st[holds >= 0, 6].any():
 					raise _ffi.RubiksHipError(f"ball search engine error codes {st[holds >= 0, 6].tolist()}")
 				done = np.nonzero((holds >= 0) & (st[:, 0] != 0))[0]
@@ -1024,6 +1011,8 @@ class DeviceBallSearchBatch(_ffi.Owner):
 						i = int(holds[s])
 						self.status[i] = st[s]
 						if st[s, 1]:
+							if paths[s, 0] < 0:
+								raise _ffi.RubiksHipError(f"{self._entries}_paths: the search of state {i} met the ball, but its queue cannot be walked ({int(paths[s, 0])})")
 							self.lengths[i] = paths[s, 0]
 							self._queues[i] = deque(paths[s, 1:1 + paths[s, 0]].tolist())
 						if keep_arrays:
@@ -1045,7 +1034,7 @@ class DeviceBallSearchBatch(_ffi.Owner):
 					break
 				room = int((budgets[holds[live]] - st[live, 2]).min())
 				burst = eng.burst(self.poll, room, K)
-				_ffi.check(lib.rk_bsearchb_run(h, burst, stream))
+				_ffi.check(run(h, burst, stream))
 				self.lockstep_iterations += burst
 			live = np.nonzero(holds >= 0)[0]
 			if len(live):                       # out of time: what the searches had reached, stop reason 0; then the slots are put to rest
@@ -1075,8 +1064,73 @@ class DeviceBallSearchBatch(_ffi.Owner):
 	def __len__(self):
 		return int(self.status[:, 2].sum())
 
+
+class DeviceBallSearchBatch(_BallSearchBatch):
+	"""
+	Shortest solutions of many states at once: `searches` slots, each a whole `DeviceBallSearch` of its own (pool, table,
+	counters), advanced in lock-step by the same four launches with the slot in the grid's second dimension (engine
+	rk_bsearchb_*, csrc/rk_ball.hip).  A single search is latency-bound -- four launches per iteration on a few per cent of the
+	card --; the batch pays those launches once for all slots.  Every state gets exactly what `DeviceBallSearch` gives it alone:
+	result, queue, states stored, depth, nodes popped, meeting and pool, whatever slot it ran in and whenever it was started.
+
+	`search(states)` takes any number of states.  Slots take them in input order; every `poll` iterations the host reads all
+	slots' status, records the searches that finished (their queues; their pools with `keep_arrays`) and starts the next waiting
+	states in the slots that became free, so short searches do not leave the card idle beside long ones.
+
+	The pool of a slot does not grow: `capacity` states per slot (default: `DeviceBallSearch`'s rule from the largest budget of
+	the call, at most `default_capacity`).  A search whose next iteration might not fit -- states + 12 x (nodes it would pop) >
+	capacity -- stops before that iteration: False, stop reason 5, `capacity_exhausted[i]` set, the other searches undisturbed.
+
+	After a call, indexed by input position: `lengths` (-1: not met), `status` (n, 10) -- rk_bsearch_status's words: done, won,
+	states, iterations, popped, stop reason, error, next pops, complete levels, meeting node --, `sizes`, `depths`, `popped`,
+	`iterations`, `meeting_depths` (-1: none), `stops`, `capacity_exhausted`, `action_queue_of(i)` and `arrays(i)`.
+	`on_poll(status)`, if set, is called at every poll with the status of the states seen finished so far (zeros for the others).
+
+	`pops` = 2 048 by default is provisional, not measured yet: 64 slots x 12 x 2 048 children fill an iteration with 1.6 M threads,
+	eight times a single search's 16 384 pops, while a level of a few thousand nodes still takes few iterations.
+	benchmarks/ball_batch.py sweeps 512 / 2 048 / 16 384 at 16 / 64 / 256 searches and names the value it favours at 64.
+	"""
+	_entries = "rk_bsearchb"
+	_ball_type = DeviceGoalBall
+
+	def __init__(self, ball: DeviceGoalBall, searches: int = 64, pops: int = 2_048, capacity: int = None, poll: int = 8):
+		super().__init__(ball, searches, pops, capacity, poll)
+
 	def __str__(self):
 		return f"Breadth-first searches to a goal ball x{self.searches} (device, radius={self.ball.radius}, pops={self.pops})"
+
+
+class DeviceSymBallSearchBatch(_BallSearchBatch):
+	"""
+	`DeviceBallSearchBatch` on a kept `DeviceSymBall`: `searches` slots, each a whole `DeviceSymBallSearch` of its own (pool, table,
+	counters, the words of the probe launch), advanced in lock-step by the same five launches with the slot in the grid's second
+	dimension (engine rk_ssearchb_*, csrc/rk_sym.hip).  A single symmetry search is 2-4 iterations of five latency-bound launches
+	at optimal lengths 12 and 14; the batch pays those launches once for all slots, and a slot stores so few states beside a
+	radius-10 ball (thousands where the plain search stores hundreds of thousands) that the same HBM holds far more of them.
+	Every state gets exactly what `DeviceSymBallSearch` gives it alone -- result, queue, states stored, depth, nodes popped, meeting
+	and pool, whatever slot it ran in and whenever it was started --, hence what `DeviceBallSearchBatch` gives it on a
+	`DeviceGoalBall` of the same radius but for the ball's half of the queue, which has the same length.
+
+	The constructor, `search`, the attributes, `action_queue_of`, `arrays`, `on_poll` and the pool-full rule (stop reason 5,
+	`capacity_exhausted[i]`) are `DeviceBallSearchBatch`'s.  `meeting_depths` comes from the symmetry ball's level boundaries;
+	`meeting_nodes` (status word 9) is the node in the ball of the REPRESENTATIVE of the state every search met, 0 for none.
+
+	`pops` = 2 048 by default is provisional, taken over from `DeviceBallSearchBatch`.  benchmarks/symball_search_batch.py sweeps
+	512 / 2 048 / 16 384 at 16 / 64 / 256 searches and names the value it favours at 64 on its mixed set; its one run so far
+	(profiles/r16_symball_search_batch.json) is no reason to move: the mixed set, whose time is that of its 16-move starts, favours
+	16 384 by 3 %, while 12- and 14-move starts run twice as fast at 512 or 2 048 as at 16 384.
+	"""
+	_entries = "rk_ssearchb"
+	_ball_type = DeviceSymBall
+
+	def __init__(self, ball: DeviceSymBall, searches: int = 64, pops: int = 2_048, capacity: int = None, poll: int = 8):
+		super().__init__(ball, searches, pops, capacity, poll)
+
+	meeting_nodes = property(lambda self: self.status[:, 9])
+
+	def __str__(self):
+		return (f"Breadth-first searches to a symmetry-reduced goal ball x{self.searches} (device, radius={self.ball.radius}, "
+		        f"pops={self.pops})")
 
 
 class PolicySearch(DeepAgent):
