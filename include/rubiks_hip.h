@@ -549,6 +549,23 @@ int rk_symball_depth(rk_symball_t *h, const int8_t *d_states, size_t n, int32_t 
  * ball that passed its build).  One launch; stream-ordered, no synchronisation. */
 int rk_symball_solve(rk_symball_t *h, const int8_t *d_states, size_t n, int32_t *d_lengths, int8_t *d_actions, int32_t *d_error,
                      void *stream);
+/* Depth-first probes past the ball's radius: for every DEVICE state i of d_states int8 (n, 20) and every word of `extra` moves
+ * (1..8) whose rank lies in [word_first, word_first + word_count), the word is applied to the state, the result canonicalised and
+ * looked up in the ball; if the ball holds it, atomicMin(d_best[i], rank).  A word is a sequence of actions 0..11 in which no
+ * action is the opposite turn (a ^ 1) of the one before it; "before the first" is d_last[i], the move that led to state i
+ * (d_last NULL, or an entry outside 0..11 such as -1: the first move has all 12 choices).  Words are ranked in lexicographic
+ * order of their actions, rank 0 first: 11^extra of them, 12 * 11^(extra-1) without a last action; ranks a state does not have
+ * are skipped.  The caller fills d_best uint32 (n) with 0xFFFFFFFF before the first launch of a round; ranks above a state's
+ * current d_best may be skipped, the result is the minimum either way.  If every state within extra - 1 moves of state i lies
+ * outside the ball, a hit lies at ball depth `radius` exactly and radius + extra is the distance of state i to solved.
+ * One launch -- a persistent grid, a wave per (state, 121 consecutive ranks), which share all but their last two moves --,
+ * stream-ordered, no synchronisation; the ball is only read, nothing but d_best is written.  RK_EINVAL for extra outside 1..8 or
+ * n * word_count above rk_sdeepen_max_probes(), RK_ESTATE for a ball that is not built. */
+int rk_sdeepen(rk_symball_t *ball, const int8_t *d_states, const int8_t *d_last, size_t n, int extra, uint32_t word_first,
+               uint32_t word_count, uint32_t *d_best, void *stream);
+/* The most probes (n * word_count) of one rk_sdeepen / rk_sdeepen_nodes launch: 2^28, which keeps a launch well under a second
+ * (benchmarks/symball_deepen.py measures a full launch).  Touches no device. */
+long long rk_sdeepen_max_probes(void);
 /* rk_bshorten against the symmetry ball: one pass over a batch of action queues, with rk_bshorten's contract (above) -- the
  * same arguments, limits, return codes and d_error semantics, scratch of rk_bshorten_scratch_bytes(n, max_len, window) bytes --
  * and d(i, j) = the symmetry ball's depth of X(i, j), i.e. the level of its representative.  That is the plain ball's d(i, j)
@@ -598,6 +615,29 @@ int rk_ssearch_export(rk_ssearch_t *h, size_t first, size_t count, int8_t *h_sta
  * at most `radius` steps; walked on the device by one wave.  Returns its length or a negative error (RK_ESTATE: not met, or a
  * state on the way down has no such child); writes at most max_len actions. */
 long long rk_ssearch_path(rk_ssearch_t *h, long long *h_actions, size_t max_len, void *stream);
+
+/* Deepening: how a search whose pool is full goes on.  The pool's newest complete level is the frontier; words from its nodes
+ * are probed against the ball by rk_sdeepen's launch, and the first round `extra` with a hit gives a shortest solution of
+ * length (level + extra + radius).
+ * rk_sdeepen_set_pops: the iterations to come pop at most `pops` nodes (1 .. the pops of rk_ssearch_create); no result depends
+ * on it.  A host whose pool cannot take 12 * pops more states lowers it to complete as many levels as fit; a reset restores the
+ * created value.  One launch of one thread, stream-ordered. */
+int rk_sdeepen_set_pops(rk_ssearch_t *h, int pops, void *stream);
+/* h_out[2] = the first and the last node of the newest complete level of the own pool (nodes behind the last are a partial next
+ * level).  Reads the counters on `stream` and synchronises it, as rk_ssearch_status; call it between iterations. */
+int rk_sdeepen_frontier(rk_ssearch_t *h, long long *h_out, void *stream);
+/* rk_sdeepen on the pool rows node_first .. node_first + node_count - 1, d_last = the stored action of each node, none for
+ * node 1; d_best[k] belongs to node node_first + k.  The rows must lie inside 1..capacity (RK_EINVAL otherwise: no launch reads
+ * outside the pool's arrays), and the caller keeps them inside rk_sdeepen_frontier's range: the entry does not wait for the
+ * counters, so a row behind n_states is probed as whatever bytes it holds and its d_best means nothing.  rk_sdeepen's limits
+ * and return codes. */
+int rk_sdeepen_nodes(rk_ssearch_t *h, int extra, size_t node_first, size_t node_count, uint32_t word_first, uint32_t word_count,
+                     uint32_t *d_best, void *stream);
+/* The action queue start -> `node` -> word `rank` of `extra` moves -> descent through the ball, walked by one wave as
+ * rk_ssearch_path.  Returns its length or a negative error: RK_EINVAL for a node outside 1..n_states or extra outside 1..8,
+ * RK_ESTATE if the node has no such word or the ball does not hold the moved state's representative.  Synchronises. */
+long long rk_sdeepen_path(rk_ssearch_t *h, long long node, int extra, uint32_t rank, long long *h_actions, size_t max_len,
+                                 void *stream);
 
 /* ---- many such searches in lock-step (rk_ssearchb_*) --------------------------------------------------------------------
  * rk_bsearchb_* for rk_ssearch: n_slots slots, each a whole rk_ssearch of its own -- pool, table sized to it, counters, batch

@@ -136,6 +136,8 @@ SIGNATURES = {
 	"rk_symball_export": (_i, [_vp, _sz, _sz, _vp, _vp]),
 	"rk_symball_depth": (_i, [_vp, _vp, _sz, _vp, _vp]),
 	"rk_symball_solve": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+	"rk_sdeepen": (_i, [_vp, _vp, _vp, _sz, _i, C.c_uint32, C.c_uint32, _vp, _vp]),
+	"rk_sdeepen_max_probes": (C.c_longlong, []),
 	"rk_sshorten": (_i, [_vp, _vp, _vp, _sz, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
 	"rk_ssearch_create": (_i, [C.POINTER(_vp), _vp, _sz, _i]),
 	"rk_ssearch_destroy": (_i, [_vp]),
@@ -146,6 +148,10 @@ SIGNATURES = {
 	"rk_ssearch_size": (C.c_longlong, [_vp]),
 	"rk_ssearch_export": (_i, [_vp, _sz, _sz, _vp, _vp, _vp, _vp]),
 	"rk_ssearch_path": (C.c_longlong, [_vp, _vp, _sz, _vp]),
+	"rk_sdeepen_set_pops": (_i, [_vp, _i, _vp]),
+	"rk_sdeepen_frontier": (_i, [_vp, _vp, _vp]),
+	"rk_sdeepen_nodes": (_i, [_vp, _i, _sz, _sz, C.c_uint32, C.c_uint32, _vp, _vp]),
+	"rk_sdeepen_path": (C.c_longlong, [_vp, C.c_longlong, _i, C.c_uint32, _vp, _sz, _vp]),
 	"rk_ssearchb_create": (_i, [C.POINTER(_vp), _vp, _i, _sz, _i]),
 	"rk_ssearchb_destroy": (_i, [_vp]),
 	"rk_ssearchb_reset": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),

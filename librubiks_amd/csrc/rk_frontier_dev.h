@@ -141,7 +141,7 @@ __device__ __forceinline__ void fr_rehash(const FrontierDev &d)
 }
 
 // ---- the searches that end at a kept ball (rk_bsearch_*, rk_bsearchb_*, rk_ssearch_*): one side, level by level ----
-enum { S_DEPTH = F_COMMON, S_HI, S_MEET, S_POPPED, S_COUNT = 32 };
+enum { S_DEPTH = F_COMMON, S_HI, S_MEET, S_POPPED, S_LO, S_COUNT = 32 };      // S_LO .. S_HI: the newest complete level
 
 // After a pop count change: the end of a level, the done flags and the next P (rk_bibfs.hip: bibfs_next, one side).  One thread.
 __device__ __forceinline__ void srch_next(const FrontierDev &d)
@@ -150,6 +150,7 @@ __device__ __forceinline__ void srch_next(const FrontierDev &d)
 	int32_t hi = d.ctr[S_HI];
 	if (head > hi) {                                                     // the level is exhausted and nothing met: it is complete
 		d.ctr[S_DEPTH] += 1;
+		d.ctr[S_LO] = hi + 1;
 		d.ctr[S_HI] = hi = size;
 	}
 	int stop = F_STOP_NO;

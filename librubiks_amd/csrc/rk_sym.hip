@@ -66,12 +66,20 @@
 //   k_ss_dp       shorten_dp
 //   k_ss_emit     a wave per queue: a replaced edge is composed again, canonicalised, probed, descended and written inverted
 // Three launches; nothing of the ball is written.
+//
+// Deepening (rk_sdeepen, rk_sdeepen_*) goes on where memory ends: short words applied to a state, each result canonicalised
+// and probed, nothing kept but the lowest rank that hit (rk_deepen_dev.h: the words, their ranks, the item of a wave).
+//   k_sd_probe       a persistent grid, waves stride over the (state, 121 ranks) items, the tables staged once per workgroup; on
+//                    the caller's states (rk_sdeepen) or on rows of a search's pool with the stored action as the last move
+//   k_ss_setpops     one thread: a lower pop count for the iterations to come (the host lowers it when the pool is nearly full)
+//   k_ss_deepen_walk one wave: the path to a pool node, a word from it, then the descent from the moved state
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <climits>
 #include <cstring>
 
 #include "../../include/rubiks_hip.h"
+#include "rk_deepen_dev.h"
 #include "rk_frontier_dev.h"
 #include "rk_device.h"
 #include "rk_error.h"
@@ -354,7 +362,7 @@ __device__ __forceinline__ void ssearch_root(const FrontierDev &d, const SymBall
 	for (int j = 0; j < 5; j++) d.states[5 + j] = s[j];
 	d.parent[1] = 0; d.pact[1] = 0;
 	d.table[hash_state(s) & d.mask] = 1u;
-	d.ctr[F_SIZE] = 1; d.ctr[F_HEAD] = 1; d.ctr[S_HI] = 1;
+	d.ctr[F_SIZE] = 1; d.ctr[F_HEAD] = 1; d.ctr[S_HI] = 1; d.ctr[S_LO] = 1;
 	d.ctr[F_BUDGET] = budget;
 	d.ctr[F_WINPOS] = (int32_t)F_NO_WIN;
 	if (e != 0u) {                                                       // the ball holds the start's orbit: nothing is popped
@@ -487,6 +495,72 @@ void k_ss_rehash(FrontierDev d) { fr_rehash(d); }
 __global__ __launch_bounds__(64)
 void k_ss_walk(FrontierDev d, SymBallView b, int32_t *out, int max_len) { ssearch_walk(d, b, out, max_len); }
 
+// ---- deepening: words from a state, every result probed (rk_deepen_dev.h) ----
+__global__ __launch_bounds__(256)
+void k_sd_probe(SymBallView b, DeepenJob job)
+{
+	__shared__ uint32_t s_sym[SYM_LDS_DWORDS];
+	__shared__ u32x4 s_act[36];
+	sym_stage(s_sym, threadIdx.x, 256);
+	stage_action_tables(s_act, threadIdx.x);
+	__syncthreads();
+	deepen_probe(b, job, s_sym, s_act, (size_t)blockIdx.x * 4 + (size_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), (size_t)gridDim.x * 4);
+}
+
+// the pops of the iterations to come; results do not depend on them.  One thread.
+__global__ void k_ss_setpops(FrontierDev d)
+{
+	if (threadIdx.x != 0 || blockIdx.x != 0 || d.ctr[F_DONE]) return;
+	d.ctr[F_NPOP] = min(d.pops, d.ctr[S_HI] - d.ctr[F_HEAD] + 1);
+}
+
+// The queue start -> `node` -> word `rank` of `extra` moves -> descent, one wave, as ssearch_walk: out[0] = length, -1 when the
+// parent chain is broken or the node has no such word, -2 when the ball does not hold the moved state's representative or the
+// descent finds no way on.  Every lane computes the same; lane 0 writes.
+__global__ __launch_bounds__(64)
+void k_ss_deepen_walk(FrontierDev d, SymBallView b, int node, int extra, uint32_t rank, int32_t *out, int max_len)
+{
+	__shared__ uint32_t s_sym[SYM_LDS_DWORDS];
+	__shared__ u32x4 s_act[36];
+	const int lane = threadIdx.x;
+	sym_stage(s_sym, lane, 64);
+	stage_action_tables(s_act, lane);
+	__syncthreads();
+	if (lane == 0) out[0] = -1;
+	int ls = 0;
+	for (int i = node; i != 1; ls++) {
+		if (i < 1 || (uint32_t)i >= d.cap1 || ls > (int)d.cap1) return;
+		i = d.parent[i];
+	}
+	int i = node;
+	for (int k = ls - 1; k >= 0; k--) {
+		if (k < max_len && lane == 0) out[1 + k] = d.pact[i] & PACT_ACTION;
+		i = d.parent[i];
+	}
+	int word[DEEPEN_MAX_EXTRA];
+	if (!deepen_word(extra, node == 1 ? -1 : deepen_last(d.pact[node] & PACT_ACTION), rank, word)) return;
+	uint32_t x[5];
+	load5(d.states + (size_t)node * 5, x);
+	int len = ls;
+	for (int k = 0; k < extra; k++, len++) {
+		if (len < max_len && lane == 0) out[1 + len] = word[k];
+		uint32_t y[5];
+		deepen_move(s_act, word[k], x, y);
+		#pragma unroll
+		for (int j = 0; j < 5; j++) x[j] = y[j];
+	}
+	const SymLane L = sym_lane(min(lane, N_SYM - 1));
+	uint32_t rep[5];
+	int sym, count;
+	sym_canonical(s_sym, L, lane, x, rep, &sym, &count);
+	const uint32_t g = probe_find(b.table, b.mask, b.states, rep);
+	bool ok = g != 0u;
+	const int own = len;
+	if (ok) len = own + sb_descend(b, s_sym, s_act, L, lane, x, level_of(b.lstart, g),
+	                               [&](int k, int a) { if (own + k < max_len && lane == 0) out[1 + own + k] = a; }, &ok);
+	if (lane == 0) out[0] = ok ? len : -2;
+}
+
 // ---- the batch: S searches in lock-step, slot blockIdx.y of `devs` per workgroup row (rk_ball.hip: kb_bsearch_*) ----
 // Every slot is a whole search of its own -- pool, table, counters, batch scratch, look-back words, ticket, epoch and the 12 P
 // words of `hit` --, so a launch reads and writes through devs[blockIdx.y] and that slot's slice of `hits` alone; the ball is read
@@ -604,6 +678,7 @@ struct rk_symball : KeptBall {
 struct rk_ssearch : FrontierPool {
 	uint32_t *hit = nullptr;                    // per child of the batch: the ball's node of its representative, or 0
 	rk_symball *ball = nullptr;
+	int pops_made = 0;                          // what it was created with: rk_sdeepen_set_pops lowers d.pops, a reset restores it
 };
 
 // S searches in lock-step: the slots (rk_search_host.h: FrontierSlots), their `hit` block and the ball they all read
@@ -634,6 +709,23 @@ int check_sym_states(const char *who, const void *d_states, size_t n)
 	if (n > (size_t)INT32_MAX) return fail(RK_EINVAL, "%s: %zu states in one launch", who, n);
 	if (n != 0 && !d_states) return fail(RK_EINVAL, "%s: null pointer", who);
 	if ((uintptr_t)d_states & 3u) return fail(RK_EINVAL, "%s: device pointers must be 4-byte aligned", who);
+	return RK_OK;
+}
+
+// the range checks of a deepening launch and the launch itself
+int launch_deepen(const char *who, rk_symball *ball, DeepenJob job, hipStream_t st)
+{
+	if (job.extra < 1 || job.extra > DEEPEN_MAX_EXTRA) return fail(RK_EINVAL, "%s: extra %d outside 1..%d", who, job.extra, DEEPEN_MAX_EXTRA);
+	if ((unsigned long long)job.n * job.word_count > DEEPEN_MAX_PROBES)
+		return fail(RK_EINVAL, "%s: %zu states x %u words are more than the %llu probes of one launch", who, job.n, job.word_count, DEEPEN_MAX_PROBES);
+	if (!job.best || ((uintptr_t)job.best & 3u)) return fail(RK_EINVAL, "%s: d_best must be a 4-byte aligned device pointer", who);
+	const unsigned long long all = deepen_words(job.extra, -1);
+	if (job.n == 0 || job.word_count == 0 || job.word_first >= all) return RK_OK;
+	job.word_count = (uint32_t)std::min<unsigned long long>(job.word_count, all - job.word_first);
+	const uint32_t span = job.extra >= 3 ? DEEPEN_SPAN : 132u;
+	const size_t items = job.n * (size_t)((job.word_first + job.word_count - 1) / span - job.word_first / span + 1);
+	hipLaunchKernelGGL(k_sd_probe, dim3(sym_grid(items)), dim3(256), 0, st, ball->view, job);
+	RK_HIP(hipGetLastError());
 	return RK_OK;
 }
 
@@ -781,6 +873,18 @@ int rk_symball_solve(rk_symball_t *h, const int8_t *d_states, size_t n, int32_t 
 	return RK_OK;
 }
 
+long long rk_sdeepen_max_probes(void) { return (long long)DEEPEN_MAX_PROBES; }
+
+int rk_sdeepen(rk_symball_t *ball, const int8_t *d_states, const int8_t *d_last, size_t n, int extra, uint32_t word_first, uint32_t word_count,
+               uint32_t *d_best, void *stream)
+{
+	if (!ball) return fail(RK_EINVAL, "rk_sdeepen: null ball");
+	if (!ball->built) return fail(RK_ESTATE, "rk_sdeepen: build the ball first");
+	if (int e = check_sym_states("rk_sdeepen", d_states, n)) return e;
+	return launch_deepen("rk_sdeepen", ball, DeepenJob{reinterpret_cast<const uint32_t *>(d_states), d_last, -1, n, extra, word_first, word_count, d_best},
+	                     (hipStream_t)stream);
+}
+
 int rk_sshorten(rk_symball_t *h, const int8_t *d_actions, const int32_t *d_len, size_t n, int max_len, int window, int8_t *d_out_actions,
                 int32_t *d_out_len, int32_t *d_error, void *d_scratch, size_t scratch_bytes, void *stream)
 {
@@ -810,6 +914,7 @@ int rk_ssearch_create(rk_ssearch_t **out, rk_symball_t *ball, size_t capacity, i
 	if (!e) e = h->pool.alloc(&h->hit, (size_t)12 * pops);
 	if (e) { delete h; return e; }
 	h->ball = ball;
+	h->pops_made = pops;
 	ball->attached += 1;
 	*out = h;
 	return RK_OK;
@@ -827,6 +932,7 @@ int rk_ssearch_reset(rk_ssearch_t *h, const int8_t *h_start_state, long long max
 	if (!h || !h_start_state) return fail(RK_EINVAL, "rk_ssearch_reset: null argument");
 	if (!h->ball->built) return fail(RK_ESTATE, "rk_ssearch_reset: build the ball first");
 	hipStream_t st = (hipStream_t)stream;
+	h->d.pops = h->pops_made;
 	return h->reset(h_start_state, st, [&] {
 		hipLaunchKernelGGL(k_ss_root, dim3(1), dim3(64), 0, st, h->d, h->ball->view, h->root_dev, budget_of(max_states));
 	});
@@ -879,6 +985,59 @@ long long rk_ssearch_path(rk_ssearch_t *h, long long *h_actions, size_t max_len,
 	if (int e = read_walk(h->walk, FRONTIER_WALK_MAX, h_actions, max_len, st, &len)) return e;
 	if (len == -2) return fail(RK_ESTATE, "rk_ssearch_path: the meeting state has no way down the ball (or is not where the search met)");
 	if (len < 0) return fail(RK_ESTATE, "rk_ssearch_path: the search has not met the ball (or a parent chain is broken)");
+	return (long long)len;
+}
+
+int rk_sdeepen_set_pops(rk_ssearch_t *h, int pops, void *stream)
+{
+	if (int e = FrontierPool::check_ready(h, "rk_sdeepen_set_pops")) return e;
+	if (pops < 1 || pops > h->pops_made) return fail(RK_EINVAL, "rk_sdeepen_set_pops: pops %d outside 1..%d", pops, h->pops_made);
+	h->d.pops = pops;
+	hipLaunchKernelGGL(k_ss_setpops, dim3(1), dim3(64), 0, (hipStream_t)stream, h->d);
+	RK_HIP(hipGetLastError());
+	return RK_OK;
+}
+
+int rk_sdeepen_frontier(rk_ssearch_t *h, long long *h_out, void *stream)
+{
+	if (int e = FrontierPool::check_ready(h, "rk_sdeepen_frontier")) return e;
+	if (!h_out) return fail(RK_EINVAL, "rk_sdeepen_frontier: null output");
+	int32_t c[S_COUNT];
+	if (int e = h->read_ctr(c, (hipStream_t)stream)) return e;
+	h_out[0] = c[S_LO];
+	h_out[1] = c[S_HI];
+	return RK_OK;
+}
+
+int rk_sdeepen_nodes(rk_ssearch_t *h, int extra, size_t node_first, size_t node_count, uint32_t word_first, uint32_t word_count, uint32_t *d_best,
+                      void *stream)
+{
+	if (int e = FrontierPool::check_ready(h, "rk_sdeepen_nodes")) return e;
+	if (!h->ball->built) return fail(RK_ESTATE, "rk_sdeepen_nodes: build the ball first");
+	if (node_first < 1 || node_count > h->cap || node_first + node_count > h->cap + 1)
+		return fail(RK_EINVAL, "rk_sdeepen_nodes: nodes %zu..%zu outside the pool", node_first, node_first + node_count);
+	return launch_deepen("rk_sdeepen_nodes", h->ball,
+	                     DeepenJob{h->d.states + node_first * 5, reinterpret_cast<const int8_t *>(h->d.pact) + node_first, 1 - (long long)node_first,
+	                               node_count, extra, word_first, word_count, d_best},
+	                     (hipStream_t)stream);
+}
+
+long long rk_sdeepen_path(rk_ssearch_t *h, long long node, int extra, uint32_t rank, long long *h_actions, size_t max_len, void *stream)
+{
+	if (int e = FrontierPool::check_ready(h, "rk_sdeepen_path")) return e;
+	if (!h->ball->built) return fail(RK_ESTATE, "rk_sdeepen_path: build the ball first");
+	if (extra < 1 || extra > DEEPEN_MAX_EXTRA) return fail(RK_EINVAL, "rk_sdeepen_path: extra %d outside 1..%d", extra, DEEPEN_MAX_EXTRA);
+	if (!h_actions && max_len > 0) return fail(RK_EINVAL, "rk_sdeepen_path: null h_actions with max_len %zu", max_len);
+	hipStream_t st = (hipStream_t)stream;
+	int32_t c[S_COUNT];
+	if (int e = h->read_ctr(c, st)) return e;
+	if (node < 1 || node > c[F_SIZE]) return fail(RK_EINVAL, "rk_sdeepen_path: node %lld outside 1..%d", node, c[F_SIZE]);
+	hipLaunchKernelGGL(k_ss_deepen_walk, dim3(1), dim3(64), 0, st, h->d, h->ball->view, (int)node, extra, rank, h->walk, FRONTIER_WALK_MAX);
+	RK_HIP(hipGetLastError());
+	int32_t len = 0;
+	if (int e = read_walk(h->walk, FRONTIER_WALK_MAX, h_actions, max_len, st, &len)) return e;
+	if (len == -2) return fail(RK_ESTATE, "rk_sdeepen_path: word %u of %d moves from node %lld does not lead into the ball", rank, extra, node);
+	if (len < 0) return fail(RK_ESTATE, "rk_sdeepen_path: node %lld has no word %u of %d moves (or a parent chain is broken)", node, rank, extra);
 	return (long long)len;
 }
 

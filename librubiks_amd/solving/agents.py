@@ -335,6 +335,14 @@ class _PoolSearch(Agent, _ffi.Owner):
 		self.grown += 1
 		return True
 
+	def _fewer_pops(self, h, pops: int) -> int:
+		"""A pool that cannot grow: a lower pop count (< `pops`) for the iterations to come, told to the engine, or 0 to give up."""
+		return 0
+
+	def _pool_full(self, h, t0: float, time_limit: float) -> bool:
+		"""What `search` returns once the pool takes no more pops: an engine that can go on without a pool does so here."""
+		return False
+
 	def _begin(self, root: np.ndarray) -> bool:
 		"""Before the engine is touched: clears the subclass's results; True when `root` needs no search."""
 		raise NotImplementedError
@@ -369,8 +377,12 @@ class _PoolSearch(Agent, _ffi.Owner):
 		while not status[0]:
 			room = (self._h_cap - self._n) // K              # iterations the pool takes whatever they find
 			if room == 0:
-				if not self._grow(h):
-					return False
+				if self._grow(h):
+					continue
+				fewer = self._fewer_pops(h, K // 12)
+				if not fewer:
+					return self._pool_full(h, t0, time_limit)
+				K = 12 * fewer
 				continue
 			_ffi.check(run(h, eng.burst(min(self.poll, room), budget - self._n, K), stream))
 			_ffi.check(read_status(h, status, stream))
@@ -496,6 +508,17 @@ class DeviceBiBFS(_PoolSearch):
 
 	def __str__(self):
 		return f"Two-sided breadth-first search (device, pops={self.pops})"
+
+
+def _words_of(ranks: np.ndarray, extra: int, last: np.ndarray) -> np.ndarray:
+	"""int64 (n, extra): word `ranks[i]` of `extra` moves behind the action `last[i]` (-1: none), rk_sdeepen's numbering: digit k of
+	the rank counts the allowed actions below action k, the opposite turn of the action before it left out."""
+	rem, prev = np.array(ranks, np.int64), np.array(last, np.int64)
+	out = np.empty((len(rem), extra), np.int64)
+	for k in range(extra):
+		d, rem = np.divmod(rem, 11 ** (extra - 1 - k))
+		out[:, k] = prev = np.where(prev < 0, d, d + (d >= (prev ^ 1)))
+	return out
 
 
 class _KeptBall(_ffi.Owner):
@@ -765,6 +788,86 @@ class DeviceSymBall(_KeptBall):
 		if int(err.item()):
 			raise _ffi.RubiksHipError(f"rk_symball_solve reported error {int(err.item())}: a state of the ball has no child one level nearer")
 
+	MAX_EXTRA = 8                           # the longest word of rk_sdeepen
+	deepen_cap = None                       # probes per launch (None: rk_sdeepen_max_probes()); tests lower it to split a round
+
+	def _launch_cap(self) -> int:
+		most = int(_ffi.lib().rk_sdeepen_max_probes())
+		return most if self.deepen_cap is None else eng.int_in("deepen_cap", self.deepen_cap, 1, most)
+
+	def solve_beyond(self, states, extra: int, last_actions=None, time_limit: float = None):
+		"""
+		(lengths int64 (n,), actions int64 (n, extra + radius)), rows padded with -1: shortest solutions past the radius by depth-first
+		probes (engine rk_sdeepen).  A state whose orbit the ball holds gets what `solve` gives.  The others run rounds
+		e = 1 .. `extra`, each on the still unanswered states only: every word of e moves is applied to the state and the result
+		looked up in the ball.  In the first round with a hit the answer is the state's lowest word in lexicographic order of its
+		actions, then `solve`'s descent from the moved state; its length e + radius is the distance to solved.  Length -1: no hit
+		within `extra` moves (or within `time_limit` seconds, checked between launches).  `extra` = 0 is `solve`.
+
+		`last_actions` (n,) names the move that led to each state, -1 for none: words that begin with its opposite turn are not
+		tried.  That is right when the state before that move is known to be no nearer to the ball -- a search's parent --; a
+		caller that cannot say so passes None.  States are in the representation cube.get_is2024() names.
+		"""
+		extra = eng.int_in("extra", extra, 0, self.MAX_EXTRA)
+		self.build()
+		rows = self._rows(states)
+		n, width = len(rows), extra + self.radius
+		last = None
+		if last_actions is not None:
+			last = np.asarray(last_actions, dtype=np.int64).reshape(-1)
+			if len(last) != n or (n and not (-1 <= last.min() and last.max() < 12)):
+				raise ValueError("last_actions must be n actions in 0..11, or -1 for none")
+		lengths, actions = np.full(n, -1, np.int64), np.full((n, width), -1, np.int64)
+		if n == 0:
+			return lengths, actions
+		t0 = time.perf_counter()
+		lib, stream, cap = _ffi.lib(), _ffi.stream_ptr(), self._launch_cap()
+		q = torch.from_numpy(rows).to(gpu)
+		got = torch.empty(n, dtype=torch.int32, device=gpu)
+		word = torch.empty((n, max(self.radius, 1)), dtype=torch.int8, device=gpu)
+		self._solve(q, n, got, word)
+		lengths[:] = got.cpu().numpy()
+		actions[:, :self.radius] = word.cpu().numpy()[:, :self.radius]
+		todo = np.nonzero(lengths < 0)[0]
+		for e in range(1, extra + 1):
+			m = len(todo)
+			if m == 0:
+				break
+			sub = q[torch.from_numpy(todo).to(gpu)].contiguous()
+			sub_last = None if last is None else last[todo]
+			d_last = None if last is None else torch.from_numpy(sub_last.astype(np.int8)).to(gpu)
+			words = (12 if last is None or (sub_last < 0).any() else 11) * 11 ** (e - 1)
+			best = torch.full((m,), -1, dtype=torch.int32, device=gpu)      # 0xFFFFFFFF: no hit
+			per = max(1, min(m, cap // words))                              # states per launch; a state's words in ranges of <= cap
+			for at in range(0, m, per):
+				cnt = min(per, m - at)
+				step = min(words, cap // cnt)
+				for first in range(0, words, step):
+					_ffi.check(lib.rk_sdeepen(self._h, sub[at:].data_ptr(), None if d_last is None else d_last[at:].data_ptr(), cnt, e, first,
+					                          min(step, words - first), best[at:].data_ptr(), stream))
+					if time_limit is not None:
+						torch.cuda.current_stream().synchronize()
+						if time.perf_counter() - t0 >= time_limit:
+							return lengths, actions
+			rank = best.cpu().numpy().view(np.uint32).astype(np.int64)
+			hit = np.nonzero(rank != 0xFFFFFFFF)[0]
+			if len(hit):
+				moves = _words_of(rank[hit], e, -np.ones(len(hit), np.int64) if last is None else sub_last[hit])
+				moved = sub[torch.from_numpy(hit).to(gpu)].contiguous()
+				for k in range(e):                                          # the hit states moved along their words, on the device
+					a = torch.from_numpy(moves[:, k].astype(np.uint8)).to(gpu)
+					_ffi.check(lib.rk_multi_rotate(_ffi.REPR_2024, moved.data_ptr(), a.data_ptr(), moved.data_ptr(), len(hit), stream))
+				got = torch.empty(len(hit), dtype=torch.int32, device=gpu)
+				self._solve(moved, len(hit), got, word)
+				down = got.cpu().numpy().astype(np.int64)
+				if (down != self.radius).any():
+					raise _ffi.RubiksHipError("rk_sdeepen reported a hit that does not lie at the ball's radius")
+				lengths[todo[hit]] = e + down
+				actions[todo[hit], :e] = moves
+				actions[todo[hit], e:e + self.radius] = word.cpu().numpy()[:len(hit), :self.radius]
+			todo = todo[rank == 0xFFFFFFFF]
+		return lengths, actions
+
 	def arrays(self):
 		"""The representatives of nodes 1 .. len(ball) in index order."""
 		is2024 = cube.get_is2024()
@@ -860,12 +963,84 @@ class DeviceSymBallSearch(_BallSearch):
 
 	`meeting` is the RAW state that met (the child that was not stored, or the start), `meeting_node` the node of its
 	representative in the ball, `meeting_depth` that node's depth.  Several agents may share one ball.
+
+	`deepen=E` > 0: a search that ends unsolved because the pool is exhausted -- and for no other reason -- goes on
+	without a pool.  First the pop count is lowered until not even one pop fits, so the complete levels are those of `pops=1`.
+	Then rounds e = 1..E apply every word of e moves to the nodes of the newest complete level L, in index order and in chunks of
+	`deepen_chunk` nodes, and look the results up in the ball (engine rk_sdeepen_nodes).  The first chunk with a hit ends the
+	search: the lowest node of it that has a hit, that node's lowest word, then the descent; `action_queue` is that path, of the
+	optimal length L + e + radius, and does not depend on `pops`, the chunk or the launch cap.  Afterwards `deepened` is e (0: the
+	pool sufficed), `probes` the probes issued, `capacity_exhausted` stays True, len(agent) and `arrays()` are still the pool
+	(its partial next level included), and there is no meeting.  The time limit covers both phases.
 	"""
 	_entries = "rk_ssearch"
 	_ball_type = DeviceSymBall
+	deepen_chunk = None                     # frontier nodes per chunk (None: as many as one launch takes with all their words)
 
-	def __init__(self, ball: DeviceSymBall, pops: int = 16_384, capacity: int = None, max_capacity: int = None, poll: int = 8):
+	def __init__(self, ball: DeviceSymBall, pops: int = 16_384, capacity: int = None, max_capacity: int = None, poll: int = 8, deepen: int = 0):
 		super().__init__(ball, pops, capacity, max_capacity, poll)
+		self.deepen = eng.int_in("deepen", deepen, 0, DeviceSymBall.MAX_EXTRA)
+		self.deepened = 0
+		self.probes = 0
+
+	def _grow(self, h) -> bool:
+		if not self.deepen or self._h_cap < self.max_capacity:
+			return super()._grow(h)                              # (a growth the device refuses raises, with or without `deepen`)
+		self.capacity_exhausted = True                           # no warning yet: the search goes on
+		return False
+
+	def _fewer_pops(self, h, pops: int) -> int:
+		fit = (self._h_cap - self._n) // 12                      # pops the pool still takes whatever they find
+		if not self.deepen or fit < 1:
+			return 0
+		fewer = min(fit, max(1, pops // 2))
+		_ffi.check(_ffi.lib().rk_sdeepen_set_pops(h, fewer, _ffi.stream_ptr()))
+		return fewer
+
+	def _pool_full(self, h, t0: float, time_limit: float) -> bool:
+		if not self.deepen:
+			return False
+		end = self._deepen_search(h, t0, time_limit)
+		if end == "none":
+			eng.pool_exhausted(self, self._h_cap, f"is full and {self.deepen} more moves from its newest complete level reach no state of the ball")
+		return end == "hit"                                      # ("time": the limit ran out, as it may in the pool phase)
+
+	@no_grad
+	def search(self, state: np.ndarray, time_limit: float = None, max_states: int = None) -> bool:
+		self.deepened, self.probes = 0, 0
+		return super().search(state, time_limit, max_states)
+
+	def _deepen_search(self, h, t0: float, time_limit: float) -> str:
+		"""Rounds 1 .. `deepen` from the newest complete level of the pool: "hit" with `action_queue` and `deepened` set at the first
+		hit, "none" when no round has one, "time" when `time_limit` seconds since `t0` are over (looked at after every launch)."""
+		lib, stream = _ffi.lib(), _ffi.stream_ptr()
+		level = (C.c_longlong * 2)()
+		_ffi.check(lib.rk_sdeepen_frontier(h, level, stream))
+		lo, hi = int(level[0]), int(level[1])
+		cap = self.ball._launch_cap()
+		chunk = eng.int_in("deepen_chunk", self.deepen_chunk, 1, none_ok=True, what="a positive integer or None")
+		for e in range(1, self.deepen + 1):
+			words = (12 if lo == 1 else 11) * 11 ** (e - 1)                 # (node 1 has no last move; it is a level of its own)
+			per = min(chunk or max(1, cap // words), cap)
+			for at in range(lo, hi + 1, per):
+				cnt = min(per, hi + 1 - at)
+				best = torch.full((cnt,), -1, dtype=torch.int32, device=gpu)    # 0xFFFFFFFF: no hit
+				step = max(1, min(words, cap // cnt))
+				for first in range(0, words, step):
+					count = min(step, words - first)
+					_ffi.check(lib.rk_sdeepen_nodes(h, e, at, cnt, first, count, best.data_ptr(), stream))
+					self.probes += cnt * count
+					torch.cuda.current_stream().synchronize()
+					if time.perf_counter() - t0 >= time_limit:
+						return "time"
+				rank = best.cpu().numpy().view(np.uint32)
+				hit = np.nonzero(rank != 0xFFFFFFFF)[0]
+				if len(hit):                                                 # the lowest node of the chunk with a hit, its lowest word
+					k = int(hit[0])
+					self.action_queue = eng.read_path(lib.rk_sdeepen_path, h, at + k, e, int(rank[k]))
+					self.deepened = e
+					return "hit"
+		return "none"
 
 	@property
 	def meeting_node(self):
