@@ -19,10 +19,10 @@
 // 0 .. L with an edge i -> j of weight d(i, j) for every window j - i <= W that the ball holds, and its best rewrite a shortest path:
 //   k_shorten_windows   a WAVE per (queue, i), the lane is the offset: the window's moves composed by scan_moves in chunks of 64
 //                       with a carried state (rk_cube_kernels.hip: k_apply_sequences_scan), probe_find, d(i, j) as one byte
-//   k_shorten_dp        a workgroup per queue: cost[j] = min cost[i] + w(i, j), the candidates of one j reduced in parallel,
-//                       ties to the largest i; cost in LDS, pred to scratch
-//   k_shorten_emit      a wave per queue: back along pred, then forward; an edge with d < j - i is replaced by the ball's word
-//                       for X(i, j) (found again by one scan and one probe), the stored actions from node 1 down to the node
+//   k_shorten_dp        (rk_shorten_dev.h, rk_sym.hip launches the same) a workgroup per queue: cost[j] = min cost[i] + w(i, j),
+//                       the candidates of one j reduced in parallel, ties to the largest i; cost in LDS, pred to scratch
+//   k_shorten_emit      a wave per queue (shorten_emit): back along pred, then forward; an edge with d < j - i is replaced by the
+//                       ball's word for X(i, j) (found again by one scan and one probe), the stored actions from node 1 down to the node
 // Nothing of the ball is written.
 //
 // The search (rk_bsearch_*) is rk_bfs.hip's protocol from the start (node 1 of a pool of its own) with rk_bibfs.hip's level
@@ -34,9 +34,12 @@
 // table is sized to the own pool; a reset clears it and never the ball's.
 //
 // The batch (rk_bsearchb_*) is S such searches in lock-step.  The kernels' bodies are __device__ functions of a FrontierDev; the single
-// engine's kernels pass theirs by value, the batch's (kb_bsearch_*) pick devs[blockIdx.y] from an array in device memory, so an
-// iteration of all slots is the same four launches with S in the grid's second dimension.  Every kind of array is one block sliced
-// per slot.  A slot's pool is fixed: it stops with reason 5 before an iteration that might not fit.
+// engine's kernels pass theirs by value, the batch's pick devs[blockIdx.y] from an array in device memory, so an iteration of all
+// slots is the same four launches with S in the grid's second dimension.  Every kind of array is one block sliced per slot.  A
+// slot's pool is fixed: it stops with reason 5 before an iteration that might not fit.
+// The kernels of this file are the root, the expand and the walk of either form (k_bsearch_*, kb_bsearch_*): what looks at the
+// ball.  The scan, the append, the end, the rehash and the batch's clear do not and are rk_frontier_dev.h's (k_fr_scan,
+// k_fr_append, k_srch_end, k_fr_rehash, kb_srch_*), launched by FrontierPool and FrontierSlots (rk_frontier_host.h).
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <climits>
@@ -48,7 +51,7 @@
 #include "rk_ballbuild_dev.h"
 #include "rk_error.h"
 #include "rk_frontier_dev.h"
-#include "rk_search_host.h"
+#include "rk_frontier_host.h"
 #include "rk_shorten_dev.h"
 
 namespace rk {
@@ -149,8 +152,8 @@ void k_ball_solve(BallView b, const uint32_t *queries, size_t n, int32_t *length
 }
 
 // ---- shortening action queues against the ball ---------------------------------------------------------------------------------
-// (the limits, chunk_states, the DP, the reversal of the pred chain and the argument checks are in rk_shorten_dev.h: rk_sym.hip's
-// rk_sshorten runs the same ones)
+// (the limits, shorten_compose, the DP and its kernel, the emit but for the word of a replaced edge and the argument checks are in
+// rk_shorten_dev.h: rk_sym.hip's rk_sshorten runs the same ones)
 // d(i, j) of every window of queue p that starts at i: wave (p, i), lane = offset inside a chunk of 64 moves.  The byte of window
 // (i, j) is depth[(p * max_len + j - 1) * window + (j - i - 1)]: the row of an END j is contiguous, which is how the DP reads it.
 __global__ __launch_bounds__(256)
@@ -176,86 +179,37 @@ void k_shorten_windows(BallView b, const int8_t *__restrict__ actions, const int
 		const uint32_t a = a_next;
 		a_next = d0 + 64 + lane < moves ? (uint32_t)(uint8_t)row[i + d0 + 64 + lane] : 0xFFu;    // behind the six scan steps
 		uint32_t st[5];
-		chunk_states(s_act, a, lane, nc, s, st);
+		shorten_compose(s_act, a, lane, nc, s, st);
 		if (lane < nc) {
 			const uint32_t e = probe_find(b.table, b.mask, b.states, st);
 			const int k = d0 + lane;                                         // j - i - 1
 			depth[(p * (size_t)max_len + (size_t)(i + k)) * (size_t)window + (size_t)k] = (int8_t)(e ? level_of(b.lstart, e) : -1);
 		}
-		#pragma unroll
-		for (int j = 0; j < 5; j++) s[j] = (uint32_t)__builtin_amdgcn_readlane((int)st[j], nc - 1);   // carries into the next chunk
+		shorten_carry(st, nc, s);                                        // into the next chunk
 	}
 }
 
-// The shortest path 0 -> L of queue blockIdx.x (shorten_dp).
-__global__ __launch_bounds__(SHORTEN_DP_THREADS)
-void k_shorten_dp(const int8_t *__restrict__ actions, const int32_t *__restrict__ len, int max_len, int window,
-                  const int8_t *__restrict__ depth, uint16_t *__restrict__ pred, int32_t *error)
-{
-	shorten_dp(actions, len, max_len, window, depth, pred, error);
-}
-
-// The rewritten queue of queue blockIdx.x: one wave.  Lane 0 turns the pred chain from L into a chain of successors from 0
-// (shorten_successors), then the wave takes the edges in order.  An edge of weight j - i (or a single move outside the ball) is
-// copied; any other is the ball's word for X(i, j), d(i, j) moves.  The output is never longer than the input; every index is
-// checked all the same.
+// The rewritten queue of queue blockIdx.x: one wave (shorten_emit).  The word of a replaced edge is the ball's own: X(i, j) is
+// probed (its level must be the stored d), then the stored actions from the node down to node 1 -- they lead away from solved, so
+// the last one first.  Lane 0 writes.
 __global__ __launch_bounds__(64)
 void k_shorten_emit(BallView b, const int8_t *__restrict__ actions, const int32_t *__restrict__ len, int max_len, int window,
                     const int8_t *__restrict__ depth, const uint16_t *__restrict__ pred, int8_t *__restrict__ out_actions,
                     int32_t *__restrict__ out_len, int32_t *error)
 {
 	__shared__ u32x4 s_act[36];
-	__shared__ uint16_t nxt[SHORTEN_MAX_LEN + 1];
-	__shared__ int s_ok;
-	const size_t p = blockIdx.x;
 	const int lane = threadIdx.x;
 	stage_action_tables(s_act, lane);
-	const int L = shorten_len(len, p, max_len);
-	const int8_t *row = actions + p * (size_t)max_len;
-	int8_t *out = out_actions + p * (size_t)max_len;
-	const uint16_t *pr = pred + p * (size_t)(max_len + 1);
-	bool ok = pr[0] != SHORTEN_KEPT;
-	int pos = 0;
-	if (ok) {
-		ok = shorten_successors(pr, L, window, lane, nxt, &s_ok);
-		for (int i = 0; ok && i < L; ) {
-			const int j = nxt[i], span = j - i;
-			if (span < 1 || span > window || j > L) { ok = false; break; }
-			const int d = depth[(p * (size_t)max_len + (size_t)(j - 1)) * (size_t)window + (size_t)(span - 1)];
-			if (d < 0 || d >= span) {                                        // as short as the ball knows: copied
-				if (pos + span > max_len) { ok = false; break; }
-				for (int k = lane; k < span; k += 64) out[pos + k] = row[i + k];
-				pos += span;
-			} else if (d > 0) {
-				uint32_t s[5] = {SOLVED_DW[0], SOLVED_DW[1], SOLVED_DW[2], SOLVED_DW[3], SOLVED_DW[4]};
-				for (int d0 = 0; d0 < span; d0 += 64) {
-					const int nc = min(64, span - d0);
-					const uint32_t a = lane < nc ? (uint32_t)(uint8_t)row[i + d0 + lane] : 0xFFu;
-					uint32_t st[5];
-					chunk_states(s_act, a, lane, nc, s, st);
-					#pragma unroll
-					for (int q = 0; q < 5; q++) s[q] = (uint32_t)__builtin_amdgcn_readlane((int)st[q], nc - 1);
-				}
-				uint32_t g = probe_find(b.table, b.mask, b.states, s);       // X(i, j): the same in every lane
-				if (g == 0u || level_of(b.lstart, g) != d || d > b.radius || pos + d > max_len) { ok = false; break; }
-				for (int k = d - 1; k >= 0; k--) {                              // the stored actions lead away from solved: the last one first
-					if (g <= 1u || g >= b.cap1) { ok = false; break; }
-					if (lane == 0) out[pos + k] = (int8_t)b.pact[g];
-					g = (uint32_t)b.parent[g];
-				}
-				if (!ok || g != 1u) { ok = false; break; }
-				pos += d;
-			}
-			i = j;
+	shorten_emit(s_act, actions, len, max_len, window, depth, pred, out_actions, out_len, error, [&](const uint32_t x[5], int d, int8_t *at) {
+		uint32_t g = probe_find(b.table, b.mask, b.states, x);
+		if (g == 0u || level_of(b.lstart, g) != d || d > b.radius) return false;
+		for (int k = d - 1; k >= 0; k--) {
+			if (g <= 1u || g >= b.cap1) return false;
+			if (lane == 0) at[k] = (int8_t)b.pact[g];
+			g = (uint32_t)b.parent[g];
 		}
-		if (!ok && lane == 0) *error = RK_ESTATE;                           // an engine error: the queue comes back as it is
-	}
-	if (!ok) {
-		for (int k = lane; k < L; k += 64) out[k] = row[k];
-		pos = L;
-	}
-	for (int k = pos + lane; k < max_len; k += 64) out[k] = -1;
-	if (lane == 0) out_len[p] = pos;
+		return g == 1u;
+	});
 }
 
 // ---- the search from a start towards the ball -------------------------------------------------------------------------------
@@ -270,20 +224,7 @@ __device__ __forceinline__ void bsearch_root(const FrontierDev &d, const BallVie
 	if (tid != 0) return;
 	uint32_t s[5];
 	load5(root, s);
-	#pragma unroll
-	for (int j = 0; j < 5; j++) d.states[5 + j] = s[j];
-	d.parent[1] = 0; d.pact[1] = 0;
-	d.table[hash_state(s) & d.mask] = 1u;
-	d.ctr[F_SIZE] = 1; d.ctr[F_HEAD] = 1; d.ctr[S_HI] = 1;
-	d.ctr[F_BUDGET] = budget;
-	d.ctr[F_WINPOS] = (int32_t)F_NO_WIN;
-	const uint32_t e = probe_find(b.table, b.mask, b.states, s);
-	if (e != 0u) {                                                       // the ball holds the start: its path is the answer, nothing is popped
-		d.ctr[F_WON] = 1; d.ctr[S_MEET] = (int32_t)e;
-		d.ctr[F_STOP] = F_STOP_WON; d.ctr[F_DONE] = 1;
-		return;
-	}
-	srch_next(d);
+	srch_root_store(d, s, budget, probe_find(b.table, b.mask, b.states, s));     // (a start the ball holds: nothing is popped)
 }
 
 // fan-out, the look-up in the ball (read-only), then membership / election in the own table: one thread per child
@@ -302,19 +243,9 @@ __device__ __forceinline__ void bsearch_expand(const FrontierDev &d, const BallV
 	// no state is in both pools (the start is outside the ball and nothing the ball holds is ever stored), so the order of the two
 	// look-ups decides nothing; the ball first, so that a meeting child leaves no claim in the own table
 	const uint32_t m = probe_find(b.table, b.mask, b.states, s);
-	if (m != 0u) {
-		atomicMin(reinterpret_cast<uint32_t *>(&d.ctr[F_WINPOS]), (uint32_t)c);
-		d.slot[c] = TENT | m;                                            // no claim (TENT bit); k_bsearch_end reads the meeting node here
-		return;
-	}
-	uint32_t slot = 0;
-	const uint32_t e = probe_elect(d.table, d.mask, d.states, s, c,
-	                               [&](int c2, uint32_t o[5]) { child_state(d.states, head + c2 / 12, s_act, (uint32_t)(c2 % 12), o); }, &slot);
-	d.slot[c] = e == 0u ? slot : NO_SLOT;
+	if (m != 0u) srch_meet(d, c, m);
+	else srch_claim(d, s_act, head, c, s);
 }
-
-__global__ __launch_bounds__(256)
-void k_bsearch_rehash(FrontierDev d) { fr_rehash(d); }
 
 // The action queue of a won search: the path from the start to the popped parent and the meeting action (none of either when
 // the ball holds the start itself), then the ball's path from the meeting node.  out[0] = length or -1.
@@ -323,16 +254,8 @@ __device__ __forceinline__ void bsearch_walk(const FrontierDev &d, const BallVie
 	out[0] = -1;
 	if (!d.ctr[F_WON]) return;
 	const int p = d.ctr[F_WPARENT];
-	int ls = 0;
-	for (int i = p; p != 0 && i != 1; ls++) {
-		if (i < 1 || (uint32_t)i >= d.cap1 || ls > (int)d.cap1) return;
-		i = d.parent[i];
-	}
-	int i = p;
-	for (int k = ls - 1; k >= 0; k--) {
-		if (k < max_len) out[1 + k] = d.pact[i];
-		i = d.parent[i];
-	}
+	const int ls = p != 0 ? fr_walk_up(d, p, out + 1, max_len, true) : 0;
+	if (ls < 0) return;
 	int len = ls;
 	if (p != 0) {
 		if (len < max_len) out[1 + len] = d.ctr[F_WACT];
@@ -346,19 +269,11 @@ __device__ __forceinline__ void bsearch_walk(const FrontierDev &d, const BallVie
 	out[0] = len;
 }
 
-// ---- the single engine: one search per launch ----
+// ---- the single engine: one search per launch (scan, append, end and rehash: rk_frontier_dev.h's k_fr_*, k_srch_end) ----
 __global__ void k_bsearch_root(FrontierDev d, BallView b, const uint32_t *root, int budget) { bsearch_root(d, b, root, budget); }
 
 __global__ __launch_bounds__(256)
 void k_bsearch_expand(FrontierDev d, BallView b) { bsearch_expand(d, b); }
-
-__global__ __launch_bounds__(ASCAN)
-void k_bsearch_scan(FrontierDev d) { fr_scan(d); }
-
-__global__ __launch_bounds__(256)
-void k_bsearch_append(FrontierDev d) { fr_append(d); }
-
-__global__ void k_bsearch_end(FrontierDev d) { if (threadIdx.x == 0 && blockIdx.x == 0) bsearch_end(d); }
 
 __global__ void k_bsearch_walk(FrontierDev d, BallView b, int32_t *out, int max_len) { if (threadIdx.x == 0 && blockIdx.x == 0) bsearch_walk(d, b, out, max_len); }
 
@@ -366,11 +281,8 @@ __global__ void k_bsearch_walk(FrontierDev d, BallView b, int32_t *out, int max_
 // Every slot is a whole search of its own -- pool, table, counters, batch scratch, look-back words, ticket and epoch --, so a
 // launch reads and writes through devs[blockIdx.y] alone.  A slot that is done, or was never started, has F_NPOP == 0: it leaves
 // at that read, draws no ticket and leaves its epoch alone.  The pool of a slot never grows: the pool-full rule (srch_fit,
-// BS_STOP_FULL) and the clearing of a slot (srch_clear) are rk_frontier_dev.h's, shared with rk_sym.hip's rk_ssearchb_*.
-
-// the named slots' tables and look-back words, zeroed: slot slots[blockIdx.y]
-__global__ __launch_bounds__(256)
-void kb_bsearch_clear(const FrontierDev *devs, const int32_t *slots, int chain_words) { srch_clear(devs[slots[blockIdx.y]], chain_words); }
+// BS_STOP_FULL) and the clear, scan, append and end of all slots (kb_srch_*) are rk_frontier_dev.h's, shared with rk_sym.hip's
+// rk_ssearchb_*.
 
 // row j of roots / budgets starts slot slots[j]
 __global__ void kb_bsearch_root(const FrontierDev *devs, BallView b, const int32_t *slots, const uint32_t *roots, const int32_t *budgets)
@@ -386,31 +298,6 @@ void kb_bsearch_expand(const FrontierDev *devs, BallView b)
 	const FrontierDev d = devs[blockIdx.y];
 	if (blockIdx.x * 256 >= 12 * d.ctr[F_NPOP]) return;                  // done, never started, or a workgroup past the batch
 	bsearch_expand(d, b);
-}
-
-__global__ __launch_bounds__(ASCAN)
-void kb_bsearch_scan(const FrontierDev *devs)
-{
-	const FrontierDev d = devs[blockIdx.y];
-	if (d.ctr[F_NPOP] == 0) return;                                      // (every workgroup of a live slot draws a ticket)
-	fr_scan(d);
-}
-
-__global__ __launch_bounds__(256)
-void kb_bsearch_append(const FrontierDev *devs)
-{
-	const FrontierDev d = devs[blockIdx.y];
-	if (blockIdx.x * 256 >= 12 * d.ctr[F_NPOP]) return;
-	fr_append(d);
-}
-
-__global__ void kb_bsearch_end(const FrontierDev *devs)
-{
-	if (threadIdx.x != 0 || blockIdx.x != 0) return;
-	const FrontierDev d = devs[blockIdx.y];
-	if (d.ctr[F_NPOP] == 0) return;
-	bsearch_end(d);
-	srch_fit(d);
 }
 
 // one thread per slot: row s of `out` (n_slots, 1 + max_len) = length or -1, then the queue
@@ -432,14 +319,10 @@ struct rk_ball : KeptBall {
 	BallView view{};
 };
 
-struct rk_bsearch : FrontierPool {
-	rk_ball *ball = nullptr;
-};
+struct rk_bsearch : FrontierPool, BallReader<rk_ball> {};
 
-// S searches in lock-step: the slots (rk_search_host.h: FrontierSlots) and the ball they all read
-struct rk_bsearchb : FrontierSlots {
-	rk_ball *ball = nullptr;
-};
+// S searches in lock-step: the slots (rk_frontier_host.h: FrontierSlots) and the ball they all read
+struct rk_bsearchb : FrontierSlots, BallReader<rk_ball> {};
 
 namespace {
 
@@ -566,16 +449,14 @@ int rk_bsearch_create(rk_bsearch_t **out, rk_ball_t *ball, size_t capacity, int 
 	if (int e = FrontierPool::check_create("rk_bsearch_create", capacity, pops)) return e;
 	rk_bsearch *h = new rk_bsearch();
 	if (int e = h->alloc(capacity, pops, S_COUNT)) { delete h; return e; }
-	h->ball = ball;
-	ball->attached += 1;
+	h->attach(ball);
 	*out = h;
 	return RK_OK;
 }
 
 int rk_bsearch_destroy(rk_bsearch_t *h)
 {
-	if (h && h->ball) h->ball->attached -= 1;
-	delete h;
+	delete h;                                   // (lets go of the ball: BallReader)
 	return RK_OK;
 }
 
@@ -594,8 +475,7 @@ int rk_bsearch_run(rk_bsearch_t *h, int iterations, void *stream)
 	if (int e = FrontierPool::check_ready(h, "rk_bsearch_run")) return e;
 	hipStream_t st = (hipStream_t)stream;
 	return h->run("rk_bsearch_run", iterations, st,
-	              [&](unsigned grid) { hipLaunchKernelGGL(k_bsearch_expand, dim3(grid), dim3(256), 0, st, h->d, h->ball->view); },
-	              k_bsearch_scan, k_bsearch_append, k_bsearch_end);
+	              [&](unsigned grid) { hipLaunchKernelGGL(k_bsearch_expand, dim3(grid), dim3(256), 0, st, h->d, h->ball->view); });
 }
 
 int rk_bsearch_status(rk_bsearch_t *h, long long *h_status, void *stream)
@@ -610,7 +490,7 @@ int rk_bsearch_status(rk_bsearch_t *h, long long *h_status, void *stream)
 int rk_bsearch_grow(rk_bsearch_t *h, size_t new_capacity, void *stream)
 {
 	if (int e = FrontierPool::check_ready(h, "rk_bsearch_grow")) return e;
-	return h->grow("rk_bsearch_grow", new_capacity, k_bsearch_rehash, (hipStream_t)stream);
+	return h->grow("rk_bsearch_grow", new_capacity, (hipStream_t)stream);
 }
 
 long long rk_bsearch_size(const rk_bsearch_t *h) { return FrontierPool::size(h); }
@@ -626,15 +506,13 @@ int rk_bsearchb_create(rk_bsearchb_t **out, rk_ball_t *ball, int n_slots, size_t
 	if (int e = FrontierSlots::check_create("rk_bsearchb_create", out, ball, n_slots, capacity_per_slot, pops)) return e;
 	rk_bsearchb *h = new rk_bsearchb();
 	if (int e = h->alloc("rk_bsearchb_create", n_slots, capacity_per_slot, pops, [] { return RK_OK; })) { delete h; return e; }
-	h->ball = ball;
-	ball->attached += 1;
+	h->attach(ball);
 	*out = h;
 	return RK_OK;
 }
 
 int rk_bsearchb_destroy(rk_bsearchb_t *h)
 {
-	if (h && h->ball) h->ball->attached -= 1;
 	delete h;
 	return RK_OK;
 }
@@ -643,7 +521,7 @@ int rk_bsearchb_reset(rk_bsearchb_t *h, int n, const int32_t *slots, const int8_
 {
 	if (!h) return fail(RK_EINVAL, "rk_bsearchb_reset: null engine");
 	hipStream_t st = (hipStream_t)stream;
-	return h->reset("rk_bsearchb_reset", h->ball->built, n, slots, h_start_states, max_states, st, kb_bsearch_clear, [&] {
+	return h->reset("rk_bsearchb_reset", h->ball->built, n, slots, h_start_states, max_states, st, [&] {
 		hipLaunchKernelGGL(kb_bsearch_root, dim3(1, n), dim3(64), 0, st, h->devs, h->ball->view, h->slots_dev, h->roots_dev, h->budgets_dev);
 	});
 }
@@ -651,19 +529,9 @@ int rk_bsearchb_reset(rk_bsearchb_t *h, int n, const int32_t *slots, const int8_
 int rk_bsearchb_run(rk_bsearchb_t *h, int iterations, void *stream)
 {
 	if (!h) return fail(RK_EINVAL, "rk_bsearchb_run: null engine");
-	if (int e = h->check_run("rk_bsearchb_run", h->ball->built, iterations)) return e;
 	hipStream_t st = (hipStream_t)stream;
-	const BallView &b = h->ball->view;
-	const size_t K = (size_t)12 * h->pops;
-	const dim3 grid(blocks(K), h->n_slots), grid_scan(blocks(K, ASCAN), h->n_slots);
-	for (int it = 0; it < iterations; it++) {
-		hipLaunchKernelGGL(kb_bsearch_expand, grid, dim3(256), 0, st, h->devs, b);
-		hipLaunchKernelGGL(kb_bsearch_scan, grid_scan, dim3(ASCAN), 0, st, h->devs);
-		hipLaunchKernelGGL(kb_bsearch_append, grid, dim3(256), 0, st, h->devs);
-		hipLaunchKernelGGL(kb_bsearch_end, dim3(1, h->n_slots), dim3(64), 0, st, h->devs);
-	}
-	RK_HIP(hipGetLastError());
-	return RK_OK;
+	return h->run("rk_bsearchb_run", h->ball->built, iterations, st,
+	              [&](dim3 grid) { hipLaunchKernelGGL(kb_bsearch_expand, grid, dim3(256), 0, st, h->devs, h->ball->view); });
 }
 
 int rk_bsearchb_status(rk_bsearchb_t *h, long long *h_status, void *stream)

@@ -6,7 +6,7 @@
 // scan, append, end, none of which synchronises with the host.  There is no goal test, budget or cut (none of the frontier
 // pool's words for them, rk_frontier_dev.h): every claim of a batch is appended, so between iterations -- and once the build is
 // over -- no table slot is tentative.  A ball keeps what makes it different: the check of a closed level, where the state of
-// batch position c comes from, and what it stores per node beside the state.  The host side is KeptBall (rk_search_host.h).
+// batch position c comes from, and what it stores per node beside the state.  The host side is KeptBall (rk_frontier_host.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -6,7 +6,7 @@
 //   table   uint32 (T)       open-addressing hash table state -> index, T = pow2 >= 2C, tentative claims TENT | position
 //   ctr     int32[16]        size, head, done, won, winning parent / action, stop reason, iterations, error, ...
 // The pool, its counters and the scan, append, end and rehash launches are the frontier pool's (rk_frontier_dev.h, FrontierPool
-// in rk_search_host.h); this file holds what is BFS's own: the stopping rule (bfs_next), the root, the goal test and membership
+// in rk_frontier_host.h); this file holds what is BFS's own: the stopping rule (bfs_next), the root, the goal test and membership
 // rule (k_bfs_expand) and the walk.
 // The FIFO queue is the pool itself in index order: the reference appends every new state to the queue as it stores it
 // (:120-121) and pops from the front (:106), so the queue is always the index range head .. size.
@@ -15,8 +15,8 @@
 // are sized for `pops`) and is four launches, none of which synchronises with the host:
 //   k_bfs_expand   one thread per child, parent-major / action-minor in pop order (:108-110): the move, the goal flag, the
 //                  membership test against the table and the in-batch first-occurrence election (probe_elect)
-//   k_bfs_scan     first-occurrence flags and their exclusive prefix over the batch (tickets + look-back, one launch)
-//   k_bfs_append   the cut (below) and the order-preserving append: new states get indices size + 1 ... in batch order
+//   k_fr_scan      first-occurrence flags and their exclusive prefix over the batch (tickets + look-back, one launch)
+//   k_fr_append    the cut (below) and the order-preserving append: new states get indices size + 1 ... in batch order
 //                  with their parent and action (:120-121), their tentative claims become those indices
 //   k_bfs_end      one thread: where the cut fell, the new size and head, the done flags, the next P
 // The reference checks `len(self) < max_states` before EVERY pop (:105) and returns a solved child BEFORE storing it
@@ -30,7 +30,7 @@
 // before every pop: a time-limited run does not stop at the reference's state.  The pool is never what cuts an iteration:
 // the host grows it (rk_bfs_grow) before an iteration whose children might not fit (size + 12 P > C); should one be launched
 // anyway, it is skipped and reported as an error.  A search stopped by its budget goes on after rk_bfs_set_budget with a larger
-// one: that entry first rebuilds the table from the pool (k_bfs_rehash), which drops the claims the cut left behind.
+// one: that entry first rebuilds the table from the pool (k_fr_rehash), which drops the claims the cut left behind.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <climits>
@@ -41,7 +41,7 @@
 #include "rk_device.h"
 #include "rk_error.h"
 #include "rk_frontier_dev.h"
-#include "rk_search_host.h"
+#include "rk_frontier_host.h"
 
 namespace rk {
 
@@ -107,22 +107,12 @@ void k_bfs_expand(FrontierDev d)
 	d.slot[c] = e == 0u ? slot : NO_SLOT;
 }
 
-__global__ __launch_bounds__(ASCAN)
-void k_bfs_scan(FrontierDev d) { fr_scan(d); }
-
-// the winning child is the first solved one: returned before it is stored                        agents.py:105, :111-121
-__global__ __launch_bounds__(256)
-void k_bfs_append(FrontierDev d) { fr_append(d); }
-
 // neither a meeting node nor a popped count: status word 4 is the head
 __global__ void k_bfs_end(FrontierDev d)
 {
 	if (threadIdx.x != 0 || blockIdx.x != 0) return;
 	fr_end<F_UNRECORDED, F_UNRECORDED>(d, [](const FrontierDev &x) { bfs_next(x); });
 }
-
-__global__ __launch_bounds__(256)
-void k_bfs_rehash(FrontierDev d) { fr_rehash(d); }
 
 // the action queue of a won search: the path to the winner's parent, then the winner's action (agents.py:114-117).
 // out[0] = length or -1 (no win, broken chain), then the actions root -> winner.
@@ -185,7 +175,7 @@ int rk_bfs_set_budget(rk_bfs_t *h, long long max_states, void *stream)
 	if (int e = h->read_ctr(c, st)) return e;
 	// A budget stop inside a batch leaves the tentative claims (TENT | position) of the first occurrences at or after the cut in
 	// the table.  A search that goes on would take them for claims of ITS batch positions: rebuild the table from the pool first.
-	if (c[F_STOP] == F_STOP_BUDGET) RK_HIP(FrontierPool::rebuild_table(h->d, (size_t)c[F_SIZE] + 1, k_bfs_rehash, st));
+	if (c[F_STOP] == F_STOP_BUDGET) RK_HIP(FrontierPool::rebuild_table(h->d, (size_t)c[F_SIZE] + 1, st));
 	hipLaunchKernelGGL(k_bfs_set_budget, dim3(1), dim3(64), 0, st, h->d, budget_of(max_states));
 	RK_HIP(hipGetLastError());
 	return RK_OK;
@@ -195,8 +185,10 @@ int rk_bfs_run(rk_bfs_t *h, int iterations, void *stream)
 {
 	if (int e = FrontierPool::check_ready(h, "rk_bfs_run")) return e;
 	hipStream_t st = (hipStream_t)stream;
+	// the append is the shared one: the winning child is the first solved one and is returned before it is stored (agents.py:105,
+	// :111-121), which is fr_append's cut at F_WINPOS
 	return h->run("rk_bfs_run", iterations, st, [&](unsigned grid) { hipLaunchKernelGGL(k_bfs_expand, dim3(grid), dim3(256), 0, st, h->d); },
-	              k_bfs_scan, k_bfs_append, k_bfs_end);
+	              k_fr_append, k_bfs_end);
 }
 
 int rk_bfs_status(rk_bfs_t *h, long long *h_status, void *stream)
@@ -212,7 +204,7 @@ int rk_bfs_status(rk_bfs_t *h, long long *h_status, void *stream)
 int rk_bfs_grow(rk_bfs_t *h, size_t new_capacity, void *stream)
 {
 	if (int e = FrontierPool::check_ready(h, "rk_bfs_grow")) return e;
-	return h->grow("rk_bfs_grow", new_capacity, k_bfs_rehash, (hipStream_t)stream);
+	return h->grow("rk_bfs_grow", new_capacity, (hipStream_t)stream);
 }
 
 long long rk_bfs_size(const rk_bfs_t *h) { return FrontierPool::size(h); }

@@ -19,7 +19,7 @@
 // code, this file holds the level bookkeeping bibfs_next, the root, the membership rule k_bibfs_expand and the walk):
 //   k_bibfs_expand   one thread per child: the move, the look-up in the table; a stored state of the growing side is skipped, one
 //                    of the other side enters its batch position for the meeting, a new state takes part in the election
-//   k_bibfs_scan     first-occurrence flags and their exclusive prefix over the batch
+//   k_fr_scan        first-occurrence flags and their exclusive prefix over the batch
 //   k_bibfs_append   the order-preserving append before the cut, with the side bit
 //   k_bibfs_end      one thread: the cut, the new size and head, the meeting, the end of a level (depth, ranges, next side)
 // The budget is the per-pop rule of rk_bfs: pop j of the batch runs only if size_before + (new states of the pops before j) <
@@ -36,7 +36,7 @@
 #include "rk_device.h"
 #include "rk_error.h"
 #include "rk_frontier_dev.h"
-#include "rk_search_host.h"
+#include "rk_frontier_host.h"
 
 namespace rk {
 
@@ -121,9 +121,6 @@ void k_bibfs_expand(FrontierDev d)
 	d.slot[c] = TENT | e;                                                // no claim (TENT bit); k_bibfs_end reads the meeting node here
 }
 
-__global__ __launch_bounds__(ASCAN)
-void k_bibfs_scan(FrontierDev d) { fr_scan(d); }
-
 // with the side that grows above the action
 __global__ __launch_bounds__(256)
 void k_bibfs_append(FrontierDev d) { fr_append(d, [&] { return (uint32_t)d.ctr[W_SIDE]; }); }
@@ -134,9 +131,6 @@ __global__ void k_bibfs_end(FrontierDev d)
 	if (threadIdx.x != 0 || blockIdx.x != 0) return;
 	fr_end<W_MEET, W_POPPED>(d, [](const FrontierDev &x) { bibfs_next(x); });
 }
-
-__global__ __launch_bounds__(256)
-void k_bibfs_rehash(FrontierDev d) { fr_rehash(d); }
 
 // steps from `node` to the root `root` of its side along the parents, or -1 for a broken chain
 __device__ __forceinline__ int bibfs_chain(const FrontierDev &d, int node, int root)
@@ -215,7 +209,7 @@ int rk_bibfs_run(rk_bibfs_t *h, int iterations, void *stream)
 	if (int e = FrontierPool::check_ready(h, "rk_bibfs_run")) return e;
 	hipStream_t st = (hipStream_t)stream;
 	return h->run("rk_bibfs_run", iterations, st, [&](unsigned grid) { hipLaunchKernelGGL(k_bibfs_expand, dim3(grid), dim3(256), 0, st, h->d); },
-	              k_bibfs_scan, k_bibfs_append, k_bibfs_end);
+	              k_bibfs_append, k_bibfs_end);
 }
 
 int rk_bibfs_status(rk_bibfs_t *h, long long *h_status, void *stream)
@@ -232,7 +226,7 @@ int rk_bibfs_status(rk_bibfs_t *h, long long *h_status, void *stream)
 int rk_bibfs_grow(rk_bibfs_t *h, size_t new_capacity, void *stream)
 {
 	if (int e = FrontierPool::check_ready(h, "rk_bibfs_grow")) return e;
-	return h->grow("rk_bibfs_grow", new_capacity, k_bibfs_rehash, (hipStream_t)stream);
+	return h->grow("rk_bibfs_grow", new_capacity, (hipStream_t)stream);
 }
 
 long long rk_bibfs_size(const rk_bibfs_t *h) { return FrontierPool::size(h); }

@@ -80,11 +80,9 @@ __device__ __forceinline__ void deepen_move(const u32x4 *s_act, int a, const uin
 }
 
 // the items wave, wave + stride, ... of the job (wave and stride in whole waves; all 64 lanes of a wave call it)
-__device__ __forceinline__ void deepen_probe(const SymBallView &b, const DeepenJob &job, const uint32_t *s_sym, const u32x4 *s_act, size_t wave,
-                                             size_t stride)
+__device__ __forceinline__ void deepen_probe(const SymBallView &b, const DeepenJob &job, const SymProbe &c, size_t wave, size_t stride)
 {
-	const int lane = threadIdx.x & 63;
-	const SymLane L = sym_lane(min(lane, N_SYM - 1));
+	const u32x4 *s_act = c.s_act;
 	const int e = job.extra;
 	const uint32_t span = e >= 3 ? DEEPEN_SPAN : 132u;                   // (extra <= 2: every rank is below 132)
 	const unsigned long long end = (unsigned long long)job.word_first + job.word_count;
@@ -141,12 +139,10 @@ __device__ __forceinline__ void deepen_probe(const SymBallView &b, const DeepenJ
 				const unsigned long long r = r0 + dl;
 				if (r < lo) continue;
 				if (r >= hi || r > best) break;
-				uint32_t s2[5], rep[5];
+				uint32_t s2[5];
 				deepen_move(s_act, deepen_action(p1, (int)dl), s1, s2);
-				int sym, count;
-				sym_canonical(s_sym, L, lane, s2, rep, &sym, &count);
-				if (probe_find(b.table, b.mask, b.states, rep) != 0u) {  // (the same in every lane)
-					if (lane == 0) atomicMin(&job.best[i], (uint32_t)r);
+				if (sb_node(b, c, s2) != 0u) {                           // (the same in every lane)
+					if (c.lane == 0) atomicMin(&job.best[i], (uint32_t)r);
 					hit = true;                                          // every later rank of the item is above r
 					break;
 				}

@@ -2,9 +2,11 @@
 // rk_bibfs.hip, rk_ball.hip's search from a start (rk_bsearch_*) and its batch (rk_bsearchb_*), and rk_sym.hip's search that ends
 // at the symmetry-reduced ball (rk_ssearch_*) and its batch (rk_ssearchb_*).  One descriptor, the common counter words, and the
 // launches of an iteration that do not look at what the engine searches for: the scan, the append, the end of an iteration with
-// the cut, and the rehash after a growth.  An engine keeps what makes it different: its counter words behind F_COMMON, its `next` (what follows a pop count
-// change: the end of a level, the done flags, the next P), its root, its expand launch -- the membership rule -- and its walk.
-// The host side is FrontierPool (rk_search_host.h), and FrontierSlots for the two batches.
+// the cut, and the rehash after a growth -- bodies (fr_*, srch_*) and, at the end of this file, the kernels around them (k_fr_scan,
+// k_fr_append, k_fr_rehash, k_srch_end, kb_srch_*).  An engine keeps what makes it different: its counter words behind F_COMMON,
+// its `next` (what follows a pop count change: the end of a level, the done flags, the next P), its root, its expand launch -- the
+// membership rule -- and its walk.
+// The host side is FrontierPool (rk_frontier_host.h), and FrontierSlots for the two batches.
 //
 // An iteration pops the P = F_NPOP nodes head .. head + P - 1 and is expand, scan, append, end; none synchronises with the host.
 // Pop j of the batch runs only if size_before + (new states of the pops before j) < budget, and the winning child is the lowest
@@ -161,7 +163,43 @@ __device__ __forceinline__ void srch_next(const FrontierDev &d)
 	d.ctr[F_NPOP] = stop ? 0 : min(d.pops, hi - head + 1);
 }
 
-__device__ __forceinline__ void bsearch_end(const FrontierDev &d) { fr_end<S_MEET, S_POPPED>(d, [](const FrontierDev &x) { srch_next(x); }); }
+__device__ __forceinline__ void srch_end(const FrontierDev &d) { fr_end<S_MEET, S_POPPED>(d, [](const FrontierDev &x) { srch_next(x); }); }
+
+// What a root launch stores once it knows e, the ball's node of the start (0: the ball does not hold it): node 1 = the start s,
+// the counters, and either the win without a pop -- the ball's path from e is the answer -- or the first pop count.  One thread,
+// after the counter block was zeroed.  S_LO is set for both balls: only rk_sdeepen_frontier exports it, no plain-ball entry does.
+__device__ __forceinline__ void srch_root_store(const FrontierDev &d, const uint32_t s[5], int budget, uint32_t e)
+{
+	#pragma unroll
+	for (int j = 0; j < 5; j++) d.states[5 + j] = s[j];
+	d.parent[1] = 0; d.pact[1] = 0;
+	d.table[hash_state(s) & d.mask] = 1u;
+	d.ctr[F_SIZE] = 1; d.ctr[F_HEAD] = 1; d.ctr[S_HI] = 1; d.ctr[S_LO] = 1;
+	d.ctr[F_BUDGET] = budget;
+	d.ctr[F_WINPOS] = (int32_t)F_NO_WIN;
+	if (e != 0u) {
+		d.ctr[F_WON] = 1; d.ctr[S_MEET] = (int32_t)e;
+		d.ctr[F_STOP] = F_STOP_WON; d.ctr[F_DONE] = 1;
+		return;
+	}
+	srch_next(d);
+}
+
+// child c of the batch is node m of the ball: the meeting.  The lowest batch position wins; no claim in the own table.
+__device__ __forceinline__ void srch_meet(const FrontierDev &d, int c, uint32_t m)
+{
+	atomicMin(reinterpret_cast<uint32_t *>(&d.ctr[F_WINPOS]), (uint32_t)c);
+	d.slot[c] = TENT | m;                                                // no claim (TENT bit); fr_end reads the meeting node here
+}
+
+// child c, state s, is not in the ball: membership / election in the own table (the other children recomputed from their parents)
+__device__ __forceinline__ void srch_claim(const FrontierDev &d, const u32x4 *s_act, int32_t head, int c, const uint32_t s[5])
+{
+	uint32_t slot = 0;
+	const uint32_t e = probe_elect(d.table, d.mask, d.states, s, c,
+	                               [&](int c2, uint32_t o[5]) { child_state(d.states, head + c2 / 12, s_act, (uint32_t)(c2 % 12), o); }, &slot);
+	d.slot[c] = e == 0u ? slot : NO_SLOT;
+}
 
 // ---- such searches in lock-step (rk_bsearchb_*, rk_ssearchb_*): a slot's pool never grows ----
 // A slot whose next iteration might not fit (size + 12 P > capacity) stops BEFORE that iteration with BS_STOP_FULL, so fr_pops()
@@ -189,5 +227,72 @@ __device__ __forceinline__ void srch_clear(const FrontierDev &d, int chain_words
 }
 
 constexpr int FRONTIER_WALK_MAX = 1 << 12;
+
+// The climb from `node` to node 1 along the parents: the steps, or -1 for a broken chain (an index outside the pool, a cycle).
+// The actions go root-first to out[0 .. min(steps, max_len) - 1] where `write` holds (one lane of a wave that walks together);
+// the tag above the action is masked off (it is 0 in every pool but rk_bibfs.hip's).
+__device__ __forceinline__ int fr_walk_up(const FrontierDev &d, int node, int32_t *out, int max_len, bool write)
+{
+	int steps = 0;
+	for (int i = node; i != 1; steps++) {
+		if (i < 1 || (uint32_t)i >= d.cap1 || steps > (int)d.cap1) return -1;
+		i = d.parent[i];
+	}
+	for (int i = node, k = steps - 1; k >= 0; k--) {
+		if (k < max_len && write) out[k] = d.pact[i] & PACT_ACTION;
+		i = d.parent[i];
+	}
+	return steps;
+}
+
+// ---- the kernels that do not look at what an engine searches for ----
+// Internal linkage: this header goes into several .hip files that are linked into one library without relocatable device code,
+// so every file that launches one of these carries its own copy.
+namespace {
+
+__global__ __launch_bounds__(ASCAN)
+void k_fr_scan(FrontierDev d) { fr_scan(d); }
+
+__global__ __launch_bounds__(256)
+void k_fr_append(FrontierDev d) { fr_append(d); }
+
+__global__ __launch_bounds__(256)
+void k_fr_rehash(FrontierDev d) { fr_rehash(d); }
+
+__global__ void k_srch_end(FrontierDev d) { if (threadIdx.x == 0 && blockIdx.x == 0) srch_end(d); }
+
+// The batch: slot blockIdx.y of `devs` per workgroup row.  A slot that is done, or was never started, has F_NPOP == 0: it leaves
+// at that read, draws no ticket and leaves its epoch alone.
+
+// the named slots' tables and look-back words, zeroed: slot slots[blockIdx.y]
+__global__ __launch_bounds__(256)
+void kb_srch_clear(const FrontierDev *devs, const int32_t *slots, int chain_words) { srch_clear(devs[slots[blockIdx.y]], chain_words); }
+
+__global__ __launch_bounds__(ASCAN)
+void kb_srch_scan(const FrontierDev *devs)
+{
+	const FrontierDev d = devs[blockIdx.y];
+	if (d.ctr[F_NPOP] == 0) return;                                      // (every workgroup of a live slot draws a ticket)
+	fr_scan(d);
+}
+
+__global__ __launch_bounds__(256)
+void kb_srch_append(const FrontierDev *devs)
+{
+	const FrontierDev d = devs[blockIdx.y];
+	if (blockIdx.x * 256 >= 12 * d.ctr[F_NPOP]) return;                  // done, never started, or a workgroup past the batch
+	fr_append(d);
+}
+
+__global__ void kb_srch_end(const FrontierDev *devs)
+{
+	if (threadIdx.x != 0 || blockIdx.x != 0) return;
+	const FrontierDev d = devs[blockIdx.y];
+	if (d.ctr[F_NPOP] == 0) return;
+	srch_end(d);
+	srch_fit(d);
+}
+
+}  // namespace
 
 }  // namespace rk

@@ -4,9 +4,10 @@
 //   windows   d(i, j) of every window as one byte, -1 outside the ball: byte (p * max_len + j - 1) * window + (j - i - 1)
 //   dp        a workgroup per queue: cost[j] = min cost[i] + w(i, j), ties to the largest i; cost in LDS, pred to scratch
 //   emit      a wave per queue: back along pred, then forward; an edge with d < j - i is replaced by the ball's word for X(i, j)
-// Nothing here looks at a ball: the limits, the composition of a chunk of 64 moves (chunk_states), the whole DP (shorten_dp),
-// the reversal of the pred chain at the top of the emit (shorten_successors), the scratch layout and the host's argument checks
-// (shorten_check).  A ball keeps what makes it different: how d(i, j) is looked up -- rk_ball.hip probes the raw state,
+// Nothing here looks at a ball: the limits, the composition of a chunk of 64 moves onto a carried state (shorten_compose, shorten_carry), the
+// DP (shorten_dp, and its kernel k_shorten_dp), the emit but for the word of a replaced edge (shorten_emit over shorten_successors,
+// the reversal of the pred chain), the scratch layout and the host's argument checks (shorten_check).  A ball keeps what makes it
+// different: how d(i, j) is looked up -- rk_ball.hip probes the raw state,
 // rk_sym.hip its canonical representative -- and which word a replaced edge gets: the stored actions along the parents there,
 // the inverse of the descent here.
 #pragma once
@@ -29,10 +30,12 @@ __device__ __forceinline__ int shorten_len(const int32_t *len, size_t p, int max
 	return L < 0 ? 0 : L > max_len ? max_len : L;
 }
 
-// One chunk of up to 64 consecutive moves, one per lane (`a`; lanes >= n hold none): st = the state after the moves of lanes
-// 0 .. lane applied to s.  An action outside 0..11 indexes no table (it counts as action 0; its queue is never rewritten).
-// All 64 lanes call it.
-__device__ __forceinline__ void chunk_states(const u32x4 *s_act, uint32_t a, int lane, int n, const uint32_t s[5], uint32_t st[5])
+// One chunk of up to 64 consecutive moves, one per lane (`a`; lanes >= n hold none), applied to the carried state s: st = the
+// state after the moves of lanes 0 .. lane.  An action outside 0..11 indexes no table (it counts as action 0; its queue is never
+// rewritten).  All 64 lanes call it.  shorten_carry then moves s on to the state after all n (lane n - 1's st, the same in every
+// lane) for the next chunk.  The two are apart because the windows kernels probe st in between: carried first, the five scalars
+// of s would live across the probes.
+__device__ __forceinline__ void shorten_compose(const u32x4 *s_act, uint32_t a, int lane, int n, const uint32_t s[5], uint32_t st[5])
 {
 	uint32_t X[12];
 	if (lane < n) load_action_table(s_act, a < 12u ? a : 0u, X);
@@ -41,6 +44,12 @@ __device__ __forceinline__ void chunk_states(const u32x4 *s_act, uint32_t a, int
 	#pragma unroll
 	for (int j = 0; j < 5; j++) st[j] = s[j];
 	move5(st, X);
+}
+
+__device__ __forceinline__ void shorten_carry(const uint32_t st[5], int n, uint32_t s[5])
+{
+	#pragma unroll
+	for (int j = 0; j < 5; j++) s[j] = (uint32_t)__builtin_amdgcn_readlane((int)st[j], n - 1);
 }
 
 // The shortest path 0 -> L of queue blockIdx.x, the whole body of a DP kernel of SHORTEN_DP_THREADS threads.  key = cost << 12 |
@@ -87,6 +96,16 @@ __device__ __forceinline__ void shorten_dp(const int8_t *__restrict__ actions, c
 	}
 }
 
+// The DP kernel of both balls (internal linkage: this header goes into two .hip files of one library).
+namespace {
+__global__ __launch_bounds__(SHORTEN_DP_THREADS)
+void k_shorten_dp(const int8_t *__restrict__ actions, const int32_t *__restrict__ len, int max_len, int window,
+                  const int8_t *__restrict__ depth, uint16_t *__restrict__ pred, int32_t *error)
+{
+	shorten_dp(actions, len, max_len, window, depth, pred, error);
+}
+}  // namespace
+
 // The top of an emit kernel of ONE wave: the pred chain of a queue of L moves, from L back to 0, turned into a chain of successors
 // from 0 in nxt (LDS, SHORTEN_MAX_LEN + 1 entries; s_ok: one LDS word).  False when the chain is not one the DP can have written
 // (never: it wrote pred[j] in j - window .. j - 1).  All 64 lanes call it and get the same answer.
@@ -107,6 +126,60 @@ __device__ __forceinline__ bool shorten_successors(const uint16_t *__restrict__ 
 	}
 	__syncthreads();
 	return *s_ok != 0;
+}
+
+// The rewritten queue of queue blockIdx.x, the body of an emit kernel of ONE wave that has staged s_act.  Lane 0 turns the pred
+// chain from L into a chain of successors from 0 (shorten_successors; its barriers are behind the kernel's staging as well), then
+// the wave takes the edges in order.  An edge of weight j - i (or a single move outside the ball) is copied.  Any other is
+// replaced: X(i, j) is composed again and word(x, d, at) writes the ball's d moves for x = X(i, j) to at[0 .. d - 1] -- they fit
+// -- and says whether it could; x is the same in every lane and all 64 lanes call it.  A word that fails or an index out of range
+// is RK_ESTATE and the queue comes back as it is.  The output is never longer than the input; every index is checked all the same.
+template <typename Word>
+__device__ __forceinline__ void shorten_emit(const u32x4 *s_act, const int8_t *__restrict__ actions, const int32_t *__restrict__ len, int max_len,
+                                             int window, const int8_t *__restrict__ depth, const uint16_t *__restrict__ pred,
+                                             int8_t *__restrict__ out_actions, int32_t *__restrict__ out_len, int32_t *error, Word &&word)
+{
+	__shared__ uint16_t nxt[SHORTEN_MAX_LEN + 1];
+	__shared__ int s_ok;
+	const size_t p = blockIdx.x;
+	const int lane = threadIdx.x;
+	const int L = shorten_len(len, p, max_len);
+	const int8_t *row = actions + p * (size_t)max_len;
+	int8_t *out = out_actions + p * (size_t)max_len;
+	const uint16_t *pr = pred + p * (size_t)(max_len + 1);
+	bool ok = pr[0] != SHORTEN_KEPT;
+	int pos = 0;
+	if (ok) {
+		ok = shorten_successors(pr, L, window, lane, nxt, &s_ok);
+		for (int i = 0; ok && i < L; ) {
+			const int j = nxt[i], span = j - i;
+			if (span < 1 || span > window || j > L) { ok = false; break; }
+			const int d = depth[(p * (size_t)max_len + (size_t)(j - 1)) * (size_t)window + (size_t)(span - 1)];
+			if (d < 0 || d >= span) {                                        // as short as the ball knows: copied
+				if (pos + span > max_len) { ok = false; break; }
+				for (int k = lane; k < span; k += 64) out[pos + k] = row[i + k];
+				pos += span;
+			} else if (d > 0) {
+				uint32_t x[5] = {SOLVED_DW[0], SOLVED_DW[1], SOLVED_DW[2], SOLVED_DW[3], SOLVED_DW[4]};
+				for (int d0 = 0; d0 < span; d0 += 64) {
+					const int nc = min(64, span - d0);
+					uint32_t st[5];
+					shorten_compose(s_act, lane < nc ? (uint32_t)(uint8_t)row[i + d0 + lane] : 0xFFu, lane, nc, x, st);
+					shorten_carry(st, nc, x);
+				}
+				if (pos + d > max_len || !word(x, d, out + pos)) { ok = false; break; }
+				pos += d;
+			}
+			i = j;
+		}
+		if (!ok && lane == 0) *error = RK_ESTATE;                           // an engine error: the queue comes back as it is
+	}
+	if (!ok) {
+		for (int k = lane; k < L; k += 64) out[k] = row[k];
+		pos = L;
+	}
+	for (int k = pos + lane; k < max_len; k += 64) out[k] = -1;
+	if (lane == 0) out_len[p] = pos;
 }
 
 // ---- the host side ---------------------------------------------------------------------------------------------------------

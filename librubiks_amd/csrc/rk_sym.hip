@@ -5,7 +5,8 @@
 // ball of rk_ball.hip in the same memory.  It keeps no parent and no action either: a shortest solution is found by descent.
 //
 // Canonicalisation (rk_sym_dev.h) is a WAVE per state: lane = symmetry, 48 of 64 lanes live, the tables staged in LDS once per
-// workgroup, the minimum of the 48 conjugates taken across the wave.
+// workgroup, the minimum of the 48 conjugates taken across the wave.  A kernel that asks the ball about states declares its LDS,
+// makes one SymProbe (sym_probe: the staging, the barrier, the lane's symmetry) and asks sb_node / sb_level / sb_descend.
 //   k_sym_canonical   waves stride over the states: representative, lowest symmetry that gives it, orbit size
 //   k_sym_conjugate   one given symmetry, a thread per state (every lane reads the same table rows)
 //
@@ -39,7 +40,7 @@
 //   k_ss_probe    a wave per child: fan-out, canonical form, read-only probe of the ball  -> hit (12 P): the ball's node or 0
 //   k_ss_expand   a thread per child: hit != 0 is a meeting (atomicMin on the win position, no claim), else membership / election
 //                 in the own table on the raw child
-//   k_ss_scan, k_ss_append, k_ss_end   fr_scan, fr_append, bsearch_end; S_MEET is the node in THIS ball
+//   k_fr_scan, k_fr_append, k_srch_end, k_fr_rehash   rk_frontier_dev.h's, the plain search's too; S_MEET is the node in THIS ball
 //   k_ss_walk     one wave: the own path and the meeting action, then the descent from the meeting state (sb_descend)
 //
 // The batch (rk_ssearchb_*) is S such searches in lock-step, as rk_ball.hip's rk_bsearchb_* is of rk_bsearch_*.  The bodies of the root,
@@ -49,13 +50,14 @@
 // scratch, look-back words and 12 P words of `hit` --; all slots read one ball.
 //   kb_ss_probe   grid (k_ss_probe's x, S): a workgroup whose first child is past 12 * F_NPOP of its slot -- done, never started, a
 //                 short batch -- returns BEFORE it stages the tables; writes nothing but the slot's hit
-//   kb_ss_expand, kb_ss_scan, kb_ss_append, kb_ss_end   ssearch_expand, fr_scan, fr_append, bsearch_end behind kb_bsearch_*'s early
-//                 exits (a slot with F_NPOP == 0 draws no ticket and leaves its epoch alone); srch_fit follows the end
-//   kb_ss_root    one wave per named slot, then srch_fit; kb_ss_clear zeroes the named slots' tables and look-back words first
+//   kb_ss_expand  ssearch_expand behind kb_bsearch_expand's early exit
+//   kb_srch_scan, kb_srch_append, kb_srch_end   rk_frontier_dev.h's, the plain batch's too: fr_scan, fr_append, srch_end behind the
+//                 early exits (a slot with F_NPOP == 0 draws no ticket and leaves its epoch alone); srch_fit follows the end
+//   kb_ss_root    one wave per named slot, then srch_fit; kb_srch_clear zeroes the named slots' tables and look-back words first
 //   kb_ss_walk    one wave per slot (the descent needs lane = symmetry) into row s of (S, 1 + max_len)
 // A slot's pool is fixed: it stops with reason 5 before an iteration that might not fit (rk_frontier_dev.h: srch_fit).  The host
-// side -- the slot block, the reset's checks, the status fetch, the paths buffer, the export -- is FrontierSlots (rk_search_host.h),
-// shared with rk_bsearchb; this engine adds the hit block.
+// side -- the slot block, the reset's checks, the iteration loop, the status fetch, the paths buffer, the export -- is FrontierSlots
+// (rk_frontier_host.h), shared with rk_bsearchb; this engine adds the hit block and the probe launch.
 //
 // Shortening (rk_sshorten) is rk_ball.hip's rk_bshorten -- the same contract, scratch, DP and copy rule (rk_shorten_dev.h) -- with
 // d(i, j) = the depth of the REPRESENTATIVE of X(i, j), which is the plain ball's d(i, j) at the same radius, so the lengths are
@@ -63,8 +65,9 @@
 // i.e. rk_symball_solve's word reversed with every action ^ 1, which may differ from the plain ball's word of the same length.
 //   k_ss_windows  a persistent grid, waves stride over the (queue, i) pairs, the tables staged once per workgroup: the windows
 //                 composed with lane = offset, then one canonical form (lane = symmetry) and one probe per window
-//   k_ss_dp       shorten_dp
-//   k_ss_emit     a wave per queue: a replaced edge is composed again, canonicalised, probed, descended and written inverted
+//   k_shorten_dp  rk_shorten_dev.h's, the plain ball's too
+//   k_ss_emit     a wave per queue (shorten_emit): a replaced edge is composed again, canonicalised, probed, descended and written
+//                 inverted
 // Three launches; nothing of the ball is written.
 //
 // Deepening (rk_sdeepen, rk_sdeepen_*) goes on where memory ends: short words applied to a state, each result canonicalised
@@ -84,7 +87,7 @@
 #include "rk_device.h"
 #include "rk_error.h"
 #include "rk_search_dev.h"
-#include "rk_search_host.h"
+#include "rk_frontier_host.h"
 #include "rk_shorten_dev.h"
 #include "rk_sym_dev.h"
 
@@ -118,18 +121,15 @@ void k_sb_canon(SymBallDev d)
 	__shared__ u32x4 s_act[36];
 	const int K = 12 * d.ctr[BB_NPOP];
 	if ((int)blockIdx.x * 4 >= K) return;                                // done, or a workgroup past the batch: nothing staged
-	sym_stage(s_sym, threadIdx.x, 256);
-	stage_action_tables(s_act, threadIdx.x);
-	__syncthreads();
-	const int lane = threadIdx.x & 63;
-	const SymLane L = sym_lane(min(lane, N_SYM - 1));
+	const SymProbe sp = sym_probe(s_sym, 256, s_act);
+	const int lane = sp.lane;
 	const int32_t head = d.ctr[BB_HEAD];
 	for (int c = blockIdx.x * 4 + (threadIdx.x >> 6); c < K; c += gridDim.x * 4) {       // (whole waves)
 		const int i = c / 12, a = c - 12 * i;
 		uint32_t x[5], rep[5];
 		child_state(d.states, head + i, s_act, (uint32_t)a, x);
 		int sym, count;
-		sym_canonical(s_sym, L, lane, x, rep, &sym, &count);
+		sym_canonical(s_sym, sp.L, lane, x, rep, &sym, &count);
 		if (lane < 5) d.cstate[(size_t)c * 5 + lane] = dword_of(rep, lane);
 		if (lane == 5) d.corbit[c] = (uint8_t)(N_SYM / count);
 	}
@@ -167,17 +167,12 @@ __global__ __launch_bounds__(256)
 void k_sb_depth(SymBallView b, const uint32_t *queries, size_t n, int32_t *depth)
 {
 	__shared__ uint32_t s_sym[SYM_LDS_DWORDS];
-	sym_stage(s_sym, threadIdx.x, 256);
-	__syncthreads();
-	const int lane = threadIdx.x & 63;
-	const SymLane L = sym_lane(min(lane, N_SYM - 1));
+	const SymProbe sp = sym_probe(s_sym, 256);
 	for (size_t q = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6); q < n; q += (size_t)gridDim.x * 4) {
-		uint32_t x[5], rep[5];
+		uint32_t x[5];
 		load5(queries + q * 5, x);
-		int sym, count;
-		sym_canonical(s_sym, L, lane, x, rep, &sym, &count);
-		const uint32_t e = probe_find(b.table, b.mask, b.states, rep);
-		if (lane == 0) depth[q] = e ? level_of(b.lstart, e) : -1;
+		const int lvl = sb_level(b, sp, x);
+		if (sp.lane == 0) depth[q] = lvl;
 	}
 }
 
@@ -187,21 +182,15 @@ void k_sb_solve(SymBallView b, const uint32_t *queries, size_t n, int32_t *lengt
 {
 	__shared__ uint32_t s_sym[SYM_LDS_DWORDS];
 	__shared__ u32x4 s_act[36];
-	sym_stage(s_sym, threadIdx.x, 256);
-	stage_action_tables(s_act, threadIdx.x);
-	__syncthreads();
-	const int lane = threadIdx.x & 63;
-	const SymLane L = sym_lane(min(lane, N_SYM - 1));
+	const SymProbe sp = sym_probe(s_sym, 256, s_act);
+	const int lane = sp.lane;
 	for (size_t q = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6); q < n; q += (size_t)gridDim.x * 4) {
-		uint32_t x[5], rep[5];
+		uint32_t x[5];
 		load5(queries + q * 5, x);
-		int sym, count;
-		sym_canonical(s_sym, L, lane, x, rep, &sym, &count);
-		const uint32_t e = probe_find(b.table, b.mask, b.states, rep);
 		int8_t *row = actions + q * (size_t)b.radius;
-		const int depth = e ? level_of(b.lstart, e) : -1;
+		const int depth = sb_level(b, sp, x);
 		bool ok;
-		const int len = sb_descend(b, s_sym, s_act, L, lane, x, depth, [&](int k, int a) { if (lane == 0) row[k] = (int8_t)a; }, &ok);
+		const int len = sb_descend(b, sp, x, depth, [&](int k, int a) { if (lane == 0) row[k] = (int8_t)a; }, &ok);
 		if (depth >= 0 && !ok && lane == 0) *error = RK_ESTATE;
 		if (lane == 0) lengths[q] = ok ? len : -1;
 		for (int k = (ok ? len : 0) + lane; k < b.radius; k += 64) row[k] = -1;
@@ -213,7 +202,7 @@ void k_sb_solve(SymBallView b, const uint32_t *queries, size_t n, int32_t *lengt
 // depth[(p * max_len + j - 1) * window + (j - i - 1)].  A persistent grid: every workgroup stages s_act (576 B) and the symmetry
 // tables (23 232 B) ONCE, then its four waves stride over the (queue, i) pairs.  A workgroup per four pairs, as in
 // k_shorten_windows, would stage 23 KB again for a handful of probes -- most pairs of a padded batch have no window at all.
-// Per pair the windows are composed as there: lane = offset, chunk_states in chunks of 64 with the carried state, the next
+// Per pair the windows are composed as there: lane = offset, shorten_compose in chunks of 64 with the carried state, the next
 // chunk's actions loaded ahead.  Then the chunk's states are taken one at a time: lane k's state is broadcast (five v_readlane),
 // canonicalised with lane = symmetry as everywhere in this file (so the table reads bank as rk_sym_dev.h describes), its
 // representative probed once, and lane k keeps the level.  The wave index goes through readfirstlane: the pair, the queue's
@@ -224,11 +213,8 @@ void k_ss_windows(SymBallView b, const int8_t *__restrict__ actions, const int32
 {
 	__shared__ uint32_t s_sym[SYM_LDS_DWORDS];
 	__shared__ u32x4 s_act[36];
-	sym_stage(s_sym, threadIdx.x, 256);
-	stage_action_tables(s_act, threadIdx.x);
-	__syncthreads();
-	const int lane = threadIdx.x & 63;
-	const SymLane SL = sym_lane(min(lane, N_SYM - 1));
+	const SymProbe sp = sym_probe(s_sym, 256, s_act);
+	const int lane = sp.lane;
 	const size_t pairs = n * (size_t)max_len;
 	for (size_t w = (size_t)blockIdx.x * 4 + (size_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); w < pairs; w += (size_t)gridDim.x * 4) {
 		const size_t p = w / (size_t)max_len;
@@ -244,40 +230,29 @@ void k_ss_windows(SymBallView b, const int8_t *__restrict__ actions, const int32
 			const uint32_t a = a_next;
 			a_next = d0 + 64 + lane < moves ? (uint32_t)(uint8_t)row[i + d0 + 64 + lane] : 0xFFu;    // behind the scan and the probes
 			uint32_t st[5];
-			chunk_states(s_act, a, lane, nc, s, st);
+			shorten_compose(s_act, a, lane, nc, s, st);
 			int mine = -1;
 			for (int k = 0; k < nc; k++) {
-				uint32_t x[5], rep[5];
+				uint32_t x[5];
 				#pragma unroll
 				for (int j = 0; j < 5; j++) x[j] = (uint32_t)__builtin_amdgcn_readlane((int)st[j], k);
-				int sym, count;
-				sym_canonical(s_sym, SL, lane, x, rep, &sym, &count);
-				const uint32_t e = probe_find(b.table, b.mask, b.states, rep);
-				const int lvl = e ? level_of(b.lstart, e) : -1;
+				const int lvl = sb_level(b, sp, x);
 				if (lane == k) mine = lvl;
 			}
 			if (lane < nc) {
 				const int k = d0 + lane;                                         // j - i - 1
 				depth[(p * (size_t)max_len + (size_t)(i + k)) * (size_t)window + (size_t)k] = (int8_t)mine;
 			}
-			#pragma unroll
-			for (int j = 0; j < 5; j++) s[j] = (uint32_t)__builtin_amdgcn_readlane((int)st[j], nc - 1);   // carries into the next chunk
+			shorten_carry(st, nc, s);                                        // into the next chunk
 		}
 	}
 }
 
-__global__ __launch_bounds__(SHORTEN_DP_THREADS)
-void k_ss_dp(const int8_t *__restrict__ actions, const int32_t *__restrict__ len, int max_len, int window, const int8_t *__restrict__ depth,
-             uint16_t *__restrict__ pred, int32_t *error)
-{
-	shorten_dp(actions, len, max_len, window, depth, pred, error);
-}
-
-// The rewritten queue of queue blockIdx.x: one wave, as rk_ball.hip's k_shorten_emit but for the word of a replaced edge.  The
-// ball keeps no parents, so X(i, j) is composed again, canonicalised and probed (its level must be the stored d), and the word
-// is the INVERSE of the descent from X(i, j): sb_descend's step k, action a, is written as a ^ 1 at place d - 1 - k, which leads
-// from solved to X(i, j), hence from s_i to s_j.  A failed descent, a level that differs or an index out of range is RK_ESTATE
-// and the queue comes back as it is.  Everything is the same in every lane; lane 0 writes the replaced words.
+// The rewritten queue of queue blockIdx.x: one wave, rk_ball.hip's k_shorten_emit (shorten_emit) but for the word of a replaced
+// edge.  The ball keeps no parents, so X(i, j) is canonicalised and probed (its level must be the stored d), and the word is the
+// INVERSE of the descent from X(i, j): sb_descend's step k, action a, is written as a ^ 1 at place d - 1 - k, which leads from
+// solved to X(i, j), hence from s_i to s_j.  A failed descent or a level that differs is RK_ESTATE and the queue comes back as it
+// is.  Everything is the same in every lane; lane 0 writes the replaced words.
 __global__ __launch_bounds__(64)
 void k_ss_emit(SymBallView b, const int8_t *__restrict__ actions, const int32_t *__restrict__ len, int max_len, int window,
                const int8_t *__restrict__ depth, const uint16_t *__restrict__ pred, int8_t *__restrict__ out_actions,
@@ -285,60 +260,13 @@ void k_ss_emit(SymBallView b, const int8_t *__restrict__ actions, const int32_t 
 {
 	__shared__ uint32_t s_sym[SYM_LDS_DWORDS];
 	__shared__ u32x4 s_act[36];
-	__shared__ uint16_t nxt[SHORTEN_MAX_LEN + 1];
-	__shared__ int s_ok;
-	const size_t p = blockIdx.x;
-	const int lane = threadIdx.x;
-	sym_stage(s_sym, lane, 64);
-	stage_action_tables(s_act, lane);
-	const SymLane SL = sym_lane(min(lane, N_SYM - 1));
-	const int L = shorten_len(len, p, max_len);
-	const int8_t *row = actions + p * (size_t)max_len;
-	int8_t *out = out_actions + p * (size_t)max_len;
-	const uint16_t *pr = pred + p * (size_t)(max_len + 1);
-	bool ok = pr[0] != SHORTEN_KEPT;
-	int pos = 0;
-	if (ok) {
-		ok = shorten_successors(pr, L, window, lane, nxt, &s_ok);            // (its barriers are behind the staging as well)
-		for (int i = 0; ok && i < L; ) {
-			const int j = nxt[i], span = j - i;
-			if (span < 1 || span > window || j > L) { ok = false; break; }
-			const int d = depth[(p * (size_t)max_len + (size_t)(j - 1)) * (size_t)window + (size_t)(span - 1)];
-			if (d < 0 || d >= span) {                                        // as short as the ball knows: copied
-				if (pos + span > max_len) { ok = false; break; }
-				for (int k = lane; k < span; k += 64) out[pos + k] = row[i + k];
-				pos += span;
-			} else if (d > 0) {
-				uint32_t s[5] = {SOLVED_DW[0], SOLVED_DW[1], SOLVED_DW[2], SOLVED_DW[3], SOLVED_DW[4]};
-				for (int d0 = 0; d0 < span; d0 += 64) {
-					const int nc = min(64, span - d0);
-					const uint32_t a = lane < nc ? (uint32_t)(uint8_t)row[i + d0 + lane] : 0xFFu;
-					uint32_t st[5];
-					chunk_states(s_act, a, lane, nc, s, st);
-					#pragma unroll
-					for (int q = 0; q < 5; q++) s[q] = (uint32_t)__builtin_amdgcn_readlane((int)st[q], nc - 1);
-				}
-				uint32_t rep[5];                                             // X(i, j) = s: the same in every lane
-				int sym, count;
-				sym_canonical(s_sym, SL, lane, s, rep, &sym, &count);
-				const uint32_t g = probe_find(b.table, b.mask, b.states, rep);
-				if (g == 0u || level_of(b.lstart, g) != d || d > b.radius || pos + d > max_len) { ok = false; break; }
-				bool down;
-				const int steps = sb_descend(b, s_sym, s_act, SL, lane, s, d, [&](int k, int a) { if (lane == 0) out[pos + d - 1 - k] = (int8_t)(a ^ 1); },
-				                             &down);
-				if (!down || steps != d) { ok = false; break; }
-				pos += d;
-			}
-			i = j;
-		}
-		if (!ok && lane == 0) *error = RK_ESTATE;                           // an engine error: the queue comes back as it is
-	}
-	if (!ok) {
-		for (int k = lane; k < L; k += 64) out[k] = row[k];
-		pos = L;
-	}
-	for (int k = pos + lane; k < max_len; k += 64) out[k] = -1;
-	if (lane == 0) out_len[p] = pos;
+	const SymProbe sp = sym_probe(s_sym, 64, s_act);
+	shorten_emit(s_act, actions, len, max_len, window, depth, pred, out_actions, out_len, error, [&](uint32_t x[5], int d, int8_t *at) {
+		if (sb_level(b, sp, x) != d) return false;
+		bool down;
+		const int steps = sb_descend(b, sp, x, d, [&](int k, int a) { if (sp.lane == 0) at[d - 1 - k] = (int8_t)(a ^ 1); }, &down);
+		return down && steps == d;
+	});
 }
 
 // ---- the search from a start towards the symmetry ball ----------------------------------------------------------------------
@@ -347,30 +275,12 @@ void k_ss_emit(SymBallView b, const int8_t *__restrict__ actions, const int32_t 
 __device__ __forceinline__ void ssearch_root(const FrontierDev &d, const SymBallView &b, const uint32_t *root, int budget)
 {
 	__shared__ uint32_t s_sym[SYM_LDS_DWORDS];
-	const int lane = threadIdx.x;
-	sym_stage(s_sym, lane, 64);
-	if (lane < S_COUNT) d.ctr[lane] = 0;
-	__syncthreads();
-	const SymLane L = sym_lane(min(lane, N_SYM - 1));
-	uint32_t s[5], rep[5];
+	if (threadIdx.x < S_COUNT) d.ctr[threadIdx.x] = 0;
+	const SymProbe sp = sym_probe(s_sym, 64);                            // (its barrier is behind the zeroed counters as well)
+	uint32_t s[5];
 	load5(root, s);
-	int sym, count;
-	sym_canonical(s_sym, L, lane, s, rep, &sym, &count);
-	const uint32_t e = probe_find(b.table, b.mask, b.states, rep);
-	if (lane != 0) return;
-	#pragma unroll
-	for (int j = 0; j < 5; j++) d.states[5 + j] = s[j];
-	d.parent[1] = 0; d.pact[1] = 0;
-	d.table[hash_state(s) & d.mask] = 1u;
-	d.ctr[F_SIZE] = 1; d.ctr[F_HEAD] = 1; d.ctr[S_HI] = 1; d.ctr[S_LO] = 1;
-	d.ctr[F_BUDGET] = budget;
-	d.ctr[F_WINPOS] = (int32_t)F_NO_WIN;
-	if (e != 0u) {                                                       // the ball holds the start's orbit: nothing is popped
-		d.ctr[F_WON] = 1; d.ctr[S_MEET] = (int32_t)e;
-		d.ctr[F_STOP] = F_STOP_WON; d.ctr[F_DONE] = 1;
-		return;
-	}
-	srch_next(d);
+	const uint32_t e = sb_node(b, sp, s);
+	if (sp.lane == 0) srch_root_store(d, s, budget, e);                  // (the ball holds the start's orbit: nothing is popped)
 }
 
 // hit[c] = the ball's node of the representative of child c of the batch, 0 when the ball does not hold it: waves stride over
@@ -381,20 +291,14 @@ __device__ __forceinline__ void ssearch_probe(const FrontierDev &d, const SymBal
 	__shared__ u32x4 s_act[36];
 	const int K = 12 * fr_pops(d);
 	if ((int)blockIdx.x * 4 >= K) return;                                // done, or a workgroup past the batch: nothing staged
-	sym_stage(s_sym, threadIdx.x, 256);
-	stage_action_tables(s_act, threadIdx.x);
-	__syncthreads();
-	const int lane = threadIdx.x & 63;
-	const SymLane L = sym_lane(min(lane, N_SYM - 1));
+	const SymProbe sp = sym_probe(s_sym, 256, s_act);
 	const int32_t head = d.ctr[F_HEAD];
 	for (int c = blockIdx.x * 4 + (threadIdx.x >> 6); c < K; c += gridDim.x * 4) {       // (whole waves)
 		const int i = c / 12, a = c - 12 * i;
-		uint32_t x[5], rep[5];
+		uint32_t x[5];
 		child_state(d.states, head + i, s_act, (uint32_t)a, x);
-		int sym, count;
-		sym_canonical(s_sym, L, lane, x, rep, &sym, &count);
-		const uint32_t e = probe_find(b.table, b.mask, b.states, rep);
-		if (lane == 0) hit[c] = e;
+		const uint32_t e = sb_node(b, sp, x);
+		if (sp.lane == 0) hit[c] = e;
 	}
 }
 
@@ -408,19 +312,12 @@ __device__ __forceinline__ void ssearch_expand(const FrontierDev &d, const uint3
 	const int c = blockIdx.x * blockDim.x + threadIdx.x;
 	if (c >= 12 * P) return;
 	const uint32_t m = hit[c];
-	if (m != 0u) {
-		atomicMin(reinterpret_cast<uint32_t *>(&d.ctr[F_WINPOS]), (uint32_t)c);
-		d.slot[c] = TENT | m;                                            // no claim (TENT bit); bsearch_end reads the meeting node here
-		return;
-	}
+	if (m != 0u) { srch_meet(d, c, m); return; }
 	const int32_t head = d.ctr[F_HEAD];
 	const int i = c / 12, a = c - 12 * i;
 	uint32_t s[5];
 	child_state(d.states, head + i, s_act, (uint32_t)a, s);
-	uint32_t slot = 0;
-	const uint32_t e = probe_elect(d.table, d.mask, d.states, s, c,
-	                               [&](int c2, uint32_t o[5]) { child_state(d.states, head + c2 / 12, s_act, (uint32_t)(c2 % 12), o); }, &slot);
-	d.slot[c] = e == 0u ? slot : NO_SLOT;
+	srch_claim(d, s_act, head, c, s);
 }
 
 // The action queue of a won search, one wave: the path from the start to the popped parent and the meeting action (none of either
@@ -431,24 +328,13 @@ __device__ __forceinline__ void ssearch_walk(const FrontierDev &d, const SymBall
 {
 	__shared__ uint32_t s_sym[SYM_LDS_DWORDS];
 	__shared__ u32x4 s_act[36];
-	const int lane = threadIdx.x;
-	sym_stage(s_sym, lane, 64);
-	stage_action_tables(s_act, lane);
-	__syncthreads();
+	const SymProbe sp = sym_probe(s_sym, 64, s_act);
+	const int lane = sp.lane;
 	if (lane == 0) out[0] = -1;
 	if (!d.ctr[F_WON]) return;
 	const int p = d.ctr[F_WPARENT];
-	int ls = 0;
-	for (int i = p; p != 0 && i != 1; ls++) {
-		if (i < 1 || (uint32_t)i >= d.cap1 || ls > (int)d.cap1) return;
-		i = d.parent[i];
-	}
-	int i = p;
-	for (int k = ls - 1; k >= 0; k--) {
-		if (k < max_len && lane == 0) out[1 + k] = d.pact[i];
-		i = d.parent[i];
-	}
-	int len = ls;
+	int len = p != 0 ? fr_walk_up(d, p, out + 1, max_len, lane == 0) : 0;
+	if (len < 0) return;
 	uint32_t x[5];
 	if (p != 0) {
 		const int a = d.ctr[F_WACT];
@@ -459,19 +345,14 @@ __device__ __forceinline__ void ssearch_walk(const FrontierDev &d, const SymBall
 	} else {
 		load5(d.states + 5, x);
 	}
-	const SymLane L = sym_lane(min(lane, N_SYM - 1));
-	uint32_t rep[5];
-	int sym, count;
-	sym_canonical(s_sym, L, lane, x, rep, &sym, &count);
-	const uint32_t g = probe_find(b.table, b.mask, b.states, rep);
+	const uint32_t g = sb_node(b, sp, x);
 	bool ok = g != 0u && g == (uint32_t)d.ctr[S_MEET];
 	const int own = len;                                                 // moves before the meeting state
-	if (ok) len = own + sb_descend(b, s_sym, s_act, L, lane, x, level_of(b.lstart, g),
-	                               [&](int k, int a) { if (own + k < max_len && lane == 0) out[1 + own + k] = a; }, &ok);
+	if (ok) len = own + sb_descend(b, sp, x, level_of(b.lstart, g), [&](int k, int a) { if (own + k < max_len && lane == 0) out[1 + own + k] = a; }, &ok);
 	if (lane == 0) out[0] = ok ? len : -2;
 }
 
-// ---- the single engine: one search per launch ----
+// ---- the single engine: one search per launch (scan, append, end and rehash: rk_frontier_dev.h's k_fr_*, k_srch_end) ----
 __global__ __launch_bounds__(64)
 void k_ss_root(FrontierDev d, SymBallView b, const uint32_t *root, int budget) { ssearch_root(d, b, root, budget); }
 
@@ -480,17 +361,6 @@ void k_ss_probe(FrontierDev d, SymBallView b, uint32_t *hit) { ssearch_probe(d, 
 
 __global__ __launch_bounds__(256)
 void k_ss_expand(FrontierDev d, const uint32_t *hit) { ssearch_expand(d, hit); }
-
-__global__ __launch_bounds__(ASCAN)
-void k_ss_scan(FrontierDev d) { fr_scan(d); }
-
-__global__ __launch_bounds__(256)
-void k_ss_append(FrontierDev d) { fr_append(d); }
-
-__global__ void k_ss_end(FrontierDev d) { if (threadIdx.x == 0 && blockIdx.x == 0) bsearch_end(d); }
-
-__global__ __launch_bounds__(256)
-void k_ss_rehash(FrontierDev d) { fr_rehash(d); }
 
 __global__ __launch_bounds__(64)
 void k_ss_walk(FrontierDev d, SymBallView b, int32_t *out, int max_len) { ssearch_walk(d, b, out, max_len); }
@@ -501,10 +371,7 @@ void k_sd_probe(SymBallView b, DeepenJob job)
 {
 	__shared__ uint32_t s_sym[SYM_LDS_DWORDS];
 	__shared__ u32x4 s_act[36];
-	sym_stage(s_sym, threadIdx.x, 256);
-	stage_action_tables(s_act, threadIdx.x);
-	__syncthreads();
-	deepen_probe(b, job, s_sym, s_act, (size_t)blockIdx.x * 4 + (size_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), (size_t)gridDim.x * 4);
+	deepen_probe(b, job, sym_probe(s_sym, 256, s_act), (size_t)blockIdx.x * 4 + (size_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), (size_t)gridDim.x * 4);
 }
 
 // the pops of the iterations to come; results do not depend on them.  One thread.
@@ -522,21 +389,11 @@ void k_ss_deepen_walk(FrontierDev d, SymBallView b, int node, int extra, uint32_
 {
 	__shared__ uint32_t s_sym[SYM_LDS_DWORDS];
 	__shared__ u32x4 s_act[36];
-	const int lane = threadIdx.x;
-	sym_stage(s_sym, lane, 64);
-	stage_action_tables(s_act, lane);
-	__syncthreads();
+	const SymProbe sp = sym_probe(s_sym, 64, s_act);
+	const int lane = sp.lane;
 	if (lane == 0) out[0] = -1;
-	int ls = 0;
-	for (int i = node; i != 1; ls++) {
-		if (i < 1 || (uint32_t)i >= d.cap1 || ls > (int)d.cap1) return;
-		i = d.parent[i];
-	}
-	int i = node;
-	for (int k = ls - 1; k >= 0; k--) {
-		if (k < max_len && lane == 0) out[1 + k] = d.pact[i] & PACT_ACTION;
-		i = d.parent[i];
-	}
+	const int ls = fr_walk_up(d, node, out + 1, max_len, lane == 0);
+	if (ls < 0) return;
 	int word[DEEPEN_MAX_EXTRA];
 	if (!deepen_word(extra, node == 1 ? -1 : deepen_last(d.pact[node] & PACT_ACTION), rank, word)) return;
 	uint32_t x[5];
@@ -549,15 +406,10 @@ void k_ss_deepen_walk(FrontierDev d, SymBallView b, int node, int extra, uint32_
 		#pragma unroll
 		for (int j = 0; j < 5; j++) x[j] = y[j];
 	}
-	const SymLane L = sym_lane(min(lane, N_SYM - 1));
-	uint32_t rep[5];
-	int sym, count;
-	sym_canonical(s_sym, L, lane, x, rep, &sym, &count);
-	const uint32_t g = probe_find(b.table, b.mask, b.states, rep);
+	const uint32_t g = sb_node(b, sp, x);
 	bool ok = g != 0u;
 	const int own = len;
-	if (ok) len = own + sb_descend(b, s_sym, s_act, L, lane, x, level_of(b.lstart, g),
-	                               [&](int k, int a) { if (own + k < max_len && lane == 0) out[1 + own + k] = a; }, &ok);
+	if (ok) len = own + sb_descend(b, sp, x, level_of(b.lstart, g), [&](int k, int a) { if (own + k < max_len && lane == 0) out[1 + own + k] = a; }, &ok);
 	if (lane == 0) out[0] = ok ? len : -2;
 }
 
@@ -565,11 +417,8 @@ void k_ss_deepen_walk(FrontierDev d, SymBallView b, int node, int extra, uint32_
 // Every slot is a whole search of its own -- pool, table, counters, batch scratch, look-back words, ticket, epoch and the 12 P
 // words of `hit` --, so a launch reads and writes through devs[blockIdx.y] and that slot's slice of `hits` alone; the ball is read
 // by all.  A slot that is done, or was never started, has F_NPOP == 0: it leaves at that read, draws no ticket and leaves its
-// epoch alone.  The pool-full rule is the plain batch's (rk_frontier_dev.h: srch_fit), so fr_pops() of a slot with P > 0 is P.
-
-// the named slots' tables and look-back words, zeroed: slot slots[blockIdx.y]
-__global__ __launch_bounds__(256)
-void kb_ss_clear(const FrontierDev *devs, const int32_t *slots, int chain_words) { srch_clear(devs[slots[blockIdx.y]], chain_words); }
+// epoch alone.  The pool-full rule is the plain batch's (rk_frontier_dev.h: srch_fit), so fr_pops() of a slot with P > 0 is P; the
+// clear, scan, append and end of all slots are the plain batch's too (kb_srch_*).
 
 // row j of roots / budgets starts slot slots[j]: one wave per named slot
 __global__ __launch_bounds__(64)
@@ -597,31 +446,6 @@ void kb_ss_expand(const FrontierDev *devs, const uint32_t *hits)
 	ssearch_expand(d, hits + (size_t)blockIdx.y * 12u * (size_t)d.pops);
 }
 
-__global__ __launch_bounds__(ASCAN)
-void kb_ss_scan(const FrontierDev *devs)
-{
-	const FrontierDev d = devs[blockIdx.y];
-	if (d.ctr[F_NPOP] == 0) return;                                      // (every workgroup of a live slot draws a ticket)
-	fr_scan(d);
-}
-
-__global__ __launch_bounds__(256)
-void kb_ss_append(const FrontierDev *devs)
-{
-	const FrontierDev d = devs[blockIdx.y];
-	if (blockIdx.x * 256 >= 12 * d.ctr[F_NPOP]) return;
-	fr_append(d);
-}
-
-__global__ void kb_ss_end(const FrontierDev *devs)
-{
-	if (threadIdx.x != 0 || blockIdx.x != 0) return;
-	const FrontierDev d = devs[blockIdx.y];
-	if (d.ctr[F_NPOP] == 0) return;
-	bsearch_end(d);
-	srch_fit(d);
-}
-
 // one WAVE per slot (the descent needs lane = symmetry): row s of `out` (n_slots, 1 + max_len) = length, -1 or -2, then the queue
 __global__ __launch_bounds__(64)
 void kb_ss_walk(const FrontierDev *devs, SymBallView b, int32_t *out, int max_len)
@@ -634,15 +458,13 @@ __global__ __launch_bounds__(256)
 void k_sym_canonical(const uint32_t *states, size_t n, uint32_t *rep_out, uint8_t *sym_out, uint8_t *orbit_out)
 {
 	__shared__ uint32_t s_sym[SYM_LDS_DWORDS];
-	sym_stage(s_sym, threadIdx.x, 256);
-	__syncthreads();
-	const int lane = threadIdx.x & 63;
-	const SymLane L = sym_lane(min(lane, N_SYM - 1));
+	const SymProbe sp = sym_probe(s_sym, 256);
+	const int lane = sp.lane;
 	for (size_t q = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6); q < n; q += (size_t)gridDim.x * 4) {
 		uint32_t x[5], rep[5];
 		load5(states + q * 5, x);
 		int sym, count;
-		sym_canonical(s_sym, L, lane, x, rep, &sym, &count);
+		sym_canonical(s_sym, sp.L, lane, x, rep, &sym, &count);
 		if (rep_out != nullptr && lane < 5) rep_out[q * 5 + lane] = dword_of(rep, lane);
 		if (sym_out != nullptr && lane == 5) sym_out[q] = (uint8_t)sym;
 		if (orbit_out != nullptr && lane == 6) orbit_out[q] = (uint8_t)(N_SYM / count);
@@ -675,16 +497,14 @@ struct rk_symball : KeptBall {
 	long long cover[SB_MAX_RADIUS + 1] = {};
 };
 
-struct rk_ssearch : FrontierPool {
+struct rk_ssearch : FrontierPool, BallReader<rk_symball> {
 	uint32_t *hit = nullptr;                    // per child of the batch: the ball's node of its representative, or 0
-	rk_symball *ball = nullptr;
 	int pops_made = 0;                          // what it was created with: rk_sdeepen_set_pops lowers d.pops, a reset restores it
 };
 
-// S searches in lock-step: the slots (rk_search_host.h: FrontierSlots), their `hit` block and the ball they all read
-struct rk_ssearchb : FrontierSlots {
+// S searches in lock-step: the slots (rk_frontier_host.h: FrontierSlots), their `hit` block and the ball they all read
+struct rk_ssearchb : FrontierSlots, BallReader<rk_symball> {
 	uint32_t *hit = nullptr;                    // (n_slots, 12 x pops): slot s's words are its own
-	rk_symball *ball = nullptr;
 };
 
 namespace {
@@ -897,7 +717,7 @@ int rk_sshorten(rk_symball_t *h, const int8_t *d_actions, const int32_t *d_len, 
 	int8_t *depth = static_cast<int8_t *>(d_scratch);
 	uint16_t *pred = reinterpret_cast<uint16_t *>(depth + shorten_depth_bytes(n, max_len, window));
 	hipLaunchKernelGGL(k_ss_windows, dim3(sym_grid(n * (size_t)max_len)), dim3(256), 0, st, h->view, d_actions, d_len, n, max_len, window, depth);
-	hipLaunchKernelGGL(k_ss_dp, dim3((unsigned)n), dim3(SHORTEN_DP_THREADS), 0, st, d_actions, d_len, max_len, window, depth, pred, d_error);
+	hipLaunchKernelGGL(k_shorten_dp, dim3((unsigned)n), dim3(SHORTEN_DP_THREADS), 0, st, d_actions, d_len, max_len, window, depth, pred, d_error);
 	hipLaunchKernelGGL(k_ss_emit, dim3((unsigned)n), dim3(64), 0, st, h->view, d_actions, d_len, max_len, window, depth, pred, d_out_actions, d_out_len,
 	                   d_error);
 	RK_HIP(hipGetLastError());
@@ -913,17 +733,15 @@ int rk_ssearch_create(rk_ssearch_t **out, rk_symball_t *ball, size_t capacity, i
 	int e = h->alloc(capacity, pops, S_COUNT);
 	if (!e) e = h->pool.alloc(&h->hit, (size_t)12 * pops);
 	if (e) { delete h; return e; }
-	h->ball = ball;
+	h->attach(ball);
 	h->pops_made = pops;
-	ball->attached += 1;
 	*out = h;
 	return RK_OK;
 }
 
 int rk_ssearch_destroy(rk_ssearch_t *h)
 {
-	if (h && h->ball) h->ball->attached -= 1;
-	delete h;
+	delete h;                                   // (lets go of the ball: BallReader)
 	return RK_OK;
 }
 
@@ -947,8 +765,7 @@ int rk_ssearch_run(rk_ssearch_t *h, int iterations, void *stream)
 	              [&](unsigned grid) {
 		              hipLaunchKernelGGL(k_ss_probe, dim3(probe_grid), dim3(256), 0, st, h->d, h->ball->view, h->hit);
 		              hipLaunchKernelGGL(k_ss_expand, dim3(grid), dim3(256), 0, st, h->d, h->hit);
-	              },
-	              k_ss_scan, k_ss_append, k_ss_end);
+	              });
 }
 
 int rk_ssearch_status(rk_ssearch_t *h, long long *h_status, void *stream)
@@ -963,7 +780,7 @@ int rk_ssearch_status(rk_ssearch_t *h, long long *h_status, void *stream)
 int rk_ssearch_grow(rk_ssearch_t *h, size_t new_capacity, void *stream)
 {
 	if (int e = FrontierPool::check_ready(h, "rk_ssearch_grow")) return e;
-	return h->grow("rk_ssearch_grow", new_capacity, k_ss_rehash, (hipStream_t)stream);
+	return h->grow("rk_ssearch_grow", new_capacity, (hipStream_t)stream);
 }
 
 long long rk_ssearch_size(const rk_ssearch_t *h) { return FrontierPool::size(h); }
@@ -1050,15 +867,13 @@ int rk_ssearchb_create(rk_ssearchb_t **out, rk_symball_t *ball, int n_slots, siz
 		delete h;
 		return e;
 	}
-	h->ball = ball;
-	ball->attached += 1;
+	h->attach(ball);
 	*out = h;
 	return RK_OK;
 }
 
 int rk_ssearchb_destroy(rk_ssearchb_t *h)
 {
-	if (h && h->ball) h->ball->attached -= 1;
 	delete h;
 	return RK_OK;
 }
@@ -1067,7 +882,7 @@ int rk_ssearchb_reset(rk_ssearchb_t *h, int n, const int32_t *slots, const int8_
 {
 	if (!h) return fail(RK_EINVAL, "rk_ssearchb_reset: null engine");
 	hipStream_t st = (hipStream_t)stream;
-	return h->reset("rk_ssearchb_reset", h->ball->built, n, slots, h_start_states, max_states, st, kb_ss_clear, [&] {
+	return h->reset("rk_ssearchb_reset", h->ball->built, n, slots, h_start_states, max_states, st, [&] {
 		hipLaunchKernelGGL(kb_ss_root, dim3(1, n), dim3(64), 0, st, h->devs, h->ball->view, h->slots_dev, h->roots_dev, h->budgets_dev);
 	});
 }
@@ -1075,20 +890,12 @@ int rk_ssearchb_reset(rk_ssearchb_t *h, int n, const int32_t *slots, const int8_
 int rk_ssearchb_run(rk_ssearchb_t *h, int iterations, void *stream)
 {
 	if (!h) return fail(RK_EINVAL, "rk_ssearchb_run: null engine");
-	if (int e = h->check_run("rk_ssearchb_run", h->ball->built, iterations)) return e;
 	hipStream_t st = (hipStream_t)stream;
-	const SymBallView &b = h->ball->view;
-	const size_t K = (size_t)12 * h->pops;
-	const dim3 grid_probe(sym_grid(K), h->n_slots), grid(blocks(K), h->n_slots), grid_scan(blocks(K, ASCAN), h->n_slots);
-	for (int it = 0; it < iterations; it++) {
-		hipLaunchKernelGGL(kb_ss_probe, grid_probe, dim3(256), 0, st, h->devs, b, h->hit);
+	const dim3 grid_probe(sym_grid((size_t)12 * h->pops), h->n_slots);
+	return h->run("rk_ssearchb_run", h->ball->built, iterations, st, [&](dim3 grid) {
+		hipLaunchKernelGGL(kb_ss_probe, grid_probe, dim3(256), 0, st, h->devs, h->ball->view, h->hit);
 		hipLaunchKernelGGL(kb_ss_expand, grid, dim3(256), 0, st, h->devs, h->hit);
-		hipLaunchKernelGGL(kb_ss_scan, grid_scan, dim3(ASCAN), 0, st, h->devs);
-		hipLaunchKernelGGL(kb_ss_append, grid, dim3(256), 0, st, h->devs);
-		hipLaunchKernelGGL(kb_ss_end, dim3(1, h->n_slots), dim3(64), 0, st, h->devs);
-	}
-	RK_HIP(hipGetLastError());
-	return RK_OK;
+	});
 }
 
 int rk_ssearchb_status(rk_ssearchb_t *h, long long *h_status, void *stream)

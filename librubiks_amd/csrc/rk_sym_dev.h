@@ -134,16 +134,49 @@ struct SymBallView {
 	const uint32_t *states; const uint32_t *table;
 };
 
-// The descent from x, a state whose representative lies at level `depth` of the ball, to the solved state: at each step the lowest
-// action whose child's representative lies one level nearer, emit(step, action) for every step, x moved along.  Returns the
-// steps taken; *ok = false when a state has no such child (the ball is broken) or depth is outside 0..radius.  ALL 64 lanes of a
-// wave call it with the same x (lane l with the SymLane of symmetry l); everything in it is the same in every lane.
-template <typename Emit>
-__device__ __forceinline__ int sb_descend(const SymBallView &b, const uint32_t *s_sym, const u32x4 *s_act, const SymLane &L, int lane,
-                                          uint32_t x[5], int depth, Emit emit, bool *ok_out)
+// What a wave needs to ask the ball about a state: the staged tables, its lane and the lane's symmetry (lane l < 48: symmetry l;
+// lanes 48..63 take no part in the minimum).  s_act is null in a kernel that moves no state.
+struct SymProbe {
+	const uint32_t *s_sym;
+	const u32x4 *s_act;
+	SymLane L;
+	int lane;
+};
+
+// All `threads` threads of the workgroup, once, after the kernel has declared its LDS (s_sym: SYM_LDS_DWORDS; s_act: 36 or null):
+// stages the symmetry tables and, where given, the action tables, then the barrier.
+__device__ __forceinline__ SymProbe sym_probe(uint32_t *s_sym, int threads, u32x4 *s_act = nullptr)
+{
+	sym_stage(s_sym, threadIdx.x, threads);
+	if (s_act != nullptr) stage_action_tables(s_act, threadIdx.x);
+	__syncthreads();
+	const int lane = threadIdx.x & 63;
+	return SymProbe{s_sym, s_act, sym_lane(min(lane, N_SYM - 1)), lane};
+}
+
+// The ball's node of the representative of x, 0 when the ball does not hold it; sb_level: its level, -1 outside the ball.  ALL 64
+// lanes of a wave call these with the same x (sym_canonical); the answer is the same in every lane.
+__device__ __forceinline__ uint32_t sb_node(const SymBallView &b, const SymProbe &c, const uint32_t x[5])
 {
 	uint32_t rep[5];
 	int sym, count;
+	sym_canonical(c.s_sym, c.L, c.lane, x, rep, &sym, &count);
+	return probe_find(b.table, b.mask, b.states, rep);
+}
+
+__device__ __forceinline__ int sb_level(const SymBallView &b, const SymProbe &c, const uint32_t x[5])
+{
+	const uint32_t e = sb_node(b, c, x);
+	return e ? level_of(b.lstart, e) : -1;
+}
+
+// The descent from x, a state whose representative lies at level `depth` of the ball, to the solved state: at each step the lowest
+// action whose child's representative lies one level nearer, emit(step, action) for every step, x moved along.  Returns the
+// steps taken; *ok = false when a state has no such child (the ball is broken) or depth is outside 0..radius.  ALL 64 lanes of a
+// wave call it with the same x; everything in it is the same in every lane.
+template <typename Emit>
+__device__ __forceinline__ int sb_descend(const SymBallView &b, const SymProbe &c, uint32_t x[5], int depth, Emit emit, bool *ok_out)
+{
 	int len = 0;
 	bool ok = depth >= 0 && depth <= b.radius;
 	while (ok && len < depth) {                                      // (everything here is the same in every lane)
@@ -152,11 +185,9 @@ __device__ __forceinline__ int sb_descend(const SymBallView &b, const uint32_t *
 			uint32_t y[5], tab[12];
 			#pragma unroll
 			for (int j = 0; j < 5; j++) y[j] = x[j];
-			load_action_table(s_act, (uint32_t)a, tab);
+			load_action_table(c.s_act, (uint32_t)a, tab);
 			move5(y, tab);
-			sym_canonical(s_sym, L, lane, y, rep, &sym, &count);
-			const uint32_t g = probe_find(b.table, b.mask, b.states, rep);
-			if (g != 0u && level_of(b.lstart, g) == depth - len - 1) {
+			if (sb_level(b, c, y) == depth - len - 1) {
 				found = a;
 				#pragma unroll
 				for (int j = 0; j < 5; j++) x[j] = y[j];
