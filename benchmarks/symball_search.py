@@ -55,16 +55,22 @@ def own_states(own_levels: int) -> float:
 	return sum(LEVELS[l] if l < len(LEVELS) else LEVELS[-1] * GROWTH ** (l - len(LEVELS) + 1) for l in range(own_levels + 1))
 
 
+#: the launches of rk_ssearch: its own kernels (k_ss_*) and the frontier pool's, which every breadth-first engine shares
+SEARCH_KERNELS = ("k_ss_", "k_fr_scan", "k_fr_append", "k_fr_rehash", "k_srch_end")
+#: of these, the launches outside an iteration (an iteration is probe, expand, scan, append, end)
+NOT_ITERATION = ("k_ss_root", "k_ss_walk", "k_fr_rehash")
+
+
 def kernel_shares(path: str) -> dict:
 	"""rocprofv3's kernel_stats.csv: time per kernel of the search, and the probe launch's share of it."""
 	rows = {}
 	with open(path) as f:
 		for r in csv.DictReader(f):
 			name = r["Name"].split("(")[0]
-			if "k_ss_" in name:
+			if any(k in name for k in SEARCH_KERNELS):
 				rows[name] = {"calls": int(r["Calls"]), "total_ns": int(r["TotalDurationNs"]), "average_ns": float(r["AverageNs"])}
 	total = sum(r["total_ns"] for r in rows.values())
-	iteration = sum(r["total_ns"] for n, r in rows.items() if not ("k_ss_root" in n or "k_ss_walk" in n or "k_ss_rehash" in n))
+	iteration = sum(r["total_ns"] for n, r in rows.items() if not any(k in n for k in NOT_ITERATION))
 	probe = sum(r["total_ns"] for n, r in rows.items() if "k_ss_probe" in n)
 	return {"kernels": rows, "search_kernels_ns": total, "probe_share": round(probe / total, 4) if total else None,
 	        "iteration_kernels_ns": iteration, "probe_share_of_iteration": round(probe / iteration, 4) if iteration else None}
