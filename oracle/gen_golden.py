@@ -15,6 +15,7 @@ Fixtures
   astar_trace.npz   unmodified reference AStar driven by an exact-integer stub net
   mcts_trace.npz    unmodified reference MCTS driven by the same stub (one case with a non-uniform exact policy)
   adi_trace.npz     unmodified reference Train.ADI_traindata (train.py:256-339), stub net, all four reward methods
+  adi_real_trace.npz  the same on real-valued nets (tests/adi_nets.py): policy, value bit patterns, one-hot hash, loss weights
   evaluator_trace.npz  unmodified reference Evaluator.eval (solving/evaluation.py:56-96) over the unmodified agents and the stubs:
                     the `res` and `states` matrices (times are wall clock: not data)
 """
@@ -362,6 +363,53 @@ def adi_traces():
 	np.savez_compressed(os.path.join(OUT, "adi_trace.npz"), **out)
 
 
+def adi_real_traces():
+	"""
+	The unmodified reference `Train.ADI_traindata` on REAL-VALUED nets: tests/adi_nets.py's float32 LookupNet and LinearLookupNet in
+	their torch forms (the reference hands the net torch one-hot slices), every reward method on each.  Arrays only: parameters,
+	policy, the value targets as bit patterns, a hash of the one-hot states, loss weights.  tests/test_adi_real_valued_cpu.py holds
+	adi_traindata_oracle to them.
+	"""
+	import types
+	from librubiks import train as ref_train
+	from librubiks.utils.ticktock import TickTock
+	import importlib.util
+	root = os.path.dirname(HERE)
+	sys.path.append(root)                          # for adi_nets' own imports; the reference has a `tests` package too, so load by path
+	spec = importlib.util.spec_from_file_location("adi_nets", os.path.join(root, "tests", "adi_nets.py"))
+	adi_nets = importlib.util.module_from_spec(spec)
+	spec.loader.exec_module(adi_nets)
+	net_of = adi_nets.net_of
+	out = {}
+	cases = {
+		"lookup_lapanfix": dict(net="lookup", method="lapanfix", seed=61, games=37, depth=9, alpha=0.3, ff=7),
+		"lookup_paper": dict(net="lookup", method="paper", seed=62, games=30, depth=11, alpha=0.3, ff=3),
+		"lookup_schultzfix": dict(net="lookup", method="schultzfix", seed=63, games=20, depth=11, alpha=0.0, ff=1),
+		"lookup_reward0": dict(net="lookup", method="reward0", seed=64, games=50, depth=6, alpha=1.0, ff=4),
+		"linear_lapanfix": dict(net="linear", method="lapanfix", seed=65, games=37, depth=9, alpha=0.3, ff=7),
+		"linear_paper": dict(net="linear", method="paper", seed=66, games=64, depth=5, alpha=0.5, ff=5),
+		"linear_schultzfix": dict(net="linear", method="schultzfix", seed=67, games=20, depth=11, alpha=0.0, ff=2),
+		"linear_reward0": dict(net="linear", method="reward0", seed=68, games=50, depth=6, alpha=1.0, ff=4),
+	}
+	for tag, c in cases.items():
+		me = types.SimpleNamespace(rollout_games=c["games"], rollout_depth=c["depth"], reward_method=c["method"],
+		                           adi_ff_batches=c["ff"], tt=TickTock(), with_analysis=False)
+		me._get_adi_ff_slices = types.MethodType(ref_train.Train._get_adi_ff_slices, me)
+		np.random.seed(c["seed"])
+		oh, policy, value, lw = ref_train.Train.ADI_traindata(me, net_of(c["net"]), c["alpha"])
+		value = np.ascontiguousarray(value.numpy(), np.float32)
+		out[f"{tag}_net"] = np.array(c["net"])
+		out[f"{tag}_method"] = np.array(c["method"])
+		out[f"{tag}_params"] = np.array([c["seed"], c["games"], c["depth"], c["ff"]])
+		out[f"{tag}_alpha"] = np.array(c["alpha"])
+		out[f"{tag}_oh_sha256"] = np.array(sha(oh.cpu().numpy().astype(np.float32)))
+		out[f"{tag}_policy"] = policy.numpy().astype(np.int64)
+		out[f"{tag}_value_bits"] = value.view(np.uint32)
+		out[f"{tag}_loss_weights"] = lw.numpy().astype(np.float32)
+		print(f"adi_real {tag}: n={len(oh)} later maxima={(policy != 0).sum().item()} distinct values={len(np.unique(value))} zeros={(value == 0).sum()}")
+	np.savez_compressed(os.path.join(OUT, "adi_real_trace.npz"), **out)
+
+
 def evaluator_traces():
 	"""
 	The unmodified reference `Evaluator.eval` (solving/evaluation.py:56-96): scrambles drawn from the global generator between the
@@ -406,11 +454,12 @@ if __name__ == "__main__":
 	ap.add_argument("--only", default="")
 	args = ap.parse_args()
 	os.makedirs(OUT, exist_ok=True)
-	todo = args.only.split(",") if args.only else ["tables", "kats", "astar", "mcts", "adi", "evaluator"]
+	todo = args.only.split(",") if args.only else ["tables", "kats", "astar", "mcts", "adi", "adi_real", "evaluator"]
 	if "tables" in todo: tables()
 	if "kats" in todo: kats(args.skip_1m)
 	if "astar" in todo: astar_traces()
 	if "mcts" in todo: mcts_traces()
 	if "adi" in todo: adi_traces()
+	if "adi_real" in todo: adi_real_traces()
 	if "evaluator" in todo: evaluator_traces()
 	print("golden vectors written to", OUT)
