@@ -673,6 +673,47 @@ int rk_ssearchb_paths(rk_ssearchb_t *h, int32_t *h_out, int max_len, void *strea
 int rk_ssearchb_export(rk_ssearchb_t *h, int slot, size_t first, size_t count, int8_t *h_states, long long *h_parents,
                        long long *h_actions, void *stream);
 
+/* Deepening in the batch: a slot whose pool is full goes on from its newest complete level by rk_sdeepen's probes, beside the
+ * slots that still pop; one launch serves every such slot.
+ * rk_sdeepenb_set: the pool-full rule of the slots that rk_ssearchb_reset starts from now on (off at creation; no
+ * launch).  On: a slot whose next iteration might not fit pops only as many nodes as surely fit, min(pops, (capacity -
+ * n_states) / 12), and stops with reason 5 only when not even one does -- its pool, popped nodes and levels are then those of
+ * pops = 1, whatever the engine's pops.  Off: rk_ssearchb's rule above, launch for launch.  Refuses a null engine. */
+int rk_sdeepenb_set(rk_ssearchb_t *h, int on);
+/* h_out (n_slots, 2) = the first and the last node of every slot's newest complete level (zeros for a slot never started).
+ * Reads the counters on `stream` and synchronises it.  The engine remembers the level and the size of every slot that is done
+ * at this read -- such a slot stands still until its next reset --; rk_sdeepenb_probe and rk_sdeepenb_paths check their
+ * arguments against that and refuse (RK_ESTATE) a slot that was running at the last call of this entry or was reset since. */
+int rk_sdeepenb_frontiers(rk_ssearchb_t *h, long long *h_out, void *stream);
+/* A job of rk_sdeepenb_probe: the words word_first .. word_first + word_count - 1 of `extra` moves behind the nodes node_first ..
+ * node_first + node_count - 1 of slot `slot`, each node's stored action as its last move (none for node 1).  new_round != 0:
+ * the slot's key is "none" before this launch lowers it; 0: the key goes on from the launches before. */
+typedef struct rk_deepen_job {
+	int32_t slot, extra;
+	uint32_t node_first, node_count, word_first, word_count;
+	uint32_t new_round, reserved;
+} rk_deepen_job_t;
+/* One launch over n_jobs HOST jobs, stream-ordered, no synchronisation: every result is canonicalised and looked up in the ball,
+ * and a slot keeps ONE 64-bit key, the lowest (node << 32 | rank) that hit -- the lowest node with a hit and that node's
+ * lowest word.  A (node, rank) above the slot's key is skipped.  Jobs of one launch may be in different rounds.  Nothing of a
+ * pool or of the ball is written.  Checked on the host before anything runs, RK_EINVAL with no launch and no key changed:
+ * n_jobs outside 0..n_slots, null jobs, a slot out of range or named twice, extra outside 1..8, a node range that is empty or
+ * not inside the slot's frontier as rk_sdeepenb_frontiers last read it, a word range that is empty or not inside the words of
+ * `extra` moves (12 * 11^(extra-1) for a frontier that is node 1, else 11^extra), and more than rk_sdeepen_max_probes() probes
+ * (the sum of node_count * word_count) in the launch.  RK_ESTATE: the ball is not built, a slot was not done at the last
+ * rk_sdeepenb_frontiers or was reset since, or a slot's first job since its reset does not set new_round. */
+int rk_sdeepenb_probe(rk_ssearchb_t *h, int n_jobs, const rk_deepen_job_t *h_jobs, void *stream);
+/* h_out[n_slots] = every slot's key of its current round, all ones for none (and for a slot without a round).  Synchronises.
+ * Refuses null arguments. */
+int rk_sdeepenb_keys(rk_ssearchb_t *h, unsigned long long *h_out, void *stream);
+/* Row j of HOST h_out int32 (n, 1 + max_len): rk_sdeepen_path for slot slots[j], node nodes[j], extras[j] moves, word ranks[j]
+ * -- the length, then the first max_len actions; -1 when the node has no such word or a parent chain is broken, -2 when the
+ * word does not lead into the ball.  One launch, one wave per row, one copy.  Synchronises.  RK_EINVAL with no launch: null
+ * arguments, n outside 0..n_slots, a slot out of range, a node outside 1..n_states of its slot, extra outside 1..8, max_len
+ * outside 0..4096; RK_ESTATE for a slot that rk_sdeepenb_probe would refuse for the same reason. */
+int rk_sdeepenb_paths(rk_ssearchb_t *h, int n, const int32_t *slots, const long long *nodes, const int32_t *extras,
+                             const uint32_t *ranks, int32_t *h_out, int max_len, void *stream);
+
 /* ---- device-resident epsilon-greedy value maximisation (agents.py:649-726) ---------------------------------------
  * W = workers walkers take D = depth moves from a root (:692-715); the visited state with the best value becomes the next
  * root (:673-677) until a walker is solved (:710-713) or another round would pass max_states (:665).  The root, the

@@ -159,6 +159,11 @@ SIGNATURES = {
 	"rk_ssearchb_status": (_i, [_vp, _vp, _vp]),
 	"rk_ssearchb_paths": (_i, [_vp, _vp, _i, _vp]),
 	"rk_ssearchb_export": (_i, [_vp, _i, _sz, _sz, _vp, _vp, _vp, _vp]),
+	"rk_sdeepenb_set": (_i, [_vp, _i]),
+	"rk_sdeepenb_frontiers": (_i, [_vp, _vp, _vp]),
+	"rk_sdeepenb_probe": (_i, [_vp, _i, _vp, _vp]),
+	"rk_sdeepenb_keys": (_i, [_vp, _vp, _vp]),
+	"rk_sdeepenb_paths": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
 	"rk_egvm_create": (_i, [C.POINTER(_vp), _i, _i, _i]),
 	"rk_egvm_destroy": (_i, [_vp]),
 	"rk_egvm_net_in": (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_sz)]),

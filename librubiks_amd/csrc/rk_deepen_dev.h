@@ -14,6 +14,11 @@
 // look-up.  Everything is the same in every lane; lane 0 does the atomicMin.  Ranks outside [word_first, word_first + word_count),
 // ranks a state does not have, and ranks above the state's current best are skipped; a hit ends the item, whose later ranks are
 // all above it.
+//
+// What is kept.  A launch on the caller's states or on one search's pool keeps a word per state, the lowest rank that hit
+// (DeepenRanks).  A slot of the batch keeps ONE 64-bit key for its whole frontier, node << 32 | rank (DeepenKey): the lowest key is
+// the lowest node that has a hit and that node's lowest rank, which is what the words give when they are read in node order.  A
+// (node, rank) above the key is skipped, so after the first hit what is left of a round collapses to the lower nodes.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -25,6 +30,7 @@ namespace rk {
 
 constexpr int DEEPEN_MAX_EXTRA = 8;
 constexpr uint32_t DEEPEN_NONE = 0xFFFFFFFFu;       // d_best of a state without a hit
+constexpr unsigned long long DEEPEN_NO_KEY = ~0ull;  // the key of a slot without a hit
 constexpr uint32_t DEEPEN_SPAN = 121;               // ranks of an item when extra >= 3
 // The most probes (states x word_count) of one launch.  Measured on the radius-10 ball (benchmarks/symball_deepen.py,
 // profiles/r17_symball_deepen.json); the cap keeps a launch well under a second on a machine that others share.
@@ -60,6 +66,16 @@ __host__ __device__ inline bool deepen_word(int extra, int last, uint32_t rank, 
 	return true;
 }
 
+// ranks per item (extra <= 2: every rank is below 132)
+__host__ __device__ inline uint32_t deepen_span(int extra) { return extra >= 3 ? DEEPEN_SPAN : 132u; }
+
+// the items per state of the ranks [word_first, word_first + word_count), word_count >= 1
+__host__ __device__ inline uint32_t deepen_groups(int extra, uint32_t word_first, uint32_t word_count)
+{
+	const uint32_t span = deepen_span(extra);
+	return (uint32_t)(((unsigned long long)word_first + word_count - 1u) / span) - word_first / span + 1u;
+}
+
 struct DeepenJob {
 	const uint32_t *states;                     // (n, 5) dwords
 	const int8_t *last;                         // (n) or null: the action that led to each state, anything outside 0..11 for none
@@ -67,7 +83,31 @@ struct DeepenJob {
 	size_t n;
 	int extra;
 	uint32_t word_first, word_count;
-	uint32_t *best;                             // (n): atomicMin of the ranks that hit
+};
+
+// What a launch keeps of its hits.  limit(i): the highest rank of state i that is still worth a probe, -1 when none is, the same
+// in every lane and read through readfirstlane; lower(i, r): rank r of state i hit (one lane calls it).
+struct DeepenRanks {                            // best (n): atomicMin of the ranks that hit, DEEPEN_NONE without one
+	uint32_t *best;
+	__device__ __forceinline__ long long limit(size_t i) const
+	{
+		return (long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(&best[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+	}
+	__device__ __forceinline__ void lower(size_t i, uint32_t r) const { atomicMin(&best[i], r); }
+};
+
+struct DeepenKey {                              // *key: atomicMin of (node_first + i) << 32 | rank over the hits, DEEPEN_NO_KEY without one
+	unsigned long long *key;
+	uint32_t node_first;
+	__device__ __forceinline__ long long limit(size_t i) const
+	{
+		const unsigned long long k = __hip_atomic_load(key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		const uint32_t node = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(k >> 32));
+		const uint32_t rank = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)k);
+		const uint32_t mine = node_first + (uint32_t)i;
+		return mine < node ? (long long)DEEPEN_NONE : mine == node ? (long long)rank : -1ll;
+	}
+	__device__ __forceinline__ void lower(size_t i, uint32_t r) const { atomicMin(key, (unsigned long long)(node_first + (uint32_t)i) << 32 | r); }
 };
 
 __device__ __forceinline__ void deepen_move(const u32x4 *s_act, int a, const uint32_t in[5], uint32_t out[5])
@@ -80,14 +120,15 @@ __device__ __forceinline__ void deepen_move(const u32x4 *s_act, int a, const uin
 }
 
 // the items wave, wave + stride, ... of the job (wave and stride in whole waves; all 64 lanes of a wave call it)
-__device__ __forceinline__ void deepen_probe(const SymBallView &b, const DeepenJob &job, const SymProbe &c, size_t wave, size_t stride)
+template <typename Keep>
+__device__ __forceinline__ void deepen_probe(const SymBallView &b, const DeepenJob &job, const SymProbe &c, size_t wave, size_t stride, const Keep &keep)
 {
 	const u32x4 *s_act = c.s_act;
 	const int e = job.extra;
-	const uint32_t span = e >= 3 ? DEEPEN_SPAN : 132u;                   // (extra <= 2: every rank is below 132)
+	const uint32_t span = deepen_span(e);
 	const unsigned long long end = (unsigned long long)job.word_first + job.word_count;
 	const uint32_t g_first = job.word_first / span;
-	const uint32_t ng = (uint32_t)((end - 1) / span) - g_first + 1u;
+	const uint32_t ng = deepen_groups(e, job.word_first, job.word_count);
 	const size_t items = job.n * (size_t)ng;
 	for (size_t w = wave; w < items; w += stride) {
 		const size_t i = w / ng;
@@ -95,10 +136,9 @@ __device__ __forceinline__ void deepen_probe(const SymBallView &b, const DeepenJ
 		// (one address for the whole wave: through readfirstlane, so that everything that depends on them is scalar)
 		const int last = job.last != nullptr && (long long)i != job.no_last ? deepen_last(__builtin_amdgcn_readfirstlane((int)job.last[i])) : -1;
 		const uint32_t n0 = last < 0 ? 12u : 11u;
-		const uint32_t best =
-			(uint32_t)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(&job.best[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-		const unsigned long long base = (unsigned long long)g * span;
-		const unsigned long long lo = max((unsigned long long)job.word_first, base), hi = min(end, base + span);
+		const long long best = keep.limit(i);
+		const long long base = (long long)g * span;
+		const long long lo = max((long long)job.word_first, base), hi = min((long long)end, base + span);
 		if (lo > best) continue;
 		uint32_t s[5];
 		load5(job.states + i * 5, s);
@@ -123,7 +163,7 @@ __device__ __forceinline__ void deepen_probe(const SymBallView &b, const DeepenJ
 		const uint32_t cl = e >= 2 ? 11u : n0;
 		bool hit = false;
 		for (uint32_t dm = 0; dm < cm && !hit; dm++) {
-			const unsigned long long r0 = base + (unsigned long long)dm * cl;
+			const long long r0 = base + (long long)dm * cl;
 			if (r0 >= hi || r0 > best) break;
 			if (r0 + cl <= lo) continue;
 			uint32_t s1[5];
@@ -136,13 +176,13 @@ __device__ __forceinline__ void deepen_probe(const SymBallView &b, const DeepenJ
 				for (int j = 0; j < 5; j++) s1[j] = s[j];
 			}
 			for (uint32_t dl = 0; dl < cl; dl++) {
-				const unsigned long long r = r0 + dl;
+				const long long r = r0 + dl;
 				if (r < lo) continue;
 				if (r >= hi || r > best) break;
 				uint32_t s2[5];
 				deepen_move(s_act, deepen_action(p1, (int)dl), s1, s2);
 				if (sb_node(b, c, s2) != 0u) {                           // (the same in every lane)
-					if (c.lane == 0) atomicMin(&job.best[i], (uint32_t)r);
+					if (c.lane == 0) keep.lower(i, (uint32_t)r);
 					hit = true;                                          // every later rank of the item is above r
 					break;
 				}

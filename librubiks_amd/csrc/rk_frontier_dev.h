@@ -143,7 +143,7 @@ __device__ __forceinline__ void fr_rehash(const FrontierDev &d)
 }
 
 // ---- the searches that end at a kept ball (rk_bsearch_*, rk_bsearchb_*, rk_ssearch_*): one side, level by level ----
-enum { S_DEPTH = F_COMMON, S_HI, S_MEET, S_POPPED, S_LO, S_COUNT = 32 };      // S_LO .. S_HI: the newest complete level
+enum { S_DEPTH = F_COMMON, S_HI, S_MEET, S_POPPED, S_LO, S_CLIP, S_COUNT = 32 };      // S_LO .. S_HI: the newest complete level
 
 // After a pop count change: the end of a level, the done flags and the next P (rk_bibfs.hip: bibfs_next, one side).  One thread.
 __device__ __forceinline__ void srch_next(const FrontierDev &d)
@@ -167,7 +167,7 @@ __device__ __forceinline__ void srch_end(const FrontierDev &d) { fr_end<S_MEET, 
 
 // What a root launch stores once it knows e, the ball's node of the start (0: the ball does not hold it): node 1 = the start s,
 // the counters, and either the win without a pop -- the ball's path from e is the answer -- or the first pop count.  One thread,
-// after the counter block was zeroed.  S_LO is set for both balls: only rk_sdeepen_frontier exports it, no plain-ball entry does.
+// after the counter block was zeroed.  S_LO is set for both balls: only rk_sdeepen_frontier and rk_sdeepenb_frontiers export it, no plain-ball entry does.
 __device__ __forceinline__ void srch_root_store(const FrontierDev &d, const uint32_t s[5], int budget, uint32_t e)
 {
 	#pragma unroll
@@ -204,6 +204,12 @@ __device__ __forceinline__ void srch_claim(const FrontierDev &d, const u32x4 *s_
 // ---- such searches in lock-step (rk_bsearchb_*, rk_ssearchb_*): a slot's pool never grows ----
 // A slot whose next iteration might not fit (size + 12 P > capacity) stops BEFORE that iteration with BS_STOP_FULL, so fr_pops()
 // of a slot with P > 0 is P and the single engine's F_ERR_CAPACITY path is never taken.
+// A slot whose root set S_CLIP (rk_sdeepenb_set; 0 in every other pool) is not stopped by a batch that might not fit: it
+// pops as many nodes as surely fit, min(P, (capacity - size) / 12), and stops only when not even one does.  A pop that runs this
+// way also runs at pops = 1, where it is asked for alone with at most as many states stored; the pool's order does not depend on
+// the pops, a level is never crossed (srch_next), and the stop is pops = 1's: size + 12 > capacity.  So the pool, the nodes
+// popped, the complete levels and the partial next level are those of pops = 1, whatever d.pops is.  Only F_NPOP is lowered:
+// d.pops, the grids and the stride of a slot's scratch stay.
 enum { BS_STOP_FULL = 5 };
 
 // after the root or the end of an iteration of a slot: does the next iteration fit the pool whatever it finds?  One thread.
@@ -211,6 +217,10 @@ __device__ __forceinline__ void srch_fit(const FrontierDev &d)
 {
 	const int P = d.ctr[F_NPOP];
 	if (P == 0 || (uint64_t)d.ctr[F_SIZE] + 12ull * (uint64_t)P <= (uint64_t)d.cap1 - 1u) return;
+	if (d.ctr[S_CLIP]) {
+		const uint32_t fit = (d.cap1 - 1u - (uint32_t)d.ctr[F_SIZE]) / 12u;  // (size <= capacity: the appends are bounded by it)
+		if (fit >= 1u) { d.ctr[F_NPOP] = (int32_t)fit; return; }            // (fit < P: P did not fit)
+	}
 	d.ctr[F_STOP] = BS_STOP_FULL; d.ctr[F_DONE] = 1; d.ctr[F_NPOP] = 0;
 }
 

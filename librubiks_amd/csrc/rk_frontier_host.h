@@ -420,9 +420,9 @@ struct FrontierSlots {
 		return RK_OK;
 	}
 
-	// the engine's walk launch into rows of 1 + max_len words, one per slot, then one copy to h_out
+	// the engine's walk launch into the first `rows` rows of 1 + max_len words of `walk` (n_slots of them), then one copy to h_out
 	template <typename Walk>
-	int paths(const char *who, bool ball_built, int32_t *h_out, int max_len, hipStream_t st, Walk &&launch_walk)
+	int paths(const char *who, bool ball_built, int32_t *h_out, int max_len, hipStream_t st, Walk &&launch_walk, int rows = -1)
 	{
 		if (!ball_built) return fail(RK_ESTATE, "%s: build the ball first", who);
 		if (max_len < 0 || max_len > FRONTIER_WALK_MAX) return fail(RK_EINVAL, "%s: max_len %d outside 0..%d", who, max_len, FRONTIER_WALK_MAX);
@@ -435,7 +435,7 @@ struct FrontierSlots {
 		}
 		launch_walk();
 		RK_HIP(hipGetLastError());
-		RK_HIP(hipMemcpyAsync(h_out, walk, words * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+		RK_HIP(hipMemcpyAsync(h_out, walk, (rows < 0 ? words : (size_t)rows * (size_t)(1 + max_len)) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
 		RK_HIP(hipStreamSynchronize(st));
 		return RK_OK;
 	}

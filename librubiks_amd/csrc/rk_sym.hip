@@ -76,6 +76,11 @@
 //                    the caller's states (rk_sdeepen) or on rows of a search's pool with the stored action as the last move
 //   k_ss_setpops     one thread: a lower pop count for the iterations to come (the host lowers it when the pool is nearly full)
 //   k_ss_deepen_walk one wave: the path to a pool node, a word from it, then the descent from the moved state
+// In the batch (rk_sdeepenb_set, _frontiers, _probe, _keys, _paths) a slot whose pool is full goes on the
+// same way beside the slots that still pop.  Its pool phase ends where pops = 1 would end it (rk_frontier_dev.h: S_CLIP, srch_fit).
+//   kb_sd_probe        grid (k_sd_probe's x, jobs): one launch for all deepening slots, each job a node range and a word range of
+//                      one slot in a round of its own; deepen_probe's body, one 64-bit key per slot instead of a word per node
+//   kb_ss_deepen_walk  one wave per named slot: k_ss_deepen_walk's body (ssearch_deepen_walk)
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <climits>
@@ -367,11 +372,12 @@ void k_ss_walk(FrontierDev d, SymBallView b, int32_t *out, int max_len) { ssearc
 
 // ---- deepening: words from a state, every result probed (rk_deepen_dev.h) ----
 __global__ __launch_bounds__(256)
-void k_sd_probe(SymBallView b, DeepenJob job)
+void k_sd_probe(SymBallView b, DeepenJob job, uint32_t *best)
 {
 	__shared__ uint32_t s_sym[SYM_LDS_DWORDS];
 	__shared__ u32x4 s_act[36];
-	deepen_probe(b, job, sym_probe(s_sym, 256, s_act), (size_t)blockIdx.x * 4 + (size_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), (size_t)gridDim.x * 4);
+	deepen_probe(b, job, sym_probe(s_sym, 256, s_act), (size_t)blockIdx.x * 4 + (size_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), (size_t)gridDim.x * 4,
+	             DeepenRanks{best});
 }
 
 // the pops of the iterations to come; results do not depend on them.  One thread.
@@ -384,8 +390,7 @@ __global__ void k_ss_setpops(FrontierDev d)
 // The queue start -> `node` -> word `rank` of `extra` moves -> descent, one wave, as ssearch_walk: out[0] = length, -1 when the
 // parent chain is broken or the node has no such word, -2 when the ball does not hold the moved state's representative or the
 // descent finds no way on.  Every lane computes the same; lane 0 writes.
-__global__ __launch_bounds__(64)
-void k_ss_deepen_walk(FrontierDev d, SymBallView b, int node, int extra, uint32_t rank, int32_t *out, int max_len)
+__device__ __forceinline__ void ssearch_deepen_walk(const FrontierDev &d, const SymBallView &b, int node, int extra, uint32_t rank, int32_t *out, int max_len)
 {
 	__shared__ uint32_t s_sym[SYM_LDS_DWORDS];
 	__shared__ u32x4 s_act[36];
@@ -413,6 +418,12 @@ void k_ss_deepen_walk(FrontierDev d, SymBallView b, int node, int extra, uint32_
 	if (lane == 0) out[0] = ok ? len : -2;
 }
 
+__global__ __launch_bounds__(64)
+void k_ss_deepen_walk(FrontierDev d, SymBallView b, int node, int extra, uint32_t rank, int32_t *out, int max_len)
+{
+	ssearch_deepen_walk(d, b, node, extra, rank, out, max_len);
+}
+
 // ---- the batch: S searches in lock-step, slot blockIdx.y of `devs` per workgroup row (rk_ball.hip: kb_bsearch_*) ----
 // Every slot is a whole search of its own -- pool, table, counters, batch scratch, look-back words, ticket, epoch and the 12 P
 // words of `hit` --, so a launch reads and writes through devs[blockIdx.y] and that slot's slice of `hits` alone; the ball is read
@@ -422,11 +433,14 @@ void k_ss_deepen_walk(FrontierDev d, SymBallView b, int node, int extra, uint32_
 
 // row j of roots / budgets starts slot slots[j]: one wave per named slot
 __global__ __launch_bounds__(64)
-void kb_ss_root(const FrontierDev *devs, SymBallView b, const int32_t *slots, const uint32_t *roots, const int32_t *budgets)
+void kb_ss_root(const FrontierDev *devs, SymBallView b, const int32_t *slots, const uint32_t *roots, const int32_t *budgets, int clip)
 {
 	const FrontierDev d = devs[slots[blockIdx.y]];
 	ssearch_root(d, b, roots + (size_t)blockIdx.y * 5, budgets[blockIdx.y]);
-	if (threadIdx.x == 0) srch_fit(d);                                   // (the thread that wrote the counters)
+	if (threadIdx.x == 0) {                                              // (the thread that wrote the counters)
+		d.ctr[S_CLIP] = clip;                                            // the pool-full rule of this search: srch_fit
+		srch_fit(d);
+	}
 }
 
 // slot blockIdx.y's children, its waves striding over them; a workgroup whose first child is past the slot's batch -- a slot that
@@ -452,6 +466,43 @@ void kb_ss_walk(const FrontierDev *devs, SymBallView b, int32_t *out, int max_le
 {
 	const FrontierDev d = devs[blockIdx.x];
 	ssearch_walk(d, b, out + (size_t)blockIdx.x * (size_t)(1 + max_len), max_len);
+}
+
+// ---- deepening in the batch: slots whose pool is full go on by probes, all of them in one launch ----
+// A job as the device reads it (rk_deepen_job_t after the host's checks).  For the probe launch: the nodes node_first ..
+// node_first + node_count - 1 of slot `slot`'s pool, the words word_first .. word_first + word_count - 1 of `extra` moves, and
+// the slot's key keys[key_at]; for the walk: node_first = the node, word_first = the rank.
+struct SlotDeepenJob {
+	int32_t slot, extra;
+	uint32_t node_first, node_count, word_first, word_count, key_at, unused;
+};
+
+// Job blockIdx.y, its waves striding over the job's items as k_sd_probe's do over theirs: the same body (deepen_probe) on the rows
+// of the slot's pool, the stored action as the last move, none for node 1.  What is kept is the slot's key (DeepenKey).  A slot
+// has two keys and a job names the one of its round; the other is set to "none" here, where no launch of this round reads or
+// lowers it, so the round that follows finds it cleared.  A workgroup past the job's items returns before the tables are staged.
+// Nothing of a pool or of the ball is written.
+__global__ __launch_bounds__(256)
+void kb_sd_probe(const FrontierDev *devs, SymBallView b, const SlotDeepenJob *jobs, unsigned long long *keys)
+{
+	__shared__ uint32_t s_sym[SYM_LDS_DWORDS];
+	__shared__ u32x4 s_act[36];
+	const SlotDeepenJob j = jobs[blockIdx.y];
+	if (blockIdx.x == 0 && threadIdx.x == 0) keys[j.key_at ^ 1u] = DEEPEN_NO_KEY;
+	if ((size_t)blockIdx.x * 4 >= (size_t)j.node_count * deepen_groups(j.extra, j.word_first, j.word_count)) return;
+	const FrontierDev d = devs[j.slot];
+	const DeepenJob job{d.states + (size_t)j.node_first * 5, reinterpret_cast<const int8_t *>(d.pact) + j.node_first, 1 - (long long)j.node_first,
+	                    j.node_count, j.extra, j.word_first, j.word_count};
+	deepen_probe(b, job, sym_probe(s_sym, 256, s_act), (size_t)blockIdx.x * 4 + (size_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), (size_t)gridDim.x * 4,
+	             DeepenKey{keys + j.key_at, j.node_first});
+}
+
+// one wave per job: row blockIdx.x of `out` (n, 1 + max_len) = ssearch_deepen_walk of the job's slot, node, extra and rank
+__global__ __launch_bounds__(64)
+void kb_ss_deepen_walk(const FrontierDev *devs, SymBallView b, const SlotDeepenJob *jobs, int32_t *out, int max_len)
+{
+	const SlotDeepenJob j = jobs[blockIdx.x];
+	ssearch_deepen_walk(devs[j.slot], b, (int)j.node_first, j.extra, j.word_first, out + (size_t)blockIdx.x * (size_t)(1 + max_len), max_len);
 }
 
 __global__ __launch_bounds__(256)
@@ -504,7 +555,32 @@ struct rk_ssearch : FrontierPool, BallReader<rk_symball> {
 
 // S searches in lock-step: the slots (rk_frontier_host.h: FrontierSlots), their `hit` block and the ball they all read
 struct rk_ssearchb : FrontierSlots, BallReader<rk_symball> {
+	// what the host knows of a slot between a rk_sdeepenb_frontiers and the slot's next reset
+	struct Front {
+		int32_t lo = 0, hi = 0, size = 0;       // the newest complete level and the states stored
+		bool stopped = false;                   // the slot was done at that read: its pool and its level stand still
+		bool round_open = false;                // a job with new_round has chosen the slot's key since
+	};
 	uint32_t *hit = nullptr;                    // (n_slots, 12 x pops): slot s's words are its own
+	bool clip = false;                          // rk_sdeepenb_set: the pool-full rule of the resets to come
+	unsigned long long *keys = nullptr;         // (n_slots, 2): a slot's key of this round and the cleared one of the next
+	SlotDeepenJob *jobs_dev = nullptr;          // (n_slots): the jobs of the launch in flight
+	std::vector<SlotDeepenJob> jobs_host;       // what the copy to jobs_dev reads: left alone until jobs_sent has passed
+	hipEvent_t jobs_sent = nullptr;
+	std::vector<Front> front;
+	std::vector<uint8_t> key_of;                // per slot: which of its two keys the current round lowers
+
+	~rk_ssearchb() { if (jobs_sent != nullptr) (void)hipEventDestroy(jobs_sent); }
+
+	// `jobs` to the device block, behind whatever the stream holds; the host copy of the launch before is no longer read by then
+	int send_jobs(std::vector<SlotDeepenJob> &jobs, hipStream_t st)
+	{
+		RK_HIP(hipEventSynchronize(jobs_sent));
+		jobs_host.swap(jobs);
+		RK_HIP(hipMemcpyAsync(jobs_dev, jobs_host.data(), jobs_host.size() * sizeof(SlotDeepenJob), hipMemcpyHostToDevice, st));
+		RK_HIP(hipEventRecord(jobs_sent, st));
+		return RK_OK;
+	}
 };
 
 namespace {
@@ -533,18 +609,17 @@ int check_sym_states(const char *who, const void *d_states, size_t n)
 }
 
 // the range checks of a deepening launch and the launch itself
-int launch_deepen(const char *who, rk_symball *ball, DeepenJob job, hipStream_t st)
+int launch_deepen(const char *who, rk_symball *ball, DeepenJob job, uint32_t *best, hipStream_t st)
 {
 	if (job.extra < 1 || job.extra > DEEPEN_MAX_EXTRA) return fail(RK_EINVAL, "%s: extra %d outside 1..%d", who, job.extra, DEEPEN_MAX_EXTRA);
 	if ((unsigned long long)job.n * job.word_count > DEEPEN_MAX_PROBES)
 		return fail(RK_EINVAL, "%s: %zu states x %u words are more than the %llu probes of one launch", who, job.n, job.word_count, DEEPEN_MAX_PROBES);
-	if (!job.best || ((uintptr_t)job.best & 3u)) return fail(RK_EINVAL, "%s: d_best must be a 4-byte aligned device pointer", who);
+	if (!best || ((uintptr_t)best & 3u)) return fail(RK_EINVAL, "%s: d_best must be a 4-byte aligned device pointer", who);
 	const unsigned long long all = deepen_words(job.extra, -1);
 	if (job.n == 0 || job.word_count == 0 || job.word_first >= all) return RK_OK;
 	job.word_count = (uint32_t)std::min<unsigned long long>(job.word_count, all - job.word_first);
-	const uint32_t span = job.extra >= 3 ? DEEPEN_SPAN : 132u;
-	const size_t items = job.n * (size_t)((job.word_first + job.word_count - 1) / span - job.word_first / span + 1);
-	hipLaunchKernelGGL(k_sd_probe, dim3(sym_grid(items)), dim3(256), 0, st, ball->view, job);
+	const size_t items = job.n * (size_t)deepen_groups(job.extra, job.word_first, job.word_count);
+	hipLaunchKernelGGL(k_sd_probe, dim3(sym_grid(items)), dim3(256), 0, st, ball->view, job, best);
 	RK_HIP(hipGetLastError());
 	return RK_OK;
 }
@@ -701,7 +776,7 @@ int rk_sdeepen(rk_symball_t *ball, const int8_t *d_states, const int8_t *d_last,
 	if (!ball) return fail(RK_EINVAL, "rk_sdeepen: null ball");
 	if (!ball->built) return fail(RK_ESTATE, "rk_sdeepen: build the ball first");
 	if (int e = check_sym_states("rk_sdeepen", d_states, n)) return e;
-	return launch_deepen("rk_sdeepen", ball, DeepenJob{reinterpret_cast<const uint32_t *>(d_states), d_last, -1, n, extra, word_first, word_count, d_best},
+	return launch_deepen("rk_sdeepen", ball, DeepenJob{reinterpret_cast<const uint32_t *>(d_states), d_last, -1, n, extra, word_first, word_count}, d_best,
 	                     (hipStream_t)stream);
 }
 
@@ -835,8 +910,8 @@ int rk_sdeepen_nodes(rk_ssearch_t *h, int extra, size_t node_first, size_t node_
 		return fail(RK_EINVAL, "rk_sdeepen_nodes: nodes %zu..%zu outside the pool", node_first, node_first + node_count);
 	return launch_deepen("rk_sdeepen_nodes", h->ball,
 	                     DeepenJob{h->d.states + node_first * 5, reinterpret_cast<const int8_t *>(h->d.pact) + node_first, 1 - (long long)node_first,
-	                               node_count, extra, word_first, word_count, d_best},
-	                     (hipStream_t)stream);
+	                               node_count, extra, word_first, word_count},
+	                     d_best, (hipStream_t)stream);
 }
 
 long long rk_sdeepen_path(rk_ssearch_t *h, long long node, int extra, uint32_t rank, long long *h_actions, size_t max_len, void *stream)
@@ -863,10 +938,23 @@ int rk_ssearchb_create(rk_ssearchb_t **out, rk_symball_t *ball, int n_slots, siz
 	if (int e = FrontierSlots::check_create("rk_ssearchb_create", out, ball, n_slots, capacity_per_slot, pops)) return e;
 	if (!ball->built) return fail(RK_ESTATE, "rk_ssearchb_create: build the ball first");
 	rk_ssearchb *h = new rk_ssearchb();
-	if (int e = h->alloc("rk_ssearchb_create", n_slots, capacity_per_slot, pops, [&] { return h->pool.alloc(&h->hit, (size_t)n_slots * 12 * (size_t)pops); })) {
+	int e = h->alloc("rk_ssearchb_create", n_slots, capacity_per_slot, pops, [&] {
+		int a = h->pool.alloc(&h->hit, (size_t)n_slots * 12 * (size_t)pops);
+		if (!a) a = h->pool.alloc(&h->keys, (size_t)n_slots * 2);
+		if (!a) a = h->pool.alloc(&h->jobs_dev, (size_t)n_slots);
+		return a;
+	});
+	if (!e) {                                   // every key "none", so whichever of a slot's two a first round names is cleared
+		hipError_t he = hipMemset(h->keys, 0xFF, (size_t)n_slots * 2 * sizeof(unsigned long long));
+		if (he == hipSuccess) he = hipEventCreateWithFlags(&h->jobs_sent, hipEventDisableTiming);
+		if (he != hipSuccess) e = fail(RK_EHIP, "rk_ssearchb_create: %s", hipGetErrorString(he));
+	}
+	if (e) {
 		delete h;
 		return e;
 	}
+	h->front.resize((size_t)n_slots);
+	h->key_of.assign((size_t)n_slots, 0);
 	h->attach(ball);
 	*out = h;
 	return RK_OK;
@@ -883,7 +971,8 @@ int rk_ssearchb_reset(rk_ssearchb_t *h, int n, const int32_t *slots, const int8_
 	if (!h) return fail(RK_EINVAL, "rk_ssearchb_reset: null engine");
 	hipStream_t st = (hipStream_t)stream;
 	return h->reset("rk_ssearchb_reset", h->ball->built, n, slots, h_start_states, max_states, st, [&] {
-		hipLaunchKernelGGL(kb_ss_root, dim3(1, n), dim3(64), 0, st, h->devs, h->ball->view, h->slots_dev, h->roots_dev, h->budgets_dev);
+		for (int j = 0; j < n; j++) h->front[(size_t)slots[j]] = rk_ssearchb::Front{};     // (checked by now) a new pool: its level is not known
+		hipLaunchKernelGGL(kb_ss_root, dim3(1, n), dim3(64), 0, st, h->devs, h->ball->view, h->slots_dev, h->roots_dev, h->budgets_dev, h->clip ? 1 : 0);
 	});
 }
 
@@ -917,6 +1006,110 @@ int rk_ssearchb_export(rk_ssearchb_t *h, int slot, size_t first, size_t count, i
 {
 	if (!h) return fail(RK_EINVAL, "rk_ssearchb_export: null engine");
 	return h->export_rows("rk_ssearchb_export", slot, first, count, h_states, h_parents, h_actions, (hipStream_t)stream);
+}
+
+int rk_sdeepenb_set(rk_ssearchb_t *h, int on)
+{
+	if (!h) return fail(RK_EINVAL, "rk_sdeepenb_set: null engine");
+	h->clip = on != 0;
+	return RK_OK;
+}
+
+int rk_sdeepenb_frontiers(rk_ssearchb_t *h, long long *h_out, void *stream)
+{
+	if (!h || !h_out) return fail(RK_EINVAL, "rk_sdeepenb_frontiers: null argument");
+	const int32_t *c = nullptr;
+	if (int e = h->ctr_host.fetch(h->d.ctr, (size_t)h->n_slots * S_COUNT, h->ctr_spare.data(), (hipStream_t)stream, &c)) return e;
+	for (int s = 0; s < h->n_slots; s++, c += S_COUNT) {
+		h_out[2 * s] = c[S_LO];
+		h_out[2 * s + 1] = c[S_HI];
+		rk_ssearchb::Front &f = h->front[(size_t)s];
+		const bool open = f.stopped && f.round_open;                     // (a stopped slot stands still: a second read changes nothing)
+		f = rk_ssearchb::Front{c[S_LO], c[S_HI], c[F_SIZE], c[F_DONE] != 0 && c[F_SIZE] >= 1, false};
+		f.round_open = f.stopped && open;
+	}
+	return RK_OK;
+}
+
+int rk_sdeepenb_probe(rk_ssearchb_t *h, int n_jobs, const rk_deepen_job_t *h_jobs, void *stream)
+{
+	const char *who = "rk_sdeepenb_probe";
+	if (!h) return fail(RK_EINVAL, "%s: null engine", who);
+	if (!h->ball->built) return fail(RK_ESTATE, "%s: build the ball first", who);
+	if (n_jobs < 0 || n_jobs > h->n_slots) return fail(RK_EINVAL, "%s: %d jobs for %d slots", who, n_jobs, h->n_slots);
+	if (n_jobs == 0) return RK_OK;
+	if (!h_jobs) return fail(RK_EINVAL, "%s: null jobs", who);
+	std::vector<char> named((size_t)h->n_slots, 0);
+	std::vector<SlotDeepenJob> jobs((size_t)n_jobs);
+	unsigned long long probes = 0;
+	size_t items = 0;
+	for (int j = 0; j < n_jobs; j++) {
+		const rk_deepen_job_t &q = h_jobs[j];
+		if (q.slot < 0 || q.slot >= h->n_slots) return fail(RK_EINVAL, "%s: slot %d outside 0..%d", who, q.slot, h->n_slots - 1);
+		if (named[q.slot]) return fail(RK_EINVAL, "%s: slot %d is named twice", who, q.slot);
+		named[q.slot] = 1;
+		if (q.extra < 1 || q.extra > DEEPEN_MAX_EXTRA) return fail(RK_EINVAL, "%s: extra %d of slot %d outside 1..%d", who, q.extra, q.slot, DEEPEN_MAX_EXTRA);
+		const rk_ssearchb::Front &f = h->front[(size_t)q.slot];
+		if (!f.stopped) return fail(RK_ESTATE, "%s: slot %d had not stopped at the last rk_sdeepenb_frontiers (or was reset since)", who, q.slot);
+		if (q.node_count < 1 || q.node_first < (uint32_t)f.lo || q.node_first > (uint32_t)f.hi || q.node_count > (uint32_t)f.hi - q.node_first + 1u)
+			return fail(RK_EINVAL, "%s: nodes %u.. (%u of them) outside slot %d's frontier %d..%d", who, q.node_first, q.node_count, q.slot, f.lo, f.hi);
+		const uint32_t words = deepen_words(q.extra, f.lo == 1 ? -1 : 0);   // (node 1 is a level of its own and has no last move)
+		if (q.word_count < 1 || q.word_first >= words || q.word_count > words - q.word_first)
+			return fail(RK_EINVAL, "%s: words %u.. (%u of them) outside the %u words of %d moves of slot %d", who, q.word_first, q.word_count, words, q.extra, q.slot);
+		if (!q.new_round && !f.round_open) return fail(RK_ESTATE, "%s: the first job of slot %d since its reset must start a round (new_round)", who, q.slot);
+		probes += (unsigned long long)q.node_count * q.word_count;
+		if (probes > DEEPEN_MAX_PROBES) return fail(RK_EINVAL, "%s: more than the %llu probes of one launch", who, DEEPEN_MAX_PROBES);
+		items = std::max(items, (size_t)q.node_count * deepen_groups(q.extra, q.word_first, q.word_count));
+		jobs[(size_t)j] = SlotDeepenJob{q.slot, q.extra, q.node_first, q.node_count, q.word_first, q.word_count, 0u, 0u};
+	}
+	for (SlotDeepenJob &job : jobs) {                                    // nothing is refused from here on
+		const size_t s = (size_t)job.slot;
+		if (h_jobs[&job - jobs.data()].new_round) h->key_of[s] ^= 1u;    // the key the launches before left cleared
+		h->front[s].round_open = true;
+		job.key_at = (uint32_t)(2 * s + h->key_of[s]);
+	}
+	hipStream_t st = (hipStream_t)stream;
+	if (int e = h->send_jobs(jobs, st)) return e;
+	hipLaunchKernelGGL(kb_sd_probe, dim3(sym_grid(items), n_jobs), dim3(256), 0, st, h->devs, h->ball->view, h->jobs_dev, h->keys);
+	RK_HIP(hipGetLastError());
+	return RK_OK;
+}
+
+int rk_sdeepenb_keys(rk_ssearchb_t *h, unsigned long long *h_out, void *stream)
+{
+	if (!h || !h_out) return fail(RK_EINVAL, "rk_sdeepenb_keys: null argument");
+	hipStream_t st = (hipStream_t)stream;
+	std::vector<unsigned long long> both((size_t)h->n_slots * 2);
+	RK_HIP(hipMemcpyAsync(both.data(), h->keys, both.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+	RK_HIP(hipStreamSynchronize(st));
+	for (size_t s = 0; s < (size_t)h->n_slots; s++) h_out[s] = h->front[s].round_open ? both[2 * s + h->key_of[s]] : DEEPEN_NO_KEY;
+	return RK_OK;
+}
+
+int rk_sdeepenb_paths(rk_ssearchb_t *h, int n, const int32_t *slots, const long long *nodes, const int32_t *extras, const uint32_t *ranks,
+                             int32_t *h_out, int max_len, void *stream)
+{
+	const char *who = "rk_sdeepenb_paths";
+	if (!h) return fail(RK_EINVAL, "%s: null engine", who);
+	if (n < 0 || n > h->n_slots) return fail(RK_EINVAL, "%s: %d rows for %d slots", who, n, h->n_slots);
+	if (n == 0) return RK_OK;
+	if (!slots || !nodes || !extras || !ranks || !h_out) return fail(RK_EINVAL, "%s: null argument", who);
+	std::vector<SlotDeepenJob> jobs((size_t)n);
+	for (int j = 0; j < n; j++) {
+		if (slots[j] < 0 || slots[j] >= h->n_slots) return fail(RK_EINVAL, "%s: slot %d outside 0..%d", who, slots[j], h->n_slots - 1);
+		const rk_ssearchb::Front &f = h->front[(size_t)slots[j]];
+		if (!f.stopped) return fail(RK_ESTATE, "%s: slot %d had not stopped at the last rk_sdeepenb_frontiers (or was reset since)", who, slots[j]);
+		if (nodes[j] < 1 || nodes[j] > f.size) return fail(RK_EINVAL, "%s: node %lld outside 1..%d of slot %d", who, nodes[j], f.size, slots[j]);
+		if (extras[j] < 1 || extras[j] > DEEPEN_MAX_EXTRA) return fail(RK_EINVAL, "%s: extra %d outside 1..%d", who, extras[j], DEEPEN_MAX_EXTRA);
+		jobs[(size_t)j] = SlotDeepenJob{slots[j], extras[j], (uint32_t)nodes[j], 1u, ranks[j], 1u, 0u, 0u};
+	}
+	hipStream_t st = (hipStream_t)stream;
+	int sent = RK_OK;
+	const int e = h->paths(who, h->ball->built, h_out, max_len, st, [&] {
+		sent = h->send_jobs(jobs, st);
+		if (sent == RK_OK) hipLaunchKernelGGL(kb_ss_deepen_walk, dim3(n), dim3(64), 0, st, h->devs, h->ball->view, h->jobs_dev, h->walk, max_len);
+	}, n);
+	return sent != RK_OK ? sent : e;
 }
 
 }  // extern "C"

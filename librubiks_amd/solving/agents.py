@@ -1100,6 +1100,23 @@ class _BallSearchBatch(_ffi.Owner):
 		self.lengths = np.full(n, -1, np.int64)
 		self._queues = [deque() for _ in range(n)]
 		self._arrays = [None] * n if keep_arrays else None
+		self._deep = {}                     # slot -> what a search that goes on past its full pool keeps on the host (`_pool_full`)
+
+	# What an engine that goes on past a full pool hooks into the loop of `search` (as `_PoolSearch` has `_fewer_pops` / `_pool_full`);
+	# here nothing does, and `_deep` stays empty.
+	def _prepare(self, h):
+		"""Before the first slot of a call is started."""
+
+	def _pool_full(self, s: int, i: int) -> bool:
+		"""Slot `s` stopped state `i` with reason 5, its status, queue and pool are recorded.  True: the slot stays held (in `_deep`)."""
+		return False
+
+	def _deepen_poll(self, h, holds: np.ndarray) -> list:
+		"""At a poll, after the status was read: the slots of `_deep` that are finished, their results recorded."""
+		return []
+
+	def _deepen_launch(self, h):
+		"""One launch for the slots of `_deep`, behind the burst of the others."""
 
 	sizes = property(lambda self: self.status[:, 2])
 	iterations = property(lambda self: self.status[:, 3])
@@ -1143,8 +1160,9 @@ class _BallSearchBatch(_ffi.Owner):
 
 	@no_grad
 	def search(self, states, time_limit: float = None, max_states=None, keep_arrays: bool = False) -> np.ndarray:
-		"""bool (n,): whether each state's search met the ball.  `max_states`: one budget for all, or one per state (n,);
-		`time_limit` bounds the whole call: searches still running or waiting when it passes come back False with stop reason 0."""
+		"""bool (n,): whether each state has a queue (`lengths` >= 0): its search met the ball, or went on past its full pool and
+		found one.  `max_states`: one budget for all, or one per state (n,); `time_limit` bounds the whole call: searches still
+		running or waiting when it passes come back False with stop reason 0 (5 for one that was past its full pool)."""
 		t0 = time.perf_counter()
 		time_limit = time_limit or 1e10         # (an exact search may run without either limit)
 		self._is2024 = cube.get_is2024()
@@ -1169,6 +1187,7 @@ class _BallSearchBatch(_ffi.Owner):
 		S, K = self.searches, 12 * self.pops
 		cap = self.capacity or min(int(budgets.max()) + K, self.default_capacity)
 		h = self._engine(max(2, min(cap, self.MAX_CAPACITY)))
+		self._prepare(h)
 		holds = np.full(S, -1, np.int64)        # the input position every slot runs, -1: free
 		waiting = 0                             # the next input position to start
 		st = np.zeros((S, 10), np.int64)
@@ -1177,7 +1196,9 @@ class _BallSearchBatch(_ffi.Owner):
 				_ffi.check(read_status(h, st.ctypes.data, stream))
 				if st[holds >= 0, 6].any():
 					raise _ffi.RubiksHipError(f"ball search engine error codes {st[holds >= 0, 6].tolist()}")
-				done = np.nonzero((holds >= 0) & (st[:, 0] != 0))[0]
+				pool = holds >= 0                   # the held slots that are in their pool phase
+				pool[list(self._deep)] = False
+				done = np.nonzero(pool & (st[:, 0] != 0))[0]
 				if len(done):
 					paths = self._paths(h, self.PATH_WORDS) if st[done, 1].any() else None
 					if paths is not None and paths[done, 0].max() > self.PATH_WORDS:
@@ -1192,7 +1213,9 @@ class _BallSearchBatch(_ffi.Owner):
 							self._queues[i] = deque(paths[s, 1:1 + paths[s, 0]].tolist())
 						if keep_arrays:
 							self._arrays[i] = self._export(h, s, int(st[s, 2]))
-						holds[s] = -1
+						if st[s, 5] != 5 or not self._pool_full(s, i):
+							holds[s] = -1
+				holds[self._deepen_poll(h, holds)] = -1
 				if self.on_poll is not None:
 					self.on_poll(self.status)
 				late = time.perf_counter() - t0 >= time_limit
@@ -1207,10 +1230,14 @@ class _BallSearchBatch(_ffi.Owner):
 				live = holds >= 0
 				if late or not live.any():
 					break
-				room = int((budgets[holds[live]] - st[live, 2]).min())
-				burst = eng.burst(self.poll, room, K)
-				_ffi.check(run(h, burst, stream))
-				self.lockstep_iterations += burst
+				live[list(self._deep)] = False      # every pass: the burst of the slots that still pop, then one launch for the others
+				if live.any():
+					room = int((budgets[holds[live]] - st[live, 2]).min())
+					burst = eng.burst(self.poll, room, K)
+					_ffi.check(run(h, burst, stream))
+					self.lockstep_iterations += burst
+				if self._deep:
+					self._deepen_launch(h)
 			live = np.nonzero(holds >= 0)[0]
 			if len(live):                       # out of time: what the searches had reached, stop reason 0; then the slots are put to rest
 				for s in live.tolist():
@@ -1222,10 +1249,11 @@ class _BallSearchBatch(_ffi.Owner):
 					for i in range(waiting, n):
 						self._arrays[i] = self._export(h, 0, 0)
 				self._start(h, live, np.repeat(_SOLVED20[None], len(live), axis=0), np.ones(len(live), np.int64))
+			self._deep = {}
 		except Exception:
 			self._free()                        # slots in an unknown state: the next call starts from a new engine
 			raise
-		return self.status[:, 1] != 0
+		return self.lengths >= 0
 
 	def action_queue_of(self, i: int) -> deque:
 		return deque(self._queues[i])
@@ -1290,6 +1318,17 @@ class DeviceSymBallSearchBatch(_BallSearchBatch):
 	`capacity_exhausted[i]`) are `DeviceBallSearchBatch`'s.  `meeting_depths` comes from the symmetry ball's level boundaries;
 	`meeting_nodes` (status word 9) is the node in the ball of the REPRESENTATIVE of the state every search met, 0 for none.
 
+	`deepen=E` > 0: a slot whose pool is full goes on as `DeviceSymBallSearch(deepen=E)` does, beside the slots that
+	still pop, and every state gets bit for bit what that agent gives it alone in a pool of the slot's size.  A slot then pops only
+	as many nodes as surely fit and ends its pool phase when not even one does, so its pool and levels are those of `pops=1`.
+	Rounds e = 1..E probe every word of e moves behind the nodes of its newest complete level L; the first round with a hit
+	answers with the lowest node that has a hit and that node's lowest word, a queue of the optimal length L + e + radius.  All
+	deepening slots share one probe launch per poll, of at most `ball._launch_cap()` probes; slots may be in different rounds in
+	it, and how the cap is shared shows in no result.  `search` returns `lengths >= 0`; `deepened` (n,) is the round that answered
+	(0: the pool sufficed, or nothing answered), `probes` the probes the call issued.  `status[i]` of a deepened state is what
+	the pool phase left -- not won, stop reason 5, no meeting --, `arrays(i)` its pool with the partial next level, and
+	`iterations[i]` depends on `pops`.  A search that a meeting, its budget or an exhausted graph ends is never deepened.
+
 	`pops` = 2 048 by default is provisional, taken over from `DeviceBallSearchBatch`.  benchmarks/symball_search_batch.py sweeps
 	512 / 2 048 / 16 384 at 16 / 64 / 256 searches and names the value it favours at 64 on its mixed set; its one run so far
 	(profiles/r16_symball_search_batch.json) is no reason to move: the mixed set, whose time is that of its 16-move starts, favours
@@ -1297,11 +1336,92 @@ class DeviceSymBallSearchBatch(_BallSearchBatch):
 	"""
 	_entries = "rk_ssearchb"
 	_ball_type = DeviceSymBall
+	_NO_KEY = 0xFFFFFFFFFFFFFFFF            # rk_sdeepenb_keys: no hit
 
-	def __init__(self, ball: DeviceSymBall, searches: int = 64, pops: int = 2_048, capacity: int = None, poll: int = 8):
+	def __init__(self, ball: DeviceSymBall, searches: int = 64, pops: int = 2_048, capacity: int = None, poll: int = 8, deepen: int = 0):
+		self.deepen = eng.int_in("deepen", deepen, 0, DeviceSymBall.MAX_EXTRA)
 		super().__init__(ball, searches, pops, capacity, poll)
 
+	def _results(self, n: int, keep_arrays: bool):
+		super()._results(n, keep_arrays)
+		self.deepened = np.zeros(n, np.int64)
+		self.probes = 0
+		self._sent = []                     # (slot, round) of the jobs of the launch in flight
+
 	meeting_nodes = property(lambda self: self.status[:, 9])
+
+	def _prepare(self, h):
+		_ffi.check(_ffi.lib().rk_sdeepenb_set(h, int(self.deepen > 0)))       # the pool-full rule of the slots this call starts; no launch
+
+	def _pool_full(self, s: int, i: int) -> bool:
+		if not self.deepen:
+			return False
+		self._deep[s] = None                # its cursor is made at this poll, once the frontiers are read
+		return True
+
+	def _deepen_poll(self, h, holds: np.ndarray) -> list:
+		if not self._deep:
+			return []
+		stream = _ffi.stream_ptr()
+		if any(c is None for c in self._deep.values()):
+			level = np.zeros((self.searches, 2), np.int64)
+			_ffi.check(_ffi.lib().rk_sdeepenb_frontiers(h, level.ctypes.data, stream))
+			for s, c in self._deep.items():
+				if c is None:                   # round, next node, next word, the frontier, "the next job starts a round"
+					lo, hi = level[s].tolist()
+					self._deep[s] = [1, lo, 0, lo, hi, 1]
+		if not self._sent:
+			return []
+		keys = np.zeros(self.searches, np.uint64)
+		_ffi.check(_ffi.lib().rk_sdeepenb_keys(h, keys.ctypes.data, stream))
+		# After any launch a key is final: the nodes below the job's were probed with all their words and had no hit, and the job
+		# was either whole nodes with all their words or one node's words in rising order.
+		hits = [(s, e, int(keys[s]) >> 32, int(keys[s]) & 0xFFFFFFFF) for s, e in self._sent if int(keys[s]) != self._NO_KEY]
+		over = [s for s, e in self._sent if int(keys[s]) == self._NO_KEY and self._deep[s][0] > self.deepen]      # no round up to `deepen` hit
+		self._sent = []
+		if hits:
+			paths = self._deepen_paths(h, hits, self.PATH_WORDS)
+			if paths[:, 0].max() > self.PATH_WORDS:
+				paths = self._deepen_paths(h, hits, 4096)
+			for (s, e, node, rank), row in zip(hits, paths):
+				i = int(holds[s])
+				if row[0] < 0:
+					raise _ffi.RubiksHipError(f"rk_sdeepenb_paths: word {rank} of {e} moves from node {node} of state {i} cannot be walked ({int(row[0])})")
+				self.lengths[i] = row[0]
+				self._queues[i] = deque(row[1:1 + row[0]].tolist())
+				self.deepened[i] = e
+		finished = [s for s, *_ in hits] + over
+		for s in finished:
+			del self._deep[s]
+		return finished
+
+	def _deepen_paths(self, h, hits: list, max_len: int) -> np.ndarray:
+		slots, extras, nodes, ranks = (np.array(col, dtype) for col, dtype in zip(zip(*hits), (np.int32, np.int32, np.int64, np.uint32)))
+		out = np.zeros((len(hits), 1 + max_len), np.int32)
+		_ffi.check(_ffi.lib().rk_sdeepenb_paths(h, len(hits), slots.ctypes.data, nodes.ctypes.data, extras.ctypes.data, ranks.ctypes.data, out.ctypes.data,
+		                                       max_len, _ffi.stream_ptr()))
+		return out
+
+	def _deepen_launch(self, h):
+		"""One launch for the deepening slots: the cap on the probes of a launch is shared out evenly; a slot's job is as many whole
+		nodes with all their words as its share takes, or, where not even one node's words fit, the next words of one node."""
+		cap = self.ball._launch_cap()
+		slots = sorted(self._deep)[:cap]
+		share = cap // len(slots)
+		jobs = np.zeros((len(slots), 8), np.uint32)                          # rk_deepen_job_t
+		for j, s in enumerate(slots):
+			e, at, first, lo, hi, new = self._deep[s]
+			words = (12 if lo == 1 else 11) * 11 ** (e - 1)                 # (node 1 has no last move; it is a level of its own)
+			if first == 0 and share >= words:
+				nodes, count = min(share // words, hi + 1 - at), words
+			else:
+				nodes, count = 1, min(share, words - first)
+			jobs[j] = (s, e, at, nodes, first, count, new, 0)
+			self.probes += nodes * count
+			self._sent.append((s, e))
+			at, first = (at + nodes, 0) if first + count == words else (at, first + count)
+			self._deep[s] = [e + 1, lo, 0, lo, hi, 1] if at > hi else [e, at, first, lo, hi, 0]
+		_ffi.check(_ffi.lib().rk_sdeepenb_probe(h, len(slots), jobs.ctypes.data, _ffi.stream_ptr()))
 
 	def __str__(self):
 		return (f"Breadth-first searches to a symmetry-reduced goal ball x{self.searches} (device, radius={self.ball.radius}, "
