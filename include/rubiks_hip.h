@@ -549,6 +549,26 @@ int rk_symball_depth(rk_symball_t *h, const int8_t *d_states, size_t n, int32_t 
  * ball that passed its build).  One launch; stream-ordered, no synchronisation. */
 int rk_symball_solve(rk_symball_t *h, const int8_t *d_states, size_t n, int32_t *d_lengths, int8_t *d_actions, int32_t *d_error,
                      void *stream);
+/* Exact values for the children of an Autodidactic-Iteration rollout (train.py:301-314: the value of every child, before the
+ * reward is added and the maximum over twelve siblings is taken).  d_states int8 (m12, 20) are rk_rollout_fanout's d_children
+ * where they lie, m12 a multiple of 12 and at most INT32_MAX; g is the goal reward of the method (0 for reward0, else 1).  With
+ * c = rk_symball_depth's answer for a row (0..radius, -1 outside the ball):
+ *   d_depth   int8 (m12)      c of every row
+ *   d_values  float32 (m12)   V*(0) = 0, V*(c) = g - (c - 1) for 1 <= c <= radius, written at the rows with c >= 0; the rows with
+ *                             c < 0 are NOT TOUCHED (the caller scatters the net's values there)
+ *   d_rows    int32 (m12)     the indices of the rows with c < 0 IN ASCENDING ORDER, the first d_count[0] entries
+ *   d_outside int8 (m12, 20)  those rows' states in the same order, the first d_count[0] rows: the net's batch, no gather needed
+ *   d_count   int32 (1)       how many rows lie outside the ball
+ * V* is the fixed point of V(s) = max_a [r(s.a) + V(s.a)] with V(solved) = 0.  The order of d_rows is part of the contract (the
+ * net's slices are cut from it): the compaction is a scan over tiles of 256 rows, not a counter.  d_scratch: device memory of
+ * rk_symball_child_values_scratch_bytes(m12) bytes (one word per tile), 4-byte aligned as every other pointer.  Four launches --
+ * a wave per child as rk_symball_depth, the tiles' counts, their prefix, the write --; the ball is only read.  Stream-ordered, no
+ * synchronisation.  RK_EINVAL for null or misaligned pointers, m12 no multiple of 12 or above INT32_MAX, too little scratch;
+ * RK_ESTATE for a ball that is not built; all before any launch. */
+int rk_symball_child_values(rk_symball_t *h, const int8_t *d_states, size_t m12, float g, int8_t *d_depth, float *d_values, int32_t *d_rows,
+                            int8_t *d_outside, int32_t *d_count, void *d_scratch, size_t scratch_bytes, void *stream);
+/* Bytes of d_scratch for m12 children: 4 * ceil(m12 / 256); RK_EINVAL above INT32_MAX.  Touches no device. */
+long long rk_symball_child_values_scratch_bytes(size_t m12);
 /* Depth-first probes past the ball's radius: for every DEVICE state i of d_states int8 (n, 20) and every word of `extra` moves
  * (1..8) whose rank lies in [word_first, word_first + word_count), the word is applied to the state, the result canonicalised and
  * looked up in the ball; if the ball holds it, atomicMin(d_best[i], rank).  A word is a sequence of actions 0..11 in which no

@@ -20,8 +20,22 @@ from librubiks_amd import gpu, no_grad, _ffi, cube
 
 @no_grad
 def adi_traindata(net, rollout_games: int, rollout_depth: int, alpha: float, reward_method: str = "lapanfix",
-                  ff_batches: int = 1, fused_first_layer=False):
+                  ff_batches: int = 1, fused_first_layer=False, ball=None):
+	"""
+	`ball`: a `DeviceSymBall(R)` (built at first use), or None for the reference's targets.  With a ball, a child whose orbit the ball
+	holds at depth c gets, as its value BEFORE the reward is added, the exact V*(0) = 0, V*(c) = g - (c - 1) for 1 <= c <= R, where g
+	is the method's goal reward (0 for reward0, else 1): the fixed point of V(s) = max_a [r(s.a) + V(s.a)] with V(solved) = 0.
+	lapanfix pins that value itself; for paper, schultzfix and reward0 it is the convention this option adopts.  The net runs only on
+	the children outside the ball, compacted on the device in ascending row order and cut into ceil(count / ff_batches) rows a call;
+	with no child outside it is not called at all.  Everything behind the children's values -- the rewards, the first maximum over
+	twelve siblings, the lapanfix / schultzfix overrides, the loss weights -- is unchanged, so every state within R - 1 moves of
+	solved gets its exact value target and the lowest optimal move as its policy target.  Works in both representations.
+	"""
 	assert reward_method in ("paper", "lapanfix", "schultzfix", "reward0")
+	if ball is not None:
+		from librubiks_amd.solving.agents import DeviceSymBall
+		if not isinstance(ball, DeviceSymBall):
+			raise TypeError(f"ball must be a DeviceSymBall or None, not {type(ball).__name__}")
 	_ffi.require_gpu()
 	is2024 = cube.get_is2024()             # 6x8x6: the same walks in 20-byte form, the net's rows from the fused converter + encoder
 	if fused_first_layer and not is2024:
@@ -41,25 +55,38 @@ def adi_traindata(net, rollout_games: int, rollout_depth: int, alpha: float, rew
 	                      torch.tensor(-1.0, device=gpu))                                         # train.py:294-296
 	# value of every child, in slices so that the one-hot batch stays bounded                      train.py:301-303
 	values = torch.empty(12 * n, dtype=torch.float32, device=gpu)
-	step = -(-12 * n // max(1, ff_batches))
+	if ball is None:
+		net_states, rows = substates, None
+	else:
+		# exact values where the ball holds the child's orbit; the net's batch is the rest, compacted in row order
+		_, _, rows, net_states = cube.device.ball_child_values(ball, substates, 0.0 if reward_method == "reward0" else 1.0, values)
+		rows = rows.long()
+	m = len(net_states)
+
+	def put(lo, hi, v):
+		if rows is None:
+			values[lo:hi] = v
+		else:
+			values[rows[lo:hi]] = v
+	step = max(1, -(-m // max(1, ff_batches)))
 	if fused_first_layer:
 		# the net's first Linear reads the 2.7 M children's 20-byte states directly: the (12 n, 480) one-hot never exists
 		from librubiks_amd.oh_linear import fused_net
 		from_states = fused_net(net, fused_first_layer)
-		for lo in range(0, 12 * n, step):
-			hi = min(lo + step, 12 * n)
-			values[lo:hi] = from_states(substates[lo:hi], policy=False, value=True).reshape(-1).float()
+		for lo in range(0, m, step):
+			hi = min(lo + step, m)
+			put(lo, hi, from_states(net_states[lo:hi], policy=False, value=True).reshape(-1).float())
 	else:
 		from librubiks_amd.solving.agents import _oh_dtype
 		oh_dtype = _oh_dtype(net)                  # a bf16 net gets bf16 rows straight from the kernel (0 / 1 are exact)
-		buf = torch.empty((min(step, 12 * n), 480 if is2024 else 288), dtype=oh_dtype, device=gpu)
-		for lo in range(0, 12 * n, step):
-			hi = min(lo + step, 12 * n)
+		buf = torch.empty((min(step, m), 480 if is2024 else 288), dtype=oh_dtype, device=gpu)
+		for lo in range(0, m, step):
+			hi = min(lo + step, m)
 			if is2024:
-				cube.device.as_oh(substates[lo:hi], buf[:hi - lo], oh_dtype)
+				cube.device.as_oh(net_states[lo:hi], buf[:hi - lo], oh_dtype)
 			else:
-				cube.device.to686(substates[lo:hi], oh_dtype, buf[:hi - lo])
-			values[lo:hi] = net(buf[:hi - lo], policy=False, value=True).reshape(-1).float()
+				cube.device.to686(net_states[lo:hi], oh_dtype, buf[:hi - lo])
+			put(lo, hi, net(buf[:hi - lo], policy=False, value=True).reshape(-1).float())
 	values = (values + rewards).reshape(-1, 12)                                                   # train.py:313-314
 	policy_targets = torch.argmax(values, dim=1)
 	value_targets = values[torch.arange(n, device=gpu), policy_targets]

@@ -30,6 +30,9 @@
 //   k_sb_depth    a wave per query: canonical form, read-only probe (probe_find), depth from the level boundaries; -1 outside
 //   k_sb_solve    the same, then the descent: at each step the lowest action whose child lies one level nearer (12 canonical
 //                 forms and probes at most), bounded by the radius; a step without such a child sets the error word
+//   k_sb_child_values   k_sb_depth for the 12 n children of an ADI rollout (rk_symball_child_values): the depth as a byte and the exact
+//                 value V*(depth) beside it; then k_sb_outside_count, _scan, _write compact the rows OUTSIDE the ball -- the net's
+//                 batch -- in ascending order
 //
 // The search (rk_ssearch_*) is rk_ball.hip's rk_bsearch_* -- a one-sided breadth-first search from a start, in a pool and table of
 // its own that hold RAW states with parent and action -- with one difference: "the ball holds this child" is "the symmetry ball
@@ -200,6 +203,84 @@ void k_sb_solve(SymBallView b, const uint32_t *queries, size_t n, int32_t *lengt
 		if (lane == 0) lengths[q] = ok ? len : -1;
 		for (int k = (ok ? len : 0) + lane; k < b.radius; k += 64) row[k] = -1;
 	}
+}
+
+// ---- exact values of the children of an ADI rollout (rk_symball_child_values) ----
+// k_sb_depth's loop with an int8 answer and V*(c) beside it: 0 at c = 0, g - (c - 1) at 1 <= c <= radius (small integers: exact
+// in float32); values[q] of a row outside the ball is not touched.
+__global__ __launch_bounds__(256)
+void k_sb_child_values(SymBallView b, const uint32_t *states, size_t n, float g, int8_t *depth, float *values)
+{
+	__shared__ uint32_t s_sym[SYM_LDS_DWORDS];
+	const SymProbe sp = sym_probe(s_sym, 256);
+	for (size_t q = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6); q < n; q += (size_t)gridDim.x * 4) {
+		uint32_t x[5];
+		load5(states + q * 5, x);
+		const int lvl = sb_level(b, sp, x);
+		if (sp.lane == 0) {
+			depth[q] = (int8_t)lvl;
+			if (lvl >= 0) values[q] = lvl == 0 ? 0.0f : g - (float)(lvl - 1);
+		}
+	}
+}
+
+// The rows outside the ball in ascending order, by a scan and not by a counter: the order is what the net's slices are cut from.
+// A tile is ASCAN rows, a thread per row.  Three launches and no waiting inside any of them: the tiles' counts, their exclusive
+// prefix in place by ONE workgroup (a tile count per 256 rows: 10 547 words for the 2.7 M children of a reference rollout), then
+// every tile ranks its rows again (block_rank256) and writes the row index and the 20 bytes of the state at base + rank.
+__global__ __launch_bounds__(ASCAN)
+void k_sb_outside_count(const int8_t *depth, size_t n, int32_t *tile)
+{
+	__shared__ int s_wave[4];
+	const size_t q = (size_t)blockIdx.x * ASCAN + threadIdx.x;
+	int total;
+	(void)block_rank256(q < n && depth[q] < 0, s_wave, &total);
+	if (threadIdx.x == 0) tile[blockIdx.x] = total;
+}
+
+constexpr int SB_SCAN_THREADS = 1024;
+
+__global__ __launch_bounds__(SB_SCAN_THREADS)
+void k_sb_outside_scan(int32_t *tile, int tiles, int32_t *count)
+{
+	__shared__ int s_sum[SB_SCAN_THREADS];
+	const int t = threadIdx.x;
+	const int per = (tiles + SB_SCAN_THREADS - 1) / SB_SCAN_THREADS;         // (at most 2^23 tiles: t * per stays far below 2^31)
+	const int lo = min(t * per, tiles), hi = min(lo + per, tiles);
+	int sum = 0;
+	for (int i = lo; i < hi; i++) sum += tile[i];
+	s_sum[t] = sum;
+	__syncthreads();
+	for (int off = 1; off < SB_SCAN_THREADS; off <<= 1) {
+		const int v = t >= off ? s_sum[t - off] : 0;
+		__syncthreads();
+		s_sum[t] += v;
+		__syncthreads();
+	}
+	int run = s_sum[t] - sum;
+	for (int i = lo; i < hi; i++) {
+		const int c = tile[i];
+		tile[i] = run;
+		run += c;
+	}
+	if (t == SB_SCAN_THREADS - 1) *count = s_sum[t];
+}
+
+__global__ __launch_bounds__(ASCAN)
+void k_sb_outside_write(const int8_t *depth, const uint32_t *states, size_t n, const int32_t *tile, int32_t *rows, uint32_t *outside)
+{
+	__shared__ int s_wave[4];
+	const size_t q = (size_t)blockIdx.x * ASCAN + threadIdx.x;
+	const bool out = q < n && depth[q] < 0;
+	int total;
+	const int r = block_rank256(out, s_wave, &total);
+	if (!out) return;
+	const size_t at = (size_t)tile[blockIdx.x] + (size_t)r;                  // < the count <= n: the caller's arrays hold n rows
+	rows[at] = (int32_t)q;
+	uint32_t x[5];
+	load5(states + q * 5, x);
+	#pragma unroll
+	for (int j = 0; j < 5; j++) outside[at * 5 + j] = x[j];
 }
 
 // ---- shortening action queues against the symmetry ball (rk_sshorten; the DP and everything ball-independent: rk_shorten_dev.h) ----
@@ -764,6 +845,42 @@ int rk_symball_solve(rk_symball_t *h, const int8_t *d_states, size_t n, int32_t 
 	if (!d_actions && h->d.radius > 0) return fail(RK_EINVAL, "rk_symball_solve: null pointer");
 	hipLaunchKernelGGL(k_sb_solve, dim3(sym_grid(n)), dim3(256), 0, st, h->view, reinterpret_cast<const uint32_t *>(d_states), n, d_lengths,
 	                   d_actions, d_error);
+	RK_HIP(hipGetLastError());
+	return RK_OK;
+}
+
+long long rk_symball_child_values_scratch_bytes(size_t m12)
+{
+	if (m12 > (size_t)INT32_MAX) return fail(RK_EINVAL, "rk_symball_child_values_scratch_bytes: %zu children in one call", m12);
+	return (long long)blocks(m12, ASCAN) * (long long)sizeof(int32_t);
+}
+
+int rk_symball_child_values(rk_symball_t *h, const int8_t *d_states, size_t m12, float g, int8_t *d_depth, float *d_values, int32_t *d_rows,
+                            int8_t *d_outside, int32_t *d_count, void *d_scratch, size_t scratch_bytes, void *stream)
+{
+	const char *who = "rk_symball_child_values";
+	if (!h) return fail(RK_EINVAL, "%s: null ball", who);
+	if (!h->built) return fail(RK_ESTATE, "%s: build the ball first", who);
+	if (m12 > (size_t)INT32_MAX) return fail(RK_EINVAL, "%s: %zu children in one call", who, m12);
+	if (m12 % N_ACTIONS) return fail(RK_EINVAL, "%s: %zu children are not twelve per state", who, m12);
+	if (!d_count) return fail(RK_EINVAL, "%s: null pointer", who);
+	if (m12 != 0 && (!d_states || !d_depth || !d_values || !d_rows || !d_outside || !d_scratch)) return fail(RK_EINVAL, "%s: null pointer", who);
+	if (((uintptr_t)d_states | (uintptr_t)d_values | (uintptr_t)d_rows | (uintptr_t)d_outside | (uintptr_t)d_count | (uintptr_t)d_scratch) & 3u)
+		return fail(RK_EINVAL, "%s: device pointers must be 4-byte aligned", who);
+	const unsigned tiles = blocks(m12, ASCAN);
+	if (scratch_bytes < (size_t)tiles * sizeof(int32_t))
+		return fail(RK_EINVAL, "%s: %zu bytes of scratch, %zu needed", who, scratch_bytes, (size_t)tiles * sizeof(int32_t));
+	hipStream_t st = (hipStream_t)stream;
+	if (m12 == 0) {
+		RK_HIP(hipMemsetAsync(d_count, 0, sizeof(int32_t), st));
+		return RK_OK;
+	}
+	const uint32_t *states = reinterpret_cast<const uint32_t *>(d_states);
+	int32_t *tile = static_cast<int32_t *>(d_scratch);
+	hipLaunchKernelGGL(k_sb_child_values, dim3(sym_grid(m12)), dim3(256), 0, st, h->view, states, m12, g, d_depth, d_values);
+	hipLaunchKernelGGL(k_sb_outside_count, dim3(tiles), dim3(ASCAN), 0, st, d_depth, m12, tile);
+	hipLaunchKernelGGL(k_sb_outside_scan, dim3(1), dim3(SB_SCAN_THREADS), 0, st, tile, (int)tiles, d_count);
+	hipLaunchKernelGGL(k_sb_outside_write, dim3(tiles), dim3(ASCAN), 0, st, d_depth, states, m12, tile, d_rows, reinterpret_cast<uint32_t *>(d_outside));
 	RK_HIP(hipGetLastError());
 	return RK_OK;
 }

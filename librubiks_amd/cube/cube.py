@@ -412,6 +412,46 @@ class device:
 		return states, state_flags, children, child_flags
 
 	@staticmethod
+	def ball_child_values(ball, substates: torch.Tensor, goal_reward: float, values: torch.Tensor = None):
+		"""Exact values of the children of a rollout that a built symmetry ball holds (engine rk_symball_child_values; train.py:301-314):
+		substates int8 (12 n, 20), the children of `rollout_fanout`; goal_reward 0.0 for reward0, else 1.0 ->
+		  values          float32 (12 n,): V*(0) = 0, V*(c) = goal_reward - (c - 1) at the rows of ball depth c >= 1; the rows outside the
+		                  ball are not written (`values`, if given, keeps what it held there; a new tensor is uninitialised there)
+		  depths          int8 (12 n,): the ball depth of every row, -1 outside
+		  rows            int32 (count,): the rows outside the ball in ascending order
+		  outside_states  int8 (count, 20): substates[rows], the net's batch
+		All on the device.  Reading the count is the call's one host read."""
+		from librubiks_amd.solving.agents import DeviceSymBall
+		if not isinstance(ball, DeviceSymBall):
+			raise TypeError(f"ball must be a DeviceSymBall, not {type(ball).__name__}")
+		_ffi.require_gpu()
+		_check_dev(substates, torch.int8, "substates")
+		m12 = len(substates)
+		if substates.numel() != 20 * m12 or m12 % 12:
+			raise ValueError(f"substates must have shape (12 n, 20), got {tuple(substates.shape)}")
+		ball.build()
+		if values is None:
+			values = torch.empty(m12, dtype=torch.float32, device=gpu)
+		else:
+			_check_dev(values, torch.float32, "values")
+			if values.numel() != m12:
+				raise ValueError(f"{m12} children but {values.numel()} values")
+		lib = _ffi.lib()
+		depths = torch.empty(m12, dtype=torch.int8, device=gpu)
+		rows = torch.empty(m12, dtype=torch.int32, device=gpu)
+		outside = torch.empty((m12, 20), dtype=torch.int8, device=gpu)
+		count = torch.empty(1, dtype=torch.int32, device=gpu)
+		need = lib.rk_symball_child_values_scratch_bytes(m12)
+		if need < 0:
+			_ffi.check(int(need))
+		scratch = torch.empty(max(int(need), 4), dtype=torch.uint8, device=gpu)
+		_ffi.check(lib.rk_symball_child_values(ball._h, substates.data_ptr(), m12, float(goal_reward), depths.data_ptr(), values.data_ptr(),
+		                                       rows.data_ptr(), outside.data_ptr(), count.data_ptr(), scratch.data_ptr(), scratch.numel(),
+		                                       _ffi.stream_ptr()))
+		k = int(count.item())
+		return values, depths, rows[:k], outside[:k]
+
+	@staticmethod
 	def as_oh(states: torch.Tensor, out: torch.Tensor = None, dtype: torch.dtype = torch.float32) -> torch.Tensor:
 		"""One-hot (n, 480 | 288) of `dtype` (float32, float16 or bfloat16)   (cube.py:265-277, 363-369)."""
 		_ffi.require_gpu()
