@@ -814,6 +814,46 @@ int rk_greedy_status(rk_greedy_t *h, long long *h_status, void *stream);
  * uint8 (n_games, max_states) of which the first `moves made` of a row are defined.  Synchronises. */
 int rk_greedy_export(rk_greedy_t *h, long long *h_status, long long *h_steps, uint8_t *h_actions, void *stream);
 
+/* ---- device-resident beam search guided by a value net (rk_beam_*), optionally ending at the symmetry ball ----
+ * Depth t holds a beam F_t of m_t <= width states in a fixed order, F_0 = the start; child c = 12 i + a is the state of member i
+ * under action a.  A depth: (1) with prune_inverse, child (i, a) is dead when a is the inverse (action ^ 1) of the action that
+ * made member i; rows beyond 12 m_t are dead; (2) with n_live live children, explored + n_live > max_states stops the search
+ * (status 2), else explored += n_live; (3) the live child that is solved -- with a ball: whose orbit the ball holds -- with the
+ * least (ball depth, c) wins (status 1); (4) of live children with equal states the lowest c survives (no dedup across depths);
+ * (5) the best min(width, survivors) by value -- larger first, any NaN above every number, -0.0 equal to +0.0, ties to the lower
+ * c -- form F_{t+1}, stored in ascending c, back[t+1][j] = i << 4 | a; (6) t + 1 == max_depth stops the search (status 3).
+ * A depth is [net forward, rk_beam_step], stream-ordered with no host synchronisation; after a stop a step writes nothing.
+ * The engine keeps the current beam, the back record, the sizes and the net batch in HBM.  A handle is not thread-safe. */
+typedef struct rk_beam rk_beam_t;
+/* width 1..65536, max_depth 1..4096; ball NULL or a BUILT symmetry ball (RK_ESTATE otherwise), to which the engine attaches:
+ * rk_symball_destroy refuses meanwhile.  RK_ECAPACITY when the device has no room. */
+int rk_beam_create(rk_beam_t **out, rk_symball_t *ball, int width, int max_depth, int prune_inverse);
+int rk_beam_destroy(rk_beam_t *h);
+/* The batch the engine writes for the net: *rows = 12 width, row 12 j + a = child a of member j, as (rows, 480) one-hot rows of
+ * out_dtype (RK_OH_F32 / _F16 / _BF16) or, with RK_OH_STATES, the (rows, 20) int8 states themselves.  The engine owns it (16-byte
+ * aligned, alive until rk_beam_destroy) and writes the form asked for last; asking for another form needs a new rk_beam_reset.
+ * Call before rk_beam_reset. */
+int rk_beam_net_in(rk_beam_t *h, int out_dtype, void **d_ptr, size_t *rows);
+/* F_0 = the host 20-byte start state, with the state budget max_states (>= 0).  Writes EVERY row of the batch: the start's
+ * twelve children, then the solved state in all others (the net reads all rows at every depth).  With a ball, a start whose
+ * orbit the ball holds has won here (status 1, meeting action -1) and no depth runs.  Synchronises. */
+int rk_beam_reset(rk_beam_t *h, const int8_t *h_start_state, long long max_states, void *stream);
+/* One depth.  d_out: the net's values on the batch, (12 width) contiguous, float32 or bfloat16 (dtype RK_OH_F32 / RK_OH_BF16,
+ * widened exactly).  A fixed sequence of launches; everything data-dependent is read from device counters.  No synchronisation. */
+int rk_beam_step(rk_beam_t *h, const void *d_out, int dtype, void *stream);
+/* Synchronises; h_status[12] = status (0 running, 1 won, 2 budget, 3 depth limit, 4 engine error), depths run, states explored,
+ * size of the current beam, error (0 none, 1 a write that had no place in the beam or the back record: not made), the winning
+ * child's member i, its action a (-1: the start itself) and its ball depth, the budget, the depth of the current beam, two zeros. */
+int rk_beam_status(rk_beam_t *h, long long *h_status, void *stream);
+/* To HOST buffers (either may be NULL): h_sizes int64 (max_depth + 1), m_t per depth (0 beyond the depths run); h_back int64
+ * (back_len <= width): the first back_len back words of depth `depth` (1..max_depth).  Synchronises. */
+int rk_beam_export(rk_beam_t *h, int depth, long long *h_sizes, long long *h_back, size_t back_len, void *stream);
+/* The action queue of a search that won, start -> solved: back upward from the winning child's parent (one wave), the winning
+ * action, then the ball's descent from the winning child -- at each step the lowest action whose child's representative lies
+ * one level nearer.  Returns its length or a negative error (RK_ESTATE: not won, or the record is broken); writes at most
+ * max_len actions.  Synchronises. */
+long long rk_beam_path(rk_beam_t *h, long long *h_actions, size_t max_len, void *stream);
+
 /* ---- batched A*: S independent searches in lock-step, no host synchronisation inside an iteration -------------
  * Every search is a complete rk_astar_* engine (agents.py:171-413: its own pool, hash table, open queue, counter block);
  * the batch launches the same kernels with a second grid dimension (search), so one iteration of ALL searches is the

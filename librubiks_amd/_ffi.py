@@ -182,6 +182,14 @@ SIGNATURES = {
 	"rk_greedy_step": (_i, [_vp, _vp, _i, _vp]),
 	"rk_greedy_status": (_i, [_vp, _vp, _vp]),
 	"rk_greedy_export": (_i, [_vp, _vp, _vp, _vp, _vp]),
+	"rk_beam_create": (_i, [C.POINTER(_vp), _vp, _i, _i, _i]),
+	"rk_beam_destroy": (_i, [_vp]),
+	"rk_beam_net_in": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_sz)]),
+	"rk_beam_reset": (_i, [_vp, _vp, C.c_longlong, _vp]),
+	"rk_beam_step": (_i, [_vp, _vp, _i, _vp]),
+	"rk_beam_status": (_i, [_vp, _vp, _vp]),
+	"rk_beam_export": (_i, [_vp, _i, _vp, _vp, _sz, _vp]),
+	"rk_beam_path": (C.c_longlong, [_vp, _vp, _sz, _vp]),
 	"rk_astarb_create": (_i, [C.POINTER(_vp), _i, _sz, _i]),
 	"rk_astarb_destroy": (_i, [_vp]),
 	"rk_astarb_reset": (_i, [_vp, _vp, _vp, C.c_double, _vp]),

@@ -629,6 +629,26 @@ struct rk_symball : KeptBall {
 	long long cover[SB_MAX_RADIUS + 1] = {};
 };
 
+// What an engine of another translation unit that ends at a built symmetry ball takes and gives back (rk_beam.hip; declared in
+// rk_sym_dev.h): the view by value and a count in `attached`, so that rk_symball_destroy refuses under it as under a search here.
+namespace rk {
+
+int symball_attach(rk_symball *ball, const char *who, SymBallView *view)
+{
+	if (!ball || !view) return fail(RK_EINVAL, "%s: null ball", who);
+	if (!ball->built) return fail(RK_ESTATE, "%s: build the ball first", who);
+	ball->attached += 1;
+	*view = ball->view;
+	return RK_OK;
+}
+
+void symball_detach(rk_symball *ball)
+{
+	if (ball) ball->attached -= 1;
+}
+
+}  // namespace rk
+
 struct rk_ssearch : FrontierPool, BallReader<rk_symball> {
 	uint32_t *hit = nullptr;                    // per child of the batch: the ball's node of its representative, or 0
 	int pops_made = 0;                          // what it was created with: rk_sdeepen_set_pops lowers d.pops, a reset restores it

@@ -134,6 +134,11 @@ struct SymBallView {
 	const uint32_t *states; const uint32_t *table;
 };
 
+// A reader in another translation unit than the ball's (rk_beam.hip): the built ball's view and a hold on its arrays, counted as
+// a search's is (rk_symball_destroy refuses meanwhile), and the hold given back.  Host side, defined in rk_sym.hip.
+int symball_attach(::rk_symball *ball, const char *who, SymBallView *view);
+void symball_detach(::rk_symball *ball);
+
 // What a wave needs to ask the ball about a state: the staged tables, its lane and the lane's symmetry (lane l < 48: symmetry l;
 // lanes 48..63 take no part in the minimum).  s_act is null in a kernel that moves no state.
 struct SymProbe {

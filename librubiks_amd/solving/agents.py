@@ -1870,6 +1870,152 @@ class GreedyBatch(DeepAgent, _ffi.Owner):
 		return f"Greedy {self.mode} x{self.games} (device)"
 
 
+class DeviceBeamSearch(DeepAgent, _ffi.Owner):
+	"""
+	Beam search guided by the net's value head, higher is better as in `ValueSearch` (engine rk_beam_*, csrc/rk_beam.hip): every
+	depth keeps the best `width` states.  The beam, the `back` record, the sizes, the dedup table and the net batch live in HBM; a
+	depth is one net forward on the 12 x `width` rows of a batch that never changes shape and a fixed sequence of launches that
+	read everything data-dependent from device counters, captured once as a hipGraph and kept from search to search.  The host
+	enqueues `poll` depths, then reads the status; after a stop a replay writes nothing.  With `ball`, a built `DeviceSymBall`, the
+	search ends at the first child whose orbit the ball holds and the ball's descent finishes the queue, so the beam has to get
+	only within `ball.radius` quarter turns of solved; a start whose orbit the ball holds is answered at the reset.
+
+	Depth t holds a beam F_t of m_t <= width states in a fixed order, F_0 the start; child c = 12 i + a is member i under action a.
+	  1. With `prune_inverse`, child (i, a) is dead when a is the inverse (action ^ 1) of the action that made member i.
+	  2. With n_live live children: explored + n_live > max_states stops the search (status 2), else explored += n_live.
+	  3. The live child that is solved -- with a ball: whose orbit the ball holds -- with the least (ball depth, c) wins (status 1).
+	  4. Of live children with equal states only the lowest c survives.  There is NO dedup across depths: a state may come back at
+	     a later depth (the engine keeps no state but the current beam's), and `prune_inverse` removes only the two-move returns.
+	  5. The best min(width, survivors) -- larger value first, any NaN above every number, -0.0 equal to +0.0, ties to the lower
+	     c, bfloat16 values widened exactly -- form F_{t+1}, stored in ascending c; back[t + 1][j] = i << 4 | a.
+	  6. t + 1 == max_depth stops the search (status 3).
+	Status 0 is a search that was still running when `time_limit` passed; the time limit is checked only where the host polls.
+
+	After a search: `status`, `depth` (the depths run), `sizes` (m_t of every beam formed), `back_of(t)`, `meeting` = (i, a, ball
+	depth) of the winning child (a = -1: the start itself, inside the ball); len(agent) is the states explored.  With a real-valued
+	net a forward on 12 x width rows need not equal a forward on other rows bit for bit, so which of two nearly equal values is
+	kept may depend on the width.  The representation follows cube.get_is2024() when a search starts (6x8x6 nets read the engine's
+	20-byte rows through _Net686).
+	"""
+	MAX_WIDTH, MAX_DEPTH, MAX_POLL = 1 << 16, 1 << 12, 1 << 12              # rk_beam_create's limits
+
+	def __init__(self, net, width: int, max_depth: int = 64, ball: DeviceSymBall = None, prune_inverse: bool = True, poll: int = 8,
+	             fused_first_layer=False):
+		super().__init__(net, fused_first_layer)
+		for name, v, top in (("width", width, self.MAX_WIDTH), ("max_depth", max_depth, self.MAX_DEPTH), ("poll", poll, self.MAX_POLL)):
+			if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= top:
+				raise ValueError(f"{name} must be an integer in 1..{top}, got {v!r}")
+		if ball is not None and not (isinstance(ball, DeviceSymBall) and ball.built):
+			raise ValueError(f"ball must be None or a built DeviceSymBall (call ball.build() first), got {ball!r}")
+		self.width, self.max_depth, self.poll = int(width), int(max_depth), int(poll)
+		self.ball, self.prune_inverse = ball, bool(prune_inverse)
+		self._h = None
+		self._graph_cache, self.captures = None, 0                          # [net forward, rk_beam_step], kept (_engine.kept_graph)
+		self._batch = None                                                  # (code, the engine's net batch as a tensor)
+		self._clear()
+
+	def _clear(self):
+		self.status, self.depth, self.meeting = 0, 0, None
+		self.sizes = np.ones(1, np.int64)
+
+	def reset(self, time_limit: float, max_states: int):
+		"""As Agent.reset, but neither limit is required: a beam search ends by itself after max_depth depths."""
+		self._explored_states = 0
+		self.action_queue = deque()
+		self.net.eval()
+		return time_limit or 1e10, max_states
+
+	# -- engine lifetime ------------------------------------------------------------------------------------
+	def _engine(self):
+		if self._h is None:
+			self._create("rk_beam_create", "rk_beam_destroy", self.ball._h if self.ball is not None else None, self.width, self.max_depth,
+			             int(self.prune_inverse))
+		return self._h
+
+	def _free(self):
+		self._graph_cache = None               # it holds the engine's addresses,
+		self._batch = None                     # and this is the engine's memory
+		super()._free()
+
+	def _net_in(self, h, code: int):
+		if self._batch is None or self._batch[0] != code:
+			ptr, rows = C.c_void_p(), C.c_size_t()
+			_ffi.check(_ffi.lib().rk_beam_net_in(h, code, C.byref(ptr), C.byref(rows)))
+			self._batch = (code, eng.engine_batch(ptr.value, rows.value, code))       # (the engine goes on writing the form it was asked for last)
+		return self._batch[1]
+
+	# -- the captured step ------------------------------------------------------------------------------------
+	def _depth_step(self, h, batch):
+		values, code = eng.engine_values(_sliced_value_forward(self._forward, batch))
+		self._keep = values                    # the kernels read it after this call returns
+		_ffi.check(_ffi.lib().rk_beam_step(h, values.data_ptr(), code, _ffi.stream_ptr()))
+
+	def _poll(self, h):
+		status = (C.c_longlong * 12)()
+		_ffi.check(_ffi.lib().rk_beam_status(h, status, _ffi.stream_ptr()))
+		return [int(x) for x in status]
+
+	# -- search -------------------------------------------------------------------------------------------------
+	@no_grad
+	def search(self, state: np.ndarray, time_limit: float = None, max_states: int = None) -> bool:
+		state = np.asarray(state)
+		if state.shape != tuple(cube.shape()):                  # before anything asks for a device
+			raise ValueError(f"the start is one state of shape {tuple(cube.shape())}, got an array of shape {state.shape}")
+		if max_states is not None and (isinstance(max_states, bool) or int(max_states) != max_states or int(max_states) < 0):
+			raise ValueError(f"max_states must be a non-negative integer or None, got {max_states!r}")
+		_ffi.require_gpu()
+		t0 = time.perf_counter()
+		time_limit, _ = self.reset(time_limit, max_states)
+		self._clear()
+		forward, _, code = self._begin_net()
+		root = self._roots20(state, 1)[0]                      # ValueError for an illegal 6x8x6 state
+		if (root == _SOLVED20).all():
+			self.status = 1                                    # (no launch: nothing met, no depth run)
+			return True
+		budget = _ffi.INT64_MAX if max_states is None else int(max_states)
+		lib, stream = _ffi.lib(), _ffi.stream_ptr()
+		h = self._engine()
+		batch = self._net_in(h, code)
+		# The captured step holds addresses (the engine's arrays and batch, the net's tensors) and the dtype code -- nothing of a
+		# search, which lives in device memory that rk_beam_reset rewrites: the graph is kept from search to search.  It is captured
+		# on an engine that has been reset; the warm-up's depth is undone by the reset below.
+		key = (h.value, code, batch.data_ptr(), eng.capture_key(self.net, forward))
+		if self._graph_cache is None or self._graph_cache[0] != key:
+			_ffi.check(lib.rk_beam_reset(h, root.ctypes.data, budget, stream))
+		step = lambda: self._depth_step(h, batch)              # noqa: E731
+		graph, _ = eng.kept_graph(self, key, step, step, batch, ((self.net, forward),))
+		_ffi.check(lib.rk_beam_reset(h, root.ctypes.data, budget, stream))
+		st = self._poll(h)                                     # (a start inside the ball has won at the reset)
+		launched = 0
+		while st[0] == 0 and launched < self.max_depth and time.perf_counter() - t0 < time_limit:
+			burst = min(self.poll, self.max_depth - launched)  # a running search advances at every replay: none is after max_depth of them
+			for _ in range(burst):
+				graph.replay()
+			launched += burst
+			st = self._poll(h)
+		self.status, self.depth, self._explored_states = st[0], st[1], st[2]
+		if st[0] == 4 or st[4]:
+			raise _ffi.RubiksHipError(f"beam engine error code {st[4]}")
+		sizes = np.zeros(self.max_depth + 1, np.int64)
+		_ffi.check(lib.rk_beam_export(h, 0, sizes.ctypes.data, None, 0, stream))
+		self.sizes = sizes[:st[9] + 1].copy()
+		if st[0] != 1:
+			return False
+		self.meeting = (st[5], st[6], st[7])
+		self.action_queue = eng.read_path(lib.rk_beam_path, h, length=self.max_depth + 1 + DeviceSymBall.MAX_RADIUS)
+		return True
+
+	def back_of(self, t: int) -> np.ndarray:
+		"""int64 (m_t,): the `back` words i << 4 | a of the beam of depth t (1 .. len(sizes) - 1) of the last search."""
+		t = eng.int_in("t", t, 1, len(self.sizes) - 1)
+		out = np.zeros(int(self.sizes[t]), np.int64)
+		_ffi.check(_ffi.lib().rk_beam_export(self._h, t, None, out.ctypes.data, len(out), _ffi.stream_ptr()))
+		return out
+
+	def __str__(self):
+		return f"Beam search (device, width={self.width}" + (f", to a symmetry ball of radius {self.ball.radius})" if self.ball is not None else ")")
+
+
 def _load_net(loc: str, use_best: bool, loader=None):
 	"""The value/policy net of a saved model folder (reference: DeepAgent.from_saved, agents.py:72-75)."""
 	if loader is not None:
