@@ -56,17 +56,6 @@ struct BeamDev {
 	void *net_in;
 };
 
-__device__ __forceinline__ long long ctr64(const int32_t *ctr, int w)
-{
-	return (long long)(((unsigned long long)(uint32_t)ctr[w + 1] << 32) | (uint32_t)ctr[w]);
-}
-
-__device__ __forceinline__ void set_ctr64(int32_t *ctr, int w, long long v)
-{
-	ctr[w] = (int32_t)(uint32_t)(unsigned long long)v;
-	ctr[w + 1] = (int32_t)(uint32_t)((unsigned long long)v >> 32);
-}
-
 // the depth a launch works on; run = false after a stop
 struct BeamNow { int t, m; bool run; };
 
@@ -429,7 +418,7 @@ struct rk_beam {
 	BeamDev d{};
 	SymBallView view{};
 	rk_symball *ball = nullptr;
-	void *batch[4] = {nullptr, nullptr, nullptr, nullptr};      // the net batch, per RK_OH_* form
+	NetBatches batch{false};                    // not cleared: rk_beam_reset writes every row before a forward reads one
 	int32_t *walk = nullptr;
 	int walk_max = 0;
 	size_t n_words = 0;
@@ -444,8 +433,6 @@ namespace {
 
 constexpr int BEAM_MAX_WIDTH = 1 << 16, BEAM_MAX_DEPTH = 1 << 12;
 constexpr unsigned BEAM_WAVE_GRID = 2048;       // workgroups of the wave-per-child launches that stage the symmetry tables
-
-size_t beam_row_bytes(int code) { return code == RK_OH_STATES ? 20 : code == RK_OH_F32 ? 1920 : 960; }
 
 }  // namespace
 
@@ -491,14 +478,9 @@ int rk_beam_net_in(rk_beam_t *h, int out_dtype, void **d_ptr, size_t *rows)
 	if (out_dtype < RK_OH_F32 || out_dtype > RK_OH_STATES) return fail(RK_EINVAL, "rk_beam_net_in: unknown dtype %d", out_dtype);
 	BeamDev &d = h->d;
 	const size_t n = (size_t)12 * d.B;
-	if (h->batch[out_dtype] == nullptr) {       // (not cleared: rk_beam_reset writes every row before a forward reads one)
-		uint8_t *p = nullptr;
-		if (int e = h->pool.alloc(&p, n * beam_row_bytes(out_dtype))) return e;
-		h->batch[out_dtype] = p;
-	}
+	if (int e = h->batch.get(h->pool, out_dtype, n, &d.net_in)) return e;
 	if (d.code != out_dtype) h->ready = false;  // the batch of a running search is in the other form: reset first
 	d.code = out_dtype;
-	d.net_in = h->batch[out_dtype];
 	*d_ptr = d.net_in;
 	*rows = n;
 	return RK_OK;
@@ -510,9 +492,7 @@ int rk_beam_reset(rk_beam_t *h, const int8_t *h_start_state, long long max_state
 	BeamDev &d = h->d;
 	if (d.code < 0) return fail(RK_ESTATE, "rk_beam_reset: ask for the net batch first (rk_beam_net_in)");
 	if (max_states < 0) return fail(RK_EINVAL, "rk_beam_reset: max_states %lld < 0", max_states);
-	for (int i = 0; i < STATE_BYTES; i++)
-		if (h_start_state[i] < 0 || h_start_state[i] >= 24)
-			return fail(RK_EINVAL, "rk_beam_reset: byte %d of the start is %d, not a cubie code", i, (int)h_start_state[i]);
+	if (int e = check_cubie_codes("rk_beam_reset", "start", h_start_state, 1)) return e;
 	hipStream_t st = (hipStream_t)stream;
 	h->ready = false;
 	RK_HIP(hipMemcpyAsync(d.root, h_start_state, STATE_BYTES, hipMemcpyHostToDevice, st));
@@ -531,15 +511,15 @@ int rk_beam_reset(rk_beam_t *h, const int8_t *h_start_state, long long max_state
 int rk_beam_step(rk_beam_t *h, const void *d_out, int dtype, void *stream)
 {
 	if (!h || !h->ready) return fail(RK_ESTATE, "rk_beam_step: reset the engine first");
-	if (!d_out) return fail(RK_EINVAL, "rk_beam_step: null net output");
-	if (dtype != RK_OH_F32 && dtype != RK_OH_BF16) return fail(RK_EINVAL, "rk_beam_step: the net's output is float32 or bfloat16, got dtype %d", dtype);
+	int bf16 = 0;
+	if (int e = check_net_out("rk_beam_step", d_out, dtype, &bf16)) return e;
 	const BeamDev &d = h->d;
 	hipStream_t st = (hipStream_t)stream;
 	const size_t K = (size_t)12 * d.B;
 	const unsigned grid = blocks(K);
 	if (d.has_ball) hipLaunchKernelGGL(k_beam_ball, dim3(std::min(blocks(K, 4), BEAM_WAVE_GRID)), dim3(256), 0, st, d, h->view);
 	hipLaunchKernelGGL(k_beam_probe, dim3(grid), dim3(256), 0, st, d);
-	hipLaunchKernelGGL(k_beam_keys, dim3(grid), dim3(256), 0, st, d, d_out, dtype == RK_OH_BF16 ? 1 : 0);
+	hipLaunchKernelGGL(k_beam_keys, dim3(grid), dim3(256), 0, st, d, d_out, bf16);
 	for (int pass = 1; pass < 4; pass++) hipLaunchKernelGGL(k_beam_hist, dim3(grid), dim3(256), 0, st, d, pass);
 	hipLaunchKernelGGL(k_beam_commit, dim3(blocks(K, ASCAN)), dim3(ASCAN), 0, st, d);
 	hipLaunchKernelGGL(k_beam_rows, dim3(blocks((size_t)d.B, 4)), dim3(256), 0, st, d);
@@ -553,9 +533,8 @@ int rk_beam_status(rk_beam_t *h, long long *h_status, void *stream)
 	if (!h || !h->ready || !h_status) return fail(RK_EINVAL, "rk_beam_status: bad argument");
 	int32_t c[W_COUNT];
 	if (int e = h->ctr_host.read(h->d.ctr, W_COUNT, c, (hipStream_t)stream)) return e;
-	auto wide = [&](int w) { return (long long)(((unsigned long long)(uint32_t)c[w + 1] << 32) | (uint32_t)c[w]); };
-	h_status[0] = c[W_STATUS]; h_status[1] = c[W_DEPTH]; h_status[2] = wide(W_EXPLORED); h_status[3] = c[W_M]; h_status[4] = c[W_ERROR];
-	h_status[5] = c[W_MEET_I]; h_status[6] = c[W_MEET_A]; h_status[7] = c[W_MEET_LEVEL]; h_status[8] = wide(W_BUDGET); h_status[9] = c[W_T];
+	h_status[0] = c[W_STATUS]; h_status[1] = c[W_DEPTH]; h_status[2] = ctr64(c, W_EXPLORED); h_status[3] = c[W_M]; h_status[4] = c[W_ERROR];
+	h_status[5] = c[W_MEET_I]; h_status[6] = c[W_MEET_A]; h_status[7] = c[W_MEET_LEVEL]; h_status[8] = ctr64(c, W_BUDGET); h_status[9] = c[W_T];
 	h_status[10] = h_status[11] = 0;
 	return RK_OK;
 }

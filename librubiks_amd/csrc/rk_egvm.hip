@@ -23,7 +23,6 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <climits>
-#include <cstring>
 #include <vector>
 
 #include "../../include/rubiks_hip.h"
@@ -226,7 +225,8 @@ using namespace rk;
 struct rk_egvm {
 	EgvmDev d{};
 	uint32_t *root_dev = nullptr;
-	void *pol[4] = {nullptr, nullptr, nullptr, nullptr}, *val[4] = {nullptr, nullptr, nullptr, nullptr};      // the net batches, per RK_OH_* form
+	// zeroed: a round that ends by a solve leaves value rows unwritten, and the value forward of that round still reads them
+	NetBatches pol{true}, val{true};
 	Landing ctr_host;
 	bool ready = false;
 	DevPool pool{64};
@@ -236,8 +236,6 @@ namespace {
 
 constexpr int EGVM_MAX_WORKERS = 1 << 16, EGVM_MAX_DEPTH = 1 << 12, EGVM_MAX_ROUNDS = 1 << 12;
 constexpr long long EGVM_MAX_STATES = 1ll << 22, EGVM_MAX_DRAWS = 1ll << 28;
-
-size_t egvm_row_bytes(int code) { return code == RK_OH_STATES ? 20 : code == RK_OH_F32 ? 1920 : 960; }
 
 int egvm_read(rk_egvm *h, int32_t *out, hipStream_t st) { return h->ctr_host.read(h->d.ctr, EGVM_WORDS, out, st); }
 
@@ -282,23 +280,15 @@ int rk_egvm_net_in(rk_egvm_t *h, int which, int out_dtype, void **d_ptr, size_t 
 	if (which != 0 && which != 1) return fail(RK_EINVAL, "rk_egvm_net_in: which is 0 (policy batch) or 1 (value batch), got %d", which);
 	if (out_dtype < RK_OH_F32 || out_dtype > RK_OH_STATES) return fail(RK_EINVAL, "rk_egvm_net_in: unknown dtype %d", out_dtype);
 	EgvmDev &d = h->d;
-	if (h->pol[out_dtype] == nullptr) {
-		// Zeroed once: a round that ends by a solve leaves value rows unwritten, and the value forward of that round still reads them
-		// (code 0 is a valid cubie code, an all-zero one-hot row a harmless input).
-		const size_t rb = egvm_row_bytes(out_dtype), nw = (size_t)d.W * rb, nv = (size_t)d.W * d.D * rb;
-		uint8_t *p = nullptr, *v = nullptr;
-		if (int e = h->pool.alloc(&p, nw)) return e;
-		if (int e = h->pool.alloc(&v, nv)) { h->pool.release(p); return e; }
-		RK_HIP(hipMemset(p, 0, nw));
-		RK_HIP(hipMemset(v, 0, nv));
-		RK_HIP(hipStreamSynchronize(nullptr));
-		h->pol[out_dtype] = p; h->val[out_dtype] = v;
-	}
+	const size_t nw = (size_t)d.W, nv = (size_t)d.W * d.D;
+	void *p = nullptr, *v = nullptr;                // both batches of a form or neither
+	if (int e = h->pol.get(h->pool, out_dtype, nw, &p)) return e;
+	if (int e = h->val.get(h->pool, out_dtype, nv, &v)) { h->pol.drop(h->pool, out_dtype); return e; }
 	if (d.code != out_dtype) h->ready = false;  // the batches of a running search are in the other form: reset first
 	d.code = out_dtype;
-	d.pol_in = h->pol[out_dtype]; d.val_in = h->val[out_dtype];
+	d.pol_in = p; d.val_in = v;
 	*d_ptr = which == 0 ? d.pol_in : d.val_in;
-	*rows = which == 0 ? (size_t)d.W : (size_t)d.W * d.D;
+	*rows = which == 0 ? nw : nv;
 	return RK_OK;
 }
 
@@ -306,8 +296,7 @@ int rk_egvm_reset(rk_egvm_t *h, const int8_t *h_root, long long max_states, void
 {
 	if (!h || !h_root) return fail(RK_EINVAL, "rk_egvm_reset: null argument");
 	if (h->d.code < 0) return fail(RK_ESTATE, "rk_egvm_reset: ask for the net batches first (rk_egvm_net_in)");
-	for (int i = 0; i < STATE_BYTES; i++)
-		if (h_root[i] < 0 || h_root[i] >= 24) return fail(RK_EINVAL, "rk_egvm_reset: byte %d of the root is %d, not a cubie code", i, (int)h_root[i]);
+	if (int e = check_cubie_codes("rk_egvm_reset", "root", h_root, 1)) return e;
 	hipStream_t st = (hipStream_t)stream;
 	RK_HIP(hipMemcpyAsync(h->root_dev, h_root, STATE_BYTES, hipMemcpyHostToDevice, st));
 	hipLaunchKernelGGL(k_egvm_begin, dim3(1), dim3(1024), 0, st, h->d, h->root_dev, std::max<long long>(max_states, 0));
@@ -337,9 +326,9 @@ int rk_egvm_set_draws(rk_egvm_t *h, const int8_t *h_draws, int rounds, void *str
 int rk_egvm_step(rk_egvm_t *h, const void *d_logits, int dtype, void *stream)
 {
 	if (!h || !h->ready) return fail(RK_ESTATE, "rk_egvm_step: reset the engine first");
-	if (!d_logits) return fail(RK_EINVAL, "rk_egvm_step: null logits");
-	if (dtype != RK_OH_F32 && dtype != RK_OH_BF16) return fail(RK_EINVAL, "rk_egvm_step: logits are float32 or bfloat16, got dtype %d", dtype);
-	hipLaunchKernelGGL(k_egvm_step, dim3(blocks((size_t)h->d.W, 4)), dim3(256), 0, (hipStream_t)stream, h->d, d_logits, dtype == RK_OH_BF16 ? 1 : 0);
+	int bf16 = 0;
+	if (int e = check_net_out("rk_egvm_step", d_logits, dtype, &bf16)) return e;
+	hipLaunchKernelGGL(k_egvm_step, dim3(blocks((size_t)h->d.W, 4)), dim3(256), 0, (hipStream_t)stream, h->d, d_logits, bf16);
 	RK_HIP(hipGetLastError());
 	return RK_OK;
 }
@@ -347,9 +336,9 @@ int rk_egvm_step(rk_egvm_t *h, const void *d_logits, int dtype, void *stream)
 int rk_egvm_round_end(rk_egvm_t *h, const void *d_values, int dtype, void *stream)
 {
 	if (!h || !h->ready) return fail(RK_ESTATE, "rk_egvm_round_end: reset the engine first");
-	if (!d_values) return fail(RK_EINVAL, "rk_egvm_round_end: null values");
-	if (dtype != RK_OH_F32 && dtype != RK_OH_BF16) return fail(RK_EINVAL, "rk_egvm_round_end: values are float32 or bfloat16, got dtype %d", dtype);
-	hipLaunchKernelGGL(k_egvm_round_end, dim3(1), dim3(1024), 0, (hipStream_t)stream, h->d, d_values, dtype == RK_OH_BF16 ? 1 : 0);
+	int bf16 = 0;
+	if (int e = check_net_out("rk_egvm_round_end", d_values, dtype, &bf16)) return e;
+	hipLaunchKernelGGL(k_egvm_round_end, dim3(1), dim3(1024), 0, (hipStream_t)stream, h->d, d_values, bf16);
 	RK_HIP(hipGetLastError());
 	return RK_OK;
 }
@@ -359,9 +348,7 @@ int rk_egvm_status(rk_egvm_t *h, long long *h_status, void *stream)
 	if (!h || !h->ready || !h_status) return fail(RK_EINVAL, "rk_egvm_status: bad argument");
 	int32_t c[EGVM_WORDS];
 	if (int e = egvm_read(h, c, (hipStream_t)stream)) return e;
-	long long big[2];
-	memcpy(big, c + E_COUNT, sizeof big);
-	h_status[0] = c[E_DONE]; h_status[1] = c[E_SOLVED]; h_status[2] = c[E_ROUND]; h_status[3] = big[E_BIG_EXPLORED];
+	h_status[0] = c[E_DONE]; h_status[1] = c[E_SOLVED]; h_status[2] = c[E_ROUND]; h_status[3] = ctr64(c, E_COUNT + 2 * E_BIG_EXPLORED);
 	h_status[4] = c[E_SOLVED] ? c[E_SWALKER] : -1; h_status[5] = c[E_SOLVED] ? c[E_SDEPTH] : -1; h_status[6] = c[E_ERROR]; h_status[7] = c[E_BASE];
 	return RK_OK;
 }

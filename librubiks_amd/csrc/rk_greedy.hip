@@ -181,7 +181,8 @@ using namespace rk;
 struct rk_greedy {
 	GreedyDev d{};
 	uint32_t *roots_dev = nullptr;
-	void *batch[4] = {nullptr, nullptr, nullptr, nullptr};      // the net batch, per RK_OH_* form
+	// zeroed: the rows of games that an engine made for G does not play are read by every forward and never written
+	NetBatches batch{true};
 	Landing ctr_host;
 	int n_games = 0, budget = 0;                                // of the last reset
 	bool ready = false;
@@ -192,8 +193,6 @@ namespace {
 
 constexpr int GREEDY_MAX_GAMES = 1 << 16;
 constexpr long long GREEDY_MAX_RECORD = 1ll << 30;
-
-size_t greedy_row_bytes(int code) { return code == RK_OH_STATES ? 20 : code == RK_OH_F32 ? 1920 : 960; }
 
 }  // namespace
 
@@ -234,18 +233,9 @@ int rk_greedy_net_in(rk_greedy_t *h, int out_dtype, void **d_ptr, size_t *rows)
 	if (out_dtype < RK_OH_F32 || out_dtype > RK_OH_STATES) return fail(RK_EINVAL, "rk_greedy_net_in: unknown dtype %d", out_dtype);
 	GreedyDev &d = h->d;
 	const size_t n = (size_t)d.G * (d.mode == GREEDY_VALUE ? 12 : 1);
-	if (h->batch[out_dtype] == nullptr) {
-		// Zeroed once: the rows of games that an engine made for G does not play are read by every forward and never written
-		// (code 0 is a valid cubie code, an all-zero one-hot row a harmless input).
-		uint8_t *p = nullptr;
-		if (int e = h->pool.alloc(&p, n * greedy_row_bytes(out_dtype))) return e;
-		RK_HIP(hipMemset(p, 0, n * greedy_row_bytes(out_dtype)));
-		RK_HIP(hipStreamSynchronize(nullptr));
-		h->batch[out_dtype] = p;
-	}
+	if (int e = h->batch.get(h->pool, out_dtype, n, &d.net_in)) return e;
 	if (d.code != out_dtype) h->ready = false;  // the batch of a running search is in the other form: reset first
 	d.code = out_dtype;
-	d.net_in = h->batch[out_dtype];
 	*d_ptr = d.net_in;
 	*rows = n;
 	return RK_OK;
@@ -258,9 +248,7 @@ int rk_greedy_reset(rk_greedy_t *h, const int8_t *h_roots, int n_games, int max_
 	if (d.code < 0) return fail(RK_ESTATE, "rk_greedy_reset: ask for the net batch first (rk_greedy_net_in)");
 	if (n_games < 1 || n_games > d.G) return fail(RK_EINVAL, "rk_greedy_reset: n_games %d outside 1..%d", n_games, d.G);
 	if (max_states < 1 || max_states > d.S) return fail(RK_EINVAL, "rk_greedy_reset: max_states %d outside 1..%d", max_states, d.S);
-	for (size_t i = 0; i < (size_t)n_games * STATE_BYTES; i++)
-		if (h_roots[i] < 0 || h_roots[i] >= 24)
-			return fail(RK_EINVAL, "rk_greedy_reset: byte %zu of root %zu is %d, not a cubie code", i % STATE_BYTES, i / STATE_BYTES, (int)h_roots[i]);
+	if (int e = check_cubie_codes("rk_greedy_reset", "root", h_roots, (size_t)n_games)) return e;
 	hipStream_t st = (hipStream_t)stream;
 	h->ready = false;
 	RK_HIP(hipMemcpyAsync(h->roots_dev, h_roots, (size_t)n_games * STATE_BYTES, hipMemcpyHostToDevice, st));
@@ -276,9 +264,9 @@ int rk_greedy_reset(rk_greedy_t *h, const int8_t *h_roots, int n_games, int max_
 int rk_greedy_step(rk_greedy_t *h, const void *d_out, int dtype, void *stream)
 {
 	if (!h || !h->ready) return fail(RK_ESTATE, "rk_greedy_step: reset the engine first");
-	if (!d_out) return fail(RK_EINVAL, "rk_greedy_step: null net output");
-	if (dtype != RK_OH_F32 && dtype != RK_OH_BF16) return fail(RK_EINVAL, "rk_greedy_step: the net's output is float32 or bfloat16, got dtype %d", dtype);
-	hipLaunchKernelGGL(k_greedy_step, dim3(blocks((size_t)h->d.G, 4)), dim3(256), 0, (hipStream_t)stream, h->d, d_out, dtype == RK_OH_BF16 ? 1 : 0);
+	int bf16 = 0;
+	if (int e = check_net_out("rk_greedy_step", d_out, dtype, &bf16)) return e;
+	hipLaunchKernelGGL(k_greedy_step, dim3(blocks((size_t)h->d.G, 4)), dim3(256), 0, (hipStream_t)stream, h->d, d_out, bf16);
 	RK_HIP(hipGetLastError());
 	return RK_OK;
 }

@@ -1,6 +1,6 @@
 // Device-side pieces shared by the search engines (single A*, sharded A*, batched A*, breadth-first search): queue records and their order,
-// the state hash, order-preserving compaction inside a workgroup, binary search in a sorted run, and the net rows and argmax rule of the
-// engines that own their net batches.
+// the state hash, order-preserving compaction inside a workgroup, binary search in a sorted run, and the net rows, the argmax rule and
+// the 64-bit counters of the engines that own their net batches.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -134,7 +134,7 @@ __device__ __forceinline__ void rehash_pool(const uint32_t *states, uint32_t *ta
 	}
 }
 
-// ---- what the engines that own their net batches share (epsilon-greedy value search, the greedy one-step games) ----
+// ---- what the engines that own their net batches share (epsilon-greedy value search, the greedy one-step games, beam search) ----
 // dword j of a state held in registers, j not known at compile time (no indexed register array)
 __device__ __forceinline__ uint32_t dword_of(const uint32_t s[5], int j)
 {
@@ -184,6 +184,18 @@ __device__ __forceinline__ bool beats(float v, int i, float bv, int bi)
 	if (vn != bn) return vn;
 	if (!vn && v != bv) return v > bv;
 	return i < bi;
+}
+
+// a 64-bit counter in words w (low half) and w + 1 of an int32 counter block (on the host: of the block's copy)
+__host__ __device__ __forceinline__ long long ctr64(const int32_t *ctr, int w)
+{
+	return (long long)(((unsigned long long)(uint32_t)ctr[w + 1] << 32) | (uint32_t)ctr[w]);
+}
+
+__device__ __forceinline__ void set_ctr64(int32_t *ctr, int w, long long v)
+{
+	ctr[w] = (int32_t)(uint32_t)(unsigned long long)v;
+	ctr[w + 1] = (int32_t)(uint32_t)((unsigned long long)v >> 32);
 }
 
 // ---- order-preserving compaction across workgroups in ONE launch: tickets + look-back --------------------------------

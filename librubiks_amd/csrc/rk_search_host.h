@@ -1,7 +1,9 @@
-// Host-side pieces shared by the search engines (A* single / sharded / batched, breadth-first search, MCTS): who owns a device
-// allocation, growing arrays in place as one transaction and the small read-backs every engine needs.  The counterpart of
-// rk_search_dev.h; header-only, nothing in here is exported.  The host half of the breadth-first engines' pool and of the kept
-// balls is rk_frontier_host.h, which only those engines include: it brings the frontier pool's kernels with it.
+// Host-side pieces shared by the search engines (A* single / sharded / batched, MCTS, the breadth-first and ball searches, and the
+// net-stepped ones: epsilon-greedy value search, the greedy games, beam search): who owns a device allocation, growing arrays in place
+// as one transaction and the small read-backs every engine needs; at the end, what only the net-stepped engines share: the net batches
+// an engine owns per RK_OH_* form, and the checks of the start states and of the net output that their entry points take.
+// The counterpart of rk_search_dev.h; header-only, nothing in here is exported.  The host half of the breadth-first engines' pool
+// and of the kept balls is rk_frontier_host.h, which only those engines include: it brings the frontier pool's kernels with it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -212,6 +214,52 @@ inline int read_walk(const int32_t *walk, size_t walk_max, long long *h_actions,
 	RK_HIP(hipStreamSynchronize(st));
 	if (*len < 0) return RK_OK;
 	return export_widened(walk + 1, std::min(std::min((size_t)*len, max_len), walk_max), h_actions, st);
+}
+
+// ---- what the net-stepped engines share (rk_egvm.hip, rk_greedy.hip, rk_beam.hip): they own the net's batch, per RK_OH_* form ----
+// bytes of a batch row: the 20-byte state, or 480 one-hot elements of 4 or 2 bytes (write_row, rk_search_dev.h)
+inline size_t net_row_bytes(int code) { return code == RK_OH_STATES ? 20 : code == RK_OH_F32 ? 1920 : 960; }
+
+// The net batches of one engine input, per form (the entry point checks the code): taken from the engine's pool when a form is
+// first asked for, alive as long as the pool.  `zeroed`: a fresh buffer is cleared (blocking), for an engine whose forwards read
+// rows that nothing has written (code 0 is a valid cubie code, an all-zero one-hot row a harmless input).
+struct NetBatches {
+	bool zeroed;
+	void *at[RK_OH_STATES + 1] = {};
+
+	int get(DevPool &pool, int code, size_t rows, void **out)
+	{
+		if (at[code] == nullptr) {
+			const size_t bytes = rows * net_row_bytes(code);
+			uint8_t *p = nullptr;
+			if (int e = pool.alloc(&p, bytes)) return e;
+			if (zeroed) { RK_HIP(hipMemset(p, 0, bytes)); RK_HIP(hipStreamSynchronize(nullptr)); }
+			at[code] = p;
+		}
+		*out = at[code];
+		return RK_OK;
+	}
+	void drop(DevPool &pool, int code) { pool.release(at[code]); at[code] = nullptr; }      // (an engine with two inputs that got only the first)
+};
+
+// `n` 20-byte host states hold only cubie codes 0..23, else "<entry>: byte b of the <what> ...", for n > 1 "... of <what> i ..."
+inline int check_cubie_codes(const char *entry, const char *what, const int8_t *h_states, size_t n)
+{
+	for (size_t i = 0; i < n * STATE_BYTES; i++) {
+		if (h_states[i] >= 0 && h_states[i] < 24) continue;
+		if (n == 1) return fail(RK_EINVAL, "%s: byte %zu of the %s is %d, not a cubie code", entry, i, what, (int)h_states[i]);
+		return fail(RK_EINVAL, "%s: byte %zu of %s %zu is %d, not a cubie code", entry, i % STATE_BYTES, what, i / STATE_BYTES, (int)h_states[i]);
+	}
+	return RK_OK;
+}
+
+// a net output handed to a step: non-null, float32 or bfloat16; *bf16 = what the launch passes on (net_out, rk_search_dev.h)
+inline int check_net_out(const char *entry, const void *d_out, int dtype, int *bf16)
+{
+	if (!d_out) return fail(RK_EINVAL, "%s: null net output", entry);
+	if (dtype != RK_OH_F32 && dtype != RK_OH_BF16) return fail(RK_EINVAL, "%s: the net's output is float32 or bfloat16, got dtype %d", entry, dtype);
+	*bf16 = dtype == RK_OH_BF16 ? 1 : 0;
+	return RK_OK;
 }
 
 }  // namespace

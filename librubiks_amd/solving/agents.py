@@ -1568,7 +1568,58 @@ class _KeptGraph:
 		self._graph_cache, self.captures = None, 0
 
 
-class DeviceEGVM(DeepAgent, _ffi.Owner):
+class _NetStepped(DeepAgent, _ffi.Owner):
+	"""
+	What the agents of the net-stepped engines share (rk_egvm_*, rk_greedy_*, rk_beam_*; the engines' side is at the end of
+	csrc/rk_search_host.h).  The ENGINE owns the net's batch in HBM, one buffer per RK_OH_* form; `_batch` = (code, tensor, ...)
+	wraps the form the net wants now.  A step -- a net forward on that batch plus the engine's launches -- is captured once as a
+	hipGraph and kept from search to search in a holder that `_engine.kept_graph` writes to (`_holders`: the agent itself, or one
+	`_KeptGraph` per step of an agent with several).  The host replays `poll` steps, then reads a counter block: each agent's own loop.
+	"""
+	_batch = None
+	_graph_cache, captures = None, 0
+
+	@staticmethod
+	def _strict_ints(*args) -> list:
+		"""(name, value, top), ...: the values as ints.  Only an int / np.integer in 1..top will do: no bool, no 2.0 (`_engine.int_in` takes it)."""
+		for name, v, top in args:
+			if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= top:
+				raise ValueError(f"{name} must be an integer in 1..{top}, got {v!r}")
+		return [int(v) for _, v, _ in args]
+
+	def _holders(self) -> tuple:
+		return (self,)
+
+	def _free(self):
+		for g in self._holders():
+			g._graph_cache = None              # the graphs hold the engine's addresses,
+		self._batch = None                     # and the batches are the engine's memory: both go before the engine does
+		super()._free()
+
+	def _net_batches(self, h, code: int, *calls) -> tuple:
+		"""The engine's batches in form `code` as tensors, one per call (entry, *arguments between the handle and the code)."""
+		if self._batch is None or self._batch[0] != code:
+			got = []
+			for entry, *lead in calls:
+				ptr, rows = C.c_void_p(), C.c_size_t()
+				_ffi.check(entry(h, *lead, code, C.byref(ptr), C.byref(rows)))
+				got.append(eng.engine_batch(ptr.value, rows.value, code))
+			self._batch = (code, *got)         # (the engine goes on writing the form it was asked for last)
+		return self._batch[1:]
+
+	def _kept_steps(self, key: tuple, forward, reset, *steps) -> list:
+		"""The hipGraphs of `steps`, each (holder, step, batch), kept or captured now.  A captured step holds addresses (the engine's
+		arrays and batches, the net's tensors) and dtype codes -- nothing of a search, which lives in device memory that `reset`, the
+		engine's reset for the search that starts, rewrites: the graphs are kept while `key`, everything they hold, stays the same.
+		A step is captured on an engine that has been reset, and what the warm-up's launches change there the last reset rewrites."""
+		if any(g._graph_cache is None or g._graph_cache[0] != key for g, _, _ in steps):
+			reset()
+		graphs = [eng.kept_graph(g, key, step, step, batch, ((self.net, forward),))[0] for g, step, batch in steps]
+		reset()
+		return graphs
+
+
+class DeviceEGVM(_NetStepped):
 	"""
 	Epsilon-greedy value maximisation (agents.py:649-726) with the whole round on the device (engine rk_egvm_*, csrc/rk_egvm.hip):
 	the walkers, the states they visit, their actions and the two net batches live in HBM.  One move of all walkers is the policy
@@ -1592,19 +1643,16 @@ class DeviceEGVM(DeepAgent, _ffi.Owner):
 
 	def __init__(self, net, epsilon: float, workers: int, depth: int, poll: int = 4, fused_first_layer=False):
 		super().__init__(net, fused_first_layer)
-		for name, v, top in (("workers", workers, self.MAX_WORKERS), ("depth", depth, self.MAX_DEPTH), ("poll", poll, self.MAX_POLL)):
-			if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= top:
-				raise ValueError(f"{name} must be an integer in 1..{top}, got {v!r}")
-		if int(workers) * int(depth) > self.MAX_STATES:
-			raise ValueError(f"workers * depth must not exceed {self.MAX_STATES}, got {int(workers) * int(depth)}")
-		if int(workers) * int(depth) * int(poll) > 1 << 28:
-			raise ValueError(f"workers * depth * poll must not exceed {1 << 28}, got {int(workers) * int(depth) * int(poll)}")
+		workers, depth, poll = self._strict_ints(("workers", workers, self.MAX_WORKERS), ("depth", depth, self.MAX_DEPTH), ("poll", poll, self.MAX_POLL))
+		if workers * depth > self.MAX_STATES:
+			raise ValueError(f"workers * depth must not exceed {self.MAX_STATES}, got {workers * depth}")
+		if workers * depth * poll > 1 << 28:
+			raise ValueError(f"workers * depth * poll must not exceed {1 << 28}, got {workers * depth * poll}")
 		if isinstance(epsilon, bool) or not isinstance(epsilon, (int, float, np.floating, np.integer)) or not 0 <= float(epsilon) <= 1:
 			raise ValueError(f"epsilon must be a number in 0..1, got {epsilon!r}")
-		self.epsilon, self.workers, self.depth, self.poll = epsilon, int(workers), int(depth), int(poll)
-		self._h, self._shape = None, None
+		self.epsilon, self.workers, self.depth, self.poll = epsilon, workers, depth, poll
+		self._shape = None
 		self._walk, self._close = _KeptGraph(), _KeptGraph()       # policy forward + rk_egvm_step; value forward + rk_egvm_round_end
-		self._batches = None                                       # (code, policy batch, value batch): the engine's own memory as tensors
 		self.rounds = 0                                            # rounds the last search closed
 
 	@property
@@ -1620,20 +1668,8 @@ class DeviceEGVM(DeepAgent, _ffi.Owner):
 			self._shape = shape
 		return self._h
 
-	def _free(self):
-		self._walk._graph_cache = self._close._graph_cache = None      # they hold the engine's addresses,
-		self._batches = None                                           # and these are the engine's memory
-		super()._free()
-
-	def _net_in(self, h, code: int):
-		if self._batches is None or self._batches[0] != code:
-			got = []
-			for which in (0, 1):
-				ptr, rows = C.c_void_p(), C.c_size_t()
-				_ffi.check(_ffi.lib().rk_egvm_net_in(h, which, code, C.byref(ptr), C.byref(rows)))
-				got.append(eng.engine_batch(ptr.value, rows.value, code))
-			self._batches = (code, *got)       # (the engine goes on writing the form it was asked for last)
-		return self._batches[1], self._batches[2]
+	def _holders(self) -> tuple:
+		return self._walk, self._close
 
 	# -- the two captured steps -------------------------------------------------------------------------------
 	def _walk_step(self, h, pol_in):
@@ -1663,19 +1699,11 @@ class DeviceEGVM(DeepAgent, _ffi.Owner):
 			return False
 		lib, stream = _ffi.lib(), _ffi.stream_ptr()
 		h = self._engine()
-		pol_in, val_in = self._net_in(h, code)
-		# The captured steps hold addresses (the engine's arrays and batches, the net's tensors) and the dtype codes -- nothing of a
-		# search, which lives in device memory that rk_egvm_reset rewrites: both graphs are kept from search to search.  They are
-		# captured on an engine that has been reset but has no draws yet, where the warm-up's launches change nothing that the reset
-		# below does not rewrite.
+		pol_in, val_in = self._net_batches(h, code, (lib.rk_egvm_net_in, 0), (lib.rk_egvm_net_in, 1))
 		key = (h.value, code, pol_in.data_ptr(), val_in.data_ptr(), eng.capture_key(self.net, forward))
-		if any(g._graph_cache is None or g._graph_cache[0] != key for g in (self._walk, self._close)):
-			_ffi.check(lib.rk_egvm_reset(h, root.ctypes.data, int(max_states), stream))
-		walk_step = lambda: self._walk_step(h, pol_in)         # noqa: E731
-		close_step = lambda: self._close_step(h, val_in)       # noqa: E731
-		walk, _ = eng.kept_graph(self._walk, key, walk_step, walk_step, pol_in, ((self.net, forward),))
-		close, _ = eng.kept_graph(self._close, key, close_step, close_step, val_in, ((self.net, forward),))
-		_ffi.check(lib.rk_egvm_reset(h, root.ctypes.data, int(max_states), stream))
+		reset = lambda: _ffi.check(lib.rk_egvm_reset(h, root.ctypes.data, int(max_states), stream))       # noqa: E731
+		walk, close = self._kept_steps(key, forward, reset, (self._walk, lambda: self._walk_step(h, pol_in), pol_in),
+		                               (self._close, lambda: self._close_step(h, val_in), val_in))
 		status = (C.c_longlong * 8)()
 		drawn = 0
 		while time.perf_counter() - t0 < time_limit:
@@ -1713,7 +1741,7 @@ class DeviceEGVM(DeepAgent, _ffi.Owner):
 		return f"EGVM (device, e={self.epsilon}, w={self.workers}, d={self.depth})"
 
 
-class GreedyBatch(DeepAgent, _ffi.Owner):
+class GreedyBatch(_NetStepped):
 	"""
 	Up to `games` independent games of a one-step agent advanced in lock-step on the device (engine rk_greedy_*,
 	csrc/rk_greedy.hip): `mode` "policy" plays every game as `PolicySearch(net)` does (greedy, agents.py:138-142), "value" as
@@ -1752,13 +1780,9 @@ class GreedyBatch(DeepAgent, _ffi.Owner):
 		super().__init__(net, fused_first_layer)
 		if not isinstance(mode, str) or mode not in self.MODES:
 			raise ValueError(f'mode is "policy" or "value", got {mode!r}')
-		for name, v, top in (("games", games, self.MAX_GAMES), ("poll", poll, self.MAX_POLL)):
-			if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= top:
-				raise ValueError(f"{name} must be an integer in 1..{top}, got {v!r}")
-		self.mode, self.games, self.poll = mode, int(games), int(poll)
-		self._h, self._room = None, 0                                       # the engine and the moves per game it has room for
-		self._graph_cache, self.captures = None, 0                          # [net forward, rk_greedy_step], kept (_engine.kept_graph)
-		self._batch = None                                                  # (code, the engine's net batch as a tensor)
+		self.games, self.poll = self._strict_ints(("games", games, self.MAX_GAMES), ("poll", poll, self.MAX_POLL))
+		self.mode = mode
+		self._room = 0                                                      # the moves per game the engine has room for
 		self.status = np.zeros(0, np.int64)
 		self.steps = np.zeros(0, np.int64)
 		self._actions = np.zeros((0, 0), np.uint8)
@@ -1781,19 +1805,7 @@ class GreedyBatch(DeepAgent, _ffi.Owner):
 			self._room = max_states
 		return self._h
 
-	def _free(self):
-		self._graph_cache = None               # it holds the engine's addresses,
-		self._batch = None                     # and this is the engine's memory
-		super()._free()
-
-	def _net_in(self, h, code: int):
-		if self._batch is None or self._batch[0] != code:
-			ptr, rows = C.c_void_p(), C.c_size_t()
-			_ffi.check(_ffi.lib().rk_greedy_net_in(h, code, C.byref(ptr), C.byref(rows)))
-			self._batch = (code, eng.engine_batch(ptr.value, rows.value, code))      # (the engine goes on writing the form it was asked for last)
-		return self._batch[1]
-
-	# -- the captured step ------------------------------------------------------------------------------------
+	# -- the captured step: [net forward, rk_greedy_step] ---------------------------------------------------------
 	def _move(self, h, batch):
 		if self.mode == "policy":
 			out, code = eng.engine_logits(self._forward(batch, policy=True, value=False))
@@ -1829,16 +1841,10 @@ class GreedyBatch(DeepAgent, _ffi.Owner):
 		self.status, self.steps, self._actions = np.zeros(n, np.int64), np.zeros(n, np.int64), np.zeros((n, 0), np.uint8)
 		lib, stream = _ffi.lib(), _ffi.stream_ptr()
 		h = self._engine(max_states)
-		batch = self._net_in(h, code)
-		# The captured step holds addresses (the engine's arrays and batch, the net's tensors) and the dtype code -- nothing of a
-		# search, which lives in device memory that rk_greedy_reset rewrites: the graph is kept from search to search.  It is captured
-		# on an engine that has been reset; the warm-up's move is undone by the reset below.
+		batch, = self._net_batches(h, code, (lib.rk_greedy_net_in,))
 		key = (h.value, code, batch.data_ptr(), self.mode, self.games, eng.capture_key(self.net, forward))
-		if self._graph_cache is None or self._graph_cache[0] != key:
-			_ffi.check(lib.rk_greedy_reset(h, roots.ctypes.data, n, max_states, stream))
-		move = lambda: self._move(h, batch)                    # noqa: E731
-		graph, _ = eng.kept_graph(self, key, move, move, batch, ((self.net, forward),))
-		_ffi.check(lib.rk_greedy_reset(h, roots.ctypes.data, n, max_states, stream))
+		reset = lambda: _ffi.check(lib.rk_greedy_reset(h, roots.ctypes.data, n, max_states, stream))      # noqa: E731
+		graph, = self._kept_steps(key, forward, reset, (self, lambda: self._move(h, batch), batch))
 		status = (C.c_longlong * 8)()
 		running = int((roots != _SOLVED20).any(axis=1).sum())
 		while running and self.launched < max_states and time.perf_counter() - t0 < time_limit:
@@ -1870,7 +1876,7 @@ class GreedyBatch(DeepAgent, _ffi.Owner):
 		return f"Greedy {self.mode} x{self.games} (device)"
 
 
-class DeviceBeamSearch(DeepAgent, _ffi.Owner):
+class DeviceBeamSearch(_NetStepped):
 	"""
 	Beam search guided by the net's value head, higher is better as in `ValueSearch` (engine rk_beam_*, csrc/rk_beam.hip): every
 	depth keeps the best `width` states.  The beam, the `back` record, the sizes, the dedup table and the net batch live in HBM; a
@@ -1902,16 +1908,11 @@ class DeviceBeamSearch(DeepAgent, _ffi.Owner):
 	def __init__(self, net, width: int, max_depth: int = 64, ball: DeviceSymBall = None, prune_inverse: bool = True, poll: int = 8,
 	             fused_first_layer=False):
 		super().__init__(net, fused_first_layer)
-		for name, v, top in (("width", width, self.MAX_WIDTH), ("max_depth", max_depth, self.MAX_DEPTH), ("poll", poll, self.MAX_POLL)):
-			if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= top:
-				raise ValueError(f"{name} must be an integer in 1..{top}, got {v!r}")
+		self.width, self.max_depth, self.poll = self._strict_ints(("width", width, self.MAX_WIDTH), ("max_depth", max_depth, self.MAX_DEPTH),
+		                                                          ("poll", poll, self.MAX_POLL))
 		if ball is not None and not (isinstance(ball, DeviceSymBall) and ball.built):
 			raise ValueError(f"ball must be None or a built DeviceSymBall (call ball.build() first), got {ball!r}")
-		self.width, self.max_depth, self.poll = int(width), int(max_depth), int(poll)
 		self.ball, self.prune_inverse = ball, bool(prune_inverse)
-		self._h = None
-		self._graph_cache, self.captures = None, 0                          # [net forward, rk_beam_step], kept (_engine.kept_graph)
-		self._batch = None                                                  # (code, the engine's net batch as a tensor)
 		self._clear()
 
 	def _clear(self):
@@ -1932,19 +1933,7 @@ class DeviceBeamSearch(DeepAgent, _ffi.Owner):
 			             int(self.prune_inverse))
 		return self._h
 
-	def _free(self):
-		self._graph_cache = None               # it holds the engine's addresses,
-		self._batch = None                     # and this is the engine's memory
-		super()._free()
-
-	def _net_in(self, h, code: int):
-		if self._batch is None or self._batch[0] != code:
-			ptr, rows = C.c_void_p(), C.c_size_t()
-			_ffi.check(_ffi.lib().rk_beam_net_in(h, code, C.byref(ptr), C.byref(rows)))
-			self._batch = (code, eng.engine_batch(ptr.value, rows.value, code))       # (the engine goes on writing the form it was asked for last)
-		return self._batch[1]
-
-	# -- the captured step ------------------------------------------------------------------------------------
+	# -- the captured step: [net forward, rk_beam_step] -----------------------------------------------------------
 	def _depth_step(self, h, batch):
 		values, code = eng.engine_values(_sliced_value_forward(self._forward, batch))
 		self._keep = values                    # the kernels read it after this call returns
@@ -1975,16 +1964,10 @@ class DeviceBeamSearch(DeepAgent, _ffi.Owner):
 		budget = _ffi.INT64_MAX if max_states is None else int(max_states)
 		lib, stream = _ffi.lib(), _ffi.stream_ptr()
 		h = self._engine()
-		batch = self._net_in(h, code)
-		# The captured step holds addresses (the engine's arrays and batch, the net's tensors) and the dtype code -- nothing of a
-		# search, which lives in device memory that rk_beam_reset rewrites: the graph is kept from search to search.  It is captured
-		# on an engine that has been reset; the warm-up's depth is undone by the reset below.
+		batch, = self._net_batches(h, code, (lib.rk_beam_net_in,))
 		key = (h.value, code, batch.data_ptr(), eng.capture_key(self.net, forward))
-		if self._graph_cache is None or self._graph_cache[0] != key:
-			_ffi.check(lib.rk_beam_reset(h, root.ctypes.data, budget, stream))
-		step = lambda: self._depth_step(h, batch)              # noqa: E731
-		graph, _ = eng.kept_graph(self, key, step, step, batch, ((self.net, forward),))
-		_ffi.check(lib.rk_beam_reset(h, root.ctypes.data, budget, stream))
+		reset = lambda: _ffi.check(lib.rk_beam_reset(h, root.ctypes.data, budget, stream))                # noqa: E731
+		graph, = self._kept_steps(key, forward, reset, (self, lambda: self._depth_step(h, batch), batch))
 		st = self._poll(h)                                     # (a start inside the ball has won at the reset)
 		launched = 0
 		while st[0] == 0 and launched < self.max_depth and time.perf_counter() - t0 < time_limit:
