@@ -854,6 +854,44 @@ int rk_beam_export(rk_beam_t *h, int depth, long long *h_sizes, long long *h_bac
  * max_len actions.  Synchronises. */
 long long rk_beam_path(rk_beam_t *h, long long *h_actions, size_t max_len, void *stream);
 
+/* ---- beam searches of many states in lock-step (rk_beamb_*) ----
+ * `searches` slots, each a whole rk_beam search of its own (beam, back record, sizes, dedup table, histograms, look-back words,
+ * counters, root); all share width, max_depth, prune_inverse and the ball, and differ in start, budget, depth reached and status.
+ * One net batch of searches x 12 width rows per form: slot s owns rows [12 width s, 12 width (s + 1)), and its values are
+ * d_out[12 width s ..] of the one forward.  A depth of all slots is [net forward, rk_beamb_step].  A slot is running (status 0),
+ * stopped as rk_beam_status says (1..4), or at rest (5): never started, or put to rest.  After a slot stops a step writes nothing
+ * of it.  Every slot gets what rk_beam_* gives its start alone.  A handle is not thread-safe. */
+typedef struct rk_beamb rk_beamb_t;
+/* searches 1..1024, width 1..65536, searches * width <= 65536, max_depth 1..4096 (RK_EINVAL before anything is allocated); ball as
+ * for rk_beam_create.  Every slot is at rest.  RK_ECAPACITY when the device has no room. */
+int rk_beamb_create(rk_beamb_t **out, rk_symball_t *ball, int searches, int width, int max_depth, int prune_inverse);
+int rk_beamb_destroy(rk_beamb_t *h);
+/* As rk_beam_net_in: *rows = searches x 12 width.  After a form is handed out that is not the one the engine writes, the next
+ * rk_beamb_reset or rk_beamb_rest first writes the solved state into EVERY row of every slot in that form and puts every running
+ * slot to rest: a slot that was not started in the current form holds legal rows and is not running. */
+int rk_beamb_net_in(rk_beamb_t *h, int out_dtype, void **d_ptr, size_t *rows);
+/* Slot slots[j] (all different, 0..searches-1) starts again from host state j (20 bytes each, cubie codes checked before anything
+ * is enqueued) with the budget max_states[j] >= 0: its counters, F_0, the ball look-up of the start (inside the ball: won here,
+ * meeting action -1), table, look-back words, histograms and sizes cleared, all its 12 width rows written (the start's children,
+ * then the solved state).  Nothing of any other slot is touched, so it may run between two steps while other slots are
+ * mid-search.  A fixed number of copies and launches per call, whatever n.  Synchronises. */
+int rk_beamb_reset(rk_beamb_t *h, int n, const int32_t *slots, const int8_t *h_start_states, const long long *max_states, void *stream);
+/* The named slots that are running are put to rest (status 5) without a search; a stopped slot keeps its result.  Only the status
+ * word is written.  Synchronises. */
+int rk_beamb_rest(rk_beamb_t *h, int n, const int32_t *slots, void *stream);
+/* One depth of every running slot.  d_out: the net's values on the whole batch, (searches x 12 width) contiguous, float32 or
+ * bfloat16.  rk_beam_step's sequence of launches (nine with a ball, eight without) with the slot in the grid's second dimension,
+ * nothing else.  RK_ESTATE before the first reset or rest in the current form.  No synchronisation. */
+int rk_beamb_step(rk_beamb_t *h, const void *d_out, int dtype, void *stream);
+/* Synchronises; h_status (searches, 12): rk_beam_status's words of every slot, read with one copy. */
+int rk_beamb_status(rk_beamb_t *h, long long *h_status, void *stream);
+/* One launch, a wave per slot; h_out int32 (searches, 1 + max_len), max_len <= max_depth + 1 + 10: word 0 the length of the slot's
+ * action queue (rk_beam_path's), -1 for a slot that has not won, -2 when the record does not lead home or the queue is longer than
+ * max_len; then the actions.  Synchronises. */
+int rk_beamb_paths(rk_beamb_t *h, int32_t *h_out, int max_len, void *stream);
+/* rk_beam_export of one slot. */
+int rk_beamb_export(rk_beamb_t *h, int slot, int depth, long long *h_sizes, long long *h_back, size_t back_len, void *stream);
+
 /* ---- batched A*: S independent searches in lock-step, no host synchronisation inside an iteration -------------
  * Every search is a complete rk_astar_* engine (agents.py:171-413: its own pool, hash table, open queue, counter block);
  * the batch launches the same kernels with a second grid dimension (search), so one iteration of ALL searches is the

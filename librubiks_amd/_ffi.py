@@ -190,6 +190,15 @@ SIGNATURES = {
 	"rk_beam_status": (_i, [_vp, _vp, _vp]),
 	"rk_beam_export": (_i, [_vp, _i, _vp, _vp, _sz, _vp]),
 	"rk_beam_path": (C.c_longlong, [_vp, _vp, _sz, _vp]),
+	"rk_beamb_create": (_i, [C.POINTER(_vp), _vp, _i, _i, _i, _i]),
+	"rk_beamb_destroy": (_i, [_vp]),
+	"rk_beamb_net_in": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_sz)]),
+	"rk_beamb_reset": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
+	"rk_beamb_rest": (_i, [_vp, _i, _vp, _vp]),
+	"rk_beamb_step": (_i, [_vp, _vp, _i, _vp]),
+	"rk_beamb_status": (_i, [_vp, _vp, _vp]),
+	"rk_beamb_paths": (_i, [_vp, _vp, _i, _vp]),
+	"rk_beamb_export": (_i, [_vp, _i, _i, _vp, _vp, _sz, _vp]),
 	"rk_astarb_create": (_i, [C.POINTER(_vp), _i, _sz, _i]),
 	"rk_astarb_destroy": (_i, [_vp]),
 	"rk_astarb_reset": (_i, [_vp, _vp, _vp, C.c_double, _vp]),

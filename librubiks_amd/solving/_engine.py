@@ -3,7 +3,7 @@ What the agents that drive a device engine share on the host, each concern defin
 step becomes a kept hipGraph, and how a finished search is read back (the lifetime of a library object is `_ffi.Owner`).  The
 engines: `rk_astar_*` (single and sharded), `rk_astarb_*`, `rk_mcts_*`; the breadth-first and ball searches `rk_bfs_*`,
 `rk_bibfs_*`, `rk_bsearch_*`, `rk_ssearch_*` and the batched `rk_bsearchb_*`, `rk_ssearchb_*`, which run no net; and the net-stepped engines
-`rk_egvm_*`, `rk_greedy_*`, `rk_beam_*`, which own their net batch (`engine_batch`).  agents.py and sharded.py hold what differs
+`rk_egvm_*`, `rk_greedy_*`, `rk_beam_*`, `rk_beamb_*`, which own their net batch (`engine_batch`).  agents.py and sharded.py hold what differs
 between the engines; what the agents of a family share beyond this module is a private base there (`_PoolSearch`, `_BallSearch`,
 `_BallSearchBatch`, and `_NetStepped`: the engine-owned batches as tensors, the kept steps and their lifetime).
 """

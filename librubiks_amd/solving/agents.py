@@ -1570,7 +1570,7 @@ class _KeptGraph:
 
 class _NetStepped(DeepAgent, _ffi.Owner):
 	"""
-	What the agents of the net-stepped engines share (rk_egvm_*, rk_greedy_*, rk_beam_*; the engines' side is at the end of
+	What the agents of the net-stepped engines share (rk_egvm_*, rk_greedy_*, rk_beam_*, rk_beamb_*; the engines' side is at the end of
 	csrc/rk_search_host.h).  The ENGINE owns the net's batch in HBM, one buffer per RK_OH_* form; `_batch` = (code, tensor, ...)
 	wraps the form the net wants now.  A step -- a net forward on that batch plus the engine's launches -- is captured once as a
 	hipGraph and kept from search to search in a holder that `_engine.kept_graph` writes to (`_holders`: the agent itself, or one
@@ -1997,6 +1997,239 @@ class DeviceBeamSearch(_NetStepped):
 
 	def __str__(self):
 		return f"Beam search (device, width={self.width}" + (f", to a symmetry ball of radius {self.ball.radius})" if self.ball is not None else ")")
+
+
+class DeviceBeamSearchBatch(_NetStepped):
+	"""
+	Beam searches of many states at once: `searches` slots, each a whole `DeviceBeamSearch` of its own (beam, `back` record, sizes,
+	dedup table, histograms, look-back words, counters), advanced in lock-step (engine rk_beamb_*, csrc/rk_beam.hip).  A depth of
+	ALL slots is one value forward on the searches x 12 x `width` rows of one batch -- slot s owns rows [12 width s, 12 width (s + 1))
+	-- and the single engine's sequence of launches with the slot in the grid's second dimension, captured once as a hipGraph and
+	kept from call to call.  A single beam search at the usual widths is bound by the latency of its launches, not by its work; the
+	batch pays the launches and the forward once for all slots.
+
+	`search(states)` takes any number of states.  Slots take them in input order; every `poll` replayed depths (never more than the
+	running slots have left of `max_depth`) the host reads all slots' status, records the searches that finished -- their queues;
+	with `keep_arrays` their `sizes` and every `back` row, before the slot is used again -- and starts the next waiting states in the
+	slots that became free.  A solved start is answered on the host as `DeviceBeamSearch` does (status 1, depth 0, nothing explored,
+	no meeting, an empty queue) and takes no slot; a start whose orbit the ball holds is done at its slot's reset.  `max_states`: one
+	budget for all, or one per state (n,), None for no budget.  `time_limit` bounds the whole call and is checked at the polls:
+	searches still running or waiting when it passes come back False with status 0.  After a call, whether it returned or raised,
+	no slot is running; an exception frees the engine.
+
+	On nets whose outputs do not depend on the shape of the batch, every state gets exactly what `DeviceBeamSearch(net, width,
+	max_depth, ball, prune_inverse)` gives it alone -- solved, status, depth, states explored, sizes, every `back` word, the meeting
+	and the queue --, bit for bit, whatever slot it ran in, whenever it was started and whatever `searches` and `poll` are.  With a
+	real-valued net a forward on searches x 12 x width rows need not equal a forward on 12 x width rows bit for bit, so a near-tie
+	between two values may resolve differently than in a search run alone.
+
+	After a call, indexed by input position: `status` (n, 12) -- rk_beam_status's words: status (0 running when the time ran out, 1
+	won, 2 budget, 3 depth limit), depths run, states explored, size of the last beam, error, the winning child's member, its action
+	(-1: the start itself, inside the ball) and its ball depth, the budget, the depth of the last beam --, `lengths` (-1: no queue),
+	`depths`, `meetings` ((i, a, ball depth) or None), `action_queue_of(i)`, and with `keep_arrays` `sizes_of(i)` and `back_of(i, t)`.
+	`on_poll(status)`, if set, is called at every poll with the status of the states seen finished so far (zeros for the others).
+	`lockstep_depths` counts the depths of all slots the last call launched, `captures` the hipGraph captures so far; len(b) is the
+	sum of the states explored.  The representation follows cube.get_is2024() when a call starts (6x8x6 nets read the engine's
+	20-byte rows through _Net686).
+	"""
+	MAX_SEARCHES, MAX_WIDTH, MAX_DEPTH, MAX_POLL = 1 << 10, 1 << 16, 1 << 12, 1 << 12      # rk_beamb_create's limits
+	MAX_BEAMS = 1 << 16                                                                   # ... on searches * width
+
+	def __init__(self, net, width: int, searches: int = 64, max_depth: int = 64, ball: DeviceSymBall = None, prune_inverse: bool = True,
+	             poll: int = 8, fused_first_layer=False):
+		super().__init__(net, fused_first_layer)
+		self.width, self.searches, self.max_depth, self.poll = self._strict_ints(
+			("width", width, self.MAX_WIDTH), ("searches", searches, self.MAX_SEARCHES), ("max_depth", max_depth, self.MAX_DEPTH),
+			("poll", poll, self.MAX_POLL))
+		if self.searches * self.width > self.MAX_BEAMS:
+			raise ValueError(f"searches * width must not exceed {self.MAX_BEAMS}, got {self.searches * self.width}")
+		if ball is not None and not (isinstance(ball, DeviceSymBall) and ball.built):
+			raise ValueError(f"ball must be None or a built DeviceSymBall (call ball.build() first), got {ball!r}")
+		self.ball, self.prune_inverse = ball, bool(prune_inverse)
+		self.on_poll = None                    # callable(status (n, 12)): called at every poll
+		self.lockstep_depths = 0               # depths of all slots the last call launched
+		self._results(0, False)
+
+	def _results(self, n: int, keep_arrays: bool):
+		self.status = np.zeros((n, 12), np.int64)
+		self.lengths = np.full(n, -1, np.int64)
+		self.meetings = [None] * n
+		self._queues = [deque() for _ in range(n)]
+		self._arrays = [(np.ones(1, np.int64), [None]) for _ in range(n)] if keep_arrays else None      # (sizes, back rows) per state
+
+	depths = property(lambda self: self.status[:, 1])
+
+	# -- engine lifetime ------------------------------------------------------------------------------------
+	def _engine(self):
+		if self._h is None:
+			self._create("rk_beamb_create", "rk_beamb_destroy", self.ball._h if self.ball is not None else None, self.searches, self.width,
+			             self.max_depth, int(self.prune_inverse))
+		return self._h
+
+	# -- the captured step: [value forward on all searches x 12 width rows, rk_beamb_step] ---------------------------
+	def _depth_step(self, h, batch):
+		values, code = eng.engine_values(_sliced_value_forward(self._forward, batch))
+		self._keep = values                    # the kernels read it after this call returns
+		_ffi.check(_ffi.lib().rk_beamb_step(h, values.data_ptr(), code, _ffi.stream_ptr()))
+
+	def _rest(self, h, slots):
+		sl = np.ascontiguousarray(slots, dtype=np.int32)
+		_ffi.check(_ffi.lib().rk_beamb_rest(h, len(sl), sl.ctypes.data if len(sl) else None, _ffi.stream_ptr()))
+
+	def _start(self, h, slots, rows: np.ndarray, budgets: np.ndarray):
+		sl = np.ascontiguousarray(slots, dtype=np.int32)
+		rows, budgets = np.ascontiguousarray(rows, dtype=np.int8), np.ascontiguousarray(budgets, dtype=np.int64)
+		_ffi.check(_ffi.lib().rk_beamb_reset(h, len(sl), sl.ctypes.data, rows.ctypes.data, budgets.ctypes.data, _ffi.stream_ptr()))
+
+	def _paths(self, h) -> np.ndarray:
+		max_len = self.max_depth + 1 + DeviceSymBall.MAX_RADIUS
+		out = np.zeros((self.searches, 1 + max_len), np.int32)
+		_ffi.check(_ffi.lib().rk_beamb_paths(h, out.ctypes.data, max_len, _ffi.stream_ptr()))
+		return out
+
+	def _record(self, h, s: int, t: int) -> tuple:
+		"""(sizes, back rows) of the search in slot `s`, whose last beam is that of depth `t`, as `DeviceBeamSearch.sizes` and its `back_of(t)`."""
+		lib, stream = _ffi.lib(), _ffi.stream_ptr()
+		sizes = np.zeros(self.max_depth + 1, np.int64)
+		_ffi.check(lib.rk_beamb_export(h, s, 0, sizes.ctypes.data, None, 0, stream))
+		sizes = sizes[:t + 1].copy()
+		back = [None]
+		for t in range(1, len(sizes)):
+			row = np.zeros(int(sizes[t]), np.int64)
+			_ffi.check(lib.rk_beamb_export(h, s, t, None, row.ctypes.data, len(row), stream))
+			back.append(row)
+		return sizes, back
+
+	@staticmethod
+	def _budgets(max_states, n: int) -> np.ndarray:
+		"""int64 (n,): one budget for all or one per state, None (also inside a list) for no budget."""
+		if max_states is None or np.ndim(max_states) == 0:
+			given = [max_states] * n
+		else:
+			given = list(max_states)
+			if np.ndim(max_states) != 1 or len(given) != n:
+				raise ValueError(f"max_states must be a number or one per state, got shape {np.shape(max_states)}")
+		out = np.zeros(n, np.int64)
+		for i, b in enumerate(given):
+			if b is None:
+				out[i] = _ffi.INT64_MAX
+				continue
+			if isinstance(b, (bool, np.bool_)) or int(b) != b or int(b) < 0:
+				raise ValueError(f"max_states must be non-negative integers or None, got {b!r}")
+			out[i] = min(int(b), _ffi.INT64_MAX)
+		return out
+
+	# -- search -------------------------------------------------------------------------------------------------
+	@no_grad
+	def search(self, states, time_limit: float = None, max_states=None, keep_arrays: bool = False) -> np.ndarray:
+		"""bool (n,): whether each state's search won (`lengths` >= 0)."""
+		t0 = time.perf_counter()
+		time_limit = time_limit or 1e10
+		arr = np.asarray(states, dtype=np.int8)
+		row_size = 20 if cube.get_is2024() else 288
+		if arr.size % row_size:                                # before anything asks for a device
+			raise ValueError(f"states must be (n, 20), or (n, 6, 8, 6) in 6x8x6 mode, got shape {arr.shape}")
+		n = arr.size // row_size
+		budgets = self._budgets(max_states, n)
+		self._results(n, keep_arrays)
+		self.lockstep_depths = 0
+		if n == 0:
+			return np.zeros(0, bool)
+		_ffi.require_gpu()
+		self.net.eval()
+		forward, _, code = self._begin_net()
+		rows = self._roots20(arr, n)                           # ValueError for an illegal 6x8x6 state, before anything runs
+		home = (rows == _SOLVED20).all(axis=1)                 # solved starts: no slot, no launch
+		self.status[home, 0] = 1
+		self.lengths[home] = 0
+		pending = np.nonzero(~home)[0]
+		if len(pending) == 0:
+			return self.lengths >= 0
+		lib, stream = _ffi.lib(), _ffi.stream_ptr()
+		try:
+			h = self._engine()
+			batch, = self._net_batches(h, code, (lib.rk_beamb_net_in,))
+			key = (h.value, code, batch.data_ptr(), self.searches, eng.capture_key(self.net, forward))
+			# (every slot is at rest between calls, and resting makes every row legal in this form: the warm-up step moves nothing)
+			graph, = self._kept_steps(key, forward, lambda: self._rest(h, []), (self, lambda: self._depth_step(h, batch), batch))
+			S = self.searches
+			holds = np.full(S, -1, np.int64)       # the input position every slot runs, -1: free
+			waiting = 0                            # the next of `pending` to start
+			st = np.zeros((S, 12), np.int64)
+			while True:
+				_ffi.check(lib.rk_beamb_status(h, st.ctypes.data, stream))
+				held = holds >= 0
+				if st[held, 4].any() or (st[held, 0] >= 4).any():
+					raise _ffi.RubiksHipError(f"beam engine: status {st[held, 0].tolist()}, error codes {st[held, 4].tolist()}")
+				done = np.nonzero(held & (st[:, 0] != 0))[0]
+				if len(done):
+					paths = self._paths(h) if (st[done, 0] == 1).any() else None
+					for s in done.tolist():
+						i = int(holds[s])
+						self.status[i] = st[s]
+						if st[s, 0] == 1:
+							if paths[s, 0] < 0:
+								raise _ffi.RubiksHipError(f"rk_beamb_paths: the search of state {i} won, but its queue cannot be walked ({int(paths[s, 0])})")
+							self.lengths[i] = paths[s, 0]
+							self._queues[i] = deque(paths[s, 1:1 + paths[s, 0]].tolist())
+							self.meetings[i] = (int(st[s, 5]), int(st[s, 6]), int(st[s, 7]))
+						if keep_arrays:
+							self._arrays[i] = self._record(h, s, int(st[s, 9]))
+						holds[s] = -1
+				if self.on_poll is not None:
+					self.on_poll(self.status)
+				late = time.perf_counter() - t0 >= time_limit
+				free = np.nonzero(holds < 0)[0]
+				if waiting < len(pending) and len(free) and not late:
+					free = free[:len(pending) - waiting]
+					took = pending[waiting:waiting + len(free)]
+					self._start(h, free, rows[took], budgets[took])
+					holds[free] = took
+					waiting += len(free)
+					continue                       # a start the ball holds is done already: look before running
+				live = holds >= 0
+				if late or not live.any():
+					break
+				burst = max(1, min(self.poll, int((self.max_depth - st[live, 9]).max())))    # a running slot advances at every replay
+				for _ in range(burst):
+					graph.replay()
+				self.lockstep_depths += burst
+			live = np.nonzero(holds >= 0)[0]
+			if len(live):                          # out of time: what the searches had reached, status 0; then the slots are put to rest
+				for s in live.tolist():
+					i = int(holds[s])
+					self.status[i] = st[s]
+					if keep_arrays:
+						self._arrays[i] = self._record(h, s, int(st[s, 9]))
+				self._rest(h, live)
+		except Exception:
+			self._free()                           # slots in an unknown state: the next call starts from a new engine
+			raise
+		return self.lengths >= 0
+
+	def action_queue_of(self, i: int) -> deque:
+		return deque(self._queues[i])
+
+	def _kept(self, i: int) -> tuple:
+		if self._arrays is None:
+			raise ValueError("the records were not kept: search(..., keep_arrays=True)")
+		return self._arrays[i]
+
+	def sizes_of(self, i: int) -> np.ndarray:
+		"""int64: m_t of every beam state i's search formed, as `DeviceBeamSearch.sizes`; needs `keep_arrays`."""
+		return self._kept(i)[0]
+
+	def back_of(self, i: int, t: int) -> np.ndarray:
+		"""int64 (m_t,): the `back` words of the beam of depth t (1 .. len(sizes_of(i)) - 1) of state i's search; needs `keep_arrays`."""
+		sizes, back = self._kept(i)
+		return back[eng.int_in("t", t, 1, len(sizes) - 1)]
+
+	def __len__(self):
+		return int(self.status[:, 2].sum())
+
+	def __str__(self):
+		return (f"Beam searches x{self.searches} (device, width={self.width}"
+		        + (f", to a symmetry ball of radius {self.ball.radius})" if self.ball is not None else ")"))
 
 
 def _load_net(loc: str, use_best: bool, loader=None):

@@ -7,8 +7,8 @@ game) and `times` (seconds).  Plots are not mirrored (UI, out of scope).
 Two ways to play the games:
 
   * one after the other (evaluation.py:68-84 to the letter): any agent, any limit;
-  * `batched`: all games of an `AStar`, `MCTS`, `DeviceBallSearch` or `DeviceSymBallSearch` agent advance in lock-step on the device
-    (`AStarBatch`, `MCTSBatch`, `DeviceBallSearchBatch`, `DeviceSymBallSearchBatch`), the form the engines were built for -- the reference plays 100 games per depth one at a time.  The scrambles are drawn from
+  * `batched`: all games of an `AStar`, `MCTS`, `DeviceBallSearch`, `DeviceSymBallSearch` or `DeviceBeamSearch` agent advance in lock-step on the device
+    (`AStarBatch`, `MCTSBatch`, `DeviceBallSearchBatch`, `DeviceSymBallSearchBatch`, `DeviceBeamSearchBatch`), the form the engines were built for -- the reference plays 100 games per depth one at a time.  The scrambles are drawn from
     the global NumPy generator in exactly the order the sequential loop draws them (A* and MCTS draw nothing while they
     search, so the interleaving of scrambling and searching does not matter), every search is the sequential search bit for
     bit, and so `res` and `states` are equal entry by entry for games bounded by `max_states`
@@ -83,11 +83,11 @@ class Evaluator:
 
 	@staticmethod
 	def can_batch(agent) -> bool:
-		"""Exactly these classes (a subclass may search differently): AStar, MCTS, DeviceBallSearch, DeviceSymBallSearch, ValueSearch,
-		and PolicySearch unless it samples."""
+		"""Exactly these classes (a subclass may search differently): AStar, MCTS, DeviceBallSearch, DeviceSymBallSearch,
+		DeviceBeamSearch (played on DeviceBeamSearchBatch), ValueSearch, and PolicySearch unless it samples."""
 		if type(agent) is agents.PolicySearch:
 			return not agent.sample_policy
-		return type(agent) in (agents.AStar, agents.MCTS, agents.ValueSearch, agents.DeviceBallSearch, agents.DeviceSymBallSearch)
+		return type(agent) in (agents.AStar, agents.MCTS, agents.ValueSearch, agents.DeviceBallSearch, agents.DeviceSymBallSearch, agents.DeviceBeamSearch)
 
 	def eval(self, agent, batched: bool = None):
 		"""
@@ -167,6 +167,11 @@ class Evaluator:
 			# (a search stops at max_states before it pops, and a pop adds at most 12 states per node: this pool is never full)
 			batch = agents.DeviceSymBallSearchBatch if isinstance(agent, agents.DeviceSymBallSearch) else agents.DeviceBallSearchBatch
 			b = batch(agent.ball, n, pops=agent.pops, poll=agent.poll, capacity=min(cap + 12 * agent.pops, batch.MAX_CAPACITY))
+		elif isinstance(agent, agents.DeviceBeamSearch):
+			# (as many slots as the engine takes at this width; the batch's refill plays the rest of the n games)
+			batch = agents.DeviceBeamSearchBatch
+			b = batch(agent.net, agent.width, searches=min(n, max(1, batch.MAX_BEAMS // agent.width)), max_depth=agent.max_depth, ball=agent.ball,
+			          prune_inverse=agent.prune_inverse, poll=agent.poll, fused_first_layer=agent._fused_mode)
 		elif isinstance(agent, agents.AStar):
 			b = agents.AStarBatch(agent.net, agent.lambda_, agent.expansions, n, capacity=cap, fused_first_layer=agent._fused_mode)
 		else:
@@ -184,7 +189,7 @@ class Evaluator:
 		try:
 			# max_time, if given, is every game's limit on the batch's one clock (the games share the device: each gets less of it
 			# than a game played alone would -- which is why eval() only chooses this form by itself for games without a time limit)
-			if isinstance(b, (agents.AStarBatch, agents.GreedyBatch, agents.DeviceBallSearchBatch, agents.DeviceSymBallSearchBatch)):
+			if isinstance(b, (agents.AStarBatch, agents.GreedyBatch, agents.DeviceBallSearchBatch, agents.DeviceSymBallSearchBatch, agents.DeviceBeamSearchBatch)):
 				solved = b.search(starts, self.max_time, self.max_states)
 			else:
 				solved = b.search(starts, self.max_time, max_states=self.max_states, use_graph=b.priors != "reference")
