@@ -569,6 +569,37 @@ int rk_symball_child_values(rk_symball_t *h, const int8_t *d_states, size_t m12,
                             int8_t *d_outside, int32_t *d_count, void *d_scratch, size_t scratch_bytes, void *stream);
 /* Bytes of d_scratch for m12 children: 4 * ceil(m12 / 256); RK_EINVAL above INT32_MAX.  Touches no device. */
 long long rk_symball_child_values_scratch_bytes(size_t m12);
+/* Unranking the ball.  THE STATE OF (d, r), 0 <= d <= radius, 0 <= r < (the orbit sizes of level d added up, status word 18 + d),
+ * is the k-th distinct conjugate, in ascending symmetry order, of the node j of level d whose cumulative orbit range holds r:
+ * with the nodes of level d in index order and their orbit sizes o(j), j is the node with sum_{i < j} o(i) <= r < sum_{i <= j} o(i)
+ * and k = r - sum_{i < j} o(i); the distinct conjugates of j's representative are conj_s of it for the symmetries s = 0 .. 47 in
+ * that order, a conjugate that a lower symmetry gave already left out.  For every d the map r -> state is a bijection onto the
+ * states at distance d from solved; like the pool it does not depend on `pops`.
+ * Row i of DEVICE d_states int8 (n, 20) = the state of (d_depth[i], d_rank[i]), d_depth int32 (n), d_rank int64 (n, 8-byte
+ * aligned), n at most INT32_MAX.  d_error[0] is cleared, then set to RK_EINVAL if a depth lies outside 0..radius or a rank outside
+ * its level -- that row is written as zeros, every other row is right -- or to RK_ESTATE if the index contradicts the ball (never
+ * after a call that passed).  One launch, a wave per sample; nothing is written but d_states and d_error; stream-ordered, no
+ * synchronisation -- except in the first call on a ball, which makes the ORBIT INDEX and synchronises for it: one byte per orbit
+ * (its orbit size) and a 64-bit prefix per 256 orbits, 161 MB at radius 10, kept in HBM until rk_symball_destroy.  The index is
+ * made by four launches (a wave per node: the node must be its own canonical form) and accepted only if the orbit sizes of every
+ * level add up to what the build reported (RK_ESTATE otherwise; RK_ECAPACITY when the device has no room; the ball stays usable
+ * and without an index).  A ball that never samples allocates nothing for it. */
+int rk_symball_state_at(rk_symball_t *h, const int32_t *d_depth, const int64_t *d_rank, size_t n, int8_t *d_states, int32_t *d_error,
+                        void *stream);
+/* h_status[16] = how often the orbit index was made (0 or 1), its bytes, its tiles, 0, then at [4 .. 15] the cumulative orbit
+ * sizes below levels 0 .. 11: level d's ranks are word 4 + d .. word 5 + d of the global cumulative (zeros before the index is
+ * made and beyond radius + 1).  Touches no device. */
+int rk_symball_index_status(rk_symball_t *h, long long *h_status);
+/* The exact distance to solved of every DEVICE state of d_states int8 (n, 20) and of its twelve children in action order:
+ * d_depth int8 (n), d_child int8 (n, 12).  A quarter turn changes the distance by exactly one, so with R = radius and c =
+ * rk_symball_depth's answer: a state with c >= 0 gets c, its children inside the ball their own c and the others c + 1 (= R + 1); a
+ * state outside the ball with a child inside gets R + 1, its children inside R and the others R + 2; a state with no child
+ * inside gets -1 thirteen times.  Every answer >= 0 is exact, and every state within R + 1 of solved gets one.  d_error[0] is
+ * cleared, then set to RK_ESTATE if the levels around a state contradict the parity (never in a ball that passed its build).  One
+ * launch, a wave per state, thirteen probes; the ball is only read; stream-ordered, no synchronisation.  All pointers but d_child
+ * 4-byte aligned. */
+int rk_symball_child_depths(rk_symball_t *h, const int8_t *d_states, size_t n, int8_t *d_depth, int8_t *d_child, int32_t *d_error,
+                            void *stream);
 /* Depth-first probes past the ball's radius: for every DEVICE state i of d_states int8 (n, 20) and every word of `extra` moves
  * (1..8) whose rank lies in [word_first, word_first + word_count), the word is applied to the state, the result canonicalised and
  * looked up in the ball; if the ball holds it, atomicMin(d_best[i], rank).  A word is a sequence of actions 0..11 in which no

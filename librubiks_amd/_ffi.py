@@ -138,6 +138,9 @@ SIGNATURES = {
 	"rk_symball_solve": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp]),
 	"rk_symball_child_values": (_i, [_vp, _vp, _sz, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 	"rk_symball_child_values_scratch_bytes": (C.c_longlong, [_sz]),
+	"rk_symball_state_at": (_i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+	"rk_symball_index_status": (_i, [_vp, _vp]),
+	"rk_symball_child_depths": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp]),
 	"rk_sdeepen": (_i, [_vp, _vp, _vp, _sz, _i, C.c_uint32, C.c_uint32, _vp, _vp]),
 	"rk_sdeepen_max_probes": (C.c_longlong, []),
 	"rk_sshorten": (_i, [_vp, _vp, _vp, _sz, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -99,3 +99,38 @@ def adi_traindata(net, rollout_games: int, rollout_depth: int, alpha: float, rew
 	ws, us = weighted.sum(), len(unweighted)
 	loss_weights = ((1 - alpha) * weighted / ws + alpha * unweighted / us) * (ws + us)
 	return oh_states, policy_targets.cpu(), value_targets.cpu(), torch.from_numpy(loss_weights).float()
+
+
+def ball_traindata(ball, n: int, depths=None, rng=None, reward_method: str = "lapanfix"):
+	"""
+	Supervised ADI data from a `DeviceSymBall(R)` alone, no net involved: n states drawn by `ball.sample(n, depths, rng)` -- uniform
+	at the given depth(s), or uniform over the whole ball for None; the draws are `sample`'s, so a seeded numpy.random.Generator
+	reproduces the rows -- each with its exact targets from `cube.device.ball_child_depths`.  The same four values as `adi_traindata`:
+	the one-hot states on `gpu` (float32, 480 or 288 wide by the representation), then on the CPU
+	  value_targets   float32: V*(0) = 0, V*(d) = g - (d - 1) for d >= 1, g = 0 for reward0 and else 1 (`adi_traindata(ball=)`'s convention)
+	  policy_targets  int64: the lowest action whose child lies one level nearer (`solve`'s rule, and `argmax`'s on ties); 0 at d = 0
+	  loss_weights    float32: all 1
+	A row costs one `state_at` sample and thirteen ball probes.
+	"""
+	assert reward_method in ("paper", "lapanfix", "schultzfix", "reward0")
+	from librubiks_amd.solving.agents import DeviceSymBall
+	if not isinstance(ball, DeviceSymBall):
+		raise TypeError(f"ball must be a DeviceSymBall, not {type(ball).__name__}")
+	_ffi.require_gpu()
+	is2024 = cube.get_is2024()
+	cube.set_is2024(True)                  # the sample as 20-byte rows, whatever the caller's representation
+	try:
+		states, _ = ball.sample(n, depths, rng)
+	finally:
+		cube.set_is2024(is2024)
+	states = torch.from_numpy(states).to(gpu)
+	oh_states = cube.device.as_oh(states) if is2024 else cube.device.to686(states, torch.float32)
+	own, children = cube.device.ball_child_depths(ball, states)
+	own, children = own.long(), children.long()
+	nearer = children == (own - 1).unsqueeze(1)
+	if bool(((own > 0) & ~nearer.any(dim=1)).any()) or bool((own < 0).any()):
+		raise _ffi.RubiksHipError("rk_symball_child_depths: a sampled state has no child one level nearer")
+	policy_targets = torch.argmax(nearer.float(), dim=1)                     # the first of the maxima: the lowest such action
+	g = 0.0 if reward_method == "reward0" else 1.0
+	value_targets = torch.where(own == 0, torch.zeros((), device=gpu), g - (own - 1).float())
+	return oh_states, policy_targets.cpu(), value_targets.cpu(), torch.ones(len(states), dtype=torch.float32)

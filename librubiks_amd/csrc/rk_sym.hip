@@ -33,6 +33,9 @@
 //   k_sb_child_values   k_sb_depth for the 12 n children of an ADI rollout (rk_symball_child_values): the depth as a byte and the exact
 //                 value V*(depth) beside it; then k_sb_outside_count, _scan, _write compact the rows OUTSIDE the ball -- the net's
 //                 batch -- in ascending order
+//   k_sb_state_at the other way round, a wave per sample: (depth, rank) -> the state, through an index over the orbit sizes that is
+//                 made at the first call (k_sb_orbit, _orbit_count, _orbit_scan, _orbit_base) and kept with the ball
+//   k_sb_child_depths   a wave per state: the level of the state and of its 12 children, made exact within radius + 1 by parity
 //
 // The search (rk_ssearch_*) is rk_ball.hip's rk_bsearch_* -- a one-sided breadth-first search from a start, in a pool and table of
 // its own that hold RAW states with parent and action -- with one difference: "the ball holds this child" is "the symmetry ball
@@ -281,6 +284,227 @@ void k_sb_outside_write(const int8_t *depth, const uint32_t *states, size_t n, c
 	load5(states + q * 5, x);
 	#pragma unroll
 	for (int j = 0; j < 5; j++) outside[at * 5 + j] = x[j];
+}
+
+// ---- unranking the ball: the state of (depth, rank) (rk_symball_state_at) and exact depths around a state (rk_symball_child_depths) ----
+// The orbit index, kept with the ball from the first rk_symball_state_at on.  Positions are nodes minus one, a tile is 256 of them:
+//   orbit  one byte per position, the orbit size 48 / |stabiliser| of the node's representative; zero behind the last node up to
+//          the end of the last tile, so a tile is always 64 whole dwords
+//   tile   64-bit exclusive prefix of the orbit sizes per tile, tile[tiles] = the sum of all
+//   base   base[l] = the orbit sizes of all nodes below level l added up, l = 0 .. radius + 1: levels are contiguous node ranges,
+//          so the ranks of level l are the range base[l] .. base[l + 1] - 1 of the global cumulative
+struct SymIndex {
+	const uint32_t *orbit; const unsigned long long *tile;
+	uint32_t tiles, len;
+	unsigned long long base[SB_MAX_RADIUS + 2];
+};
+
+// the sum of the four bytes of a dword
+__device__ __forceinline__ uint32_t bytes_sum(uint32_t w) { return (w & 0xFFu) + ((w >> 8) & 0xFFu) + ((w >> 16) & 0xFFu) + (w >> 24); }
+
+// orbit[node - 1] of every node, a wave per node: the canonical form of the stored representative gives the stabiliser's size,
+// and must give the representative itself at symmetry 0 -- a node that is not its own canonical form sets the error word
+__global__ __launch_bounds__(256)
+void k_sb_orbit(SymBallView b, uint32_t len, uint8_t *orbit, int32_t *error)
+{
+	__shared__ uint32_t s_sym[SYM_LDS_DWORDS];
+	const SymProbe sp = sym_probe(s_sym, 256);
+	for (size_t p = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6); p < (size_t)len; p += (size_t)gridDim.x * 4) {
+		uint32_t x[5], rep[5];
+		load5(b.states + (p + 1) * 5, x);
+		int sym, count;
+		sym_canonical(s_sym, sp.L, sp.lane, x, rep, &sym, &count);
+		bool own = sym == 0;
+		#pragma unroll
+		for (int j = 0; j < 5; j++) own = own && rep[j] == x[j];
+		if (sp.lane == 0) {
+			orbit[p] = (uint8_t)(N_SYM / count);
+			if (!own) *error = RK_ESTATE;
+		}
+	}
+}
+
+// the orbit sizes of a tile added up, a wave per tile: a dword per lane
+__global__ __launch_bounds__(256)
+void k_sb_orbit_count(const uint32_t *orbit, uint32_t tiles, unsigned long long *tile)
+{
+	const uint32_t t = blockIdx.x * 4 + (threadIdx.x >> 6);
+	if (t >= tiles) return;                                              // (whole waves)
+	uint32_t sum = bytes_sum(orbit[(size_t)t * 64 + (threadIdx.x & 63)]);
+	#pragma unroll
+	for (int m = 32; m > 0; m >>= 1) sum += (uint32_t)__shfl_xor((int)sum, m, 64);
+	if ((threadIdx.x & 63) == 0) tile[t] = sum;
+}
+
+// k_sb_outside_scan on 64-bit sums (the orbit sizes of radius 10 add up to 7.5e9): the exclusive prefix in place by ONE workgroup,
+// tile[tiles] = the sum of all
+__global__ __launch_bounds__(SB_SCAN_THREADS)
+void k_sb_orbit_scan(unsigned long long *tile, uint32_t tiles)
+{
+	__shared__ unsigned long long s_sum[SB_SCAN_THREADS];
+	const uint32_t t = threadIdx.x;
+	const uint32_t per = (tiles + SB_SCAN_THREADS - 1) / SB_SCAN_THREADS;    // (at most 2^22 tiles: t * per stays far below 2^32)
+	const uint32_t lo = min(t * per, tiles), hi = min(lo + per, tiles);
+	unsigned long long sum = 0;
+	for (uint32_t i = lo; i < hi; i++) sum += tile[i];
+	s_sum[t] = sum;
+	__syncthreads();
+	for (uint32_t off = 1; off < SB_SCAN_THREADS; off <<= 1) {
+		const unsigned long long v = t >= off ? s_sum[t - off] : 0ull;
+		__syncthreads();
+		s_sum[t] += v;
+		__syncthreads();
+	}
+	unsigned long long run = s_sum[t] - sum;
+	for (uint32_t i = lo; i < hi; i++) {
+		const unsigned long long c = tile[i];
+		tile[i] = run;
+		run += c;
+	}
+	if (t == SB_SCAN_THREADS - 1) tile[tiles] = s_sum[t];
+}
+
+// base[l], l = 0 .. radius + 1, a thread per level boundary: the prefix of the boundary's tile and the bytes in front of it
+__global__ __launch_bounds__(64)
+void k_sb_orbit_base(SymBallView b, const uint8_t *orbit, const unsigned long long *tile, unsigned long long *base)
+{
+	const int l = threadIdx.x;
+	if (l > b.radius + 1) return;
+	const uint32_t p = (uint32_t)b.lstart[l] - 1u;                       // positions below level l (level radius + 1 starts behind the last node)
+	unsigned long long sum = tile[p >> 8];                               // (p = len on a tile boundary reads tile[tiles])
+	for (uint32_t q = p & ~255u; q < p; q++) sum += orbit[q];
+	base[l] = sum;
+}
+
+// an inclusive prefix sum over the 64 lanes.  ALL 64 lanes call it.
+__device__ __forceinline__ uint32_t wave_inclusive_sum(uint32_t v, int lane)
+{
+	#pragma unroll
+	for (int m = 1; m < 64; m <<= 1) {
+		const uint32_t up = (uint32_t)__shfl_up((int)v, m, 64);
+		if (lane >= m) v += up;
+	}
+	return v;
+}
+
+// Row i of `out` = the state of (depth[i], rank[i]): the k-th distinct conjugate, in ascending symmetry order, of the node of
+// level depth[i] whose cumulative orbit range holds the rank.  Waves stride over the samples; everything up to the conjugates is
+// the same in every lane (the wave index goes through readfirstlane, so the sample, its tile and its node are wave-uniform).
+//   G = base[depth] + rank; the tile that holds G by bisection over the tiles of the level; the tile's 256 orbit bytes a dword per
+//   lane, their sums scanned across the wave: the lane, then the byte, whose range holds G - tile[t] -> node j, k = what is left;
+//   lane s < 48 conjugates the representative by s and is FIRST when no lower lane holds the same state; the first lanes are the
+//   orbit (orbit[j] of them, anything else is RK_ESTATE), and the one with k first lanes below it writes its conjugate.
+// A depth outside 0..radius or a rank outside the level sets RK_EINVAL and the row is zeroed, as is a row of a broken index.
+// Nothing is written but `out` and the error word.
+__global__ __launch_bounds__(256)
+void k_sb_state_at(SymBallView b, SymIndex ix, const int32_t *depth, const long long *rank, size_t n, uint32_t *out, int32_t *error)
+{
+	__shared__ uint32_t s_sym[SYM_LDS_DWORDS];
+	const SymProbe sp = sym_probe(s_sym, 256);
+	const int lane = sp.lane;
+	for (size_t i = (size_t)blockIdx.x * 4 + (size_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); i < n; i += (size_t)gridDim.x * 4) {
+		const int d = depth[i];
+		const long long r = rank[i];
+		int bad = RK_OK;
+		if (d < 0 || d > b.radius || r < 0 || (unsigned long long)r >= ix.base[d + 1] - ix.base[d]) bad = RK_EINVAL;
+		uint32_t y[5] = {0u, 0u, 0u, 0u, 0u};
+		bool writer = false;
+		if (!bad) {
+			const unsigned long long G = ix.base[d] + (unsigned long long)r;
+			uint32_t lo = ((uint32_t)b.lstart[d] - 1u) >> 8, hi = min(((uint32_t)b.lstart[d + 1] - 2u) >> 8, ix.tiles - 1u);
+			while (lo < hi) {                                                // the last tile of the level whose prefix is <= G
+				const uint32_t mid = (lo + hi + 1u) >> 1;
+				if (ix.tile[mid] <= G) lo = mid; else hi = mid - 1u;
+			}
+			const unsigned long long left = G - ix.tile[lo];                 // (>= 0: the level's first tile starts at or below base[d])
+			const uint32_t w = ix.orbit[(size_t)lo * 64 + lane];
+			const uint32_t mine = bytes_sum(w), incl = wave_inclusive_sum(mine, lane), excl = incl - mine;
+			const unsigned long long holds = __ballot((unsigned long long)excl <= left && left < (unsigned long long)incl);
+			if (holds == 0ull) {
+				bad = RK_ESTATE;                                             // the tile's prefix and its bytes disagree
+			} else {
+				const int src = __builtin_amdgcn_readfirstlane(__ffsll((long long)holds) - 1);
+				uint32_t bytes = (uint32_t)__builtin_amdgcn_readlane((int)w, src);
+				uint32_t k = (uint32_t)left - (uint32_t)__builtin_amdgcn_readlane((int)excl, src);
+				uint32_t j = lo * 256u + (uint32_t)src * 4u + 1u;
+				while (k >= (bytes & 0xFFu)) {                               // (ends inside the dword: k < the sum of its bytes)
+					k -= bytes & 0xFFu;
+					bytes >>= 8;
+					j++;
+				}
+				const uint32_t size = bytes & 0xFFu;
+				if (j > ix.len) {
+					bad = RK_ESTATE;
+				} else {
+					uint32_t x[5];
+					load5(b.states + (size_t)j * 5, x);
+					sym_conjugate(sp.s_sym, sp.L, x, y);
+					bool first = lane < N_SYM;
+					for (int t = 0; t < N_SYM - 1; t++) {
+						bool same = true;
+						#pragma unroll
+						for (int q = 0; q < 5; q++) same = same && (uint32_t)__builtin_amdgcn_readlane((int)y[q], t) == y[q];
+						if (same && t < lane) first = false;
+					}
+					const unsigned long long firsts = __ballot(first);
+					if ((uint32_t)__popcll(firsts) != size) bad = RK_ESTATE;
+					else writer = first && (uint32_t)__popcll(firsts & ((1ull << lane) - 1ull)) == k;
+				}
+			}
+		}
+		if (bad) {
+			if (lane == 0) *error = bad;
+			if (lane < 5) out[i * 5 + lane] = 0u;
+		} else if (writer) {
+			#pragma unroll
+			for (int q = 0; q < 5; q++) out[i * 5 + q] = y[q];
+		}
+	}
+}
+
+// The exact depth of every state within radius + 1 of solved and of its twelve children, a wave per state: the level of the
+// state and of each child in action order, then the parity of quarter turns -- a turn changes the distance by exactly one.
+//   own level o in 0..R: a child the ball holds has its level, any other lies at o + 1 (with o < R the ball is broken: RK_ESTATE)
+//   own state outside, a child inside: that child lies at R (anything else: RK_ESTATE), the state at R + 1, a child outside at R + 2
+//   own state and all children outside: -1 for all thirteen
+// Lane a < 12 keeps and writes child a.
+__global__ __launch_bounds__(256)
+void k_sb_child_depths(SymBallView b, const uint32_t *states, size_t n, int8_t *depth, int8_t *child, int32_t *error)
+{
+	__shared__ uint32_t s_sym[SYM_LDS_DWORDS];
+	__shared__ u32x4 s_act[36];
+	const SymProbe sp = sym_probe(s_sym, 256, s_act);
+	const int lane = sp.lane, R = b.radius;
+	for (size_t q = (size_t)blockIdx.x * 4 + (size_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); q < n; q += (size_t)gridDim.x * 4) {
+		uint32_t x[5];
+		load5(states + q * 5, x);
+		const int own = sb_level(b, sp, x);
+		int mine = -1;
+		for (int a = 0; a < N_ACTIONS; a++) {
+			uint32_t y[5], tab[12];
+			#pragma unroll
+			for (int j = 0; j < 5; j++) y[j] = x[j];
+			load_action_table(sp.s_act, (uint32_t)a, tab);
+			move5(y, tab);
+			const int lvl = sb_level(b, sp, y);
+			if (lane == a) mine = lvl;
+		}
+		const bool inside = lane < N_ACTIONS && mine >= 0;
+		const bool any = __ballot(inside) != 0ull;
+		int d = own, c = mine;
+		bool broken = false;
+		if (own >= 0) {
+			if (!inside) { c = own + 1; broken = own < R; }
+		} else if (any) {
+			d = R + 1;
+			if (inside) broken = mine != R; else c = R + 2;
+		}
+		if (lane < N_ACTIONS) {
+			child[q * N_ACTIONS + lane] = (int8_t)c;
+			if (broken) *error = RK_ESTATE;
+		}
+		if (lane == 0) depth[q] = (int8_t)d;
+	}
 }
 
 // ---- shortening action queues against the symmetry ball (rk_sshorten; the DP and everything ball-independent: rk_shorten_dev.h) ----
@@ -627,6 +851,10 @@ struct rk_symball : KeptBall {
 	SymBallDev d{};
 	SymBallView view{};
 	long long cover[SB_MAX_RADIUS + 1] = {};
+	// the orbit index of rk_symball_state_at: made at its first call, in the ball's pool (so it goes with the ball)
+	SymIndex index{};
+	uint8_t *orbit = nullptr; unsigned long long *tile = nullptr;
+	long long index_builds = 0, index_bytes = 0;
 };
 
 // What an engine of another translation unit that ends at a built symmetry ball takes and gives back (rk_beam.hip; declared in
@@ -722,6 +950,68 @@ int launch_deepen(const char *who, rk_symball *ball, DeepenJob job, uint32_t *be
 	const size_t items = job.n * (size_t)deepen_groups(job.extra, job.word_first, job.word_count);
 	hipLaunchKernelGGL(k_sd_probe, dim3(sym_grid(items)), dim3(256), 0, st, ball->view, job, best);
 	RK_HIP(hipGetLastError());
+	return RK_OK;
+}
+
+// The orbit index of a built ball, made once: the orbit bytes, the tiles' counts, their prefix and the level bases -- four launches
+// and one read -- then the check that every level's orbit sizes add up to what the ball's own build reported.  Synchronises when
+// it builds; a ball that has its index returns at once.  Whatever fails leaves the ball without an index.
+int ensure_index(const char *who, rk_symball *h, hipStream_t st)
+{
+	if (h->orbit != nullptr) return RK_OK;
+	const uint32_t len = (uint32_t)h->size, tiles = blocks(len, 256);
+	const int levels = h->d.radius + 2;
+	uint8_t *orbit = nullptr;
+	unsigned long long *tile = nullptr, *base = nullptr;
+	int32_t *error = nullptr;
+	const auto drop = [&] {
+		for (void *p : {(void *)orbit, (void *)tile, (void *)base, (void *)error}) h->pool.release(p);
+	};
+	int e = h->pool.alloc(&orbit, (size_t)tiles * 256);
+	if (!e) e = h->pool.alloc(&tile, (size_t)tiles + 1);
+	if (!e) e = h->pool.alloc(&base, (size_t)SB_MAX_RADIUS + 2);
+	if (!e) e = h->pool.alloc(&error, 1);
+	if (e) {
+		(void)hipGetLastError();
+		drop();
+		return fail(RK_ECAPACITY, "%s: no device memory for the orbit index of %u orbits", who, len);
+	}
+	unsigned long long sums[SB_MAX_RADIUS + 2] = {};
+	int32_t err = 0;
+	const hipError_t he = [&]() -> hipError_t {
+		RK_FILL(hipMemsetAsync(orbit, 0, (size_t)tiles * 256, st));
+		RK_FILL(hipMemsetAsync(error, 0, sizeof(int32_t), st));
+		hipLaunchKernelGGL(k_sb_orbit, dim3(sym_grid(len)), dim3(256), 0, st, h->view, len, orbit, error);
+		hipLaunchKernelGGL(k_sb_orbit_count, dim3(blocks(tiles, 4)), dim3(256), 0, st, reinterpret_cast<const uint32_t *>(orbit), tiles, tile);
+		hipLaunchKernelGGL(k_sb_orbit_scan, dim3(1), dim3(SB_SCAN_THREADS), 0, st, tile, tiles);
+		hipLaunchKernelGGL(k_sb_orbit_base, dim3(1), dim3(64), 0, st, h->view, orbit, tile, base);
+		RK_FILL(hipGetLastError());
+		RK_FILL(hipMemcpyAsync(sums, base, (size_t)levels * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+		RK_FILL(hipMemcpyAsync(&err, error, sizeof err, hipMemcpyDeviceToHost, st));
+		return hipStreamSynchronize(st);
+	}();
+	if (he != hipSuccess) {
+		(void)hipStreamSynchronize(st);
+		drop();
+		return fail(RK_EHIP, "%s: the orbit index: %s", who, hipGetErrorString(he));
+	}
+	int wrong = -1;
+	for (int l = h->d.radius; l >= 0; l--)
+		if ((long long)(sums[l + 1] - sums[l]) != h->cover[l]) wrong = l;
+	if (err || sums[0] != 0ull || wrong >= 0) {
+		drop();
+		if (err) return fail(RK_ESTATE, "%s: a node of the ball is not the canonical form of its orbit", who);
+		return fail(RK_ESTATE, "%s: the orbit sizes of level %d add up to %llu in the index, the build reported %lld", who, std::max(wrong, 0),
+		            sums[std::max(wrong, 0) + 1] - sums[std::max(wrong, 0)], h->cover[std::max(wrong, 0)]);
+	}
+	h->pool.release(base);
+	h->pool.release(error);
+	h->orbit = orbit;
+	h->tile = tile;
+	h->index = SymIndex{reinterpret_cast<const uint32_t *>(orbit), tile, tiles, len, {}};
+	for (int l = 0; l < levels; l++) h->index.base[l] = sums[l];
+	h->index_builds += 1;
+	h->index_bytes = (long long)tiles * 256 + (long long)(tiles + 1) * (long long)sizeof(unsigned long long);
 	return RK_OK;
 }
 
@@ -901,6 +1191,52 @@ int rk_symball_child_values(rk_symball_t *h, const int8_t *d_states, size_t m12,
 	hipLaunchKernelGGL(k_sb_outside_count, dim3(tiles), dim3(ASCAN), 0, st, d_depth, m12, tile);
 	hipLaunchKernelGGL(k_sb_outside_scan, dim3(1), dim3(SB_SCAN_THREADS), 0, st, tile, (int)tiles, d_count);
 	hipLaunchKernelGGL(k_sb_outside_write, dim3(tiles), dim3(ASCAN), 0, st, d_depth, states, m12, tile, d_rows, reinterpret_cast<uint32_t *>(d_outside));
+	RK_HIP(hipGetLastError());
+	return RK_OK;
+}
+
+int rk_symball_state_at(rk_symball_t *h, const int32_t *d_depth, const int64_t *d_rank, size_t n, int8_t *d_states, int32_t *d_error, void *stream)
+{
+	const char *who = "rk_symball_state_at";
+	if (!h) return fail(RK_EINVAL, "%s: null ball", who);
+	if (!h->built) return fail(RK_ESTATE, "%s: build the ball first", who);
+	if (n > (size_t)INT32_MAX) return fail(RK_EINVAL, "%s: %zu samples in one launch", who, n);
+	if (!d_error || (n != 0 && (!d_depth || !d_rank || !d_states))) return fail(RK_EINVAL, "%s: null pointer", who);
+	if ((((uintptr_t)d_depth | (uintptr_t)d_states | (uintptr_t)d_error) & 3u) || ((uintptr_t)d_rank & 7u))
+		return fail(RK_EINVAL, "%s: device pointers must be 4-byte aligned, the ranks 8-byte", who);
+	hipStream_t st = (hipStream_t)stream;
+	if (int e = ensure_index(who, h, st)) return e;
+	RK_HIP(hipMemsetAsync(d_error, 0, sizeof(int32_t), st));
+	if (n == 0) return RK_OK;
+	hipLaunchKernelGGL(k_sb_state_at, dim3(sym_grid(n)), dim3(256), 0, st, h->view, h->index, d_depth, reinterpret_cast<const long long *>(d_rank), n,
+	                   reinterpret_cast<uint32_t *>(d_states), d_error);
+	RK_HIP(hipGetLastError());
+	return RK_OK;
+}
+
+int rk_symball_index_status(rk_symball_t *h, long long *h_status)
+{
+	if (!h || !h_status) return fail(RK_EINVAL, "rk_symball_index_status: null argument");
+	const bool made = h->orbit != nullptr;
+	h_status[0] = h->index_builds;
+	h_status[1] = made ? h->index_bytes : 0;
+	h_status[2] = made ? (long long)h->index.tiles : 0;
+	h_status[3] = 0;
+	for (int l = 0; l < SB_MAX_RADIUS + 2; l++) h_status[4 + l] = made && l <= h->d.radius + 1 ? (long long)h->index.base[l] : 0;
+	return RK_OK;
+}
+
+int rk_symball_child_depths(rk_symball_t *h, const int8_t *d_states, size_t n, int8_t *d_depth, int8_t *d_child, int32_t *d_error, void *stream)
+{
+	const char *who = "rk_symball_child_depths";
+	if (int e = KeptBall::check_queries(who, "states", h, d_states, n, d_depth)) return e;
+	if (n != 0 && !d_child) return fail(RK_EINVAL, "%s: null pointer", who);
+	if (!d_error || ((uintptr_t)d_error & 3u)) return fail(RK_EINVAL, "%s: the error word must be a 4-byte aligned device pointer", who);
+	hipStream_t st = (hipStream_t)stream;
+	RK_HIP(hipMemsetAsync(d_error, 0, sizeof(int32_t), st));
+	if (n == 0) return RK_OK;
+	hipLaunchKernelGGL(k_sb_child_depths, dim3(sym_grid(n)), dim3(256), 0, st, h->view, reinterpret_cast<const uint32_t *>(d_states), n, d_depth, d_child,
+	                   d_error);
 	RK_HIP(hipGetLastError());
 	return RK_OK;
 }

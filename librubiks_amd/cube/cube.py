@@ -452,6 +452,59 @@ class device:
 		return values, depths, rows[:k], outside[:k]
 
 	@staticmethod
+	def _sym_ball(ball):
+		from librubiks_amd.solving.agents import DeviceSymBall
+		if not isinstance(ball, DeviceSymBall):
+			raise TypeError(f"ball must be a DeviceSymBall, not {type(ball).__name__}")
+		_ffi.require_gpu()
+		return ball.build()
+
+	@staticmethod
+	def ball_state_at(ball, depths: torch.Tensor, ranks: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
+		"""The states of (depths[i], ranks[i]) of a symmetry ball (engine rk_symball_state_at; the map: `DeviceSymBall.state_at`):
+		depths int32 (n,), ranks int64 (n,) -> int8 (n, 20), all on the device, 20-byte states whatever the representation.  A depth
+		outside 0..radius or a rank outside [0, states_covered[depth]) raises ValueError AFTER the launch (its row is zeros): reading
+		the error word is the call's one host read.  The ball's first call makes its orbit index."""
+		ball = device._sym_ball(ball)
+		_check_dev(depths, torch.int32, "depths")
+		_check_dev(ranks, torch.int64, "ranks")
+		n = ranks.numel()
+		if depths.numel() != n:
+			raise ValueError(f"{depths.numel()} depths for {n} ranks")
+		if out is None:
+			out = torch.empty((n, 20), dtype=torch.int8, device=gpu)
+		else:
+			_check_dev(out, torch.int8, "out")
+			if out.numel() != 20 * n:
+				raise ValueError(f"out must have shape ({n}, 20), got {tuple(out.shape)}")
+		err = torch.empty(1, dtype=torch.int32, device=gpu)
+		_ffi.check(_ffi.lib().rk_symball_state_at(ball._h, depths.data_ptr(), ranks.data_ptr(), n, out.data_ptr(), err.data_ptr(), _ffi.stream_ptr()))
+		code = int(err.item())
+		if code == -1:
+			raise ValueError("a depth outside 0..radius or a rank outside [0, states_covered[depth]): those rows are zeros")
+		if code:
+			raise _ffi.RubiksHipError(f"rk_symball_state_at reported error {code}: the orbit index contradicts the ball")
+		return out
+
+	@staticmethod
+	def ball_child_depths(ball, states: torch.Tensor):
+		"""(depth int8 (n,), children int8 (n, 12)) on the device: the exact distance to solved of every 20-byte state of `states`
+		int8 (n, 20) and of its twelve children in action order, -1 where a state lies further than radius + 1 from solved (engine
+		rk_symball_child_depths; the rules: `DeviceSymBall.child_depths`).  Reading the error word is the call's one host read."""
+		ball = device._sym_ball(ball)
+		_check_dev(states, torch.int8, "states")
+		n = len(states)
+		if states.numel() != 20 * n:
+			raise ValueError(f"states must have shape (n, 20), got {tuple(states.shape)}")
+		depth = torch.empty(n, dtype=torch.int8, device=gpu)
+		children = torch.empty((n, 12), dtype=torch.int8, device=gpu)
+		err = torch.empty(1, dtype=torch.int32, device=gpu)
+		_ffi.check(_ffi.lib().rk_symball_child_depths(ball._h, states.data_ptr(), n, depth.data_ptr(), children.data_ptr(), err.data_ptr(), _ffi.stream_ptr()))
+		if int(err.item()):
+			raise _ffi.RubiksHipError(f"rk_symball_child_depths reported error {int(err.item())}: the levels around a state contradict the parity of quarter turns")
+		return depth, children
+
+	@staticmethod
 	def as_oh(states: torch.Tensor, out: torch.Tensor = None, dtype: torch.dtype = torch.float32) -> torch.Tensor:
 		"""One-hot (n, 480 | 288) of `dtype` (float32, float16 or bfloat16)   (cube.py:265-277, 363-369)."""
 		_ffi.require_gpu()

@@ -753,6 +753,11 @@ class DeviceSymBall(_KeptBall):
 	a build that does not fit stops cleanly with a RubiksHipError (RK_ECAPACITY).  `states_covered[l]` is the sum of the orbit
 	sizes of level l: the number of states of the plain ball's level (checked by the engine for levels 0..8).  States are in the
 	representation cube.get_is2024() names when a method is called.
+
+	The ball also hands out states: `state_at(depths, ranks)` unranks it -- rank r of level d is one of the `states_covered[d]`
+	states at distance exactly d, each exactly once --, `sample` draws uniform ranks, and `child_depths` gives the exact depth of a
+	state and of its twelve children within radius + 1.  The first `state_at` adds an orbit index of one byte per orbit and eight
+	bytes per 256 orbits to the ball's memory (`index_bytes`, shown by `str(ball)` once it exists).
 	"""
 	LEVELS = DeviceGoalBall.LEVELS                                  # states at distance 0 .. 8: what states_covered is checked against
 	MAX_RADIUS = 10
@@ -868,6 +873,121 @@ class DeviceSymBall(_KeptBall):
 			todo = todo[rank == 0xFFFFFFFF]
 		return lengths, actions
 
+	def _depths_ranks(self, depths, ranks):
+		"""(depths int64 (n,), ranks int64 (n,)) of a `state_at` call, checked on the host: ValueError for anything but integers,
+		for lengths that differ, a depth outside 0..radius or a rank outside [0, states_covered[depth])."""
+		r = np.asarray(ranks)
+		d = np.asarray(depths)
+		for what, a in (("depths", d), ("ranks", r)):
+			if a.dtype == bool or not (np.issubdtype(a.dtype, np.integer) or a.size == 0):
+				raise ValueError(f"{what} must be integers, got dtype {a.dtype}")
+		if r.dtype == np.uint64 and r.size and int(r.max()) > _ffi.INT64_MAX:
+			raise ValueError("a rank above 2^63 - 1")
+		r = r.astype(np.int64).reshape(-1)
+		if d.ndim == 0:
+			d = np.full(len(r), int(d), np.int64)
+		d = d.astype(np.int64).reshape(-1)
+		if len(d) != len(r):
+			raise ValueError(f"{len(d)} depths for {len(r)} ranks")
+		if len(r):
+			if d.min() < 0 or d.max() > self.radius:
+				raise ValueError(f"a depth outside 0..{self.radius}")
+			if r.min() < 0 or (r >= self.states_covered[d]).any():
+				raise ValueError("a rank outside [0, states_covered[depth])")
+		return d, r
+
+	def state_at(self, depths, ranks) -> np.ndarray:
+		"""
+		The states of (depths[i], ranks[i]), int8 (n, 20) or (n, 6, 8, 6) in the representation cube.get_is2024() names (engine
+		rk_symball_state_at, one launch, a wave per sample).  THE STATE OF (d, r) is the k-th distinct conjugate, in ascending symmetry
+		order, of the node j of level d whose cumulative orbit range holds r: the nodes of level d in index order, each counting
+		for the size of its orbit, j the one whose range holds r and k = r minus the sizes in front of j.  For every d this maps
+		[0, states_covered[d]) one to one onto the states at distance exactly d from solved, so a uniform rank is a uniform state
+		at that distance; the map does not depend on `pops`.
+
+		`depths` is an int (all ranks at that depth) or an array as long as `ranks`.  ValueError, before anything is launched, for a
+		depth outside 0..radius, a rank outside [0, states_covered[depth]) or lengths that differ.  The first call makes the ball's
+		orbit index on the device -- a byte per orbit and a 64-bit prefix per 256 orbits (`index_bytes`; 161 MB at radius 10 beside
+		the ball's 5.3 GB) -- which is kept until the ball goes; a ball that never samples holds none.
+		"""
+		self.build()
+		d, r = self._depths_ranks(depths, ranks)
+		n = len(r)
+		is2024 = cube.get_is2024()
+		rows = np.zeros((n + 1, 20), np.int8)
+		if n:
+			out = cube.device.ball_state_at(self, torch.from_numpy(d.astype(np.int32)).to(gpu), torch.from_numpy(r).to(gpu))
+			rows[1:] = out.cpu().numpy()
+		return _states_out(is2024, rows, n)[1:]
+
+	def sample(self, n: int, depth=None, rng=None):
+		"""
+		(states, depths int64 (n,)): n states drawn uniformly, by `state_at` of uniform ranks.  `rng` is a numpy.random.Generator
+		(None: np.random.default_rng()), and it is asked exactly ONCE, so a generator seeded alike reproduces the states:
+		  depth an int or an (n,) array   ranks = rng.integers(0, self.states_covered[depths], dtype=np.int64) with depths the (n,)
+		                                  array (an int repeated n times): state i is uniform among the states at distance depths[i];
+		  depth None                      g = rng.integers(0, self.states_covered.sum(), n, dtype=np.int64): uniform over the whole
+		                                  ball; with c = np.cumsum(self.states_covered), depths = np.searchsorted(c, g, side="right")
+		                                  and ranks = g - (c - self.states_covered)[depths].
+		"""
+		n = eng.int_in("n", n, 0)
+		if rng is None:
+			rng = np.random.default_rng()
+		elif not isinstance(rng, np.random.Generator):
+			raise TypeError(f"rng must be a numpy.random.Generator or None, not {type(rng).__name__}")
+		covered = self.states_covered
+		if depth is None:
+			g = rng.integers(0, int(covered.sum()), n, dtype=np.int64)
+			c = np.cumsum(covered)
+			depths = np.searchsorted(c, g, side="right").astype(np.int64)
+			ranks = g - (c - covered)[depths]
+		else:
+			depths = np.asarray(depth)
+			if depths.dtype == bool or not np.issubdtype(depths.dtype, np.integer):
+				raise ValueError(f"depth must be an integer, an integer array or None, got dtype {depths.dtype}")
+			depths = np.full(n, int(depths), np.int64) if depths.ndim == 0 else depths.astype(np.int64).reshape(-1)
+			if len(depths) != n:
+				raise ValueError(f"{len(depths)} depths for n = {n}")
+			if n and (depths.min() < 0 or depths.max() > self.radius):
+				raise ValueError(f"a depth outside 0..{self.radius}")
+			ranks = rng.integers(0, covered[depths], dtype=np.int64)
+		return self.state_at(depths, ranks), depths
+
+	def child_depths(self, states):
+		"""(depth int64 (n,), children int64 (n, 12)): the exact distance to solved of every state and of its twelve children in action
+		order (engine rk_symball_child_depths, one launch).  A quarter turn changes the distance by exactly one, so the answers are
+		exact for every state within radius + 1 of solved -- radius + 1 for a state outside the ball with a child inside, radius + 2
+		for such a state's other children --; a state further out gets -1 thirteen times."""
+		self.build()
+		rows = self._rows(states)
+		n = len(rows)
+		if n == 0:
+			return np.zeros(0, np.int64), np.zeros((0, 12), np.int64)
+		depth, children = cube.device.ball_child_depths(self, torch.from_numpy(rows).to(gpu))
+		return depth.cpu().numpy().astype(np.int64), children.cpu().numpy().astype(np.int64)
+
+	def _index_status(self):
+		status = (C.c_longlong * 16)()
+		_ffi.check(_ffi.lib().rk_symball_index_status(self.build()._h, status))
+		return status
+
+	@property
+	def index_builds(self) -> int:
+		"""How often this ball's orbit index was made: 0 before the first `state_at`, 1 from then on."""
+		return int(self._index_status()[0])
+
+	@property
+	def index_bytes(self) -> int:
+		"""The device memory of the orbit index: 0 before the first `state_at`."""
+		return int(self._index_status()[1])
+
+	@property
+	def index_levels(self) -> np.ndarray:
+		"""int64 (radius + 1,): the orbit sizes of every level as the orbit index adds them up (= `states_covered`), None before the
+		first `state_at`."""
+		status = self._index_status()
+		return np.diff(np.array(status[4:4 + self.radius + 2], np.int64)) if status[0] else None
+
 	def arrays(self):
 		"""The representatives of nodes 1 .. len(ball) in index order."""
 		is2024 = cube.get_is2024()
@@ -879,7 +999,8 @@ class DeviceSymBall(_KeptBall):
 		return self._cache[is2024]
 
 	def __str__(self):
-		return f"Symmetry-reduced goal ball (device, radius={self.radius})"
+		index = f", orbit index {self.index_bytes / 1e6:.1f} MB" if self.built and self.index_builds else ""
+		return f"Symmetry-reduced goal ball (device, radius={self.radius}{index})"
 
 
 class _BallSearch(_PoolSearch):
