@@ -208,6 +208,23 @@ int rk_ohl_forward(rk_ohl_t *h, const int8_t *d_states, void *d_out, int out_dty
  * beta - mean * scale) that follow the layer, computed in float32 on the accumulators.  d_scale / d_shift: H float32
  * values on the device, copied; both null = no affine part.  act RK_OHL_ACT_NONE and null pointers restore the plain layer. */
 int rk_ohl_set_epilogue(rk_ohl_t *h, int act, float alpha, const float *d_scale, const float *d_shift, void *stream);
+/* Training (train.py:165-179 with the layer reading states): the handle follows live parameters and gives their gradient.
+ * rk_ohl_set_weights runs rk_ohl_create's layout preparation again, from d_weight (H, 480) / d_bias (H or NULL) of w_dtype, into the
+ * buffers the handle already owns, in stream order: no allocation, no synchronisation (the tensors must stay alive until the stream
+ * has got there), a set epilogue stays set.  A following rk_ohl_forward on any route gives, bit for bit, what a handle created on
+ * those weights gives.
+ * rk_ohl_backward: d_states (n, 20) int8, d_dy (n, H) float32 row-major, 16-byte aligned ->
+ *     d_dw[h, 24 i + v] = sum over the rows r with code(r, i) = v of d_dy[r, h]         (H, 480) float32, nn.Linear.weight's layout
+ *     d_db[h]           = sum over all rows of d_dy[r, h]                               H float32, or NULL
+ * with the forward's codes (the byte read as unsigned, anything >= 24 counts as 23).  Both outputs are OVERWRITTEN: a column no row
+ * selects is +0.0 whatever the buffer held, n = 0 writes zeros.  Plain float32 adds in an order that is a function of (n, H) alone
+ * -- rows ascending inside a workgroup's row range (rk_ohl_backward_rows(n, H) rows each), the ranges ascending, db as the sum of cubie
+ * 0's 24 bins ascending -- and no atomics: the same inputs give the same bits on every call and on every handle.  Arguments are checked
+ * before any launch (RK_EINVAL: a null handle, states, dY or dW; d_dy or d_dw off 16-byte alignment).  The partial sums live in scratch
+ * the handle owns, allocated at the first call that needs that much; later calls of the same or a smaller (n, H) need allocate nothing. */
+int rk_ohl_set_weights(rk_ohl_t *h, const void *d_weight, int w_dtype, const void *d_bias, void *stream);
+int rk_ohl_backward(rk_ohl_t *h, const int8_t *d_states, const float *d_dy, size_t n, float *d_dw, float *d_db, void *stream);
+size_t rk_ohl_backward_rows(size_t n, int H);
 
 /* The net's other end (model.py:124-125,128-129: policy_net / value_net end in activation -> Linear(K, 12) / Linear(K, 1), and the
  * engines read those 12 + 1 numbers per row): y = act(x) @ W^T + b in ONE pass over x for a last layer of M <= 16 outputs, instead of an

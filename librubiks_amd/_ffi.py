@@ -59,6 +59,9 @@ SIGNATURES = {
 	"rk_ohl_destroy": (_i, [_vp]),
 	"rk_ohl_forward": (_i, [_vp, _vp, _vp, _i, _sz, _i, _vp]),
 	"rk_ohl_set_epilogue": (_i, [_vp, _i, C.c_float, _vp, _vp, _vp]),
+	"rk_ohl_set_weights": (_i, [_vp, _vp, _i, _vp, _vp]),
+	"rk_ohl_backward": (_i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+	"rk_ohl_backward_rows": (_sz, [_sz, _i]),
 	"rk_tail_linear": (_i, [_vp, _sz, _i, _sz, _vp, _vp, _i, _i, C.c_float, _vp, _vp]),
 	"rk_as_correct686": (_i, [_vp, _vp, _sz, _vp]),
 	"rk_oh686_from2024": (_i, [_vp, _vp, _i, _sz, _vp]),

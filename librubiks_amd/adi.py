@@ -20,8 +20,10 @@ from librubiks_amd import gpu, no_grad, _ffi, cube
 
 @no_grad
 def adi_traindata(net, rollout_games: int, rollout_depth: int, alpha: float, reward_method: str = "lapanfix",
-                  ff_batches: int = 1, fused_first_layer=False, ball=None):
+                  ff_batches: int = 1, fused_first_layer=False, ball=None, return_states: bool = False):
 	"""
+	`return_states`: the first value is the (games * depth, 20) int8 device tensor of the scrambled states themselves instead of their
+	one-hot rows (for `oh_linear.train_on_states`; 20-byte representation only).  Same draws, same other three values.
 	`ball`: a `DeviceSymBall(R)` (built at first use), or None for the reference's targets.  With a ball, a child whose orbit the ball
 	holds at depth c gets, as its value BEFORE the reward is added, the exact V*(0) = 0, V*(c) = g - (c - 1) for 1 <= c <= R, where g
 	is the method's goal reward (0 for reward0, else 1): the fixed point of V(s) = max_a [r(s.a) + V(s.a)] with V(solved) = 0.
@@ -40,6 +42,8 @@ def adi_traindata(net, rollout_games: int, rollout_depth: int, alpha: float, rew
 	is2024 = cube.get_is2024()             # 6x8x6: the same walks in 20-byte form, the net's rows from the fused converter + encoder
 	if fused_first_layer and not is2024:
 		raise ValueError("fused_first_layer reads 20-byte states into a Linear(480, H); a 6x8x6 net has 288 inputs")
+	if return_states and not is2024:
+		raise ValueError("return_states hands out 20-byte states for a Linear(480, H); a 6x8x6 net has 288 inputs")
 	net.eval()
 	with_solved = reward_method == "lapanfix"
 	# scrambling: draws as cube.sequence_scrambler (cube.py:226-227), walks on the device           train.py:277
@@ -49,7 +53,7 @@ def adi_traindata(net, rollout_games: int, rollout_depth: int, alpha: float, rew
 	# walks, goal test of the scrambled states, fan-out and its goal test: ONE launch              train.py:277, :281, :285, :292
 	states, solved_scrambled, substates, solved_sub = cube.device.rollout_fanout(acts, with_solved)  # (games*depth, 20), ..., (12*games*depth, 20), ...
 	n = len(states)
-	oh_states = cube.device.as_oh(states) if is2024 else cube.device.to686(states, torch.float32)
+	oh_states = states if return_states else cube.device.as_oh(states) if is2024 else cube.device.to686(states, torch.float32)
 	solved_scrambled, solved_sub = solved_scrambled.bool(), solved_sub.bool()
 	rewards = torch.where(solved_sub, torch.tensor(0.0 if reward_method == "reward0" else 1.0, device=gpu),
 	                      torch.tensor(-1.0, device=gpu))                                         # train.py:294-296
@@ -101,7 +105,7 @@ def adi_traindata(net, rollout_games: int, rollout_depth: int, alpha: float, rew
 	return oh_states, policy_targets.cpu(), value_targets.cpu(), torch.from_numpy(loss_weights).float()
 
 
-def ball_traindata(ball, n: int, depths=None, rng=None, reward_method: str = "lapanfix"):
+def ball_traindata(ball, n: int, depths=None, rng=None, reward_method: str = "lapanfix", return_states: bool = False):
 	"""
 	Supervised ADI data from a `DeviceSymBall(R)` alone, no net involved: n states drawn by `ball.sample(n, depths, rng)` -- uniform
 	at the given depth(s), or uniform over the whole ball for None; the draws are `sample`'s, so a seeded numpy.random.Generator
@@ -110,7 +114,8 @@ def ball_traindata(ball, n: int, depths=None, rng=None, reward_method: str = "la
 	  value_targets   float32: V*(0) = 0, V*(d) = g - (d - 1) for d >= 1, g = 0 for reward0 and else 1 (`adi_traindata(ball=)`'s convention)
 	  policy_targets  int64: the lowest action whose child lies one level nearer (`solve`'s rule, and `argmax`'s on ties); 0 at d = 0
 	  loss_weights    float32: all 1
-	A row costs one `state_at` sample and thirteen ball probes.
+	A row costs one `state_at` sample and thirteen ball probes.  `return_states`: the (n, 20) int8 device tensor of the states instead of
+	their one-hot rows, as in `adi_traindata` (20-byte representation only).
 	"""
 	assert reward_method in ("paper", "lapanfix", "schultzfix", "reward0")
 	from librubiks_amd.solving.agents import DeviceSymBall
@@ -118,13 +123,15 @@ def ball_traindata(ball, n: int, depths=None, rng=None, reward_method: str = "la
 		raise TypeError(f"ball must be a DeviceSymBall, not {type(ball).__name__}")
 	_ffi.require_gpu()
 	is2024 = cube.get_is2024()
+	if return_states and not is2024:
+		raise ValueError("return_states hands out 20-byte states for a Linear(480, H); a 6x8x6 net has 288 inputs")
 	cube.set_is2024(True)                  # the sample as 20-byte rows, whatever the caller's representation
 	try:
 		states, _ = ball.sample(n, depths, rng)
 	finally:
 		cube.set_is2024(is2024)
 	states = torch.from_numpy(states).to(gpu)
-	oh_states = cube.device.as_oh(states) if is2024 else cube.device.to686(states, torch.float32)
+	oh_states = states if return_states else cube.device.as_oh(states) if is2024 else cube.device.to686(states, torch.float32)
 	own, children = cube.device.ball_child_depths(ball, states)
 	own, children = own.long(), children.long()
 	nearer = children == (own - 1).unsqueeze(1)

@@ -186,8 +186,131 @@ void k_ohl_gather(const uint32_t *__restrict__ states, const float *__restrict__
 	}
 }
 
+// ---- backward of the layer: dW and db from the 20-byte states (float32) ----------------------------------------------
+// dW[h, 24 i + v] = sum over the rows r with code(r, i) = v of dY[r, h]: the mirror image of k_ohl_gather.  A workgroup owns 64 output
+// columns and a contiguous row range and keeps that slice's [480][64] float32 sums in LDS (the forward's 122 880 B).  Wave w owns the
+// cubies 2 w and 2 w + 1 (ten waves), lane = column: no two waves ever touch the same LDS word, every wave walks its rows in ascending
+// order, and a row's 256 B of dY are read once per wave for both of its cubies.  The sum of a bin is therefore
+// ((0 + dY[r_1]) + dY[r_2]) + ... over its rows ascending -- a function of the row range alone, no atomics anywhere.
+//
+// A bin's running sum is an LDS read-modify-write, and one row after the other that is a chain of dependent LDS round trips.  Four rows
+// go through together instead: all eight reads (4 rows x 2 cubies) are issued before anything waits, and where a later row of the four
+// selects the bin of an earlier one (the codes are wave-uniform, the compares scalar) it takes that row's NEW sum instead of what it read;
+// the four writes follow in row order (LDS serves a wave's instructions in order: the last write of a bin wins).  Same adds, same order.
+// The partial slices go to scratch [split][480][H]; k_ohl_backward_reduce sums the splits ascending, transposes and makes db.
+constexpr int OHL_BWD_WAVES = 10;            // two cubies each
+constexpr int OHL_BWD_THREADS = 64 * OHL_BWD_WAVES;
+constexpr int OHL_BWD_R = 4;                 // rows in flight per wave
+constexpr size_t OHL_BWD_MIN_ROWS = 256;     // a workgroup's row range is at least this long (rk_ohl_backward_min_rows)
+constexpr size_t OHL_BWD_SLOTS = 256;        // workgroups the chip holds at once with 120 KB of LDS each: one per CU
+
+__global__ __launch_bounds__(OHL_BWD_THREADS)
+void k_ohl_backward_partial(const uint32_t *__restrict__ states, const float *__restrict__ dy, float *__restrict__ part,
+                            size_t n, int H, size_t rows_per_group)
+{
+	__shared__ __attribute__((aligned(16))) float s_acc[OHL_K * OHL_TN];     // 122 880 B: this workgroup's 64 columns of dW^T
+	const int tid = threadIdx.x, lane = tid & 63, c0 = blockIdx.x * OHL_TN;
+	const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);                 // (uniform: the state words below become scalar loads)
+	constexpr int SLICE4 = OHL_K * (OHL_TN / 4), PER_THREAD = SLICE4 / OHL_BWD_THREADS;
+	static_assert(PER_THREAD * OHL_BWD_THREADS == SLICE4, "the slice divides evenly over the workgroup");
+	#pragma unroll
+	for (int j = 0; j < PER_THREAD; j++) reinterpret_cast<f32x4 *>(s_acc)[tid + OHL_BWD_THREADS * j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+	__syncthreads();
+	const size_t r_begin = (size_t)blockIdx.y * rows_per_group;
+	const size_t r_end = r_begin + rows_per_group < n ? r_begin + rows_per_group : n;
+	// cubies 2 wv and 2 wv + 1 are bytes (2 wv & 3) and (2 wv & 3) + 1 of state word wv / 2
+	const int word = wv >> 1, shift = 16 * (wv & 1);
+	float *const bins0 = s_acc + (size_t)(24 * (2 * wv)) * OHL_TN + lane, *const bins1 = bins0 + 24 * OHL_TN;
+	const float *const dcol = dy + c0 + lane;
+	auto code = [](uint32_t c) { c &= 0xFFu; return c < 24u ? c : 23u; };     // code_of: unsigned byte, anything >= 24 counts as 23
+	size_t r = r_begin;
+	float d[OHL_BWD_R] = {0.0f, 0.0f, 0.0f, 0.0f};
+	uint32_t w[OHL_BWD_R] = {0u, 0u, 0u, 0u};
+	bool have = r + OHL_BWD_R <= r_end;
+	if (have) {
+		#pragma unroll
+		for (int j = 0; j < OHL_BWD_R; j++) { d[j] = dcol[(r + j) * (size_t)H]; w[j] = states[(r + j) * 5 + word]; }
+	}
+	while (have) {
+		float dn[OHL_BWD_R] = {0.0f, 0.0f, 0.0f, 0.0f};
+		uint32_t wn[OHL_BWD_R] = {0u, 0u, 0u, 0u};
+		const bool more = r + 2 * OHL_BWD_R <= r_end;
+		if (more) {                                                          // the next four rows while these are summed
+			#pragma unroll
+			for (int j = 0; j < OHL_BWD_R; j++) { dn[j] = dcol[(r + OHL_BWD_R + j) * (size_t)H]; wn[j] = states[(r + OHL_BWD_R + j) * 5 + word]; }
+		}
+		uint32_t k0[OHL_BWD_R], k1[OHL_BWD_R];
+		float a0[OHL_BWD_R], a1[OHL_BWD_R];
+		#pragma unroll
+		for (int j = 0; j < OHL_BWD_R; j++) { k0[j] = code(w[j] >> shift); k1[j] = code(w[j] >> (shift + 8)); }
+		#pragma unroll
+		for (int j = 0; j < OHL_BWD_R; j++) { a0[j] = bins0[k0[j] * OHL_TN]; a1[j] = bins1[k1[j] * OHL_TN]; }
+		#pragma unroll
+		for (int j = 0; j < OHL_BWD_R; j++) {
+			#pragma unroll
+			for (int p = 0; p < j; p++) {                                    // the latest earlier row with this bin, if any: ascending p, last match stays
+				if (k0[p] == k0[j]) a0[j] = a0[p];
+				if (k1[p] == k1[j]) a1[j] = a1[p];
+			}
+			a0[j] += d[j];
+			a1[j] += d[j];
+		}
+		#pragma unroll
+		for (int j = 0; j < OHL_BWD_R; j++) { bins0[k0[j] * OHL_TN] = a0[j]; bins1[k1[j] * OHL_TN] = a1[j]; }
+		r += OHL_BWD_R;
+		have = more;
+		#pragma unroll
+		for (int j = 0; j < OHL_BWD_R; j++) { d[j] = dn[j]; w[j] = wn[j]; }
+	}
+	for (; r < r_end; r++) {                                                 // up to three rows left over, one at a time
+		const float dr = dcol[r * (size_t)H];
+		const uint32_t wr = states[r * 5 + word];
+		const uint32_t c0r = code(wr >> shift), c1r = code(wr >> (shift + 8));
+		const float b0 = bins0[c0r * OHL_TN], b1 = bins1[c1r * OHL_TN];
+		bins0[c0r * OHL_TN] = b0 + dr;
+		bins1[c1r * OHL_TN] = b1 + dr;
+	}
+	__syncthreads();
+	float *const dst = part + (size_t)blockIdx.y * OHL_K * (size_t)H + c0;
+	#pragma unroll
+	for (int j = 0; j < PER_THREAD; j++) {
+		const int i = tid + OHL_BWD_THREADS * j, k = i >> 4, q = i & 15;
+		*reinterpret_cast<f32x4 *>(dst + (size_t)k * H + 4 * q) = reinterpret_cast<const f32x4 *>(s_acc)[i];
+	}
+}
+
+// dW[h, k] = part[0][k][h] + part[1][k][h] + ... in that order, through an LDS tile so that both sides move whole lines; db[h] is the sum
+// of cubie 0's 24 bins in ascending order (every row selects exactly one of them), made by the workgroups that hold those bins.
+constexpr int OHL_RED_K = 32;                // one-hot columns per workgroup: 480 = 15 x 32, cubie 0's 24 bins inside the first tile
+__global__ __launch_bounds__(256)
+void k_ohl_backward_reduce(const float *__restrict__ part, int splits, int H, float *__restrict__ dw, float *__restrict__ db)
+{
+	__shared__ float s_t[OHL_RED_K][OHL_TN + 1];
+	const int tid = threadIdx.x, hh = tid & 63, kq = tid >> 6, h0 = blockIdx.x * OHL_TN, k0 = blockIdx.y * OHL_RED_K;
+	#pragma unroll
+	for (int j = 0; j < OHL_RED_K / 4; j++) {
+		const int kl = kq + 4 * j;
+		const float *src = part + (size_t)(k0 + kl) * H + h0 + hh;
+		float acc = src[0];
+		for (int s = 1; s < splits; s++) acc += src[(size_t)s * OHL_K * (size_t)H];
+		s_t[kl][hh] = acc;
+	}
+	__syncthreads();
+	#pragma unroll
+	for (int p = 0; p < OHL_TN / 8; p++) {
+		const int hl = 8 * p + (tid >> 5), kl = tid & 31;
+		dw[(size_t)(h0 + hl) * OHL_K + k0 + kl] = s_t[kl][hl];
+	}
+	if (blockIdx.y == 0 && db != nullptr && tid < OHL_TN) {
+		float s = s_t[0][tid];
+		#pragma unroll
+		for (int v = 1; v < 24; v++) s += s_t[v][tid];
+		db[h0 + tid] = s;
+	}
+}
+
 // ---- route MFMA --------------------------------------------------------------------------------------------------
-constexpr int OHL_WROW = 976;                // bytes per LDS row of the W tile (480 bf16 + 16 B pad)
+constexpr int OHL_WROW = 976;               // bytes per LDS row of the W tile (480 bf16 + 16 B pad)
 constexpr int OHL_DROW = 144;                // bytes per LDS row of a wave's output staging (64 bf16 + 16 B pad)
 
 template <int RT, int ACT, bool AFFINE>
@@ -484,7 +607,31 @@ struct rk_ohl {
 	int act = RK_OHL_ACT_NONE;                    // epilogue (rk_ohl_set_epilogue)
 	float alpha = 1.0f;
 	float *affine = nullptr;                      // scale[H] then shift[H], or null
+	float *bwd_part = nullptr;                    // rk_ohl_backward's partial slices [split][480][H], made at first use, grown when needed
+	size_t bwd_floats = 0;
 };
+
+// the layouts of the three routes from nn.Linear's own: both launches, nothing else
+static int ohl_prepare(rk_ohl *h, const void *d_weight, int w_dtype, const void *d_bias, hipStream_t st)
+{
+	const size_t total = (size_t)h->H * OHL_K;
+	hipLaunchKernelGGL(k_ohl_prepare, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, d_weight, w_dtype == RK_OH_BF16 ? 1 : 0, h->H, h->wt_f32, h->w_bf16, h->w_frag);
+	hipLaunchKernelGGL(k_ohl_bias, dim3((unsigned)((h->H + 255) / 256)), dim3(256), 0, st, d_bias, w_dtype == RK_OH_BF16 ? 1 : 0, h->H, h->bias);
+	RK_HIP(hipGetLastError());
+	return RK_OK;
+}
+
+// rows of a workgroup of k_ohl_backward_partial: as many row ranges as give every CU one workgroup, none shorter than OHL_BWD_MIN_ROWS
+// (below that the 120 KB a workgroup zeroes and writes out outweigh its rows), whole groups of OHL_BWD_R rows.  A function of (n, H) alone.
+static size_t ohl_backward_rows(size_t n, int H)
+{
+	const size_t col_tiles = (size_t)H / OHL_TN;
+	size_t groups = OHL_BWD_SLOTS / col_tiles;
+	if (groups < 1) groups = 1;
+	size_t rows = (n + groups - 1) / groups;
+	if (rows < OHL_BWD_MIN_ROWS) rows = OHL_BWD_MIN_ROWS;
+	return (rows + OHL_BWD_R - 1) / OHL_BWD_R * OHL_BWD_R;
+}
 
 extern "C" {
 
@@ -501,10 +648,7 @@ int rk_ohl_create(rk_ohl_t **out, const void *d_weight, int w_dtype, const void 
 	if (e == hipSuccess) e = hipMalloc((void **)&h->w_frag, (size_t)H * OHL_K * sizeof(uint16_t));
 	if (e == hipSuccess) e = hipMalloc((void **)&h->bias, (size_t)H * sizeof(float));
 	if (e != hipSuccess) { rk_ohl_destroy(h); return fail(RK_EHIP, "rk_ohl_create: hipMalloc failed: %s", hipGetErrorString(e)); }
-	const size_t total = (size_t)H * OHL_K;
-	hipLaunchKernelGGL(k_ohl_prepare, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, d_weight, w_dtype == RK_OH_BF16 ? 1 : 0, H, h->wt_f32, h->w_bf16, h->w_frag);
-	hipLaunchKernelGGL(k_ohl_bias, dim3((unsigned)((H + 255) / 256)), dim3(256), 0, st, d_bias, w_dtype == RK_OH_BF16 ? 1 : 0, H, h->bias);
-	RK_HIP(hipGetLastError());
+	if (const int rc = ohl_prepare(h, d_weight, w_dtype, d_bias, st)) return rc;
 	RK_HIP(hipStreamSynchronize(st));              // the caller's weight tensor may go away
 	*out = h;
 	return RK_OK;
@@ -514,7 +658,52 @@ int rk_ohl_destroy(rk_ohl_t *h)
 {
 	if (!h) return RK_OK;
 	(void)hipFree(h->wt_f32); (void)hipFree(h->w_bf16); (void)hipFree(h->w_frag); (void)hipFree(h->bias); (void)hipFree(h->affine);
+	(void)hipFree(h->bwd_part);
 	delete h;
+	return RK_OK;
+}
+
+int rk_ohl_set_weights(rk_ohl_t *h, const void *d_weight, int w_dtype, const void *d_bias, void *stream)
+{
+	if (!h || !d_weight) return fail(RK_EINVAL, "rk_ohl_set_weights: null argument");
+	if (w_dtype != RK_OH_F32 && w_dtype != RK_OH_BF16) return fail(RK_EINVAL, "rk_ohl_set_weights: weights must be float32 or bfloat16");
+	return ohl_prepare(h, d_weight, w_dtype, d_bias, (hipStream_t)stream);   // in stream order: the caller's tensors stay alive until it has run
+}
+
+size_t rk_ohl_backward_rows(size_t n, int H)
+{
+	if (H < OHL_TN || H % OHL_TN != 0) return 0;
+	return ohl_backward_rows(n, H);
+}
+
+int rk_ohl_backward(rk_ohl_t *h, const int8_t *d_states, const float *d_dy, size_t n, float *d_dw, float *d_db, void *stream)
+{
+	if (!h) return fail(RK_EINVAL, "rk_ohl_backward: null handle");
+	if (!d_dw || (n != 0 && (!d_states || !d_dy))) return fail(RK_EINVAL, "rk_ohl_backward: null pointer");
+	if ((reinterpret_cast<uintptr_t>(d_states) & 3) || (reinterpret_cast<uintptr_t>(d_dy) & 15) || (reinterpret_cast<uintptr_t>(d_dw) & 15) ||
+	    (reinterpret_cast<uintptr_t>(d_db) & 3))
+		return fail(RK_EINVAL, "rk_ohl_backward: states and db must be 4-byte, dY and dW 16-byte aligned");
+	hipStream_t st = (hipStream_t)stream;
+	const size_t H = (size_t)h->H;
+	if (n == 0) {                                  // no rows: every sum is empty (+0.0 is all zero bits)
+		RK_HIP(hipMemsetAsync(d_dw, 0, H * OHL_K * sizeof(float), st));
+		if (d_db) RK_HIP(hipMemsetAsync(d_db, 0, H * sizeof(float), st));
+		return RK_OK;
+	}
+	const size_t rows = ohl_backward_rows(n, h->H), splits = (n + rows - 1) / rows;       // splits <= OHL_BWD_SLOTS: rows >= n / groups
+	const size_t need = splits * OHL_K * H;
+	if (need > h->bwd_floats) {
+		// (hipFree waits for the device: an earlier call's kernels are done with the old buffer)
+		if (h->bwd_part) { (void)hipFree(h->bwd_part); h->bwd_part = nullptr; h->bwd_floats = 0; }
+		hipError_t e = hipMalloc((void **)&h->bwd_part, need * sizeof(float));
+		if (e != hipSuccess) { h->bwd_part = nullptr; return fail(RK_EHIP, "rk_ohl_backward: hipMalloc of %zu bytes failed: %s", need * sizeof(float), hipGetErrorString(e)); }
+		h->bwd_floats = need;
+	}
+	hipLaunchKernelGGL(k_ohl_backward_partial, dim3((unsigned)(H / OHL_TN), (unsigned)splits), dim3(OHL_BWD_THREADS), 0, st,
+	                   (const uint32_t *)d_states, d_dy, h->bwd_part, n, h->H, rows);
+	hipLaunchKernelGGL(k_ohl_backward_reduce, dim3((unsigned)(H / OHL_TN), OHL_K / OHL_RED_K), dim3(256), 0, st,
+	                   (const float *)h->bwd_part, (int)splits, h->H, d_dw, d_db);
+	RK_HIP(hipGetLastError());
 	return RK_OK;
 }
 

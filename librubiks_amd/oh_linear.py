@@ -15,6 +15,10 @@ states instead of one-hot rows: `AStar(..., fused_first_layer=True)` and `adi_tr
 side by side) with the activation in front of it as ONE launch (`rk_tail_linear`) instead of an elementwise kernel over (n, K) and a
 GEMM with a 13-column output; `fuse_first_linear(..., fold_batchnorm=True)` uses it for bfloat16 nets (`FUSE_TAIL`).
 
+`StateLinear(net.shared_net[0])` is the layer for TRAINING a float32 net: it shares the layer's Parameters, follows their live values and
+has a backward (`rk_ohl_backward`: the weight gradient from the states, no one-hot and no dense GEMM against a matrix that is 96 % zeros);
+`train_on_states(net)` is the whole net on states with everything behind the first layer live.  `librubiks_amd.train.Train` uses them.
+
 `fuse_first_linear(net, epilogue=True)` also moves the activation and the eval-mode BatchNorm1d that follow the layer
 (model.py:157-159) into the kernel's epilogue, `fold_batchnorm=True` folds the remaining eval-mode BatchNorm1d layers into
 the Linear layers behind them: the same function in exact arithmetic, different float rounding (so not the default).
@@ -85,6 +89,97 @@ class OhLinear(_ffi.Owner):
 			out = torch.empty((n, self.out_features), dtype=dtype, device=device or "cuda")
 		_ffi.check(_ffi.lib().rk_ohl_forward(self._h, d_states, out.data_ptr(), _CODES[out.dtype], n, _ROUTES[route], _ffi.stream_ptr()))
 		return out
+
+
+def backward_rows(n: int, out_features: int) -> int:
+	"""Rows of one workgroup's row range in `rk_ohl_backward` on (n, out_features): the partial sums change hands every this many rows."""
+	return int(_ffi.lib().rk_ohl_backward_rows(n, out_features))
+
+
+BACKWARD_MIN_ROWS = 256    # no row range of rk_ohl_backward is shorter (csrc/rk_oh_linear.hip: OHL_BWD_MIN_ROWS; backward_rows(1, H) says so)
+
+
+class _StateLinearFn(torch.autograd.Function):
+	@staticmethod
+	def forward(ctx, states, weight, bias, engine):
+		w = weight.detach().contiguous()
+		b = bias.detach().contiguous() if bias is not None else None
+		# the engine's layouts from the parameters as they are NOW, in stream order (no sync: w and b outlive the launch in torch's allocator)
+		_ffi.check(_ffi.lib().rk_ohl_set_weights(engine._h, w.data_ptr(), _ffi.OH_F32, b.data_ptr() if b is not None else None, _ffi.stream_ptr()))
+		y = engine(states, route="gather")
+		ctx.engine, ctx.has_bias = engine, bias is not None
+		ctx.save_for_backward(states)
+		return y
+
+	@staticmethod
+	def backward(ctx, grad):
+		(states,) = ctx.saved_tensors
+		g = grad.contiguous()
+		if g.dtype != torch.float32:
+			g = g.float()
+		if g.data_ptr() % 16:
+			g = g.clone()
+		H = ctx.engine.out_features
+		dw = torch.empty((H, 480), dtype=torch.float32, device=g.device)
+		db = torch.empty(H, dtype=torch.float32, device=g.device) if ctx.has_bias else None
+		_ffi.check(_ffi.lib().rk_ohl_backward(ctx.engine._h, states.data_ptr(), g.data_ptr(), len(g), dw.data_ptr(),
+		                                      db.data_ptr() if db is not None else None, _ffi.stream_ptr()))
+		return None, dw, db, None
+
+
+class StateLinear(torch.nn.Module):
+	"""
+	The first Linear(480, H) of a float32 net for TRAINING: takes (n, 20) int8 states on the GPU instead of their one-hot rows and is
+	differentiable in the layer's parameters.  `weight` and `bias` ARE `linear.weight` and `linear.bias` -- the same Parameter objects,
+	so the owning net's optimizer, `state_dict`, `clone` and `load_state_dict` go on working and see every update.
+
+	forward: the exact gather route (`OhLinear(linear, "gather")`'s bits) on the parameters' values at the time of the call: every forward
+	refreshes the engine's layouts with `rk_ohl_set_weights`.  Deliberately every call and not "when the version counter moved": the
+	counter misses `param.data.copy_(...)`, which is how the reference's `_update_gen_net` writes (train.py:347); the refresh reads and
+	writes about 24 MB at H = 4096.  backward: `rk_ohl_backward`, a fixed-order float32 sum over the rows of every (cubie, code) bin; dW
+	and db are new tensors (autograd accumulates them into `.grad`), the states get no gradient.
+	"""
+
+	def __init__(self, linear: torch.nn.Linear):
+		super().__init__()
+		if not isinstance(linear, torch.nn.Linear):
+			raise TypeError(f"StateLinear wraps an nn.Linear, not {type(linear).__name__}")
+		if linear.weight.dtype != torch.float32:
+			raise ValueError("StateLinear trains in float32 (the reference's training precision): the layer must be float32")
+		if linear.out_features % 64 != 0:
+			raise ValueError(f"out_features {linear.out_features} must be a multiple of 64")
+		self._engine = OhLinear(linear, "gather")          # refuses what OhLinear refuses: in_features != 480, weights off the GPU
+		self.in_features, self.out_features = 20, linear.out_features
+		self.weight, self.bias = linear.weight, linear.bias
+
+	def forward(self, states: torch.Tensor) -> torch.Tensor:
+		if states.dtype != torch.int8 or not states.is_cuda or states.dim() != 2 or states.shape[1] != 20:
+			raise ValueError("states must be an (n, 20) int8 tensor on the GPU")
+		return _StateLinearFn.apply(states.contiguous(), self.weight, self.bias, self._engine)
+
+
+def train_on_states(net):
+	"""
+	-> callable(states, policy=True, value=True) with the semantics and the return convention of `net(as_oh(states), policy, value)`
+	(model.py:131-141) for a float32 net of the reference's structure, differentiable in every parameter: `StateLinear(shared_net[0])`, then
+	the LIVE `shared_net[1:]`, `policy_net` and `value_net` -- the net's own modules at the time of each call, nothing snapshotted, so a
+	training-mode BatchNorm1d updates its running statistics and `net.train()` / `net.eval()` mean what they always mean.
+	"""
+	shared = getattr(net, "shared_net", None)
+	if not isinstance(shared, torch.nn.Sequential) or not isinstance(shared[0], torch.nn.Linear):
+		raise TypeError("train_on_states needs a net whose shared_net starts with nn.Linear(480, H) (the reference's Model)")
+	first = StateLinear(shared[0])
+
+	def forward(states: torch.Tensor, policy: bool = True, value: bool = True):
+		assert policy or value
+		x = first(states)
+		for m in list(net.shared_net)[1:]:
+			x = m(x)
+		out = ([net.policy_net(x)] if policy else []) + ([net.value_net(x)] if value else [])
+		return out if len(out) > 1 else out[0]
+
+	forward.first = first
+	return forward
 
 
 def _act_code(activation):
