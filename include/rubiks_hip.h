@@ -14,7 +14,10 @@
  *     pointers.  The library never frees or retains caller memory.
  *   - `stream` is a hipStream_t passed as void* (NULL = default stream).  Device-pointer entries
  *     are stream-ordered and do not synchronise; *_host entries copy, launch, copy back and
- *     synchronise `stream` before returning.
+ *     synchronise `stream` before returning.  Everything an entry launches, copies or waits for goes to
+ *     its `stream` argument; an rk_*_create takes no stream and has finished its own initialisation
+ *     when it returns.  One handle is driven on one stream at a time: two streams using the same
+ *     handle at once is not supported (two handles on two streams are independent).
  *   - A 20-byte state is int8[20]: 8 corner codes slot*3+ori then 12 edge codes slot*2+ori
  *     (cube.py:58-65).  State arrays are dense row-major (n, 20); their base must be 4-byte
  *     aligned (always true for rows of a 256-B aligned allocation).

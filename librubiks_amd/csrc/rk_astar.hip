@@ -1570,6 +1570,7 @@ static int astar_create_impl(rk_astar_t **out, size_t capacity, int max_expansio
 		hipError_t he = hipMemset(d.chain0, 0, n_scan_blocks * sizeof(unsigned long long));
 		if (he == hipSuccess) he = hipMemset(d.chain1, 0, n_scan_blocks * world * sizeof(unsigned long long));
 		if (he == hipSuccess) he = hipMemset(d.chain2, 0, n_scan_blocks * world * sizeof(unsigned long long));
+		if (he == hipSuccess) he = hipStreamSynchronize(nullptr);          // the look-back words are clear when create returns, whatever stream the search takes
 		if (he != hipSuccess) e = fail(RK_EHIP, "hipMemset failed: %s", hipGetErrorString(he));
 	}
 	if (e) { rk_astar_destroy(h); return e; }

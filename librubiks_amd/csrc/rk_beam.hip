@@ -799,7 +799,8 @@ int rk_beamb_create(rk_beamb_t **out, rk_symball_t *ball, int searches, int widt
 	}
 	std::vector<int32_t> ctr(S * W_COUNT, 0);                                  // every slot at rest
 	for (size_t s = 0; s < S; s++) { ctr[s * W_COUNT + W_STATUS] = BEAM_IDLE; ctr[s * W_COUNT + W_WINKEY] = NO_WIN; }
-	const hipError_t he = hipMemcpy(d.ctr, ctr.data(), ctr.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+	hipError_t he = hipMemcpy(d.ctr, ctr.data(), ctr.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+	if (he == hipSuccess) he = hipStreamSynchronize(nullptr);                  // the counters are in place when create returns, whatever stream the first reset takes
 	if (he != hipSuccess) { delete h; return fail(RK_EHIP, "rk_beamb_create: %s", hipGetErrorString(he)); }
 	h->ctr_host.reserve(S * W_COUNT);
 	h->ctr_spare.resize(S * W_COUNT);

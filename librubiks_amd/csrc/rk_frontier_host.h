@@ -356,6 +356,7 @@ struct FrontierSlots {
 		}
 		hipError_t he = hipMemcpy(devs, table.data(), S * sizeof(FrontierDev), hipMemcpyHostToDevice);
 		if (he == hipSuccess) he = hipMemset(d.ctr, 0, S * S_COUNT * sizeof(int32_t));
+		if (he == hipSuccess) he = hipStreamSynchronize(nullptr);          // both are in place when create returns, whatever stream the first reset takes
 		if (he != hipSuccess) return fail(RK_EHIP, "%s: %s", who, hipGetErrorString(he));
 		ctr_host.reserve(S * S_COUNT);
 		ctr_spare.resize(S * S_COUNT);

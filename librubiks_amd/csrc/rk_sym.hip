@@ -1419,6 +1419,7 @@ int rk_ssearchb_create(rk_ssearchb_t **out, rk_symball_t *ball, int n_slots, siz
 	});
 	if (!e) {                                   // every key "none", so whichever of a slot's two a first round names is cleared
 		hipError_t he = hipMemset(h->keys, 0xFF, (size_t)n_slots * 2 * sizeof(unsigned long long));
+		if (he == hipSuccess) he = hipStreamSynchronize(nullptr);         // filled when create returns, whatever stream the first reset takes
 		if (he == hipSuccess) he = hipEventCreateWithFlags(&h->jobs_sent, hipEventDisableTiming);
 		if (he != hipSuccess) e = fail(RK_EHIP, "rk_ssearchb_create: %s", hipGetErrorString(he));
 	}
