@@ -1113,7 +1113,10 @@ int rk_mcts_backup_select_logits_range(rk_mcts_t *h, int first_tree, int n_trees
  * whose first layer reads states (rk_ohl_forward) can take them where they lie. */
 const int8_t *rk_mcts_children(rk_mcts_t *h);
 /* Synchronises.  h_status is (T, 6) int64: done, solved, n_states, simulations, path_len, error (1: path longer than max_path,
- * 2: broken neighbour link, 3: backup without a pending expansion). */
+ * 2: broken neighbour link, 3: backup without a pending expansion, 4: a NaN in the value, or a NaN or an infinity among the 12
+ * priors -- after the softmax of the logits entries, so a +inf logit counts and a -inf logit does not --, of a NEW child or of a
+ * root: that tree stops (done = 1) before anything of the simulation is written; infinite values are accepted, and the rows of
+ * children that are already in the tree are not looked at). */
 int rk_mcts_status(rk_mcts_t *h, long long *h_status, void *stream);
 /* Rows [first, first+count) of one tree's arrays to HOST buffers in the reference's dtypes (any may be NULL):
  * states int8 (count,20), neighbors int64 (count,12), leaves uint8, P/W/L float64 (count,12), V float64, N int64. */

@@ -55,7 +55,7 @@ struct MctsDev {
 // leaf been expanded already" therefore lives on the DEVICE: a k_mcts_expand that finds it set leaves at once, a backup that
 // finds it clear reports error 3 instead of backing up garbage -- so a captured step replays correctly from any state.
 enum { TR_PLEN = 0, TR_NSTATES, TR_MAXSTATES, TR_SIMS, TR_SOLVE_ACTION, TR_SOLVE_LEAF, TR_READY, TR_FLAGS /* done | solved << 8 | error << 16 */, TR_INTS = 8 };
-enum { MCTS_ERR_PATH = 1, MCTS_ERR_LINK = 2, MCTS_ERR_NOT_EXPANDED = 3 };
+enum { MCTS_ERR_PATH = 1, MCTS_ERR_LINK = 2, MCTS_ERR_NOT_EXPANDED = 3, MCTS_ERR_NONFINITE = 4 };
 __host__ __device__ inline int flags_done(int f) { return f & 0xFF; }
 __host__ __device__ inline int flags_solved(int f) { return (f >> 8) & 0xFF; }
 __host__ __device__ inline int flags_error(int f) { return (f >> 16) & 0xFF; }
@@ -173,14 +173,35 @@ void k_mcts_root(MctsDev d, const uint32_t *starts, const int32_t *max_states)
 	}
 }
 
+// What may enter a tree ("No NaN enters a tree"): the descent's arg-max takes the row maximum with the bare
+// v_max_f64 and is only right while no score U + Q is NaN.  That holds as long as every stored V is not NaN (+-inf are fine: all
+// twelve scores are then the same infinity and the first lane wins, as np.argmax) and every stored P is finite (a softmax never
+// returns an infinity; a caller's "probability" might, and inf * sqrt(0) is NaN).  Whoever stores P and V checks them with these.
+__device__ __forceinline__ bool value_refused(float v) { return v != v; }
+__device__ __forceinline__ bool prior_refused(float p) { return !(fabsf(p) <= 3.402823466e+38f); }
+
+// one thread per tree: the root's 12 priors and its value, all or nothing
 __global__ void k_mcts_set_root_pv(MctsDev d, const float *probs, const float *values)
 {
-	const int i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= d.T * 12) return;
-	const int t = i / 12, k = i - 12 * t;
+	const int t = blockIdx.x * blockDim.x + threadIdx.x;
+	if (t >= d.T) return;
+	float p[12];
+	#pragma unroll
+	for (int k = 0; k < 12; k++) p[k] = probs[(size_t)t * 12 + k];
+	const float v = values[t];
+	int32_t *tr = d.tree + (size_t)t * TR_INTS;
+	const int flags = tr[TR_FLAGS];
+	bool refused = value_refused(v);
+	#pragma unroll
+	for (int k = 0; k < 12; k++) refused |= prior_refused(p[k]);
+	if (refused) {                                                      // (a tree that is done -- a solved start -- never reads them: no error)
+		if (!flags_done(flags)) tr[TR_FLAGS] = flags | 1 | (MCTS_ERR_NONFINITE << 16);
+		return;
+	}
 	const Node root = node_of(d, (size_t)t * d.cap1, 1);
-	root.P()[k] = (double)probs[i];                                     // agents.py:472
-	if (k == 0) root.V() = (double)values[t];                           // agents.py:473
+	#pragma unroll
+	for (int k = 0; k < 12; k++) root.P()[k] = (double)p[k];            // agents.py:472
+	root.V() = (double)v;                                               // agents.py:473
 }
 
 __global__ void k_mcts_gather_roots(MctsDev d, uint32_t *out)
@@ -282,11 +303,18 @@ __device__ __forceinline__ float net_scalar(const void *p, size_t i)
 	return reinterpret_cast<const float *>(p)[i];
 }
 
+// a child's 12 numbers of the policy head as the net wrote them ...
 template <int IN>
-__device__ __forceinline__ void child_policy(const void *probs, size_t row, int stride, float out[12])
+__device__ __forceinline__ void child_policy_row(const void *probs, size_t row, int stride, float out[12])
 {
 	#pragma unroll
 	for (int k = 0; k < 12; k++) out[k] = net_scalar<IN>(probs, row * (size_t)stride + k);
+}
+
+// ... and its priors from them, in place
+template <int IN>
+__device__ __forceinline__ void child_policy(float out[12])
+{
 	if (IN == 0) return;
 	float m = out[0];
 	#pragma unroll
@@ -333,6 +361,8 @@ void k_mcts_backup_select(MctsDev d, const void *probs, const void *values, int 
 	const bool is_new = active && d.child_new[cbase] != 0;
 	const size_t rbase = (size_t)blockIdx.x * 12 + lane;                   // this child's row in the net's outputs of this launch
 	const float vf = active ? net_scalar<IN>(values, rbase * (size_t)v_stride) : 0.0f;
+	float pk[12] = {};                                                     // this child's row of the policy head (the net wrote all 12 T rows):
+	if (active) child_policy_row<IN>(probs, rbase, p_stride, pk);          // requested with the rest, used by the new children only
 	if (is_done) {
 		if (ahead_limit != 0 && active) d.child_new[cbase] = 0;            // (k_mcts_expand does this when it runs)
 		return;
@@ -341,14 +371,27 @@ void k_mcts_backup_select(MctsDev d, const void *probs, const void *values, int 
 		if (lane == 0) trw[TR_FLAGS] = tr.v[TR_FLAGS] | 1 | (MCTS_ERR_NOT_EXPANDED << 16);
 		return;
 	}
+	// No NaN enters the tree (value_refused / prior_refused above; a +inf logit is a NaN after the softmax, a -inf logit an exact
+	// zero): one NaN among the value and the priors of the NEW children -- the rows of known children are never read (agents.py:556-557
+	// assign the new ones only) -- stops the tree before anything of it is written.  The reference would go on; see DESIGN.md 3.2.
+	bool refused = false;
+	if (is_new) {
+		child_policy<IN>(pk);
+		refused = value_refused(vf);
+		#pragma unroll
+		for (int k = 0; k < 12; k++) refused |= prior_refused(pk[k]);
+	}
+	if (__ballot(refused) != 0ull) {
+		if (lane == 0) trw[TR_FLAGS] = tr.v[TR_FLAGS] | 1 | (MCTS_ERR_NONFINITE << 16);
+		if (ahead_limit != 0 && active) d.child_new[cbase] = 0;
+		return;
+	}
 	if (lane == 0) trw[TR_READY] = 0;                                      // consumed here; set again below if this launch expands ahead
 	const int leaf = pnodes[plen - 1];
 	const double v = (double)vf;
 	if (is_new) {
 		const Node child = node_of(d, node0, idx);
 		child.V() = v;                                                     // agents.py:557
-		float pk[12];
-		child_policy<IN>(probs, rbase, p_stride, pk);
 		#pragma unroll
 		for (int k = 0; k < 12; k++) {
 			child.P()[k] = (double)pk[k];                                  // agents.py:556
@@ -697,6 +740,7 @@ int rk_mcts_destroy(rk_mcts_t *h)
 int rk_mcts_reset(rk_mcts_t *h, const int8_t *h_start_states, const long long *h_max_states, double c, double nu, void *stream)
 {
 	if (!h || !h_start_states) return fail(RK_EINVAL, "rk_mcts_reset: null argument");
+	if (!std::isfinite(c) || !std::isfinite(nu)) return fail(RK_EINVAL, "rk_mcts_reset: c and nu must be finite");     // (the scores must never be NaN)
 	hipStream_t st = (hipStream_t)stream;
 	MctsDev &d = h->d;
 	const size_t T = (size_t)d.T, rows = T * d.cap1;
@@ -857,7 +901,7 @@ int rk_mcts_set_root_pv(rk_mcts_t *h, const float *d_probs, const float *d_value
 {
 	if (!h || !h->ready) return fail(RK_ESTATE, "rk_mcts_set_root_pv: reset the engine first");
 	if (!d_probs || !d_values) return fail(RK_EINVAL, "rk_mcts_set_root_pv: null pointer");
-	hipLaunchKernelGGL(k_mcts_set_root_pv, dim3(blocks((size_t)h->d.T * 12)), dim3(256), 0, (hipStream_t)stream, h->d, d_probs, d_values);
+	hipLaunchKernelGGL(k_mcts_set_root_pv, dim3(blocks((size_t)h->d.T)), dim3(256), 0, (hipStream_t)stream, h->d, d_probs, d_values);
 	RK_HIP(hipGetLastError());
 	return RK_OK;
 }

@@ -2705,7 +2705,8 @@ class MCTSBatch(DeepAgent, _ffi.Owner):
 		self._graph_cache = None              # it holds the engine's addresses
 		super()._free()
 
-	_ERRORS = {1: "path longer than max_path", 2: "broken neighbour link", 3: "backup without a pending expansion (rk_mcts_expand missing from the step)"}
+	_ERRORS = {1: "path longer than max_path", 2: "broken neighbour link", 3: "backup without a pending expansion (rk_mcts_expand missing from the step)",
+	           4: "NaN in the net's policy or value"}
 
 	def _poll(self):
 		st = np.zeros((self.n_trees, 6), np.int64)
