@@ -536,6 +536,34 @@ int rk_sym_canonical(const int8_t *d_states, size_t n, int8_t *d_rep, uint8_t *d
 /* d_out int8 (n, 20) = conj_sym of every DEVICE state of d_states, sym 0..47.  One launch; stream-ordered. */
 int rk_sym_conjugate(const int8_t *d_states, size_t n, int sym, int8_t *d_out, void *stream);
 
+/* ---- the cube group on 20-byte states: composition, inverse, a state seen from a goal, legality (rk_group_*) ----------------
+ * A move permutes all 24 sticker slots of a kind (corner slot 3 * pos + k, edge slot 2 * pos + k), so a state b reached from
+ * solved by a word has a full action g_b on the slots, the product of the word's moves.
+ *     apply(a, b)[c]    = g_b(a[c])                  a's word, then b's; apply(s, solved moved by m) = s moved by m
+ *     inverse(b)        : apply(b, inverse(b)) = apply(inverse(b), b) = solved
+ *     relative(s, goal) = apply(inverse(goal), s)    relative(goal, goal) = solved; relative(rotate(s, m), goal) =
+ *                                                    rotate(relative(s, goal), m): the distance from s to goal is the depth of it
+ * For an edge g_b(2 p + k) = b[p] ^ k; for a corner g_b(3 p + k) = full[0][p][b[p]][k].  All tables are derived from the move
+ * table at compile time.  Every entry below that launches is ONE launch, a thread per state, stream-ordered without
+ * synchronisation; n at most INT32_MAX, n = 0 does nothing; device pointers 4-byte aligned.  The output may be exactly an operand
+ * of n rows (a thread reads its operands before it stores); any other overlap of the output with an operand is RK_EINVAL.  A row
+ * that is no legal state is read in bounds and gives an unspecified row: rk_group_legal is the entry that reports such rows. */
+#define RK_GROUP_GRID 2048   /* workgroups of 256 states a launch has at most: beyond RK_GROUP_GRID * 256 states a thread takes several */
+/* HOST: full uint8 (2, 12, 24, 3) = [kind][home][code][k] the slot g_b sends slot k of cubie `home` to when b[home] = code (corners:
+ * homes 0..7; edges: k 0..1; zero elsewhere), inv uint8 (2, 12, 24) the slot of cubie `home` that g_b sends to the primary slot of
+ * the position of `code`, tau uint8 (24) the twist of a corner code.  Any may be NULL, not all.  Touches no device. */
+int rk_group_tables(uint8_t *h_full, uint8_t *h_inv, uint8_t *h_tau);
+/* d_out int8 (n, 20) = apply(state i, effect i); n_effects = n, or 1: effect 0 for every state (RK_EINVAL otherwise). */
+int rk_group_apply(const int8_t *d_states, size_t n, const int8_t *d_effects, size_t n_effects, int8_t *d_out, void *stream);
+int rk_group_inverse(const int8_t *d_states, size_t n, int8_t *d_out, void *stream);
+/* d_out int8 (n, 20) = relative(state i, goal i), inverse and apply in one pass; n_goals = n, or 1: goal 0 for every state. */
+int rk_group_relative(const int8_t *d_states, size_t n, const int8_t *d_goals, size_t n_goals, int8_t *d_out, void *stream);
+/* d_flags uint8 (n): 1 where row i is a state reachable from solved -- every code below 24, the corner and the edge positions
+ * permutations of equal parity, an even number of flipped edges, corner twists that add up to 0 mod 3 --, 0 elsewhere.  d_stats
+ * int64[2] (8-byte aligned; initialise to [0, INT64_MAX]): += the rows that are not, min= the lowest of them, as rk_686_to2024
+ * counts.  Either may be NULL, not both. */
+int rk_group_legal(const int8_t *d_states, size_t n, uint8_t *d_flags, long long *d_stats, void *stream);
+
 /* ---- the symmetry-reduced goal ball: one representative per orbit (rk_symball_*) -------------------------------------------
  * The canonical representatives of the states within `radius` quarter turns of solved, built once and kept in HBM; the depth of
  * a representative is the depth of the up to 48 states of its orbit.  Node 1 is the solved state, the pool is in index order: a

@@ -132,6 +132,11 @@ SIGNATURES = {
 	"rk_sym_tables": (_i, [_vp, _vp, _vp]),
 	"rk_sym_canonical": (_i, [_vp, _sz, _vp, _vp, _vp, _vp]),
 	"rk_sym_conjugate": (_i, [_vp, _sz, _i, _vp, _vp]),
+	"rk_group_tables": (_i, [_vp, _vp, _vp]),
+	"rk_group_apply": (_i, [_vp, _sz, _vp, _sz, _vp, _vp]),
+	"rk_group_inverse": (_i, [_vp, _sz, _vp, _vp]),
+	"rk_group_relative": (_i, [_vp, _sz, _vp, _sz, _vp, _vp]),
+	"rk_group_legal": (_i, [_vp, _sz, _vp, _vp, _vp]),
 	"rk_symball_create": (_i, [C.POINTER(_vp), _i, _i, _sz]),
 	"rk_symball_destroy": (_i, [_vp]),
 	"rk_symball_build": (_i, [_vp, _i, _vp]),

@@ -570,6 +570,99 @@ class device:
 				raise ValueError(f"{bad} of {n} rows are not legal 6x8x6 cube states (the first is row {first})")
 		return out
 
+	# ---- the cube group on 20-byte states (csrc/rk_group.hip; not in the reference) ----
+	#: a launch of rk_group_* has at most RK_GROUP_GRID workgroups of 256 states: beyond this many rows a thread takes several
+	GROUP_PASS_ROWS = 2048 * 256
+
+	@staticmethod
+	def _group_rows(t: torch.Tensor, what: str, n: int = None) -> int:
+		"""The rows of an (n, 20) int8 device operand; with `n`: one row or n (the broadcast rule of the second operand)."""
+		_check_dev(t, torch.int8, what)
+		rows = t.numel() // 20
+		if t.numel() != 20 * rows or (t.dim() and t.shape[-1] != 20) or (n is not None and rows not in (1, n)):
+			raise ValueError(f"{what} must have shape (n, 20)" + ("" if n is None else f" with n = 1 or {n}") + f", got {tuple(t.shape)}")
+		return rows
+
+	@staticmethod
+	def _group_out(out: torch.Tensor, n: int, like: torch.Tensor) -> torch.Tensor:
+		if out is None:
+			return torch.empty((n, 20), dtype=torch.int8, device=like.device)
+		_check_dev(out, torch.int8, "out")
+		if out.numel() != 20 * n:
+			raise ValueError(f"out must have shape ({n}, 20), got {tuple(out.shape)}")
+		return out
+
+	@staticmethod
+	def _group_check(check: bool, **operands):
+		"""`check`: every operand through rk_group_legal first (one launch and one synchronisation each); ValueError for an illegal row."""
+		if check:
+			for what, t in operands.items():
+				n = t.numel() // 20
+				stats = _new_stats()
+				_ffi.check(_ffi.lib().rk_group_legal(t.data_ptr(), n, None, stats.data_ptr(), _ffi.stream_ptr()))
+				bad, first = stats.tolist()
+				if bad:
+					raise ValueError(f"{bad} of {n} rows of {what} are not legal cube states (the first is row {first})")
+
+	@staticmethod
+	def is_legal(states: torch.Tensor, out: torch.Tensor = None, stats: torch.Tensor = None) -> torch.Tensor:
+		"""uint8 (n,): 1 where row i of the int8 (n, 20) states can be reached from solved -- every code in range, the corner and
+		edge positions permutations of equal parity, edge flips and corner twists that add up to zero --, 0 elsewhere.  `stats`
+		(int64[2] = [count, first index] of the rows that are not, initialise to [0, INT64_MAX]) is updated if given.  One launch."""
+		_ffi.require_gpu()
+		n = device._group_rows(states, "states")
+		if out is None:
+			out = torch.empty(n, dtype=torch.uint8, device=states.device)
+		else:
+			_check_dev(out, torch.uint8, "out")
+			if out.numel() != n:
+				raise ValueError(f"out must have shape ({n},), got {tuple(out.shape)}")
+		if stats is not None:
+			_check_dev(stats, torch.int64, "stats")
+		_ffi.check(_ffi.lib().rk_group_legal(states.data_ptr(), n, out.data_ptr(), stats.data_ptr() if stats is not None else None,
+		                                     _ffi.stream_ptr()))
+		return out
+
+	@staticmethod
+	def apply_state(states: torch.Tensor, effects: torch.Tensor, out: torch.Tensor = None, check: bool = True) -> torch.Tensor:
+		"""(n, 20): the states after the net effect of `effects` (one state, or one for each) is applied to them -- if a word A
+		makes states[i] from solved and B makes the effect, A followed by B makes the result.  apply_state(s, solved moved by m) is
+		s moved by m.  One launch (engine rk_group_apply); `out` may be `states`.  `check`: ValueError for an operand row that is
+		no legal cube state, at the price of a launch and a synchronisation per operand; without it such a row gives an
+		unspecified row."""
+		_ffi.require_gpu()
+		n = device._group_rows(states, "states")
+		m = device._group_rows(effects, "effects", n)
+		out = device._group_out(out, n, states)
+		device._group_check(check, states=states, effects=effects)
+		_ffi.check(_ffi.lib().rk_group_apply(states.data_ptr(), n, effects.data_ptr(), m, out.data_ptr(), _ffi.stream_ptr()))
+		return out
+
+	@staticmethod
+	def inverse(states: torch.Tensor, out: torch.Tensor = None, check: bool = True) -> torch.Tensor:
+		"""(n, 20): the states x with apply_state(s, x) = apply_state(x, s) = solved; as far from solved as s.  One launch
+		(engine rk_group_inverse); `out` may be `states`.  `check` as in `apply_state`."""
+		_ffi.require_gpu()
+		n = device._group_rows(states, "states")
+		out = device._group_out(out, n, states)
+		device._group_check(check, states=states)
+		_ffi.check(_ffi.lib().rk_group_inverse(states.data_ptr(), n, out.data_ptr(), _ffi.stream_ptr()))
+		return out
+
+	@staticmethod
+	def relative(states: torch.Tensor, goal: torch.Tensor, out: torch.Tensor = None, check: bool = True) -> torch.Tensor:
+		"""(n, 20): the states seen from `goal` (one state, or one for each), apply_state(inverse(goal), states): solved where a
+		state is its goal, and moved by m where the state is moved by m.  The distance of the result to solved is the distance from
+		the state to its goal, and a solution of the result turns the state into the goal.  One launch (engine rk_group_relative);
+		`out` may be `states`.  `check` as in `apply_state`."""
+		_ffi.require_gpu()
+		n = device._group_rows(states, "states")
+		m = device._group_rows(goal, "goal", n)
+		out = device._group_out(out, n, states)
+		device._group_check(check, states=states, goal=goal)
+		_ffi.check(_ffi.lib().rk_group_relative(states.data_ptr(), n, goal.data_ptr(), m, out.data_ptr(), _ffi.stream_ptr()))
+		return out
+
 
 def as686(states20: np.ndarray) -> np.ndarray:
 	"""20-byte states (n, 20) [or one state (20,)] -> the same cubes as int8 (n, 6, 8, 6) [or (6, 8, 6)], whatever the current repr.
@@ -677,6 +770,78 @@ def conjugate(states, sym: int):
 	out = torch.empty((n, 20), dtype=torch.int8, device=gpu)
 	_ffi.check(_ffi.lib().rk_sym_conjugate(q.data_ptr(), n, int(sym), out.data_ptr(), _ffi.stream_ptr()))
 	return _rows_out(_to_host(out))
+
+
+###################
+# The cube group  #   (csrc/rk_group.hip, rk_group_tables.h; not in the reference)
+###################
+def group_tables():
+	"""(full (2, 12, 24, 3), inv (2, 12, 24), tau (24,)) uint8: the library's tables of the full action of a state on the sticker
+	slots.  full[kind][p][v][k] is where slot k of cubie p goes under every state b with b[p] = v, inv[kind][p][v] the slot of cubie
+	p that goes to the primary slot of v's position, tau the twist of a corner code.  Needs no GPU."""
+	full, inv, tau = np.empty((2, 12, 24, 3), np.uint8), np.empty((2, 12, 24), np.uint8), np.empty(24, np.uint8)
+	_ffi.check(_ffi.lib().rk_group_tables(full.ctypes.data, inv.ctypes.data, tau.ctypes.data))
+	return full, inv, tau
+
+
+def _group_operands(states, second=None, what: str = None):
+	"""The (n, 20) rows of `states` and the 1 or n rows of the second operand, on the device."""
+	rows = _rows2024(states)
+	q = torch.from_numpy(rows).to(gpu)
+	if second is None:
+		return rows, q, None
+	other = _rows2024(second)
+	if len(other) not in (1, len(rows)):
+		raise ValueError(f"{what} must be one state or one for each of the {len(rows)} states, got {len(other)}")
+	return rows, q, torch.from_numpy(other).to(gpu)
+
+
+def apply_state(states, effects, check: bool = True):
+	"""The n states in the current representation after the net effect of `effects` (one state or n) is applied to them: if a
+	word A makes states[i] from solved and B the effect, A followed by B makes the result (`device.apply_state`)."""
+	_ffi.require_gpu()
+	rows, q, e = _group_operands(states, effects, "effects")
+	if len(rows) == 0:
+		return _rows_out(rows)
+	return _rows_out(_to_host(device.apply_state(q, e, out=q, check=check)))
+
+
+def inverse(states, check: bool = True):
+	"""The inverses of n states in the current representation: apply_state(s, inverse(s)) is solved (`device.inverse`)."""
+	_ffi.require_gpu()
+	rows, q, _ = _group_operands(states)
+	if len(rows) == 0:
+		return _rows_out(rows)
+	return _rows_out(_to_host(device.inverse(q, out=q, check=check)))
+
+
+def relative(states, goal, check: bool = True):
+	"""n states in the current representation seen from `goal` (one state or n): solved where a state is its goal; the distance
+	of the result to solved is the distance from the state to the goal, and what solves the result turns the state into the goal
+	(`device.relative`)."""
+	_ffi.require_gpu()
+	rows, q, g = _group_operands(states, goal, "goal")
+	if len(rows) == 0:
+		return _rows_out(rows)
+	return _rows_out(_to_host(device.relative(q, g, out=q, check=check)))
+
+
+def is_legal(states) -> np.ndarray:
+	"""bool (n,): which of n states in the current representation can be reached from solved.  In 6x8x6 mode a row that is no
+	well-formed one-hot showing every cubie once is not legal either (no ValueError here)."""
+	_ffi.require_gpu()
+	if _is2024:
+		rows = _rows2024(states)
+		q = torch.from_numpy(rows).to(gpu)
+	else:
+		arr = np.ascontiguousarray(states, dtype=np.int8)
+		if arr.size % 288 or (arr.ndim and arr.shape[-1] != 6):
+			raise ValueError(f"states must be (n, 6, 8, 6) in 6x8x6 mode, got shape {arr.shape}")
+		rows = arr.reshape(-1, 288)
+		q = device.from686(torch.from_numpy(rows).to(gpu), check=False) if len(rows) else None      # an ill-formed row: -1 bytes
+	if len(rows) == 0:
+		return np.zeros(0, bool)
+	return device.is_legal(q).cpu().numpy().astype(bool)
 
 
 ################

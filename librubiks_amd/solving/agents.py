@@ -585,10 +585,13 @@ class _KeptBall(_ffi.Owner):
 		the others.  One launch."""
 		self.build()
 		rows = self._rows(states)
-		n = len(rows)
-		if n == 0:
+		if len(rows) == 0:
 			return np.zeros(0, np.int64)
-		q = torch.from_numpy(rows).to(gpu)
+		return self._depth_of(torch.from_numpy(rows).to(gpu))
+
+	def _depth_of(self, q: torch.Tensor) -> np.ndarray:
+		"""`depth` of (n, 20) rows on the device, n > 0."""
+		n = len(q)
 		out = torch.empty(n, dtype=torch.int32, device=gpu)
 		_ffi.check(self._entry("depth")(self._h, q.data_ptr(), n, out.data_ptr(), _ffi.stream_ptr()))
 		return out.cpu().numpy().astype(np.int64)
@@ -603,14 +606,43 @@ class _KeptBall(_ffi.Owner):
 		outside the ball.  One launch."""
 		self.build()
 		rows = self._rows(states)
-		n = len(rows)
-		if n == 0:
+		if len(rows) == 0:
 			return np.zeros(0, np.int64), np.zeros((0, self.radius), np.int64)
-		q = torch.from_numpy(rows).to(gpu)
+		return self._solve_of(torch.from_numpy(rows).to(gpu))
+
+	def _solve_of(self, q: torch.Tensor):
+		"""`solve` of (n, 20) rows on the device, n > 0."""
+		n = len(q)
 		lengths = torch.empty(n, dtype=torch.int32, device=gpu)
 		actions = torch.empty((n, max(self.radius, 1)), dtype=torch.int8, device=gpu)
 		self._solve(q, n, lengths, actions)
 		return lengths.cpu().numpy().astype(np.int64), actions.cpu().numpy().astype(np.int64)[:, :self.radius]
+
+	def _relative(self, a, b, check: bool):
+		"""(n, 20) rows on the device: a[i] seen from b[i] (`b`: one state or n), in the representation cube.get_is2024() names;
+		None for no rows.  The rows stay on the device: what reads them next is the ball's own launch."""
+		self.build()
+		rows, goals = self._rows(a), self._rows(b)
+		if len(goals) not in (1, len(rows)):
+			raise ValueError(f"b must be one state or one for each of the {len(rows)} states of a, got {len(goals)}")
+		if len(rows) == 0:
+			return None
+		q = torch.from_numpy(rows).to(gpu)
+		return cube.device.relative(q, torch.from_numpy(goals).to(gpu), out=q, check=check)
+
+	def distance(self, a, b, check: bool = True) -> np.ndarray:
+		"""int64 (n,): the exact number of quarter turns from a[i] to b[i] (`b`: one state or n) where the ball holds it, -1 elsewhere:
+		`depth` of `cube.relative(a, b)`, the relative states made on the device and read there by the depth launch.  `check`:
+		ValueError for a row that is no legal cube state (`cube.device.relative`)."""
+		q = self._relative(a, b, check)
+		return np.zeros(0, np.int64) if q is None else self._depth_of(q)
+
+	def path(self, a, b, check: bool = True):
+		"""(lengths int64 (n,), actions int64 (n, radius)) shaped like `solve`'s: a shortest sequence of moves that turns a[i] into
+		b[i] (`b`: one state or n), length -1 where the two are further apart than the ball reaches: `solve` of
+		`cube.relative(a, b)`, made and read on the device."""
+		q = self._relative(a, b, check)
+		return (np.zeros(0, np.int64), np.zeros((0, self.radius), np.int64)) if q is None else self._solve_of(q)
 
 	MAX_QUEUE = 4096                        # the longest queue of rk_bshorten and rk_sshorten
 	shorten_scratch_bytes = 256 << 20       # the most scratch one call of the engine is given; a batch is cut into calls to fit
@@ -816,7 +848,11 @@ class DeviceSymBall(_KeptBall):
 		extra = eng.int_in("extra", extra, 0, self.MAX_EXTRA)
 		self.build()
 		rows = self._rows(states)
-		n, width = len(rows), extra + self.radius
+		return self._solve_beyond_of(torch.from_numpy(rows).to(gpu) if len(rows) else None, len(rows), extra, last_actions, time_limit)
+
+	def _solve_beyond_of(self, q, n: int, extra: int, last_actions=None, time_limit: float = None):
+		"""`solve_beyond` of (n, 20) rows on the device (None for n = 0), `extra` checked."""
+		width = extra + self.radius
 		last = None
 		if last_actions is not None:
 			last = np.asarray(last_actions, dtype=np.int64).reshape(-1)
@@ -827,7 +863,6 @@ class DeviceSymBall(_KeptBall):
 			return lengths, actions
 		t0 = time.perf_counter()
 		lib, stream, cap = _ffi.lib(), _ffi.stream_ptr(), self._launch_cap()
-		q = torch.from_numpy(rows).to(gpu)
 		got = torch.empty(n, dtype=torch.int32, device=gpu)
 		word = torch.empty((n, max(self.radius, 1)), dtype=torch.int8, device=gpu)
 		self._solve(q, n, got, word)
@@ -872,6 +907,20 @@ class DeviceSymBall(_KeptBall):
 				actions[todo[hit], e:e + self.radius] = word.cpu().numpy()[:len(hit), :self.radius]
 			todo = todo[rank == 0xFFFFFFFF]
 		return lengths, actions
+
+	def distance(self, a, b, extra: int = 0, check: bool = True) -> np.ndarray:
+		"""`_KeptBall.distance`; with `extra` > 0 pairs up to radius + extra quarter turns apart are answered, by `solve_beyond`'s
+		probes on the relative states (its lengths)."""
+		return self.path(a, b, extra, check)[0] if extra else super().distance(a, b, check)
+
+	def path(self, a, b, extra: int = 0, check: bool = True):
+		"""`_KeptBall.path`; with `extra` > 0 through `solve_beyond`: (lengths, actions (n, extra + radius)), pairs up to radius +
+		extra quarter turns apart answered."""
+		extra = eng.int_in("extra", extra, 0, self.MAX_EXTRA)
+		if not extra:
+			return super().path(a, b, check)
+		q = self._relative(a, b, check)
+		return self._solve_beyond_of(q, 0 if q is None else len(q), extra)
 
 	def _depths_ranks(self, depths, ranks):
 		"""(depths int64 (n,), ranks int64 (n,)) of a `state_at` call, checked on the host: ValueError for anything but integers,
@@ -3235,3 +3284,58 @@ class AStarBatch(DeepAgent, _ffi.Owner):
 
 	def __str__(self):
 		return f"Batched AStar x{self.n_searches} (lambda={self.lambda_}, N={self.expansions})"
+
+
+class TowardsGoal:
+	"""
+	Any agent as a solver towards `goal` instead of the solved state: `search` hands the wrapped agent `cube.relative(state, goal)`.
+	Relabelling the cubies by a goal commutes with the 12 moves, so the relative state is as far from solved as the state is from
+	the goal, the queue that solves it turns `state` into `goal`, and a net trained on the distance to solved is the heuristic for
+	the distance to the goal.  Works for the one-state agents (`search(state, time_limit, max_states) -> bool`) and for the batch
+	agents (`search(states, ...)` on all rows); `action_queue`, `len()`, `lengths`, `action_queue_of(i)` and every other attribute
+	are the wrapped agent's.  States and goal are in the representation cube.get_is2024() names when a method is called.
+
+	`goal` is checked once, here (ValueError unless `cube.is_legal`); with `check_states` every call checks its states the same
+	way, at the price of a launch and a synchronisation.
+	"""
+
+	def __init__(self, agent, goal, check_states: bool = True):
+		rows = cube.cube._rows2024(goal)
+		if len(rows) != 1:
+			raise ValueError(f"goal must be one state, got {len(rows)}")
+		if not cube.is_legal(goal).all():
+			raise ValueError("1 of 1 rows of goal are not legal cube states (the first is row 0)")
+		self.agent, self.check_states = agent, bool(check_states)
+		self._goal20 = rows.copy()
+
+	@property
+	def goal(self) -> np.ndarray:
+		"""The goal in the current representation."""
+		return cube.cube._rows_out(self._goal20)[0]
+
+	def relative(self, states) -> np.ndarray:
+		"""`states` (one, or n rows) seen from the goal, in the shape they came in."""
+		if self.check_states:
+			bad = np.nonzero(~cube.is_legal(states))[0]
+			if len(bad):
+				raise ValueError(f"{len(bad)} of {len(cube.cube._rows2024(states))} rows of states are not legal cube states (the first is row {bad[0]})")
+		rows = cube.cube._rows2024(states)
+		if len(rows) == 0:
+			return np.asarray(states, dtype=np.int8)
+		q = torch.from_numpy(rows).to(gpu)
+		rel = cube.device.relative(q, torch.from_numpy(self._goal20).to(gpu), out=q, check=False)
+		return cube.cube._rows_out(cube.cube._to_host(rel)).reshape(np.shape(states))
+
+	def search(self, states, *args, **kwargs):
+		return self.agent.search(self.relative(states), *args, **kwargs)
+
+	def __getattr__(self, name):
+		if name == "agent":                                              # (before __init__ has set it)
+			raise AttributeError(name)
+		return getattr(self.agent, name)
+
+	def __len__(self):
+		return len(self.agent)
+
+	def __str__(self):
+		return f"{self.agent} towards a goal"
