@@ -564,6 +564,47 @@ int rk_group_relative(const int8_t *d_states, size_t n, const int8_t *d_goals, s
  * counts.  Either may be NULL, not both. */
 int rk_group_legal(const int8_t *d_states, size_t n, uint8_t *d_flags, long long *d_stats, void *stream);
 
+/* ---- pattern databases: exact distances and solutions for partial goals (rk_pdb_*) -------------------------------------------
+ * A pattern is a set of kc corner cubies (0..7) and ke edge cubies (0..11), each ascending, kc + ke >= 1; its goal is those
+ * cubies at their home codes (3 c, 2 e), the others anywhere.  A move maps every cubie's code on its own, so the selected codes
+ * of a state are closed under the 12 moves, and their space is small enough for a dense table of one byte per entry in HBM:
+ * the exact number of quarter turns that bring the selected cubies home.  THE INDEX of the selected codes, over the selected
+ * cubies of a kind in order (N = 8 or 12, position = code / 3 or code / 2, digit = code % 3 or code % 2):
+ *     r = 0; for i in 0..k-1: d_i = p_i - #{j < i : p_j < p_i}; r = r * (N - i) + d_i          range P(N, k) = N! / (N - k)!
+ *     o = 0; for i: o = o * 3 + digit_i (edges: * 2)                                            range O_c = 3^kc, 2^ke
+ *     with all 8 corners the last corner's digit is left out (O_c = 3^7): the twists tau (rk_group_tables) add up to 0 mod 3
+ *     index = ((r_c * O_c + o_c) * P(12, ke) + r_e) * 2^ke + o_e                                size = P(8, kc) O_c P(12, ke) 2^ke
+ * Every entry of an accepted pattern is reachable, and the build checks it.  Queries are ONE launch, a thread per state under a
+ * capped grid, stream-ordered without synchronisation; n at most INT32_MAX, n = 0 does nothing; device pointers 4-byte aligned.
+ * A row whose SELECTED codes are no partial pattern -- a code outside 0..23, two selected cubies of a kind on one position --
+ * is answered -1 before any table access; the other bytes of a row do not matter. */
+#define RK_PDB_GRID 2048     /* workgroups of 256 states a query has at most: beyond RK_PDB_GRID * 256 states a thread takes several */
+#define RK_PDB_MAX_SIZE 2147483648ULL
+typedef struct rk_pdb rk_pdb_t;
+/* h_corners uint8 (kc), h_edges uint8 (ke): the selected cubies, ascending (either may be NULL when its count is 0).  RK_EINVAL
+ * for an empty pattern, a cubie out of range or out of order, ke >= 11 (the permutation parity would leave entries unreachable)
+ * or a size above RK_PDB_MAX_SIZE.  Allocates nothing. */
+int rk_pdb_create(rk_pdb_t **out, const uint8_t *h_corners, int kc, const uint8_t *h_edges, int ke);
+int rk_pdb_destroy(rk_pdb_t *h);
+/* Builds the table (nothing if it is built): level d is one sweep over the whole table, which stores d + 1 into the unreached
+ * children of every entry equal to d and counts the entries of level d; the host reads that count after every level and stops
+ * at the first empty one.  RK_ECAPACITY when the device has no room; RK_ESTATE unless the level sizes add up to the size and
+ * level 0 holds one entry (the table is freed and the handle stays unbuilt).  Synchronises. */
+int rk_pdb_build(rk_pdb_t *h, void *stream);
+/* h_status[64] = built, size, kc, ke, levels, then the level sizes at [5 .. 5 + levels - 1] (zeros before the build and beyond).
+ * Touches no device. */
+int rk_pdb_status(rk_pdb_t *h, long long *h_status);
+/* Entries [first, first+count) of the table to HOST h_bytes uint8 (count).  Synchronises. */
+int rk_pdb_export(rk_pdb_t *h, size_t first, size_t count, uint8_t *h_bytes, void *stream);
+/* d_depth[q] = the exact number of quarter turns that bring the selected cubies of DEVICE state q of d_states int8 (n, 20) home,
+ * -1 for a row whose selected codes are no partial pattern. */
+int rk_pdb_depth(rk_pdb_t *h, const int8_t *d_states, size_t n, int32_t *d_depth, void *stream);
+/* A shortest word that brings the selected cubies home, by descent -- at each step the lowest action whose child's entry is one
+ * less --: d_lengths[q] moves (-1 for an invalid row), row q of d_actions int8 (n, levels - 1) holds them, padded with -1.
+ * d_error[0] is cleared, then set to RK_ESTATE if a reached entry has no such child (its length is -1 then; never in a table
+ * that passed its build). */
+int rk_pdb_solve(rk_pdb_t *h, const int8_t *d_states, size_t n, int32_t *d_lengths, int8_t *d_actions, int32_t *d_error, void *stream);
+
 /* ---- the symmetry-reduced goal ball: one representative per orbit (rk_symball_*) -------------------------------------------
  * The canonical representatives of the states within `radius` quarter turns of solved, built once and kept in HBM; the depth of
  * a representative is the depth of the up to 48 states of its orbit.  Node 1 is the solved state, the pool is in index order: a

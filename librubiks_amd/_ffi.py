@@ -137,6 +137,13 @@ SIGNATURES = {
 	"rk_group_inverse": (_i, [_vp, _sz, _vp, _vp]),
 	"rk_group_relative": (_i, [_vp, _sz, _vp, _sz, _vp, _vp]),
 	"rk_group_legal": (_i, [_vp, _sz, _vp, _vp, _vp]),
+	"rk_pdb_create": (_i, [C.POINTER(_vp), _vp, _i, _vp, _i]),
+	"rk_pdb_destroy": (_i, [_vp]),
+	"rk_pdb_build": (_i, [_vp, _vp]),
+	"rk_pdb_status": (_i, [_vp, _vp]),
+	"rk_pdb_export": (_i, [_vp, _sz, _sz, _vp, _vp]),
+	"rk_pdb_depth": (_i, [_vp, _vp, _sz, _vp, _vp]),
+	"rk_pdb_solve": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp]),
 	"rk_symball_create": (_i, [C.POINTER(_vp), _i, _i, _sz]),
 	"rk_symball_destroy": (_i, [_vp]),
 	"rk_symball_build": (_i, [_vp, _i, _vp]),
