@@ -80,7 +80,7 @@ constexpr size_t ZERO_COPY_MAX = 1u << 20;            // staged bytes (inputs + 
 struct PinnedBuf { char *host = nullptr; char *dev = nullptr; int device = -1; bool tried = false; };
 thread_local PinnedBuf g_pinned;
 
-inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
+constexpr size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // the buffer of this thread for the current device, or nullptr (then the caller stages through device memory as before)
 PinnedBuf *pinned_buffer()
@@ -97,6 +97,96 @@ PinnedBuf *pinned_buffer()
 	if (hipHostGetDevicePointer(&d, h, 0) != hipSuccess) { (void)hipGetLastError(); (void)hipHostFree(h); return nullptr; }
 	b.host = (char *)h; b.dev = (char *)d;
 	return &b;
+}
+
+// Where the parts of a host call lie in the pinned buffer: the running sum of up256(bytes), in declaration order.  The same
+// numbers decide the route (fits) and give the pointers (off); nothing else computes an offset.
+constexpr int MAX_PARTS = 4;
+struct Layout { size_t off[MAX_PARTS]; size_t total; };
+constexpr Layout layout_of(size_t b0, size_t b1 = 0, size_t b2 = 0, size_t b3 = 0)
+{
+	const size_t o1 = up256(b0), o2 = o1 + up256(b1), o3 = o2 + up256(b2);
+	return Layout{{0, o1, o2, o3}, o3 + up256(b3)};
+}
+constexpr bool fits(const Layout &l) { return l.total <= ZERO_COPY_MAX; }
+
+// multi_rotate of one 20-byte state: states, actions, out
+static_assert(layout_of(20, 1, 20).off[0] == 0 && layout_of(20, 1, 20).off[1] == 256 && layout_of(20, 1, 20).off[2] == 512, "layout");
+static_assert(layout_of(20, 1, 20).total == 768 && layout_of(256, 257).off[2] == 768 && layout_of(0, 20).off[1] == 0, "layout");
+static_assert(layout_of(ZERO_COPY_MAX - 512, 256, 256).total == ZERO_COPY_MAX && fits(layout_of(ZERO_COPY_MAX - 512, 256, 256)), "limit fits");
+static_assert(layout_of(ZERO_COPY_MAX - 512, 256, 257).total == ZERO_COPY_MAX + 256 && !fits(layout_of(ZERO_COPY_MAX - 512, 256, 257)), "one step more does not");
+
+const long long STATS_INIT[2] = {0, LLONG_MAX};
+
+// One *_host call: the entry declares its arrays in order (in: host bytes the kernel reads; out: bytes the kernel writes, copied
+// back when the host pointer is given -- the device part exists either way), calls begin(), launches on dev(k), returns finish().
+//   zero-copy  when the entry allows it, the layout fits ZERO_COPY_MAX and this thread has its pinned buffer: the inputs are
+//              memcpy'd to their offsets, the kernel works on the buffer over the bus, finish() synchronises once and memcpy's
+//              the wanted outputs out
+//   staged     otherwise: one scratch slot per part, hipMemcpyAsync in, the launch, hipMemcpyAsync of the wanted outputs, one
+//              synchronise
+// finish() synchronises on either route, also when the entry's own output is a device pointer: the pinned buffer and the slots
+// belong to this thread's next call from then on.
+// The counters (how many solved, the first one's index) are atomics, so they stay in device memory: an entry whose caller wants
+// them does not allow zero-copy, and on that route stats() is null.  On the staged route begin(.., got) seeds one more part from
+// STATS_INIT and finish() reads the two raw words back into got; what the caller sees of them is the entry's business.
+struct HostCall {
+	struct Part { const void *in; void *out; size_t bytes; char *dev, *pinned; };
+	Part part[MAX_PARTS] = {};
+	int count = 0;
+	hipStream_t st;
+	bool zero_copy = false;
+	void *d_stats = nullptr;
+
+	explicit HostCall(void *stream) : st((hipStream_t)stream) {}
+	HostCall &in(const void *h, size_t bytes) { part[count++] = Part{h, nullptr, bytes, nullptr, nullptr}; return *this; }
+	HostCall &out(void *h, size_t bytes) { part[count++] = Part{nullptr, h, bytes, nullptr, nullptr}; return *this; }
+	void *dev(int k) const { return part[k].dev; }
+	long long *stats() const { return (long long *)d_stats; }
+
+	int begin(bool allow_zero_copy, long long *got = nullptr)
+	{
+		const Layout l = layout_of(part[0].bytes, part[1].bytes, part[2].bytes, part[3].bytes);
+		PinnedBuf *b = allow_zero_copy && fits(l) ? pinned_buffer() : nullptr;
+		if (b) {
+			zero_copy = true;
+			for (Part *p = part; p < part + count; p++) {
+				p->dev = b->dev + l.off[p - part];
+				p->pinned = b->host + l.off[p - part];
+				if (p->in && p->bytes) memcpy(p->pinned, p->in, p->bytes);
+			}
+			return RK_OK;
+		}
+		if (got) part[count++] = Part{STATS_INIT, got, sizeof STATS_INIT, nullptr, nullptr};
+		ScratchScope scope;                          // slots in declaration order: a thread's cached slot sizes stay matched
+		for (Part *p = part; p < part + count; p++) {
+			DevBuf d;
+			if (int e = d.alloc(p->bytes)) return e;
+			p->dev = (char *)d.p;
+		}
+		if (got) d_stats = part[count - 1].dev;
+		for (Part *p = part; p < part + count; p++)
+			if (p->in && p->bytes) RK_HIP(hipMemcpyAsync(p->dev, p->in, p->bytes, hipMemcpyHostToDevice, st));
+		return RK_OK;
+	}
+
+	int finish()
+	{
+		if (zero_copy) RK_HIP(hipStreamSynchronize(st));
+		for (Part *p = part; p < part + count; p++) {
+			if (!p->out || !p->bytes) continue;
+			if (zero_copy) memcpy(p->out, p->pinned, p->bytes);
+			else RK_HIP(hipMemcpyAsync(p->out, p->dev, p->bytes, hipMemcpyDeviceToHost, st));
+		}
+		if (!zero_copy) RK_HIP(hipStreamSynchronize(st));
+		return RK_OK;
+	}
+};
+
+// what expand12 and is_solved report: {how many solved, the first one's index or -1}
+inline void solved_stats(long long *h_stats, const long long got[2])
+{
+	if (h_stats) { h_stats[0] = got[0]; h_stats[1] = got[0] ? got[1] : -1; }
 }
 
 }  // namespace
@@ -463,7 +553,7 @@ int rk_686_to2024(const int8_t *d_states686, int8_t *d_out20, long long *d_stats
 
 // ---- host-pointer conveniences ------------------------------------------------------------------------------
 
-static const long long STATS_INIT[2] = {0, LLONG_MAX};
+// Each one: its checks, its parts in order, one launch on the parts' device pointers, its counter mapping (see HostCall).
 
 int rk_multi_rotate_host(int repr, const int8_t *h_states, const uint8_t *h_actions, int8_t *h_out, size_t n, void *stream)
 {
@@ -473,29 +563,11 @@ int rk_multi_rotate_host(int repr, const int8_t *h_states, const uint8_t *h_acti
 	for (size_t i = 0; i < n; i++)
 		if (h_actions[i] >= N_ACTIONS) return fail(RK_EINVAL, "rk_multi_rotate_host: action %u at row %zu out of range", h_actions[i], i);
 	const size_t sb = (size_t)state_bytes(repr);
-	hipStream_t st = (hipStream_t)stream;
-	if (up256(n * sb) * 2 + up256(n) <= ZERO_COPY_MAX) {
-		if (PinnedBuf *b = pinned_buffer()) {                 // zero-copy: see ZERO_COPY_MAX
-			const size_t o_act = up256(n * sb), o_out = o_act + up256(n);
-			memcpy(b->host, h_states, n * sb);
-			memcpy(b->host + o_act, h_actions, n);
-			if (int e = rk_multi_rotate(repr, (const int8_t *)b->dev, (const uint8_t *)(b->dev + o_act), (int8_t *)(b->dev + o_out), n, stream)) return e;
-			RK_HIP(hipStreamSynchronize(st));
-			memcpy(h_out, b->host + o_out, n * sb);
-			return RK_OK;
-		}
-	}
-	ScratchScope scope;
-	DevBuf in, act, out;
-	if (int e = in.alloc(n * sb)) return e;
-	if (int e = act.alloc(n)) return e;
-	if (int e = out.alloc(n * sb)) return e;
-	RK_HIP(hipMemcpyAsync(in.p, h_states, n * sb, hipMemcpyHostToDevice, st));
-	RK_HIP(hipMemcpyAsync(act.p, h_actions, n, hipMemcpyHostToDevice, st));
-	if (int e = rk_multi_rotate(repr, (const int8_t *)in.p, (const uint8_t *)act.p, (int8_t *)out.p, n, stream)) return e;
-	RK_HIP(hipMemcpyAsync(h_out, out.p, n * sb, hipMemcpyDeviceToHost, st));
-	RK_HIP(hipStreamSynchronize(st));
-	return RK_OK;
+	HostCall c(stream);
+	c.in(h_states, n * sb).in(h_actions, n).out(h_out, n * sb);
+	if (int e = c.begin(true)) return e;
+	if (int e = rk_multi_rotate(repr, (const int8_t *)c.dev(0), (const uint8_t *)c.dev(1), (int8_t *)c.dev(2), n, stream)) return e;
+	return c.finish();
 }
 
 int rk_expand12_host(int repr, const int8_t *h_parents, int8_t *h_children, uint8_t *h_solved, long long *h_stats, size_t n,
@@ -506,33 +578,14 @@ int rk_expand12_host(int repr, const int8_t *h_parents, int8_t *h_children, uint
 	if (n == 0) return RK_OK;
 	if (!h_parents || !h_children) return fail(RK_EINVAL, "rk_expand12_host: null pointer");
 	const size_t sb = (size_t)state_bytes(repr);
-	hipStream_t st = (hipStream_t)stream;
-	if (!h_stats && up256(n * sb) + up256(12 * n * sb) + up256(12 * n) <= ZERO_COPY_MAX) {     // (the counters are atomics: they stay in device memory)
-		if (PinnedBuf *b = pinned_buffer()) {                 // zero-copy: see ZERO_COPY_MAX
-			const size_t o_ch = up256(n * sb), o_fl = o_ch + up256(12 * n * sb);
-			memcpy(b->host, h_parents, n * sb);
-			if (int e = rk_expand12(repr, (const int8_t *)b->dev, (int8_t *)(b->dev + o_ch), h_solved ? (uint8_t *)(b->dev + o_fl) : nullptr, nullptr, n, stream)) return e;
-			RK_HIP(hipStreamSynchronize(st));
-			memcpy(h_children, b->host + o_ch, 12 * n * sb);
-			if (h_solved) memcpy(h_solved, b->host + o_fl, 12 * n);
-			return RK_OK;
-		}
-	}
-	ScratchScope scope;
-	DevBuf in, ch, fl, stt;
-	if (int e = in.alloc(n * sb)) return e;
-	if (int e = ch.alloc(12 * n * sb)) return e;
-	if (int e = fl.alloc(12 * n)) return e;
-	if (int e = stt.alloc(sizeof STATS_INIT)) return e;
-	RK_HIP(hipMemcpyAsync(in.p, h_parents, n * sb, hipMemcpyHostToDevice, st));
-	RK_HIP(hipMemcpyAsync(stt.p, STATS_INIT, sizeof STATS_INIT, hipMemcpyHostToDevice, st));
-	if (int e = rk_expand12(repr, (const int8_t *)in.p, (int8_t *)ch.p, (uint8_t *)fl.p, (long long *)stt.p, n, stream)) return e;
-	RK_HIP(hipMemcpyAsync(h_children, ch.p, 12 * n * sb, hipMemcpyDeviceToHost, st));
-	if (h_solved) RK_HIP(hipMemcpyAsync(h_solved, fl.p, 12 * n, hipMemcpyDeviceToHost, st));
-	long long stats[2];
-	RK_HIP(hipMemcpyAsync(stats, stt.p, sizeof stats, hipMemcpyDeviceToHost, st));
-	RK_HIP(hipStreamSynchronize(st));
-	if (h_stats) { h_stats[0] = stats[0]; h_stats[1] = stats[0] ? stats[1] : -1; }
+	long long got[2];
+	HostCall c(stream);
+	c.in(h_parents, n * sb).out(h_children, 12 * n * sb).out(h_solved, 12 * n);
+	if (int e = c.begin(!h_stats, got)) return e;
+	uint8_t *d_solved = h_solved || c.stats() ? (uint8_t *)c.dev(2) : nullptr;     // the counters need the flags
+	if (int e = rk_expand12(repr, (const int8_t *)c.dev(0), (int8_t *)c.dev(1), d_solved, c.stats(), n, stream)) return e;
+	if (int e = c.finish()) return e;
+	solved_stats(h_stats, got);
 	return RK_OK;
 }
 
@@ -542,33 +595,13 @@ int rk_multi_is_solved_host(int repr, const int8_t *h_states, uint8_t *h_flags, 
 	if (h_stats) { h_stats[0] = 0; h_stats[1] = -1; }
 	if (n == 0) return RK_OK;
 	if (!h_states) return fail(RK_EINVAL, "rk_multi_is_solved_host: null pointer");
-	const size_t sb = (size_t)state_bytes(repr);
-	hipStream_t st = (hipStream_t)stream;
-	if (!h_stats && up256(n * sb) + up256(n) <= ZERO_COPY_MAX) {     // (the counters are atomics: they stay in device memory)
-		if (PinnedBuf *b = pinned_buffer()) {                 // zero-copy: see ZERO_COPY_MAX
-			const size_t o_fl = up256(n * sb);
-			memcpy(b->host, h_states, n * sb);
-			if (int e = rk_multi_is_solved(repr, (const int8_t *)b->dev, (uint8_t *)(b->dev + o_fl), nullptr, n, stream)) return e;
-			RK_HIP(hipStreamSynchronize(st));
-			if (h_flags) memcpy(h_flags, b->host + o_fl, n);
-			return RK_OK;
-		}
-	}
-	ScratchScope scope;
-	DevBuf in, fl, stt;
-	if (int e = in.alloc(n * sb)) return e;
-	if (int e = fl.alloc(n)) return e;
-	RK_HIP(hipMemcpyAsync(in.p, h_states, n * sb, hipMemcpyHostToDevice, st));
-	if (h_stats) {                                   // the counters cost two extra copies: only when asked for
-		if (int e = stt.alloc(sizeof STATS_INIT)) return e;
-		RK_HIP(hipMemcpyAsync(stt.p, STATS_INIT, sizeof STATS_INIT, hipMemcpyHostToDevice, st));
-	}
-	if (int e = rk_multi_is_solved(repr, (const int8_t *)in.p, (uint8_t *)fl.p, (long long *)stt.p, n, stream)) return e;
-	if (h_flags) RK_HIP(hipMemcpyAsync(h_flags, fl.p, n, hipMemcpyDeviceToHost, st));
-	long long stats[2] = {0, 0};
-	if (h_stats) RK_HIP(hipMemcpyAsync(stats, stt.p, sizeof stats, hipMemcpyDeviceToHost, st));
-	RK_HIP(hipStreamSynchronize(st));
-	if (h_stats) { h_stats[0] = stats[0]; h_stats[1] = stats[0] ? stats[1] : -1; }
+	long long got[2];
+	HostCall c(stream);
+	c.in(h_states, n * (size_t)state_bytes(repr)).out(h_flags, n);
+	if (int e = c.begin(!h_stats, h_stats ? got : nullptr)) return e;      // the counters cost two extra copies: only when asked for
+	if (int e = rk_multi_is_solved(repr, (const int8_t *)c.dev(0), (uint8_t *)c.dev(1), c.stats(), n, stream)) return e;
+	if (int e = c.finish()) return e;
+	solved_stats(h_stats, got);
 	return RK_OK;
 }
 
@@ -587,27 +620,11 @@ int rk_apply_sequences_host(int repr, const uint8_t *h_actions, int depth, int g
 	const size_t nact = (size_t)moves * games;
 	for (size_t i = 0; i < nact; i++)
 		if (h_actions[i] >= N_ACTIONS) return fail(RK_EINVAL, "rk_apply_sequences_host: action %u out of range", h_actions[i]);
-	hipStream_t st = (hipStream_t)stream;
-	const size_t out_bytes = (size_t)games * rows * STATE_BYTES;
-	if (up256(nact) + up256(out_bytes) <= ZERO_COPY_MAX) {
-		if (PinnedBuf *b = pinned_buffer()) {                 // zero-copy: see ZERO_COPY_MAX
-			const size_t o_out = up256(nact);
-			if (nact) memcpy(b->host, h_actions, nact);
-			if (int e = rk_apply_sequences(repr, (const uint8_t *)b->dev, depth, games, with_solved, only_last, (int8_t *)(b->dev + o_out), stream)) return e;
-			RK_HIP(hipStreamSynchronize(st));
-			memcpy(h_out, b->host + o_out, out_bytes);
-			return RK_OK;
-		}
-	}
-	ScratchScope scope;
-	DevBuf act, out;
-	if (int e = act.alloc(nact)) return e;
-	if (int e = out.alloc((size_t)games * rows * STATE_BYTES)) return e;
-	if (nact) RK_HIP(hipMemcpyAsync(act.p, h_actions, nact, hipMemcpyHostToDevice, st));
-	if (int e = rk_apply_sequences(repr, (const uint8_t *)act.p, depth, games, with_solved, only_last, (int8_t *)out.p, stream)) return e;
-	RK_HIP(hipMemcpyAsync(h_out, out.p, (size_t)games * rows * STATE_BYTES, hipMemcpyDeviceToHost, st));
-	RK_HIP(hipStreamSynchronize(st));
-	return RK_OK;
+	HostCall c(stream);
+	c.in(h_actions, nact).out(h_out, (size_t)games * rows * STATE_BYTES);      // no moves: an empty part, nothing is copied
+	if (int e = c.begin(true)) return e;
+	if (int e = rk_apply_sequences(repr, (const uint8_t *)c.dev(0), depth, games, with_solved, only_last, (int8_t *)c.dev(1), stream)) return e;
+	return c.finish();
 }
 
 int rk_as_oh_host(int repr, const int8_t *h_states, void *d_out, int out_dtype, size_t n, void *stream)
@@ -615,23 +632,11 @@ int rk_as_oh_host(int repr, const int8_t *h_states, void *d_out, int out_dtype, 
 	if (int e = check_repr(repr)) return e;
 	if (n == 0) return RK_OK;
 	if (!h_states || !d_out) return fail(RK_EINVAL, "rk_as_oh_host: null pointer");
-	const size_t sb = (size_t)state_bytes(repr);
-	hipStream_t st = (hipStream_t)stream;
-	if (up256(n * sb) <= ZERO_COPY_MAX) {
-		if (PinnedBuf *b = pinned_buffer()) {                 // zero-copy: see ZERO_COPY_MAX
-			memcpy(b->host, h_states, n * sb);
-			if (int e = rk_as_oh(repr, (const int8_t *)b->dev, d_out, out_dtype, n, stream)) return e;
-			RK_HIP(hipStreamSynchronize(st));                 // the buffer belongs to the next call from here on
-			return RK_OK;
-		}
-	}
-	ScratchScope scope;
-	DevBuf in;
-	if (int e = in.alloc(n * sb)) return e;
-	RK_HIP(hipMemcpyAsync(in.p, h_states, n * sb, hipMemcpyHostToDevice, st));
-	if (int e = rk_as_oh(repr, (const int8_t *)in.p, d_out, out_dtype, n, stream)) return e;
-	RK_HIP(hipStreamSynchronize(st));
-	return RK_OK;
+	HostCall c(stream);
+	c.in(h_states, n * (size_t)state_bytes(repr));
+	if (int e = c.begin(true)) return e;
+	if (int e = rk_as_oh(repr, (const int8_t *)c.dev(0), d_out, out_dtype, n, stream)) return e;
+	return c.finish();
 }
 
 int rk_oh686_from2024_host(const int8_t *h_states20, void *d_out, int out_dtype, size_t n, void *stream)
@@ -641,42 +646,24 @@ int rk_oh686_from2024_host(const int8_t *h_states20, void *d_out, int out_dtype,
 	if (n == 0) return RK_OK;
 	if (!h_states20 || !d_out) return fail(RK_EINVAL, "rk_oh686_from2024_host: null pointer");
 	if (misaligned(d_out, 16)) return fail(RK_EINVAL, "rk_oh686_from2024_host: output must be 16-byte aligned");
-	hipStream_t st = (hipStream_t)stream;
-	if (up256(n * STATE_BYTES) <= ZERO_COPY_MAX) {
-		if (PinnedBuf *b = pinned_buffer()) {                 // zero-copy: see ZERO_COPY_MAX
-			memcpy(b->host, h_states20, n * STATE_BYTES);
-			if (int e = rk_oh686_from2024((const int8_t *)b->dev, d_out, out_dtype, n, stream)) return e;
-			RK_HIP(hipStreamSynchronize(st));                 // the buffer belongs to the next call from here on
-			return RK_OK;
-		}
-	}
-	ScratchScope scope;
-	DevBuf in;
-	if (int e = in.alloc(n * STATE_BYTES)) return e;
-	RK_HIP(hipMemcpyAsync(in.p, h_states20, n * STATE_BYTES, hipMemcpyHostToDevice, st));
-	if (int e = rk_oh686_from2024((const int8_t *)in.p, d_out, out_dtype, n, stream)) return e;
-	RK_HIP(hipStreamSynchronize(st));
-	return RK_OK;
+	HostCall c(stream);
+	c.in(h_states20, n * STATE_BYTES);
+	if (int e = c.begin(true)) return e;
+	if (int e = rk_oh686_from2024((const int8_t *)c.dev(0), d_out, out_dtype, n, stream)) return e;
+	return c.finish();
 }
 
 int rk_686_to2024_host(const int8_t *h_states686, int8_t *h_out20, long long *h_stats, size_t n, void *stream)
 {
 	if (n == 0) return RK_OK;
 	if (!h_states686 || !h_out20) return fail(RK_EINVAL, "rk_686_to2024_host: null pointer");
-	hipStream_t st = (hipStream_t)stream;
-	ScratchScope scope;
-	DevBuf in, out, stats;
-	if (int e = in.alloc(n * S686_BYTES)) return e;
-	if (int e = out.alloc(n * STATE_BYTES)) return e;
-	if (int e = stats.alloc(sizeof STATS_INIT)) return e;
-	RK_HIP(hipMemcpyAsync(in.p, h_states686, n * S686_BYTES, hipMemcpyHostToDevice, st));
-	RK_HIP(hipMemcpyAsync(stats.p, STATS_INIT, sizeof STATS_INIT, hipMemcpyHostToDevice, st));
-	if (int e = rk_686_to2024((const int8_t *)in.p, (int8_t *)out.p, (long long *)stats.p, n, stream)) return e;
-	RK_HIP(hipMemcpyAsync(h_out20, out.p, n * STATE_BYTES, hipMemcpyDeviceToHost, st));
-	long long got[2] = {0, LLONG_MAX};
-	RK_HIP(hipMemcpyAsync(got, stats.p, sizeof got, hipMemcpyDeviceToHost, st));
-	RK_HIP(hipStreamSynchronize(st));
-	if (h_stats) { h_stats[0] = got[0]; h_stats[1] = got[1]; }
+	long long got[2];
+	HostCall c(stream);
+	c.in(h_states686, n * S686_BYTES).out(h_out20, n * STATE_BYTES);
+	if (int e = c.begin(false, got)) return e;       // always staged: it always counts (illegal rows, the first one's index)
+	if (int e = rk_686_to2024((const int8_t *)c.dev(0), (int8_t *)c.dev(1), c.stats(), n, stream)) return e;
+	if (int e = c.finish()) return e;
+	if (h_stats) { h_stats[0] = got[0]; h_stats[1] = got[1]; }       // the raw words
 	return RK_OK;
 }
 

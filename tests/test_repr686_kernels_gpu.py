@@ -22,7 +22,7 @@ import pytest
 import torch
 
 from librubiks_amd import _ffi, cube
-from oracle import cube_oracle as orc
+from oracle import c_oracle, cube_oracle as orc
 from tests import repr686_pairs as pairs
 
 pytestmark = pytest.mark.gpu
@@ -420,3 +420,178 @@ def test_host_entries_on_both_sides_of_the_zero_copy_limit():
 	bad[TILE] = pairs.make_illegal(bad[TILE], "edge_twice")
 	with pytest.raises(ValueError, match=rf"first is row {TILE}\)"):
 		cube.as2024(bad)
+
+
+# Every rk_*_host entry at the exact edge of ITS layout.  A host call lays its arrays out at 256-byte steps in declaration order;
+# while the total fits ZERO_COPY_MAX it goes through the page-locked buffer, one row more goes through device scratch.  The
+# totals below are the layouts of rk_api.hip (its static_asserts pin the arithmetic); the tests assert results only.
+def _up256(b: int) -> int:
+	return (b + 255) // 256 * 256
+
+
+def _largest_fit(total) -> int:
+	"""The largest n whose layout `total(n)` (nondecreasing) fits ZERO_COPY_MAX."""
+	limit = _zero_copy_max()
+	lo, hi = 1, limit
+	assert total(lo) <= limit < total(hi)
+	while hi - lo > 1:
+		mid = (lo + hi) // 2
+		lo, hi = (mid, hi) if total(mid) <= limit else (lo, mid)
+	assert total(lo) <= limit < total(lo + 1), (lo, total(lo), total(lo + 1))
+	return lo
+
+
+def _ptr(a):
+	return None if a is None else a.ctypes.data
+
+
+def _put(row: int, state):
+	"""An edit of gather()'s 20-byte rows: `state` at `row`."""
+	def edit(s20):
+		s20[row] = state
+	return edit
+
+
+def _run_multi_rotate(repr_, n):
+	_, s20, s686 = pairs.gather(n, n)
+	s = s686 if repr_ else s20
+	acts = np.random.RandomState(n).randint(0, 12, n).astype(np.uint8)
+	out = np.full_like(s, SENTINEL)
+	_ffi.check(_ffi.lib().rk_multi_rotate_host(repr_, _ptr(s), _ptr(acts), _ptr(out), n, None))
+	assert np.array_equal(out, c_oracle.multi_rotate686(s, acts) if repr_ else c_oracle.multi_rotate(s, acts)), n
+
+
+def _run_expand12(n, flags=True, counters=False, edit=None):
+	_, s20, _ = pairs.gather(n, n)
+	if edit:
+		edit(s20)
+	want_ch, want_fl = c_oracle.expand12(s20)
+	ch, fl, st = np.full((12 * n, 20), SENTINEL, np.int8), np.full(12 * n, SENTINEL, np.uint8), np.full(2, 7, np.int64)
+	_ffi.check(_ffi.lib().rk_expand12_host(0, _ptr(s20), _ptr(ch), _ptr(fl if flags else None), _ptr(st if counters else None), n, None))
+	assert np.array_equal(ch, want_ch), n
+	assert np.array_equal(fl, want_fl) if flags else (fl == SENTINEL).all(), n          # the guard: not passed, not written
+	assert st.tolist() == ([int(want_fl.sum()), int(np.argmax(want_fl)) if want_fl.any() else -1] if counters else [7, 7]), n
+	return st.tolist()
+
+
+def _run_is_solved(n, flags=True, counters=False, edit=None):
+	_, s20, _ = pairs.gather(n, n)
+	if edit:
+		edit(s20)
+	want = orc.multi_is_solved(s20)
+	fl, st = np.full(n, SENTINEL, np.uint8), np.full(2, 7, np.int64)
+	_ffi.check(_ffi.lib().rk_multi_is_solved_host(0, _ptr(s20), _ptr(fl if flags else None), _ptr(st if counters else None), n, None))
+	assert np.array_equal(fl.astype(bool), want) and fl.max() <= 1 if flags else (fl == SENTINEL).all(), n
+	assert st.tolist() == ([int(want.sum()), int(np.argmax(want)) if want.any() else -1] if counters else [7, 7]), n
+	return st.tolist()
+
+
+SEQ_DEPTH = 6
+
+
+def _run_apply_sequences(games):
+	seq = np.random.RandomState(games).randint(0, 12, (SEQ_DEPTH, games)).astype(np.uint8)
+	got = np.full((games * SEQ_DEPTH, 20), SENTINEL, np.int8)
+	_ffi.check(_ffi.lib().rk_apply_sequences_host(0, _ptr(seq), SEQ_DEPTH, games, 0, 0, _ptr(got), None))
+	assert np.array_equal(got, orc.sequence_states(seq // 2, 1 - seq % 2, False)), games
+
+
+def _run_as_oh(repr_, n):
+	_, s20, s686 = pairs.gather(n, n)
+	oh = torch.full((n, 288 if repr_ else 480), float(SENTINEL), dtype=torch.float32, device="cuda")
+	_ffi.check(_ffi.lib().rk_as_oh_host(repr_, _ptr(s686 if repr_ else s20), oh.data_ptr(), _ffi.OH_F32, n, None))
+	assert np.array_equal(oh.cpu().numpy(), orc.as_oh686(s686) if repr_ else c_oracle.as_oh(s20)), n
+
+
+def _run_oh686_from2024(n):
+	_, s20, s686 = pairs.gather(n, n)
+	oh = torch.full((n, 288), float(SENTINEL), dtype=torch.float32, device="cuda")
+	_ffi.check(_ffi.lib().rk_oh686_from2024_host(_ptr(s20), oh.data_ptr(), _ffi.OH_F32, n, None))
+	assert np.array_equal(oh.cpu().numpy(), orc.as_oh686(s686)), n
+
+
+def _run_686_to2024(n):
+	_, s20, s686 = pairs.gather(n, n)
+	out, st = np.full((n, 20), SENTINEL, np.int8), np.full(2, 7, np.int64)
+	_ffi.check(_ffi.lib().rk_686_to2024_host(_ptr(s686), _ptr(out), _ptr(st), n, None))
+	assert np.array_equal(out, s20) and st.tolist() == [0, _ffi.INT64_MAX], n             # the raw counters: no illegal row
+
+
+#: entry -> (its layout's total bytes at n rows, the call checked against the oracle at n rows)
+HOST_ENTRIES = {
+	"multi_rotate-2024": (lambda n: 2 * _up256(20 * n) + _up256(n), lambda n: _run_multi_rotate(0, n)),
+	"multi_rotate-686": (lambda n: 2 * _up256(288 * n) + _up256(n), lambda n: _run_multi_rotate(1, n)),
+	"expand12": (lambda n: _up256(20 * n) + _up256(240 * n) + _up256(12 * n), _run_expand12),
+	"multi_is_solved": (lambda n: _up256(20 * n) + _up256(n), _run_is_solved),
+	"apply_sequences": (lambda g: _up256(SEQ_DEPTH * g) + _up256(g * SEQ_DEPTH * 20), _run_apply_sequences),
+	"as_oh-2024": (lambda n: _up256(20 * n), lambda n: _run_as_oh(0, n)),
+	"as_oh-686": (lambda n: _up256(288 * n), lambda n: _run_as_oh(1, n)),
+	"oh686_from2024": (lambda n: _up256(20 * n), _run_oh686_from2024),
+	"686_to2024": (lambda n: _up256(288 * n) + _up256(20 * n), _run_686_to2024),        # always staged (it counts): same results at both
+}
+
+
+@pytest.mark.parametrize("entry", list(HOST_ENTRIES))
+def test_every_host_entry_at_its_own_zero_copy_limit(entry):
+	"""The largest call that fits the page-locked buffer and the one a row (a game) larger, byte for byte against the oracle."""
+	total, run = HOST_ENTRIES[entry]
+	fit = _largest_fit(total)
+	for n in (fit, fit + 1):
+		run(n)
+
+
+@pytest.mark.parametrize("entry", ["expand12", "multi_is_solved"])
+def test_host_counters_and_null_flags_at_the_zero_copy_limit(entry):
+	"""With the counters (always through device memory) and without the flag output, at the same two sizes: `[1, index]` with one
+	solved row (one solved child) at a known index, `[0, -1]` with none; flags that are not asked for are not written."""
+	total, run = HOST_ENTRIES[entry]
+	fit = _largest_fit(total)
+	for n in (fit, fit + 1):
+		row = n - 3
+		if entry == "expand12":                         # one quarter turn from solved: of its 12 children, the one by the opposite turn
+			edit, index = _put(row, orc.rotate(orc.SOLVED, 4, 0)), 12 * row + 8
+		else:
+			edit, index = _put(row, orc.SOLVED), row
+		assert run(n, counters=True) == [0, -1]
+		assert run(n, counters=True, edit=edit) == [1, index]
+		assert run(n, flags=False, counters=True, edit=edit) == [1, index]
+		run(n, flags=False)
+
+
+def test_host_entries_in_any_order_share_the_buffer_and_the_slots():
+	"""The pinned buffer and the cached scratch slots are per thread and shared by all entries: a large staged call, a small
+	zero-copy one, a large call of another entry (other slot sizes), and back -- each against the oracle."""
+	above = {e: _largest_fit(HOST_ENTRIES[e][0]) + 1 for e in ("multi_rotate-2024", "expand12", "multi_is_solved", "as_oh-686")}
+	_run_multi_rotate(0, above["multi_rotate-2024"])
+	_run_is_solved(12)
+	_run_expand12(above["expand12"])
+	_run_multi_rotate(0, 1)
+	_run_is_solved(above["multi_is_solved"], counters=True, edit=_put(5, orc.SOLVED))
+	_run_expand12(1, flags=False)
+	_run_as_oh(1, above["as_oh-686"])
+	_run_apply_sequences(3)
+	_run_686_to2024(above["expand12"])
+	_run_multi_rotate(1, 7)
+
+
+def test_host_entries_with_nothing_to_do_and_with_null_pointers():
+	"""n = 0 returns 0 before any pointer is looked at; a null array with n > 0 is refused with -1."""
+	lib = _ffi.lib()
+	_, s20, s686 = pairs.gather(3, 3)
+	acts, out20, out686 = np.zeros(SEQ_DEPTH * 3, np.uint8), np.empty((SEQ_DEPTH * 3, 20), np.int8), np.empty_like(s686)
+	ch, st = np.empty((36, 20), np.int8), np.zeros(2, np.int64)
+	oh = torch.empty((3, 480), dtype=torch.float32, device="cuda")
+	for n, a, b, want in ((0, None, None, 0), (3, None, _ptr(out20), -1), (3, _ptr(s20), None, -1)):
+		assert lib.rk_multi_rotate_host(0, a, _ptr(acts), b, n, None) == want
+		assert lib.rk_multi_rotate_host(1, a and _ptr(s686), _ptr(acts), b and _ptr(out686), n, None) == want
+		assert lib.rk_expand12_host(0, a, b and _ptr(ch), None, None, n, None) == want
+		assert lib.rk_apply_sequences_host(0, a and _ptr(acts), SEQ_DEPTH, n, 0, 0, b, None) == want
+		assert lib.rk_as_oh_host(0, a, b and oh.data_ptr(), _ffi.OH_F32, n, None) == want
+		assert lib.rk_oh686_from2024_host(a, b and oh.data_ptr(), _ffi.OH_F32, n, None) == want
+		assert lib.rk_686_to2024_host(a and _ptr(s686), b, None, n, None) == want
+	assert lib.rk_multi_rotate_host(0, _ptr(s20), None, _ptr(out20), 3, None) == -1
+	assert lib.rk_multi_is_solved_host(0, None, None, None, 0, None) == 0 and lib.rk_multi_is_solved_host(0, None, None, None, 3, None) == -1
+	st[:] = 7
+	assert lib.rk_multi_is_solved_host(0, None, None, _ptr(st), 0, None) == 0 and st.tolist() == [0, -1]     # the counters of an empty call
+	st[:] = 7
+	assert lib.rk_expand12_host(0, None, None, None, _ptr(st), 0, None) == 0 and st.tolist() == [0, -1]
