@@ -605,6 +605,50 @@ int rk_pdb_depth(rk_pdb_t *h, const int8_t *d_states, size_t n, int32_t *d_depth
  * that passed its build). */
 int rk_pdb_solve(rk_pdb_t *h, const int8_t *d_states, size_t n, int32_t *d_lengths, int8_t *d_actions, int32_t *d_error, void *stream);
 
+/* ---- the subgroup chain: a solution for every legal state (rk_chain_*) ---------------------------------------------------------
+ * Four stages, each with a table of one byte per coset: the cost of the cheapest word of the stage's generators that brings a
+ * state of that coset into the next subgroup.  A generator is a quarter turn (cost 1) or the half turn XX = the action 2 f twice
+ * (cost 2); generators are ordered by their first action.  position = code / 3 (edges / 2), digit = code % 3 (% 2); slice s = the
+ * four edges that neither face of an axis moves: 0 the axis F B, 1 the axis T D, 2 the axis L R (all read off the move table).
+ *     stage  generators                  goal                                        THE INDEX                                   size
+ *     1      the 12 quarter turns        every edge digit 0                          sum over positions p = 0..10 of             2^11
+ *                                                                                    (digit of the edge AT p) << p
+ *     2      F F' B B' TT DD L L' R R'   every corner digit 0, slice 0 on its        (sum over p = 0..6 of (digit of the corner  3^7 * 495
+ *                                        positions                                   AT p) 3^p) * 495 + subset(positions of
+ *                                                                                    slice 0's edges)
+ *     3      F F' B B' TT DD LL RR       in the group of the six half turns          coset(P) * 70 + subset(positions of slice   420 * 70
+ *                                                                                    1's edges, counted among the eight
+ *                                                                                    positions outside slice 0)
+ *     4      FF BB TT DD LL RR           solved                                      ((c3(P) * 24 + q_0) * 24 + q_1) * 24 + q_2  96 * 24^3
+ * subset(S) = the ordinal of a set of four among the 4-subsets ordered by the largest element, then the next: the sum of
+ * C(p_i, i + 1) over its elements ascending.  P = (position of corner cubie 0, .., 7); C3 = the 96 such sequences the half turns
+ * reach from solved; coset(P) = the ordinal of the class {P o h, h in C3} by its lexicographically least member (420 classes);
+ * c3(P) = the ordinal of P in C3, lexicographic; q_s = the lexicographic ordinal of (place of slice s's i-th edge within slice
+ * s's positions, i = 0..3).  The tables reach exactly 2 048, 1 082 565, 29 400 and 663 552 entries; the rest stay 255.
+ * A solution is four descents: per step the LOWEST generator whose entry equals the current entry minus its cost.  It is not
+ * optimal; rk_ball_shorten / rk_symball_shorten improve it. */
+#define RK_CHAIN_GRID 2048   /* workgroups of 256 states a solve has at most: beyond RK_CHAIN_GRID * 256 states a thread takes several */
+typedef struct rk_chain rk_chain_t;
+/* Builds the four tables and the two corner maps (coset, c3) on the HOST -- level d + 1 takes the cost-1 children of level d and
+ * the cost-2 children of level d - 1 and stores only over unreached entries -- and uploads them on `stream`.  RK_ESTATE unless C3
+ * has 96 sequences in 420 cosets and every table reaches exactly the count above with one entry 0; RK_ECAPACITY when the device
+ * has no room for the 2.5 MB.  Synchronises. */
+int rk_chain_create(rk_chain_t **out, void *stream);
+int rk_chain_destroy(rk_chain_t *h);
+/* h_status[16] = the four reached counts, the four deepest entries at [4..7], max_length (their sum: the row stride of
+ * rk_chain_solve) at [8], the four table sizes at [9..12].  Touches no device. */
+int rk_chain_status(rk_chain_t *h, long long *h_status);
+/* Entries [first, first+count) of the table of `stage` (1..4) to HOST h_bytes uint8 (count).  Synchronises. */
+int rk_chain_export(rk_chain_t *h, int stage, size_t first, size_t count, uint8_t *h_bytes, void *stream);
+/* ONE launch, a thread per state under a capped grid, stream-ordered without synchronisation; n at most INT32_MAX, n = 0 does
+ * nothing at all; d_states, d_lengths, d_stage_lengths, d_error 4-byte aligned.  Row q of d_states int8 (n, 20): d_lengths[q] =
+ * the length of its solution, whose actions are the first d_lengths[q] bytes of row q of d_actions int8 (n, max_length); the
+ * bytes beyond are NOT written.  d_stage_lengths int32 (n, 4), or NULL: the cost of each stage.  A row that is no legal state
+ * (rk_group_legal's test, made before any table is read) gets length -1, stage lengths -1 and no action.  d_error int32[1], or
+ * NULL: set to -1, then to the lowest row that got -1. */
+int rk_chain_solve(rk_chain_t *h, const int8_t *d_states, size_t n, int32_t *d_lengths, int8_t *d_actions, int32_t *d_stage_lengths,
+                   int32_t *d_error, void *stream);
+
 /* ---- the symmetry-reduced goal ball: one representative per orbit (rk_symball_*) -------------------------------------------
  * The canonical representatives of the states within `radius` quarter turns of solved, built once and kept in HBM; the depth of
  * a representative is the depth of the up to 48 states of its orbit.  Node 1 is the solved state, the pool is in index order: a

@@ -144,6 +144,11 @@ SIGNATURES = {
 	"rk_pdb_export": (_i, [_vp, _sz, _sz, _vp, _vp]),
 	"rk_pdb_depth": (_i, [_vp, _vp, _sz, _vp, _vp]),
 	"rk_pdb_solve": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+	"rk_chain_create": (_i, [C.POINTER(_vp), _vp]),
+	"rk_chain_destroy": (_i, [_vp]),
+	"rk_chain_status": (_i, [_vp, _vp]),
+	"rk_chain_export": (_i, [_vp, _i, _sz, _sz, _vp, _vp]),
+	"rk_chain_solve": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
 	"rk_symball_create": (_i, [C.POINTER(_vp), _i, _i, _sz]),
 	"rk_symball_destroy": (_i, [_vp]),
 	"rk_symball_build": (_i, [_vp, _i, _vp]),

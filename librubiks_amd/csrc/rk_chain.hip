@@ -1,0 +1,562 @@
+// The subgroup chain (rk_chain_*): a solution for EVERY legal state by four table descents -- no search, no pool, no net.
+//
+// Thistlethwaite's four stages restated for the 12 quarter turns.  Stage k may use only the generators that keep what stages 1..k-1
+// reached, a half turn XX (the action 2 f twice, cost 2) where the quarter turn would not; it brings the state into the next
+// subgroup, and its table holds, for every coset of that subgroup, the cost of the cheapest word that does so.  DESIGN 3.59.8 and
+// include/rubiks_hip.h define the signatures and THE INDEX of each table; chain_index below is that definition, one function for
+// the host build and the kernel.  Signatures are taken BY POSITION (the digit of the cubie AT position p, the positions that hold
+// a set of cubies, the corner sequence up to relabelling the cubies by the half-turn group): only then does a move's effect on the
+// signature depend on the signature alone.
+//
+// Everything is read off the move table at compile time (ChainConsts): which faces flip an edge, which take a corner's digit off
+// 0, the three slices (the edges neither face of an axis moves), the generators of every stage.  The corner sequences of the
+// half-turn group (C3, 96 of them) and the coset map (40 320 entries, 420 cosets) come from a closure at create time.
+//
+// The build is on the host: level d + 1 takes the cost-1 children of level d and the cost-2 children of level d - 1 and stores
+// only over "unreached", so a table does not depend on the visiting order; one representative state per coset carries the search.
+// The coset counts 2 048 / 1 082 565 / 29 400 / 663 552 are conditions: any other count is RK_ESTATE.
+//
+// The query is ONE launch, a thread per state under a capped grid, the per-action tables staged in LDS once per workgroup, the
+// state in five dwords.  Per step a thread applies each generator of the stage, forms the child's index, reads one byte and takes
+// the LOWEST generator whose entry equals the current entry minus its cost.  The generator loop is a template recursion: every
+// generator's action and cost are compile-time constants, every loop bound is wave-uniform, nothing is indexed dynamically in
+// registers.  The legality test of rk_group_legal runs before any table access, every table and map read is guarded by its size,
+// and every descent is bounded by the stage's deepest entry.
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <array>
+#include <climits>
+#include <cstring>
+#include <vector>
+
+#include "../../include/rubiks_hip.h"
+#include "rk_device.h"
+#include "rk_error.h"
+#include "rk_group_dev.h"
+#include "rk_search_dev.h"
+
+namespace rk {
+
+constexpr int CHAIN_STAGES = 4;
+constexpr uint32_t CHAIN_UNREACHED = 255;
+constexpr uint32_t CHAIN_PERMS = 40320;             // 8!
+constexpr uint32_t CHAIN_C3 = 96, CHAIN_COSETS = 420;
+constexpr uint32_t CHAIN_SIZE[CHAIN_STAGES] = {2048u, 2187u * 495u, CHAIN_COSETS * 70u, CHAIN_C3 * 13824u};
+constexpr uint32_t CHAIN_COUNT[CHAIN_STAGES] = {2048u, 1082565u, 29400u, 663552u};      // the cosets each build must reach
+
+struct ChainConsts {
+	bool flips[6], twists[6];                       // the face changes an edge's digit / takes a corner's digit off 0
+	uint8_t slice[3][4];                            // the edges neither face of an axis moves, ascending: 0 the axis that keeps both digits,
+	uint16_t slice_mask[3];                         // 1 the axis that flips edges, 2 the third
+	uint8_t outside0[8];                            // the positions outside slice 0, ascending
+	uint8_t gen_action[CHAIN_STAGES][12], gen_cost[CHAIN_STAGES][12];
+	int gen_count[CHAIN_STAGES];
+	bool consistent;
+};
+
+constexpr ChainConsts make_chain_consts()
+{
+	const Tables t = make_tables();
+	ChainConsts c{};
+	c.consistent = true;
+	uint16_t moved[6] = {};
+	for (int f = 0; f < 6; f++) {
+		for (int v = 0; v < 24; v++)
+			if ((t.lut[2 * f][1][v] & 1) != (v & 1)) c.flips[f] = true;
+		for (int q = 0; q < 8; q++)
+			if (t.lut[2 * f][0][3 * q] % 3 != 0) c.twists[f] = true;
+		for (int e = 0; e < 12; e++)
+			if (t.lut[2 * f][1][2 * e] != 2 * e) moved[f] |= (uint16_t)(1u << e);
+	}
+	int found[3] = {0, 0, 0};
+	for (int f = 0; f < 6; f++)
+		for (int g = f + 1; g < 6; g++) {
+			if (moved[f] & moved[g]) continue;
+			if (c.flips[f] != c.flips[g] || c.twists[f] != c.twists[g]) c.consistent = false;
+			const int s = c.flips[f] ? 1 : c.twists[f] ? 2 : 0;
+			found[s]++;
+			c.slice_mask[s] = (uint16_t)(0xFFFu & ~(moved[f] | moved[g]));
+		}
+	for (int s = 0; s < 3; s++) {
+		int k = 0;
+		for (int e = 0; e < 12; e++)
+			if (c.slice_mask[s] >> e & 1) {
+				if (k < 4) c.slice[s][k] = (uint8_t)e;
+				k++;
+			}
+		if (found[s] != 1 || k != 4) c.consistent = false;
+	}
+	if ((c.slice_mask[0] | c.slice_mask[1] | c.slice_mask[2]) != 0xFFFu) c.consistent = false;
+	for (int p = 0, k = 0; p < 12; p++)
+		if (!(c.slice_mask[0] >> p & 1) && k < 8) c.outside0[k++] = (uint8_t)p;
+	for (int stage = 0; stage < CHAIN_STAGES; stage++) {
+		int n = 0;
+		for (int f = 0; f < 6; f++) {
+			const bool quarter = stage == 0 || (stage == 1 && !c.flips[f]) || (stage == 2 && !c.flips[f] && !c.twists[f]);
+			c.gen_action[stage][n] = (uint8_t)(2 * f);
+			c.gen_cost[stage][n++] = quarter ? 1 : 2;
+			if (quarter) {
+				c.gen_action[stage][n] = (uint8_t)(2 * f + 1);
+				c.gen_cost[stage][n++] = 1;
+			}
+		}
+		c.gen_count[stage] = n;
+	}
+	return c;
+}
+
+constexpr ChainConsts CHAIN = make_chain_consts();
+static_assert(CHAIN.consistent, "the move table does not give three axes with a slice of four edges each");
+
+template <int S> constexpr uint32_t CHAIN_SLICE = CHAIN.slice[S][0] | CHAIN.slice[S][1] << 4 | CHAIN.slice[S][2] << 8 | CHAIN.slice[S][3] << 12;
+template <int S> constexpr uint32_t CHAIN_SLICE_MASK = CHAIN.slice_mask[S];
+constexpr uint32_t chain_outside0()
+{
+	uint32_t v = 0;
+	for (int i = 0; i < 8; i++) v |= (uint32_t)CHAIN.outside0[i] << (4 * i);
+	return v;
+}
+constexpr uint32_t CHAIN_OUTSIDE0 = chain_outside0();
+template <int STAGE> constexpr int CHAIN_GENS = CHAIN.gen_count[STAGE];
+template <int STAGE, int G> constexpr uint32_t CHAIN_ACTION = CHAIN.gen_action[STAGE][G];
+template <int STAGE, int G> constexpr uint32_t CHAIN_COST = CHAIN.gen_cost[STAGE][G];
+
+struct ChainDev {
+	const uint8_t *table[CHAIN_STAGES];
+	uint32_t depth[CHAIN_STAGES];                   // the deepest entry of each table
+	const uint16_t *coset;                          // [rank of the corner sequence] -> its coset under C3, 0..419
+	const uint8_t *c3;                              // [rank] -> its ordinal in C3, 255 outside
+};
+
+// byte i of a state in five dwords, i a constant once the loops are unrolled
+#define CHAIN_BYTE(x, i) (((x)[(i) >> 2] >> (8 * ((i) & 3))) & 0xFFu)
+
+__host__ __device__ __forceinline__ uint32_t chain_popc(uint32_t v)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+	return (uint32_t)__popc(v);
+#else
+	return (uint32_t)__builtin_popcount(v);
+#endif
+}
+
+// the ordinal of a set of four among the 4-subsets of 0..11, ordered by the largest element, then the next: sum of C(p_i, i + 1)
+// over its elements ascending.  A set of fewer elements gives a number that means nothing; the caller guards the table read.
+__host__ __device__ __forceinline__ uint32_t chain_subset(uint32_t set)
+{
+	uint32_t p[4];
+	#pragma unroll
+	for (int i = 0; i < 4; i++) {
+		p[i] = set != 0u ? (uint32_t)__builtin_ctz(set) : 0u;
+		set &= set - 1u;
+	}
+	return p[0] + p[1] * (p[1] - 1u) / 2u + p[2] * (p[2] - 1u) * (p[2] - 2u) / 6u + p[3] * (p[3] - 1u) * (p[3] - 2u) * (p[3] - 3u) / 24u;
+}
+
+// the positions that hold the four edges of slice S, as a bit set
+template <int S>
+__host__ __device__ __forceinline__ uint32_t chain_slice_at(const uint32_t x[5])
+{
+	uint32_t set = 0;
+	#pragma unroll
+	for (int i = 0; i < 4; i++) set |= 1u << ((CHAIN_BYTE(x, 8 + ((CHAIN_SLICE<S> >> (4 * i)) & 15u)) >> 1) & 15u);
+	return set;
+}
+
+// the ordinal, among the 24 sequences in lexicographic order, of the places the edges of slice S take within the slice
+template <int S>
+__host__ __device__ __forceinline__ uint32_t chain_places(const uint32_t x[5])
+{
+	uint32_t q = 0, seen = 0;
+	#pragma unroll
+	for (int i = 0; i < 4; i++) {
+		const uint32_t pos = (CHAIN_BYTE(x, 8 + ((CHAIN_SLICE<S> >> (4 * i)) & 15u)) >> 1) & 15u;
+		const uint32_t place = chain_popc(CHAIN_SLICE_MASK<S> & ((1u << pos) - 1u)) & 3u;
+		q = q * (uint32_t)(4 - i) + place - chain_popc(seen & ((1u << place) - 1u));
+		seen |= 1u << place;
+	}
+	return q;
+}
+
+// the lexicographic rank of the corner sequence P = (position of cubie 0, .., of cubie 7); code / 3 = code * 11 >> 5 below 24
+__host__ __device__ __forceinline__ uint32_t chain_corner_rank(const uint32_t x[5])
+{
+	uint32_t r = 0, seen = 0;
+	#pragma unroll
+	for (int c = 0; c < 8; c++) {
+		const uint32_t pos = ((CHAIN_BYTE(x, c) * 11u) >> 5) & 7u, bit = 1u << pos;
+		r = r * (uint32_t)(8 - c) + pos - chain_popc(seen & (bit - 1u));
+		seen |= bit;
+	}
+	return r;
+}
+
+// THE INDEX of a state in the table of STAGE (include/rubiks_hip.h).  A value at or above the table's size: the state has none.
+template <int STAGE>
+__host__ __device__ __forceinline__ uint32_t chain_index(const uint32_t x[5], const uint16_t *coset, const uint8_t *c3)
+{
+	if (STAGE == 0) {
+		uint32_t bits = 0;
+		#pragma unroll
+		for (int e = 0; e < 12; e++) {
+			const uint32_t code = CHAIN_BYTE(x, 8 + e);
+			bits |= (code & 1u) << ((code >> 1) & 15u);
+		}
+		return bits & 2047u;
+	}
+	if (STAGE == 1) {
+		uint32_t digits = 0, ori = 0;
+		#pragma unroll
+		for (int c = 0; c < 8; c++) {
+			const uint32_t code = CHAIN_BYTE(x, c), pos = ((code * 11u) >> 5) & 7u;
+			digits |= ((code - 3u * pos) & 3u) << (2u * pos);
+		}
+		#pragma unroll
+		for (int p = 6; p >= 0; p--) ori = ori * 3u + ((digits >> (2 * p)) & 3u);
+		return ori * 495u + chain_subset(chain_slice_at<0>(x));
+	}
+	const uint32_t rank = chain_corner_rank(x);
+	if (rank >= CHAIN_PERMS) return 0xFFFFFFFFu;
+	if (STAGE == 2) {
+		const uint32_t at = chain_slice_at<1>(x);
+		uint32_t narrow = 0;
+		#pragma unroll
+		for (int i = 0; i < 8; i++) narrow |= ((at >> ((CHAIN_OUTSIDE0 >> (4 * i)) & 15u)) & 1u) << i;
+		return (uint32_t)coset[rank] * 70u + chain_subset(narrow);
+	}
+	const uint32_t g = c3[rank];
+	if (g >= CHAIN_C3) return 0xFFFFFFFFu;
+	return ((g * 24u + chain_places<0>(x)) * 24u + chain_places<1>(x)) * 24u + chain_places<2>(x);
+}
+
+// the entry of a state, CHAIN_UNREACHED where it has none
+template <int STAGE>
+__device__ __forceinline__ uint32_t chain_entry(const ChainDev &d, const uint32_t x[5])
+{
+	const uint32_t index = chain_index<STAGE>(x, d.coset, d.c3);
+	return index < CHAIN_SIZE[STAGE] ? (uint32_t)d.table[STAGE][index] : CHAIN_UNREACHED;
+}
+
+constexpr uint32_t CHAIN_NO_PICK = 0xFFu;
+
+// Generators G, G - 1, .., 0 in turn, each overwriting the pick: the lowest that fits stays.  pick = action | cost << 4.
+template <int STAGE, int G>
+__device__ __forceinline__ void chain_try(const ChainDev &d, const u32x4 *s_tab, const uint32_t x[5], uint32_t cur, uint32_t &pick)
+{
+	if constexpr (G >= 0) {
+		constexpr uint32_t a = CHAIN_ACTION<STAGE, G>, cost = CHAIN_COST<STAGE, G>;
+		uint32_t tab[12], s[5] = {x[0], x[1], x[2], x[3], x[4]};
+		load_action_table(s_tab, a, tab);
+		move5(s, tab);
+		if (cost == 2u) move5(s, tab);
+		if (chain_entry<STAGE>(d, s) + cost == cur) pick = a | cost << 4;
+		chain_try<STAGE, G - 1>(d, s_tab, x, cur, pick);
+	}
+}
+
+// One stage's descent of state x; the actions go to row[t...].  false: the state has no entry, or an entry has no generator that
+// fits (never with tables that passed their build and a legal state).
+template <int STAGE>
+__device__ __forceinline__ bool chain_descend(const ChainDev &d, const u32x4 *s_tab, uint32_t x[5], int8_t *row, uint32_t &t, uint32_t &length)
+{
+	uint32_t cur = chain_entry<STAGE>(d, x);
+	if (cur > d.depth[STAGE]) return false;
+	length = cur;
+	for (uint32_t step = 0; step < d.depth[STAGE] && cur != 0u; step++) {
+		uint32_t pick = CHAIN_NO_PICK;
+		chain_try<STAGE, CHAIN_GENS<STAGE> - 1>(d, s_tab, x, cur, pick);
+		if (pick == CHAIN_NO_PICK) return false;
+		const uint32_t a = pick & 15u, cost = pick >> 4;
+		uint32_t tab[12];
+		load_action_table(s_tab, a, tab);
+		move5(x, tab);
+		row[t++] = (int8_t)a;
+		if (cost == 2u) {
+			move5(x, tab);
+			row[t++] = (int8_t)a;
+		}
+		cur -= cost;                                                     // cost <= cur: the pick's entry + cost == cur
+	}
+	return cur == 0u;
+}
+
+// lengths[q] = the moves written to row q of `actions` (`stride` = the four depths added up, which no row exceeds: a stage writes
+// exactly its entry's cost); -1 and no action for a row that is no legal state.  error = min(error, q) over the rows that get -1.
+__global__ __launch_bounds__(256)
+void k_chain_solve(ChainDev d, const uint32_t *states, size_t n, uint32_t stride, int32_t *lengths, int8_t *actions, int32_t *stage_lengths,
+                   uint32_t *error)
+{
+	__shared__ u32x4 s_tab[36];
+	stage_action_tables(s_tab, (int)threadIdx.x);
+	__syncthreads();
+	for (size_t q = (size_t)blockIdx.x * 256 + threadIdx.x; q < n; q += (size_t)gridDim.x * 256) {
+		uint32_t x[5], t = 0, l0 = 0, l1 = 0, l2 = 0, l3 = 0;
+		load5(states + q * 5, x);
+		int8_t *row = actions + q * (size_t)stride;
+		const bool ok = group_legal(x) && chain_descend<0>(d, s_tab, x, row, t, l0) && chain_descend<1>(d, s_tab, x, row, t, l1) &&
+		                chain_descend<2>(d, s_tab, x, row, t, l2) && chain_descend<3>(d, s_tab, x, row, t, l3);
+		lengths[q] = ok ? (int32_t)t : -1;
+		if (stage_lengths != nullptr) {
+			int32_t *out = stage_lengths + q * 4;
+			out[0] = ok ? (int32_t)l0 : -1;
+			out[1] = ok ? (int32_t)l1 : -1;
+			out[2] = ok ? (int32_t)l2 : -1;
+			out[3] = ok ? (int32_t)l3 : -1;
+		}
+		if (!ok && error != nullptr) atomicMin(error, (uint32_t)q);
+	}
+}
+
+}  // namespace rk
+
+using namespace rk;
+
+struct rk_chain {
+	ChainDev d{};
+	uint8_t *d_block = nullptr;                         // the four tables and the two maps, one allocation
+	long long counts[CHAIN_STAGES] = {};
+	~rk_chain()
+	{
+		if (d_block) (void)hipFree(d_block);
+	}
+};
+
+namespace {
+
+typedef std::array<uint32_t, 5> ChainState;
+
+unsigned chain_grid(size_t n) { return (unsigned)std::min<size_t>((n + 255) / 256, (size_t)RK_CHAIN_GRID); }
+
+const Tables &chain_tables()
+{
+	static const Tables t = make_tables();
+	return t;
+}
+
+ChainState chain_move(const ChainState &s, int action)
+{
+	const Tables &t = chain_tables();
+	uint8_t b[STATE_BYTES];
+	memcpy(b, s.data(), STATE_BYTES);
+	for (int i = 0; i < 8; i++) b[i] = t.lut[action][0][b[i]];
+	for (int i = 8; i < STATE_BYTES; i++) b[i] = t.lut[action][1][b[i]];
+	ChainState out;
+	memcpy(out.data(), b, STATE_BYTES);
+	return out;
+}
+
+ChainState chain_generate(const ChainState &s, int stage, int g)
+{
+	ChainState out = chain_move(s, CHAIN.gen_action[stage][g]);
+	return CHAIN.gen_cost[stage][g] == 2 ? chain_move(out, CHAIN.gen_action[stage][g]) : out;
+}
+
+ChainState chain_solved()
+{
+	ChainState s;
+	memcpy(s.data(), chain_tables().solved, STATE_BYTES);
+	return s;
+}
+
+// The two corner maps.  C3: the corner sequences that the half turns reach from solved, by a closure.  coset[r]: sequences P and
+// P o h, h in C3 (the cubies relabelled), share a coset -- the side on which a move, which acts on the positions, maps cosets to
+// cosets --; cosets are numbered by their least rank.  false: not 96 sequences or not 420 cosets.
+bool chain_corner_maps(std::vector<uint16_t> &coset, std::vector<uint8_t> &c3)
+{
+	std::vector<uint8_t> in_c3(CHAIN_PERMS, 0);
+	std::vector<ChainState> todo{chain_solved()};
+	in_c3[chain_corner_rank(todo[0].data())] = 1;
+	while (!todo.empty()) {
+		const ChainState s = todo.back();
+		todo.pop_back();
+		for (int g = 0; g < CHAIN.gen_count[3]; g++) {
+			const ChainState c = chain_generate(s, 3, g);
+			const uint32_t r = chain_corner_rank(c.data());
+			if (!in_c3[r]) {
+				in_c3[r] = 1;
+				todo.push_back(c);
+			}
+		}
+	}
+	// every sequence by rank, eight positions each
+	std::vector<uint8_t> seq((size_t)CHAIN_PERMS * 8);
+	uint8_t p[8] = {0, 1, 2, 3, 4, 5, 6, 7};
+	for (uint32_t r = 0; r < CHAIN_PERMS; r++, std::next_permutation(p, p + 8)) memcpy(&seq[(size_t)r * 8], p, 8);
+	const auto rank_of = [](const uint8_t *q) {
+		uint32_t x[5] = {0, 0, 0, 0, 0};
+		for (int c = 0; c < 8; c++) x[c >> 2] |= (uint32_t)(3 * q[c]) << (8 * (c & 3));
+		return chain_corner_rank(x);
+	};
+	c3.assign(CHAIN_PERMS, 255);
+	std::vector<uint32_t> members;
+	for (uint32_t r = 0; r < CHAIN_PERMS; r++)
+		if (in_c3[r]) {
+			if (rank_of(&seq[(size_t)r * 8]) != r) return false;
+			c3[r] = (uint8_t)std::min<size_t>(members.size(), 254);
+			members.push_back(r);
+		}
+	if (members.size() != CHAIN_C3) return false;
+	coset.assign(CHAIN_PERMS, 0xFFFF);
+	uint32_t cosets = 0;
+	for (uint32_t r = 0; r < CHAIN_PERMS; r++) {
+		if (coset[r] != 0xFFFF) continue;
+		if (cosets == CHAIN_COSETS) return false;
+		for (uint32_t h : members) {
+			uint8_t q[8];
+			for (int c = 0; c < 8; c++) q[c] = seq[(size_t)r * 8 + seq[(size_t)h * 8 + c]];
+			const uint32_t other = rank_of(q);
+			if (coset[other] != 0xFFFF && coset[other] != cosets) return false;
+			coset[other] = (uint16_t)cosets;
+		}
+		cosets++;
+	}
+	return cosets == CHAIN_COSETS;
+}
+
+// One table: see the head of this file.  Returns the deepest entry, -1 unless exactly CHAIN_COUNT[STAGE] entries were reached and
+// one of them is 0.
+template <int STAGE>
+int chain_build(std::vector<uint8_t> &table, const uint16_t *coset, const uint8_t *c3, long long &count)
+{
+	table.assign(CHAIN_SIZE[STAGE], (uint8_t)CHAIN_UNREACHED);
+	std::vector<ChainState> before, level{chain_solved()}, next;        // levels d - 1, d, d + 1: one representative per entry
+	const uint32_t goal = chain_index<STAGE>(level[0].data(), coset, c3);
+	if (goal >= CHAIN_SIZE[STAGE]) return -1;
+	table[goal] = 0;
+	count = 1;
+	int d = 0;
+	for (; !level.empty() || !before.empty(); d++) {
+		if (d + 1 >= (int)CHAIN_UNREACHED) return -1;
+		next.clear();
+		for (int g = 0; g < CHAIN.gen_count[STAGE]; g++)
+			for (const ChainState &s : CHAIN.gen_cost[STAGE][g] == 1 ? level : before) {
+				const ChainState c = chain_generate(s, STAGE, g);
+				const uint32_t index = chain_index<STAGE>(c.data(), coset, c3);
+				if (index >= CHAIN_SIZE[STAGE]) return -1;
+				if (table[index] != CHAIN_UNREACHED) continue;
+				table[index] = (uint8_t)(d + 1);
+				next.push_back(c);
+			}
+		count += (long long)next.size();
+		before.swap(level);
+		level.swap(next);
+	}
+	long long zeros = 0;
+	for (uint8_t v : table) zeros += v == 0;
+	if (count != (long long)CHAIN_COUNT[STAGE] || zeros != 1) return -1;
+	return d - 2;                                                        // the last two levels were empty
+}
+
+}  // namespace
+
+extern "C" {
+
+int rk_chain_create(rk_chain_t **out, void *stream)
+{
+	if (!out) return fail(RK_EINVAL, "rk_chain_create: null out pointer");
+	std::vector<uint16_t> coset;
+	std::vector<uint8_t> c3, table[CHAIN_STAGES];
+	if (!chain_corner_maps(coset, c3))
+		return fail(RK_ESTATE, "rk_chain_create: the half turns do not give %u corner sequences in %u cosets", CHAIN_C3, CHAIN_COSETS);
+	rk_chain *h = new rk_chain();
+	int depth[CHAIN_STAGES];
+	depth[0] = chain_build<0>(table[0], coset.data(), c3.data(), h->counts[0]);
+	depth[1] = chain_build<1>(table[1], coset.data(), c3.data(), h->counts[1]);
+	depth[2] = chain_build<2>(table[2], coset.data(), c3.data(), h->counts[2]);
+	depth[3] = chain_build<3>(table[3], coset.data(), c3.data(), h->counts[3]);
+	for (int s = 0; s < CHAIN_STAGES; s++)
+		if (depth[s] < 0) {
+			const long long got = h->counts[s];
+			delete h;
+			return fail(RK_ESTATE, "rk_chain_create: the table of stage %d reached %lld cosets, not %u with one goal", s + 1, got, CHAIN_COUNT[s]);
+		}
+	// one block: the tables, then the maps, each 16-byte aligned
+	size_t at[CHAIN_STAGES + 2], bytes = 0;
+	for (int s = 0; s < CHAIN_STAGES; s++) {
+		at[s] = bytes;
+		bytes += ((size_t)CHAIN_SIZE[s] + 15) / 16 * 16;
+	}
+	at[CHAIN_STAGES] = bytes;
+	bytes += (size_t)CHAIN_PERMS * sizeof(uint16_t);
+	at[CHAIN_STAGES + 1] = bytes;
+	bytes += CHAIN_PERMS;
+	if (hipMalloc((void **)&h->d_block, bytes) != hipSuccess) {
+		(void)hipGetLastError();
+		h->d_block = nullptr;
+		delete h;
+		return fail(RK_ECAPACITY, "rk_chain_create: no device memory for %zu bytes of tables", bytes);
+	}
+	hipStream_t st = (hipStream_t)stream;
+	const auto upload = [&]() -> int {
+		for (int s = 0; s < CHAIN_STAGES; s++) RK_HIP(hipMemcpyAsync(h->d_block + at[s], table[s].data(), CHAIN_SIZE[s], hipMemcpyHostToDevice, st));
+		RK_HIP(hipMemcpyAsync(h->d_block + at[CHAIN_STAGES], coset.data(), (size_t)CHAIN_PERMS * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+		RK_HIP(hipMemcpyAsync(h->d_block + at[CHAIN_STAGES + 1], c3.data(), CHAIN_PERMS, hipMemcpyHostToDevice, st));
+		RK_HIP(hipStreamSynchronize(st));                                   // the host copies go out of scope
+		return RK_OK;
+	};
+	if (int e = upload()) {
+		delete h;
+		return e;
+	}
+	for (int s = 0; s < CHAIN_STAGES; s++) {
+		h->d.table[s] = h->d_block + at[s];
+		h->d.depth[s] = (uint32_t)depth[s];
+	}
+	h->d.coset = reinterpret_cast<const uint16_t *>(h->d_block + at[CHAIN_STAGES]);
+	h->d.c3 = h->d_block + at[CHAIN_STAGES + 1];
+	*out = h;
+	return RK_OK;
+}
+
+int rk_chain_destroy(rk_chain_t *h)
+{
+	delete h;
+	return RK_OK;
+}
+
+int rk_chain_status(rk_chain_t *h, long long *h_status)
+{
+	if (!h || !h_status) return fail(RK_EINVAL, "rk_chain_status: null argument");
+	memset(h_status, 0, 16 * sizeof(long long));
+	for (int s = 0; s < CHAIN_STAGES; s++) {
+		h_status[s] = h->counts[s];
+		h_status[4 + s] = (long long)h->d.depth[s];
+		h_status[8] += (long long)h->d.depth[s];
+		h_status[9 + s] = (long long)CHAIN_SIZE[s];
+	}
+	return RK_OK;
+}
+
+int rk_chain_export(rk_chain_t *h, int stage, size_t first, size_t count, uint8_t *h_bytes, void *stream)
+{
+	if (!h) return fail(RK_EINVAL, "rk_chain_export: null handle");
+	if (stage < 1 || stage > CHAIN_STAGES) return fail(RK_EINVAL, "rk_chain_export: stage %d outside 1..%d", stage, CHAIN_STAGES);
+	const size_t size = CHAIN_SIZE[stage - 1];
+	if (first > size || count > size - first) return fail(RK_EINVAL, "rk_chain_export: entries %zu..%zu outside the table", first, first + count);
+	if (count == 0) return RK_OK;
+	if (!h_bytes) return fail(RK_EINVAL, "rk_chain_export: null pointer");
+	hipStream_t st = (hipStream_t)stream;
+	RK_HIP(hipMemcpyAsync(h_bytes, h->d.table[stage - 1] + first, count, hipMemcpyDeviceToHost, st));
+	RK_HIP(hipStreamSynchronize(st));
+	return RK_OK;
+}
+
+int rk_chain_solve(rk_chain_t *h, const int8_t *d_states, size_t n, int32_t *d_lengths, int8_t *d_actions, int32_t *d_stage_lengths,
+                   int32_t *d_error, void *stream)
+{
+	if (!h) return fail(RK_EINVAL, "rk_chain_solve: null handle");
+	if (n > (size_t)INT32_MAX) return fail(RK_EINVAL, "rk_chain_solve: %zu states in one launch", n);
+	if (n != 0 && (!d_states || !d_lengths || !d_actions)) return fail(RK_EINVAL, "rk_chain_solve: null pointer");
+	if (((uintptr_t)d_states | (uintptr_t)d_lengths | (uintptr_t)d_stage_lengths | (uintptr_t)d_error) & 3u)
+		return fail(RK_EINVAL, "rk_chain_solve: device pointers must be 4-byte aligned");
+	if (n == 0) return RK_OK;
+	hipStream_t st = (hipStream_t)stream;
+	if (d_error) RK_HIP(hipMemsetAsync(d_error, 0xFF, sizeof(int32_t), st));         // -1: no row so far
+	const uint32_t stride = h->d.depth[0] + h->d.depth[1] + h->d.depth[2] + h->d.depth[3];
+	hipLaunchKernelGGL(k_chain_solve, dim3(chain_grid(n)), dim3(256), 0, st, h->d, reinterpret_cast<const uint32_t *>(d_states), n, stride,
+	                   d_lengths, d_actions, d_stage_lengths, reinterpret_cast<uint32_t *>(d_error));
+	RK_HIP(hipGetLastError());
+	return RK_OK;
+}
+
+}  // extern "C"

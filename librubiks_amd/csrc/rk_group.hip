@@ -23,6 +23,7 @@
 #include "../../include/rubiks_hip.h"
 #include "rk_device.h"
 #include "rk_error.h"
+#include "rk_group_dev.h"
 #include "rk_group_tables.h"
 #include "rk_search_dev.h"
 
@@ -41,20 +42,6 @@ constexpr GroupDev make_group_dev()
 }
 
 static __constant__ GroupDev D_GROUP = make_group_dev();
-
-__device__ __forceinline__ uint32_t group_div3(uint32_t x)
-{
-	const uint32_t t[6] = {GROUP_TABLES.div3[0], GROUP_TABLES.div3[1], GROUP_TABLES.div3[2], GROUP_TABLES.div3[3], GROUP_TABLES.div3[4],
-	                       GROUP_TABLES.div3[5]};
-	return lut4(x, t);
-}
-
-__device__ __forceinline__ uint32_t group_mod3(uint32_t x)
-{
-	const uint32_t t[6] = {GROUP_TABLES.mod3[0], GROUP_TABLES.mod3[1], GROUP_TABLES.mod3[2], GROUP_TABLES.mod3[3], GROUP_TABLES.mod3[4],
-	                       GROUP_TABLES.mod3[5]};
-	return lut4(x, t);
-}
 
 // byte `pos` (0..7) of the pair |= v; a position beyond 7 cannot be given
 __device__ __forceinline__ void group_put8(uint32_t &lo, uint32_t &hi, uint32_t pos, uint32_t v)
@@ -125,45 +112,6 @@ __device__ __forceinline__ void group_relative(const uint32_t *lds, const uint32
 		#pragma unroll
 		for (int i = 0; i < 4; i++) group_put12(y + 2, (pos4 >> (8 * i)) & 0xFFu, (v4 >> (8 * i)) & 0xFFu);
 	}
-}
-
-// A row is legal when it is reachable from solved: every code below 24, the corner positions a permutation of 0..7 and the edge
-// positions one of 0..11, the two permutations of equal parity, the edge flips even in number and the corner twists 0 mod 3.
-__device__ __forceinline__ bool group_legal(const uint32_t x[5])
-{
-	uint32_t high = 0;                                                                       // bit 7 of a byte: the code is 24 or more
-	#pragma unroll
-	for (int j = 0; j < 5; j++) high |= ((x[j] & 0x7F7F7F7Fu) + 0x68686868u) | x[j];
-	bool ok = (high & 0x80808080u) == 0u;
-	// positions seen so far, and the inversions of both permutations together: an element counts the greater positions before it
-	uint32_t seen = 0, inversions = 0, twist = 0;
-	#pragma unroll
-	for (int j = 0; j < 2; j++) {
-		const uint32_t pos4 = group_div3(x[j]);
-		#pragma unroll
-		for (int i = 0; i < 4; i++) {
-			const uint32_t pos = (pos4 >> (8 * i)) & 7u;
-			inversions += (uint32_t)__popc(seen & (0xFFFFFFFEu << pos));
-			seen |= 1u << pos;
-			twist += (uint32_t)(GROUP_TAU_BITS >> (2u * ((x[j] >> (8 * i)) & 31u))) & 3u;
-		}
-	}
-	ok = ok && seen == 0xFFu;
-	seen = 0;
-	#pragma unroll
-	for (int j = 2; j < 5; j++) {
-		#pragma unroll
-		for (int i = 0; i < 4; i++) {
-			const uint32_t pos = (x[j] >> (8 * i + 1)) & 15u;
-			inversions += (uint32_t)__popc(seen & (0xFFFFFFFEu << pos));
-			seen |= 1u << pos;
-		}
-	}
-	ok = ok && seen == 0xFFFu;
-	uint32_t flips = x[2] ^ x[3] ^ x[4];
-	flips ^= flips >> 16;
-	flips ^= flips >> 8;
-	return ok && ((inversions | flips) & 1u) == 0u && twist % 3u == 0u;
 }
 
 __device__ __forceinline__ void group_stage(uint32_t *lds /* 256 */)

@@ -1228,6 +1228,95 @@ class DevicePatternDB(_ffi.Owner):
 		return f"Pattern database (device, corners={self.corner_cubies}, edges={self.edge_cubies}, {self.size} entries)"
 
 
+class DeviceChainSolver(Agent, _ffi.Owner):
+	"""
+	A solution for EVERY legal state, batched on the device (engine rk_chain_*, csrc/rk_chain.hip): the subgroup chain -- four
+	stages, each a table of exact costs over the cosets of the next subgroup, built on the host when the solver is made and kept
+	in HBM (2.5 MB) -- answered by four table descents in one launch, a thread per state: no search, no pool, no net.  Stage 1
+	uses the 12 quarter turns, the later ones fewer and fewer of them and the half turns XX (the action 2 f twice) of the other
+	faces.  Solutions are NOT optimal -- at most `max_length` moves, some tens on average --; `shorten=ball` (a
+	`DeviceGoalBall` or `DeviceSymBall`) pipes every queue through `ball.shorten`, which makes it locally optimal.
+
+	`solve(states)` takes a batch: numpy in -> numpy out, device tensor in -> device tensor out; states are in the representation
+	cube.get_is2024() names when a method is called.  As an agent (`search(state)` fills `action_queue`; never fails on a legal
+	state) it plays in `Evaluator` and under `TowardsGoal`.  A row that is no legal state (`cube.is_legal`) is a ValueError naming
+	the lowest such row, or, with `allow_illegal`, gets length -1 (its stage lengths -1, its actions all -1).
+	"""
+	GRID_ROWS = 2048 * 256                  # RK_CHAIN_GRID workgroups of 256 states: beyond this many rows a thread takes several
+
+	def __init__(self, shorten=None, allow_illegal: bool = False):
+		Agent.__init__(self)
+		if shorten is not None and not isinstance(shorten, _KeptBall):
+			raise ValueError("shorten must be a DeviceGoalBall, a DeviceSymBall or None")
+		self.shorten, self.allow_illegal = shorten, bool(allow_illegal)
+		_ffi.require_gpu()
+		self._create("rk_chain_create", "rk_chain_destroy", _ffi.stream_ptr())
+		status = (C.c_longlong * 16)()
+		_ffi.check(_ffi.lib().rk_chain_status(self._h, status))
+		self.coset_counts = tuple(int(v) for v in status[0:4])
+		self.stage_depths = tuple(int(v) for v in status[4:8])           # the deepest entry of each table
+		self.max_length = int(status[8])                                 # the row length of `solve`'s actions
+		self.table_sizes = tuple(int(v) for v in status[9:13])
+
+	_rows = DevicePatternDB._rows
+
+	def solve(self, states, stage_lengths: bool = False):
+		"""(lengths int32 (n,), actions int8 (n, max_length) padded with -1[, stage lengths int32 (n, 4)]): per stage, at each step
+		the lowest generator whose entry equals the current entry minus its cost.  One launch; reading the error word (not with
+		`allow_illegal`) is the call's one host read.  With `shorten` the queues come back through `ball.shorten` (lengths and
+		actions then describe the shortened queues; the stage lengths stay the chain's own)."""
+		q, dev = self._rows(states)
+		n = len(q)
+		lengths = torch.empty(n, dtype=torch.int32, device=gpu)
+		actions = torch.full((n, self.max_length), -1, dtype=torch.int8, device=gpu)
+		stages = torch.empty((n, 4), dtype=torch.int32, device=gpu) if stage_lengths else None
+		err = None if self.allow_illegal else torch.full((1,), -1, dtype=torch.int32, device=gpu)
+		_ffi.check(_ffi.lib().rk_chain_solve(self._h, q.data_ptr(), n, lengths.data_ptr(), actions.data_ptr(),
+		                                     stages.data_ptr() if stage_lengths else None, None if err is None else err.data_ptr(), _ffi.stream_ptr()))
+		if err is not None and int(err.item()) >= 0:
+			raise ValueError(f"row {int(err.item())} of states is not a legal cube state (the lowest such row)")
+		if self.shorten is not None and n:
+			lengths, actions = self._shortened(lengths, actions)
+		out = (lengths, actions) + ((stages,) if stage_lengths else ())
+		return out if dev else tuple(t.cpu().numpy() for t in out)
+
+	def _shortened(self, lengths, actions):
+		"""The queues after `self.shorten.shorten`, back in `solve`'s shape on the device."""
+		h_len, h_act = lengths.cpu().numpy(), actions.cpu().numpy()
+		queues = self.shorten.shorten([h_act[i, :max(int(h_len[i]), 0)] for i in range(len(h_len))])
+		out = np.full(h_act.shape, -1, np.int8)
+		for i, queue in enumerate(queues):
+			out[i, :len(queue)] = queue
+			if h_len[i] >= 0:
+				h_len[i] = len(queue)
+		return torch.from_numpy(h_len).to(gpu), torch.from_numpy(out).to(gpu)
+
+	def export(self, stage: int) -> np.ndarray:
+		"""uint8 (table_sizes[stage - 1],): the table of stage 1..4, entry by index; 255 = no coset has this index."""
+		stage = eng.int_in("stage", stage, 1, 4, what="a stage 1..4")
+		out = np.empty(self.table_sizes[stage - 1], np.uint8)
+		_ffi.check(_ffi.lib().rk_chain_export(self._h, stage, 0, len(out), out.ctypes.data, _ffi.stream_ptr()))
+		return out
+
+	def search(self, state: np.ndarray, time_limit: float = None, max_states: int = None) -> bool:
+		"""The state's solution into `action_queue`; len(agent) is 1, the one state looked at.  Neither limit is needed or used."""
+		self._explored_states = 0
+		self.action_queue = deque()
+		is2024 = cube.get_is2024()
+		rows = _roots20(is2024, state, 1)
+		was_illegal, self.allow_illegal = self.allow_illegal, False       # an agent cannot answer "no state"
+		try:
+			lengths, actions = self.solve(rows if is2024 else cube.as686(rows))
+		finally:
+			self.allow_illegal = was_illegal
+		self._explored_states = 1
+		self.action_queue = deque(int(a) for a in actions[0, :int(lengths[0])])
+		return True
+
+	def __str__(self):
+		return "Subgroup chain solver (device)" + (f", shortened by {self.shorten}" if self.shorten is not None else "")
+
+
 class _BallSearch(_PoolSearch):
 	"""What `DeviceBallSearch` and `DeviceSymBallSearch` share on top of `_PoolSearch`: the ball they end at (`_ball_type` is its
 	kind), the meeting and the levels around the start.  Their engines have one argument list and one status layout."""
