@@ -604,6 +604,16 @@ int rk_pdb_depth(rk_pdb_t *h, const int8_t *d_states, size_t n, int32_t *d_depth
  * d_error[0] is cleared, then set to RK_ESTATE if a reached entry has no such child (its length is -1 then; never in a table
  * that passed its build). */
 int rk_pdb_solve(rk_pdb_t *h, const int8_t *d_states, size_t n, int32_t *d_lengths, int8_t *d_actions, int32_t *d_error, void *stream);
+/* A bound over several databases (rk_bound_*): a pattern's entry never exceeds the distance to solved, so the greatest entry of
+ * a state over 1..4 BUILT databases is an admissible lower bound on it.  The handle copies the databases' descriptors and
+ * allocates nothing on the device; the databases must outlive it.  RK_EINVAL for n outside 1..4, a null database or the same
+ * database twice, RK_ESTATE for a database that is not built. */
+typedef struct rk_bound rk_bound_t;
+int rk_bound_create(rk_bound_t **out, rk_pdb_t *const *dbs, int n);
+int rk_bound_destroy(rk_bound_t *h);
+/* d_bound[q] = the greatest of the databases' rk_pdb_depth of DEVICE state q of d_states int8 (n, 20), -1 only where every
+ * database answers -1.  One launch, rk_pdb_depth's limits. */
+int rk_bound_depth(rk_bound_t *h, const int8_t *d_states, size_t n, int32_t *d_bound, void *stream);
 
 /* ---- the subgroup chain: a solution for every legal state (rk_chain_*) ---------------------------------------------------------
  * Four stages, each with a table of one byte per coset: the cost of the cheapest word of the stage's generators that brings a
@@ -750,6 +760,15 @@ int rk_sdeepen(rk_symball_t *ball, const int8_t *d_states, const int8_t *d_last,
 /* The most probes (n * word_count) of one rk_sdeepen / rk_sdeepen_nodes launch: 2^28, which keeps a launch well under a second
  * (benchmarks/symball_deepen.py measures a full launch).  Touches no device. */
 long long rk_sdeepen_max_probes(void);
+/* rk_sdeepen with its look-ups pruned by an admissible bound (rk_bound_*): d_best comes out as rk_sdeepen leaves it, bit for
+ * bit.  With R the ball's radius, a word is dropped without a look-up where the bound of a state on its way shows that no state
+ * of the ball lies behind it: bound > R + (moves still to make), tested at the start state, after every shared move, at the
+ * next-to-last state and at the leaf.  A word that hits has no such prefix -- the state after k of its `extra` moves is at most
+ * (extra - k) + R from solved, and the bound is admissible --, so the set of hits is rk_sdeepen's.  d_lookups (NULL: not
+ * counted; else a DEVICE uint64, 8-byte aligned, which the caller zeroes) += the ball look-ups made, one atomic add per wave.
+ * word_count counts the words ISSUED, pruned or not: rk_sdeepen's limits and return codes, plus RK_EINVAL for a null bound. */
+int rk_sdeepen_pruned(rk_symball_t *ball, rk_bound_t *bound, const int8_t *d_states, const int8_t *d_last, size_t n, int extra,
+                      uint32_t word_first, uint32_t word_count, uint32_t *d_best, unsigned long long *d_lookups, void *stream);
 /* rk_bshorten against the symmetry ball: one pass over a batch of action queues, with rk_bshorten's contract (above) -- the
  * same arguments, limits, return codes and d_error semantics, scratch of rk_bshorten_scratch_bytes(n, max_len, window) bytes --
  * and d(i, j) = the symmetry ball's depth of X(i, j), i.e. the level of its representative.  That is the plain ball's d(i, j)
@@ -817,6 +836,9 @@ int rk_sdeepen_frontier(rk_ssearch_t *h, long long *h_out, void *stream);
  * and return codes. */
 int rk_sdeepen_nodes(rk_ssearch_t *h, int extra, size_t node_first, size_t node_count, uint32_t word_first, uint32_t word_count,
                      uint32_t *d_best, void *stream);
+/* rk_sdeepen_nodes with rk_sdeepen_pruned's launch: the same d_best, fewer look-ups, d_lookups as there. */
+int rk_sdeepen_nodes_pruned(rk_ssearch_t *h, rk_bound_t *bound, int extra, size_t node_first, size_t node_count, uint32_t word_first,
+                            uint32_t word_count, uint32_t *d_best, unsigned long long *d_lookups, void *stream);
 /* The action queue start -> `node` -> word `rank` of `extra` moves -> descent through the ball, walked by one wave as
  * rk_ssearch_path.  Returns its length or a negative error: RK_EINVAL for a node outside 1..n_states or extra outside 1..8,
  * RK_ESTATE if the node has no such word or the ball does not hold the moved state's representative.  Synchronises. */

@@ -144,6 +144,9 @@ SIGNATURES = {
 	"rk_pdb_export": (_i, [_vp, _sz, _sz, _vp, _vp]),
 	"rk_pdb_depth": (_i, [_vp, _vp, _sz, _vp, _vp]),
 	"rk_pdb_solve": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+	"rk_bound_create": (_i, [C.POINTER(_vp), _vp, _i]),
+	"rk_bound_destroy": (_i, [_vp]),
+	"rk_bound_depth": (_i, [_vp, _vp, _sz, _vp, _vp]),
 	"rk_chain_create": (_i, [C.POINTER(_vp), _vp]),
 	"rk_chain_destroy": (_i, [_vp]),
 	"rk_chain_status": (_i, [_vp, _vp]),
@@ -163,6 +166,7 @@ SIGNATURES = {
 	"rk_symball_child_depths": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp]),
 	"rk_sdeepen": (_i, [_vp, _vp, _vp, _sz, _i, C.c_uint32, C.c_uint32, _vp, _vp]),
 	"rk_sdeepen_max_probes": (C.c_longlong, []),
+	"rk_sdeepen_pruned": (_i, [_vp, _vp, _vp, _vp, _sz, _i, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
 	"rk_sshorten": (_i, [_vp, _vp, _vp, _sz, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
 	"rk_ssearch_create": (_i, [C.POINTER(_vp), _vp, _sz, _i]),
 	"rk_ssearch_destroy": (_i, [_vp]),
@@ -176,6 +180,7 @@ SIGNATURES = {
 	"rk_sdeepen_set_pops": (_i, [_vp, _i, _vp]),
 	"rk_sdeepen_frontier": (_i, [_vp, _vp, _vp]),
 	"rk_sdeepen_nodes": (_i, [_vp, _i, _sz, _sz, C.c_uint32, C.c_uint32, _vp, _vp]),
+	"rk_sdeepen_nodes_pruned": (_i, [_vp, _vp, _i, _sz, _sz, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
 	"rk_sdeepen_path": (C.c_longlong, [_vp, C.c_longlong, _i, C.c_uint32, _vp, _sz, _vp]),
 	"rk_ssearchb_create": (_i, [C.POINTER(_vp), _vp, _i, _sz, _i]),
 	"rk_ssearchb_destroy": (_i, [_vp]),

@@ -19,10 +19,14 @@
 // (DeepenRanks).  A slot of the batch keeps ONE 64-bit key for its whole frontier, node << 32 | rank (DeepenKey): the lowest key is
 // the lowest node that has a hit and that node's lowest rank, which is what the words give when they are read in node order.  A
 // (node, rank) above the key is skipped, so after the first hit what is left of a round collapses to the lower nodes.
+//
+// Pruning.  A launch may carry an admissible bound (PdbPrune below): words behind a state that is provably too far from the
+// ball are not looked up, which changes no hit and therefore nothing that is kept.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "rk_device.h"
+#include "rk_pdb_dev.h"
 #include "rk_search_dev.h"
 #include "rk_sym_dev.h"
 
@@ -119,10 +123,88 @@ __device__ __forceinline__ void deepen_move(const u32x4 *s_act, int a, const uin
 	move5(out, tab);
 }
 
-// the items wave, wave + stride, ... of the job (wave and stride in whole waves; all 64 lanes of a wave call it)
+// What a launch knows about words that cannot hit.  NoPrune: nothing, every word is looked up.  PdbPrune: an admissible bound
+// (rk_pdb_dev.h) and the ball's radius R; left(s, m) says that no state of the ball lies within m moves of s, bound(s) > R + m.
+// A word that hits has no such prefix -- the state after k of its e moves is at most (e - k) + R from solved --, so the hits,
+// and with them everything a launch keeps, are NoPrune's.  lookups (null: not counted) += the sb_node calls of a wave, once.
+struct NoPrune {
+	static constexpr bool on = false;
+};
+
+struct PdbPrune {
+	static constexpr bool on = true;
+	PdbBound bound;
+	int radius;
+	unsigned long long *lookups;
+	__device__ __forceinline__ bool left(const uint32_t s[5], int m) const { return pdb_bound(bound, s) > radius + m; }
+	// the same for a state that every lane holds: one answer for the wave, in a scalar register
+	__device__ __forceinline__ bool left_uniform(const uint32_t s[5], int m) const { return __builtin_amdgcn_readfirstlane((int)left(s, m)) != 0; }
+};
+
+// The last two moves of an item under PdbPrune.  The item's up to 132 (next-to-last, last) pairs are filtered with lane = word,
+// 64 at a time: a lane makes its own two moves and asks the bound about its next-to-last state and its leaf; lanes whose rank
+// is outside [lo, hi), above `best` or not a rank of the item are off.  The ballot is the pass's survivors, which the wave takes
+// in ascending rank order as deepen_probe takes every word: the leaf made again in every lane, one cooperative look-up, a hit
+// ends the item.  s: the state after the shared moves, prev: the move before the pair; cm x cl pairs, rank = base + dm * cl + dl.
 template <typename Keep>
-__device__ __forceinline__ void deepen_probe(const SymBallView &b, const DeepenJob &job, const SymProbe &c, size_t wave, size_t stride, const Keep &keep)
+__device__ __forceinline__ void deepen_pairs_pruned(const SymBallView &b, const SymProbe &c, const PdbPrune &prune, const Keep &keep, size_t i, int e,
+                                                    const uint32_t s[5], int prev, uint32_t cm, uint32_t cl, long long base, long long lo, long long hi,
+                                                    long long best, unsigned long long &lookups)
 {
+	const u32x4 *s_act = c.s_act;
+	const uint32_t pairs = cm * cl;
+	uint32_t s1[5];
+	uint32_t at = ~0u;                                               // the next-to-last move s1 holds
+	int p1 = prev;
+	#pragma unroll
+	for (int j = 0; j < 5; j++) s1[j] = s[j];
+	for (uint32_t first = 0; first < pairs; first += WAVE) {
+		if (base + first >= hi || base + first > best) break;
+		if (base + first + WAVE <= lo) continue;
+		const uint32_t mine = first + (uint32_t)c.lane;
+		const long long r = base + mine;
+		bool live = mine < pairs && r >= lo && r < hi && r <= best;
+		{                                                            // lane = word (a lane that is off makes pair 0's moves)
+			const uint32_t w = live ? mine : 0u, dm = w / cl, dl = w - dm * cl;
+			uint32_t x[5], y[5];
+			int q = prev;
+			if (e >= 2) {
+				q = deepen_action(prev, (int)dm);
+				deepen_move(s_act, q, s, x);
+				live = live && !prune.left(x, 1);
+			} else {
+				#pragma unroll
+				for (int j = 0; j < 5; j++) x[j] = s[j];
+			}
+			deepen_move(s_act, deepen_action(q, (int)dl), x, y);
+			live = live && !prune.left(y, 0);
+		}
+		unsigned long long todo = __ballot(live);
+		while (todo != 0ull) {                                       // (the same in every lane from here on)
+			const uint32_t w = first + (uint32_t)__ffsll((long long)todo) - 1u, dm = w / cl, dl = w - dm * cl;
+			todo &= todo - 1ull;
+			if (e >= 2 && dm != at) {
+				p1 = deepen_action(prev, (int)dm);
+				deepen_move(s_act, p1, s, s1);
+				at = dm;
+			}
+			uint32_t s2[5];
+			deepen_move(s_act, deepen_action(p1, (int)dl), s1, s2);
+			lookups++;
+			if (sb_node(b, c, s2) != 0u) {
+				if (c.lane == 0) keep.lower(i, (uint32_t)(base + w));
+				return;                                              // every later rank of the item is above this one
+			}
+		}
+	}
+}
+
+// the items wave, wave + stride, ... of the job (wave and stride in whole waves; all 64 lanes of a wave call it)
+template <typename Keep, typename Prune = NoPrune>
+__device__ __forceinline__ void deepen_probe(const SymBallView &b, const DeepenJob &job, const SymProbe &c, size_t wave, size_t stride, const Keep &keep,
+                                             const Prune &prune = Prune{})
+{
+	[[maybe_unused]] unsigned long long lookups = 0;                     // (PdbPrune: the sb_node calls of this wave)
 	const u32x4 *s_act = c.s_act;
 	const int e = job.extra;
 	const uint32_t span = deepen_span(e);
@@ -144,6 +226,8 @@ __device__ __forceinline__ void deepen_probe(const SymBallView &b, const DeepenJ
 		load5(job.states + i * 5, s);
 		int prev = last;
 		bool exists = true;
+		if constexpr (Prune::on)
+			if (prune.left_uniform(s, e)) continue;                      // nothing of the ball within e moves of the state
 		if (e >= 3) {                                                    // the shared moves: the digits of g
 			uint32_t rem = g;
 			for (int k = 0; k < e - 2; k++) {
@@ -156,11 +240,17 @@ __device__ __forceinline__ void deepen_probe(const SymBallView &b, const DeepenJ
 				deepen_move(s_act, prev, s, t);
 				#pragma unroll
 				for (int j = 0; j < 5; j++) s[j] = t[j];
+				if constexpr (Prune::on)
+					if (prune.left_uniform(s, e - 1 - k)) { exists = false; break; }      // nor within the e - (k + 1) moves still to make
 			}
 		}
 		if (!exists) continue;
 		const uint32_t cm = e >= 3 ? 11u : e == 2 ? n0 : 1u;             // next-to-last moves, last moves
 		const uint32_t cl = e >= 2 ? 11u : n0;
+		if constexpr (Prune::on) {
+			deepen_pairs_pruned(b, c, prune, keep, i, e, s, prev, cm, cl, base, lo, hi, best, lookups);
+			continue;
+		}
 		bool hit = false;
 		for (uint32_t dm = 0; dm < cm && !hit; dm++) {
 			const long long r0 = base + (long long)dm * cl;
@@ -189,6 +279,8 @@ __device__ __forceinline__ void deepen_probe(const SymBallView &b, const DeepenJ
 			}
 		}
 	}
+	if constexpr (Prune::on)
+		if (prune.lookups != nullptr && c.lane == 0 && lookups != 0ull) atomicAdd(prune.lookups, lookups);
 }
 
 }  // namespace rk

@@ -20,6 +20,9 @@
 // kc / ke hold code 0 and are never ranked.  A move is lut4 on the five dwords (move5).  Every loop over the selected cubies is
 // unrolled to the maximum with a wave-uniform bound test, so nothing is indexed dynamically in registers.  A query gathers the
 // selected bytes of a row with v_perm_b32 by selectors made at create: what the other bytes hold cannot matter.
+//
+// A bound (rk_bound_*) is the descriptors of 1..4 built tables in one handle: rk_bound_depth answers the greatest entry of a
+// state over them in one launch, and the deepening probes of rk_sym.hip prune by it (rk_pdb_dev.h: pdb_bound).
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <climits>
@@ -29,23 +32,13 @@
 #include "rk_device.h"
 #include "rk_error.h"
 #include "rk_group_tables.h"
+#include "rk_pdb_dev.h"
 #include "rk_search_dev.h"
 
 namespace rk {
 
 constexpr int PDB_MAX_EDGES = 10;                   // ke = 11 or 12: the parity of the edge permutation is bound to the corners'
-constexpr int PDB_EDGE_SLOTS = 7;                   // the most edges a table of at most 2^31 entries has (eight: 5.1 G): what the loops unroll to
 constexpr int PDB_MAX_LEVELS = 59;                  // what rk_pdb_status has room for; no pattern comes near
-constexpr uint32_t PDB_UNREACHED = 255;
-
-struct PdbDesc {
-	uint8_t *table;                                 // `groups` * 16 bytes; the bytes past `size` stay 255
-	uint32_t size, groups;
-	uint32_t kc, ke;
-	uint32_t oc_digits;                             // corner orientation digits in the index: kc, 7 with all eight corners
-	uint32_t Oc, Pe;                                // 3^oc_digits, P(12, ke)
-	uint32_t sel_c[2], sel_lo[3], sel_hi[3];        // v_perm selectors: packed corners from row dwords 0..1, edges from 2..3 and from 4
-};
 
 constexpr uint32_t pdb_chi_bits()
 {
@@ -54,52 +47,6 @@ constexpr uint32_t pdb_chi_bits()
 	return b;
 }
 constexpr uint32_t PDB_CHI_BITS = pdb_chi_bits();
-
-__device__ __forceinline__ uint32_t pdb_div3(uint32_t x)
-{
-	const uint32_t t[6] = {GROUP_TABLES.div3[0], GROUP_TABLES.div3[1], GROUP_TABLES.div3[2], GROUP_TABLES.div3[3], GROUP_TABLES.div3[4],
-	                       GROUP_TABLES.div3[5]};
-	return lut4(x, t);
-}
-
-__device__ __forceinline__ uint32_t pdb_mod3(uint32_t x)
-{
-	const uint32_t t[6] = {GROUP_TABLES.mod3[0], GROUP_TABLES.mod3[1], GROUP_TABLES.mod3[2], GROUP_TABLES.mod3[3], GROUP_TABLES.mod3[4],
-	                       GROUP_TABLES.mod3[5]};
-	return lut4(x, t);
-}
-
-// byte i of a packed array of dwords, i a compile-time constant
-#define PDB_BYTE(w, i) (((w)[(i) >> 2] >> (8 * ((i) & 3))) & 0xFFu)
-
-// The index of packed selected codes, all below 24.  false: two selected cubies of a kind share a position (the index means nothing).
-__device__ __forceinline__ bool pdb_rank(const PdbDesc &p, const uint32_t c[2], const uint32_t e[3], uint32_t &index)
-{
-	const uint32_t pos4[2] = {pdb_div3(c[0]), pdb_div3(c[1])}, dig4[2] = {pdb_mod3(c[0]), pdb_mod3(c[1])};
-	uint32_t r = 0, o = 0, seen = 0, twice = 0;
-	#pragma unroll
-	for (int i = 0; i < 8; i++)
-		if ((uint32_t)i < p.kc) {
-			const uint32_t pos = PDB_BYTE(pos4, i) & 7u, bit = 1u << pos;
-			twice |= seen & bit;
-			r = r * (uint32_t)(8 - i) + pos - (uint32_t)__popc(seen & (bit - 1u));
-			seen |= bit;
-			if ((uint32_t)i < p.oc_digits) o = o * 3u + (PDB_BYTE(dig4, i) & 3u);
-		}
-	uint32_t x = r * p.Oc + o;
-	r = 0; o = 0; seen = 0;
-	#pragma unroll
-	for (int i = 0; i < PDB_EDGE_SLOTS; i++)
-		if ((uint32_t)i < p.ke) {
-			const uint32_t code = PDB_BYTE(e, i), pos = (code >> 1) & 15u, bit = 1u << pos;
-			twice |= seen & bit;
-			r = r * (uint32_t)(12 - i) + pos - (uint32_t)__popc(seen & (bit - 1u));
-			seen |= bit;
-			o = o * 2u + (code & 1u);
-		}
-	index = ((x * p.Pe + r) << p.ke) | o;
-	return twice == 0u;
-}
 
 // the d-th free position, ascending
 __device__ __forceinline__ uint32_t pdb_nth_free(uint32_t free, uint32_t d)
@@ -167,23 +114,6 @@ __device__ __forceinline__ void pdb_unrank(const PdbDesc &p, uint32_t index, uin
 		}
 }
 
-// The selected codes of a row, packed.  false: a selected code is 24 or more (or negative).
-__device__ __forceinline__ bool pdb_gather(const PdbDesc &p, const uint32_t x[5], uint32_t c[2], uint32_t e[3])
-{
-	uint32_t high = 0;
-	#pragma unroll
-	for (int j = 0; j < 2; j++) {
-		c[j] = bperm(x[1], x[0], p.sel_c[j]);
-		high |= ((c[j] & 0x7F7F7F7Fu) + 0x68686868u) | c[j];
-	}
-	#pragma unroll
-	for (int j = 0; j < 3; j++) {
-		e[j] = bperm(x[3], x[2], p.sel_lo[j]) | bperm(0u, x[4], p.sel_hi[j]);
-		high |= ((e[j] & 0x7F7F7F7Fu) + 0x68686868u) | e[j];
-	}
-	return (high & 0x80808080u) == 0u;
-}
-
 // a dword that has a zero byte: the classic test, exact for the question "is there one"
 __device__ __forceinline__ bool pdb_has_zero_byte(uint32_t v) { return ((v - 0x01010101u) & ~v & 0x80808080u) != 0u; }
 
@@ -249,6 +179,21 @@ void k_pdb_depth(PdbDesc p, const uint32_t *states, size_t n, int32_t *depth)
 		load5(states + q * 5, x);
 		const bool ok = pdb_gather(p, x, c, e) && pdb_rank(p, c, e, index) && index < p.size;
 		depth[q] = ok ? (int32_t)p.table[index] : -1;
+	}
+}
+
+// bound[q] = the greatest entry of row q over the tables of B, -1 where it has none in any of them
+__global__ __launch_bounds__(256)
+void k_bound_depth(PdbBound B, const uint32_t *states, size_t n, int32_t *bound)
+{
+	for (size_t q = (size_t)blockIdx.x * 256 + threadIdx.x; q < n; q += (size_t)gridDim.x * 256) {
+		uint32_t x[5];
+		load5(states + q * 5, x);
+		int best = -1;
+		#pragma unroll
+		for (int k = 0; k < PDB_BOUND_MAX; k++)
+			if (k < B.n) best = max(best, pdb_entry(B.db[k], x));
+		bound[q] = best;
 	}
 }
 
@@ -477,6 +422,44 @@ int rk_pdb_solve(rk_pdb_t *h, const int8_t *d_states, size_t n, int32_t *d_lengt
 	if (n == 0) return RK_OK;
 	hipLaunchKernelGGL(k_pdb_solve, dim3(pdb_grid(n)), dim3(256), 0, st, h->d, reinterpret_cast<const uint32_t *>(d_states), n,
 	                   (uint32_t)(h->levels - 1), d_lengths, d_actions, d_error);
+	RK_HIP(hipGetLastError());
+	return RK_OK;
+}
+
+int rk_bound_create(rk_bound_t **out, rk_pdb_t *const *dbs, int n)
+{
+	if (!out) return fail(RK_EINVAL, "rk_bound_create: null out pointer");
+	if (n < 1 || n > PDB_BOUND_MAX) return fail(RK_EINVAL, "rk_bound_create: %d databases outside 1..%d", n, PDB_BOUND_MAX);
+	if (!dbs) return fail(RK_EINVAL, "rk_bound_create: null pointer");
+	for (int k = 0; k < n; k++) {
+		if (!dbs[k]) return fail(RK_EINVAL, "rk_bound_create: database %d is null", k);
+		for (int j = 0; j < k; j++)
+			if (dbs[j] == dbs[k]) return fail(RK_EINVAL, "rk_bound_create: databases %d and %d are the same", j, k);
+	}
+	for (int k = 0; k < n; k++)
+		if (!dbs[k]->built) return fail(RK_ESTATE, "rk_bound_create: build database %d first", k);
+	rk_bound *h = new rk_bound();
+	for (int k = 0; k < n; k++) h->b.db[k] = dbs[k]->d;
+	h->b.n = n;
+	*out = h;
+	return RK_OK;
+}
+
+int rk_bound_destroy(rk_bound_t *h)
+{
+	delete h;
+	return RK_OK;
+}
+
+int rk_bound_depth(rk_bound_t *h, const int8_t *d_states, size_t n, int32_t *d_bound, void *stream)
+{
+	if (!h) return fail(RK_EINVAL, "rk_bound_depth: null handle");
+	if (n > (size_t)INT32_MAX) return fail(RK_EINVAL, "rk_bound_depth: %zu states in one launch", n);
+	if (n != 0 && (!d_states || !d_bound)) return fail(RK_EINVAL, "rk_bound_depth: null pointer");
+	if (((uintptr_t)d_states | (uintptr_t)d_bound) & 3u) return fail(RK_EINVAL, "rk_bound_depth: device pointers must be 4-byte aligned");
+	if (n == 0) return RK_OK;
+	hipLaunchKernelGGL(k_bound_depth, dim3(pdb_grid(n)), dim3(256), 0, (hipStream_t)stream, h->b, reinterpret_cast<const uint32_t *>(d_states), n,
+	                   d_bound);
 	RK_HIP(hipGetLastError());
 	return RK_OK;
 }

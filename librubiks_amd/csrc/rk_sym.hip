@@ -80,6 +80,8 @@
 // and probed, nothing kept but the lowest rank that hit (rk_deepen_dev.h: the words, their ranks, the item of a wave).
 //   k_sd_probe       a persistent grid, waves stride over the (state, 121 ranks) items, the tables staged once per workgroup; on
 //                    the caller's states (rk_sdeepen) or on rows of a search's pool with the stored action as the last move
+//   k_sd_probe_pruned  k_sd_probe with the words that an admissible bound of pattern databases rules out left unprobed
+//                    (rk_sdeepen_pruned, rk_sdeepen_nodes_pruned; rk_deepen_dev.h: PdbPrune): the same lowest ranks, fewer look-ups
 //   k_ss_setpops     one thread: a lower pop count for the iterations to come (the host lowers it when the pool is nearly full)
 //   k_ss_deepen_walk one wave: the path to a pool node, a word from it, then the descent from the moved state
 // In the batch (rk_sdeepenb_set, _frontiers, _probe, _keys, _paths) a slot whose pool is full goes on the
@@ -685,6 +687,16 @@ void k_sd_probe(SymBallView b, DeepenJob job, uint32_t *best)
 	             DeepenRanks{best});
 }
 
+// k_sd_probe with the words that an admissible bound rules out left unprobed (rk_deepen_dev.h: PdbPrune): the same `best`
+__global__ __launch_bounds__(256)
+void k_sd_probe_pruned(SymBallView b, DeepenJob job, uint32_t *best, PdbBound bound, unsigned long long *lookups)
+{
+	__shared__ uint32_t s_sym[SYM_LDS_DWORDS];
+	__shared__ u32x4 s_act[36];
+	deepen_probe(b, job, sym_probe(s_sym, 256, s_act), (size_t)blockIdx.x * 4 + (size_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), (size_t)gridDim.x * 4,
+	             DeepenRanks{best}, PdbPrune{bound, b.radius, lookups});
+}
+
 // the pops of the iterations to come; results do not depend on them.  One thread.
 __global__ void k_ss_setpops(FrontierDev d)
 {
@@ -937,9 +949,11 @@ int check_sym_states(const char *who, const void *d_states, size_t n)
 	return RK_OK;
 }
 
-// the range checks of a deepening launch and the launch itself
-int launch_deepen(const char *who, rk_symball *ball, DeepenJob job, uint32_t *best, hipStream_t st)
+// the range checks of a deepening launch and the launch itself; `bound` (null: every word is looked up) prunes, `lookups` counts
+int launch_deepen(const char *who, rk_symball *ball, DeepenJob job, uint32_t *best, hipStream_t st, const rk_bound *bound = nullptr,
+                  unsigned long long *lookups = nullptr)
 {
+	if ((uintptr_t)lookups & 7u) return fail(RK_EINVAL, "%s: d_lookups must be an 8-byte aligned device pointer", who);
 	if (job.extra < 1 || job.extra > DEEPEN_MAX_EXTRA) return fail(RK_EINVAL, "%s: extra %d outside 1..%d", who, job.extra, DEEPEN_MAX_EXTRA);
 	if ((unsigned long long)job.n * job.word_count > DEEPEN_MAX_PROBES)
 		return fail(RK_EINVAL, "%s: %zu states x %u words are more than the %llu probes of one launch", who, job.n, job.word_count, DEEPEN_MAX_PROBES);
@@ -948,7 +962,10 @@ int launch_deepen(const char *who, rk_symball *ball, DeepenJob job, uint32_t *be
 	if (job.n == 0 || job.word_count == 0 || job.word_first >= all) return RK_OK;
 	job.word_count = (uint32_t)std::min<unsigned long long>(job.word_count, all - job.word_first);
 	const size_t items = job.n * (size_t)deepen_groups(job.extra, job.word_first, job.word_count);
-	hipLaunchKernelGGL(k_sd_probe, dim3(sym_grid(items)), dim3(256), 0, st, ball->view, job, best);
+	if (bound != nullptr)
+		hipLaunchKernelGGL(k_sd_probe_pruned, dim3(sym_grid(items)), dim3(256), 0, st, ball->view, job, best, bound->b, lookups);
+	else
+		hipLaunchKernelGGL(k_sd_probe, dim3(sym_grid(items)), dim3(256), 0, st, ball->view, job, best);
 	RK_HIP(hipGetLastError());
 	return RK_OK;
 }
@@ -1243,14 +1260,28 @@ int rk_symball_child_depths(rk_symball_t *h, const int8_t *d_states, size_t n, i
 
 long long rk_sdeepen_max_probes(void) { return (long long)DEEPEN_MAX_PROBES; }
 
+// rk_sdeepen and rk_sdeepen_pruned (`bound` null: the former)
+static int sdeepen_states(const char *who, rk_symball *ball, const rk_bound *bound, const int8_t *d_states, const int8_t *d_last, size_t n, int extra,
+                          uint32_t word_first, uint32_t word_count, uint32_t *d_best, unsigned long long *d_lookups, void *stream)
+{
+	if (!ball) return fail(RK_EINVAL, "%s: null ball", who);
+	if (!ball->built) return fail(RK_ESTATE, "%s: build the ball first", who);
+	if (int e = check_sym_states(who, d_states, n)) return e;
+	return launch_deepen(who, ball, DeepenJob{reinterpret_cast<const uint32_t *>(d_states), d_last, -1, n, extra, word_first, word_count}, d_best,
+	                     (hipStream_t)stream, bound, d_lookups);
+}
+
 int rk_sdeepen(rk_symball_t *ball, const int8_t *d_states, const int8_t *d_last, size_t n, int extra, uint32_t word_first, uint32_t word_count,
                uint32_t *d_best, void *stream)
 {
-	if (!ball) return fail(RK_EINVAL, "rk_sdeepen: null ball");
-	if (!ball->built) return fail(RK_ESTATE, "rk_sdeepen: build the ball first");
-	if (int e = check_sym_states("rk_sdeepen", d_states, n)) return e;
-	return launch_deepen("rk_sdeepen", ball, DeepenJob{reinterpret_cast<const uint32_t *>(d_states), d_last, -1, n, extra, word_first, word_count}, d_best,
-	                     (hipStream_t)stream);
+	return sdeepen_states("rk_sdeepen", ball, nullptr, d_states, d_last, n, extra, word_first, word_count, d_best, nullptr, stream);
+}
+
+int rk_sdeepen_pruned(rk_symball_t *ball, rk_bound_t *bound, const int8_t *d_states, const int8_t *d_last, size_t n, int extra, uint32_t word_first,
+                      uint32_t word_count, uint32_t *d_best, unsigned long long *d_lookups, void *stream)
+{
+	if (!bound) return fail(RK_EINVAL, "rk_sdeepen_pruned: null bound");
+	return sdeepen_states("rk_sdeepen_pruned", ball, bound, d_states, d_last, n, extra, word_first, word_count, d_best, d_lookups, stream);
 }
 
 int rk_sshorten(rk_symball_t *h, const int8_t *d_actions, const int32_t *d_len, size_t n, int max_len, int window, int8_t *d_out_actions,
@@ -1374,17 +1405,31 @@ int rk_sdeepen_frontier(rk_ssearch_t *h, long long *h_out, void *stream)
 	return RK_OK;
 }
 
+// rk_sdeepen_nodes and rk_sdeepen_nodes_pruned (`bound` null: the former)
+static int sdeepen_nodes(const char *who, rk_ssearch *h, const rk_bound *bound, int extra, size_t node_first, size_t node_count, uint32_t word_first,
+                         uint32_t word_count, uint32_t *d_best, unsigned long long *d_lookups, void *stream)
+{
+	if (int e = FrontierPool::check_ready(h, who)) return e;
+	if (!h->ball->built) return fail(RK_ESTATE, "%s: build the ball first", who);
+	if (node_first < 1 || node_count > h->cap || node_first + node_count > h->cap + 1)
+		return fail(RK_EINVAL, "%s: nodes %zu..%zu outside the pool", who, node_first, node_first + node_count);
+	return launch_deepen(who, h->ball,
+	                     DeepenJob{h->d.states + node_first * 5, reinterpret_cast<const int8_t *>(h->d.pact) + node_first, 1 - (long long)node_first,
+	                               node_count, extra, word_first, word_count},
+	                     d_best, (hipStream_t)stream, bound, d_lookups);
+}
+
 int rk_sdeepen_nodes(rk_ssearch_t *h, int extra, size_t node_first, size_t node_count, uint32_t word_first, uint32_t word_count, uint32_t *d_best,
                       void *stream)
 {
-	if (int e = FrontierPool::check_ready(h, "rk_sdeepen_nodes")) return e;
-	if (!h->ball->built) return fail(RK_ESTATE, "rk_sdeepen_nodes: build the ball first");
-	if (node_first < 1 || node_count > h->cap || node_first + node_count > h->cap + 1)
-		return fail(RK_EINVAL, "rk_sdeepen_nodes: nodes %zu..%zu outside the pool", node_first, node_first + node_count);
-	return launch_deepen("rk_sdeepen_nodes", h->ball,
-	                     DeepenJob{h->d.states + node_first * 5, reinterpret_cast<const int8_t *>(h->d.pact) + node_first, 1 - (long long)node_first,
-	                               node_count, extra, word_first, word_count},
-	                     d_best, (hipStream_t)stream);
+	return sdeepen_nodes("rk_sdeepen_nodes", h, nullptr, extra, node_first, node_count, word_first, word_count, d_best, nullptr, stream);
+}
+
+int rk_sdeepen_nodes_pruned(rk_ssearch_t *h, rk_bound_t *bound, int extra, size_t node_first, size_t node_count, uint32_t word_first,
+                            uint32_t word_count, uint32_t *d_best, unsigned long long *d_lookups, void *stream)
+{
+	if (!bound) return fail(RK_EINVAL, "rk_sdeepen_nodes_pruned: null bound");
+	return sdeepen_nodes("rk_sdeepen_nodes_pruned", h, bound, extra, node_first, node_count, word_first, word_count, d_best, d_lookups, stream);
 }
 
 long long rk_sdeepen_path(rk_ssearch_t *h, long long node, int extra, uint32_t rank, long long *h_actions, size_t max_len, void *stream)

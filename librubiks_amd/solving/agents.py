@@ -832,7 +832,10 @@ class DeviceSymBall(_KeptBall):
 		most = int(_ffi.lib().rk_sdeepen_max_probes())
 		return most if self.deepen_cap is None else eng.int_in("deepen_cap", self.deepen_cap, 1, most)
 
-	def solve_beyond(self, states, extra: int, last_actions=None, time_limit: float = None):
+	probes = 0                              # after solve_beyond / distance / path with extra: the words issued ...
+	lookups = 0                             # ... and the ball look-ups made (fewer with `prune`)
+
+	def solve_beyond(self, states, extra: int, last_actions=None, time_limit: float = None, prune=None):
 		"""
 		(lengths int64 (n,), actions int64 (n, extra + radius)), rows padded with -1: shortest solutions past the radius by depth-first
 		probes (engine rk_sdeepen).  A state whose orbit the ball holds gets what `solve` gives.  The others run rounds
@@ -844,14 +847,23 @@ class DeviceSymBall(_KeptBall):
 		`last_actions` (n,) names the move that led to each state, -1 for none: words that begin with its opposite turn are not
 		tried.  That is right when the state before that move is known to be no nearer to the ball -- a search's parent --; a
 		caller that cannot say so passes None.  States are in the representation cube.get_is2024() names.
+
+		`prune` (a `DevicePatternBound`, or a list of 1..4 `DevicePatternDB` that is wrapped into one) leaves out look-ups that
+		cannot hit (engine rk_sdeepen_pruned).  With R the radius, a word of e moves that hits leads into the ball, so the state
+		after k of its moves is at most (e - k) + R from solved and its admissible bound is no greater: a state whose bound is
+		greater than R + (e - k) has no hit behind it, and every word through it is dropped.  No prefix of a hit word is ever
+		dropped, so the answers -- lengths and actions -- are those of the unpruned call, bit for bit.  Afterwards `probes` is the
+		words issued and `lookups` the ball look-ups made (equal without `prune`).
 		"""
 		extra = eng.int_in("extra", extra, 0, self.MAX_EXTRA)
+		prune = DevicePatternBound.of(prune)
 		self.build()
 		rows = self._rows(states)
-		return self._solve_beyond_of(torch.from_numpy(rows).to(gpu) if len(rows) else None, len(rows), extra, last_actions, time_limit)
+		return self._solve_beyond_of(torch.from_numpy(rows).to(gpu) if len(rows) else None, len(rows), extra, last_actions, time_limit, prune)
 
-	def _solve_beyond_of(self, q, n: int, extra: int, last_actions=None, time_limit: float = None):
-		"""`solve_beyond` of (n, 20) rows on the device (None for n = 0), `extra` checked."""
+	def _solve_beyond_of(self, q, n: int, extra: int, last_actions=None, time_limit: float = None, prune=None):
+		"""`solve_beyond` of (n, 20) rows on the device (None for n = 0), `extra` checked, `prune` a usable DevicePatternBound or None."""
+		self.probes = self.lookups = 0
 		width = extra + self.radius
 		last = None
 		if last_actions is not None:
@@ -862,13 +874,22 @@ class DeviceSymBall(_KeptBall):
 		if n == 0:
 			return lengths, actions
 		t0 = time.perf_counter()
-		lib, stream, cap = _ffi.lib(), _ffi.stream_ptr(), self._launch_cap()
 		got = torch.empty(n, dtype=torch.int32, device=gpu)
 		word = torch.empty((n, max(self.radius, 1)), dtype=torch.int8, device=gpu)
 		self._solve(q, n, got, word)
 		lengths[:] = got.cpu().numpy()
 		actions[:, :self.radius] = word.cpu().numpy()[:, :self.radius]
 		todo = np.nonzero(lengths < 0)[0]
+		looked = None if prune is None else torch.zeros(1, dtype=torch.int64, device=gpu)
+		try:
+			self._deepen_rounds(q, extra, last, time_limit, prune, looked, t0, todo, lengths, actions, word)
+		finally:
+			self.lookups = self.probes if looked is None else int(looked.item())
+		return lengths, actions
+
+	def _deepen_rounds(self, q, extra, last, time_limit, prune, looked, t0, todo, lengths, actions, word):
+		"""The rounds of `_solve_beyond_of` on the unanswered rows `todo`; fills `lengths` and `actions`, counts `probes`."""
+		lib, stream, cap = _ffi.lib(), _ffi.stream_ptr(), self._launch_cap()
 		for e in range(1, extra + 1):
 			m = len(todo)
 			if m == 0:
@@ -883,12 +904,17 @@ class DeviceSymBall(_KeptBall):
 				cnt = min(per, m - at)
 				step = min(words, cap // cnt)
 				for first in range(0, words, step):
-					_ffi.check(lib.rk_sdeepen(self._h, sub[at:].data_ptr(), None if d_last is None else d_last[at:].data_ptr(), cnt, e, first,
-					                          min(step, words - first), best[at:].data_ptr(), stream))
+					args = (sub[at:].data_ptr(), None if d_last is None else d_last[at:].data_ptr(), cnt, e, first, min(step, words - first),
+					        best[at:].data_ptr())
+					if prune is None:
+						_ffi.check(lib.rk_sdeepen(self._h, *args, stream))
+					else:
+						_ffi.check(lib.rk_sdeepen_pruned(self._h, prune._h, *args, looked.data_ptr(), stream))
+					self.probes += cnt * min(step, words - first)
 					if time_limit is not None:
 						torch.cuda.current_stream().synchronize()
 						if time.perf_counter() - t0 >= time_limit:
-							return lengths, actions
+							return
 			rank = best.cpu().numpy().view(np.uint32).astype(np.int64)
 			hit = np.nonzero(rank != 0xFFFFFFFF)[0]
 			if len(hit):
@@ -906,21 +932,21 @@ class DeviceSymBall(_KeptBall):
 				actions[todo[hit], :e] = moves
 				actions[todo[hit], e:e + self.radius] = word.cpu().numpy()[:len(hit), :self.radius]
 			todo = todo[rank == 0xFFFFFFFF]
-		return lengths, actions
 
-	def distance(self, a, b, extra: int = 0, check: bool = True) -> np.ndarray:
+	def distance(self, a, b, extra: int = 0, check: bool = True, prune=None) -> np.ndarray:
 		"""`_KeptBall.distance`; with `extra` > 0 pairs up to radius + extra quarter turns apart are answered, by `solve_beyond`'s
-		probes on the relative states (its lengths)."""
-		return self.path(a, b, extra, check)[0] if extra else super().distance(a, b, check)
+		probes on the relative states (its lengths); `prune` as there: fewer look-ups, the same answers."""
+		return self.path(a, b, extra, check, prune)[0] if extra else super().distance(a, b, check)
 
-	def path(self, a, b, extra: int = 0, check: bool = True):
+	def path(self, a, b, extra: int = 0, check: bool = True, prune=None):
 		"""`_KeptBall.path`; with `extra` > 0 through `solve_beyond`: (lengths, actions (n, extra + radius)), pairs up to radius +
-		extra quarter turns apart answered."""
+		extra quarter turns apart answered; `prune` as there: fewer look-ups, the same answers."""
 		extra = eng.int_in("extra", extra, 0, self.MAX_EXTRA)
 		if not extra:
 			return super().path(a, b, check)
+		prune = DevicePatternBound.of(prune)
 		q = self._relative(a, b, check)
-		return self._solve_beyond_of(q, 0 if q is None else len(q), extra)
+		return self._solve_beyond_of(q, 0 if q is None else len(q), extra, prune=prune)
 
 	def _depths_ranks(self, depths, ranks):
 		"""(depths int64 (n,), ranks int64 (n,)) of a `state_at` call, checked on the host: ValueError for anything but integers,
@@ -1071,7 +1097,8 @@ class DevicePatternDB(_ffi.Owner):
 	databases, is an admissible lower bound for every state.
 
 	Out of scope: goals other than the home positions; orientation-only or position-only patterns (not closed under the moves in
-	a cubie-indexed state); any use inside A*, MCTS or the beam.
+	a cubie-indexed state); any use inside A*, MCTS or the beam (the deepening probes of the symmetry ball read them:
+	`DevicePatternBound`).
 	"""
 	MAX_EDGES = 10
 	MAX_SIZE = 1 << 31
@@ -1226,6 +1253,64 @@ class DevicePatternDB(_ffi.Owner):
 
 	def __str__(self):
 		return f"Pattern database (device, corners={self.corner_cubies}, edges={self.edge_cubies}, {self.size} entries)"
+
+
+class DevicePatternBound(_ffi.Owner):
+	"""
+	An admissible lower bound from 1..4 pattern databases in one handle (engine rk_bound_*, csrc/rk_pdb.hip): the greatest of the
+	databases' depths of a state.  `depth(states)` is `DevicePatternDB.lower_bound(states, dbs)` in ONE launch, with the same
+	input rules (numpy in -> numpy out, device tensor in -> device tensor out, -1 only where every database answers -1).  The
+	databases are built if need be and kept alive by this object; ValueError for an empty list, more than four databases, a repeat
+	or anything that is no `DevicePatternDB`.
+
+	Its use is `prune=` of `DeviceSymBall.solve_beyond` / `distance` / `path` and of `DeviceSymBallSearch(deepen=E)`: the probes past
+	the ball skip every word behind a state whose bound shows that no state of the ball lies within the moves still to make.  The
+	bound is admissible, so no word that hits is skipped and the answers are the unpruned engine's, bit for bit.
+	"""
+	MAX_DBS = 4
+
+	def __init__(self, dbs):
+		try:
+			dbs = tuple(dbs)
+		except TypeError:
+			raise ValueError("dbs must be a sequence of DevicePatternDB") from None
+		if not 1 <= len(dbs) <= self.MAX_DBS or not all(isinstance(db, DevicePatternDB) for db in dbs):
+			raise ValueError(f"dbs must be 1..{self.MAX_DBS} DevicePatternDB, got {dbs!r}")
+		if len({id(db) for db in dbs}) != len(dbs):
+			raise ValueError("dbs must not repeat a database")
+		self.dbs = dbs
+		for db in dbs:
+			db.build()
+		handles = (C.c_void_p * len(dbs))(*(db._h.value for db in dbs))
+		self._create("rk_bound_create", "rk_bound_destroy", handles, len(dbs))
+
+	@classmethod
+	def of(cls, prune):
+		"""A `prune=` argument as the engines take it: None stays None, a `DevicePatternBound` must still be usable, a list of
+		databases is wrapped into one."""
+		if prune is None:
+			return None
+		bound = prune if isinstance(prune, cls) else cls(prune)
+		bound._need_handle()
+		return bound
+
+	def _need_handle(self):
+		"""ValueError for a bound that was freed, or whose databases were: the handle holds their tables' addresses."""
+		if self._h is None or not all(db.built for db in self.dbs):
+			raise ValueError("the pattern bound or one of its databases was freed")
+
+	def depth(self, states):
+		"""int32 (n,): the greatest of the databases' depths, an admissible lower bound on the distance to solved of every state.
+		One launch, no synchronisation for device tensors."""
+		self._need_handle()
+		q, dev = self.dbs[0]._rows(states)
+		n = len(q)
+		out = torch.empty(n, dtype=torch.int32, device=gpu)
+		_ffi.check(_ffi.lib().rk_bound_depth(self._h, q.data_ptr(), n, out.data_ptr(), _ffi.stream_ptr()))
+		return out if dev else out.cpu().numpy()
+
+	def __str__(self):
+		return "Pattern bound (device, " + "; ".join(f"corners={db.corner_cubies} edges={db.edge_cubies}" for db in self.dbs) + ")"
 
 
 class DeviceChainSolver(Agent, _ffi.Owner):
@@ -1407,16 +1492,27 @@ class DeviceSymBallSearch(_BallSearch):
 	optimal length L + e + radius, and does not depend on `pops`, the chunk or the launch cap.  Afterwards `deepened` is e (0: the
 	pool sufficed), `probes` the probes issued, `capacity_exhausted` stays True, len(agent) and `arrays()` are still the pool
 	(its partial next level included), and there is no meeting.  The time limit covers both phases.
+
+	`prune` (with `deepen` > 0 only; a `DevicePatternBound` or a list of 1..4 `DevicePatternDB`) leaves out the look-ups that an
+	admissible bound rules out (engine rk_sdeepen_nodes_pruned): a state whose bound exceeds the radius plus the moves still to
+	make has no state of the ball behind it, and no prefix of a word that hits is such a state.  The hits are therefore the same:
+	`action_queue`, `deepened` and `probes` are those of the search without `prune`, and `lookups` -- the ball look-ups made,
+	equal to `probes` without `prune` -- is what drops.
 	"""
 	_entries = "rk_ssearch"
 	_ball_type = DeviceSymBall
 	deepen_chunk = None                     # frontier nodes per chunk (None: as many as one launch takes with all their words)
 
-	def __init__(self, ball: DeviceSymBall, pops: int = 16_384, capacity: int = None, max_capacity: int = None, poll: int = 8, deepen: int = 0):
+	def __init__(self, ball: DeviceSymBall, pops: int = 16_384, capacity: int = None, max_capacity: int = None, poll: int = 8, deepen: int = 0,
+	             prune=None):
 		super().__init__(ball, pops, capacity, max_capacity, poll)
 		self.deepen = eng.int_in("deepen", deepen, 0, DeviceSymBall.MAX_EXTRA)
+		if prune is not None and not self.deepen:
+			raise ValueError("prune needs deepen > 0: only the probes past the pool are pruned")
+		self.prune = prune if prune is None or isinstance(prune, DevicePatternBound) else DevicePatternBound(prune)
 		self.deepened = 0
 		self.probes = 0
+		self.lookups = 0
 
 	def _grow(self, h) -> bool:
 		if not self.deepen or self._h_cap < self.max_capacity:
@@ -1442,12 +1538,22 @@ class DeviceSymBallSearch(_BallSearch):
 
 	@no_grad
 	def search(self, state: np.ndarray, time_limit: float = None, max_states: int = None) -> bool:
-		self.deepened, self.probes = 0, 0
+		self.deepened, self.probes, self.lookups = 0, 0, 0
+		if self.prune is not None:
+			self.prune._need_handle()
 		return super().search(state, time_limit, max_states)
 
 	def _deepen_search(self, h, t0: float, time_limit: float) -> str:
 		"""Rounds 1 .. `deepen` from the newest complete level of the pool: "hit" with `action_queue` and `deepened` set at the first
 		hit, "none" when no round has one, "time" when `time_limit` seconds since `t0` are over (looked at after every launch)."""
+		looked = None if self.prune is None else torch.zeros(1, dtype=torch.int64, device=gpu)
+		try:
+			return self._deepen_rounds(h, t0, time_limit, looked)
+		finally:
+			self.lookups = self.probes if looked is None else int(looked.item())
+
+	def _deepen_rounds(self, h, t0: float, time_limit: float, looked) -> str:
+		"""`_deepen_search`'s rounds; `looked`: the device word that counts the look-ups of a pruned search, None without `prune`."""
 		lib, stream = _ffi.lib(), _ffi.stream_ptr()
 		level = (C.c_longlong * 2)()
 		_ffi.check(lib.rk_sdeepen_frontier(h, level, stream))
@@ -1463,7 +1569,10 @@ class DeviceSymBallSearch(_BallSearch):
 				step = max(1, min(words, cap // cnt))
 				for first in range(0, words, step):
 					count = min(step, words - first)
-					_ffi.check(lib.rk_sdeepen_nodes(h, e, at, cnt, first, count, best.data_ptr(), stream))
+					if looked is None:
+						_ffi.check(lib.rk_sdeepen_nodes(h, e, at, cnt, first, count, best.data_ptr(), stream))
+					else:
+						_ffi.check(lib.rk_sdeepen_nodes_pruned(h, self.prune._h, e, at, cnt, first, count, best.data_ptr(), looked.data_ptr(), stream))
 					self.probes += cnt * count
 					torch.cuda.current_stream().synchronize()
 					if time.perf_counter() - t0 >= time_limit:
