@@ -659,6 +659,56 @@ int rk_chain_export(rk_chain_t *h, int stage, size_t first, size_t count, uint8_
 int rk_chain_solve(rk_chain_t *h, const int8_t *d_states, size_t n, int32_t *d_lengths, int8_t *d_actions, int32_t *d_stage_lengths,
                    int32_t *d_error, void *stream);
 
+/* ---- two-phase search: short solutions for every legal state (rk_twophase_*) --------------------------------------------------
+ * IDA* into the subgroup H = <F, B, TT, DD, LL, RR> (phase 1 = the chain's stages 1 + 2, the 12 quarter turns at cost 1), then
+ * IDA* inside it (phase 2 = stages 3 + 4, the generators F F' B B' (1) TT DD LL RR (2) in the chain's stage-3 order); the chain's
+ * answer is every row's first best, so an answer is never longer than rk_chain_solve's.  Four pruning tables, one byte per entry,
+ * the exact cost under the phase's generators; coordinates BY POSITION as the chain's (above):
+ *     table  phase  THE INDEX                                                                                    size        reached
+ *     1      1      twist * 495 + slice = the index of the chain's stage 2                                       2187 * 495  1 082 565
+ *     2      1      flip * 495 + slice, flip = the index of the chain's stage 1, slice = subset(positions of     2048 * 495  1 013 760
+ *                   slice 0's edges)
+ *     3      2      corners * 24 + places, corners = the lexicographic rank of P, places = q_0                   40320 * 24  967 680
+ *     4      2      edges * 24 + places, edges = the lexicographic rank of (place of the i-th edge outside       40320 * 24  967 680
+ *                   slice 0 among the eight positions outside slice 0, i = 0..7)
+ * MOVE PRUNING (both phases; a generator is named by its action a, a half turn by the even action; last, last2 = the two
+ * generators before it in the same phase): a is skipped if a == last ^ 1; if its face is the lower one of last's axis and last's
+ * face the upper (opposite faces commute: lower face first); if a == last and a is odd (X'X' = XX); if a == last == last2 (XXX);
+ * if a == last is a half turn of phase 2.  A cheapest word per element survives, so a phase's first solution is optimal for it.
+ * Children are taken in ascending order of a.
+ * THE SEARCH of a state: best = the chain's length; D = its phase-1 entry (the greater of tables 1 and 2); while D < best: depth-
+ * first over the phase-1 words of exactly D generators (a child is kept if depth + entry <= D), each of which ends in H and is a
+ * phase-1 solution p1 = D: for D2 = the phase-2 entry of the state behind it (the greater of tables 3 and 4) .. best - p1 - 1,
+ * depth-first over phase-2 words (a child is kept if cost + entry <= D2) up to the first child whose entry is 0: best = p1 + cost,
+ * the row is rewritten.  After the phase 2 of the `tries`-th phase-1 solution, or once D >= best, the search is over.
+ * THE BUDGET: a node is one child evaluation (a generator the move pruning lets through, its coordinates stepped, its two entries
+ * read) in either phase.  Immediately before each evaluation the state's counter is compared with max_nodes: if equal the search
+ * of that state ends, otherwise the counter goes up by one.  Nothing else counts.  The answer is a function of (state, tries,
+ * max_nodes) alone. */
+#define RK_TWOPHASE_GRID 1024   /* workgroups of 256 lanes the search has at most; a lane that ends a state takes the next row */
+typedef struct rk_twophase rk_twophase_t;
+/* Builds six u16 move tables (a coordinate under every generator) and the four pruning tables on the HOST -- level d + 1 takes the
+ * cost-1 children of level d and the cost-2 children of level d - 1 and stores only over unreached entries -- and uploads them on
+ * `stream` (5.6 MB).  RK_ESTATE unless every coordinate takes every value under its generators and every table reaches exactly the count
+ * above with one entry 0; RK_ECAPACITY when the device has no room.  Synchronises. */
+int rk_twophase_create(rk_twophase_t **out, void *stream);
+int rk_twophase_destroy(rk_twophase_t *h);
+/* h_status[16] = the four reached counts, the four deepest entries at [4..7], the four table sizes at [8..11], RK_TWOPHASE_GRID
+ * at [12], the workgroup size at [13], the longest row the search's stack holds at [14].  Touches no device. */
+int rk_twophase_status(rk_twophase_t *h, long long *h_status);
+/* Entries [first, first+count) of pruning table `table` (1..4) to HOST h_bytes uint8 (count).  Synchronises. */
+int rk_twophase_export(rk_twophase_t *h, int table, size_t first, size_t count, uint8_t *h_bytes, void *stream);
+/* TWO launches, stream-ordered without synchronisation: rk_chain_solve(chain, d_states, n, d_lengths, d_actions, NULL, d_error)
+ * with its limits and its treatment of rows that are no legal state, then the search, which replaces a row by every strictly
+ * shorter answer it finds (the bytes from the new length up to the length the row had are set to -1; the bytes beyond are not
+ * written).  tries >= 1, max_nodes >= 1.  d_phase_lengths int32 (n, 2): the moves of the answer before and inside H -- for a row
+ * that still holds the chain's answer the cost of its stages 1 + 2 and 3 + 4 --, -1 -1 for a row that is no legal state.
+ * d_reason int32 (n): 0 the search ended by itself and improved the chain's answer, 1 the budget ended it and the answer is from
+ * the search, 2 the row still holds the chain's answer.  d_nodes int64 (n, 8-byte aligned): the state's counter.  One handle
+ * serves one solve at a time (it owns the row counter).  RK_ESTATE if the chain's rows are wider than [14] of the status. */
+int rk_twophase_solve(rk_twophase_t *h, rk_chain_t *chain, const int8_t *d_states, size_t n, int tries, long long max_nodes, int32_t *d_lengths,
+                      int8_t *d_actions, int32_t *d_phase_lengths, int32_t *d_reason, long long *d_nodes, int32_t *d_error, void *stream);
+
 /* ---- the symmetry-reduced goal ball: one representative per orbit (rk_symball_*) -------------------------------------------
  * The canonical representatives of the states within `radius` quarter turns of solved, built once and kept in HBM; the depth of
  * a representative is the depth of the up to 48 states of its orbit.  Node 1 is the solved state, the pool is in index order: a

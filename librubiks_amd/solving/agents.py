@@ -1402,6 +1402,89 @@ class DeviceChainSolver(Agent, _ffi.Owner):
 		return "Subgroup chain solver (device)" + (f", shortened by {self.shorten}" if self.shorten is not None else "")
 
 
+class DeviceTwoPhaseSolver(Agent, _ffi.Owner):
+	"""
+	SHORT solutions for every legal state, batched on the device, by search and without a net (engine rk_twophase_*,
+	csrc/rk_twophase.hip): IDA* over the 12 quarter turns into the subgroup <F, B, TT, DD, LL, RR> -- the one the chain's stage 3
+	starts in --, then IDA* inside it, over four pruning tables of exact costs and six move tables built on the host when the solver
+	is made (5.6 MB in HBM).  The chain's answer (`chain`, a `DeviceChainSolver`; one is made and kept when none is passed) is every
+	row's first best, so an answer is never longer than the chain's and the search never fails.  `tries` = the phase-1 solutions
+	whose phase 2 is searched, `max_nodes` = the child evaluations a state may cost; the answer is a function of (state, tries,
+	max_nodes) alone (include/rubiks_hip.h states the move-pruning and the budget rule, DESIGN 3.59.9 the kernel).  The defaults of
+	`tries` and `max_nodes` were provisional until benchmarks/two_phase.py had run; they are now chosen from that run
+	(profiles/r29_two_phase.json): on 40-move scrambles 35.8 moves on average against the chain's 48.4 at 85 000
+	states/s, where max_nodes = 2^16 leaves 84 % of the rows with the chain's answer.
+
+	`solve(states)` has `DeviceChainSolver.solve`'s rules: numpy in -> numpy out, device tensor in -> device tensor out, states in the
+	representation cube.get_is2024() names, a row that is no legal state a ValueError naming the lowest such row or, with
+	`allow_illegal`, length -1 (phase lengths -1, actions all -1, reason 2, no node).  As an agent it plays in `Evaluator` and under
+	`TowardsGoal`; `shorten=ball` pipes every queue through `ball.shorten`.
+	"""
+	GRID_ROWS = 1024 * 256                  # RK_TWOPHASE_GRID workgroups of 256 lanes: beyond this many rows a lane takes several
+
+	def __init__(self, chain=None, tries: int = 8, max_nodes: int = 1 << 20, shorten=None, allow_illegal: bool = False):
+		Agent.__init__(self)
+		if chain is not None and not isinstance(chain, DeviceChainSolver):
+			raise ValueError("chain must be a DeviceChainSolver or None")
+		if shorten is not None and not isinstance(shorten, _KeptBall):
+			raise ValueError("shorten must be a DeviceGoalBall, a DeviceSymBall or None")
+		self.tries = eng.int_in("tries", tries, 1, (1 << 31) - 1)
+		self.max_nodes = eng.int_in("max_nodes", max_nodes, 1, _ffi.INT64_MAX)
+		self.shorten, self.allow_illegal = shorten, bool(allow_illegal)
+		_ffi.require_gpu()
+		self.chain = chain if chain is not None else DeviceChainSolver()
+		self._create("rk_twophase_create", "rk_twophase_destroy", _ffi.stream_ptr())
+		status = (C.c_longlong * 16)()
+		_ffi.check(_ffi.lib().rk_twophase_status(self._h, status))
+		self.table_counts = tuple(int(v) for v in status[0:4])
+		self.table_depths = tuple(int(v) for v in status[4:8])           # the deepest entry of each pruning table
+		self.table_sizes = tuple(int(v) for v in status[8:12])
+		self.grid_rows = int(status[12]) * int(status[13])
+		self.max_length = self.chain.max_length                          # the row length of `solve`'s actions
+
+	_rows = DevicePatternDB._rows
+	_shortened = DeviceChainSolver._shortened
+
+	def solve(self, states, phase_lengths: bool = False, details: bool = False):
+		"""(lengths int32 (n,), actions int8 (n, max_length) padded with -1[, phase lengths int32 (n, 2)][, reason int32 (n,), nodes
+		int64 (n,)]): reason 0 = the search ended by itself and improved the chain's answer, 1 = the budget ended it and the answer is
+		from the search, 2 = the row holds the chain's answer.  Two launches; reading the error word (not with `allow_illegal`) is the
+		call's one host read.  With `shorten` the queues come back through `ball.shorten` (lengths and actions then describe the
+		shortened queues; phase lengths, reason and nodes stay the search's own)."""
+		if self.chain._h is None:
+			raise ValueError("the chain solver was freed")
+		q, dev = self._rows(states)
+		n = len(q)
+		lengths = torch.empty(n, dtype=torch.int32, device=gpu)
+		actions = torch.full((n, self.max_length), -1, dtype=torch.int8, device=gpu)
+		phases = torch.empty((n, 2), dtype=torch.int32, device=gpu)
+		reason = torch.empty(n, dtype=torch.int32, device=gpu)
+		nodes = torch.empty(n, dtype=torch.int64, device=gpu)
+		err = None if self.allow_illegal else torch.full((1,), -1, dtype=torch.int32, device=gpu)
+		_ffi.check(_ffi.lib().rk_twophase_solve(self._h, self.chain._h, q.data_ptr(), n, self.tries, self.max_nodes, lengths.data_ptr(),
+		                                        actions.data_ptr(), phases.data_ptr(), reason.data_ptr(), nodes.data_ptr(),
+		                                        None if err is None else err.data_ptr(), _ffi.stream_ptr()))
+		if err is not None and int(err.item()) >= 0:
+			raise ValueError(f"row {int(err.item())} of states is not a legal cube state (the lowest such row)")
+		if self.shorten is not None and n:
+			lengths, actions = self._shortened(lengths, actions)
+		out = (lengths, actions) + ((phases,) if phase_lengths else ()) + ((reason, nodes) if details else ())
+		return out if dev else tuple(t.cpu().numpy() for t in out)
+
+	def export(self, table: int) -> np.ndarray:
+		"""uint8 (table_sizes[table - 1],): pruning table 1..4, entry by index (every entry is reached)."""
+		table = eng.int_in("table", table, 1, 4, what="a table 1..4")
+		out = np.empty(self.table_sizes[table - 1], np.uint8)
+		_ffi.check(_ffi.lib().rk_twophase_export(self._h, table, 0, len(out), out.ctypes.data, _ffi.stream_ptr()))
+		return out
+
+	search = DeviceChainSolver.search
+
+	def __str__(self):
+		return f"Two-phase solver (device, tries={self.tries}, max_nodes={self.max_nodes})" + \
+			(f", shortened by {self.shorten}" if self.shorten is not None else "")
+
+
 class _BallSearch(_PoolSearch):
 	"""What `DeviceBallSearch` and `DeviceSymBallSearch` share on top of `_PoolSearch`: the ball they end at (`_ball_type` is its
 	kind), the meeting and the levels around the start.  Their engines have one argument list and one status layout."""
