@@ -12,8 +12,9 @@
 // 0, the three slices (the edges neither face of an axis moves), the generators of every stage.  The corner sequences of the
 // half-turn group (C3, 96 of them) and the coset map (40 320 entries, 420 cosets) come from a closure at create time.
 //
-// The build is on the host: level d + 1 takes the cost-1 children of level d and the cost-2 children of level d - 1 and stores
-// only over "unreached", so a table does not depend on the visiting order; one representative state per coset carries the search.
+// The build is on the host, build_cost_table of rk_table_host.h: level d + 1 takes the cost-1 children of level d and the cost-2
+// children of level d - 1 and stores only over "unreached", so a table does not depend on the visiting order; one representative
+// state per coset carries the search.  The tables and the two maps go to the device as one TableBlock.
 // The coset counts 2 048 / 1 082 565 / 29 400 / 663 552 are conditions: any other count is RK_ESTATE.
 //
 // The query is ONE launch, a thread per state under a capped grid, the per-action tables staged in LDS once per workgroup, the
@@ -24,8 +25,6 @@
 // and every descent is bounded by the stage's deepest entry.
 #include <hip/hip_runtime.h>
 #include <algorithm>
-#include <array>
-#include <climits>
 #include <cstring>
 #include <vector>
 
@@ -35,6 +34,8 @@
 #include "rk_error.h"
 #include "rk_group_dev.h"
 #include "rk_search_dev.h"
+#include "rk_search_host.h"
+#include "rk_table_host.h"
 
 namespace rk {
 
@@ -139,40 +140,7 @@ struct rk_chain {
 
 namespace {
 
-typedef std::array<uint32_t, 5> ChainState;
-
 unsigned chain_grid(size_t n) { return (unsigned)std::min<size_t>((n + 255) / 256, (size_t)RK_CHAIN_GRID); }
-
-const Tables &chain_tables()
-{
-	static const Tables t = make_tables();
-	return t;
-}
-
-ChainState chain_move(const ChainState &s, int action)
-{
-	const Tables &t = chain_tables();
-	uint8_t b[STATE_BYTES];
-	memcpy(b, s.data(), STATE_BYTES);
-	for (int i = 0; i < 8; i++) b[i] = t.lut[action][0][b[i]];
-	for (int i = 8; i < STATE_BYTES; i++) b[i] = t.lut[action][1][b[i]];
-	ChainState out;
-	memcpy(out.data(), b, STATE_BYTES);
-	return out;
-}
-
-ChainState chain_generate(const ChainState &s, int stage, int g)
-{
-	ChainState out = chain_move(s, CHAIN.gen_action[stage][g]);
-	return CHAIN.gen_cost[stage][g] == 2 ? chain_move(out, CHAIN.gen_action[stage][g]) : out;
-}
-
-ChainState chain_solved()
-{
-	ChainState s;
-	memcpy(s.data(), chain_tables().solved, STATE_BYTES);
-	return s;
-}
 
 // The two corner maps.  C3: the corner sequences that the half turns reach from solved, by a closure.  coset[r]: sequences P and
 // P o h, h in C3 (the cubies relabelled), share a coset -- the side on which a move, which acts on the positions, maps cosets to
@@ -180,13 +148,13 @@ ChainState chain_solved()
 bool chain_corner_maps(std::vector<uint16_t> &coset, std::vector<uint8_t> &c3)
 {
 	std::vector<uint8_t> in_c3(CHAIN_PERMS, 0);
-	std::vector<ChainState> todo{chain_solved()};
+	std::vector<HostState> todo{host_solved()};
 	in_c3[chain_corner_rank(todo[0].data())] = 1;
 	while (!todo.empty()) {
-		const ChainState s = todo.back();
+		const HostState s = todo.back();
 		todo.pop_back();
 		for (int g = 0; g < CHAIN.gen_count[3]; g++) {
-			const ChainState c = chain_generate(s, 3, g);
+			const HostState c = host_generate(s, CHAIN.gen_action[3][g], CHAIN.gen_cost[3][g]);
 			const uint32_t r = chain_corner_rank(c.data());
 			if (!in_c3[r]) {
 				in_c3[r] = 1;
@@ -229,38 +197,16 @@ bool chain_corner_maps(std::vector<uint16_t> &coset, std::vector<uint8_t> &c3)
 	return cosets == CHAIN_COSETS;
 }
 
-// One table: see the head of this file.  Returns the deepest entry, -1 unless exactly CHAIN_COUNT[STAGE] entries were reached and
-// one of them is 0.
+// One table: build_cost_table (rk_table_host.h) over the stage's generators, one representative state per coset.  Returns the
+// deepest entry, -1 unless exactly CHAIN_COUNT[STAGE] entries were reached and one of them is 0.  The index is forced inline: the
+// builder calls it at two places, and left as a call the later stages' builds take a third longer.
 template <int STAGE>
 int chain_build(std::vector<uint8_t> &table, const uint16_t *coset, const uint8_t *c3, long long &count)
 {
-	table.assign(CHAIN_SIZE[STAGE], (uint8_t)CHAIN_UNREACHED);
-	std::vector<ChainState> before, level{chain_solved()}, next;        // levels d - 1, d, d + 1: one representative per entry
-	const uint32_t goal = chain_index<STAGE>(level[0].data(), coset, c3);
-	if (goal >= CHAIN_SIZE[STAGE]) return -1;
-	table[goal] = 0;
-	count = 1;
-	int d = 0;
-	for (; !level.empty() || !before.empty(); d++) {
-		if (d + 1 >= (int)CHAIN_UNREACHED) return -1;
-		next.clear();
-		for (int g = 0; g < CHAIN.gen_count[STAGE]; g++)
-			for (const ChainState &s : CHAIN.gen_cost[STAGE][g] == 1 ? level : before) {
-				const ChainState c = chain_generate(s, STAGE, g);
-				const uint32_t index = chain_index<STAGE>(c.data(), coset, c3);
-				if (index >= CHAIN_SIZE[STAGE]) return -1;
-				if (table[index] != CHAIN_UNREACHED) continue;
-				table[index] = (uint8_t)(d + 1);
-				next.push_back(c);
-			}
-		count += (long long)next.size();
-		before.swap(level);
-		level.swap(next);
-	}
-	long long zeros = 0;
-	for (uint8_t v : table) zeros += v == 0;
-	if (count != (long long)CHAIN_COUNT[STAGE] || zeros != 1) return -1;
-	return d - 2;                                                        // the last two levels were empty
+	return build_cost_table(
+		table, CHAIN_SIZE[STAGE], (long long)CHAIN_COUNT[STAGE], CHAIN.gen_count[STAGE], CHAIN.gen_cost[STAGE], host_solved(),
+		[](const HostState &s, int g) { return host_generate(s, CHAIN.gen_action[STAGE][g], CHAIN.gen_cost[STAGE][g]); },
+		[=](const HostState &s) __attribute__((always_inline)) { return chain_index<STAGE>(s.data(), coset, c3); }, count);
 }
 
 }  // namespace
@@ -286,40 +232,21 @@ int rk_chain_create(rk_chain_t **out, void *stream)
 			delete h;
 			return fail(RK_ESTATE, "rk_chain_create: the table of stage %d reached %lld cosets, not %u with one goal", s + 1, got, CHAIN_COUNT[s]);
 		}
-	// one block: the tables, then the maps, each 16-byte aligned
-	size_t at[CHAIN_STAGES + 2], bytes = 0;
-	for (int s = 0; s < CHAIN_STAGES; s++) {
-		at[s] = bytes;
-		bytes += ((size_t)CHAIN_SIZE[s] + 15) / 16 * 16;
-	}
-	at[CHAIN_STAGES] = bytes;
-	bytes += (size_t)CHAIN_PERMS * sizeof(uint16_t);
-	at[CHAIN_STAGES + 1] = bytes;
-	bytes += CHAIN_PERMS;
-	if (hipMalloc((void **)&h->d_block, bytes) != hipSuccess) {
-		(void)hipGetLastError();
-		h->d_block = nullptr;
-		delete h;
-		return fail(RK_ECAPACITY, "rk_chain_create: no device memory for %zu bytes of tables", bytes);
-	}
-	hipStream_t st = (hipStream_t)stream;
-	const auto upload = [&]() -> int {
-		for (int s = 0; s < CHAIN_STAGES; s++) RK_HIP(hipMemcpyAsync(h->d_block + at[s], table[s].data(), CHAIN_SIZE[s], hipMemcpyHostToDevice, st));
-		RK_HIP(hipMemcpyAsync(h->d_block + at[CHAIN_STAGES], coset.data(), (size_t)CHAIN_PERMS * sizeof(uint16_t), hipMemcpyHostToDevice, st));
-		RK_HIP(hipMemcpyAsync(h->d_block + at[CHAIN_STAGES + 1], c3.data(), CHAIN_PERMS, hipMemcpyHostToDevice, st));
-		RK_HIP(hipStreamSynchronize(st));                                   // the host copies go out of scope
-		return RK_OK;
-	};
-	if (int e = upload()) {
+	TableBlock block;                                                   // the tables, then the maps
+	for (int s = 0; s < CHAIN_STAGES; s++) block.add(table[s].data(), CHAIN_SIZE[s]);
+	block.add(coset.data(), (size_t)CHAIN_PERMS * sizeof(uint16_t));
+	block.add(c3.data(), CHAIN_PERMS);
+	if (int e = block.upload("rk_chain_create", (hipStream_t)stream)) {
 		delete h;
 		return e;
 	}
 	for (int s = 0; s < CHAIN_STAGES; s++) {
-		h->d.table[s] = h->d_block + at[s];
+		h->d.table[s] = block.at(s);
 		h->d.depth[s] = (uint32_t)depth[s];
 	}
-	h->d.coset = reinterpret_cast<const uint16_t *>(h->d_block + at[CHAIN_STAGES]);
-	h->d.c3 = h->d_block + at[CHAIN_STAGES + 1];
+	h->d.coset = block.at<uint16_t>(CHAIN_STAGES);
+	h->d.c3 = block.at(CHAIN_STAGES + 1);
+	h->d_block = block.release();
 	*out = h;
 	return RK_OK;
 }
@@ -346,24 +273,16 @@ int rk_chain_status(rk_chain_t *h, long long *h_status)
 int rk_chain_export(rk_chain_t *h, int stage, size_t first, size_t count, uint8_t *h_bytes, void *stream)
 {
 	if (!h) return fail(RK_EINVAL, "rk_chain_export: null handle");
-	if (stage < 1 || stage > CHAIN_STAGES) return fail(RK_EINVAL, "rk_chain_export: stage %d outside 1..%d", stage, CHAIN_STAGES);
-	const size_t size = CHAIN_SIZE[stage - 1];
-	if (first > size || count > size - first) return fail(RK_EINVAL, "rk_chain_export: entries %zu..%zu outside the table", first, first + count);
-	if (count == 0) return RK_OK;
-	if (!h_bytes) return fail(RK_EINVAL, "rk_chain_export: null pointer");
-	hipStream_t st = (hipStream_t)stream;
-	RK_HIP(hipMemcpyAsync(h_bytes, h->d.table[stage - 1] + first, count, hipMemcpyDeviceToHost, st));
-	RK_HIP(hipStreamSynchronize(st));
-	return RK_OK;
+	return export_table("rk_chain_export", "stage", stage, CHAIN_STAGES, h->d.table, CHAIN_SIZE, first, count, h_bytes, stream);
 }
 
 int rk_chain_solve(rk_chain_t *h, const int8_t *d_states, size_t n, int32_t *d_lengths, int8_t *d_actions, int32_t *d_stage_lengths,
                    int32_t *d_error, void *stream)
 {
 	if (!h) return fail(RK_EINVAL, "rk_chain_solve: null handle");
-	if (n > (size_t)INT32_MAX) return fail(RK_EINVAL, "rk_chain_solve: %zu states in one launch", n);
-	if (n != 0 && (!d_states || !d_lengths || !d_actions)) return fail(RK_EINVAL, "rk_chain_solve: null pointer");
-	if (((uintptr_t)d_states | (uintptr_t)d_lengths | (uintptr_t)d_stage_lengths | (uintptr_t)d_error) & 3u)
+	if (int e = check_state_rows("rk_chain_solve", d_states, n)) return e;
+	if (n != 0 && (!d_lengths || !d_actions)) return fail(RK_EINVAL, "rk_chain_solve: null pointer");
+	if (((uintptr_t)d_lengths | (uintptr_t)d_stage_lengths | (uintptr_t)d_error) & 3u)
 		return fail(RK_EINVAL, "rk_chain_solve: device pointers must be 4-byte aligned");
 	if (n == 0) return RK_OK;
 	hipStream_t st = (hipStream_t)stream;

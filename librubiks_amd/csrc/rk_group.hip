@@ -26,6 +26,7 @@
 #include "rk_group_dev.h"
 #include "rk_group_tables.h"
 #include "rk_search_dev.h"
+#include "rk_search_host.h"
 
 namespace rk {
 
@@ -173,15 +174,6 @@ bool group_overlap(const void *p, size_t p_bytes, const void *q, size_t q_bytes)
 	return a < b + q_bytes && b < a + p_bytes;
 }
 
-// n rows of device states: the checks of check_sym_states (rk_sym.hip)
-int check_group_rows(const char *who, const void *d_rows, size_t n)
-{
-	if (n > (size_t)INT32_MAX) return fail(RK_EINVAL, "%s: %zu states in one launch", who, n);
-	if (n != 0 && !d_rows) return fail(RK_EINVAL, "%s: null pointer", who);
-	if ((uintptr_t)d_rows & 3u) return fail(RK_EINVAL, "%s: device pointers must be 4-byte aligned", who);
-	return RK_OK;
-}
-
 // the output may be exactly an operand of n rows; any other overlap is a race between threads
 int check_group_out(const char *who, const void *d_out, size_t n, const void *d_in, size_t in_rows)
 {
@@ -194,10 +186,10 @@ int check_group_out(const char *who, const void *d_out, size_t n, const void *d_
 template <int OP>
 int group_binary(const char *who, const int8_t *d_a, size_t n, const int8_t *d_b, size_t b_rows, int8_t *d_out, void *stream)
 {
-	if (int e = check_group_rows(who, d_a, n)) return e;
+	if (int e = check_state_rows(who, d_a, n)) return e;
 	if (b_rows != n && b_rows != 1) return fail(RK_EINVAL, "%s: %zu second operands for %zu states: one, or one for each", who, b_rows, n);
-	if (int e = check_group_rows(who, d_b, n)) return e;
-	if (int e = check_group_rows(who, d_out, n)) return e;
+	if (int e = check_state_rows(who, d_b, n)) return e;
+	if (int e = check_state_rows(who, d_out, n)) return e;
 	if (n == 0) return RK_OK;
 	if (int e = check_group_out(who, d_out, n, d_a, n)) return e;
 	if (int e = check_group_out(who, d_out, n, d_b, b_rows)) return e;
@@ -227,8 +219,8 @@ int rk_group_apply(const int8_t *d_states, size_t n, const int8_t *d_effects, si
 
 int rk_group_inverse(const int8_t *d_states, size_t n, int8_t *d_out, void *stream)
 {
-	if (int e = check_group_rows("rk_group_inverse", d_states, n)) return e;
-	if (int e = check_group_rows("rk_group_inverse", d_out, n)) return e;
+	if (int e = check_state_rows("rk_group_inverse", d_states, n)) return e;
+	if (int e = check_state_rows("rk_group_inverse", d_out, n)) return e;
 	if (n == 0) return RK_OK;
 	if (int e = check_group_out("rk_group_inverse", d_out, n, d_states, n)) return e;
 	hipLaunchKernelGGL((k_group<GROUP_INVERSE>), dim3(group_grid(n)), dim3(256), 0, (hipStream_t)stream,
@@ -244,7 +236,7 @@ int rk_group_relative(const int8_t *d_states, size_t n, const int8_t *d_goals, s
 
 int rk_group_legal(const int8_t *d_states, size_t n, uint8_t *d_flags, long long *d_stats, void *stream)
 {
-	if (int e = check_group_rows("rk_group_legal", d_states, n)) return e;
+	if (int e = check_state_rows("rk_group_legal", d_states, n)) return e;
 	if (d_stats && ((uintptr_t)d_stats & 7u)) return fail(RK_EINVAL, "rk_group_legal: stats must be 8-byte aligned");
 	if (n == 0) return RK_OK;
 	if (!d_flags && !d_stats) return fail(RK_EINVAL, "rk_group_legal: null pointer");

@@ -34,6 +34,8 @@
 #include "rk_group_tables.h"
 #include "rk_pdb_dev.h"
 #include "rk_search_dev.h"
+#include "rk_search_host.h"
+#include "rk_table_host.h"
 
 namespace rk {
 
@@ -275,10 +277,8 @@ int check_pdb_queries(const char *who, const rk_pdb *h, const void *d_states, si
 {
 	if (!h) return fail(RK_EINVAL, "%s: null handle", who);
 	if (!h->built) return fail(RK_ESTATE, "%s: build the table first", who);
-	if (n > (size_t)INT32_MAX) return fail(RK_EINVAL, "%s: %zu states in one launch", who, n);
-	if (n != 0 && (!d_states || !out)) return fail(RK_EINVAL, "%s: null pointer", who);
-	if (((uintptr_t)d_states | (uintptr_t)out) & 3u) return fail(RK_EINVAL, "%s: device pointers must be 4-byte aligned", who);
-	return RK_OK;
+	if (int e = check_state_rows(who, d_states, n)) return e;
+	return check_state_rows(who, out, n);                                   // the output: n dwords, the same three tests
 }
 
 }  // namespace
@@ -392,14 +392,7 @@ int rk_pdb_export(rk_pdb_t *h, size_t first, size_t count, uint8_t *h_bytes, voi
 {
 	if (!h) return fail(RK_EINVAL, "rk_pdb_export: null handle");
 	if (!h->built) return fail(RK_ESTATE, "rk_pdb_export: build the table first");
-	if (first > (size_t)h->d.size || count > (size_t)h->d.size - first)
-		return fail(RK_EINVAL, "rk_pdb_export: entries %zu..%zu outside the table", first, first + count);
-	if (count == 0) return RK_OK;
-	if (!h_bytes) return fail(RK_EINVAL, "rk_pdb_export: null pointer");
-	hipStream_t st = (hipStream_t)stream;
-	RK_HIP(hipMemcpyAsync(h_bytes, h->d.table + first, count, hipMemcpyDeviceToHost, st));
-	RK_HIP(hipStreamSynchronize(st));
-	return RK_OK;
+	return export_table("rk_pdb_export", "table", 1, 1, &h->d.table, &h->d.size, first, count, h_bytes, stream);
 }
 
 int rk_pdb_depth(rk_pdb_t *h, const int8_t *d_states, size_t n, int32_t *d_depth, void *stream)
@@ -454,9 +447,8 @@ int rk_bound_destroy(rk_bound_t *h)
 int rk_bound_depth(rk_bound_t *h, const int8_t *d_states, size_t n, int32_t *d_bound, void *stream)
 {
 	if (!h) return fail(RK_EINVAL, "rk_bound_depth: null handle");
-	if (n > (size_t)INT32_MAX) return fail(RK_EINVAL, "rk_bound_depth: %zu states in one launch", n);
-	if (n != 0 && (!d_states || !d_bound)) return fail(RK_EINVAL, "rk_bound_depth: null pointer");
-	if (((uintptr_t)d_states | (uintptr_t)d_bound) & 3u) return fail(RK_EINVAL, "rk_bound_depth: device pointers must be 4-byte aligned");
+	if (int e = check_state_rows("rk_bound_depth", d_states, n)) return e;
+	if (int e = check_state_rows("rk_bound_depth", d_bound, n)) return e;
 	if (n == 0) return RK_OK;
 	hipLaunchKernelGGL(k_bound_depth, dim3(pdb_grid(n)), dim3(256), 0, (hipStream_t)stream, h->b, reinterpret_cast<const uint32_t *>(d_states), n,
 	                   d_bound);

@@ -216,6 +216,16 @@ inline int read_walk(const int32_t *walk, size_t walk_max, long long *h_actions,
 	return export_widened(walk + 1, std::min(std::min((size_t)*len, max_len), walk_max), h_actions, st);
 }
 
+// n rows of 20-byte device states, read as dwords, as every batched entry takes them: the caller checks its handle first, then
+// this, then its own arguments
+inline int check_state_rows(const char *who, const void *d_rows, size_t n)
+{
+	if (n > (size_t)INT32_MAX) return fail(RK_EINVAL, "%s: %zu states in one launch", who, n);
+	if (n != 0 && !d_rows) return fail(RK_EINVAL, "%s: null pointer", who);
+	if ((uintptr_t)d_rows & 3u) return fail(RK_EINVAL, "%s: device pointers must be 4-byte aligned", who);
+	return RK_OK;
+}
+
 // ---- what the net-stepped engines share (rk_egvm.hip, rk_greedy.hip, rk_beam.hip): they own the net's batch, per RK_OH_* form ----
 // bytes of a batch row: the 20-byte state, or 480 one-hot elements of 4 or 2 bytes (write_row, rk_search_dev.h)
 inline size_t net_row_bytes(int code) { return code == RK_OH_STATES ? 20 : code == RK_OH_F32 ? 1920 : 960; }

@@ -941,14 +941,6 @@ size_t sb_default_capacity(int radius)
 
 unsigned sym_grid(size_t waves) { return std::min(blocks(waves, 4), SYM_GRID); }
 
-int check_sym_states(const char *who, const void *d_states, size_t n)
-{
-	if (n > (size_t)INT32_MAX) return fail(RK_EINVAL, "%s: %zu states in one launch", who, n);
-	if (n != 0 && !d_states) return fail(RK_EINVAL, "%s: null pointer", who);
-	if ((uintptr_t)d_states & 3u) return fail(RK_EINVAL, "%s: device pointers must be 4-byte aligned", who);
-	return RK_OK;
-}
-
 // the range checks of a deepening launch and the launch itself; `bound` (null: every word is looked up) prunes, `lookups` counts
 int launch_deepen(const char *who, rk_symball *ball, DeepenJob job, uint32_t *best, hipStream_t st, const rk_bound *bound = nullptr,
                   unsigned long long *lookups = nullptr)
@@ -1047,7 +1039,7 @@ int rk_sym_tables(uint8_t *h_actions, uint8_t *h_src, uint8_t *h_map)
 
 int rk_sym_canonical(const int8_t *d_states, size_t n, int8_t *d_rep, uint8_t *d_sym, uint8_t *d_orbit, void *stream)
 {
-	if (int e = check_sym_states("rk_sym_canonical", d_states, n)) return e;
+	if (int e = check_state_rows("rk_sym_canonical", d_states, n)) return e;
 	if ((uintptr_t)d_rep & 3u) return fail(RK_EINVAL, "rk_sym_canonical: device pointers must be 4-byte aligned");
 	if (n == 0) return RK_OK;
 	hipLaunchKernelGGL(k_sym_canonical, dim3(sym_grid(n)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t *>(d_states), n,
@@ -1059,7 +1051,7 @@ int rk_sym_canonical(const int8_t *d_states, size_t n, int8_t *d_rep, uint8_t *d
 int rk_sym_conjugate(const int8_t *d_states, size_t n, int sym, int8_t *d_out, void *stream)
 {
 	if (sym < 0 || sym >= N_SYM) return fail(RK_EINVAL, "rk_sym_conjugate: symmetry %d outside 0..%d", sym, N_SYM - 1);
-	if (int e = check_sym_states("rk_sym_conjugate", d_states, n)) return e;
+	if (int e = check_state_rows("rk_sym_conjugate", d_states, n)) return e;
 	if (n != 0 && !d_out) return fail(RK_EINVAL, "rk_sym_conjugate: null pointer");
 	if ((uintptr_t)d_out & 3u) return fail(RK_EINVAL, "rk_sym_conjugate: device pointers must be 4-byte aligned");
 	if (n == 0) return RK_OK;
@@ -1266,7 +1258,7 @@ static int sdeepen_states(const char *who, rk_symball *ball, const rk_bound *bou
 {
 	if (!ball) return fail(RK_EINVAL, "%s: null ball", who);
 	if (!ball->built) return fail(RK_ESTATE, "%s: build the ball first", who);
-	if (int e = check_sym_states(who, d_states, n)) return e;
+	if (int e = check_state_rows(who, d_states, n)) return e;
 	return launch_deepen(who, ball, DeepenJob{reinterpret_cast<const uint32_t *>(d_states), d_last, -1, n, extra, word_first, word_count}, d_best,
 	                     (hipStream_t)stream, bound, d_lookups);
 }

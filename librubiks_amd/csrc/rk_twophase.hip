@@ -44,8 +44,6 @@
 // column.  Vector stores only; the one atomic is the row counter.
 #include <hip/hip_runtime.h>
 #include <algorithm>
-#include <array>
-#include <climits>
 #include <cstring>
 #include <vector>
 
@@ -54,6 +52,8 @@
 #include "rk_chain_dev.h"
 #include "rk_error.h"
 #include "rk_search_dev.h"
+#include "rk_search_host.h"
+#include "rk_table_host.h"
 
 namespace rk {
 
@@ -352,42 +352,15 @@ struct rk_twophase {
 
 namespace {
 
-typedef std::array<uint32_t, 5> TpState;
-
 unsigned tp_grid(size_t n) { return (unsigned)std::min<size_t>((n + TP_THREADS - 1) / TP_THREADS, (size_t)RK_TWOPHASE_GRID); }
 
-const Tables &tp_tables()
-{
-	static const Tables t = make_tables();
-	return t;
-}
-
-TpState tp_from_bytes(const uint8_t *b)
-{
-	TpState s;
-	memcpy(s.data(), b, STATE_BYTES);
-	return s;
-}
-
-TpState tp_move(const TpState &s, int action)
-{
-	const Tables &t = tp_tables();
-	uint8_t b[STATE_BYTES];
-	memcpy(b, s.data(), STATE_BYTES);
-	for (int i = 0; i < 8; i++) b[i] = t.lut[action][0][b[i]];
-	for (int i = 8; i < STATE_BYTES; i++) b[i] = t.lut[action][1][b[i]];
-	return tp_from_bytes(b);
-}
-
 // column `col` of a phase's move tables: an action, or a generator of the chain's stage 3
-TpState tp_column(const TpState &s, bool two, int col)
+HostState tp_column(const HostState &s, bool two, int col)
 {
-	if (!two) return tp_move(s, col);
-	const TpState once = tp_move(s, CHAIN.gen_action[2][col]);
-	return CHAIN.gen_cost[2][col] == 2 ? tp_move(once, CHAIN.gen_action[2][col]) : once;
+	return two ? host_generate(s, CHAIN.gen_action[2][col], CHAIN.gen_cost[2][col]) : host_move(s, col);
 }
 
-uint32_t tp_coordinate(int which, const TpState &s)
+uint32_t tp_coordinate(int which, const HostState &s)
 {
 	const uint32_t *x = s.data();
 	switch (which) {
@@ -403,23 +376,21 @@ uint32_t tp_coordinate(int which, const TpState &s)
 // One representative state per value of coordinate `which`: a closure from solved under the phase's generators, so every
 // representative is a legal state (a digit or a place that the coordinate leaves out is the one the others force).  false: a value
 // is out of range or not every value is reached.
-bool tp_representatives(int which, std::vector<TpState> &reps)
+bool tp_representatives(int which, std::vector<HostState> &reps)
 {
 	const uint32_t rows = TP_MT_ROWS[which];
-	uint8_t home[STATE_BYTES];
-	memcpy(home, tp_tables().solved, STATE_BYTES);
-	const TpState solved = tp_from_bytes(home);
+	const HostState solved = host_solved();
 	reps.assign(rows, solved);
 	std::vector<uint8_t> have(rows, 0);
-	std::vector<TpState> todo{solved};
+	std::vector<HostState> todo{solved};
 	uint32_t v = tp_coordinate(which, solved), count = 1;
 	if (v >= rows) return false;
 	have[v] = 1;
 	while (!todo.empty()) {
-		const TpState s = todo.back();
+		const HostState s = todo.back();
 		todo.pop_back();
 		for (uint32_t col = 0; col < TP_MT_COLS[which]; col++) {
-			const TpState c = tp_column(s, which >= 3, (int)col);
+			const HostState c = tp_column(s, which >= 3, (int)col);
 			v = tp_coordinate(which, c);
 			if (v >= rows) return false;
 			if (have[v]) continue;
@@ -434,7 +405,7 @@ bool tp_representatives(int which, std::vector<TpState> &reps)
 
 bool tp_move_table(int which, std::vector<uint16_t> &mt)
 {
-	std::vector<TpState> reps;
+	std::vector<HostState> reps;
 	if (!tp_representatives(which, reps)) return false;
 	const uint32_t cols = TP_MT_COLS[which];
 	mt.assign((size_t)TP_MT_ROWS[which] * cols, 0);
@@ -447,39 +418,22 @@ bool tp_move_table(int which, std::vector<uint16_t> &mt)
 	return true;
 }
 
-// One pruning table over the pairs (a, b), index a * K + b, as the chain's tables are built: level d + 1 takes the cost-1 children
-// of level d and the cost-2 children of level d - 1 and stores only over "unreached".  Returns the deepest entry, -1 unless
-// exactly TP_COUNT[table] entries were reached and one of them is 0.
+// One pruning table over the pairs (a, b), index a * K + b: build_cost_table (rk_table_host.h) on the indices themselves, a child
+// stepped through the two move tables.  Returns the deepest entry, -1 unless exactly TP_COUNT[table] entries were reached and one
+// of them is 0.
 int tp_build(int table, const std::vector<uint16_t> &mta, const std::vector<uint16_t> &mtb, uint32_t goal, std::vector<uint8_t> &out, long long &count)
 {
 	const bool two = table >= 2;
 	const uint32_t K = two ? TP_PLACES : TP_SLICE, cols = two ? 8 : 12;
-	out.assign(TP_SIZE[table], (uint8_t)CHAIN_UNREACHED);
-	std::vector<uint32_t> before, level{goal}, next;
-	if (goal >= TP_SIZE[table]) return -1;
-	out[goal] = 0;
-	count = 1;
-	int d = 0;
-	for (; !level.empty() || !before.empty(); d++) {
-		if (d + 1 >= (int)CHAIN_UNREACHED) return -1;
-		next.clear();
-		for (uint32_t col = 0; col < cols; col++)
-			for (uint32_t index : (two ? CHAIN.gen_cost[2][col] : 1) == 1 ? level : before) {
-				const uint32_t a = index / K, b = index - a * K;
-				const uint32_t to = (uint32_t)mta[(size_t)a * cols + col] * K + mtb[(size_t)b * cols + col];
-				if (to >= TP_SIZE[table]) return -1;
-				if (out[to] != CHAIN_UNREACHED) continue;
-				out[to] = (uint8_t)(d + 1);
-				next.push_back(to);
-			}
-		count += (long long)next.size();
-		before.swap(level);
-		level.swap(next);
-	}
-	long long zeros = 0;
-	for (uint8_t v : out) zeros += v == 0;
-	if (count != (long long)TP_COUNT[table] || zeros != 1) return -1;
-	return d - 2;
+	const uint8_t quarter_turns[12] = {1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1};
+	const uint16_t *ma = mta.data(), *mb = mtb.data();
+	return build_cost_table(
+		out, TP_SIZE[table], (long long)TP_COUNT[table], (int)cols, two ? CHAIN.gen_cost[2] : quarter_turns, goal,
+		[=](uint32_t index, int col) {
+			const uint32_t a = index / K, b = index - a * K;
+			return (uint32_t)ma[(size_t)a * cols + col] * K + mb[(size_t)b * cols + col];
+		},
+		[](uint32_t index) { return index; }, count);
 }
 
 }  // namespace
@@ -492,9 +446,7 @@ int rk_twophase_create(rk_twophase_t **out, void *stream)
 	std::vector<uint16_t> mt[TP_MOVES];
 	for (int w = 0; w < TP_MOVES; w++)
 		if (!tp_move_table(w, mt[w])) return fail(RK_ESTATE, "rk_twophase_create: coordinate %d does not take every value under its generators", w);
-	uint8_t home[STATE_BYTES];
-	memcpy(home, tp_tables().solved, STATE_BYTES);
-	const TpState solved = tp_from_bytes(home);
+	const HostState solved = host_solved();
 	uint32_t goal[TP_MOVES];
 	for (int w = 0; w < TP_MOVES; w++) goal[w] = tp_coordinate(w, solved);
 	rk_twophase *h = new rk_twophase();
@@ -509,40 +461,18 @@ int rk_twophase_create(rk_twophase_t **out, void *stream)
 			delete h;
 			return fail(RK_ESTATE, "rk_twophase_create: pruning table %d reached %lld entries, not %u with one goal", s + 1, got, TP_COUNT[s]);
 		}
-	// one block: the pruning tables, the move tables, the row counter, each 16-byte aligned
-	size_t at[TP_TABLES + TP_MOVES + 1], bytes = 0;
-	for (int s = 0; s < TP_TABLES; s++) {
-		at[s] = bytes;
-		bytes += ((size_t)TP_SIZE[s] + 15) / 16 * 16;
-	}
-	for (int w = 0; w < TP_MOVES; w++) {
-		at[TP_TABLES + w] = bytes;
-		bytes += (mt[w].size() * sizeof(uint16_t) + 15) / 16 * 16;
-	}
-	at[TP_TABLES + TP_MOVES] = bytes;
-	bytes += 16;
-	if (hipMalloc((void **)&h->d_block, bytes) != hipSuccess) {
-		(void)hipGetLastError();
-		h->d_block = nullptr;
-		delete h;
-		return fail(RK_ECAPACITY, "rk_twophase_create: no device memory for %zu bytes of tables", bytes);
-	}
-	hipStream_t st = (hipStream_t)stream;
-	const auto upload = [&]() -> int {
-		for (int s = 0; s < TP_TABLES; s++) RK_HIP(hipMemcpyAsync(h->d_block + at[s], table[s].data(), TP_SIZE[s], hipMemcpyHostToDevice, st));
-		for (int w = 0; w < TP_MOVES; w++)
-			RK_HIP(hipMemcpyAsync(h->d_block + at[TP_TABLES + w], mt[w].data(), mt[w].size() * sizeof(uint16_t), hipMemcpyHostToDevice, st));
-		RK_HIP(hipMemsetAsync(h->d_block + at[TP_TABLES + TP_MOVES], 0, 16, st));
-		RK_HIP(hipStreamSynchronize(st));                                   // the host copies go out of scope
-		return RK_OK;
-	};
-	if (int e = upload()) {
+	TableBlock block;                                                   // the pruning tables, the move tables, the row counter
+	for (int s = 0; s < TP_TABLES; s++) block.add(table[s].data(), TP_SIZE[s]);
+	for (int w = 0; w < TP_MOVES; w++) block.add(mt[w].data(), mt[w].size() * sizeof(uint16_t));
+	block.add_zeros(16);
+	if (int e = block.upload("rk_twophase_create", (hipStream_t)stream)) {
 		delete h;
 		return e;
 	}
-	for (int s = 0; s < TP_TABLES; s++) h->d.prune[s] = h->d_block + at[s];
-	for (int w = 0; w < TP_MOVES; w++) h->d.mt[w] = reinterpret_cast<const uint16_t *>(h->d_block + at[TP_TABLES + w]);
-	h->d_counter = reinterpret_cast<uint32_t *>(h->d_block + at[TP_TABLES + TP_MOVES]);
+	for (int s = 0; s < TP_TABLES; s++) h->d.prune[s] = block.at(s);
+	for (int w = 0; w < TP_MOVES; w++) h->d.mt[w] = block.at<uint16_t>(TP_TABLES + w);
+	h->d_counter = block.at<uint32_t>(TP_TABLES + TP_MOVES);
+	h->d_block = block.release();
 	h->d.goal_twist = goal[0];
 	h->d.goal_flip = goal[1];
 	h->d.goal_slice = goal[2];
@@ -574,15 +504,7 @@ int rk_twophase_status(rk_twophase_t *h, long long *h_status)
 int rk_twophase_export(rk_twophase_t *h, int table, size_t first, size_t count, uint8_t *h_bytes, void *stream)
 {
 	if (!h) return fail(RK_EINVAL, "rk_twophase_export: null handle");
-	if (table < 1 || table > TP_TABLES) return fail(RK_EINVAL, "rk_twophase_export: table %d outside 1..%d", table, TP_TABLES);
-	const size_t size = TP_SIZE[table - 1];
-	if (first > size || count > size - first) return fail(RK_EINVAL, "rk_twophase_export: entries %zu..%zu outside the table", first, first + count);
-	if (count == 0) return RK_OK;
-	if (!h_bytes) return fail(RK_EINVAL, "rk_twophase_export: null pointer");
-	hipStream_t st = (hipStream_t)stream;
-	RK_HIP(hipMemcpyAsync(h_bytes, h->d.prune[table - 1] + first, count, hipMemcpyDeviceToHost, st));
-	RK_HIP(hipStreamSynchronize(st));
-	return RK_OK;
+	return export_table("rk_twophase_export", "table", table, TP_TABLES, h->d.prune, TP_SIZE, first, count, h_bytes, stream);
 }
 
 int rk_twophase_solve(rk_twophase_t *h, rk_chain_t *chain, const int8_t *d_states, size_t n, int tries, long long max_nodes, int32_t *d_lengths,
@@ -590,10 +512,9 @@ int rk_twophase_solve(rk_twophase_t *h, rk_chain_t *chain, const int8_t *d_state
 {
 	if (!h || !chain) return fail(RK_EINVAL, "rk_twophase_solve: null handle");
 	if (tries < 1 || max_nodes < 1) return fail(RK_EINVAL, "rk_twophase_solve: tries %d and max_nodes %lld must be at least 1", tries, max_nodes);
-	if (n > (size_t)INT32_MAX) return fail(RK_EINVAL, "rk_twophase_solve: %zu states in one launch", n);
-	if (n != 0 && (!d_states || !d_lengths || !d_actions || !d_phase_lengths || !d_reason || !d_nodes))
-		return fail(RK_EINVAL, "rk_twophase_solve: null pointer");
-	if (((uintptr_t)d_states | (uintptr_t)d_lengths | (uintptr_t)d_phase_lengths | (uintptr_t)d_reason | (uintptr_t)d_error) & 3u)
+	if (int e = check_state_rows("rk_twophase_solve", d_states, n)) return e;
+	if (n != 0 && (!d_lengths || !d_actions || !d_phase_lengths || !d_reason || !d_nodes)) return fail(RK_EINVAL, "rk_twophase_solve: null pointer");
+	if (((uintptr_t)d_lengths | (uintptr_t)d_phase_lengths | (uintptr_t)d_reason | (uintptr_t)d_error) & 3u)
 		return fail(RK_EINVAL, "rk_twophase_solve: device pointers must be 4-byte aligned");
 	if ((uintptr_t)d_nodes & 7u) return fail(RK_EINVAL, "rk_twophase_solve: d_nodes must be 8-byte aligned");
 	long long chain_status[16];

@@ -92,6 +92,32 @@ def _roots20(is2024: bool, states, n: int) -> np.ndarray:
 	return np.ascontiguousarray(cube.as2024(np.asarray(states, dtype=np.int8).reshape(n, 6, 8, 6)))
 
 
+def _device_rows20(states):
+	"""A batch of states as ((n, 20) int8 rows on the device, whether the caller gave a device tensor), in the representation
+	cube.get_is2024() names."""
+	if cube.cube._is_dev(states):
+		t = states if states.dtype == torch.int8 else states.to(torch.int8)
+		if cube.get_is2024():
+			if t.numel() % 20 or (t.dim() and t.shape[-1] != 20):
+				raise ValueError(f"states must be (n, 20), got shape {tuple(t.shape)}")
+			q = t.reshape(-1, 20)
+			if not q.is_contiguous() or q.data_ptr() % 4:
+				q = q.clone(memory_format=torch.contiguous_format)
+		else:
+			if t.numel() % 288 or (t.dim() and t.shape[-1] != 6):
+				raise ValueError(f"states must be (n, 6, 8, 6) in 6x8x6 mode, got shape {tuple(t.shape)}")
+			q = cube.as2024(t.reshape(-1, 6, 8, 6))
+		return q, True
+	rows = cube.cube._rows2024(states)
+	return (torch.from_numpy(rows).to(gpu) if len(rows) else torch.empty((0, 20), dtype=torch.int8, device=gpu)), False
+
+
+def _batch_out(was_device: bool, *tensors):
+	"""A batch's answer as the caller gave the states: device tensors, or numpy arrays; one tensor alone, several as a tuple."""
+	out = tensors if was_device else tuple(t.cpu().numpy() for t in tensors)
+	return out[0] if len(out) == 1 else out
+
+
 def _states_out(is2024: bool, states20: np.ndarray, n: int) -> np.ndarray:
 	"""An exported (rows, 20) array whose rows 1..n hold nodes, in the search's representation (other rows stay zero)."""
 	if is2024:
@@ -1188,40 +1214,22 @@ class DevicePatternDB(_ffi.Owner):
 	def __len__(self):
 		return self.size
 
-	def _rows(self, states):
-		"""-> ((n, 20) int8 rows on the device, whether the caller gave a device tensor)"""
-		if cube.cube._is_dev(states):
-			t = states if states.dtype == torch.int8 else states.to(torch.int8)
-			if cube.get_is2024():
-				if t.numel() % 20 or (t.dim() and t.shape[-1] != 20):
-					raise ValueError(f"states must be (n, 20), got shape {tuple(t.shape)}")
-				q = t.reshape(-1, 20)
-				if not q.is_contiguous() or q.data_ptr() % 4:
-					q = q.clone(memory_format=torch.contiguous_format)
-			else:
-				if t.numel() % 288 or (t.dim() and t.shape[-1] != 6):
-					raise ValueError(f"states must be (n, 6, 8, 6) in 6x8x6 mode, got shape {tuple(t.shape)}")
-				q = cube.as2024(t.reshape(-1, 6, 8, 6))
-			return q, True
-		rows = cube.cube._rows2024(states)
-		return (torch.from_numpy(rows).to(gpu) if len(rows) else torch.empty((0, 20), dtype=torch.int8, device=gpu)), False
-
 	def depth(self, states):
 		"""int32 (n,): the exact number of quarter turns that bring the selected cubies home, -1 for a row whose selected codes are
 		no partial pattern.  One launch, no synchronisation for device tensors."""
 		self._need_built()
-		q, dev = self._rows(states)
+		q, dev = _device_rows20(states)
 		n = len(q)
 		out = torch.empty(n, dtype=torch.int32, device=gpu)
 		_ffi.check(_ffi.lib().rk_pdb_depth(self._h, q.data_ptr(), n, out.data_ptr(), _ffi.stream_ptr()))
-		return out if dev else out.cpu().numpy()
+		return _batch_out(dev, out)
 
 	def solve(self, states):
 		"""(lengths int32 (n,), actions int8 (n, max_depth)): a shortest word that brings the selected cubies home -- at each step
 		the lowest action whose child's entry is one less --, rows padded with -1; length -1 for a row whose selected codes are no
 		partial pattern.  One launch; reading the error word is the call's one host read."""
 		self._need_built()
-		q, dev = self._rows(states)
+		q, dev = _device_rows20(states)
 		n = len(q)
 		lengths = torch.empty(n, dtype=torch.int32, device=gpu)
 		actions = torch.empty((n, self.max_depth), dtype=torch.int8, device=gpu)
@@ -1229,7 +1237,7 @@ class DevicePatternDB(_ffi.Owner):
 		_ffi.check(_ffi.lib().rk_pdb_solve(self._h, q.data_ptr(), n, lengths.data_ptr(), actions.data_ptr(), err.data_ptr(), _ffi.stream_ptr()))
 		if int(err.item()):
 			raise _ffi.RubiksHipError(f"rk_pdb_solve reported error {int(err.item())}: an entry of the table has no child one level nearer")
-		return (lengths, actions) if dev else (lengths.cpu().numpy(), actions.cpu().numpy())
+		return _batch_out(dev, lengths, actions)
 
 	@staticmethod
 	def lower_bound(states, dbs):
@@ -1303,67 +1311,32 @@ class DevicePatternBound(_ffi.Owner):
 		"""int32 (n,): the greatest of the databases' depths, an admissible lower bound on the distance to solved of every state.
 		One launch, no synchronisation for device tensors."""
 		self._need_handle()
-		q, dev = self.dbs[0]._rows(states)
+		q, dev = _device_rows20(states)
 		n = len(q)
 		out = torch.empty(n, dtype=torch.int32, device=gpu)
 		_ffi.check(_ffi.lib().rk_bound_depth(self._h, q.data_ptr(), n, out.data_ptr(), _ffi.stream_ptr()))
-		return out if dev else out.cpu().numpy()
+		return _batch_out(dev, out)
 
 	def __str__(self):
 		return "Pattern bound (device, " + "; ".join(f"corners={db.corner_cubies} edges={db.edge_cubies}" for db in self.dbs) + ")"
 
 
-class DeviceChainSolver(Agent, _ffi.Owner):
-	"""
-	A solution for EVERY legal state, batched on the device (engine rk_chain_*, csrc/rk_chain.hip): the subgroup chain -- four
-	stages, each a table of exact costs over the cosets of the next subgroup, built on the host when the solver is made and kept
-	in HBM (2.5 MB) -- answered by four table descents in one launch, a thread per state: no search, no pool, no net.  Stage 1
-	uses the 12 quarter turns, the later ones fewer and fewer of them and the half turns XX (the action 2 f twice) of the other
-	faces (DESIGN 3.59.8).  Solutions are NOT optimal -- at most `max_length` moves, some tens on average --; `shorten=ball` (a
-	`DeviceGoalBall` or `DeviceSymBall`) pipes every queue through `ball.shorten`, which makes it locally optimal.
+class _TableSolver(Agent, _ffi.Owner):
+	"""What the table solvers share: `shorten` and `allow_illegal`, the error word that names the lowest row that is no legal state,
+	the export of a table, and `search`.  A subclass makes its handle and writes `solve`, which returns lengths and actions first."""
 
-	`solve(states)` takes a batch: numpy in -> numpy out, device tensor in -> device tensor out; states are in the representation
-	cube.get_is2024() names when a method is called.  As an agent (`search(state)` fills `action_queue`; never fails on a legal
-	state) it plays in `Evaluator` and under `TowardsGoal`.  A row that is no legal state (`cube.is_legal`) is a ValueError naming
-	the lowest such row, or, with `allow_illegal`, gets length -1 (its stage lengths -1, its actions all -1).
-	"""
-	GRID_ROWS = 2048 * 256                  # RK_CHAIN_GRID workgroups of 256 states: beyond this many rows a thread takes several
-
-	def __init__(self, shorten=None, allow_illegal: bool = False):
+	def __init__(self, shorten, allow_illegal):
 		Agent.__init__(self)
 		if shorten is not None and not isinstance(shorten, _KeptBall):
 			raise ValueError("shorten must be a DeviceGoalBall, a DeviceSymBall or None")
 		self.shorten, self.allow_illegal = shorten, bool(allow_illegal)
-		_ffi.require_gpu()
-		self._create("rk_chain_create", "rk_chain_destroy", _ffi.stream_ptr())
-		status = (C.c_longlong * 16)()
-		_ffi.check(_ffi.lib().rk_chain_status(self._h, status))
-		self.coset_counts = tuple(int(v) for v in status[0:4])
-		self.stage_depths = tuple(int(v) for v in status[4:8])           # the deepest entry of each table
-		self.max_length = int(status[8])                                 # the row length of `solve`'s actions
-		self.table_sizes = tuple(int(v) for v in status[9:13])
 
-	_rows = DevicePatternDB._rows
+	def _error_word(self):                                               # where a solve entry names the lowest illegal row
+		return None if self.allow_illegal else torch.full((1,), -1, dtype=torch.int32, device=gpu)
 
-	def solve(self, states, stage_lengths: bool = False):
-		"""(lengths int32 (n,), actions int8 (n, max_length) padded with -1[, stage lengths int32 (n, 4)]): per stage, at each step
-		the lowest generator whose entry equals the current entry minus its cost.  One launch; reading the error word (not with
-		`allow_illegal`) is the call's one host read.  With `shorten` the queues come back through `ball.shorten` (lengths and
-		actions then describe the shortened queues; the stage lengths stay the chain's own)."""
-		q, dev = self._rows(states)
-		n = len(q)
-		lengths = torch.empty(n, dtype=torch.int32, device=gpu)
-		actions = torch.full((n, self.max_length), -1, dtype=torch.int8, device=gpu)
-		stages = torch.empty((n, 4), dtype=torch.int32, device=gpu) if stage_lengths else None
-		err = None if self.allow_illegal else torch.full((1,), -1, dtype=torch.int32, device=gpu)
-		_ffi.check(_ffi.lib().rk_chain_solve(self._h, q.data_ptr(), n, lengths.data_ptr(), actions.data_ptr(),
-		                                     stages.data_ptr() if stage_lengths else None, None if err is None else err.data_ptr(), _ffi.stream_ptr()))
+	def _raise_illegal(self, err):                                       # the call's one host read
 		if err is not None and int(err.item()) >= 0:
 			raise ValueError(f"row {int(err.item())} of states is not a legal cube state (the lowest such row)")
-		if self.shorten is not None and n:
-			lengths, actions = self._shortened(lengths, actions)
-		out = (lengths, actions) + ((stages,) if stage_lengths else ())
-		return out if dev else tuple(t.cpu().numpy() for t in out)
 
 	def _shortened(self, lengths, actions):
 		"""The queues after `self.shorten.shorten`, back in `solve`'s shape on the device."""
@@ -1376,11 +1349,10 @@ class DeviceChainSolver(Agent, _ffi.Owner):
 				h_len[i] = len(queue)
 		return torch.from_numpy(h_len).to(gpu), torch.from_numpy(out).to(gpu)
 
-	def export(self, stage: int) -> np.ndarray:
-		"""uint8 (table_sizes[stage - 1],): the table of stage 1..4, entry by index; 255 = no coset has this index."""
-		stage = eng.int_in("stage", stage, 1, 4, what="a stage 1..4")
-		out = np.empty(self.table_sizes[stage - 1], np.uint8)
-		_ffi.check(_ffi.lib().rk_chain_export(self._h, stage, 0, len(out), out.ctypes.data, _ffi.stream_ptr()))
+	def _export(self, entry: str, which, what: str) -> np.ndarray:
+		which = eng.int_in(what, which, 1, 4, what=f"a {what} 1..4")
+		out = np.empty(self.table_sizes[which - 1], np.uint8)
+		_ffi.check(getattr(_ffi.lib(), entry)(self._h, which, 0, len(out), out.ctypes.data, _ffi.stream_ptr()))
 		return out
 
 	def search(self, state: np.ndarray, time_limit: float = None, max_states: int = None) -> bool:
@@ -1398,11 +1370,61 @@ class DeviceChainSolver(Agent, _ffi.Owner):
 		self.action_queue = deque(int(a) for a in actions[0, :int(lengths[0])])
 		return True
 
+
+class DeviceChainSolver(_TableSolver):
+	"""
+	A solution for EVERY legal state, batched on the device (engine rk_chain_*, csrc/rk_chain.hip): the subgroup chain -- four
+	stages, each a table of exact costs over the cosets of the next subgroup, built on the host when the solver is made and kept
+	in HBM (2.5 MB) -- answered by four table descents in one launch, a thread per state: no search, no pool, no net.  Stage 1
+	uses the 12 quarter turns, the later ones fewer and fewer of them and the half turns XX (the action 2 f twice) of the other
+	faces (DESIGN 3.59.8).  Solutions are NOT optimal -- at most `max_length` moves, some tens on average --; `shorten=ball` (a
+	`DeviceGoalBall` or `DeviceSymBall`) pipes every queue through `ball.shorten`, which makes it locally optimal.
+
+	`solve(states)` takes a batch: numpy in -> numpy out, device tensor in -> device tensor out; states are in the representation
+	cube.get_is2024() names when a method is called.  As an agent (`search(state)` fills `action_queue`; never fails on a legal
+	state) it plays in `Evaluator` and under `TowardsGoal`.  A row that is no legal state (`cube.is_legal`) is a ValueError naming
+	the lowest such row, or, with `allow_illegal`, gets length -1 (its stage lengths -1, its actions all -1).
+	"""
+	GRID_ROWS = 2048 * 256                  # RK_CHAIN_GRID workgroups of 256 states: beyond this many rows a thread takes several
+
+	def __init__(self, shorten=None, allow_illegal: bool = False):
+		super().__init__(shorten, allow_illegal)
+		_ffi.require_gpu()
+		self._create("rk_chain_create", "rk_chain_destroy", _ffi.stream_ptr())
+		status = (C.c_longlong * 16)()
+		_ffi.check(_ffi.lib().rk_chain_status(self._h, status))
+		self.coset_counts = tuple(int(v) for v in status[0:4])
+		self.stage_depths = tuple(int(v) for v in status[4:8])           # the deepest entry of each table
+		self.max_length = int(status[8])                                 # the row length of `solve`'s actions
+		self.table_sizes = tuple(int(v) for v in status[9:13])
+
+	def solve(self, states, stage_lengths: bool = False):
+		"""(lengths int32 (n,), actions int8 (n, max_length) padded with -1[, stage lengths int32 (n, 4)]): per stage, at each step
+		the lowest generator whose entry equals the current entry minus its cost.  One launch; reading the error word (not with
+		`allow_illegal`) is the call's one host read.  With `shorten` the queues come back through `ball.shorten` (lengths and
+		actions then describe the shortened queues; the stage lengths stay the chain's own)."""
+		q, dev = _device_rows20(states)
+		n = len(q)
+		lengths = torch.empty(n, dtype=torch.int32, device=gpu)
+		actions = torch.full((n, self.max_length), -1, dtype=torch.int8, device=gpu)
+		stages = torch.empty((n, 4), dtype=torch.int32, device=gpu) if stage_lengths else None
+		err = self._error_word()
+		_ffi.check(_ffi.lib().rk_chain_solve(self._h, q.data_ptr(), n, lengths.data_ptr(), actions.data_ptr(),
+		                                     stages.data_ptr() if stage_lengths else None, None if err is None else err.data_ptr(), _ffi.stream_ptr()))
+		self._raise_illegal(err)
+		if self.shorten is not None and n:
+			lengths, actions = self._shortened(lengths, actions)
+		return _batch_out(dev, lengths, actions, *((stages,) if stage_lengths else ()))
+
+	def export(self, stage: int) -> np.ndarray:
+		"""uint8 (table_sizes[stage - 1],): the table of stage 1..4, entry by index; 255 = no coset has this index."""
+		return self._export("rk_chain_export", stage, "stage")
+
 	def __str__(self):
 		return "Subgroup chain solver (device)" + (f", shortened by {self.shorten}" if self.shorten is not None else "")
 
 
-class DeviceTwoPhaseSolver(Agent, _ffi.Owner):
+class DeviceTwoPhaseSolver(_TableSolver):
 	"""
 	SHORT solutions for every legal state, batched on the device, by search and without a net (engine rk_twophase_*,
 	csrc/rk_twophase.hip): IDA* over the 12 quarter turns into the subgroup <F, B, TT, DD, LL, RR> -- the one the chain's stage 3
@@ -1423,14 +1445,11 @@ class DeviceTwoPhaseSolver(Agent, _ffi.Owner):
 	GRID_ROWS = 1024 * 256                  # RK_TWOPHASE_GRID workgroups of 256 lanes: beyond this many rows a lane takes several
 
 	def __init__(self, chain=None, tries: int = 8, max_nodes: int = 1 << 20, shorten=None, allow_illegal: bool = False):
-		Agent.__init__(self)
 		if chain is not None and not isinstance(chain, DeviceChainSolver):
 			raise ValueError("chain must be a DeviceChainSolver or None")
-		if shorten is not None and not isinstance(shorten, _KeptBall):
-			raise ValueError("shorten must be a DeviceGoalBall, a DeviceSymBall or None")
+		super().__init__(shorten, allow_illegal)
 		self.tries = eng.int_in("tries", tries, 1, (1 << 31) - 1)
 		self.max_nodes = eng.int_in("max_nodes", max_nodes, 1, _ffi.INT64_MAX)
-		self.shorten, self.allow_illegal = shorten, bool(allow_illegal)
 		_ffi.require_gpu()
 		self.chain = chain if chain is not None else DeviceChainSolver()
 		self._create("rk_twophase_create", "rk_twophase_destroy", _ffi.stream_ptr())
@@ -1442,9 +1461,6 @@ class DeviceTwoPhaseSolver(Agent, _ffi.Owner):
 		self.grid_rows = int(status[12]) * int(status[13])
 		self.max_length = self.chain.max_length                          # the row length of `solve`'s actions
 
-	_rows = DevicePatternDB._rows
-	_shortened = DeviceChainSolver._shortened
-
 	def solve(self, states, phase_lengths: bool = False, details: bool = False):
 		"""(lengths int32 (n,), actions int8 (n, max_length) padded with -1[, phase lengths int32 (n, 2)][, reason int32 (n,), nodes
 		int64 (n,)]): reason 0 = the search ended by itself and improved the chain's answer, 1 = the budget ended it and the answer is
@@ -1453,32 +1469,25 @@ class DeviceTwoPhaseSolver(Agent, _ffi.Owner):
 		shortened queues; phase lengths, reason and nodes stay the search's own)."""
 		if self.chain._h is None:
 			raise ValueError("the chain solver was freed")
-		q, dev = self._rows(states)
+		q, dev = _device_rows20(states)
 		n = len(q)
 		lengths = torch.empty(n, dtype=torch.int32, device=gpu)
 		actions = torch.full((n, self.max_length), -1, dtype=torch.int8, device=gpu)
 		phases = torch.empty((n, 2), dtype=torch.int32, device=gpu)
 		reason = torch.empty(n, dtype=torch.int32, device=gpu)
 		nodes = torch.empty(n, dtype=torch.int64, device=gpu)
-		err = None if self.allow_illegal else torch.full((1,), -1, dtype=torch.int32, device=gpu)
+		err = self._error_word()
 		_ffi.check(_ffi.lib().rk_twophase_solve(self._h, self.chain._h, q.data_ptr(), n, self.tries, self.max_nodes, lengths.data_ptr(),
 		                                        actions.data_ptr(), phases.data_ptr(), reason.data_ptr(), nodes.data_ptr(),
 		                                        None if err is None else err.data_ptr(), _ffi.stream_ptr()))
-		if err is not None and int(err.item()) >= 0:
-			raise ValueError(f"row {int(err.item())} of states is not a legal cube state (the lowest such row)")
+		self._raise_illegal(err)
 		if self.shorten is not None and n:
 			lengths, actions = self._shortened(lengths, actions)
-		out = (lengths, actions) + ((phases,) if phase_lengths else ()) + ((reason, nodes) if details else ())
-		return out if dev else tuple(t.cpu().numpy() for t in out)
+		return _batch_out(dev, lengths, actions, *((phases,) if phase_lengths else ()), *((reason, nodes) if details else ()))
 
 	def export(self, table: int) -> np.ndarray:
 		"""uint8 (table_sizes[table - 1],): pruning table 1..4, entry by index (every entry is reached)."""
-		table = eng.int_in("table", table, 1, 4, what="a table 1..4")
-		out = np.empty(self.table_sizes[table - 1], np.uint8)
-		_ffi.check(_ffi.lib().rk_twophase_export(self._h, table, 0, len(out), out.ctypes.data, _ffi.stream_ptr()))
-		return out
-
-	search = DeviceChainSolver.search
+		return self._export("rk_twophase_export", table, "table")
 
 	def __str__(self):
 		return f"Two-phase solver (device, tries={self.tries}, max_nodes={self.max_nodes})" + \
