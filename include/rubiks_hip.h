@@ -277,7 +277,18 @@ int rk_686_to2024(const int8_t *d_states686, int8_t *d_out20, long long *d_stats
  * Six launches per iteration (plus merge passes when 12 N > 2048), fixed shapes: an iteration can be captured in a
  * hipGraph.  Once `done` (won, out of budget, queue empty) further steps are no-ops.  Results are identical to the
  * reference's arrays (same index numbering, G, parents, parent_actions) whenever the value net returns the same
- * numbers.  An engine handle is not thread-safe: one host thread drives it, on one stream at a time. */
+ * numbers.  An engine handle is not thread-safe: one host thread drives it, on one stream at a time.
+ *
+ * NON-FINITE VALUES (the single, the batched and the sharded engine alike).  A NaN among the values of the new states that
+ * get a cost record -- values[j] for j below the number of new states of the iteration (and below `rows` of
+ * rk_astar_shard_push_rows), exactly the values the engine reads; either sign, quiet or signalling, float32 or a bfloat16
+ * NaN -- ends THAT search with engine error 4 (the first error of a search wins): the commit that read it reports done = 1,
+ * error = 4, and nothing is popped again; the other searches of a batch run on undisturbed; every rank of a sharded search
+ * takes stop reason 6 with error 4 at the next rk_astar_shard_select, before any pop is counted.  A cost has to have a place
+ * in the order of the open queue and a NaN has none.  +inf and -inf are ordinary values and keep their order (a cost of
+ * -inf is popped first, +inf last).  Values at and beyond the count are never read: a NaN there changes nothing.  A reset
+ * (rk_astar_reset, rk_astarb_reset, rk_astar_shard_reset) clears the error.
+ * Engine error codes: 1 pool capacity, 2 look-back chain, 3 more new states than net rows, 4 NaN value. */
 typedef struct rk_astar rk_astar_t;
 int rk_astar_create(rk_astar_t **out, size_t capacity, int max_expansions);
 int rk_astar_destroy(rk_astar_t *h);
@@ -1139,7 +1150,8 @@ int rk_beamb_export(rk_beamb_t *h, int slot, int depth, long long *h_sizes, long
  *   rk_astarb_step_commit : d_values (S * 12 N) from the net (float32, or bfloat16 after rk_astarb_set_values_dtype);
  *                           cost, push, relaxation, bookkeeping, next pop lists
  *   rk_astarb_status      : synchronises; h_status (S, 7) int64 = done, won (2 = start already solved), n_states,
- *                           iterations, open-queue length, index of the solved state, error
+ *                           iterations, open-queue length, index of the solved state, error (the codes of rk_astar_status;
+ *                           4 = a NaN value ended this search alone, see NON-FINITE VALUES at rk_astar_create)
  * h_max_states of rk_astarb_reset: per-search state budgets (null = the capacity). */
 typedef struct rk_astarb rk_astarb_t;
 int rk_astarb_create(rk_astarb_t **out, int n_searches, size_t capacity_per_search, int max_expansions);
@@ -1191,7 +1203,8 @@ int rk_astar_shard_reset(rk_astar_t *h, const int8_t *h_start_state, double lamb
 int rk_astar_shard_select(rk_astar_t *h, const void *d_gathered, double time_limit, double max_states, void *d_send, void *stream);
 /* h_out[8] = {stop reason (0 none, 1 won, 2 budget, 3 capacity, 4 time, 5 nothing open, 6 error), winner rank, winner
  * index, total states, this rank's pops, iterations, this rank's states, the largest error code any rank reported (1 pool
- * capacity, 2 look-back chain, 3 more new states than net rows: rk_astar_shard_push_rows)}. */
+ * capacity, 2 look-back chain, 3 more new states than net rows: rk_astar_shard_push_rows, 4 a NaN among the values a rank
+ * read: see NON-FINITE VALUES at rk_astar_create)}. */
 int rk_astar_shard_decision(rk_astar_t *h, long long *h_out, void *stream);
 int rk_astar_shard_insert(rk_astar_t *h, const void *d_recv, void *d_send, void *d_onehot, int out_dtype, void *stream);
 /* Between insert and push: asynchronous copy of this iteration's new-state count (<= 12 N: all ranks together pop at most N

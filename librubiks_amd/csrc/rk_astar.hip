@@ -70,7 +70,8 @@ enum {
 	C_NOFF, C_EPOCH, C_TICKET0 = 16, C_TICKET1, C_TICKET2, C_CLOCK0 = 20 /* and 21: the search's start on the device clock */,
 	C_DECIDE_ACC = 22, C_DECIDE_TICKET = 23 /* k_shard_decide: pops counted so far, workgroups done */, C_COUNT = 32
 };
-enum { ERR_NONE = 0, ERR_CAPACITY = 1, ERR_CHAIN = 2, ERR_NET_ROWS = 3 /* sharded: more new states than net rows were evaluated */ };
+enum { ERR_NONE = 0, ERR_CAPACITY = 1, ERR_CHAIN = 2, ERR_NET_ROWS = 3 /* sharded: more new states than net rows were evaluated */,
+       ERR_NONFINITE = 4 /* a NaN among the values of the new states that get a cost record (include/rubiks_hip.h) */ };
 
 constexpr int QL = 12;                          // maximal number of queue levels
 constexpr int SORT_CHUNK = 2048;                // records sorted per workgroup in LDS (32 KB) when K > 2048
@@ -618,11 +619,15 @@ __device__ __forceinline__ int new_covered(const AstarDev &d, int n_new_all)
 
 // cost record of new state j: cost = lambda * G + (-value), float64, no fused multiply-add (agents.py:380-383).
 // Padding records carry distinct maximal keys.
+// A NaN value (either sign, quiet or signalling; a bfloat16 NaN widens to a float32 one) has no place in any order: it ends the
+// search with ERR_NONFINITE, first error wins, and the end of this iteration reports the search as finished (end_body).  The
+// record it gets here is never popped.  +-inf are ordinary values.
 __device__ __forceinline__ Rec cost_record(const AstarDev &d, const float *values, int j, int n_new, uint32_t n_before)
 {
 	if (j >= n_new) return Rec{~0ull, 0xFFFFFFFF00000000ull + (uint64_t)j};
 	const uint32_t idx = n_before + 1u + (uint32_t)j;
 	const float val = d.values_bf16 ? __builtin_bit_cast(float, (uint32_t)reinterpret_cast<const uint16_t *>(values)[j] << 16) : values[j];
+	if (val != val) atomicCAS(&d.ctr[C_ERROR], (int32_t)ERR_NONE, (int32_t)ERR_NONFINITE);
 	const double hv = (double)(-val);
 	const double lg = d.lambda * (double)d.G[idx];
 	return Rec{sortable_key(lg + hv), (uint64_t)idx};
@@ -1016,7 +1021,7 @@ __device__ __forceinline__ void end_body(const AstarDev &d, int new_in_rec1, int
 		s_ctr[C_TICKET0] = 0; s_ctr[C_TICKET1] = 0; s_ctr[C_TICKET2] = 0;
 		const int n_exp = s_ctr[C_NEXP];
 		int done = s_ctr[C_DONE];
-		if (s_ctr[C_WON]) done = 1;
+		if (s_ctr[C_WON] || s_ctr[C_ERROR] == ERR_NONFINITE) done = 1;   // (a NaN value: nothing is popped again, here or on any rank)
 		if (!SHARDED && (n_states + 12 * n_exp > s_ctr[C_BUDGET] || open == 0)) done = 1;      // loop guard, agents.py:236
 		s_ctr[C_DONE] = done;
 		const int n_cand = open < n_exp ? open : n_exp;
@@ -1072,7 +1077,7 @@ void k_pop_select_only(AstarDev d, int n_exp)
 		const int n_cand = open < n_exp ? open : n_exp;
 		d.ctr[C_NEXP] = n_exp;
 		d.ctr[C_NCAND] = n_cand;
-		int done = d.ctr[C_WON] ? 1 : 0;
+		int done = d.ctr[C_WON] || d.ctr[C_ERROR] == ERR_NONFINITE ? 1 : 0;
 		if (d.ctr[C_NSTATES] + 12 * n_exp > d.ctr[C_BUDGET] || open == 0) done = 1;
 		d.ctr[C_DONE] = done;
 		d.ctr[C_NPOP] = done ? 0 : n_cand;
@@ -1115,7 +1120,7 @@ __global__ void k_set_budget(AstarDev d, int budget)
 {
 	if (threadIdx.x != 0) return;
 	d.ctr[C_BUDGET] = budget;
-	if (d.world == 1 && !d.ctr[C_WON]) {
+	if (d.world == 1 && !d.ctr[C_WON] && d.ctr[C_ERROR] != ERR_NONFINITE) {
 		const int done = (d.ctr[C_NSTATES] + 12 * d.ctr[C_NEXP] > budget || d.ctr[C_OPEN] == 0) ? 1 : 0;
 		d.ctr[C_DONE] = done;
 		d.ctr[C_NPOP] = done ? 0 : d.ctr[C_NCAND];

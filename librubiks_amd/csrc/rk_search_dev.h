@@ -21,7 +21,8 @@ __device__ __forceinline__ bool rec_less(const Rec &a, const Rec &b)
 	return a.key < b.key || (a.key == b.key && a.idx < b.idx);
 }
 
-// float64 -> uint64 whose unsigned order is the float order (no NaNs expected)
+// float64 -> uint64 whose unsigned order is the float order.  A NaN maps below -inf or above +inf by its sign bit, in bounds but in
+// no order a search could use: the A* engines end the search that meets one with ERR_NONFINITE (cost_record, rk_astar.hip).
 __device__ __forceinline__ uint64_t sortable_key(double c)
 {
 	c = c + 0.0;                                  // -0.0 -> +0.0: Python compares them equal

@@ -26,6 +26,16 @@ OH_CODES = {torch.float32: _ffi.OH_F32, torch.float16: _ffi.OH_F16, torch.bfloat
 OH_DTYPES = {_ffi.OH_F32: torch.float32, _ffi.OH_F16: torch.float16, _ffi.OH_BF16: torch.bfloat16, _ffi.OH_STATES: torch.int8}
 
 
+# -- the A* engines' error codes (rk_astar_status slot 6, rk_astarb_status column 6, slot 7 of a sharded decision) ----------
+ASTAR_ERRORS = {1: "pool capacity exceeded", 2: "look-back chain broken", 3: "more new states than net rows were evaluated",
+                4: "NaN among the net's values of the new states"}
+
+
+def astar_errors(codes) -> str:
+	"""The texts of the non-zero A* error codes in `codes` (ints), for the message of a RubiksHipError."""
+	return "; ".join(f"{k}: {ASTAR_ERRORS.get(k, '?')}" for k in sorted({int(c) for c in codes if int(c)}))
+
+
 def param_dtype(net):
 	"""The dtype of the net's first floating-point parameter; None for anything that is not a torch module with one."""
 	params = getattr(net, "parameters", None)

@@ -3026,6 +3026,8 @@ class AStar(DeepAgent, _ffi.Owner):
 				n_pop, n_new, won, solved_idx, self._n = (int(x) for x in info)
 				if n_pop == 0:
 					done = 1
+					_ffi.check(lib.rk_astar_status(h, status, _ffi.stream_ptr()))      # why nothing was popped: the guard, or an error
+					err = int(status[6])
 					break
 				self.iterations += 1
 				if won:
@@ -3052,11 +3054,11 @@ class AStar(DeepAgent, _ffi.Owner):
 						self._iteration(h, oh, code)
 				_ffi.check(lib.rk_astar_status(h, status, _ffi.stream_ptr()))
 				done, won, self._n, self.iterations, solved_idx, err = (int(status[i]) for i in (0, 1, 2, 3, 5, 6))
-				if err:
-					raise _ffi.RubiksHipError(f"A* engine error code {err}")
-				if won or done or time.perf_counter() - t0 >= time_limit:
+				if won or done or err or time.perf_counter() - t0 >= time_limit:
 					break
 			self._cache = None
+			if err:
+				raise _ffi.RubiksHipError(f"A* engine error {eng.astar_errors([err])}")
 			if won:
 				self.action_queue = eng.read_path(lib.rk_astar_path, h, solved_idx)
 				return True
@@ -3631,7 +3633,9 @@ class AStarBatch(DeepAgent, _ffi.Owner):
 		st = np.zeros((self.n_searches, 7), np.int64)
 		_ffi.check(_ffi.lib().rk_astarb_status(self._h, st.ctypes.data, _ffi.stream_ptr()))
 		if st[:, 6].any():
-			raise _ffi.RubiksHipError(f"batched A* engine error codes {st[:, 6].tolist()}")
+			bad = {int(s): int(st[s, 6]) for s in np.flatnonzero(st[:, 6])}
+			raise _ffi.RubiksHipError(f"batched A* engine error codes {st[:, 6].tolist()}: searches {sorted(bad)} ended with "
+			                          + eng.astar_errors(bad.values()))
 		self.status = st
 		if self.on_poll is not None:
 			self.on_poll(st)

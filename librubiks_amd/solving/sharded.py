@@ -342,7 +342,7 @@ class ShardedAStar(DeepAgent, _ffi.Owner):
 			self.repeated += 1
 			return self.search(state, *limits)
 		if stop == 6:
-			raise _ffi.RubiksHipError(f"rank {tp.rank}: a rank reported engine error {int(decision[7])}; every rank stops together")
+			raise _ffi.RubiksHipError(f"rank {tp.rank}: a rank reported engine error {eng.astar_errors([decision[7]])}; every rank stops together")
 		if stop == 1:
 			self._walk(int(decision[1]), int(decision[2]), root_owner)
 			return True

@@ -371,6 +371,8 @@ class AStarOracle:
 		# cost and push (:315-317, :369-383): float64 lambda*G plus float32 heuristic
 		if len(new_idx):
 			H = -_values(self.net, new_states)
+			if np.isnan(H).any():                                              # heapq has no order for it; the engines end the search (error 4)
+				raise ValueError(f"A* oracle: the net returned NaN for {int(np.isnan(H).sum())} of {len(H)} new states")
 			cost = self.lambda_ * np.array([self.G[i] for i in new_idx], dtype=np.float64) + H
 			for c, i in zip(cost, new_idx):
 				heapq.heappush(self.open, (c, i))

@@ -212,6 +212,8 @@ class ShardedAStarOracle:
 		# cost and push (agents.py:315-317, :369-383): float64 lambda * G plus the float32 heuristic
 		if new_idx:
 			H = -_values(self.net, np.array([rk.states[i] for i in new_idx]))
+			if np.isnan(H).any():                                           # heapq has no order for it; the engines stop every rank (error 4)
+				raise ValueError(f"sharded A* oracle: the net returned NaN for {int(np.isnan(H).sum())} of {len(H)} new states of rank {rk.rank}")
 			for i, h in zip(new_idx, H):
 				heapq.heappush(rk.open, (self.lambda_ * float(rk.G[i]) + float(h) + 0.0, i))
 		# relaxation case 2 as offers to the parents' owners (k_shard_offers), G as it stands after case 1

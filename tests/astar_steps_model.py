@@ -129,6 +129,8 @@ class StepModel(AStarOracle):
 		return cum, np.array(G, np.float64)
 
 	def step(self, n_expand: int, values) -> Step:
+		if np.isnan(np.asarray(values, np.float32)).any():                    # before anything changes: heapq has no order for a NaN cost,
+			raise ValueError("a NaN among the scripted values: the engine ends the search with error 4, the model has no answer")
 		if not self.runs(n_expand):
 			return Step(n_expand, [], 0, int(self.won), self.solved, len(self), -1)
 		popped = [heapq.heappop(self.open)[1] for _ in range(min(len(self.open), n_expand))]
@@ -248,6 +250,14 @@ FILLERS = (1, 2, 3, 4, 5, 7)    # pop counts between targets
 # the one run that ends on the loop guard on purpose (budget GUARD_BUDGET), and goes on after rk_astar_set_budget
 GUARD_CASE = Geometry(5, 9000, 0.5, 12, 21, 1, 80, 3, "ends on the loop guard")
 GUARD_BUDGET = 700
+# tests/test_astar_nonfinite_gpu.py: the smallest engines in which every form of the kernel that READS the values runs -- one
+# k_records_sort<256> workgroup; several of them (a value at j >= 256 is read by a later workgroup); k_records_sort<2048> with
+# k_merge_pass behind it (a value at j >= 2048).  The schedule is `run`'s; the test stops it at the iteration it poisons.
+NAN_GEOMETRIES = [
+	Geometry(4, 9000, 0.5, 14, 31, 1, 40, 3, "K = 48: one run of 256"),
+	Geometry(30, 60_000, 0.3, 12, 32, 1, 40, 3, "K = 360: two runs of 256, the second workgroup reads j >= 256"),
+	Geometry(1366, 400_000, 0.3, 12, 18, 1, 40, 8, "Kpad = 18 432: nine 2048-record chunks and k_merge_pass (GEOMETRIES[7])"),
+]
 
 
 def start_state(g: Geometry) -> np.ndarray:

@@ -86,6 +86,12 @@ class Engine:
 		_ffi.check(self.lib.rk_astar_new_states_oh(self.h, out.data_ptr(), _ffi.OH_STATES, None))
 		assert (out[:n].cpu().numpy() == states).all() and (out[n] == -1).all(), (at, "raw states")
 
+	def upload(self, values):
+		"""the values as the engine takes them: float32, or the upper halves as bfloat16"""
+		if self.bf16:
+			return torch.from_numpy((values.view(np.uint32) >> 16).astype(np.uint16).view(np.int16)).cuda()
+		return torch.from_numpy(values).cuda()
+
 	def iteration(self, m, n_expand, values, pattern, target):
 		lib, h, g = self.lib, self.h, self.g
 		at = self.where(n_expand, len(values), pattern)
@@ -102,10 +108,7 @@ class Engine:
 		special = target is not None or self.it == 0
 		if special and step.n_new:
 			self.check_new_states(m, step, at)
-		if self.bf16:
-			dev = torch.from_numpy((values.view(np.uint32) >> 16).astype(np.uint16).view(np.int16)).cuda()
-		else:
-			dev = torch.from_numpy(values).cuda()
+		dev = self.upload(values)
 		_ffi.check(lib.rk_astar_commit(h, dev.data_ptr() if len(values) else None, None))
 		assert self.next_pops() == m.next_pops(n_expand), (at, "pop list after the commit")
 		st = self.status()

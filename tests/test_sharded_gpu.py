@@ -53,7 +53,8 @@ def test_world1_equals_oracle(seed, depth, lam, n, budget):
 	assert list(agent.action_queue) == list(ref.action_queue)
 
 
-def _simulate_ranks(world, start, lam, N, budget, capacity, oracle=None, net=None, values_bf16=False, short_rows=None, inspect=None):
+def _simulate_ranks(world, start, lam, N, budget, capacity, oracle=None, net=None, values_bf16=False, short_rows=None, inspect=None,
+                    short_tail=float("-inf")):
 	"""
 	All `world` ranks of a sharded search in ONE process on one GPU: one engine per rank, the two collectives done by hand
 	(all-gather = stack the contributions, all-to-all = transpose the send blocks).  Checks on the way that every rank takes
@@ -64,8 +65,8 @@ def _simulate_ranks(world, start, lam, N, budget, capacity, oracle=None, net=Non
 	oracle's float64 costs bit for bit, +inf behind them.
 	`values_bf16`: the net returns bfloat16 values; the engines are told so (rk_astar_set_values_dtype) and read the tensor as it is.
 	`short_rows`: every push promises values for this many rows only and hands over a view of that length at the front of a larger
-	tensor whose tail is -inf (a value no net row holds); `inspect(rank, handle, new states of the last iteration)` runs before
-	the engines go away.
+	tensor whose tail is `short_tail`: -inf (a value no net row holds) or a NaN (which would end the search with error 4 if it were
+	read); `inspect(rank, handle, new states of the last iteration)` runs before the engines go away.
 	"""
 	import ctypes as C
 	from librubiks_amd.solving.sharded import net_rows, select_pops
@@ -127,7 +128,7 @@ def _simulate_ranks(world, start, lam, N, budget, capacity, oracle=None, net=Non
 			# sizes this iteration's sort / insert launches (shard_push_impl); the whole-batch entry on every third iteration
 			if short_rows is not None:
 				# (the tail covers the sort's whole rounded-up geometry: whatever the engine reads stays inside this allocation)
-				padded = torch.full((short_rows + 4096,), float("-inf"), dtype=values.dtype, device="cuda")
+				padded = torch.full((short_rows + 4096,), short_tail, dtype=values.dtype, device="cuda")
 				padded[:short_rows] = values[:short_rows]
 				_ffi.check(lib.rk_astar_shard_push_rows(hs[r], padded[:short_rows].data_ptr(), short_rows, recvs[r].data_ptr(), sends[r].data_ptr(), st()))
 			elif iters % 3 == 2:
