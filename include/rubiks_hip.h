@@ -692,10 +692,14 @@ int rk_chain_solve(rk_chain_t *h, const int8_t *d_states, size_t n, int32_t *d_l
  * phase-1 solution p1 = D: for D2 = the phase-2 entry of the state behind it (the greater of tables 3 and 4) .. best - p1 - 1,
  * depth-first over phase-2 words (a child is kept if cost + entry <= D2) up to the first child whose entry is 0: best = p1 + cost,
  * the row is rewritten.  After the phase 2 of the `tries`-th phase-1 solution, or once D >= best, the search is over.
+ * WITH A CAP C on the phase-2 bound (rk_twophase_solve_capped) two conditions change and nothing else does: a phase-1 solution
+ * whose phase-2 entry h2 is not 0 is left behind, and phase 1 goes on, if p1 + h2 >= best OR h2 > C (without a cap: the first
+ * alone); and when a phase-2 bound is exhausted, D2 += 1, phase 1 goes on if p1 + D2 >= best OR D2 > C.  Every phase-1 solution
+ * still counts towards `tries`, and one whose h2 is 0 still ends the search.
  * THE BUDGET: a node is one child evaluation (a generator the move pruning lets through, its coordinates stepped, its two entries
  * read) in either phase.  Immediately before each evaluation the state's counter is compared with max_nodes: if equal the search
  * of that state ends, otherwise the counter goes up by one.  Nothing else counts.  The answer is a function of (state, tries,
- * max_nodes) alone. */
+ * max_nodes) alone; with a cap, of (state, tries, max_nodes, C). */
 #define RK_TWOPHASE_GRID 1024   /* workgroups of 256 lanes the search has at most; a lane that ends a state takes the next row */
 typedef struct rk_twophase rk_twophase_t;
 /* Builds six u16 move tables (a coordinate under every generator) and the four pruning tables on the HOST -- level d + 1 takes the
@@ -719,6 +723,14 @@ int rk_twophase_export(rk_twophase_t *h, int table, size_t first, size_t count, 
  * serves one solve at a time (it owns the row counter).  RK_ESTATE if the chain's rows are wider than [14] of the status. */
 int rk_twophase_solve(rk_twophase_t *h, rk_chain_t *chain, const int8_t *d_states, size_t n, int tries, long long max_nodes, int32_t *d_lengths,
                       int8_t *d_actions, int32_t *d_phase_lengths, int32_t *d_reason, long long *d_nodes, int32_t *d_error, void *stream);
+/* rk_twophase_solve with a cap on the phase-2 bound (the two changed conditions above) and two counts per row.  phase2_cap <= 0:
+ * no cap, every output as rk_twophase_solve's; a cap above [14] of the status is RK_EINVAL.  With a cap `tries` is no longer what
+ * ends a search, so callers pass a large value.  d_counts int32 (n, 2), 4-byte aligned, or NULL: the phase-1 solutions the search
+ * found and the phase-2 searches it entered (entered <= found <= tries), written once when the row's search ends; 0 0 for a row
+ * that is no legal state.  Everything else is rk_twophase_solve's, which is this entry with phase2_cap 0 and d_counts NULL. */
+int rk_twophase_solve_capped(rk_twophase_t *h, rk_chain_t *chain, const int8_t *d_states, size_t n, int tries, long long max_nodes, int phase2_cap,
+                             int32_t *d_lengths, int8_t *d_actions, int32_t *d_phase_lengths, int32_t *d_reason, long long *d_nodes,
+                             int32_t *d_counts, int32_t *d_error, void *stream);
 
 /* ---- the symmetry-reduced goal ball: one representative per orbit (rk_symball_*) -------------------------------------------
  * The canonical representatives of the states within `radius` quarter turns of solved, built once and kept in HBM; the depth of

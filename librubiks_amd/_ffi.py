@@ -157,6 +157,7 @@ SIGNATURES = {
 	"rk_twophase_status": (_i, [_vp, _vp]),
 	"rk_twophase_export": (_i, [_vp, _i, _sz, _sz, _vp, _vp]),
 	"rk_twophase_solve": (_i, [_vp, _vp, _vp, _sz, _i, C.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+	"rk_twophase_solve_capped": (_i, [_vp, _vp, _vp, _sz, _i, C.c_longlong, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 	"rk_symball_create": (_i, [C.POINTER(_vp), _i, _i, _sz]),
 	"rk_symball_destroy": (_i, [_vp]),
 	"rk_symball_build": (_i, [_vp, _i, _vp]),

@@ -30,18 +30,23 @@
 //         if cost + its entry <= D2); the first child whose entry is 0 is solved: best = p1 + cost, the row is rewritten, phase 2 ends.
 //         After phase 2 (solved or exhausted): stop if found == tries or D >= best, else phase 1 goes on behind that word.
 //         D += 1 when the depth-first pass is exhausted.
+//     WITH A CAP C ON THE PHASE-2 BOUND (rk_twophase_solve_capped, tests/twophase_cap_model.py) two conditions change and nothing
+//     else: a phase-1 solution with h2 != 0 is left behind -- phase 1 goes on -- if p1 + h2 >= best OR h2 > C; and after D2 += 1
+//     phase 1 goes on if p1 + D2 >= best OR D2 > C.  found still counts every phase-1 solution, h2 == 0 still ends the search.
 // THE BUDGET RULE.  A node is one child evaluation: a generator that the move-pruning rule lets through at the current node, its
 // three coordinates stepped and its two entries read, in either phase.  Immediately BEFORE each evaluation the state's counter is
 // compared with max_nodes: if equal, the state's search ends there (reason 1 or 2); otherwise the counter goes up by one and the
 // child is evaluated.  Root entries, pops, restarts and the replay of the chain's row count nothing.  So the answer is a function
-// of (state, tries, max_nodes) alone.
+// of (state, tries, max_nodes) alone -- with a cap, of (state, tries, max_nodes, C).
 //
 // THE KERNEL is one persistent grid of at most RK_TWOPHASE_GRID workgroups of 256.  A lane owns one state and runs the explicit-
 // stack depth-first search as a UNIFORM loop: per trip one child (or one pop, or one move of the chain's row) per lane, by
 // predication -- divergence costs branches, not serialised subtrees.  A lane that finishes takes the next row from a device
 // counter (one atomic per wave and refill); which lane gets which row influences no output.  The stack holds generators only, a
 // byte per entry in LDS (72 x 256 B per workgroup); coordinates are not stacked: a pop steps them through the inverse generator's
-// column.  Vector stores only; the one atomic is the row counter.
+// column.  Vector stores only; the one atomic is the row counter.  The kernel is a template: k_twophase_search<false> is the search
+// without a cap and without counts, the code rk_twophase_solve has always run; <true> compares with the cap (0xFFFFFFFF: none),
+// counts the phase-2 searches it enters and writes the two counts of a row at its end.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstring>
@@ -115,9 +120,11 @@ constexpr uint32_t TP_IMPROVED = 1u, TP_BUDGET = 2u;
 
 __device__ __forceinline__ uint32_t tp_max(uint32_t a, uint32_t b) { return a > b ? a : b; }
 
+template <bool EXT>                                                 // EXT: the cap on the phase-2 bound and the two counts per row
 __global__ __launch_bounds__(TP_THREADS)
 void k_twophase_search(TpDev dv, const uint32_t *states, uint32_t n, uint32_t stride, uint32_t tries, unsigned long long max_nodes,
-                       int32_t *lengths, int8_t *actions, int32_t *phase_lengths, int32_t *reason, long long *nodes_out, uint32_t *counter)
+                       int32_t *lengths, int8_t *actions, int32_t *phase_lengths, int32_t *reason, long long *nodes_out, uint32_t *counter,
+                       uint32_t cap, int32_t *counts)
 {
 	__shared__ u32x4 s_tab[36];
 	__shared__ uint8_t s_stack[TP_STACK * TP_THREADS];              // entry e of this lane: s_stack[e * 256 + tid]
@@ -130,6 +137,7 @@ void k_twophase_search(TpDev dv, const uint32_t *states, uint32_t n, uint32_t st
 	uint32_t phase = 1, depth = 0, cost = 0, g = 0;                 // generators and cost behind the current node; the next action to try
 	uint32_t D = 0, D2 = 0, best = 0, p1 = 0, bp1 = 0, found = 0, flags = 0, t = 0;
 	unsigned long long nodes = 0;
+	uint32_t entered = 0;                                           // EXT: the phase-2 searches of this row
 
 	// the end of a state's search
 	const auto finish = [&]() {
@@ -138,6 +146,12 @@ void k_twophase_search(TpDev dv, const uint32_t *states, uint32_t n, uint32_t st
 		phase_lengths[2 * (size_t)q + 1] = (int32_t)(best - bp1);
 		reason[q] = (flags & TP_IMPROVED) == 0u ? 2 : (flags & TP_BUDGET) != 0u ? 1 : 0;
 		nodes_out[q] = (long long)nodes;
+		if constexpr (EXT) {
+			if (counts) {
+				counts[2 * (size_t)q] = (int32_t)found;
+				counts[2 * (size_t)q + 1] = (int32_t)entered;
+			}
+		}
 		mode = TP_IDLE;
 	};
 	// after phase 2: phase 1 goes on behind the word that ended at `leaf` (its next trip pops), unless the search is over
@@ -181,6 +195,12 @@ void k_twophase_search(TpDev dv, const uint32_t *states, uint32_t n, uint32_t st
 					phase_lengths[2 * (size_t)q + 1] = -1;
 					reason[q] = 2;
 					nodes_out[q] = 0;
+					if constexpr (EXT) {
+						if (counts) {
+							counts[2 * (size_t)q] = 0;
+							counts[2 * (size_t)q + 1] = 0;
+						}
+					}
 				} else {
 					uint32_t x[5];
 					load5(states + (size_t)q * 5, x);
@@ -192,6 +212,7 @@ void k_twophase_search(TpDev dv, const uint32_t *states, uint32_t n, uint32_t st
 					D = tp_max(dv.prune[0][i1], dv.prune[1][c1 * TP_SLICE + c2]);
 					best = (uint32_t)L;
 					nodes = 0; found = 0; flags = 0; t = 0; phase = 1;
+					if constexpr (EXT) entered = 0;
 					mode = TP_REPLAY;
 				}
 			}
@@ -214,9 +235,10 @@ void k_twophase_search(TpDev dv, const uint32_t *states, uint32_t n, uint32_t st
 				best = p1; bp1 = p1; flags |= TP_IMPROVED;
 				write_row(p1, old);
 				finish();
-			} else if (p1 + h2 >= best) {                                   // nothing below best behind this word
+			} else if (p1 + h2 >= best || (EXT && h2 > cap)) {              // nothing below best behind this word, or only past the cap
 				resume1();
 			} else {
+				if constexpr (EXT) entered++;
 				phase = 2;
 				root2 = cp | ep << 16;
 				c0 = cp; c1 = ep; c2 = sp;
@@ -275,7 +297,7 @@ void k_twophase_search(TpDev dv, const uint32_t *states, uint32_t n, uint32_t st
 				step = true;
 			} else if (phase == 2u) {                                       // this bound is exhausted
 				D2++;
-				if (p1 + D2 >= best) {
+				if (p1 + D2 >= best || (EXT && D2 > cap)) {
 					resume1();
 				} else {
 					c0 = root2 & 0xFFFFu; c1 = root2 >> 16; c2 = root2p;
@@ -436,6 +458,39 @@ int tp_build(int table, const std::vector<uint16_t> &mta, const std::vector<uint
 		[](uint32_t index) { return index; }, count);
 }
 
+// Both solve entries: phase2_cap <= 0 is no cap, d_counts may be null; without either the launch is k_twophase_search<false>.
+int tp_solve(const char *who, rk_twophase_t *h, rk_chain_t *chain, const int8_t *d_states, size_t n, int tries, long long max_nodes, int phase2_cap,
+             int32_t *d_lengths, int8_t *d_actions, int32_t *d_phase_lengths, int32_t *d_reason, long long *d_nodes, int32_t *d_counts,
+             int32_t *d_error, void *stream)
+{
+	if (!h || !chain) return fail(RK_EINVAL, "%s: null handle", who);
+	if (tries < 1 || max_nodes < 1) return fail(RK_EINVAL, "%s: tries %d and max_nodes %lld must be at least 1", who, tries, max_nodes);
+	if (phase2_cap > (int)TP_STACK - 2) return fail(RK_EINVAL, "%s: phase2_cap %d is above the longest row, %u", who, phase2_cap, TP_STACK - 2);
+	if (int e = check_state_rows(who, d_states, n)) return e;
+	if (n != 0 && (!d_lengths || !d_actions || !d_phase_lengths || !d_reason || !d_nodes)) return fail(RK_EINVAL, "%s: null pointer", who);
+	if (((uintptr_t)d_lengths | (uintptr_t)d_phase_lengths | (uintptr_t)d_reason | (uintptr_t)d_counts | (uintptr_t)d_error) & 3u)
+		return fail(RK_EINVAL, "%s: device pointers must be 4-byte aligned", who);
+	if ((uintptr_t)d_nodes & 7u) return fail(RK_EINVAL, "%s: d_nodes must be 8-byte aligned", who);
+	long long chain_status[16];
+	if (int e = rk_chain_status(chain, chain_status)) return e;
+	const long long stride = chain_status[8];
+	if (stride < 1 || stride > (long long)TP_STACK - 2)
+		return fail(RK_ESTATE, "%s: the chain's rows are %lld wide, the search's stack holds %u", who, stride, TP_STACK - 2);
+	if (n == 0) return RK_OK;
+	hipStream_t st = (hipStream_t)stream;
+	// launch 1: the chain's answer into the output rows
+	if (int e = rk_chain_solve(chain, d_states, n, d_lengths, d_actions, nullptr, d_error, stream)) return e;
+	// launch 2: the search
+	RK_HIP(hipMemsetAsync(h->d_counter, 0, sizeof(uint32_t), st));
+	const bool ext = phase2_cap > 0 || d_counts != nullptr;
+	hipLaunchKernelGGL(ext ? k_twophase_search<true> : k_twophase_search<false>, dim3(tp_grid(n)), dim3(TP_THREADS), 0, st, h->d,
+	                   reinterpret_cast<const uint32_t *>(d_states), (uint32_t)n, (uint32_t)stride, (uint32_t)tries, (unsigned long long)max_nodes,
+	                   d_lengths, d_actions, d_phase_lengths, d_reason, d_nodes, h->d_counter, phase2_cap > 0 ? (uint32_t)phase2_cap : 0xFFFFFFFFu,
+	                   d_counts);
+	RK_HIP(hipGetLastError());
+	return RK_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -510,29 +565,16 @@ int rk_twophase_export(rk_twophase_t *h, int table, size_t first, size_t count, 
 int rk_twophase_solve(rk_twophase_t *h, rk_chain_t *chain, const int8_t *d_states, size_t n, int tries, long long max_nodes, int32_t *d_lengths,
                       int8_t *d_actions, int32_t *d_phase_lengths, int32_t *d_reason, long long *d_nodes, int32_t *d_error, void *stream)
 {
-	if (!h || !chain) return fail(RK_EINVAL, "rk_twophase_solve: null handle");
-	if (tries < 1 || max_nodes < 1) return fail(RK_EINVAL, "rk_twophase_solve: tries %d and max_nodes %lld must be at least 1", tries, max_nodes);
-	if (int e = check_state_rows("rk_twophase_solve", d_states, n)) return e;
-	if (n != 0 && (!d_lengths || !d_actions || !d_phase_lengths || !d_reason || !d_nodes)) return fail(RK_EINVAL, "rk_twophase_solve: null pointer");
-	if (((uintptr_t)d_lengths | (uintptr_t)d_phase_lengths | (uintptr_t)d_reason | (uintptr_t)d_error) & 3u)
-		return fail(RK_EINVAL, "rk_twophase_solve: device pointers must be 4-byte aligned");
-	if ((uintptr_t)d_nodes & 7u) return fail(RK_EINVAL, "rk_twophase_solve: d_nodes must be 8-byte aligned");
-	long long chain_status[16];
-	if (int e = rk_chain_status(chain, chain_status)) return e;
-	const long long stride = chain_status[8];
-	if (stride < 1 || stride > (long long)TP_STACK - 2)
-		return fail(RK_ESTATE, "rk_twophase_solve: the chain's rows are %lld wide, the search's stack holds %u", stride, TP_STACK - 2);
-	if (n == 0) return RK_OK;
-	hipStream_t st = (hipStream_t)stream;
-	// launch 1: the chain's answer into the output rows
-	if (int e = rk_chain_solve(chain, d_states, n, d_lengths, d_actions, nullptr, d_error, stream)) return e;
-	// launch 2: the search
-	RK_HIP(hipMemsetAsync(h->d_counter, 0, sizeof(uint32_t), st));
-	hipLaunchKernelGGL(k_twophase_search, dim3(tp_grid(n)), dim3(TP_THREADS), 0, st, h->d, reinterpret_cast<const uint32_t *>(d_states), (uint32_t)n,
-	                   (uint32_t)stride, (uint32_t)tries, (unsigned long long)max_nodes, d_lengths, d_actions, d_phase_lengths, d_reason, d_nodes,
-	                   h->d_counter);
-	RK_HIP(hipGetLastError());
-	return RK_OK;
+	return tp_solve("rk_twophase_solve", h, chain, d_states, n, tries, max_nodes, 0, d_lengths, d_actions, d_phase_lengths, d_reason, d_nodes, nullptr,
+	                d_error, stream);
+}
+
+int rk_twophase_solve_capped(rk_twophase_t *h, rk_chain_t *chain, const int8_t *d_states, size_t n, int tries, long long max_nodes, int phase2_cap,
+                             int32_t *d_lengths, int8_t *d_actions, int32_t *d_phase_lengths, int32_t *d_reason, long long *d_nodes,
+                             int32_t *d_counts, int32_t *d_error, void *stream)
+{
+	return tp_solve("rk_twophase_solve_capped", h, chain, d_states, n, tries, max_nodes, phase2_cap, d_lengths, d_actions, d_phase_lengths, d_reason,
+	                d_nodes, d_counts, d_error, stream);
 }
 
 }  // extern "C"

@@ -1437,6 +1437,14 @@ class DeviceTwoPhaseSolver(_TableSolver):
 	(profiles/r29_two_phase.json): on 40-move scrambles 35.8 moves on average against the chain's 48.4 at 85 000
 	states/s, where max_nodes = 2^16 leaves 84 % of the rows with the chain's answer.
 
+	`phase2_cap=C` (1..the chain's `max_length`; None: no cap, the search above answer for answer) cuts every phase 2 short: a
+	phase-1 solution whose phase-2 entry is above C is left behind, and a phase 2 whose bound passes C is given up, so the budget
+	goes to many phase-1 solutions instead of one deep phase 2 and an improved row has at most C moves inside the subgroup.  With a
+	cap `tries` is no longer what ends a search: pass `tries=None`, 2^31 - 1.  The answer is then a function of (state, tries,
+	max_nodes, C) alone.  Measured (profiles/r32_two_phase_cap.json): on 40-move scrambles `tries=None, max_nodes=1 << 20,
+	phase2_cap=18` gives 30.1 moves where the defaults give 35.8, with 8 % of the rows still the chain's instead of 26 %, at 1.8x the
+	defaults' time; at max_nodes = 2^16 no cap beats the search without one.
+
 	`solve(states)` has `DeviceChainSolver.solve`'s rules: numpy in -> numpy out, device tensor in -> device tensor out, states in the
 	representation cube.get_is2024() names, a row that is no legal state a ValueError naming the lowest such row or, with
 	`allow_illegal`, length -1 (phase lengths -1, actions all -1, reason 2, no node).  As an agent it plays in `Evaluator` and under
@@ -1444,11 +1452,11 @@ class DeviceTwoPhaseSolver(_TableSolver):
 	"""
 	GRID_ROWS = 1024 * 256                  # RK_TWOPHASE_GRID workgroups of 256 lanes: beyond this many rows a lane takes several
 
-	def __init__(self, chain=None, tries: int = 8, max_nodes: int = 1 << 20, shorten=None, allow_illegal: bool = False):
+	def __init__(self, chain=None, tries: int = 8, max_nodes: int = 1 << 20, phase2_cap: int = None, shorten=None, allow_illegal: bool = False):
 		if chain is not None and not isinstance(chain, DeviceChainSolver):
 			raise ValueError("chain must be a DeviceChainSolver or None")
 		super().__init__(shorten, allow_illegal)
-		self.tries = eng.int_in("tries", tries, 1, (1 << 31) - 1)
+		self.tries = (1 << 31) - 1 if tries is None else eng.int_in("tries", tries, 1, (1 << 31) - 1)
 		self.max_nodes = eng.int_in("max_nodes", max_nodes, 1, _ffi.INT64_MAX)
 		_ffi.require_gpu()
 		self.chain = chain if chain is not None else DeviceChainSolver()
@@ -1460,13 +1468,15 @@ class DeviceTwoPhaseSolver(_TableSolver):
 		self.table_sizes = tuple(int(v) for v in status[8:12])
 		self.grid_rows = int(status[12]) * int(status[13])
 		self.max_length = self.chain.max_length                          # the row length of `solve`'s actions
+		self.phase2_cap = eng.int_in("phase2_cap", phase2_cap, 1, self.max_length, none_ok=True)
 
-	def solve(self, states, phase_lengths: bool = False, details: bool = False):
+	def solve(self, states, phase_lengths: bool = False, details: bool = False, counts: bool = False):
 		"""(lengths int32 (n,), actions int8 (n, max_length) padded with -1[, phase lengths int32 (n, 2)][, reason int32 (n,), nodes
-		int64 (n,)]): reason 0 = the search ended by itself and improved the chain's answer, 1 = the budget ended it and the answer is
-		from the search, 2 = the row holds the chain's answer.  Two launches; reading the error word (not with `allow_illegal`) is the
+		int64 (n,)][, counts int32 (n, 2)]): reason 0 = the search ended by itself and improved the chain's answer, 1 = the budget ended it and the answer is
+		from the search, 2 = the row holds the chain's answer; counts = the phase-1 solutions the search found and the phase-2 searches
+		it entered (0 0 for a row that is no legal state).  Two launches; reading the error word (not with `allow_illegal`) is the
 		call's one host read.  With `shorten` the queues come back through `ball.shorten` (lengths and actions then describe the
-		shortened queues; phase lengths, reason and nodes stay the search's own)."""
+		shortened queues; phase lengths, reason, nodes and counts stay the search's own)."""
 		if self.chain._h is None:
 			raise ValueError("the chain solver was freed")
 		q, dev = _device_rows20(states)
@@ -1476,21 +1486,25 @@ class DeviceTwoPhaseSolver(_TableSolver):
 		phases = torch.empty((n, 2), dtype=torch.int32, device=gpu)
 		reason = torch.empty(n, dtype=torch.int32, device=gpu)
 		nodes = torch.empty(n, dtype=torch.int64, device=gpu)
+		both = torch.empty((n, 2), dtype=torch.int32, device=gpu) if counts else None
 		err = self._error_word()
-		_ffi.check(_ffi.lib().rk_twophase_solve(self._h, self.chain._h, q.data_ptr(), n, self.tries, self.max_nodes, lengths.data_ptr(),
-		                                        actions.data_ptr(), phases.data_ptr(), reason.data_ptr(), nodes.data_ptr(),
-		                                        None if err is None else err.data_ptr(), _ffi.stream_ptr()))
+		_ffi.check(_ffi.lib().rk_twophase_solve_capped(self._h, self.chain._h, q.data_ptr(), n, self.tries, self.max_nodes, self.phase2_cap or 0,
+		                                               lengths.data_ptr(), actions.data_ptr(), phases.data_ptr(), reason.data_ptr(), nodes.data_ptr(),
+		                                               both.data_ptr() if counts else None, None if err is None else err.data_ptr(),
+		                                               _ffi.stream_ptr()))
 		self._raise_illegal(err)
 		if self.shorten is not None and n:
 			lengths, actions = self._shortened(lengths, actions)
-		return _batch_out(dev, lengths, actions, *((phases,) if phase_lengths else ()), *((reason, nodes) if details else ()))
+		return _batch_out(dev, lengths, actions, *((phases,) if phase_lengths else ()), *((reason, nodes) if details else ()),
+		                  *((both,) if counts else ()))
 
 	def export(self, table: int) -> np.ndarray:
 		"""uint8 (table_sizes[table - 1],): pruning table 1..4, entry by index (every entry is reached)."""
 		return self._export("rk_twophase_export", table, "table")
 
 	def __str__(self):
-		return f"Two-phase solver (device, tries={self.tries}, max_nodes={self.max_nodes})" + \
+		return f"Two-phase solver (device, tries={self.tries}, max_nodes={self.max_nodes}" + \
+			(f", phase2_cap={self.phase2_cap})" if self.phase2_cap is not None else ")") + \
 			(f", shortened by {self.shorten}" if self.shorten is not None else "")
 
 
